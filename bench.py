@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Benchmark of the OF_DIS hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--tv on|off] [--total-frames T]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--tv on|off] [--total-frames T] [--full]
+                    [--dump-outputs DIR]
 
 A "step" is one pass of the whole hot path (OFC::OFClass scope: per-level DIS search + densification
 + TV-L1 refinement, pyramids already resident in HBM) over one batch of synthetic 1024x436 frame pairs at
@@ -17,7 +18,13 @@ configs[4]: a fixed batch of T pairs cut into contiguous per-rank shares, of_dis
 modes a frame's content depends on its GLOBAL index only, and rank 0 re-computes frames of the other ranks on its
 own GPU and compares checksums: results must be bit-identical to the one-GPU run.
 
-The JSON carries, besides the contract fields:
+A plain run sets up, decides the arithmetic contract (--contract auto: the gate below), warms up, times the K steps and
+prints the headline: metric, value, unit, higher_is_better, dtype, ms_per_step (one timed step) and the run's configuration.
+--dump-outputs DIR then also writes what the timed path computed in its last step (a fixed, seeded sample of its frames'
+flows, float32, with their frame indices) as DIR/<name>.npy, so that two builds can be compared output for output.
+
+Everything else -- per-kernel and roofline figures, the secondary blocks, the checks against the oracle and across ranks,
+the CPU baseline -- runs only with --full.  With --full the JSON also carries:
   roofline, roofline_valu   the kernel class that takes the most time: algorithmic bytes / measured time against the HBM
                     peak, and its VALU instruction count (PMC, profiles/) against the issue peak
   kernels           the same HBM figures for every kernel class (incl. the in-pipeline warp kernel)
@@ -313,6 +320,29 @@ def flows_tensor(capi, torch, batch, p, n, dev):
     capi.check(capi.lib().ofdis_memcpy_d2d(out.data_ptr(), batch.flow_ptr(), out.numel() * 4, None))
     capi.check(capi.lib().ofdis_sync(None))
     return out
+
+
+DUMP_SEED = 20240917
+DUMP_BUDGET = 48 << 20  # bytes of flow written by --dump-outputs (the option's limit is 64 MB in all)
+
+
+def dump_outputs(out_dir, capi, torch, batch, p, B, lo, full, dev):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, for a fixed, seeded sample of the B
+    frames (at most 256, and at most DUMP_BUDGET bytes): flow.npy = the level flow [n, h, w, 2] (OFClass scope) or the
+    full-resolution flow [n, HEIGHT, WIDTH, 2] (e2e scope), float32; frame_index.npy = the frames' global indices, float64."""
+    import numpy as np
+    per_frame = (full[0].numel() * 4) if full is not None else (p.level_size(p.sc_l)[0] * p.level_size(p.sc_l)[1] * 2 * 4)
+    n = max(1, min(B, 256, DUMP_BUDGET // per_frame))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(B, size=n, replace=False))
+    sel = torch.as_tensor(idx, device=dev)
+    if full is not None:
+        torch.cuda.synchronize()
+        flow = full.index_select(0, sel).cpu().numpy()
+    else:
+        flow = flows_tensor(capi, torch, batch, p, B, dev).index_select(0, sel).cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "flow.npy"), np.ascontiguousarray(flow, dtype=np.float32))
+    np.save(os.path.join(out_dir, "frame_index.npy"), (idx + lo).astype(np.float64))
 
 
 def same_frames(capi, torch, small, big, p, n, dev):
@@ -848,7 +878,15 @@ def main():
     ap.add_argument("--scope", choices=["ofclass", "e2e"], default="ofclass",
                     help="ofclass (the metric): pyramids resident in HBM -> level flow.  e2e (secondary, DESIGN.md 5): "
                          "8-bit frames resident in HBM -> pyramids -> flow -> full-resolution flow in HBM")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline (kernels, roofline, secondary blocks, parity, "
+                         "multi-rank check, CPU baseline); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step (a fixed, seeded sample of the frames' flows) "
+                         "as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(spawn_ranks(args.gpus))
@@ -925,7 +963,7 @@ def main():
     #      resident result is sampled -- the kernel mappings, strip lengths and sub-batch split that are timed below.
     sample, gate = None, None
     contract = args.contract
-    if rank == 0 and (contract == "auto" or args.cpu_seconds > 0):
+    if rank == 0 and (contract == "auto" or (args.full and args.cpu_seconds > 0)):
         try:
             sample = ReferenceSample(p, batch, sample_indices(B))
         except Exception as e:  # no oracle on this box: the exact contract needs no gate
@@ -949,10 +987,11 @@ def main():
             torch.cuda.synchronize()
             g_epe = sample.epe_of_context(fb, "fused", timed_what)
             gate = {"passed": gate_passes(g_epe), "bar": {"mean_px": GATE_MEAN_PX, "max_px": GATE_MAX_PX},
-                    "decides": contract == "auto", "epe_vs_reference": g_epe,
-                    # (second figure, for comparison with earlier rounds: the same frames in a 16-frame context, which
-                    # selects the small-batch mappings -- NOT what is timed)
-                    "epe_vs_reference_small_context": sample.epe("fused")}
+                    "decides": contract == "auto", "epe_vs_reference": g_epe}
+            if args.full:
+                # (second figure, for comparison with earlier rounds: the same frames in a 16-frame context, which
+                # selects the small-batch mappings -- NOT what is timed)
+                gate["epe_vs_reference_small_context"] = sample.epe("fused")
     if contract == "auto":
         ok = bool(gate and gate.get("passed"))
         contract = "fused" if shard.gather_objects(ok, dist, world)[0] else "exact"
@@ -986,18 +1025,20 @@ def main():
     counts = shard.gather_objects(B, dist, world)
     fps = shard.throughput(counts, args.steps, elapsed)
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, capi, torch, batch, p, B, lo, full if e2e else None, dev)
+
     # ---- rank 0: the end-point error of the timed context's OWN result (its last timed pass) against the reference
     timed_epe = None
-    if rank == 0 and sample is not None:
+    if rank == 0 and sample is not None and args.full:
         torch.cuda.synchronize()
         timed_epe = sample.epe_of_context(batch, contract, f"the timed {B}-pair context ({contract} contract"
                                           + (f", {pipeline} pipelined sub-batches)" if pipeline > 1 else ")"))
 
     # ---- every rank: checksums of its frames' results; rank 0 re-computes other ranks' frames and compares
-    sums = frame_checksums(capi, torch, batch, p, B, dev)
-    all_sums = shard.gather_objects((lo, sums), dist, world)
+    all_sums = shard.gather_objects((lo, frame_checksums(capi, torch, batch, p, B, dev)), dist, world) if args.full else None
     mg_check = None
-    if rank == 0 and world > 1:
+    if rank == 0 and world > 1 and args.full:
         compared, bad = 0, 0
         for r in range(1, world):
             rlo, rsums = all_sums[r]
@@ -1094,14 +1135,14 @@ def main():
 
     only_blocks = os.environ.get("OFDIS_BENCH_BLOCKS")  # developer switch: just these secondary blocks (comma separated)
     batch512, strong4096 = None, None
-    if not args.no_extras and not e2e and tv and not only_blocks:
+    if args.full and not args.no_extras and not e2e and tv and not only_blocks:
         batch512 = strong_block(512)
         strong4096 = strong_block(4096)
 
     # ---- the headline loop again for >= 1 s of wall time (the K-step figure above is the contract's; this one shows
     #      that it is sustained)
     sustained = None
-    if not args.no_extras and not only_blocks:
+    if args.full and not args.no_extras and not only_blocks:
         k_s = max(args.steps, int(1.05 / max(elapsed / args.steps, 1e-6)) + 1)
         while True:  # (every rank sees the same max-over-ranks time, so all take the same decision)
             barrier()
@@ -1127,7 +1168,8 @@ def main():
         raise SystemExit(f"bench.py: --gpus {args.gpus} but world_size {ws}, {len(pci)} ranks reported, {len(set(pci))} distinct GPUs")
 
     result = None
-    if rank == 0:
+    kernels, roofline, roofline_valu, pipeline_roofline = None, None, None, None
+    if rank == 0 and args.full:
         # ---- per-kernel timing with HIP events on the launch stream (separate, untimed pass)
         kernels = kernel_table(capi, torch, batch, p, B, stream)
         # HBM traffic per step from the PMC counters (rocprofv3 FETCH_SIZE x2 + WRITE_SIZE, calibrated in
@@ -1305,6 +1347,7 @@ def main():
                 vt = sum(valu.get(k, 0.0) for k in kernels)
                 pipeline_roofline["valu_instructions_per_step"] = vt
                 pipeline_roofline["valu_frac"] = round(vt / step_s / 1e9 / (1024 * clk / 2.0), 4)
+    if rank == 0:
         result = {
             "metric": "frames/sec at 1024×436 op-point-2 (INT)", "value": round(fps, 1), "unit": "frames/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1331,8 +1374,9 @@ def main():
                                            ("torch.distributed.run" if world > 1 else "single process")},
                        "pipeline": f"{pipeline} sub-batches per GPU on internal HIP streams, consecutive steps "
                                    f"overlap inside the timed region" if pipeline > 1 else "off"},
-            "roofline": roofline, "kernels": kernels,
         }
+        if kernels:
+            result["roofline"], result["kernels"] = roofline, kernels
         if gate is not None:
             result["contract_gate"] = gate
         if roofline_valu:
@@ -1347,7 +1391,7 @@ def main():
             result["batch512"] = batch512
         if batch512 or strong4096:
             result["strong_scaling"] = {k: v for k, v in (("512", batch512), ("4096", strong4096)) if v}
-        if not args.no_parity:
+        if args.full and not args.no_parity:
             try:
                 import oracle
                 O = oracle.c_oracle()
@@ -1376,7 +1420,7 @@ def main():
                                           "oracle" % (f, 1 << p.sc_l, st[0] * (1 << p.sc_l), st[1] * (1 << p.sc_l))}
             except Exception as e:  # the checker is optional for the measurement
                 result["parity_check"] = f"not run ({type(e).__name__}: {e})"
-        extras = world == 1 and tv and not e2e and not args.no_extras
+        extras = args.full and world == 1 and tv and not e2e and not args.no_extras
         if extras and not only_blocks:
             # BASELINE.json also lists the same operating point with the refinement switched off (configs[1]); report it
             # next to the headline (configs[2], TV on -- what operating point 2 is in the reference, run_dense.cpp:259-265)
@@ -1424,7 +1468,7 @@ def main():
                 except Exception as e:
                     result[name] = {"value": None, "error": f"{type(e).__name__}: {e}"}
         # ---- what scales, stated BEFORE an 8-GPU node measures it (one-GPU run only: projected from this run's own figures)
-        if world == 1 and not strong:
+        if args.full and world == 1 and not strong:
             exp = {"weak": {"expected_at_8_gpus": round(8 * fps, 1), "unit": "frames/s",
                             "why": "every rank owns --batch pairs of its own and nothing is shared on the data path: linear by "
                                    "construction (RCCL carries two barriers, one 8-byte MAX and small reports per timed region)"}}
@@ -1468,7 +1512,7 @@ def main():
                         "expected_at_8_gpus": round(8 * bf, 1), "vs_one_gpu": round(8 * bf / b4096["value"], 2),
                         "from": f"512 pairs per GPU with {b512['in_flight']['best_depth']} steps in flight = {bf} frames/s per GPU"}
             result["scaling_expectation"] = exp
-        if args.cpu_seconds > 0:  # (rank 0 only, whatever the world size: the other ranks wait in the barrier below)
+        if args.full and args.cpu_seconds > 0:  # (rank 0 only, whatever the world size: the other ranks wait in the barrier below)
             try:
                 if sample is None:
                     raise RuntimeError("no reference sample (oracle missing)")

@@ -1,35 +1,46 @@
 """Natural images for the parity tests.
 
-Every other parity input of this repository is synthetic (tools/gen_synth.py).  The build image happens to carry a few
-photographs inside its Python packages -- scikit-image's data directory (among them a real Middlebury 2014 stereo pair,
-`motorcycle_left.png` / `motorcycle_right.png`, with its ground-truth disparity) and scikit-learn's two sample JPEGs.  They
-are NOT part of this repository and not of the reference: the tests read them where they lie if they are there (the GPU
-box runs the same image) and skip otherwise; nothing is copied.  tests/golden/natural.json holds the SHA-256 of each input
-as decoded here and of the reference build's output for it (made by tests/golden/make_natural.py), so that the CPU
-restatement is pinned on photographs as well wherever the same files decode to the same bytes.
+Every other parity input of this repository is synthetic (tools/gen_synth.py).  These are a few photographs stored under
+tests/golden/natural/ (see the README there for where they come from): a real Middlebury 2014 stereo pair,
+`motorcycle_left.png` / `motorcycle_right.png`, with its ground-truth disparity, and four single photographs.
+tests/golden/natural.json holds the SHA-256 of each input as decoded here and of the reference build's output for it (made by
+tests/golden/make_natural.py), so that the CPU restatement is pinned on photographs as well.
 """
-import glob
 import hashlib
+import lzma
 import os
 
 import numpy as np
 
 
-def _dirs():
-    out = []
-    for pat in ("/opt/conda/lib/python3*/site-packages/skimage/data", "/usr/lib/python3*/site-packages/skimage/data",
-                "/usr/local/lib/python3*/dist-packages/skimage/data", "/usr/local/lib/python3*/dist-packages/sklearn/datasets/images",
-                "/opt/conda/lib/python3*/site-packages/sklearn/datasets/images"):
-        out += sorted(glob.glob(pat))
-    return out
+DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "natural")
 
 
 def find(name):
-    for d in _dirs():
-        p = os.path.join(d, name)
-        if os.path.exists(p):
-            return p
-    return None
+    p = os.path.join(DIR, name)
+    return p if os.path.exists(p) else None
+
+
+def pack_f32(arr, path):
+    """A float32 image stored losslessly in about two thirds of the bytes np.savez_compressed needs (smooth fields such as a
+    disparity map): the bit patterns as int32 differences down the columns, split into four byte planes, xz-compressed
+    behind an 8-byte header (rows, columns as little-endian uint32).  load_f32 returns the same bits."""
+    a = np.ascontiguousarray(arr, dtype=np.float32)
+    bits = a.view(np.int32).astype(np.int64)
+    delta = np.diff(bits, axis=0, prepend=0).astype("<i4")
+    planes = np.frombuffer(delta.tobytes(), np.uint8).reshape(-1, 4).T.tobytes()
+    head = np.array(a.shape, "<u4").tobytes()
+    filt = [{"id": lzma.FILTER_LZMA2, "preset": 9 | lzma.PRESET_EXTREME, "lc": 4, "pb": 2}]
+    with open(path, "wb") as f:
+        f.write(lzma.compress(head + planes, format=lzma.FORMAT_XZ, filters=filt))
+
+
+def load_f32(path):
+    with open(path, "rb") as f:
+        raw = lzma.decompress(f.read())
+    h, w = (int(v) for v in np.frombuffer(raw[:8], "<u4"))
+    delta = np.frombuffer(raw[8:], np.uint8).reshape(4, h * w).T.copy().view("<i4").reshape(h, w)
+    return np.cumsum(delta, axis=0, dtype=np.int32).view(np.float32)  # (int32 sums wrap: the exact inverse of the differences)
 
 
 def load_rgb(name):
@@ -92,11 +103,11 @@ def pair(name):
         if a is None or b is None:
             return None
         truth = {}
-        p = find("motorcycle_disp.npz")
+        p = find("motorcycle_disp.f32.xz")
         if p is not None:
-            truth["disparity"] = np.load(p)["arr_0"].astype(np.float32)
+            truth["disparity"] = load_f32(p)
         return a, b, truth
-    src = {"china": ("china.jpg", 1.2, 1.015, 4.3, -2.6), "astronaut": ("astronaut.png", -2.0, 0.99, -6.4, 3.2),
+    src = {"china": ("china.png", 1.2, 1.015, 4.3, -2.6), "astronaut": ("astronaut.png", -2.0, 0.99, -6.4, 3.2),
            "coffee": ("coffee.png", 0.8, 1.0, 9.5, 1.25), "chelsea": ("chelsea.png", -0.6, 1.02, -3.1, -4.7)}.get(name)
     if src is None:
         return None

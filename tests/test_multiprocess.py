@@ -156,7 +156,7 @@ def test_bench_eight_ranks_control_flow(gpu):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     d = _run_bench([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--total-frames", "512", "--steps", "2",
-                    "--warmup", "1", "--cpu-seconds", "0", "--no-extras"], env)
+                    "--warmup", "1", "--full", "--cpu-seconds", "0", "--no-extras"], env)
     assert d["n_gpus"] == 8 and d["scaling"] == "strong"
     assert d["config"]["global_frames_per_step"] == 512 and d["config"]["frames_per_gpu_per_step"] == 64
     rk = d["config"]["ranks"]
@@ -174,7 +174,7 @@ def test_bench_two_ranks_under_torchrun(gpu):
     env, backend = _bench_env(gpu)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--batch", "64", "--cpu-seconds", "0", "--no-extras"]
+           "--warmup", "1", "--batch", "64", "--full", "--cpu-seconds", "0", "--no-extras"]
     d = _run_bench(cmd, env)
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["config"]["global_frames_per_step"] == 128
     rk = d["config"]["ranks"]
@@ -196,7 +196,7 @@ def test_bench_spawns_its_own_ranks(gpu):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     d = _run_bench([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                    "--batch", "96", "--cpu-seconds", "0", "--no-extras"], env)
+                    "--batch", "96", "--full", "--cpu-seconds", "0", "--no-extras"], env)
     assert d["n_gpus"] == 2 and d["config"]["global_frames_per_step"] == 192
     rk = d["config"]["ranks"]
     assert (rk["world_size"], rk["backend"], rk["launch"]) == (2, backend, "self-spawned by bench.py --gpus")
@@ -213,7 +213,7 @@ def test_bench_batch512_block_with_two_ranks(gpu):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     d = _run_bench([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                    "--batch", "256", "--cpu-seconds", "0", "--no-parity"], env)
+                    "--batch", "256", "--full", "--cpu-seconds", "0", "--no-parity"], env)
     assert d["n_gpus"] == 2 and d["multi_gpu_check"]["bit_identical_to_1gpu"]
     b5 = d["batch512"]
     assert b5["scaling"] == "strong" and b5["value"] > 0 and "256 pairs on rank 0" in b5["workload"]
@@ -233,7 +233,7 @@ def test_bench_strong_scaling_partition(gpu):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     d = _run_bench([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--total-frames", "75", "--steps", "2",
-                    "--warmup", "1", "--cpu-seconds", "0", "--no-extras"], env)
+                    "--warmup", "1", "--full", "--cpu-seconds", "0", "--no-extras"], env)
     assert d["n_gpus"] == 2 and d["scaling"] == "strong"
     assert d["config"]["global_frames_per_step"] == 75 and d["config"]["frames_per_gpu_per_step"] == [38, 37]
     assert d["multi_gpu_check"] == {**d["multi_gpu_check"], "frames_compared": 37, "mismatches": 0, "bit_identical_to_1gpu": True}
@@ -250,7 +250,36 @@ def test_bench_rccl_calls_with_one_rank(gpu):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "OFDIS_BENCH_BACKEND", "OFDIS_BENCH_SHARE_GPU"):
         env.pop(k, None)
     d = _run_bench([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                    "--batch", "64", "--cpu-seconds", "0", "--no-extras"], env)
+                    "--batch", "64", "--full", "--cpu-seconds", "0", "--no-extras"], env)
     assert d["n_gpus"] == 1 and d["config"]["ranks"]["world_size"] == 1
     assert d["config"]["ranks"]["backend"] == "rccl (torch.distributed nccl)"
     assert _parity_ok(d)
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_and_dump_outputs(gpu, tmp_path):
+    """A plain `bench.py --gpus 1` line carries the headline and nothing that --full measures; --dump-outputs writes the
+    timed path's last-step flows for a fixed sample of frames, the same bits when the same run is repeated."""
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "OFDIS_BENCH_FORCE_DIST", "OFDIS_BENCH_BACKEND",
+              "OFDIS_BENCH_SHARE_GPU", "OFDIS_BENCH_BLOCKS"):
+        env.pop(k, None)
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        d = _run_bench([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--batch", "64", "--dump-outputs", str(out)], env)
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0
+        assert (d["unit"], d["higher_is_better"], d["dtype"]) == ("frames/s", True, "f32") and d["metric"].startswith("frames/sec")
+        for k in ("roofline", "kernels", "parity_check", "cpu_baseline", "sustained", "batch512", "small_batch", "tv_off"):
+            assert k not in d, k
+        flow, idx = np.load(out / "flow.npy"), np.load(out / "frame_index.npy")
+        assert flow.dtype == np.float32 and idx.dtype == np.float64 and flow.shape[0] == idx.shape[0] == 64
+        assert flow.shape[-1] == 2 and np.isfinite(flow).all() and np.abs(flow).max() > 0
+        assert list(idx) == sorted(set(idx)) and 0 <= idx.min() and idx.max() < 64
+        assert flow.nbytes + idx.nbytes <= 64 << 20
+        dumps.append((flow, idx, d["contract"]))
+    assert dumps[0][2] == dumps[1][2]
+    assert np.array_equal(dumps[0][1], dumps[1][1]) and np.array_equal(dumps[0][0].view(np.int32), dumps[1][0].view(np.int32))

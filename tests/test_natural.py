@@ -1,7 +1,6 @@
-"""Photographs through both sides.  Every other parity input is synthetic; these tests run the few natural images the build
-image carries inside its Python packages (tests/natural.py: a real Middlebury stereo pair and four photographs turned into
-pairs by a known similarity warp) through the reference build, the C restatement, the HIP library and the command-line
-binaries.  They skip where the files (or a PNG / JPEG decoder) are missing."""
+"""Photographs through both sides.  Every other parity input is synthetic; these tests run the few natural images stored
+under tests/golden/natural/ (tests/natural.py: a real Middlebury stereo pair and four photographs turned into pairs by a
+known similarity warp) through the reference build, the C restatement, the HIP library and the command-line binaries."""
 import json
 import os
 import subprocess

@@ -5,7 +5,7 @@ rounds=$1; shift
 for r in $(seq $rounds); do
   for v in "$@"; do
     if [ "$v" = main ]; then L=of_dis_amd/lib/libofdis_hip.so; else L=of_dis_amd/lib/ab_$v/libofdis_hip.so; fi
-    OFDIS_LIB=$L timeout 300 python bench.py --no-extras --cpu-seconds 0 --contract ${CONTRACT:-fused} 2>/dev/null | python -c "
+    OFDIS_LIB=$L timeout 300 python bench.py --full --no-extras --cpu-seconds 0 --contract ${CONTRACT:-fused} 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); k=d['kernels']
 print('$v', round(d['value']), d['ms_per_step'], ' '.join(f\"{n}={k[n]['ms_per_step']}\" for n in k), 'tv levels', k.get('tv_fused',{}).get('ms_per_level'))"

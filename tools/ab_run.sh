@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of library builds made by tools/ab_build.py on the 64-pair and 1-pair workloads:  bash tools/ab_run.sh NAME [NAME...]
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R; OUT=$R/gpurun_out/ab; mkdir -p $OUT
-run() { env $2 timeout 300 python bench.py --no-extras --cpu-seconds 0 --no-parity $3 > $OUT/$1.json 2>> $OUT/err.log
+run() { env $2 timeout 300 python bench.py --full --no-extras --cpu-seconds 0 --no-parity $3 > $OUT/$1.json 2>> $OUT/err.log
   python - "$1" $OUT/$1.json <<'PY'
 import json,sys
 try:

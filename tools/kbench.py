@@ -22,7 +22,7 @@ for a in args:
     k, v = a.split("=", 1)
     env[k] = v
     tag.append(a)
-r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--cpu-seconds", "0", "--no-parity"] + bargs,
+r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--cpu-seconds", "0", "--no-parity"] + bargs,
                    env=env, capture_output=True, text=True)
 line = [l for l in r.stdout.splitlines() if l.startswith("{")]
 if not line:

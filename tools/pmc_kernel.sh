@@ -9,7 +9,7 @@ i=0
 IFS='|' read -ra ARR <<< "$SETS"
 for set in "${ARR[@]}"; do
   i=$((i+1))
-  timeout 120 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $OUT/raw$i -- python $R/bench.py --steps 1 --warmup 0 --cpu-seconds 0 --no-parity --no-extras --pipeline 1 $BARGS > $OUT/set$i.log 2>&1
+  timeout 120 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $OUT/raw$i -- python $R/bench.py --full --steps 1 --warmup 0 --cpu-seconds 0 --no-parity --no-extras --pipeline 1 $BARGS > $OUT/set$i.log 2>&1
   f=$(find $OUT/raw$i -name "*counter_collection.csv" | head -1)
   [ -n "$f" ] && python $R/tools/pmc_summary.py $f $K > $OUT/set$i.txt || tail -5 $OUT/set$i.log
   rm -rf $OUT/raw$i

@@ -18,18 +18,18 @@ cd $R
 bash tools/pmc_round.sh $TAG $PMC_BATCH $CONTRACT
 cp $R/gpurun_out/pmc_$TAG/traffic_$CONTRACT.json $OUT/traffic_$CONTRACT.json 2>/dev/null
 if [ "$SKIP_BENCH" != "1" ]; then
-timeout 1200 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout 1200 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 tail -c 300 $OUT/bench.json; echo
 fi
 export TMPDIR=/tmp
 cd /tmp
 # un-pipelined kernel trace of the headline workload only (no secondary blocks): per level rows + the --stats summary
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- python $R/bench.py --batch $BATCH --steps 3 --warmup 1 --cpu-seconds 0 --no-parity --no-extras --pipeline 1 --contract $CONTRACT > $OUT/kt.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- python $R/bench.py --full --batch $BATCH --steps 3 --warmup 1 --cpu-seconds 0 --no-parity --no-extras --pipeline 1 --contract $CONTRACT > $OUT/kt.log 2>&1
 f=$(find $OUT/kt -name "*kernel_trace.csv" | head -1); [ -n "$f" ] && python $R/tools/prof_summary.py $f > $OUT/kernel_levels.csv
 f=$(find $OUT/kt -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && python $R/tools/prof_summary.py $f > $OUT/kernel_stats.csv
 rm -rf $OUT/kt
 # BASELINE configs[3] (the config4 block of bench.py alone, a small main batch beside it)
-OFDIS_BENCH_CONFIG4_PAIRS=96 OFDIS_BENCH_BLOCKS=config4 timeout 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/kt4 -- python $R/bench.py --batch 64 --steps 1 --warmup 0 --cpu-seconds 0 --no-parity --contract $CONTRACT > $OUT/kt4.log 2>&1
+OFDIS_BENCH_CONFIG4_PAIRS=96 OFDIS_BENCH_BLOCKS=config4 timeout 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/kt4 -- python $R/bench.py --full --batch 64 --steps 1 --warmup 0 --cpu-seconds 0 --no-parity --contract $CONTRACT > $OUT/kt4.log 2>&1
 f=$(find $OUT/kt4 -name "*kernel_trace.csv" | head -1); [ -n "$f" ] && python $R/tools/prof_summary.py $f > $OUT/config4_kernel_levels.csv
 rm -rf $OUT/kt4
 cd $R
