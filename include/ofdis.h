@@ -125,9 +125,55 @@ void ofdis_flow_cache_clear(void);
  * ------------------------------------------------------------------------------------------- */
 typedef struct ofdis_batch ofdis_batch;
 
-/* nframes: 1..65535.  All device memory of the context is one allocation. */
+/* nframes: 1..65535.  All device memory of the context is one allocation.  Same as ofdis_batch_create_ex(out, p, nframes, 0). */
 int ofdis_batch_create(ofdis_batch** out, const ofdis_params* p, int nframes);
 void ofdis_batch_destroy(ofdis_batch* b);
+
+/* ---------------------------------------------------------------------------------------------
+ * Bidirectional flow and forward-backward occlusion masks (the consistency check of Sundaram, Brox and Keutzer, 2010).
+ * ------------------------------------------------------------------------------------------- */
+#define OFDIS_BATCH_REVERSE 1u          /* flag of ofdis_batch_create_ex */
+#define OFDIS_FB_ALPHA 0.01f            /* defaults of the consistency test */
+#define OFDIS_FB_BETA  0.5f
+enum { OFDIS_FB_CONSISTENT = 0, OFDIS_FB_INCONSISTENT = 1, OFDIS_FB_OUTSIDE = 2 };
+
+/* flags = 0 is ofdis_batch_create.  Unknown flag bits: OFDIS_ERR_INVALID.
+ * OFDIS_BATCH_REVERSE: the context also computes the REVERSE flow B -> A of every pair.  It allocates B's gradient planes
+ * (input kinds 4 and 5, filled by ofdis_batch_build_pyramids_u8 or ofdis_batch_upload_b_gradients) whatever usefbcon says, and
+ * per-level reverse flow buffers; all other scratch is shared.  ofdis_batch_run then runs the coarse-to-fine pass twice on
+ * `stream`: first forward, exactly as a plain context, then on the swapped pair.  Frame k's reverse flow (every level) is
+ * bit-identical to the forward flow that a plain context of the same nframes, params, contract and pipelining computes for
+ * the pair (B_k, A_k); the forward flow is bit-identical to a plain context's.  Pipelining, graph replay, kernel timing and
+ * ofdis_batch_status cover both passes (a lost hand-over of the cross-CU TV variant in either fails the pass).
+ * Stereo depth (selectmode 2) with OFDIS_BATCH_REVERSE: OFDIS_ERR_UNSUPPORTED. */
+int ofdis_batch_create_ex(ofdis_batch** out, const ofdis_params* p, int nframes, unsigned flags);
+/* The reverse results of an OFDIS_BATCH_REVERSE context, laid out as ofdis_batch_flow / ofdis_batch_level_flow /
+ * ofdis_batch_download; NULL or OFDIS_ERR_INVALID on a context created without the flag. */
+const float* ofdis_batch_flow_reverse(const ofdis_batch* b);
+const float* ofdis_batch_level_flow_reverse(const ofdis_batch* b, int level);
+int ofdis_batch_download_reverse(ofdis_batch* b, int frame, float* outflow_host, void* stream);
+/* Warm start of the reverse direction: borrows a device array laid out as for ofdis_batch_set_initflow (which stays
+ * forward-only); NULL = zero flow.  OFDIS_ERR_INVALID on a context created without OFDIS_BATCH_REVERSE. */
+int ofdis_batch_set_initflow_reverse(ofdis_batch* b, const float* initflow_dev);
+/* One launch over the frames [first_frame, first_frame + count) of an OFDIS_BATCH_REVERSE context: out_fw / out_rev =
+ * device [count][height_org][width_org][2], bit-identical to what ofdis_batch_upsample_frames makes of the forward flow
+ * (and a plain context on the swapped pairs of the reverse flow); mask_fw / mask_rev = device [count][height_org][width_org]
+ * bytes, bit-identical to ofdis_fb_check(fw, rev) and ofdis_fb_check(rev, fw) on those materialised flows.  Any of the four
+ * outputs may be NULL (not written).  alpha, beta: as for ofdis_fb_check.  Joins a pipelined pass by itself. */
+int ofdis_batch_upsample_bidir(ofdis_batch* b, int first_frame, int count, float* out_fw, float* out_rev,
+                               uint8_t* mask_fw, uint8_t* mask_rev, int width_org, int height_org,
+                               float alpha, float beta, void* stream);
+/* The forward-backward consistency test on device arrays of AoS flows [nframes][height][width][2]: one byte per pixel of
+ * `flow` (the image `flow` starts in) into `mask` [nframes][height][width].  For pixel (x, y) with (u, v) = flow, every
+ * operation a separately rounded fp32 operation in this order:
+ *   xb = x + u, yb = y + v; not (0 <= xb <= W-1 and 0 <= yb <= H-1) (NaN included): OFDIS_FB_OUTSIDE
+ *   x0 = floor(xb) clamped to W-2 (x0 = 0, ax = 0 when W == 1), ax = xb - x0, x1 = min(x0+1, W-1); the same for y
+ *   r = (R[y0][x0]*(1-ax) + R[y0][x1]*ax) * (1-ay) + (R[y1][x0]*(1-ax) + R[y1][x1]*ax) * ay   (R = flow_other, per component)
+ *   du = u + ru, dv = v + rv; lhs = du*du + dv*dv; rhs = alpha * ((u*u + v*v) + (ru*ru + rv*rv)) + beta
+ *   lhs <= rhs: OFDIS_FB_CONSISTENT, else OFDIS_FB_INCONSISTENT
+ * Independent of the arithmetic contract.  Invalid sizes, or alpha / beta negative or not finite: OFDIS_ERR_INVALID. */
+int ofdis_fb_check(const float* flow, const float* flow_other, uint8_t* mask, int nframes, int width, int height,
+                   float alpha, float beta, void* stream);
 
 /* device pointers to the context-owned input planes of level l: kind 0 = image A, 1 = A_dx,
  * 2 = A_dy, 3 = image B (with usefbcon also 4 = B_dx, 5 = B_dy).  The caller fills them (hipMemcpy, its own kernels, ofdis_batch_upload

@@ -35,7 +35,12 @@ ABI_SYMBOLS = [
     "ofdis_batch_upsample_frames",
     "ofdis_build_id", "ofdis_stream_create", "ofdis_stream_destroy", "ofdis_host_alloc", "ofdis_host_free", "ofdis_memcpy_h2d_async", "ofdis_memcpy_d2h_async",
     "ofdis_event_create", "ofdis_event_destroy", "ofdis_event_record", "ofdis_stream_wait_event", "ofdis_event_sync",
+    "ofdis_batch_create_ex", "ofdis_batch_flow_reverse", "ofdis_batch_level_flow_reverse", "ofdis_batch_set_initflow_reverse",
+    "ofdis_batch_download_reverse", "ofdis_batch_upsample_bidir", "ofdis_fb_check",
 ]
+BATCH_REVERSE = 1  # include/ofdis.h: OFDIS_BATCH_REVERSE
+FB_ALPHA, FB_BETA = 0.01, 0.5  # OFDIS_FB_ALPHA / OFDIS_FB_BETA
+FB_CONSISTENT, FB_INCONSISTENT, FB_OUTSIDE = 0, 1, 2
 OFDIS_VERSION = 3  # include/ofdis.h: the struct layouts below (OfdisTuning: 20 ints) belong to this ABI version
 
 
@@ -130,6 +135,15 @@ def lib():
         L.ofdis_batch_kernel_times.argtypes = [VP, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int)]
         L.ofdis_get_tuning.argtypes = [C.POINTER(OfdisTuning)]
         L.ofdis_set_tuning.argtypes = [C.POINTER(OfdisTuning)]
+        L.ofdis_batch_create_ex.argtypes = [C.POINTER(VP), C.POINTER(OfdisParams), C.c_int, C.c_uint]
+        L.ofdis_batch_flow_reverse.restype = VP
+        L.ofdis_batch_flow_reverse.argtypes = [VP]
+        L.ofdis_batch_level_flow_reverse.restype = VP
+        L.ofdis_batch_level_flow_reverse.argtypes = [VP, C.c_int]
+        L.ofdis_batch_set_initflow_reverse.argtypes = [VP, VP]
+        L.ofdis_batch_download_reverse.argtypes = [VP, C.c_int, FP, VP]
+        L.ofdis_batch_upsample_bidir.argtypes = [VP, C.c_int, C.c_int, VP, VP, VP, VP, C.c_int, C.c_int, C.c_float, C.c_float, VP]
+        L.ofdis_fb_check.argtypes = [VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, VP]
         _lib = L
     return _lib
 
@@ -378,14 +392,30 @@ def flow(p, pyr_a, pyr_a_dx, pyr_a_dy, pyr_b, initflow=None, pyr_b_dx=None, pyr_
     return out
 
 
-class Batch:
-    """ofdis_batch: `nframes` frame pairs of one geometry resident in HBM."""
+def fb_check(flow, other, alpha=FB_ALPHA, beta=FB_BETA):
+    """ofdis_fb_check on the device: flow, other [..., h, w, 2] float32 (the same shape; leading axes are frames) ->
+    uint8 mask [..., h, w] of FB_CONSISTENT / FB_INCONSISTENT / FB_OUTSIDE for every pixel of `flow`."""
+    flow, other = _f(flow), _f(other)
+    assert flow.shape == other.shape and flow.ndim >= 3 and flow.shape[-1] == 2, (flow.shape, other.shape)
+    h, w = flow.shape[-3:-1]
+    n = int(np.prod(flow.shape[:-3], dtype=np.int64))
+    df, do = Dev(flow), Dev(other)
+    dm = Dev(nbytes=max(1, n * h * w))
+    check(lib().ofdis_fb_check(df.ptr, do.ptr, dm.ptr, n, w, h, alpha, beta, None))
+    check(lib().ofdis_sync(None))
+    return dm.get(flow.shape[:-1], np.uint8)
 
-    def __init__(self, p, nframes):
+
+class Batch:
+    """ofdis_batch: `nframes` frame pairs of one geometry resident in HBM.  reverse=True: ofdis_batch_create_ex with
+    OFDIS_BATCH_REVERSE (every pass also computes the flow B -> A of each pair)."""
+
+    def __init__(self, p, nframes, reverse=False):
         self.p = p.copy()
         self.nframes = nframes
+        self.reverse = bool(reverse)
         self.h = VP()
-        check(lib().ofdis_batch_create(C.byref(self.h), C.byref(self.p), nframes))
+        check(lib().ofdis_batch_create_ex(C.byref(self.h), C.byref(self.p), nframes, BATCH_REVERSE if reverse else 0))
 
     def close(self):
         if self.h:
@@ -497,6 +527,45 @@ class Batch:
         check(lib().ofdis_sync(None))
         check(lib().ofdis_memcpy_d2h(out.ctypes.data, lib().ofdis_batch_level_flow(self.h, level), out.nbytes))
         return out
+
+    # ---- reverse direction (reverse=True contexts)
+    def set_initflow_reverse(self, dev_ptr):
+        check(lib().ofdis_batch_set_initflow_reverse(self.h, dev_ptr))
+
+    def download_reverse(self, frame, stream=None):
+        w, h = self.p.level_size(self.p.sc_l)
+        out = np.zeros((h, w, self.p.nop), _f32)
+        check(lib().ofdis_batch_download_reverse(self.h, frame, out.ctypes.data_as(FP), stream))
+        return out
+
+    def level_flow_reverse(self, level):
+        ptr = lib().ofdis_batch_level_flow_reverse(self.h, level)
+        if not ptr:
+            raise OfdisError("ofdis_batch_level_flow_reverse: not a reverse context, or no such level")
+        w, h = self.p.level_size(level)
+        out = np.zeros((self.nframes, h, w, self.p.nop), _f32)
+        self.join(None)
+        check(lib().ofdis_sync(None))
+        check(lib().ofdis_memcpy_d2h(out.ctypes.data, ptr, out.nbytes))
+        return out
+
+    def download_all_reverse(self):
+        return self.level_flow_reverse(self.p.sc_l)
+
+    def upsample_bidir(self, width_org, height_org, alpha=FB_ALPHA, beta=FB_BETA, first=0, count=None,
+                       outputs=(True, True, True, True), stream=None):
+        """ofdis_batch_upsample_bidir over frames [first, first + count): (fw, rev, mask_fw, mask_rev) as host arrays,
+        [count][height_org][width_org][2] float32 and [count][height_org][width_org] uint8.  `outputs` selects which of the
+        four the library writes (the others are passed as NULL and returned as None)."""
+        count = self.nframes - first if count is None else count
+        shapes = [(count, height_org, width_org, 2)] * 2 + [(count, height_org, width_org)] * 2
+        dtypes = [_f32, _f32, np.uint8, np.uint8]
+        devs = [Dev(nbytes=max(1, int(np.prod(s)) * np.dtype(t).itemsize)) if want else None
+                for s, t, want in zip(shapes, dtypes, outputs)]
+        check(lib().ofdis_batch_upsample_bidir(self.h, first, count, *[d.ptr if d else None for d in devs], width_org,
+                                               height_org, alpha, beta, stream))
+        check(lib().ofdis_sync(stream))
+        return tuple(d.get(s, t) if d else None for d, s, t in zip(devs, shapes, dtypes))
 
     def timing(self, enable=True):
         check(lib().ofdis_batch_timing(self.h, int(enable)))

@@ -176,6 +176,13 @@ bool pyr_planes_fuses_down(int w, int h, int noc, int pad);
 // x 2^sc_l, bilinear upsample (cv::resize INTER_LINEAR) and crop of the AoS result (run_dense.cpp:406-414)
 hipError_t launch_upsample_crop(const float* flow, float* out, int nframes, int sw, int sh, int sc_l, int left, int top,
                                 int wo, int ho, int channels, hipStream_t s);
+// forward-backward consistency test (include/ofdis.h: ofdis_fb_check) on full-resolution AoS flows
+hipError_t launch_fb_check(const float* flow, const float* other, uint8_t* mask, int nframes, int w, int h, float alpha,
+                           float beta, hipStream_t s);
+// both directions' level flows to full resolution plus both masks in one launch (ofdis_batch_upsample_bidir); outputs may be null
+hipError_t launch_upsample_bidir(const float* fw, const float* rev, float* out_fw, float* out_rev, uint8_t* mask_fw,
+                                 uint8_t* mask_rev, int nframes, int sw, int sh, int sc_l, int left, int top, int wo, int ho,
+                                 float alpha, float beta, hipStream_t s);
 
 // ---- stereo-depth mode (SELECTMODE=2; ofdis_de.hip)
 struct DeSystemArgs {

@@ -399,4 +399,138 @@ hipError_t launch_upsample_crop(const float* flow, float* out, int nframes, int 
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------ forward-backward consistency
+// The test of include/ofdis.h (ofdis_fb_check), written once for both kernels below.  This file is compiled under the exact
+// contract only (-ffp-contract=off): every operation is separately rounded, so the mask is a fixed function of the two flows.
+// `R(xx, yy)` returns the other direction's flow at an integer pixel of the full-resolution image.
+enum : uint8_t { FB_CONSISTENT = 0, FB_INCONSISTENT = 1, FB_OUTSIDE = 2 };
+template <class Other>
+__device__ __forceinline__ uint8_t fb_code(float u, float v, int x, int y, int W, int H, float alpha, float beta, Other R) {
+  const float xb = (float)x + u, yb = (float)y + v;
+  if (!(xb >= 0.0f && xb <= (float)(W - 1) && yb >= 0.0f && yb <= (float)(H - 1))) return FB_OUTSIDE;  // (NaN lands here)
+  int x0 = 0, y0 = 0;
+  float ax = 0.0f, ay = 0.0f;
+  if (W > 1) { x0 = min((int)floorf(xb), W - 2); ax = xb - (float)x0; }
+  if (H > 1) { y0 = min((int)floorf(yb), H - 2); ay = yb - (float)y0; }
+  const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
+  float2 r00, r01, r10, r11;
+  R(x0, x1, y0, y1, r00, r01, r10, r11);
+  const float bx = 1.0f - ax, by = 1.0f - ay;
+  const float ru = (r00.x * bx + r01.x * ax) * by + (r10.x * bx + r11.x * ax) * ay;
+  const float rv = (r00.y * bx + r01.y * ax) * by + (r10.y * bx + r11.y * ax) * ay;
+  const float du = u + ru, dv = v + rv;
+  const float lhs = du * du + dv * dv;
+  const float rhs = alpha * ((u * u + v * v) + (ru * ru + rv * rv)) + beta;
+  return lhs <= rhs ? FB_CONSISTENT : FB_INCONSISTENT;
+}
+
+// materialised flows: one pixel per thread, grid-stride over all frames
+__global__ __launch_bounds__(256) void fb_check_kernel(const float2* __restrict__ flow, const float2* __restrict__ other,
+                                                       uint8_t* __restrict__ mask, long long total, int w, int h,
+                                                       float alpha, float beta) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int x = (int)(i % w);
+    const long long r = i / w;
+    const int y = (int)(r % h);
+    const float2* R = other + (i - (long long)y * w - x);  // the frame's first pixel
+    const float2 uv = flow[i];
+    mask[i] = fb_code(uv.x, uv.y, x, y, w, h, alpha, beta,
+                      [&](int x0, int x1, int y0, int y1, float2& r00, float2& r01, float2& r10, float2& r11) {
+                        r00 = R[(size_t)y0 * w + x0]; r01 = R[(size_t)y0 * w + x1];
+                        r10 = R[(size_t)y1 * w + x0]; r11 = R[(size_t)y1 * w + x1];
+                      });
+  }
+}
+
+hipError_t launch_fb_check(const float* flow, const float* other, uint8_t* mask, int nframes, int w, int h, float alpha,
+                           float beta, hipStream_t s) {
+  const long long total = (long long)nframes * w * h;
+  hipLaunchKernelGGL(fb_check_kernel, dim3(grid_for(total)), dim3(256), 0, s, (const float2*)flow, (const float2*)other, mask,
+                     total, w, h, alpha, beta);
+  return hipGetLastError();
+}
+
+// Vertical source rows and weight of padded full-resolution row Y: the vertical step of upsample_crop_kernel for one row.
+// (There the rows of a group share sy; floor((Y + 0.5) / s - 0.5) is exact, so per row it is the same value.)
+struct UpRow {
+  int sy, sy1;
+  float fy;
+};
+__device__ __forceinline__ UpRow up_row(int Y, int sh, float inv) {
+  UpRow r;
+  const float fy = ((float)Y + 0.5f) * inv - 0.5f;
+  r.sy = (int)floorf(fy);
+  const bool clamp = r.sy < 0 || r.sy >= sh - 1;
+  r.fy = clamp ? 0.0f : fy - floorf(fy);
+  r.sy = r.sy < 0 ? 0 : (r.sy >= sh - 1 ? sh - 1 : r.sy);
+  r.sy1 = min(r.sy + 1, sh - 1);
+  return r;
+}
+__device__ __forceinline__ float2 up_mix(float2 a0, float2 a1, float fy) {
+  const float ay = 1.0f - fy;
+  return make_float2(a0.x * ay + a1.x * fy, a0.y * ay + a1.y * fy);
+}
+
+// Both directions to full resolution and both masks, one pixel per thread (grid = (x chunks of 256, output rows, frames)).
+// The masks need the OTHER direction's upsampled flow at the four integer neighbours of a non-integer target: recomputed
+// from the level flow with upsample_h / up_row / up_mix -- the arithmetic of upsample_crop_kernel, so the values are the
+// bits ofdis_batch_upsample_frames writes -- instead of read back from HBM.  Neighbour rows y0 and y1 usually share their
+// source rows (for s > 1): then the two horizontal interpolations are reused.  The level flows (57 KB per frame and
+// direction at operating point 2, 2 MB at 1080p) are gathered through the caches.
+typedef float f2n __attribute__((ext_vector_type(2)));
+__global__ __launch_bounds__(256) void upsample_bidir_kernel(const float2* __restrict__ fw, const float2* __restrict__ rev,
+                                                             float2* __restrict__ out_fw, float2* __restrict__ out_rev,
+                                                             uint8_t* __restrict__ mask_fw, uint8_t* __restrict__ mask_rev,
+                                                             int sw, int sh, int sc_l, int left, int top, int wo, int ho,
+                                                             float alpha, float beta) {
+  const int f = blockIdx.z, y = blockIdx.y;
+  const int x = blockIdx.x * 256 + threadIdx.x;
+  if (x >= wo) return;
+  const float scf = (float)(1 << sc_l), inv = 1.0f / scf;
+  const bool scale = sc_l > 0;
+  const float2* flw[2] = {fw + (size_t)f * sw * sh, rev + (size_t)f * sw * sh};
+  const UpRow ry = up_row(y + top, sh, inv);
+  float2 val[2];
+#pragma unroll
+  for (int d = 0; d < 2; ++d) {
+    float2 a0, a1;
+    upsample_h(flw[d], sw, ry.sy, ry.sy1, x + left, inv, scf, scale, a0, a1);
+    val[d] = up_mix(a0, a1, ry.fy);
+  }
+  const size_t o = ((size_t)f * ho + y) * wo + x;
+  if (out_fw) __builtin_nontemporal_store((f2n){val[0].x, val[0].y}, reinterpret_cast<f2n*>(out_fw + o));
+  if (out_rev) __builtin_nontemporal_store((f2n){val[1].x, val[1].y}, reinterpret_cast<f2n*>(out_rev + o));
+  uint8_t* masks[2] = {mask_fw, mask_rev};
+#pragma unroll
+  for (int d = 0; d < 2; ++d) {
+    if (!masks[d]) continue;
+    const float2* oth = flw[1 - d];
+    masks[d][o] = fb_code(val[d].x, val[d].y, x, y, wo, ho, alpha, beta,
+                          [&](int x0, int x1, int y0, int y1, float2& r00, float2& r01, float2& r10, float2& r11) {
+                            const UpRow q0 = up_row(y0 + top, sh, inv), q1 = up_row(y1 + top, sh, inv);
+                            float2 p0, p1, n0, n1;  // row pair of y0 at columns x0 and x1
+                            upsample_h(oth, sw, q0.sy, q0.sy1, x0 + left, inv, scf, scale, p0, p1);
+                            upsample_h(oth, sw, q0.sy, q0.sy1, x1 + left, inv, scf, scale, n0, n1);
+                            r00 = up_mix(p0, p1, q0.fy);
+                            r01 = up_mix(n0, n1, q0.fy);
+                            if (q1.sy != q0.sy) {  // (sy1 is a function of sy)
+                              upsample_h(oth, sw, q1.sy, q1.sy1, x0 + left, inv, scf, scale, p0, p1);
+                              upsample_h(oth, sw, q1.sy, q1.sy1, x1 + left, inv, scf, scale, n0, n1);
+                            }
+                            r10 = up_mix(p0, p1, q1.fy);
+                            r11 = up_mix(n0, n1, q1.fy);
+                          });
+  }
+}
+
+hipError_t launch_upsample_bidir(const float* fw, const float* rev, float* out_fw, float* out_rev, uint8_t* mask_fw,
+                                 uint8_t* mask_rev, int nframes, int sw, int sh, int sc_l, int left, int top, int wo, int ho,
+                                 float alpha, float beta, hipStream_t s) {
+  if (ho > 65535 || nframes > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(upsample_bidir_kernel, dim3((wo + 255) / 256, ho, nframes), dim3(256), 0, s, (const float2*)fw,
+                     (const float2*)rev, (float2*)out_fw, (float2*)out_rev, mask_fw, mask_rev, sw, sh, sc_l, left, top, wo, ho,
+                     alpha, beta);
+  return hipGetLastError();
+}
+
 }  // namespace ofdis

@@ -3,10 +3,13 @@ run_DE_* binaries do (run_dense.cpp:185-431), for a list of pairs at once and wi
 8-bit frames, pad + pyramid + Sobel on the device, the hot path, x 2^lv_l upsample + crop on the device, write Middlebury .flo
 (.pfm with --stereo).
 
-    python tools/flow_images.py [--rgb] [--stereo] [--op 1..4] [--fused] img1a img1b out1.flo [img2a img2b out2.flo ...]
+    python tools/flow_images.py [--rgb] [--stereo] [--op 1..4] [--fused] [--reverse] img1a img1b out1.flo [img2a img2b out2.flo ...]
 
 All pairs must have one size.  --fused selects the FMA / fast-reciprocal arithmetic contract (default: the exact one, bit for
-bit what run_OF_INT / run_OF_RGB write)."""
+bit what run_OF_INT / run_OF_RGB write).  --reverse (optical flow only) also writes, next to <stem>.flo, the reverse flow
+<stem>.rev.flo (second image to first) and the forward-backward consistency masks <stem>.mask.pgm / <stem>.rev.mask.pgm
+(binary PGM, maxval 2, the raw codes: 0 consistent, 1 inconsistent, 2 target outside the image; ofdis_batch_upsample_bidir
+with the default alpha 0.01 and beta 0.5)."""
 import os
 import struct
 import sys
@@ -47,8 +50,15 @@ def write_pfm(path, disp):  # run_dense.cpp:60-81: rows bottom-up, values negate
         f.write(np.ascontiguousarray(-disp[::-1], np.float32).tobytes())
 
 
+def write_pgm(path, mask):
+    h, w = mask.shape
+    with open(path, "wb") as f:
+        f.write(b"P5\n%d %d\n2\n" % (w, h))
+        f.write(np.ascontiguousarray(mask, np.uint8).tobytes())
+
+
 def main(argv):
-    opts = {"--rgb": False, "--stereo": False, "--fused": False}
+    opts = {"--rgb": False, "--stereo": False, "--fused": False, "--reverse": False}
     op = 2
     args = []
     it = iter(argv)
@@ -61,6 +71,8 @@ def main(argv):
             args.append(a)
     if not args or len(args) % 3:
         sys.exit(__doc__)
+    if opts["--reverse"] and opts["--stereo"]:
+        sys.exit("--reverse: there is no reverse direction in stereo mode")
     noc = 3 if opts["--rgb"] else 1
     trip = [args[k:k + 3] for k in range(0, len(args), 3)]
     frames_a = [load(t[0], noc) for t in trip]
@@ -71,11 +83,14 @@ def main(argv):
     capi.set_tuning(contract=1 if opts["--fused"] else 0)
     p = oppoint(op, w, h, noc=noc).copy(selectmode=2 if opts["--stereo"] else 1)
     p.width, p.height = padded_size(w, h, p.sc_f)
-    b = capi.Batch(p, len(trip))
+    b = capi.Batch(p, len(trip), reverse=opts["--reverse"])
     da, db = capi.Dev(np.stack(frames_a)), capi.Dev(np.stack(frames_b))
     b.build_pyramids_u8(da.ptr, db.ptr, w, h)
     b.run()
-    full = b.upsample(w, h)          # [pairs][h][w][2] (one channel in stereo mode)
+    if opts["--reverse"]:            # both directions and both masks in one launch; the forward flow is upsample()'s
+        full, rev, mask_fw, mask_rev = b.upsample_bidir(w, h)
+    else:
+        full = b.upsample(w, h)      # [pairs][h][w][2] (one channel in stereo mode)
     b.close()
     da.free()
     db.free()
@@ -86,6 +101,14 @@ def main(argv):
             write_flo(t[2], f)
         mag = np.sqrt((f.astype(np.float64) ** 2).sum(-1))
         print(f"{t[2]}: {w}x{h}, mean |flow| {mag.mean():.3f} px, max {mag.max():.2f}")
+    if opts["--reverse"]:
+        for k, t in enumerate(trip):
+            stem = t[2][:-4] if t[2].endswith(".flo") else t[2]
+            write_flo(stem + ".rev.flo", rev[k])
+            write_pgm(stem + ".mask.pgm", mask_fw[k])
+            write_pgm(stem + ".rev.mask.pgm", mask_rev[k])
+            print(f"{stem}.rev.flo, .mask.pgm, .rev.mask.pgm: consistent {np.mean(mask_fw[k] == 0):.3f} / "
+                  f"{np.mean(mask_rev[k] == 0):.3f} of the pixels")
 
 
 if __name__ == "__main__":
