@@ -175,6 +175,50 @@ int ofdis_batch_upsample_bidir(ofdis_batch* b, int first_frame, int count, float
 int ofdis_fb_check(const float* flow, const float* flow_other, uint8_t* mask, int nframes, int width, int height,
                    float alpha, float beta, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Frame interpolation from bidirectional flow with occlusion masks.
+ *
+ * Inputs per frame pair k: 8-bit frames A, B of size W x H x noc (noc 1 or 3, channels interleaved, BGR as the binaries use
+ * it); full-resolution flows F01 (A -> B) and F10 (B -> A), each [H][W][2] fp32; optionally the masks M01 and M10
+ * (OFDIS_FB_* codes); times t_0 ... t_{n-1}.  For every output pixel (x, y) and time t, every operation is a separately
+ * rounded fp32 operation in this order:
+ *   (u0,v0) = F01[y][x]      (u1,v1) = F10[y][x]
+ *   s = 1 - t;  a = s * t;  tt = t * t;  ss = s * s
+ *   ft0x = tt*u1 - a*u0;  ft0y = tt*v1 - a*v0          (flow t -> 0, Jiang et al., "Super SloMo", CVPR 2018, eq. 4)
+ *   ft1x = ss*u0 - a*u1;  ft1y = ss*v0 - a*v1          (flow t -> 1)
+ *   p0 = ((float)x + ft0x, (float)y + ft0y);  p1 = ((float)x + ft1x, (float)y + ft1y)
+ *   sample(I, p): pxc = fminf(fmaxf(px, 0), W-1), pyc likewise (IEEE fmin/fmax: NaN -> the other operand)
+ *       x0 = min((int)floorf(pxc), W-2), ax = pxc - x0   (x0 = 0, ax = 0 when W == 1); y0, ay likewise; x1 = min(x0+1, W-1)
+ *       c = (I[y0][x0]*(1-ax) + I[y0][x1]*ax) * (1-ay) + (I[y1][x0]*(1-ax) + I[y1][x1]*ax) * ay      per channel, taps as float
+ *       (fb_code's expression in of_dis_amd/csrc/ofdis_upsample.h, with bx = 1-ax, by = 1-ay computed once)
+ *   c0 = sample(A, p0);  c1 = sample(B, p1)
+ *   inside(p) = 0 <= px <= W-1 and 0 <= py <= H-1, on the unclamped p (NaN: false)
+ *   near(p)   = (min((int)floorf(pxc + 0.5f), W-1), min((int)floorf(pyc + 0.5f), H-1))
+ *   v0 = inside(p0) and M01[near(p0)] == OFDIS_FB_CONSISTENT;  v1 = inside(p1) and M10[near(p1)] == OFDIS_FB_CONSISTENT
+ *        (a NULL mask counts as all consistent)
+ *   (w0, w1) = (s, t) if v0 == v1;  (1, 0) if v0 only and t < 1, else (0, 1);  (0, 1) if v1 only and t > 0, else (1, 0)
+ *   out = (uint8) clamp((int)floorf((w0*c0 + w1*c1) + 0.5f), 0, 255)
+ * For finite flows, t = 0 returns A and t = 1 returns B bit for bit.
+ * ------------------------------------------------------------------------------------------- */
+#define OFDIS_INTERP_MAX_TIMES 16
+/* device arrays: img_a, img_b [nframes][height][width][noc] u8; flow_fw, flow_rev [nframes][height][width][2] f32;
+ * mask_fw, mask_rev [nframes][height][width] u8 or NULL; out [nframes][ntimes][height][width][noc] u8.
+ * times: HOST array of ntimes values (copied into the launch).  Independent of the arithmetic contract.
+ * OFDIS_ERR_INVALID before any device work: a NULL frame, flow, out or times pointer; ntimes outside
+ * 1..OFDIS_INTERP_MAX_TIMES; a time that is not finite or lies outside [0, 1]; noc not 1 or 3; sizes as ofdis_fb_check. */
+int ofdis_interpolate(const uint8_t* img_a, const uint8_t* img_b, const float* flow_fw, const float* flow_rev,
+                      const uint8_t* mask_fw, const uint8_t* mask_rev, uint8_t* out, int nframes, int width, int height,
+                      int noc, const float* times, int ntimes, void* stream);
+/* OFDIS_BATCH_REVERSE contexts: frames [first_frame, first_frame+count) of the context, straight from its level flows.
+ * img_a / img_b are the whole [nframes][height_org][width_org][noc] arrays given to ofdis_batch_build_pyramids_u8.
+ * out = [count][ntimes][height_org][width_org][noc].  Bit-identical to ofdis_interpolate applied to the four outputs
+ * of ofdis_batch_upsample_bidir(b, first_frame, count, ..., alpha, beta).  Joins a pipelined pass by itself.
+ * OFDIS_ERR_INVALID as ofdis_interpolate, and for a context created without OFDIS_BATCH_REVERSE, a frame range outside the
+ * batch, an original size above the padded size, and alpha / beta as ofdis_fb_check rejects them. */
+int ofdis_batch_interpolate(ofdis_batch* b, const uint8_t* img_a, const uint8_t* img_b, int first_frame, int count,
+                            const float* times, int ntimes, uint8_t* out, int width_org, int height_org,
+                            float alpha, float beta, void* stream);
+
 /* device pointers to the context-owned input planes of level l: kind 0 = image A, 1 = A_dx,
  * 2 = A_dy, 3 = image B (with usefbcon also 4 = B_dx, 5 = B_dy).  The caller fills them (hipMemcpy, its own kernels, ofdis_batch_upload
  * or ofdis_batch_build_pyramids_u8). */

@@ -37,10 +37,12 @@ ABI_SYMBOLS = [
     "ofdis_event_create", "ofdis_event_destroy", "ofdis_event_record", "ofdis_stream_wait_event", "ofdis_event_sync",
     "ofdis_batch_create_ex", "ofdis_batch_flow_reverse", "ofdis_batch_level_flow_reverse", "ofdis_batch_set_initflow_reverse",
     "ofdis_batch_download_reverse", "ofdis_batch_upsample_bidir", "ofdis_fb_check",
+    "ofdis_interpolate", "ofdis_batch_interpolate",
 ]
 BATCH_REVERSE = 1  # include/ofdis.h: OFDIS_BATCH_REVERSE
 FB_ALPHA, FB_BETA = 0.01, 0.5  # OFDIS_FB_ALPHA / OFDIS_FB_BETA
 FB_CONSISTENT, FB_INCONSISTENT, FB_OUTSIDE = 0, 1, 2
+INTERP_MAX_TIMES = 16  # OFDIS_INTERP_MAX_TIMES
 OFDIS_VERSION = 3  # include/ofdis.h: the struct layouts below (OfdisTuning: 20 ints) belong to this ABI version
 
 
@@ -144,6 +146,9 @@ def lib():
         L.ofdis_batch_download_reverse.argtypes = [VP, C.c_int, FP, VP]
         L.ofdis_batch_upsample_bidir.argtypes = [VP, C.c_int, C.c_int, VP, VP, VP, VP, C.c_int, C.c_int, C.c_float, C.c_float, VP]
         L.ofdis_fb_check.argtypes = [VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, VP]
+        L.ofdis_interpolate.argtypes = [VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, FP, C.c_int, VP]
+        L.ofdis_batch_interpolate.argtypes = [VP, VP, VP, C.c_int, C.c_int, FP, C.c_int, VP, C.c_int, C.c_int, C.c_float,
+                                              C.c_float, VP]
         _lib = L
     return _lib
 
@@ -406,6 +411,39 @@ def fb_check(flow, other, alpha=FB_ALPHA, beta=FB_BETA):
     return dm.get(flow.shape[:-1], np.uint8)
 
 
+def _times(times):
+    t = np.ascontiguousarray(np.atleast_1d(np.asarray(times, _f32)).ravel())
+    return t, t.ctypes.data_as(FP)
+
+
+def interpolate(img_a, img_b, flow_fw, flow_rev, times, mask_fw=None, mask_rev=None):
+    """ofdis_interpolate on the device: frames img_a, img_b uint8 [..., h, w] (gray) or [..., h, w, 3]; flows [..., h, w, 2]
+    float32 (A -> B and B -> A); masks uint8 [..., h, w] or None (all consistent); times: a sequence of 1..INTERP_MAX_TIMES
+    values in [0, 1].  Returns uint8 [..., len(times), h, w] (+ [3]); the leading axes are frames."""
+    flow_fw, flow_rev = _f(flow_fw), _f(flow_rev)
+    assert flow_fw.shape == flow_rev.shape and flow_fw.ndim >= 3 and flow_fw.shape[-1] == 2, (flow_fw.shape, flow_rev.shape)
+    lead, (h, w) = flow_fw.shape[:-3], flow_fw.shape[-3:-1]
+    img_a, img_b = np.ascontiguousarray(img_a, np.uint8), np.ascontiguousarray(img_b, np.uint8)
+    assert img_a.shape == img_b.shape, (img_a.shape, img_b.shape)
+    noc = 1 if img_a.shape == flow_fw.shape[:-1] else 3
+    assert img_a.shape == flow_fw.shape[:-1] + ((3,) if noc == 3 else ()), (img_a.shape, flow_fw.shape)
+    n = int(np.prod(lead, dtype=np.int64))
+    t, tp = _times(times)
+    devs = [Dev(x) for x in (img_a, img_b, flow_fw, flow_rev)]
+    masks = []
+    for m in (mask_fw, mask_rev):
+        if m is not None:
+            m = np.ascontiguousarray(m, np.uint8)
+            assert m.shape == flow_fw.shape[:-1], (m.shape, flow_fw.shape)
+        masks.append(Dev(m) if m is not None else None)
+    shape = lead + (t.size, h, w) + ((3,) if noc == 3 else ())
+    do = Dev(nbytes=max(1, int(np.prod(shape, dtype=np.int64))))
+    check(lib().ofdis_interpolate(*[d.ptr for d in devs], *[m.ptr if m else None for m in masks], do.ptr, n, w, h, noc, tp,
+                                  t.size, None))
+    check(lib().ofdis_sync(None))
+    return do.get(shape, np.uint8)
+
+
 class Batch:
     """ofdis_batch: `nframes` frame pairs of one geometry resident in HBM.  reverse=True: ofdis_batch_create_ex with
     OFDIS_BATCH_REVERSE (every pass also computes the flow B -> A of each pair)."""
@@ -566,6 +604,25 @@ class Batch:
                                                height_org, alpha, beta, stream))
         check(lib().ofdis_sync(stream))
         return tuple(d.get(s, t) if d else None for d, s, t in zip(devs, shapes, dtypes))
+
+    def interpolate(self, img_a_ptr, img_b_ptr, width_org, height_org, times, first=0, count=None, alpha=FB_ALPHA,
+                    beta=FB_BETA, out_ptr=None, stream=None):
+        """ofdis_batch_interpolate over frames [first, first + count): img_a_ptr / img_b_ptr are the whole device arrays given
+        to build_pyramids_u8.  out_ptr None: returns the host array [count][len(times)][height_org][width_org] (+ [noc]
+        for RGB); else writes the device array out_ptr on `stream` and returns None."""
+        count = self.nframes - first if count is None else count
+        t, tp = _times(times)
+        shape = (count, t.size, height_org, width_org) + ((self.p.noc,) if self.p.noc > 1 else ())
+        d = None
+        if out_ptr is None:
+            d = Dev(nbytes=max(1, int(np.prod(shape, dtype=np.int64))))
+            out_ptr = d.ptr
+        check(lib().ofdis_batch_interpolate(self.h, img_a_ptr, img_b_ptr, first, count, tp, t.size, out_ptr, width_org,
+                                            height_org, alpha, beta, stream))
+        if d is None:
+            return None
+        check(lib().ofdis_sync(stream))
+        return d.get(shape, np.uint8)
 
     def timing(self, enable=True):
         check(lib().ofdis_batch_timing(self.h, int(enable)))

@@ -183,6 +183,19 @@ hipError_t launch_fb_check(const float* flow, const float* other, uint8_t* mask,
 hipError_t launch_upsample_bidir(const float* fw, const float* rev, float* out_fw, float* out_rev, uint8_t* mask_fw,
                                  uint8_t* mask_rev, int nframes, int sw, int sh, int sc_l, int left, int top, int wo, int ho,
                                  float alpha, float beta, hipStream_t s);
+// frame interpolation (include/ofdis.h: ofdis_interpolate; ofdis_interp.hip).  The times travel by value in the launch.
+struct InterpTimes {
+  float t[16];  // OFDIS_INTERP_MAX_TIMES
+  int n;
+};
+// on materialised arrays: frames [n][h][w][noc] u8, AoS flows [n][h][w][2], masks [n][h][w] or null, out [n][ts.n][h][w][noc]
+hipError_t launch_interp_frames(const uint8_t* img_a, const uint8_t* img_b, const float* flow_fw, const float* flow_rev,
+                                const uint8_t* mask_fw, const uint8_t* mask_rev, uint8_t* out, int nframes, int w, int h,
+                                int noc, const InterpTimes& ts, hipStream_t s);
+// straight from both directions' level flows (ofdis_batch_interpolate): flows and masks as launch_upsample_bidir computes them
+hipError_t launch_interp_bidir(const uint8_t* img_a, const uint8_t* img_b, const float* fw, const float* rev, uint8_t* out,
+                               int nframes, int sw, int sh, int sc_l, int left, int top, int wo, int ho, int noc,
+                               const InterpTimes& ts, float alpha, float beta, hipStream_t s);
 
 // ---- stereo-depth mode (SELECTMODE=2; ofdis_de.hip)
 struct DeSystemArgs {
