@@ -21,9 +21,9 @@ ROOT = os.path.dirname(HERE)
 # order, include/ofdis.h) and the C ABI are compiled once.
 KERNEL_SOURCES = ["ofdis_dis.hip", "ofdis_tv.hip", "ofdis_prep.hip", "ofdis_sor.hip", "ofdis_fused.hip", "ofdis_fused_xcu.hip",
                   "ofdis_fused_tall.hip", "ofdis_de.hip"]
-COMMON_SOURCES = ["ofdis_pyr.hip", "ofdis_interp.hip", "ofdis_capi.hip"]
+COMMON_SOURCES = ["ofdis_pyr.hip", "ofdis_interp.hip", "ofdis_context.hip", "ofdis_schedule.hip", "ofdis_capi.hip"]
 HIP_SOURCES = KERNEL_SOURCES + COMMON_SOURCES
-# -fvisibility=hidden: the shared library exports the C ABI of include/ofdis.h (marked in ofdis_capi.hip) and nothing else.
+# -fvisibility=hidden: the shared library exports the C ABI of include/ofdis.h (marked in ofdis_context.h) and nothing else.
 BASEFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
              "-Wall", "-Wno-unused-function", "-Wno-bitwise-instead-of-logical"]
 # exact: -ffp-contract=off, every fp32 operation separately rounded, like the reference's SSE path (bit-identical results).

@@ -1,0 +1,607 @@
+// ofdis_context.hip -- the batch context's own half of the C ABI of include/ofdis.h: kernel-selection knobs, parameter
+// handling, the context's device memory (array descriptions, frame views), creation, inputs and result accessors.
+#include <cmath>
+
+#include "ofdis_context.h"
+
+using namespace ofdis;
+
+namespace ofdis {
+
+#define OFDIS_LAUNCHER_TABLE(ns)                                                                                        \
+  {ns::launch_patch_optimize, ns::patch_pixel_weights_supported, ns::launch_densify, ns::launch_patch_p_reference_order, ns::launch_warp, ns::launch_derivatives, ns::tv_prep_supported, ns::tv_prep_densifies,      \
+   ns::launch_tv_prep, ns::launch_tv_system, ns::launch_sor, ns::tv_fused_supported, ns::tv_fused_params_ok,            \
+   ns::tv_fused_mode, ns::launch_tv_fused, ns::launch_tv_finish_records, ns::launch_to_diag, ns::launch_from_diag,      \
+   ns::launch_tv_finish, ns::launch_flow_split, ns::launch_de_system, ns::launch_de_sor, ns::launch_de_update,          \
+   ns::de_fused_supported, ns::launch_de_fused}
+const Launchers kExactLaunchers = OFDIS_LAUNCHER_TABLE(exact);
+const Launchers kFusedLaunchers = OFDIS_LAUNCHER_TABLE(fused);
+#undef OFDIS_LAUNCHER_TABLE
+const Launchers& launchers(int contract) { return contract ? kFusedLaunchers : kExactLaunchers; }
+
+// Kernel-selection knobs (include/ofdis.h: ofdis_tuning): read ONCE from the environment, changed only through
+// ofdis_set_tuning; every launch path takes a snapshot (no getenv on the dispatch path).
+static std::mutex g_tuning_mutex;
+static ofdis_tuning g_tuning;
+static bool g_tuning_init = false;
+static unsigned g_tuning_epoch = 0;
+static void tuning_init_locked() {
+  if (g_tuning_init) return;
+  auto on = [](const char* name) { return getenv(name) != nullptr; };
+  auto num = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+  g_tuning.gray8 = !on("OFDIS_NO_GRAY8");
+  g_tuning.rgb12 = !on("OFDIS_NO_RGB12");
+  {
+    const int l = num("OFDIS_RGB12_LPP", 0);
+    g_tuning.rgb12_lpp = (l == 16 || l == 32 || l == 64) ? l : 0;
+  }
+  g_tuning.fused_tv = !on("OFDIS_NO_FUSED");
+  g_tuning.fused_mw_max = std::max(0, num("OFDIS_FUSED_MW_MAX", 512));
+  g_tuning.fused_split = !on("OFDIS_FUSED_NO_SPLIT");
+  g_tuning.finish_fusion = !on("OFDIS_NO_FINISH_FUSION");
+  g_tuning.fused_strip = std::max(0, num("OFDIS_FUSED_STRIP", 0));
+  g_tuning.prep_band_rows = std::max(0, num("OFDIS_PREP_BAND_ROWS", 0));
+  g_tuning.graph = !on("OFDIS_NO_GRAPH");
+  g_tuning.flow_dma = on("OFDIS_FLOW_DMA");
+  g_tuning.flow_whole = on("OFDIS_FLOW_WHOLE");
+  g_tuning.fused_xcu_max = std::max(0, num("OFDIS_FUSED_XCU_MAX", 768));
+  g_tuning.fused_tp_pipe = std::max(0, std::min(2, num("OFDIS_FUSED_TP_PIPE", 1)));
+  g_tuning.fused_xcu_spin = std::max(0, num("OFDIS_FUSED_XCU_SPIN", 0));
+  g_tuning.fused_xcu_drop = num("OFDIS_FUSED_XCU_DROP", 0) != 0;  // test hook
+  g_tuning.prep_densify = !on("OFDIS_NO_PREP_DENSIFY");
+  g_tuning.fused_tall_group = on("OFDIS_NO_TALL_GROUP") ? 0 : std::max(1, std::min(7, num("OFDIS_TALL_GROUP", 1)));
+  g_tuning.fused_rgb_min = std::max(0, num("OFDIS_FUSED_RGB_MIN", 0));
+  {  // arithmetic contract: "fused" / "1" = the tolerance contract, anything else (or unset) = exact
+    const char* e = getenv("OFDIS_CONTRACT");
+    g_tuning.contract = (e && (!strcmp(e, "fused") || !strcmp(e, "1"))) ? 1 : 0;
+  }
+  g_tuning_init = true;
+}
+
+ofdis_tuning tuning(unsigned* epoch) {
+  std::lock_guard<std::mutex> lock(g_tuning_mutex);
+  tuning_init_locked();
+  if (epoch) *epoch = g_tuning_epoch;
+  return g_tuning;
+}
+
+static thread_local std::string g_err;
+
+int fail(int code, const std::string& msg) {
+  g_err = msg;
+  return code;
+}
+int hipfail(hipError_t e, const char* what) {
+  g_err = std::string(what) + ": " + hipGetErrorString(e);
+  return OFDIS_ERR_DEVICE;
+}
+
+// Level geometry exactly as the reference derives it (oflow.cpp:91-92,138-151; patchgrid.cpp:42-48).
+LevelGeom make_geom(const ofdis_params& p, int sl) {
+  LevelGeom g;
+  memset(&g, 0, sizeof(g));
+  const float sc_fct = (float)pow(2, -sl);
+  g.level = sl;
+  g.h = (int)(p.height * sc_fct);
+  g.w = (int)(p.width * sc_fct);
+  g.pad = p.imgpadding;
+  g.noc = p.noc;
+  g.P = p.p_samp_s;
+  g.lb = -(float)p.p_samp_s / 2;
+  g.ubw = (float)(g.w + p.p_samp_s / 2 - 2);
+  g.ubh = (float)(g.h + p.p_samp_s / 2 - 2);
+  g.tmp_w = g.w + 2 * g.pad;
+  g.tmp_h = g.h + 2 * g.pad;
+  int steps = (int)floor(p.p_samp_s * (1 - p.patove));
+  g.steps = steps < 1 ? 1 : steps;
+  g.steps_magic = g.steps > 1 ? (unsigned)((0x100000000ull + (unsigned)g.steps - 1) / (unsigned)g.steps) : 0u;
+  g.novals = p.noc * p.p_samp_s * p.p_samp_s;
+  g.nopw = (int)ceil((float)g.w / (float)g.steps);
+  g.noph = (int)ceil((float)g.h / (float)g.steps);
+  g.offw = (int)floor((g.w - (g.nopw - 1) * g.steps) / 2);
+  g.offh = (int)floor((g.h - (g.noph - 1) * g.steps) / 2);
+  g.nop = g.nopw * g.noph;
+  g.plane_elems = (size_t)g.tmp_w * g.tmp_h * g.noc;
+  return g;
+}
+
+int check_params(const ofdis_params* p) {
+  if (!p) return fail(OFDIS_ERR_INVALID, "params is NULL");
+  if (p->noc != 1 && p->noc != 3) return fail(OFDIS_ERR_INVALID, "noc must be 1 or 3");
+  if (p->sc_l < 0 || p->sc_f < p->sc_l || p->sc_f > 20) return fail(OFDIS_ERR_INVALID, "need 0 <= sc_l <= sc_f");
+  if (p->width <= 0 || p->height <= 0 || (p->width % (1 << p->sc_f)) || (p->height % (1 << p->sc_f)))
+    return fail(OFDIS_ERR_INVALID, "width/height must be positive multiples of 2^sc_f (oflow.h:87)");
+  if ((p->width >> p->sc_l) > 32768 || (p->height >> p->sc_l) > 32768)
+    return fail(OFDIS_ERR_UNSUPPORTED, "finest level larger than 32768 pixels in one dimension");
+  if (p->p_samp_s < 2 || (p->p_samp_s & 1)) return fail(OFDIS_ERR_INVALID, "p_samp_s must be even and >= 2");
+  if (p->imgpadding < p->p_samp_s) return fail(OFDIS_ERR_INVALID, "imgpadding must be >= p_samp_s (oflow.cpp:147-149)");
+  if (p->noc * p->p_samp_s * p->p_samp_s > 64 * 12) return fail(OFDIS_ERR_UNSUPPORTED, "patch too large (novals > 768)");
+  if (p->costfct < 0 || p->costfct > 2) return fail(OFDIS_ERR_UNSUPPORTED, "costfct must be 0, 1 or 2");
+  if (!(p->patove >= 0.0f && p->patove < 1.0f)) return fail(OFDIS_ERR_INVALID, "patove must be in [0,1)");
+  if (p->usetvref && ((p->height >> p->sc_f) < 4))
+    return fail(OFDIS_ERR_INVALID, "coarsest level must have >= 4 rows for the TV derivative filter (image.c:401-434)");
+  if (p->max_iter < 0 || p->tv_innerit < 0 || p->tv_solverit < 0) return fail(OFDIS_ERR_INVALID, "negative iteration count");
+  if (p->selectmode < 0 || p->selectmode > 2) return fail(OFDIS_ERR_INVALID, "selectmode must be 0/1 (optical flow) or 2 (stereo depth)");
+  return OFDIS_OK;
+}
+
+// What create turns (params, frame count, knob snapshot) into before any memory is requested: contract, launchers, frame
+// counts, flow channels and the geometry of levels first_level .. last_level (a whole context: sc_l .. sc_f).
+void context_init(ofdis_batch* b, const ofdis_params& p, int nframes, const ofdis_tuning& tn, int first_level, int last_level) {
+  b->p = p;
+  b->contract = tn.contract ? 1 : 0;
+  b->k = &launchers(b->contract);
+  b->nframes = b->total_frames = nframes;
+  b->nlevels = last_level - first_level + 1;
+  b->nop = p.selectmode == 2 ? 1 : 2;
+  for (int l = first_level; l <= last_level; ++l) b->geom.push_back(make_geom(p, l));
+}
+
+static float*& member(const ofdis_batch& b, const ofdis_batch::Array& a) { return *(float**)((char*)&b + a.slot); }
+static size_t array_bytes(const ofdis_batch& b, const ofdis_batch::Array& a) {
+  const size_t elems = a.per_frame * b.nframes;
+  return ((elems ? elems : 1) * sizeof(float) + 255) & ~(size_t)255;
+}
+
+// THE description of a device array: `per_frame` floats for each of the context's frames, at `slot` (a float* member of *b).
+void dalloc(ofdis_batch* b, float** slot, size_t per_frame, bool view) {
+  *slot = nullptr;
+  b->arrays.push_back({(size_t)((char*)slot - (char*)b), per_frame, view});
+}
+// Test hook OFDIS_POISON_SCRATCH=1: fresh device memory holds NaN patterns instead of zeros.  Read at every allocation (never
+// on a launch path): the tests switch it while the library is loaded.
+static int scratch_fill_byte() {
+  const char* poison = getenv("OFDIS_POISON_SCRATCH");
+  return (poison && poison[0] == '1') ? 0xFF : 0;
+}
+int dcommit(ofdis_batch* b) {
+  size_t total = 0;
+  for (size_t i = b->committed; i < b->arrays.size(); ++i) total += array_bytes(*b, b->arrays[i]);
+  if (!total) return OFDIS_OK;
+  void* d = nullptr;
+  hipError_t e = hipMalloc(&d, total);
+  if (e == hipSuccess) {
+    b->allocs.push_back(d);
+    // Every context starts from zeroed scratch: no result may depend on what an allocation held before.  (Poisoned: the GPU
+    // tests run whole flows and single levels that way and expect the same bits, i.e. nothing is read before it is written
+    // except where zero is the defined initial value.)
+    e = hipMemsetAsync(d, scratch_fill_byte(), total, nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+  }
+  if (e != hipSuccess) {
+    b->arrays.resize(b->committed);  // (their members are null)
+    return hipfail(e, d ? "hipMemset" : "hipMalloc");
+  }
+  char* c = (char*)d;
+  for (; b->committed < b->arrays.size(); ++b->committed) {
+    member(*b, b->arrays[b->committed]) = (float*)c;
+    c += array_bytes(*b, b->arrays[b->committed]);
+  }
+  return OFDIS_OK;
+}
+// the TV scratch of `sc`: requests, which dcommit serves (or fails)
+void dalloc_tv_scratch(ofdis_batch* b, const Scratch& sc) {
+  const size_t npx = (size_t)b->geom[0].w * b->geom[0].h, noc = b->p.noc;
+  if (sc.planes) {
+    dalloc(b, &b->wx, npx); dalloc(b, &b->wy, npx); dalloc(b, &b->du, npx); dalloc(b, &b->dv, npx);
+    dalloc(b, &b->mask, npx); dalloc(b, &b->w_im2, npx * noc); dalloc(b, &b->sys, npx * 7);
+  }
+  dalloc(b, &b->derivs, npx * 8 * noc);
+  b->rec_px = sc.rec_px;
+  if (sc.rec_px) dalloc(b, &b->wrec, sc.rec_px * 2);
+  if (sc.rec_px && sc.uv) dalloc(b, &b->uv, sc.rec_px * 2);
+  if (sc.xbuf_per_frame) dalloc(b, &b->xbuf, sc.xbuf_per_frame);
+}
+
+size_t frame_elems(const ofdis_batch& b, float* const& slot) {
+  const size_t off = (size_t)((const char*)&slot - (const char*)&b);
+  for (const ofdis_batch::Array& a : b.arrays)
+    if (a.slot == off) return a.per_frame;
+  return 0;  // (never requested: the member is null)
+}
+float* frame_at(const ofdis_batch& b, float* const& slot, int f) {
+  return slot ? slot + (size_t)f * frame_elems(b, slot) : nullptr;
+}
+
+// A contiguous range of a batch's frames as a batch of its own: every array a view sees is advanced to frame f0 by its own
+// description, so a sub-batch gets exactly its share of every input, output and scratch array and the shares never overlap.
+// The view owns nothing.
+ofdis_batch frame_view(const ofdis_batch& b, int f0, int n) {
+  ofdis_batch v = b;
+  v.allocs.clear(); v.sub_streams.clear(); v.sub_done.clear();
+  v.timing = false;
+  v.nframes = n;
+  for (const ofdis_batch::Array& a : b.arrays) {
+    float*& ptr = member(v, a);
+    if (!a.view) ptr = nullptr;
+    else if (ptr) ptr += (size_t)f0 * a.per_frame;
+  }
+  if (v.initflow) v.initflow += (size_t)f0 * ofdis_batch_initflow_elems(&b);
+  if (v.initflow_rev) v.initflow_rev += (size_t)f0 * ofdis_batch_initflow_elems(&b);
+  return v;
+}
+
+std::mutex g_xcu_mutex;
+std::vector<ofdis_batch*> g_xcu_contexts;
+
+// The cross-CU variant's state of a context that owns granules (with the context, never on a launch path): their tags zeroed
+// on `s` (0 = not yet written; the kernel restores the zeros itself) and the error word.
+int xcu_arm(ofdis_batch* b, hipStream_t s) {
+  if (!b->xbuf) return OFDIS_OK;
+  HIPCHK(hipMemsetAsync(b->xbuf, 0, frame_elems(*b, b->xbuf) * b->nframes * sizeof(float), s));
+  void* h = nullptr;
+  void* d = nullptr;
+  HIPCHK(hipHostMalloc(&h, sizeof(int), hipHostMallocMapped | hipHostMallocPortable));
+  *(volatile int*)h = 0;
+  hipError_t e = hipHostGetDevicePointer(&d, h, 0);
+  if (e != hipSuccess) { (void)hipHostFree(h); return hipfail(e, "hipHostGetDevicePointer"); }
+  b->xcu = new XcuState();
+  b->xcu->host = (int*)h;
+  b->xcu->dev = (int*)d;
+  return OFDIS_OK;
+}
+
+void context_release(ofdis_batch* b) {
+  if (b->xcu) {
+    {
+      std::lock_guard<std::mutex> lock(g_xcu_mutex);
+      g_xcu_contexts.erase(std::remove(g_xcu_contexts.begin(), g_xcu_contexts.end(), b), g_xcu_contexts.end());
+    }
+    (void)hipHostFree(b->xcu->host);
+    delete b->xcu;
+    b->xcu = nullptr;
+  }
+  for (hipStream_t st : b->sub_streams) {
+    (void)hipStreamSynchronize(st);
+    (void)hipStreamDestroy(st);
+  }
+  for (hipEvent_t ev : b->sub_done) (void)hipEventDestroy(ev);
+  if (b->sub_start) (void)hipEventDestroy(b->sub_start);
+  if (b->graph_exec) (void)hipGraphExecDestroy(b->graph_exec);
+  if (b->cap_stream) (void)hipStreamDestroy(b->cap_stream);
+  for (void* d : b->allocs) (void)hipFree(d);
+  for (int k = 0; k < OFDIS_K_COUNT; ++k)
+    for (auto& e : b->ev[k]) {
+      (void)hipEventDestroy(e.a);
+      (void)hipEventDestroy(e.b);
+    }
+}
+
+// host pyramids src[0 .. nkinds) into frame `frame` of the input planes in[first_kind ..]
+static int upload_planes(ofdis_batch* b, int frame, int first_kind, int nkinds, const float* const* const* src, hipStream_t s) {
+  for (int l = b->p.sc_l; l <= b->p.sc_f; ++l)
+    for (int k = 0; k < nkinds; ++k) {
+      float* const& plane = b->in[first_kind + k][l - b->p.sc_l];
+      if (!src[k][l]) return fail(OFDIS_ERR_INVALID, "pyramid level pointer is NULL");
+      HIPCHK(hipMemcpyAsync(frame_at(*b, plane, frame), src[k][l], frame_elems(*b, plane) * sizeof(float), hipMemcpyHostToDevice, s));
+    }
+  return OFDIS_OK;
+}
+
+// the forward / reverse halves of the result accessors
+static const float* level_flow(const ofdis_batch& b, int level, bool reverse) {
+  if (level < b.p.sc_l || level > b.p.sc_f) return nullptr;
+  return (reverse ? b.flow_rev : b.flow)[level - b.p.sc_l];  // (flow_rev: null without OFDIS_BATCH_REVERSE)
+}
+static int download(ofdis_batch* b, int frame, float* outflow_host, hipStream_t s, bool reverse) {
+  float* const& flow = reverse ? b->flow_rev[0] : b->flow[0];
+  if (int rc = ofdis_batch_join(b, s)) return rc;
+  HIPCHK(hipMemcpyAsync(outflow_host, frame_at(*b, flow, frame), frame_elems(*b, flow) * sizeof(float), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return xcu_poll(b);
+}
+
+static bool fb_constants_ok(float alpha, float beta) {
+  return std::isfinite(alpha) && std::isfinite(beta) && alpha >= 0.0f && beta >= 0.0f;
+}
+
+static_assert(sizeof(InterpTimes::t) / sizeof(float) == OFDIS_INTERP_MAX_TIMES, "InterpTimes holds OFDIS_INTERP_MAX_TIMES");
+static int interp_times(const float* times, int ntimes, InterpTimes& ts) {
+  if (!times) return fail(OFDIS_ERR_INVALID, "times is NULL");
+  if (ntimes < 1 || ntimes > OFDIS_INTERP_MAX_TIMES) return fail(OFDIS_ERR_INVALID, "ntimes must be 1..OFDIS_INTERP_MAX_TIMES");
+  memset(&ts, 0, sizeof(ts));
+  for (int k = 0; k < ntimes; ++k) {
+    if (!(std::isfinite(times[k]) && times[k] >= 0.0f && times[k] <= 1.0f))
+      return fail(OFDIS_ERR_INVALID, "every time must be finite and inside [0, 1]");
+    ts.t[k] = times[k];
+  }
+  ts.n = ntimes;
+  return OFDIS_OK;
+}
+
+}  // namespace ofdis
+
+extern "C" {
+
+const char* ofdis_last_error(void) { return g_err.c_str(); }
+
+// ------------------------------------------------------------------------------------ kernel-selection knobs
+int ofdis_get_tuning(ofdis_tuning* out) {
+  if (!out) return fail(OFDIS_ERR_INVALID, "out is NULL");
+  *out = ofdis::tuning();
+  return OFDIS_OK;
+}
+int ofdis_set_tuning(const ofdis_tuning* in) {
+  if (!in) return fail(OFDIS_ERR_INVALID, "tuning is NULL");
+  if (in->rgb12_lpp != 0 && in->rgb12_lpp != 16 && in->rgb12_lpp != 32 && in->rgb12_lpp != 64)
+    return fail(OFDIS_ERR_INVALID, "rgb12_lpp must be 0 (library's choice), 16, 32 or 64");
+  if (in->fused_mw_max < 0 || in->fused_strip < 0 || in->prep_band_rows < 0 || in->fused_xcu_max < 0 || in->fused_xcu_spin < 0)
+    return fail(OFDIS_ERR_INVALID, "negative knob");
+  if (in->fused_strip > 64 || in->prep_band_rows > 64)  // (strips index their records with 32-bit byte offsets)
+    return fail(OFDIS_ERR_INVALID, "fused_strip / prep_band_rows must be <= 64");
+  if (in->fused_tp_pipe < 0 || in->fused_tp_pipe > 2) return fail(OFDIS_ERR_INVALID, "fused_tp_pipe must be 0, 1 or 2");
+  if (in->contract != 0 && in->contract != 1) return fail(OFDIS_ERR_INVALID, "contract must be 0 (exact) or 1 (fused)");
+  if (in->fused_xcu_spin > 30000000) return fail(OFDIS_ERR_INVALID, "fused_xcu_spin is a wait in microseconds, at most 30 s");
+  if (in->fused_xcu_drop != 0 && in->fused_xcu_drop != 1) return fail(OFDIS_ERR_INVALID, "fused_xcu_drop (test hook) must be 0 or 1");
+  if (in->prep_densify != 0 && in->prep_densify != 1) return fail(OFDIS_ERR_INVALID, "prep_densify must be 0 or 1");
+  if (in->fused_tall_group < 0 || in->fused_tall_group > 7) return fail(OFDIS_ERR_INVALID, "fused_tall_group must be 0 .. 7");
+  if (in->fused_rgb_min < 0) return fail(OFDIS_ERR_INVALID, "negative knob");
+  ofdis::tuning();  // initialise from the environment first
+  std::lock_guard<std::mutex> lock(ofdis::g_tuning_mutex);
+  ofdis::g_tuning = *in;
+  ++ofdis::g_tuning_epoch;
+  return OFDIS_OK;
+}
+
+// ------------------------------------------------------------------------------------ batch context
+int ofdis_batch_create(ofdis_batch** out, const ofdis_params* p, int nframes) { return ofdis_batch_create_ex(out, p, nframes, 0); }
+
+int ofdis_batch_create_ex(ofdis_batch** out, const ofdis_params* p, int nframes, unsigned flags) {
+  if (!out) return fail(OFDIS_ERR_INVALID, "out is NULL");
+  *out = nullptr;
+  int rc = check_params(p);
+  if (rc) return rc;
+  if (nframes < 1) return fail(OFDIS_ERR_INVALID, "nframes must be >= 1");
+  if (flags & ~OFDIS_BATCH_REVERSE) return fail(OFDIS_ERR_INVALID, "unknown flag bits");
+  const bool reverse = (flags & OFDIS_BATCH_REVERSE) != 0;
+  if (reverse && p->selectmode == 2)
+    return fail(OFDIS_ERR_UNSUPPORTED, "OFDIS_BATCH_REVERSE: no reverse direction in stereo-depth mode (selectmode 2)");
+  if (nframes > 65535)  // launch_warp / launch_upsample_crop carry the frame in grid.z
+    return fail(OFDIS_ERR_UNSUPPORTED, "at most 65535 frames per batch context");
+  ofdis_batch* b = new ofdis_batch();
+  const ofdis_tuning tn = tuning();  // ONE snapshot decides the contract and the scratch
+  context_init(b, *p, nframes, tn, p->sc_l, p->sc_f);
+  b->reverse = reverse;
+  const int nin = (p->usefbcon || reverse) ? 6 : 4;  // (the reverse pass reads B's gradients as its A's)
+  for (int i = 0; i < b->nlevels; ++i)  // the input planes first: one contiguous region in (level, kind) order
+    for (int k = 0; k < nin; ++k) dalloc(b, &b->in[k][i], b->geom[i].plane_elems);
+  for (const ofdis_batch::Array& a : b->arrays) b->in_bytes += array_bytes(*b, a);
+  for (int i = 0; i < b->nlevels; ++i) {
+    const size_t flow_elems = (size_t)b->geom[i].w * b->geom[i].h * b->nop;
+    dalloc(b, &b->flow[i], flow_elems);
+    if (reverse) dalloc(b, &b->flow_rev[i], flow_elems);
+    if (p->usefbcon && i > 0) dalloc(b, &b->flow_bw[i], flow_elems);
+  }
+  const LevelGeom& g0 = b->geom[0];  // finest level: largest of everything
+  size_t nop_max = 0;
+  for (auto& g : b->geom) nop_max = std::max(nop_max, (size_t)g.nop);
+  const Scratch sc = size_scratch(*b, tn);
+  dalloc(b, &b->pvec, nop_max * 2);
+  dalloc(b, &b->pweight, nop_max * g0.novals);
+  if (sc.pixw) dalloc(b, &b->pixw, nop_max * (size_t)g0.P * g0.P);
+  if (p->usefbcon) dalloc(b, &b->pvec_bw, nop_max * 2);
+  if (p->usefbcon) dalloc(b, &b->pweight_bw, nop_max * g0.novals);
+  if (p->usetvref) dalloc_tv_scratch(b, sc);
+  rc = dcommit(b);
+  if (!rc) b->in_base = (char*)b->in[0][0];
+  if (!rc) rc = xcu_arm(b, nullptr);
+  if (!rc && b->xcu) {
+    const hipError_t e = hipStreamSynchronize(nullptr);  // (the zeroing)
+    if (e != hipSuccess) rc = hipfail(e, "hipMemset");
+  }
+  if (!rc && b->xcu) {
+    std::lock_guard<std::mutex> lock(g_xcu_mutex);
+    g_xcu_contexts.push_back(b);
+  }
+  if (rc) {
+    ofdis_batch_destroy(b);
+    return rc == OFDIS_ERR_DEVICE ? OFDIS_ERR_NOMEM : rc;
+  }
+  *out = b;
+  return OFDIS_OK;
+}
+
+void ofdis_batch_destroy(ofdis_batch* b) {
+  if (b) context_release(b);
+  delete b;
+}
+
+float* ofdis_batch_input(ofdis_batch* b, int level, int kind) {
+  if (!b || level < b->p.sc_l || level > b->p.sc_f || kind < 0 || kind > ((b->p.usefbcon || b->reverse) ? 5 : 3)) return nullptr;
+  return b->in[kind][level - b->p.sc_l];
+}
+size_t ofdis_batch_input_elems(const ofdis_batch* b, int level) {
+  if (!b || level < b->p.sc_l || level > b->p.sc_f) return 0;
+  return b->g(level).plane_elems;
+}
+
+int ofdis_batch_upload(ofdis_batch* b, int frame, const float* const* im_a, const float* const* im_a_dx,
+                       const float* const* im_a_dy, const float* const* im_b, void* stream) {
+  if (!b || frame < 0 || frame >= b->nframes || !im_a || !im_a_dx || !im_a_dy || !im_b)
+    return fail(OFDIS_ERR_INVALID, "bad arguments");
+  const float* const* src[4] = {im_a, im_a_dx, im_a_dy, im_b};
+  return upload_planes(b, frame, 0, 4, src, (hipStream_t)stream);
+}
+
+int ofdis_batch_upload_b_gradients(ofdis_batch* b, int frame, const float* const* im_b_dx, const float* const* im_b_dy,
+                                   void* stream) {
+  if (!b || frame < 0 || frame >= b->nframes || !im_b_dx || !im_b_dy) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (!b->p.usefbcon && !b->reverse) return OFDIS_OK;  // never read (patch.cpp:90-97)
+  const float* const* src[2] = {im_b_dx, im_b_dy};
+  return upload_planes(b, frame, 4, 2, src, (hipStream_t)stream);
+}
+
+int ofdis_batch_build_pyramids_u8(ofdis_batch* b, const uint8_t* img_a, const uint8_t* img_b, int width_org,
+                                  int height_org, void* stream) {
+  if (!b || !img_a || !img_b) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  const ofdis_params& p = b->p;
+  // the padded size must be what run_dense.cpp:298-305 derives from the original size
+  const int sc = 1 << p.sc_f;
+  if (width_org < 1 || height_org < 1 || width_org > p.width || height_org > p.height || p.width - width_org >= sc ||
+      p.height - height_org >= sc)
+    return fail(OFDIS_ERR_INVALID, "params.width/height are not the 2^sc_f padding of the original size");
+  // level l images need 8+2l bits, the Sobel partial sums 10+2l: exact in fp32 up to l = 7 (ofdis_pyr.hip)
+  if (p.sc_f > 7) return fail(OFDIS_ERR_UNSUPPORTED, "exact fp32 pyramid needs sc_f <= 7");
+  hipStream_t s = (hipStream_t)stream;
+  if (!b->pyr_tmp[0]) {  // (a frame view never sees them)
+    for (int i = 0; i < b->nlevels; ++i) dalloc(b, &b->pyr_tmp[i], (size_t)b->geom[i].w * b->geom[i].h * b->geom[i].noc, false);
+    if (int rc = dcommit(b)) return rc;
+  }
+  for (int which = 0; which < 2; ++which) {
+    const uint8_t* src = which ? img_b : img_a;
+    HIPCHK(launch_pyr_base(src, b->pyr_tmp[0], b->nframes, width_org, height_org, p.width, p.height, p.noc, p.sc_l, s));
+    for (int i = 0; i < b->nlevels; ++i) {
+      const LevelGeom& g = b->geom[i];
+      // the planes of level i and, in the same launch where the geometry allows, the unpadded image of level i + 1
+      // (2x2 means: cv::resize(.5,.5), run_dense.cpp:150)
+      float* down = i + 1 < b->nlevels ? b->pyr_tmp[i + 1] : nullptr;
+      if (which == 0)
+        HIPCHK(launch_pyr_planes(b->pyr_tmp[i], b->in[0][i], b->in[1][i], b->in[2][i], b->nframes, g.w, g.h, p.noc, g.pad, s, down));
+      else
+        HIPCHK(launch_pyr_planes(b->pyr_tmp[i], b->in[3][i], b->in[4][i], b->in[5][i], b->nframes, g.w, g.h, p.noc, g.pad, s,
+                                 down));  // B's gradients only exist (non-null) with usefbcon
+    }
+  }
+  return OFDIS_OK;
+}
+
+// ------------------------------------------------------------------------------------ results
+const float* ofdis_batch_flow(const ofdis_batch* b) { return b ? b->flow[0] : nullptr; }
+const float* ofdis_batch_level_flow(const ofdis_batch* b, int level) { return b ? level_flow(*b, level, false) : nullptr; }
+
+int ofdis_batch_download(ofdis_batch* b, int frame, float* outflow_host, void* stream) {
+  if (!b || frame < 0 || frame >= b->nframes || !outflow_host) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  return download(b, frame, outflow_host, (hipStream_t)stream, false);
+}
+
+// Warm start (oflow.cpp:217-220): the coarsest level initialises its patches from this flow exactly as finer levels
+// do from the level above, i.e. it is indexed as a (w >> (sc_f+1)) x (h >> (sc_f+1)) AoS plane per frame.
+size_t ofdis_batch_initflow_elems(const ofdis_batch* b) {
+  if (!b) return 0;
+  const LevelGeom& g = b->geom[b->nlevels - 1];
+  return (size_t)(g.w / 2) * (g.h / 2) * b->nop;
+}
+
+int ofdis_batch_set_initflow(ofdis_batch* b, const float* initflow_dev) {
+  if (!b) return fail(OFDIS_ERR_INVALID, "batch is NULL");
+  b->initflow = initflow_dev;
+  return OFDIS_OK;
+}
+
+int ofdis_batch_upload_initflow(ofdis_batch* b, int frame, const float* initflow_host, void* stream) {
+  if (!b || frame < 0 || frame >= b->nframes || !initflow_host) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  const size_t n = ofdis_batch_initflow_elems(b);
+  if (!b->initflow_own) {
+    dalloc(b, &b->initflow_own, n);
+    if (int rc = dcommit(b)) return rc;
+    HIPCHK(hipMemsetAsync(b->initflow_own, 0, n * b->nframes * sizeof(float), (hipStream_t)stream));
+  }
+  HIPCHK(hipMemcpyAsync(frame_at(*b, b->initflow_own, frame), initflow_host, n * sizeof(float), hipMemcpyHostToDevice,
+                        (hipStream_t)stream));
+  b->initflow = b->initflow_own;
+  return OFDIS_OK;
+}
+
+int ofdis_batch_upsample_frames(ofdis_batch* b, int first_frame, int count, float* out_dev, int width_org,
+                                int height_org, void* stream) {
+  if (!b || !out_dev) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (first_frame < 0 || count < 1 || first_frame > b->nframes - count) return fail(OFDIS_ERR_INVALID, "frame range outside the batch");
+  const ofdis_params& p = b->p;
+  if (width_org < 1 || height_org < 1 || width_org > p.width || height_org > p.height)
+    return fail(OFDIS_ERR_INVALID, "original size exceeds the padded size");
+  const LevelGeom& g = b->geom[0];
+  if (int rc = ofdis_batch_join(b, stream)) return rc;
+  HIPCHK(launch_upsample_crop(frame_at(*b, b->flow[0], first_frame), out_dev, count, g.w, g.h, p.sc_l,
+                              (p.width - width_org) / 2, (p.height - height_org) / 2, width_org, height_org, b->nop,
+                              (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+int ofdis_batch_upsample(ofdis_batch* b, float* out_dev, int width_org, int height_org, void* stream) {
+  if (!b) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  return ofdis_batch_upsample_frames(b, 0, b->nframes, out_dev, width_org, height_org, stream);
+}
+
+// ------------------------------------------------------------------------------------ reverse direction (OFDIS_BATCH_REVERSE)
+const float* ofdis_batch_flow_reverse(const ofdis_batch* b) { return b ? b->flow_rev[0] : nullptr; }
+const float* ofdis_batch_level_flow_reverse(const ofdis_batch* b, int level) { return b ? level_flow(*b, level, true) : nullptr; }
+
+int ofdis_batch_set_initflow_reverse(ofdis_batch* b, const float* initflow_dev) {
+  if (!b || !b->reverse) return fail(OFDIS_ERR_INVALID, "not a context created with OFDIS_BATCH_REVERSE");
+  b->initflow_rev = initflow_dev;
+  return OFDIS_OK;
+}
+
+int ofdis_batch_download_reverse(ofdis_batch* b, int frame, float* outflow_host, void* stream) {
+  if (!b || !b->reverse) return fail(OFDIS_ERR_INVALID, "not a context created with OFDIS_BATCH_REVERSE");
+  if (frame < 0 || frame >= b->nframes || !outflow_host) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  return download(b, frame, outflow_host, (hipStream_t)stream, true);
+}
+
+int ofdis_batch_upsample_bidir(ofdis_batch* b, int first_frame, int count, float* out_fw, float* out_rev,
+                               uint8_t* mask_fw, uint8_t* mask_rev, int width_org, int height_org,
+                               float alpha, float beta, void* stream) {
+  if (!b || !b->reverse) return fail(OFDIS_ERR_INVALID, "not a context created with OFDIS_BATCH_REVERSE");
+  if (first_frame < 0 || count < 1 || first_frame > b->nframes - count) return fail(OFDIS_ERR_INVALID, "frame range outside the batch");
+  const ofdis_params& p = b->p;
+  if (width_org < 1 || height_org < 1 || width_org > p.width || height_org > p.height)
+    return fail(OFDIS_ERR_INVALID, "original size exceeds the padded size");
+  if (!fb_constants_ok(alpha, beta)) return fail(OFDIS_ERR_INVALID, "alpha and beta must be finite and >= 0");
+  const LevelGeom& g = b->geom[0];
+  if (int rc = ofdis_batch_join(b, stream)) return rc;
+  if (!out_fw && !out_rev && !mask_fw && !mask_rev) return OFDIS_OK;
+  HIPCHK(launch_upsample_bidir(frame_at(*b, b->flow[0], first_frame), frame_at(*b, b->flow_rev[0], first_frame), out_fw, out_rev,
+                               mask_fw, mask_rev, count, g.w, g.h, p.sc_l, (p.width - width_org) / 2,
+                               (p.height - height_org) / 2, width_org, height_org, alpha, beta, (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+int ofdis_fb_check(const float* flow, const float* flow_other, uint8_t* mask, int nframes, int width, int height,
+                   float alpha, float beta, void* stream) {
+  if (!flow || !flow_other || !mask) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (nframes < 1 || width < 1 || height < 1 || (long long)width * height > (1ll << 30))
+    return fail(OFDIS_ERR_INVALID, "bad sizes");
+  if (!fb_constants_ok(alpha, beta)) return fail(OFDIS_ERR_INVALID, "alpha and beta must be finite and >= 0");
+  HIPCHK(launch_fb_check(flow, flow_other, mask, nframes, width, height, alpha, beta, (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+// ------------------------------------------------------------------------------------ frame interpolation (ofdis_interp.hip)
+int ofdis_interpolate(const uint8_t* img_a, const uint8_t* img_b, const float* flow_fw, const float* flow_rev,
+                      const uint8_t* mask_fw, const uint8_t* mask_rev, uint8_t* out, int nframes, int width, int height,
+                      int noc, const float* times, int ntimes, void* stream) {
+  if (!img_a || !img_b || !flow_fw || !flow_rev || !out) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  InterpTimes ts;
+  if (int rc = interp_times(times, ntimes, ts)) return rc;
+  if (noc != 1 && noc != 3) return fail(OFDIS_ERR_INVALID, "noc must be 1 or 3");
+  if (nframes < 1 || width < 1 || height < 1 || (long long)width * height > (1ll << 30))
+    return fail(OFDIS_ERR_INVALID, "bad sizes");
+  HIPCHK(launch_interp_frames(img_a, img_b, flow_fw, flow_rev, mask_fw, mask_rev, out, nframes, width, height, noc, ts,
+                              (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+int ofdis_batch_interpolate(ofdis_batch* b, const uint8_t* img_a, const uint8_t* img_b, int first_frame, int count,
+                            const float* times, int ntimes, uint8_t* out, int width_org, int height_org,
+                            float alpha, float beta, void* stream) {
+  if (!b || !b->reverse) return fail(OFDIS_ERR_INVALID, "not a context created with OFDIS_BATCH_REVERSE");
+  if (!img_a || !img_b || !out) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  InterpTimes ts;
+  if (int rc = interp_times(times, ntimes, ts)) return rc;
+  if (first_frame < 0 || count < 1 || first_frame > b->nframes - count) return fail(OFDIS_ERR_INVALID, "frame range outside the batch");
+  const ofdis_params& p = b->p;
+  if (p.noc != 1 && p.noc != 3) return fail(OFDIS_ERR_INVALID, "noc must be 1 or 3");
+  if (width_org < 1 || height_org < 1 || width_org > p.width || height_org > p.height)
+    return fail(OFDIS_ERR_INVALID, "original size exceeds the padded size");
+  if (!fb_constants_ok(alpha, beta)) return fail(OFDIS_ERR_INVALID, "alpha and beta must be finite and >= 0");
+  const LevelGeom& g = b->geom[0];
+  if (int rc = ofdis_batch_join(b, stream)) return rc;
+  const size_t img_off = (size_t)first_frame * width_org * height_org * p.noc;
+  HIPCHK(launch_interp_bidir(img_a + img_off, img_b + img_off, frame_at(*b, b->flow[0], first_frame),
+                             frame_at(*b, b->flow_rev[0], first_frame), out, count, g.w, g.h, p.sc_l,
+                             (p.width - width_org) / 2, (p.height - height_org) / 2, width_org, height_org, p.noc, ts, alpha,
+                             beta, (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+}  // extern "C"

@@ -83,13 +83,13 @@ def test_tuning_environment_variables_match_header():
     body = re.search(r"typedef struct ofdis_tuning \{(.*?)\} ofdis_tuning;", src, re.S).group(1)
     documented = set(re.findall(r"OFDIS_[A-Z0-9_]+", body))
     csrc = os.path.join(ROOT, "of_dis_amd", "csrc")
-    capi_src = open(os.path.join(csrc, "ofdis_capi.hip")).read()
-    init = capi_src[capi_src.index("void tuning_init_locked()"):capi_src.index("ofdis_tuning tuning(unsigned* epoch)")]
+    knobs_src = open(os.path.join(csrc, "ofdis_context.hip")).read()
+    init = knobs_src[knobs_src.index("void tuning_init_locked()"):knobs_src.index("ofdis_tuning tuning(unsigned* epoch)")]
     assert set(re.findall(r'"(OFDIS_[A-Z0-9_]+)"', init)) == documented
     for name in os.listdir(csrc):
         if name.endswith((".hip", ".h")):
             text = open(os.path.join(csrc, name)).read()
-            if name == "ofdis_capi.hip":
+            if name == "ofdis_context.hip":
                 text = text.replace(init, "")
             code = re.sub(r"//[^\n]*", "", text)  # (comments may mention it)
             # the one exception: the scratch-poisoning TEST HOOK, read where a context allocates its memory (never on a launch

@@ -1,4 +1,4 @@
-"""Which kernel classes one pass launches on each route of the TV refinement (ofdis_capi.hip: plan_level).
+"""Which kernel classes one pass launches on each route of the TV refinement (ofdis_schedule.hip: plan_level).
 
 Under the exact contract every route gives the same bits, so the bit-exact tests cannot tell a misrouted level from a right
 one: a level that silently loses its fused route still passes them.  These cases pin, per kernel class of capi.K_NAMES, how

@@ -111,3 +111,33 @@ def test_stereo_forward_backward(gpu, size, noc, opp, tv):
     assert not np.array_equal(ref, plain)
     got = gpu.flow(p, pa[0], pa[1], pa[2], pb[0], pyr_b_dx=pb[1], pyr_b_dy=pb[2])
     assert_bits_equal(got, ref, "stereo + usefbcon vs reference sources")
+
+
+@pytest.mark.parametrize("nsub", [2, 4])
+def test_stereo_forward_backward_pipelined(gpu, nsub):
+    """usefbcon in stereo mode on frame views (ofdis_batch_set_pipeline): the one configuration whose backward flow arrays
+    hold ONE channel per pixel, so a sub-batch's share of them starts at w * h floats per frame, not 2 * w * h.  Every frame of
+    the pipelined context -- different pairs, a ragged split -- has the bits of the un-pipelined context, and of the reference
+    sources where they are present."""
+    cases = [_case(640, 480, 94 + k, 1, 2, 1) for k in range(3)]
+    p = cases[0][0].copy(usefbcon=1)
+    order = [0, 1, 2, 2, 1, 0, 1]
+    outs = []
+    for pipeline in (0, nsub):
+        b = gpu.Batch(p, len(order))
+        for slot, k in enumerate(order):
+            _, pa, pb = cases[k]
+            b.upload(slot, pa[0], pa[1], pa[2], pb[0])
+            b.upload_b_gradients(slot, pb[1], pb[2])
+        b.set_pipeline(pipeline)
+        b.run()
+        b.run()                                  # two passes in flight before anything joins
+        outs.append(b.download_all())
+        b.close()
+    R = oracle.need_ref("de_int", True)
+    for slot, k in enumerate(order):
+        assert_bits_equal(outs[1][slot], outs[0][slot], f"pipelined({nsub}) slot {slot} (pair {k}) vs the un-pipelined context")
+        if R is not None and slot < 3:
+            _, pa, pb = cases[k]
+            ref = R.flow(p, pa[0], pa[1], pa[2], pb[0], pyr_b_dx=pb[1], pyr_b_dy=pb[2])
+            assert_bits_equal(outs[0][slot], ref, f"slot {slot} (pair {k}) vs reference sources")
