@@ -145,7 +145,8 @@ enum { OFDIS_FB_CONSISTENT = 0, OFDIS_FB_INCONSISTENT = 1, OFDIS_FB_OUTSIDE = 2 
  * bit-identical to the forward flow that a plain context of the same nframes, params, contract and pipelining computes for
  * the pair (B_k, A_k); the forward flow is bit-identical to a plain context's.  Pipelining, graph replay, kernel timing and
  * ofdis_batch_status cover both passes (a lost hand-over of the cross-CU TV variant in either fails the pass).
- * Stereo depth (selectmode 2) with OFDIS_BATCH_REVERSE: OFDIS_ERR_UNSUPPORTED. */
+ * Stereo depth (selectmode 2) with OFDIS_BATCH_REVERSE: OFDIS_ERR_UNSUPPORTED, whatever other bits are set -- the second view
+ * of a stereo pair is OFDIS_BATCH_STEREO_LR (below: "Stereo depth: right-view disparity ..."). */
 int ofdis_batch_create_ex(ofdis_batch** out, const ofdis_params* p, int nframes, unsigned flags);
 /* The reverse results of an OFDIS_BATCH_REVERSE context, laid out as ofdis_batch_flow / ofdis_batch_level_flow /
  * ofdis_batch_download; NULL or OFDIS_ERR_INVALID on a context created without the flag. */
@@ -174,6 +175,70 @@ int ofdis_batch_upsample_bidir(ofdis_batch* b, int first_frame, int count, float
  * Independent of the arithmetic contract.  Invalid sizes, or alpha / beta negative or not finite: OFDIS_ERR_INVALID. */
 int ofdis_fb_check(const float* flow, const float* flow_other, uint8_t* mask, int nframes, int width, int height,
                    float alpha, float beta, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Stereo depth: right-view disparity, left-right check and occlusion fill.
+ *
+ * Let mir(I)[y][x] = I[y][W-1-x] on the original 8-bit W x H frames (all channels of a pixel together).  For a pair (L, R) the
+ * MIRROR PASS is the ordinary stereo pass (left camera, displacement <= 0) on the pair (A', B') = (mir(R), mir(L)); Dm is its
+ * full-resolution result.  The right-view disparity is DR[y][x] = -Dm[y][W-1-x] (>= 0): pixel (x, y) of R shows what L shows
+ * at x + DR.  The left-view result DL (<= 0) is what a plain stereo context computes.
+ * ------------------------------------------------------------------------------------------- */
+#define OFDIS_BATCH_STEREO_LR 2u        /* flag of ofdis_batch_create_ex */
+enum { OFDIS_FILL_NONE = 0, OFDIS_FILL_INVALIDATE = 1, OFDIS_FILL_BACKGROUND = 2 };
+#define OFDIS_LR_FUSED_MAX_WIDTH 4096   /* ofdis_batch_upsample_lr: widest original frame the one-launch kernel takes */
+/* OFDIS_BATCH_STEREO_LR is valid with selectmode 2 only (any other selectmode: OFDIS_ERR_INVALID).  The context allocates a
+ * second set of input planes for (A', B') -- ofdis_batch_input kinds 6 = A', 7 = A'_dx, 8 = A'_dy, 9 = B' (with usefbcon also
+ * 10 = B'_dx, 11 = B'_dy) -- and per-level mirror disparity buffers; all other scratch is shared.
+ * ofdis_batch_build_pyramids_u8 also builds the mirror planes, from mir(img_b) and mir(img_a): the pyramid of a mirrored frame
+ * is not the mirror of the pyramid (one-sided padding, the sign of dx, the downsampling phase), so they hold the bits the same
+ * call on a plain context given host-mirrored, swapped frames produces.  ofdis_batch_run runs the forward pass exactly as a
+ * plain context does, then the mirror pass on `stream`: every level of it is bit-identical to what a plain stereo context of
+ * the same nframes, params, contract and pipelining computes from the mirrored, swapped frames.  Pipelining, graph replay,
+ * kernel timing and ofdis_batch_status cover both passes.  The warm start stays forward-only: ofdis_batch_set_initflow /
+ * ofdis_batch_upload_initflow warm-start the forward pass, the mirror pass always starts from zero.
+ *
+ * The raw mirror-pass disparities (MIRRORED coordinates, <= 0), laid out as ofdis_batch_flow / ofdis_batch_level_flow.  They
+ * exist for the parity tests; applications take ofdis_batch_upsample_lr.  NULL on a context created without the flag. */
+const float* ofdis_batch_flow_mirror(const ofdis_batch* b);
+const float* ofdis_batch_level_flow_mirror(const ofdis_batch* b, int level);
+/* The left-right consistency test on device arrays [nframes][height][width], one float per pixel: the displacement in x
+ * towards the other view (left view <= 0, right view >= 0).  One byte per pixel of `disp` into `mask`, codes OFDIS_FB_*.  For
+ * pixel (x, y) with d = disp, every operation a separately rounded fp32 operation in this order:
+ *   xb = x + d;  not (0 <= xb <= W-1) (NaN included): OFDIS_FB_OUTSIDE
+ *   x0 = min(floor(xb), W-2), ax = xb - x0  (x0 = 0, ax = 0 when W == 1);  x1 = min(x0+1, W-1)
+ *   r = R[y][x0]*(1-ax) + R[y][x1]*ax                    (R = disp_other, same row)
+ *   s = d + r;  lhs = s*s;  rhs = alpha*(d*d + r*r) + beta;  lhs <= rhs: OFDIS_FB_CONSISTENT, else OFDIS_FB_INCONSISTENT
+ * i.e. the test of ofdis_fb_check with v = 0 and the vertical blend dropped: for finite inputs the same codes as ofdis_fb_check
+ * on the flows (d, 0).  Independent of the arithmetic contract.  Argument errors as ofdis_fb_check. */
+int ofdis_lr_check(const float* disp, const float* disp_other, uint8_t* mask, int nframes, int width, int height,
+                   float alpha, float beta, void* stream);
+/* What to do with the pixels a mask flags (mask != OFDIS_FB_CONSISTENT); device arrays as above, `out` may be `disp`.
+ *   OFDIS_FILL_NONE        out = disp
+ *   OFDIS_FILL_INVALIDATE  out = +inf where flagged (the "unknown" of Middlebury .pfm files), else disp bit for bit
+ *   OFDIS_FILL_BACKGROUND  a flagged pixel x takes its value from the nearest consistent pixels of its row: l the largest
+ *                          x' < x and r the smallest x' > x with mask == OFDIS_FB_CONSISTENT.  Both exist:
+ *                          out = fabsf(d[l]) <= fabsf(d[r]) ? d[l] : d[r] (the farther surface; the left one on a tie); one
+ *                          exists: that one; the row has none: out = disp.  Consistent pixels are copied bit for bit.
+ * No arithmetic is involved: the result is a pure function of the inputs.  Any other mode, NULL pointers or bad sizes:
+ * OFDIS_ERR_INVALID before any device work. */
+int ofdis_disparity_fill(const float* disp, const uint8_t* mask, float* out, int nframes, int width, int height, int mode,
+                         void* stream);
+/* The fused finish of an OFDIS_BATCH_STEREO_LR context, one launch over the frames [first_frame, first_frame + count):
+ * out_left / out_right = device [count][height_org][width_org] floats, mask_left / mask_right = the same shape in bytes; any
+ * of the four may be NULL (not written).  Bit-identical to the materialised composition
+ *   U = ofdis_batch_upsample_frames of the forward disparity; Dm = the same upsample of the mirror disparity;
+ *   DR[y][x] = -Dm[y][width_org-1-x];
+ *   mask_left = ofdis_lr_check(U, DR), mask_right = ofdis_lr_check(DR, U)     (always of the UNFILLED disparities)
+ *   out_left = ofdis_disparity_fill(U, mask_left, fill_mode), out_right = ofdis_disparity_fill(DR, mask_right, fill_mode)
+ * A wavefront builds a row of U and DR in LDS from the level disparities, checks both against each other there, fills and
+ * writes each output once.  Original widths above OFDIS_LR_FUSED_MAX_WIDTH take the composition itself (several launches,
+ * staging buffers owned by the context).  Joins a pipelined pass by itself.  OFDIS_ERR_INVALID: a context created without
+ * OFDIS_BATCH_STEREO_LR, a frame range outside the batch, an original size above the padded size, a fill mode that does not
+ * exist, alpha / beta as ofdis_fb_check rejects them. */
+int ofdis_batch_upsample_lr(ofdis_batch* b, int first_frame, int count, float* out_left, float* out_right,
+                            uint8_t* mask_left, uint8_t* mask_right, int fill_mode, int width_org, int height_org,
+                            float alpha, float beta, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Frame interpolation from bidirectional flow with occlusion masks.
@@ -220,7 +285,7 @@ int ofdis_batch_interpolate(ofdis_batch* b, const uint8_t* img_a, const uint8_t*
                             float alpha, float beta, void* stream);
 
 /* device pointers to the context-owned input planes of level l: kind 0 = image A, 1 = A_dx,
- * 2 = A_dy, 3 = image B (with usefbcon also 4 = B_dx, 5 = B_dy).  The caller fills them (hipMemcpy, its own kernels, ofdis_batch_upload
+ * 2 = A_dy, 3 = image B (with usefbcon also 4 = B_dx, 5 = B_dy; OFDIS_BATCH_STEREO_LR: 6 .. 11, the same of the mirrored pair).  The caller fills them (hipMemcpy, its own kernels, ofdis_batch_upload
  * or ofdis_batch_build_pyramids_u8). */
 float* ofdis_batch_input(ofdis_batch* b, int level, int kind);
 size_t ofdis_batch_input_elems(const ofdis_batch* b, int level); /* floats per frame per plane */

@@ -38,8 +38,12 @@ ABI_SYMBOLS = [
     "ofdis_batch_create_ex", "ofdis_batch_flow_reverse", "ofdis_batch_level_flow_reverse", "ofdis_batch_set_initflow_reverse",
     "ofdis_batch_download_reverse", "ofdis_batch_upsample_bidir", "ofdis_fb_check",
     "ofdis_interpolate", "ofdis_batch_interpolate",
+    "ofdis_batch_flow_mirror", "ofdis_batch_level_flow_mirror", "ofdis_lr_check", "ofdis_disparity_fill", "ofdis_batch_upsample_lr",
 ]
 BATCH_REVERSE = 1  # include/ofdis.h: OFDIS_BATCH_REVERSE
+BATCH_STEREO_LR = 2  # OFDIS_BATCH_STEREO_LR
+FILL_NONE, FILL_INVALIDATE, FILL_BACKGROUND = 0, 1, 2  # OFDIS_FILL_*
+LR_FUSED_MAX_WIDTH = 4096  # OFDIS_LR_FUSED_MAX_WIDTH
 FB_ALPHA, FB_BETA = 0.01, 0.5  # OFDIS_FB_ALPHA / OFDIS_FB_BETA
 FB_CONSISTENT, FB_INCONSISTENT, FB_OUTSIDE = 0, 1, 2
 INTERP_MAX_TIMES = 16  # OFDIS_INTERP_MAX_TIMES
@@ -148,6 +152,14 @@ def lib():
         L.ofdis_fb_check.argtypes = [VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, VP]
         L.ofdis_interpolate.argtypes = [VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, FP, C.c_int, VP]
         L.ofdis_batch_interpolate.argtypes = [VP, VP, VP, C.c_int, C.c_int, FP, C.c_int, VP, C.c_int, C.c_int, C.c_float,
+                                              C.c_float, VP]
+        L.ofdis_batch_flow_mirror.restype = VP
+        L.ofdis_batch_flow_mirror.argtypes = [VP]
+        L.ofdis_batch_level_flow_mirror.restype = VP
+        L.ofdis_batch_level_flow_mirror.argtypes = [VP, C.c_int]
+        L.ofdis_lr_check.argtypes = [VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, VP]
+        L.ofdis_disparity_fill.argtypes = [VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, VP]
+        L.ofdis_batch_upsample_lr.argtypes = [VP, C.c_int, C.c_int, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_float,
                                               C.c_float, VP]
         _lib = L
     return _lib
@@ -411,6 +423,35 @@ def fb_check(flow, other, alpha=FB_ALPHA, beta=FB_BETA):
     return dm.get(flow.shape[:-1], np.uint8)
 
 
+def lr_check(disp, other, alpha=FB_ALPHA, beta=FB_BETA):
+    """ofdis_lr_check on the device: disp, other [..., h, w] float32 (the same shape; leading axes are frames), the
+    displacement in x towards the other view -> uint8 mask [..., h, w] of FB_* codes for every pixel of `disp`."""
+    disp, other = _f(disp), _f(other)
+    assert disp.shape == other.shape and disp.ndim >= 2, (disp.shape, other.shape)
+    h, w = disp.shape[-2:]
+    n = int(np.prod(disp.shape[:-2], dtype=np.int64))
+    dd, do = Dev(disp), Dev(other)
+    dm = Dev(nbytes=max(1, n * h * w))
+    check(lib().ofdis_lr_check(dd.ptr, do.ptr, dm.ptr, n, w, h, alpha, beta, None))
+    check(lib().ofdis_sync(None))
+    return dm.get(disp.shape, np.uint8)
+
+
+def disparity_fill(disp, mask, mode, in_place=False):
+    """ofdis_disparity_fill on the device: disp [..., h, w] float32, mask the same shape uint8 -> filled disparities.
+    in_place: `out` is `disp` itself (the library allows it)."""
+    disp = _f(disp)
+    mask = np.ascontiguousarray(mask, np.uint8)
+    assert disp.shape == mask.shape and disp.ndim >= 2, (disp.shape, mask.shape)
+    h, w = disp.shape[-2:]
+    n = int(np.prod(disp.shape[:-2], dtype=np.int64))
+    dd, dm = Dev(disp), Dev(mask)
+    do = dd if in_place else Dev(nbytes=max(4, disp.nbytes))
+    check(lib().ofdis_disparity_fill(dd.ptr, dm.ptr, do.ptr, n, w, h, mode, None))
+    check(lib().ofdis_sync(None))
+    return do.get(disp.shape, _f32)
+
+
 def _times(times):
     t = np.ascontiguousarray(np.atleast_1d(np.asarray(times, _f32)).ravel())
     return t, t.ctypes.data_as(FP)
@@ -446,14 +487,17 @@ def interpolate(img_a, img_b, flow_fw, flow_rev, times, mask_fw=None, mask_rev=N
 
 class Batch:
     """ofdis_batch: `nframes` frame pairs of one geometry resident in HBM.  reverse=True: ofdis_batch_create_ex with
-    OFDIS_BATCH_REVERSE (every pass also computes the flow B -> A of each pair)."""
+    OFDIS_BATCH_REVERSE (every pass also computes the flow B -> A of each pair).  stereo_lr=True: OFDIS_BATCH_STEREO_LR
+    (stereo-depth mode: every pass also runs on the mirrored, swapped pair, which gives the right view's disparity)."""
 
-    def __init__(self, p, nframes, reverse=False):
+    def __init__(self, p, nframes, reverse=False, stereo_lr=False):
         self.p = p.copy()
         self.nframes = nframes
         self.reverse = bool(reverse)
+        self.stereo_lr = bool(stereo_lr)
         self.h = VP()
-        check(lib().ofdis_batch_create_ex(C.byref(self.h), C.byref(self.p), nframes, BATCH_REVERSE if reverse else 0))
+        flags = (BATCH_REVERSE if reverse else 0) | (BATCH_STEREO_LR if stereo_lr else 0)
+        check(lib().ofdis_batch_create_ex(C.byref(self.h), C.byref(self.p), nframes, flags))
 
     def close(self):
         if self.h:
@@ -589,6 +633,34 @@ class Batch:
 
     def download_all_reverse(self):
         return self.level_flow_reverse(self.p.sc_l)
+
+    # ---- stereo left-right (stereo_lr=True contexts)
+    def level_flow_mirror(self, level):
+        """The raw mirror-pass disparity of a level (mirrored coordinates, <= 0): for the parity tests."""
+        ptr = lib().ofdis_batch_level_flow_mirror(self.h, level)
+        if not ptr:
+            raise OfdisError("ofdis_batch_level_flow_mirror: not a stereo_lr context, or no such level")
+        w, h = self.p.level_size(level)
+        out = np.zeros((self.nframes, h, w, self.p.nop), _f32)
+        self.join(None)
+        check(lib().ofdis_sync(None))
+        check(lib().ofdis_memcpy_d2h(out.ctypes.data, ptr, out.nbytes))
+        return out
+
+    def upsample_lr(self, width_org, height_org, fill=FILL_NONE, alpha=FB_ALPHA, beta=FB_BETA, first=0, count=None,
+                    outputs=(True, True, True, True), stream=None):
+        """ofdis_batch_upsample_lr over frames [first, first + count): (left, right, mask_left, mask_right) as host arrays
+        [count][height_org][width_org], float32 and uint8.  `outputs` selects which of the four the library writes (the
+        others are passed as NULL and returned as None)."""
+        count = self.nframes - first if count is None else count
+        shape = (count, height_org, width_org)
+        dtypes = [_f32, _f32, np.uint8, np.uint8]
+        devs = [Dev(nbytes=max(1, int(np.prod(shape)) * np.dtype(t).itemsize)) if want else None
+                for t, want in zip(dtypes, outputs)]
+        check(lib().ofdis_batch_upsample_lr(self.h, first, count, *[d.ptr if d else None for d in devs], fill, width_org,
+                                            height_org, alpha, beta, stream))
+        check(lib().ofdis_sync(stream))
+        return tuple(d.get(shape, t) if d else None for d, t in zip(devs, dtypes))
 
     def upsample_bidir(self, width_org, height_org, alpha=FB_ALPHA, beta=FB_BETA, first=0, count=None,
                        outputs=(True, True, True, True), stream=None):

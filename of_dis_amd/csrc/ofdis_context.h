@@ -149,7 +149,9 @@ struct ofdis_batch {
   int nop = 2;                       // flow channels (1 in stereo-depth mode)
   const float* initflow = nullptr;   // borrowed device pointer (ofdis_batch_set_initflow) or null
   bool reverse = false;              // OFDIS_BATCH_REVERSE: every pass also runs on the swapped pair (swap_direction)
-  float* flow_rev[MAX_LEVELS] = {};  // ... into these per-level buffers
+  bool stereo_lr = false;            // OFDIS_BATCH_STEREO_LR: ... on the mirrored, swapped pair, whose planes are
+  float* in_mir[6][MAX_LEVELS] = {}; //     A', A'_dx, A'_dy, B' per level (+ B'_dx, B'_dy when usefbcon)
+  float* flow_rev[MAX_LEVELS] = {};  // the second direction's per-level results (reverse flow / mirror disparity)
   const float* initflow_rev = nullptr;  // ... from this warm start (ofdis_batch_set_initflow_reverse)
   float* initflow_own = nullptr;     // staging buffer of ofdis_batch_upload_initflow
   // scratch, sized for the finest level
@@ -163,6 +165,8 @@ struct ofdis_batch {
   float* xbuf = nullptr;                 // ... and the hand-over granules of its cross-CU variant (small contexts only)
   struct XcuState* xcu = nullptr;        // ... with the variant's error word (owned by the context; frame views share it)
   float* pyr_tmp[MAX_LEVELS] = {};   // unpadded level images (ofdis_batch_build_pyramids_u8), lazily allocated
+  float* mir_u8 = nullptr;           // ... and, OFDIS_BATCH_STEREO_LR, one mirrored 8-bit frame set (bytes, held as floats)
+  float *lr_u = nullptr, *lr_dr = nullptr, *lr_mask = nullptr;  // staging of ofdis_batch_upsample_lr above its fused width, lazy
   // device memory: requests are collected (dalloc) and served from ONE hipMalloc per commit (dcommit) -- a context is
   // one allocation (two with the u8 pyramid scratch), and the input planes form one contiguous region [in_base,
   // in_base + in_bytes) in (level, kind) order so that a single-frame context is uploaded with one copy (ofdis_flow)

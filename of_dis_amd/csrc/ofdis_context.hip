@@ -352,24 +352,30 @@ int ofdis_batch_create_ex(ofdis_batch** out, const ofdis_params* p, int nframes,
   int rc = check_params(p);
   if (rc) return rc;
   if (nframes < 1) return fail(OFDIS_ERR_INVALID, "nframes must be >= 1");
-  if (flags & ~OFDIS_BATCH_REVERSE) return fail(OFDIS_ERR_INVALID, "unknown flag bits");
-  const bool reverse = (flags & OFDIS_BATCH_REVERSE) != 0;
+  if (flags & ~(OFDIS_BATCH_REVERSE | OFDIS_BATCH_STEREO_LR)) return fail(OFDIS_ERR_INVALID, "unknown flag bits");
+  const bool reverse = (flags & OFDIS_BATCH_REVERSE) != 0, stereo_lr = (flags & OFDIS_BATCH_STEREO_LR) != 0;
   if (reverse && p->selectmode == 2)
-    return fail(OFDIS_ERR_UNSUPPORTED, "OFDIS_BATCH_REVERSE: no reverse direction in stereo-depth mode (selectmode 2)");
+    return fail(OFDIS_ERR_UNSUPPORTED, "OFDIS_BATCH_REVERSE: no reverse direction in stereo-depth mode (selectmode 2); the "
+                                       "right view is OFDIS_BATCH_STEREO_LR");
+  if (stereo_lr && p->selectmode != 2) return fail(OFDIS_ERR_INVALID, "OFDIS_BATCH_STEREO_LR needs stereo-depth mode (selectmode 2)");
   if (nframes > 65535)  // launch_warp / launch_upsample_crop carry the frame in grid.z
     return fail(OFDIS_ERR_UNSUPPORTED, "at most 65535 frames per batch context");
   ofdis_batch* b = new ofdis_batch();
   const ofdis_tuning tn = tuning();  // ONE snapshot decides the contract and the scratch
   context_init(b, *p, nframes, tn, p->sc_l, p->sc_f);
   b->reverse = reverse;
+  b->stereo_lr = stereo_lr;
   const int nin = (p->usefbcon || reverse) ? 6 : 4;  // (the reverse pass reads B's gradients as its A's)
   for (int i = 0; i < b->nlevels; ++i)  // the input planes first: one contiguous region in (level, kind) order
     for (int k = 0; k < nin; ++k) dalloc(b, &b->in[k][i], b->geom[i].plane_elems);
   for (const ofdis_batch::Array& a : b->arrays) b->in_bytes += array_bytes(*b, a);
+  if (stereo_lr)  // the mirrored pair's planes: the same sizes, stated by the same expression
+    for (int i = 0; i < b->nlevels; ++i)
+      for (int k = 0; k < nin; ++k) dalloc(b, &b->in_mir[k][i], b->geom[i].plane_elems);
   for (int i = 0; i < b->nlevels; ++i) {
     const size_t flow_elems = (size_t)b->geom[i].w * b->geom[i].h * b->nop;
     dalloc(b, &b->flow[i], flow_elems);
-    if (reverse) dalloc(b, &b->flow_rev[i], flow_elems);
+    if (reverse || stereo_lr) dalloc(b, &b->flow_rev[i], flow_elems);
     if (p->usefbcon && i > 0) dalloc(b, &b->flow_bw[i], flow_elems);
   }
   const LevelGeom& g0 = b->geom[0];  // finest level: largest of everything
@@ -407,8 +413,11 @@ void ofdis_batch_destroy(ofdis_batch* b) {
 }
 
 float* ofdis_batch_input(ofdis_batch* b, int level, int kind) {
-  if (!b || level < b->p.sc_l || level > b->p.sc_f || kind < 0 || kind > ((b->p.usefbcon || b->reverse) ? 5 : 3)) return nullptr;
-  return b->in[kind][level - b->p.sc_l];
+  if (!b || level < b->p.sc_l || level > b->p.sc_f || kind < 0) return nullptr;
+  const int nin = (b->p.usefbcon || b->reverse) ? 6 : 4;
+  if (kind < nin) return b->in[kind][level - b->p.sc_l];
+  if (b->stereo_lr && kind >= 6 && kind < 6 + nin) return b->in_mir[kind - 6][level - b->p.sc_l];  // the mirrored pair's
+  return nullptr;
 }
 size_t ofdis_batch_input_elems(const ofdis_batch* b, int level) {
   if (!b || level < b->p.sc_l || level > b->p.sc_f) return 0;
@@ -445,22 +454,29 @@ int ofdis_batch_build_pyramids_u8(ofdis_batch* b, const uint8_t* img_a, const ui
   hipStream_t s = (hipStream_t)stream;
   if (!b->pyr_tmp[0]) {  // (a frame view never sees them)
     for (int i = 0; i < b->nlevels; ++i) dalloc(b, &b->pyr_tmp[i], (size_t)b->geom[i].w * b->geom[i].h * b->geom[i].noc, false);
+    if (b->stereo_lr) dalloc(b, &b->mir_u8, ((size_t)p.width * p.height * p.noc + 3) / 4, false);
     if (int rc = dcommit(b)) return rc;
   }
-  for (int which = 0; which < 2; ++which) {
-    const uint8_t* src = which ? img_b : img_a;
+  // the planes of one frame set: image, and the gradients where the set has them (B's only exist, non-null, with usefbcon)
+  auto build = [&](const uint8_t* src, float* (*planes)[ofdis_batch::MAX_LEVELS]) -> int {
     HIPCHK(launch_pyr_base(src, b->pyr_tmp[0], b->nframes, width_org, height_org, p.width, p.height, p.noc, p.sc_l, s));
     for (int i = 0; i < b->nlevels; ++i) {
       const LevelGeom& g = b->geom[i];
       // the planes of level i and, in the same launch where the geometry allows, the unpadded image of level i + 1
       // (2x2 means: cv::resize(.5,.5), run_dense.cpp:150)
       float* down = i + 1 < b->nlevels ? b->pyr_tmp[i + 1] : nullptr;
-      if (which == 0)
-        HIPCHK(launch_pyr_planes(b->pyr_tmp[i], b->in[0][i], b->in[1][i], b->in[2][i], b->nframes, g.w, g.h, p.noc, g.pad, s, down));
-      else
-        HIPCHK(launch_pyr_planes(b->pyr_tmp[i], b->in[3][i], b->in[4][i], b->in[5][i], b->nframes, g.w, g.h, p.noc, g.pad, s,
-                                 down));  // B's gradients only exist (non-null) with usefbcon
+      HIPCHK(launch_pyr_planes(b->pyr_tmp[i], planes[0][i], planes[1][i], planes[2][i], b->nframes, g.w, g.h, p.noc, g.pad, s, down));
     }
+    return OFDIS_OK;
+  };
+  if (int rc = build(img_a, &b->in[0])) return rc;
+  if (int rc = build(img_b, &b->in[3])) return rc;
+  if (b->stereo_lr) {  // (A', B') = (mir(B), mir(A)): mirrored as 8-bit frames into scratch, then the same kernels
+    uint8_t* m = reinterpret_cast<uint8_t*>(b->mir_u8);
+    HIPCHK(launch_mirror_u8(img_b, m, b->nframes, width_org, height_org, p.noc, s));
+    if (int rc = build(m, &b->in_mir[0])) return rc;
+    HIPCHK(launch_mirror_u8(img_a, m, b->nframes, width_org, height_org, p.noc, s));
+    if (int rc = build(m, &b->in_mir[3])) return rc;
   }
   return OFDIS_OK;
 }
@@ -523,8 +539,10 @@ int ofdis_batch_upsample(ofdis_batch* b, float* out_dev, int width_org, int heig
 }
 
 // ------------------------------------------------------------------------------------ reverse direction (OFDIS_BATCH_REVERSE)
-const float* ofdis_batch_flow_reverse(const ofdis_batch* b) { return b ? b->flow_rev[0] : nullptr; }
-const float* ofdis_batch_level_flow_reverse(const ofdis_batch* b, int level) { return b ? level_flow(*b, level, true) : nullptr; }
+const float* ofdis_batch_flow_reverse(const ofdis_batch* b) { return b && b->reverse ? b->flow_rev[0] : nullptr; }
+const float* ofdis_batch_level_flow_reverse(const ofdis_batch* b, int level) {
+  return b && b->reverse ? level_flow(*b, level, true) : nullptr;
+}
 
 int ofdis_batch_set_initflow_reverse(ofdis_batch* b, const float* initflow_dev) {
   if (!b || !b->reverse) return fail(OFDIS_ERR_INVALID, "not a context created with OFDIS_BATCH_REVERSE");
@@ -563,6 +581,75 @@ int ofdis_fb_check(const float* flow, const float* flow_other, uint8_t* mask, in
     return fail(OFDIS_ERR_INVALID, "bad sizes");
   if (!fb_constants_ok(alpha, beta)) return fail(OFDIS_ERR_INVALID, "alpha and beta must be finite and >= 0");
   HIPCHK(launch_fb_check(flow, flow_other, mask, nframes, width, height, alpha, beta, (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+// ------------------------------------------------------------------------------------ stereo left-right (OFDIS_BATCH_STEREO_LR)
+const float* ofdis_batch_flow_mirror(const ofdis_batch* b) { return b && b->stereo_lr ? b->flow_rev[0] : nullptr; }
+const float* ofdis_batch_level_flow_mirror(const ofdis_batch* b, int level) {
+  return b && b->stereo_lr ? level_flow(*b, level, true) : nullptr;
+}
+
+int ofdis_lr_check(const float* disp, const float* disp_other, uint8_t* mask, int nframes, int width, int height,
+                   float alpha, float beta, void* stream) {
+  if (!disp || !disp_other || !mask) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (nframes < 1 || width < 1 || height < 1 || (long long)width * height > (1ll << 30))
+    return fail(OFDIS_ERR_INVALID, "bad sizes");
+  if (!fb_constants_ok(alpha, beta)) return fail(OFDIS_ERR_INVALID, "alpha and beta must be finite and >= 0");
+  HIPCHK(launch_lr_check(disp, disp_other, mask, nframes, width, height, alpha, beta, (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+static bool fill_mode_ok(int mode) { return mode == OFDIS_FILL_NONE || mode == OFDIS_FILL_INVALIDATE || mode == OFDIS_FILL_BACKGROUND; }
+
+int ofdis_disparity_fill(const float* disp, const uint8_t* mask, float* out, int nframes, int width, int height, int mode,
+                         void* stream) {
+  if (!fill_mode_ok(mode)) return fail(OFDIS_ERR_INVALID, "fill mode must be OFDIS_FILL_NONE, _INVALIDATE or _BACKGROUND");
+  if (!disp || !mask || !out) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (nframes < 1 || width < 1 || height < 1 || (long long)width * height > (1ll << 30))
+    return fail(OFDIS_ERR_INVALID, "bad sizes");
+  HIPCHK(launch_disparity_fill(disp, mask, out, nframes, width, height, mode, (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+int ofdis_batch_upsample_lr(ofdis_batch* b, int first_frame, int count, float* out_left, float* out_right,
+                            uint8_t* mask_left, uint8_t* mask_right, int fill_mode, int width_org, int height_org,
+                            float alpha, float beta, void* stream) {
+  if (!b || !b->stereo_lr) return fail(OFDIS_ERR_INVALID, "not a context created with OFDIS_BATCH_STEREO_LR");
+  if (first_frame < 0 || count < 1 || first_frame > b->nframes - count) return fail(OFDIS_ERR_INVALID, "frame range outside the batch");
+  const ofdis_params& p = b->p;
+  if (width_org < 1 || height_org < 1 || width_org > p.width || height_org > p.height)
+    return fail(OFDIS_ERR_INVALID, "original size exceeds the padded size");
+  if (!fill_mode_ok(fill_mode)) return fail(OFDIS_ERR_INVALID, "fill mode must be OFDIS_FILL_NONE, _INVALIDATE or _BACKGROUND");
+  if (!fb_constants_ok(alpha, beta)) return fail(OFDIS_ERR_INVALID, "alpha and beta must be finite and >= 0");
+  const LevelGeom& g = b->geom[0];
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = ofdis_batch_join(b, stream)) return rc;
+  if (!out_left && !out_right && !mask_left && !mask_right) return OFDIS_OK;
+  const float* fw = frame_at(*b, b->flow[0], first_frame);
+  const float* mir = frame_at(*b, b->flow_rev[0], first_frame);
+  const int left = (p.width - width_org) / 2, top = (p.height - height_org) / 2;
+  if (upsample_lr_fuses(width_org)) {
+    HIPCHK(launch_upsample_lr(fw, mir, out_left, out_right, mask_left, mask_right, count, g.w, g.h, p.sc_l, left, top, width_org,
+                              height_org, fill_mode, alpha, beta, s));
+    return OFDIS_OK;
+  }
+  // wider than the fused kernel's rows: the composition itself, through staging owned by the context
+  const size_t px = (size_t)p.width * p.height;
+  if (!b->lr_u) {
+    dalloc(b, &b->lr_u, px, false);
+    dalloc(b, &b->lr_dr, px, false);
+    dalloc(b, &b->lr_mask, (2 * px + 3) / 4, false);
+    if (int rc = dcommit(b)) return rc;
+  }
+  const size_t n = (size_t)count * width_org * height_org;  // (count <= nframes, original size <= padded size)
+  uint8_t* ml = mask_left ? mask_left : reinterpret_cast<uint8_t*>(b->lr_mask);
+  uint8_t* mr = mask_right ? mask_right : reinterpret_cast<uint8_t*>(b->lr_mask) + n;
+  HIPCHK(launch_lr_materialise(fw, mir, b->lr_u, b->lr_dr, count, g.w, g.h, p.sc_l, left, top, width_org, height_org, s));
+  if (mask_left || out_left) HIPCHK(launch_lr_check(b->lr_u, b->lr_dr, ml, count, width_org, height_org, alpha, beta, s));
+  if (mask_right || out_right) HIPCHK(launch_lr_check(b->lr_dr, b->lr_u, mr, count, width_org, height_org, alpha, beta, s));
+  if (out_left) HIPCHK(launch_disparity_fill(b->lr_u, ml, out_left, count, width_org, height_org, fill_mode, s));
+  if (out_right) HIPCHK(launch_disparity_fill(b->lr_dr, mr, out_right, count, width_org, height_org, fill_mode, s));
   return OFDIS_OK;
 }
 

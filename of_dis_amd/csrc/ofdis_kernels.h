@@ -183,6 +183,22 @@ hipError_t launch_fb_check(const float* flow, const float* other, uint8_t* mask,
 hipError_t launch_upsample_bidir(const float* fw, const float* rev, float* out_fw, float* out_rev, uint8_t* mask_fw,
                                  uint8_t* mask_rev, int nframes, int sw, int sh, int sc_l, int left, int top, int wo, int ho,
                                  float alpha, float beta, hipStream_t s);
+// stereo left-right step (include/ofdis.h; ofdis_stereo_lr.hip).  mir(I)[y][x] = I[y][w-1-x] on [n][h][w][noc] 8-bit frames:
+hipError_t launch_mirror_u8(const uint8_t* src, uint8_t* dst, int nframes, int w, int h, int noc, hipStream_t s);
+hipError_t launch_lr_check(const float* disp, const float* other, uint8_t* mask, int nframes, int w, int h, float alpha,
+                           float beta, hipStream_t s);
+hipError_t launch_disparity_fill(const float* disp, const uint8_t* mask, float* out, int nframes, int w, int h, int mode,
+                                 hipStream_t s);
+// forward and mirror level disparities to both views' full-resolution disparities and masks in one launch
+// (ofdis_batch_upsample_lr; outputs may be null), for original widths upsample_lr_fuses() accepts ...
+bool upsample_lr_fuses(int wo);
+size_t upsample_lr_row_bytes(int wo);  // LDS per output row
+hipError_t launch_upsample_lr(const float* fw, const float* mir, float* out_l, float* out_r, uint8_t* mask_l, uint8_t* mask_r,
+                              int nframes, int sw, int sh, int sc_l, int left, int top, int wo, int ho, int fill_mode,
+                              float alpha, float beta, hipStream_t s);
+// ... and, above them, the first step of the composition: U and DR = -Dm un-mirrored, materialised
+hipError_t launch_lr_materialise(const float* fw, const float* mir, float* u, float* dr, int nframes, int sw, int sh, int sc_l,
+                                 int left, int top, int wo, int ho, hipStream_t s);
 // frame interpolation (include/ofdis.h: ofdis_interpolate; ofdis_interp.hip).  The times travel by value in the launch.
 struct InterpTimes {
   float t[16];  // OFDIS_INTERP_MAX_TIMES

@@ -403,12 +403,19 @@ int refine_level(ofdis_batch* b, const LevelGeom& g, const LevelPlan& pl, const 
   return OFDIS_OK;
 }
 
-// The reverse direction of an OFDIS_BATCH_REVERSE context: the same context with A's planes and B's planes exchanged, the
-// reverse flow buffers in place of the forward ones and the reverse warm start.  Everything else -- frame count, scratch,
-// contract, kernel selection -- stays, so the pass computes what a plain context computes for the swapped pairs.  Done in
-// place (applying it twice restores the context), so that kernel timing records both directions.
+// The second direction of a context, described by a plane set and a result set:
+//   OFDIS_BATCH_REVERSE    planes: A's and B's exchanged; results: flow_rev, from the reverse warm start
+//   OFDIS_BATCH_STEREO_LR  planes: the mirrored, swapped pair's own (in_mir); results: flow_rev, never warm-started
+//                          (initflow_rev stays null on such a context)
+// Everything else -- frame count, scratch, contract, kernel selection, the level plan -- stays, so the pass computes what a
+// plain context computes for that pair.  Done in place (applying it twice restores the context), so that kernel timing records
+// both directions.
+static bool has_second_direction(const ofdis_batch& b) { return b.reverse || b.stereo_lr; }
 static void swap_direction(ofdis_batch* b) {
-  for (int k = 0; k < 3; ++k) std::swap(b->in[k], b->in[3 + k]);
+  if (b->stereo_lr)
+    for (int k = 0; k < 6; ++k) std::swap(b->in[k], b->in_mir[k]);
+  else
+    for (int k = 0; k < 3; ++k) std::swap(b->in[k], b->in[3 + k]);
   std::swap(b->flow, b->flow_rev);
   std::swap(b->initflow, b->initflow_rev);
 }
@@ -516,7 +523,7 @@ static int run_levels(ofdis_batch* b, hipStream_t s) {
   if (verbose > 1) printf("TIME (Grid Memo. Alloc. ) (ms): %3g\n", 0.0);  // buffers live in the batch context
   for (int sl = p.sc_f; sl >= p.sc_l; --sl)
     if (int rc = run_one_level(b, sl, s)) return rc;
-  if (b->reverse) {  // the same levels on the swapped pairs, one direction after the other on `s`
+  if (has_second_direction(*b)) {  // the same levels on the second direction's pairs, one direction after the other on `s`
     swap_direction(b);
     int rc = OFDIS_OK;
     for (int sl = p.sc_f; sl >= p.sc_l && !rc; --sl) rc = run_one_level(b, sl, s);

@@ -3,13 +3,17 @@ run_DE_* binaries do (run_dense.cpp:185-431), for a list of pairs at once and wi
 8-bit frames, pad + pyramid + Sobel on the device, the hot path, x 2^lv_l upsample + crop on the device, write Middlebury .flo
 (.pfm with --stereo).
 
-    python tools/flow_images.py [--rgb] [--stereo] [--op 1..4] [--fused] [--reverse] img1a img1b out1.flo [img2a img2b out2.flo ...]
+    python tools/flow_images.py [--rgb] [--stereo [--lr [--fill MODE]]] [--op 1..4] [--fused] [--reverse] img1a img1b out1.flo [img2a img2b out2.flo ...]
 
 All pairs must have one size.  --fused selects the FMA / fast-reciprocal arithmetic contract (default: the exact one, bit for
 bit what run_OF_INT / run_OF_RGB write).  --reverse (optical flow only) also writes, next to <stem>.flo, the reverse flow
 <stem>.rev.flo (second image to first) and the forward-backward consistency masks <stem>.mask.pgm / <stem>.rev.mask.pgm
 (binary PGM, maxval 2, the raw codes: 0 consistent, 1 inconsistent, 2 target outside the image; ofdis_batch_upsample_bidir
-with the default alpha 0.01 and beta 0.5)."""
+with the default alpha 0.01 and beta 0.5).  --stereo --lr (the third argument of a pair is then a NAME, not a file) writes both
+views of a stereo pair through an OFDIS_BATCH_STEREO_LR context and ofdis_batch_upsample_lr: <name>_left.pfm and
+<name>_right.pfm (disparity magnitudes as Middlebury stores them, rows bottom-up, +inf = unknown) and the left-right masks
+<name>_left_mask.pgm / <name>_right_mask.pgm (the same codes).  --fill none | invalidate | background (default none) says what
+happens to the pixels the masks flag (ofdis_disparity_fill)."""
 import os
 import struct
 import sys
@@ -50,6 +54,15 @@ def write_pfm(path, disp):  # run_dense.cpp:60-81: rows bottom-up, values negate
         f.write(np.ascontiguousarray(-disp[::-1], np.float32).tobytes())
 
 
+def write_pfm_magnitude(path, disp, sign):
+    """sign * disp >= 0 (left view: -1, right view: +1), rows bottom-up, little endian; an invalidated pixel stays +inf"""
+    h, w = disp.shape[:2]
+    mag = np.where(np.isinf(disp), np.float32(np.inf), np.float32(sign) * disp).astype(np.float32)
+    with open(path, "wb") as f:
+        f.write(b"Pf\n%d %d\n-1.000000\n" % (w, h))
+        f.write(np.ascontiguousarray(mag[::-1]).tobytes())
+
+
 def write_pgm(path, mask):
     h, w = mask.shape
     with open(path, "wb") as f:
@@ -58,8 +71,9 @@ def write_pgm(path, mask):
 
 
 def main(argv):
-    opts = {"--rgb": False, "--stereo": False, "--fused": False, "--reverse": False}
+    opts = {"--rgb": False, "--stereo": False, "--fused": False, "--reverse": False, "--lr": False}
     op = 2
+    fill = "none"
     args = []
     it = iter(argv)
     for a in it:
@@ -67,12 +81,19 @@ def main(argv):
             opts[a] = True
         elif a == "--op":
             op = int(next(it))
+        elif a == "--fill":
+            fill = next(it)
         else:
             args.append(a)
     if not args or len(args) % 3:
         sys.exit(__doc__)
     if opts["--reverse"] and opts["--stereo"]:
-        sys.exit("--reverse: there is no reverse direction in stereo mode")
+        sys.exit("--reverse: there is no reverse direction in stereo mode; the right view of a stereo pair is --lr")
+    fills = {"none": capi.FILL_NONE, "invalidate": capi.FILL_INVALIDATE, "background": capi.FILL_BACKGROUND}
+    if opts["--lr"] and not opts["--stereo"]:
+        sys.exit("--lr needs --stereo")
+    if fill not in fills or (fill != "none" and not opts["--lr"]):
+        sys.exit("--fill none | invalidate | background, with --stereo --lr")
     noc = 3 if opts["--rgb"] else 1
     trip = [args[k:k + 3] for k in range(0, len(args), 3)]
     frames_a = [load(t[0], noc) for t in trip]
@@ -83,10 +104,23 @@ def main(argv):
     capi.set_tuning(contract=1 if opts["--fused"] else 0)
     p = oppoint(op, w, h, noc=noc).copy(selectmode=2 if opts["--stereo"] else 1)
     p.width, p.height = padded_size(w, h, p.sc_f)
-    b = capi.Batch(p, len(trip), reverse=opts["--reverse"])
+    b = capi.Batch(p, len(trip), reverse=opts["--reverse"], stereo_lr=opts["--lr"])
     da, db = capi.Dev(np.stack(frames_a)), capi.Dev(np.stack(frames_b))
     b.build_pyramids_u8(da.ptr, db.ptr, w, h)
     b.run()
+    if opts["--lr"]:                 # both views and both masks in one launch
+        left, right, mask_l, mask_r = b.upsample_lr(w, h, fills[fill])
+        b.close()
+        da.free()
+        db.free()
+        for k, t in enumerate(trip):
+            write_pfm_magnitude(t[2] + "_left.pfm", left[k], -1)
+            write_pfm_magnitude(t[2] + "_right.pfm", right[k], 1)
+            write_pgm(t[2] + "_left_mask.pgm", mask_l[k])
+            write_pgm(t[2] + "_right_mask.pgm", mask_r[k])
+            print(f"{t[2]}_left.pfm, _right.pfm, _left_mask.pgm, _right_mask.pgm: {w}x{h}, fill {fill}, consistent "
+                  f"{np.mean(mask_l[k] == 0):.3f} / {np.mean(mask_r[k] == 0):.3f} of the pixels")
+        return
     if opts["--reverse"]:            # both directions and both masks in one launch; the forward flow is upsample()'s
         full, rev, mask_fw, mask_rev = b.upsample_bidir(w, h)
     else:
