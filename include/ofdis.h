@@ -354,6 +354,44 @@ int ofdis_batch_upsample(ofdis_batch* b, float* out_dev, int width_org, int heig
 int ofdis_batch_upsample_frames(ofdis_batch* b, int first_frame, int count, float* out_dev, int width_org,
                                 int height_org, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Compact output encodings.  The full-resolution fp32 result is four times the bytes most bulk consumers keep (fp16 in
+ * memory, 16-bit fixed point in KITTI-style files, clipped 8-bit planes in two-stream datasets), and over a PCIe link the
+ * download of that result is what bounds a host loop.  An encoding is applied per value v (each component of a flow vector
+ * on its own); the output keeps the AoS order of the fp32 result, [..][2] or [..][1] in stereo-depth mode.  Every operation is
+ * a separately rounded fp32 operation, independent of the arithmetic contract:
+ *   OFDIS_ENC_F32  the bits of v unchanged (accepted everywhere, so that a caller has one code path)
+ *   OFDIS_ENC_F16  IEEE binary16 of v, round to nearest even; gradual underflow (subnormal halves are produced, not flushed);
+ *                  |v| >= 65520 gives +-inf; NaN gives some NaN.  scale and offset are ignored
+ *   OFDIS_ENC_U16 (M = 65535), OFDIS_ENC_U8 (M = 255):
+ *                  t = v * scale + offset   (two operations);  t = fminf(fmaxf(t, 0), M)   (IEEE: a NaN becomes 0);
+ *                  q = (int)floorf(t + 0.5f)                   (a tie x.5 rounds up)
+ *                  A consumer decodes v ~ (q - offset) / scale.  KITTI flow .png is {U16, 64, 32768}, KITTI disparity of the
+ *                  left view {U16, -256, 0} (the left-view result is <= 0), the two-stream "bound 20" format {U8, 255/40, 127.5}
+ * OFDIS_ERR_INVALID before any device work: a NULL encoding, an unknown type; for the integer types a scale that is zero or
+ * not finite, an offset that is not finite.  of_dis_amd/encoding.py states the same arithmetic in numpy.
+ * ------------------------------------------------------------------------------------------- */
+enum { OFDIS_ENC_F32 = 0, OFDIS_ENC_F16 = 1, OFDIS_ENC_U16 = 2, OFDIS_ENC_U8 = 3 };
+typedef struct ofdis_encoding {
+  int   type;            /* OFDIS_ENC_* */
+  float scale, offset;   /* integer types only */
+} ofdis_encoding;
+size_t ofdis_encoding_bytes(int type);   /* bytes per element: 4, 2, 2, 1; 0 for an unknown type */
+/* Materialised: n fp32 values of the device array `src` into the device array `dst` (ofdis_encoding_bytes(type) bytes each).
+ * Not in place: src == dst is OFDIS_ERR_INVALID, like NULL pointers.  16-byte loads and stores where both arrays are 16-byte
+ * aligned (what ofdis_dev_alloc returns), element by element otherwise.  Enqueues on `stream`. */
+int ofdis_encode(const float* src, void* dst, size_t n, const ofdis_encoding* enc, void* stream);
+/* ofdis_batch_upsample_frames writing the encoded result directly: out = device [count][height_org][width_org][C] elements
+ * (C = 2, or 1 in stereo-depth mode).  Bit-identical to ofdis_encode applied to what ofdis_batch_upsample_frames writes for
+ * the same arguments, for both contracts and every kind of context (of an OFDIS_BATCH_REVERSE or OFDIS_BATCH_STEREO_LR
+ * context: the forward result); the fp32 array is never written.  A lane encodes in registers and issues one 16-byte store per
+ * output row where the rows' byte length and `out` are multiples of 16 bytes; other sizes take narrower stores, same bytes.
+ * `out` is aligned to its element size (OFDIS_ENC_F32 with two channels: to 16 bytes, as for ofdis_batch_upsample_frames,
+ * whose kernel that route is); nothing outside it is written.  Joins a pipelined pass by itself.  Argument errors: those of
+ * ofdis_batch_upsample_frames and of the encoding. */
+int ofdis_batch_upsample_frames_enc(ofdis_batch* b, int first_frame, int count, void* out, int width_org, int height_org,
+                                    const ofdis_encoding* enc, void* stream);
+
 /* Kernel timing for the roofline report: when enabled, ofdis_batch_run brackets every launch of
  * the named kernel class with hipEvents on `stream`; ofdis_batch_kernel_time returns the summed
  * milliseconds and launch count since the last reset (synchronises the events). */

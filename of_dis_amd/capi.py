@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "ofdis_batch_download_reverse", "ofdis_batch_upsample_bidir", "ofdis_fb_check",
     "ofdis_interpolate", "ofdis_batch_interpolate",
     "ofdis_batch_flow_mirror", "ofdis_batch_level_flow_mirror", "ofdis_lr_check", "ofdis_disparity_fill", "ofdis_batch_upsample_lr",
+    "ofdis_encoding_bytes", "ofdis_encode", "ofdis_batch_upsample_frames_enc",
 ]
 BATCH_REVERSE = 1  # include/ofdis.h: OFDIS_BATCH_REVERSE
 BATCH_STEREO_LR = 2  # OFDIS_BATCH_STEREO_LR
@@ -47,6 +48,7 @@ LR_FUSED_MAX_WIDTH = 4096  # OFDIS_LR_FUSED_MAX_WIDTH
 FB_ALPHA, FB_BETA = 0.01, 0.5  # OFDIS_FB_ALPHA / OFDIS_FB_BETA
 FB_CONSISTENT, FB_INCONSISTENT, FB_OUTSIDE = 0, 1, 2
 INTERP_MAX_TIMES = 16  # OFDIS_INTERP_MAX_TIMES
+ENC_F32, ENC_F16, ENC_U16, ENC_U8 = 0, 1, 2, 3  # OFDIS_ENC_*
 OFDIS_VERSION = 3  # include/ofdis.h: the struct layouts below (OfdisTuning: 20 ints) belong to this ABI version
 
 
@@ -56,6 +58,23 @@ class OfdisTuning(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("gray8", "rgb12", "rgb12_lpp", "fused_tv", "fused_mw_max", "fused_split",
                                        "finish_fusion", "fused_strip", "prep_band_rows", "graph", "flow_dma", "flow_whole",
                                        "fused_xcu_max", "fused_tp_pipe", "fused_xcu_spin", "contract", "fused_xcu_drop", "prep_densify", "fused_tall_group", "fused_rgb_min")]
+
+
+class Encoding(C.Structure):
+    """include/ofdis.h: ofdis_encoding -- an output format of the full-resolution result.  of_dis_amd/encoding.py has the
+    numpy model of its arithmetic, the presets and the decoder."""
+    _fields_ = [("type", C.c_int), ("scale", C.c_float), ("offset", C.c_float)]
+
+    def __init__(self, type=ENC_F32, scale=1.0, offset=0.0):
+        super().__init__(int(type), float(scale), float(offset))
+
+    @property
+    def dtype(self):
+        """numpy dtype of one encoded element"""
+        return np.dtype({ENC_F32: np.float32, ENC_F16: np.float16, ENC_U16: np.uint16, ENC_U8: np.uint8}[self.type])
+
+    def __repr__(self):
+        return f"Encoding(type={self.type}, scale={self.scale!r}, offset={self.offset!r})"
 
 
 class OfdisError(RuntimeError):
@@ -161,6 +180,10 @@ def lib():
         L.ofdis_disparity_fill.argtypes = [VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, VP]
         L.ofdis_batch_upsample_lr.argtypes = [VP, C.c_int, C.c_int, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_float,
                                               C.c_float, VP]
+        L.ofdis_encoding_bytes.restype = C.c_size_t
+        L.ofdis_encoding_bytes.argtypes = [C.c_int]
+        L.ofdis_encode.argtypes = [VP, VP, C.c_size_t, C.POINTER(Encoding), VP]
+        L.ofdis_batch_upsample_frames_enc.argtypes = [VP, C.c_int, C.c_int, VP, C.c_int, C.c_int, C.POINTER(Encoding), VP]
         _lib = L
     return _lib
 
@@ -452,6 +475,16 @@ def disparity_fill(disp, mask, mode, in_place=False):
     return do.get(disp.shape, _f32)
 
 
+def encode(array, enc):
+    """ofdis_encode on the device: a float32 array of any shape -> the same shape in enc.dtype."""
+    a = _f(array)
+    out_bytes = a.size * lib().ofdis_encoding_bytes(enc.type)  # (0 for an unknown type: the library rejects it below)
+    ds, dd = Dev(a), Dev(nbytes=max(1, out_bytes))
+    check(lib().ofdis_encode(ds.ptr, dd.ptr, a.size, C.byref(enc), None))
+    check(lib().ofdis_sync(None))
+    return dd.get(a.shape, enc.dtype)
+
+
 def _times(times):
     t = np.ascontiguousarray(np.atleast_1d(np.asarray(times, _f32)).ravel())
     return t, t.ctypes.data_as(FP)
@@ -593,6 +626,16 @@ class Batch:
         check(lib().ofdis_sync(stream))
         check(lib().ofdis_memcpy_d2h(out.ctypes.data, d.ptr, out.nbytes))
         return out
+
+    def upsample_frames_enc(self, first, count, width_org, height_org, enc, stream=None):
+        """ofdis_batch_upsample_frames_enc: the full-resolution result of frames [first, first + count) written in the
+        encoding `enc` (an Encoding), as a host array [count][height_org][width_org][nop] of enc.dtype."""
+        shape = (count, height_org, width_org, self.p.nop)
+        nbytes = int(np.prod(shape, dtype=np.int64)) * lib().ofdis_encoding_bytes(enc.type)
+        d = Dev(nbytes=max(1, nbytes))
+        check(lib().ofdis_batch_upsample_frames_enc(self.h, first, count, d.ptr, width_org, height_org, C.byref(enc), stream))
+        check(lib().ofdis_sync(stream))
+        return d.get(shape, enc.dtype)
 
     def download_all(self):
         w, h = self.p.level_size(self.p.sc_l)

@@ -195,4 +195,49 @@ bool write_pfm(const std::string& path, const float* disp, int width, int height
   return ok;
 }
 
+// binary PGM of one component of an interleaved integer array; 16-bit samples most significant byte first (the PNM rule)
+bool write_pgm_plane(const std::string& path, const void* samples, int width, int height, int channels, int channel,
+                     int sample_bytes, std::string* err) {
+  FILE* f = fopen(path.c_str(), "wb");
+  if (!f) { *err = "WriteFile: could not open file " + path; return false; }
+  fprintf(f, "P5\n%d %d\n%d\n", width, height, sample_bytes == 2 ? 65535 : 255);
+  const size_t n = (size_t)width * height;
+  std::vector<uint8_t> plane(n * sample_bytes);
+  if (sample_bytes == 2) {
+    const uint16_t* q = (const uint16_t*)samples;
+    for (size_t i = 0; i < n; ++i) {
+      const uint16_t v = q[i * channels + channel];
+      plane[2 * i] = (uint8_t)(v >> 8);
+      plane[2 * i + 1] = (uint8_t)(v & 255);
+    }
+  } else {
+    const uint8_t* q = (const uint8_t*)samples;
+    for (size_t i = 0; i < n; ++i) plane[i] = q[i * channels + channel];
+  }
+  const bool ok = fwrite(plane.data(), 1, plane.size(), f) == plane.size();
+  fclose(f);
+  if (!ok) *err = "WriteFile: problem writing data to " + path;
+  return ok;
+}
+
+// IEEE binary16 -> binary32, exact (subnormals, infinities and NaNs included)
+void half_to_float(const uint16_t* src, float* dst, size_t n) {
+  for (size_t i = 0; i < n; ++i) {
+    const uint32_t h = src[i], sign = (h & 0x8000u) << 16;
+    uint32_t e = (h >> 10) & 31, m = h & 1023, bits;
+    if (e == 31) {
+      bits = sign | 0x7f800000u | (m << 13);
+    } else if (e != 0) {
+      bits = sign | ((e + 112) << 23) | (m << 13);
+    } else if (m == 0) {
+      bits = sign;
+    } else {  // subnormal half: normalise
+      e = 113;
+      while (!(m & 1024)) { m <<= 1; --e; }
+      bits = sign | (e << 23) | ((m & 1023) << 13);
+    }
+    memcpy(dst + i, &bits, sizeof(bits));
+  }
+}
+
 }  // namespace ofdis_host

@@ -23,5 +23,12 @@ bool read_image(const std::string& path, int want_channels, Image8* out, std::st
 bool write_flo(const std::string& path, const float* flow_uv, int width, int height, std::string* err);
 // stereo-depth result (run_dense.cpp:60-81): one channel, PFM
 bool write_pfm(const std::string& path, const float* disp, int width, int height, std::string* err);
+// Integer-encoded results (run_*_seq --link u8 / u16): component `channel` of the interleaved array
+// samples[height][width][channels] (sample_bytes 1 or 2, host byte order) as a binary PGM (P5), maxval 255 or 65535; 16-bit
+// samples are written most significant byte first, as PNM defines.
+bool write_pgm_plane(const std::string& path, const void* samples, int width, int height, int channels, int channel,
+                     int sample_bytes, std::string* err);
+// IEEE binary16 values to float, exactly (run_*_seq --link f16 widens on the host before it writes .flo / .pfm)
+void half_to_float(const uint16_t* src, float* dst, size_t n);
 
 }  // namespace ofdis_host

@@ -3,7 +3,8 @@
 // With -DOFDIS_MODE=2: run_DE_INT_seq / run_DE_RGB_seq, the stereo-depth binaries' counterpart (one displacement channel,
 // "img1 img2 out.pfm" per line).
 //
-//   run_OF_INT_seq pairs.txt [--gpus N | --devices d0,d1,..] [--chunk C] [--depth D] [--dry-run 1] [oppoint 1-4 | p1 .. p20]
+//   run_OF_INT_seq pairs.txt [--gpus N | --devices d0,d1,..] [--chunk C] [--depth D] [--link FORMAT] [--dry-run 1]
+//                  [oppoint 1-4 | p1 .. p20]
 //
 // pairs.txt: one pair per line, "img1 img2 out.flo" (blank lines and lines starting with # are skipped); all images of one
 // size.  The parameter block after the options is the single-pair binaries' (README.md:48-88).
@@ -23,6 +24,14 @@
 // contract every .flo is byte-identical to what the single-pair binary writes for that pair, whatever the chunk size and
 // the number of GPUs (tests/test_cli.py::test_sequence_driver_*).
 //
+// --link f32|f16|u8:BOUND|u16:SCALE:OFFSET|kitti: the format the result takes over the link (include/ofdis.h: ofdis_encoding;
+// ofdis_batch_upsample_frames_enc writes it directly).  The full-resolution fp32 flow is four times the 8-bit frames that went
+// up, so the download bounds the device stage; the device buffer, the pinned chunk buffer and the download shrink to the
+// encoded size.  f32 (the default): as above.  f16: half precision over the link, widened on the host, the usual .flo / .pfm
+// with values rounded to half precision.  u8:BOUND = {U8, 255 / (2 BOUND), 127.5}, u16:SCALE:OFFSET, kitti = {U16, 64, 32768}
+// (run_DE_*_seq: {U16, -256, 0}, the KITTI disparity of the left view): binary PGM planes <out>.u.pgm and <out>.v.pgm (stereo
+// depth: <out>.pgm), maxval 255 or 65535, 16-bit samples big-endian; of_dis_amd/encoding.py decodes them.
+//
 // --devices 0,0 puts two shares on one device (how the two-GPU split is tested on a one-GPU box).
 // --dry-run 1 prints the partition ("share r: device d pairs lo..hi") and exits without touching a device or a file
 // (tests/test_cli.py checks it against of_dis_amd.shard.frame_range on the CPU).
@@ -33,6 +42,7 @@
 #include <sys/time.h>
 
 #include <algorithm>
+#include <cmath>
 #include <atomic>
 #include <condition_variable>
 #include <deque>
@@ -114,7 +124,7 @@ struct Chunk {
   // (pinned: ofdis_host_alloc -- the asynchronous copies are DMAs only from / to page-locked memory)
   uint8_t *ha = nullptr, *hb = nullptr;
   int init_upto = 0;
-  float* full = nullptr;            // [C][h][w][2] full-resolution flows
+  uint8_t* full = nullptr;          // [C][h][w][2] full-resolution flows, in the encoding of the link
   std::vector<char> ok;
 };
 // One slot of the device stage: a resident context with its own compute stream and device buffers.  The copies do NOT run on
@@ -126,7 +136,7 @@ struct Slot {
   ofdis_batch* b = nullptr;
   void* stream = nullptr;           // pyramids, the hot path, upsample
   void *da = nullptr, *db = nullptr;
-  float* dfull = nullptr;
+  void* dfull = nullptr;            // the chunk's result in the encoding of the link
   void *ev_up = nullptr, *ev_done = nullptr, *ev_down = nullptr;  // upload complete / kernels complete / download complete
   Chunk* chunk = nullptr;           // the chunk in flight on this slot, or null
 };
@@ -160,7 +170,7 @@ class ChunkQueue {  // a blocking FIFO of chunk pointers
 // device stage N times, no .flo is written -- what the device stage (link + kernels) sustains when neither the decoder nor
 // the file system holds it back (tools/seq_probe.py).
 void run_share(const std::vector<Pair>& pairs, const ofdis_params& p0, int width_org, int height_org, int chunk, int depth,
-               int device_bench, int io_threads, Share* sh) {
+               int device_bench, int io_threads, const ofdis_encoding& link, Share* sh) {
   const int n_share = sh->hi - sh->lo;
   if (n_share < 1) return;
   auto bail = [&](const char* what) { sh->error = std::string(what) + ": " + ofdis_last_error(); sh->failed = n_share; };
@@ -176,6 +186,7 @@ void run_share(const std::vector<Pair>& pairs, const ofdis_params& p0, int width
   const int D = std::max(1, std::min(depth, device_bench > 0 ? device_bench : (n_share + C - 1) / C));  // slots in flight on the device
   const size_t img_bytes = (size_t)width_org * height_org * OFDIS_NOC;
   const size_t flo_floats = (size_t)OFDIS_NCH * width_org * height_org;
+  const size_t flo_bytes = flo_floats * ofdis_encoding_bytes(link.type);  // one pair's result as it crosses the link
   std::vector<Slot> slots(D);
   // chunk buffers: one being decoded, D on the device, one being written
   std::vector<Chunk> bufs(D + 2);
@@ -193,7 +204,7 @@ void run_share(const std::vector<Pair>& pairs, const ofdis_params& p0, int width
     if (!sl.ev_up || !sl.ev_done || !sl.ev_down) { bail("ofdis_event_create"); ok = false; break; }
     sl.da = ofdis_dev_alloc(img_bytes * C);
     sl.db = ofdis_dev_alloc(img_bytes * C);
-    sl.dfull = (float*)ofdis_dev_alloc(flo_floats * sizeof(float) * C);
+    sl.dfull = ofdis_dev_alloc(flo_bytes * C);
     if (!sl.stream || !sl.da || !sl.db || !sl.dfull) { bail("slot allocation"); ok = false; break; }
   }
   // (page-locking memory costs ~0.25 ms per MB, a 64-pair chunk of 1024x436 frames is 285 MB: the buffers are allocated by the
@@ -203,7 +214,7 @@ void run_share(const std::vector<Pair>& pairs, const ofdis_params& p0, int width
     if (c.ha) return true;
     c.ha = (uint8_t*)ofdis_host_alloc(img_bytes * C);
     c.hb = (uint8_t*)ofdis_host_alloc(img_bytes * C);
-    c.full = (float*)ofdis_host_alloc(flo_floats * sizeof(float) * C);
+    c.full = (uint8_t*)ofdis_host_alloc(flo_bytes * C);
     c.ok.assign(C, 0);
     return c.ha && c.hb && c.full;
   };
@@ -214,6 +225,7 @@ void run_share(const std::vector<Pair>& pairs, const ofdis_params& p0, int width
     std::atomic<int> written{0};    // .flo files of this share that exist now
     std::atomic<bool> stop{false};  // the device stage gave up: the reader stops feeding it
     std::thread reader([&] {  // decode (cv::imread in the reference, run_dense.cpp:208-209)
+      (void)ofdis_set_device(sh->device);  // (this thread page-locks the chunk buffers: on the share's device, not on device 0)
       for (int ci = 0; ci < n_chunks && !stop; ++ci) {
         const int c0 = device_bench > 0 ? sh->lo : sh->lo + ci * C;
         Chunk* c = free_q.pop();
@@ -264,18 +276,38 @@ void run_share(const std::vector<Pair>& pairs, const ofdis_params& p0, int width
       ready_q.push(end);
     });
     const bool discard = device_bench > 0;
-    std::thread writer([&] {  // one Middlebury .flo per pair (run_dense.cpp:16-57)
+    auto write_float = [&](const std::string& out, const float* v, std::string* err) {
+#if OFDIS_MODE == 2
+      return ofdis_host::write_pfm(out, v, width_org, height_org, err);
+#else
+      return ofdis_host::write_flo(out, v, width_org, height_org, err);
+#endif
+    };
+    // one result per pair: Middlebury .flo (run_dense.cpp:16-57) / .pfm, or the PGM planes of an integer encoding
+    auto write_pair = [&](const std::string& out, const uint8_t* q, std::string* err) {
+      if (link.type == OFDIS_ENC_F32) return write_float(out, (const float*)q, err);
+      if (link.type == OFDIS_ENC_F16) {
+        std::vector<float> wide(flo_floats);
+        ofdis_host::half_to_float((const uint16_t*)q, wide.data(), flo_floats);
+        return write_float(out, wide.data(), err);
+      }
+      const int sb = (int)ofdis_encoding_bytes(link.type);
+#if OFDIS_MODE == 2
+      return ofdis_host::write_pgm_plane(out + ".pgm", q, width_org, height_org, 1, 0, sb, err);
+#else
+      return ofdis_host::write_pgm_plane(out + ".u.pgm", q, width_org, height_org, 2, 0, sb, err) &&
+             ofdis_host::write_pgm_plane(out + ".v.pgm", q, width_org, height_org, 2, 1, sb, err);
+#endif
+    };
+    std::thread writer([&] {
+      (void)ofdis_set_device(sh->device);
       for (;;) {
         Chunk* c = done_q.pop();
         if (c->m == 0) break;
         parallel_for(discard ? 0 : c->m, io_threads, [&](int k) {
           if (!c->ok[k]) return;
           std::string err;
-#if OFDIS_MODE == 2
-          if (!ofdis_host::write_pfm(pairs[c->c0 + k].out, c->full + k * flo_floats, width_org, height_org, &err))
-#else
-          if (!ofdis_host::write_flo(pairs[c->c0 + k].out, c->full + k * flo_floats, width_org, height_org, &err))
-#endif
+          if (!write_pair(pairs[c->c0 + k].out, c->full + k * flo_bytes, &err))
             fprintf(stderr, "%s\n", err.c_str());
           else
             ++written;
@@ -296,10 +328,10 @@ void run_share(const std::vector<Pair>& pairs, const ofdis_params& p0, int width
         if (!rc) rc = ofdis_batch_build_pyramids_u8(sl.b, (const uint8_t*)sl.da, (const uint8_t*)sl.db, width_org, height_org, sl.stream);
       }
       if (!rc) rc = ofdis_batch_run(sl.b, sl.stream);
-      if (!rc) rc = ofdis_batch_upsample_frames(sl.b, 0, c->m, sl.dfull, width_org, height_org, sl.stream);
+      if (!rc) rc = ofdis_batch_upsample_frames_enc(sl.b, 0, c->m, sl.dfull, width_org, height_org, &link, sl.stream);
       if (!rc) rc = ofdis_event_record(sl.ev_done, sl.stream);
       if (!rc) rc = ofdis_stream_wait_event(s_out, sl.ev_done);
-      if (!rc) rc = ofdis_memcpy_d2h_async(c->full, sl.dfull, flo_floats * sizeof(float) * c->m, s_out);
+      if (!rc) rc = ofdis_memcpy_d2h_async(c->full, sl.dfull, flo_bytes * c->m, s_out);
       if (!rc) rc = ofdis_event_record(sl.ev_down, s_out);
       return rc;
     };
@@ -319,6 +351,8 @@ void run_share(const std::vector<Pair>& pairs, const ofdis_params& p0, int width
       }
       sl.chunk = nullptr;
       if (rc) {
+        (void)ofdis_sync(s_out);  // (a download may still be writing the chunk's buffer: drain before it is reused)
+        (void)ofdis_sync(sl.stream);
         free_q.push(c);
         return rc;
       }
@@ -383,15 +417,17 @@ void run_share(const std::vector<Pair>& pairs, const ofdis_params& p0, int width
     if (alloc_failed && sh->error.empty()) sh->error = "pinned host memory";
     sh->chunks_done = n_chunks - bench_skip;
   }
+  // (no copy may still read or write a pinned buffer when it is freed)
+  if (s_in) (void)ofdis_sync(s_in);
+  if (s_out) (void)ofdis_sync(s_out);
+  for (Slot& sl : slots)
+    if (sl.stream) (void)ofdis_sync(sl.stream);
   for (Chunk& c : bufs) {
     ofdis_host_free(c.ha);
     ofdis_host_free(c.hb);
     ofdis_host_free(c.full);
   }
-  if (s_in) (void)ofdis_sync(s_in);
-  if (s_out) (void)ofdis_sync(s_out);
   for (Slot& sl : slots) {
-    if (sl.stream) (void)ofdis_sync(sl.stream);
     ofdis_event_destroy(sl.ev_up);
     ofdis_event_destroy(sl.ev_done);
     ofdis_event_destroy(sl.ev_down);
@@ -405,16 +441,58 @@ void run_share(const std::vector<Pair>& pairs, const ofdis_params& p0, int width
   ofdis_stream_destroy(s_out);
 }
 
+int usage(const char* argv0) {
+  fprintf(stderr, "usage: %s pairs.txt [--gpus N | --devices d0,d1,..] [--chunk C] [--depth D] [--size W H] [--device-bench N] [--io-threads T] "
+                  "[--link f32|f16|u8:BOUND|u16:SCALE:OFFSET|kitti] [--dry-run 1] [oppoint 1-4 | lv_f lv_l maxiter miniter "
+                  "mindprate mindrrate minimgerr patchsz poverl usefbcon patnorm costfct usetvref tv_alpha tv_gamma tv_delta "
+                  "tv_innerit tv_solverit tv_sor verbosity]\n  pairs.txt: one \"img1 img2 out.flo\" per line\n", argv0);
+  return 2;
+}
+
+// one number, nothing after it, finite
+bool parse_float(const std::string& t, float* out) {
+  if (t.empty()) return false;
+  char* end = nullptr;
+  const float v = strtof(t.c_str(), &end);
+  if (end != t.c_str() + t.size() || !std::isfinite(v)) return false;
+  *out = v;
+  return true;
+}
+
+// --link FORMAT (the top of this file) into the library's encoding
+bool parse_link(const std::string& v, ofdis_encoding* enc) {
+  enc->scale = 1.0f;
+  enc->offset = 0.0f;
+  if (v == "f32") { enc->type = OFDIS_ENC_F32; return true; }
+  if (v == "f16") { enc->type = OFDIS_ENC_F16; return true; }
+  if (v == "kitti") {
+    enc->type = OFDIS_ENC_U16;
+    enc->scale = OFDIS_MODE == 2 ? -256.0f : 64.0f;
+    enc->offset = OFDIS_MODE == 2 ? 0.0f : 32768.0f;
+    return true;
+  }
+  if (v.compare(0, 3, "u8:") == 0) {
+    float bound;
+    if (!parse_float(v.substr(3), &bound) || !(bound > 0.0f)) return false;
+    enc->type = OFDIS_ENC_U8;
+    enc->scale = 255.0f / (2.0f * bound);
+    enc->offset = 127.5f;
+    return std::isfinite(enc->scale) && enc->scale != 0.0f;
+  }
+  if (v.compare(0, 4, "u16:") == 0) {
+    const size_t colon = v.find(':', 4);
+    if (colon == std::string::npos) return false;
+    enc->type = OFDIS_ENC_U16;
+    return parse_float(v.substr(4, colon - 4), &enc->scale) && parse_float(v.substr(colon + 1), &enc->offset) && enc->scale != 0.0f;
+  }
+  return false;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
   const double t_start = now_ms();
-  if (argc < 2) {
-    fprintf(stderr, "usage: %s pairs.txt [--gpus N | --devices d0,d1,..] [--chunk C] [--depth D] [--size W H] [--device-bench N] [--io-threads T] [--dry-run 1] [oppoint 1-4 | lv_f lv_l maxiter miniter "
-                    "mindprate mindrrate minimgerr patchsz poverl usefbcon patnorm costfct usetvref tv_alpha tv_gamma tv_delta "
-                    "tv_innerit tv_solverit tv_sor verbosity]\n  pairs.txt: one \"img1 img2 out.flo\" per line\n", argv[0]);
-    return 2;
-  }
+  if (argc < 2) return usage(argv[0]);
   std::vector<Pair> pairs;
   {
     std::ifstream f(argv[1]);
@@ -446,6 +524,8 @@ int main(int argc, char** argv) {
   int device_bench = 0;        // --device-bench N: measurement mode (run_share)
   int io_threads = 0;          // --io-threads T: decoder / writer workers per share (0 = hardware threads / (2 x shares), 1..16)
   bool dry_run = false;
+  ofdis_encoding link = {OFDIS_ENC_F32, 1.0f, 0.0f};  // --link
+  std::string link_name = "f32";
   std::vector<int> devices;
   while (k < argc && argv[k][0] == '-' && argv[k][1] == '-') {
     const std::string opt = argv[k];
@@ -478,6 +558,12 @@ int main(int argc, char** argv) {
       size_w = atoi(val);
       size_h = atoi(argv[k + 2]);
       ++k;
+    } else if (opt == "--link") {
+      if (!parse_link(val, &link)) {
+        fprintf(stderr, "--link %s: not a link format\n", val);
+        return usage(argv[0]);
+      }
+      link_name = val;
     } else if (opt == "--dry-run") {
       dry_run = atoi(val) != 0;
     } else {
@@ -539,7 +625,7 @@ int main(int argc, char** argv) {
   for (int r = 0; r < R; ++r) {
     shares[r].device = devices[r];
     frame_range((int)pairs.size(), r, R, &shares[r].lo, &shares[r].hi);
-    threads.emplace_back(run_share, std::cref(pairs), std::cref(p), width_org, height_org, chunk, depth, device_bench, io_threads, &shares[r]);
+    threads.emplace_back(run_share, std::cref(pairs), std::cref(p), width_org, height_org, chunk, depth, device_bench, io_threads, std::cref(link), &shares[r]);
   }
   for (auto& t : threads) t.join();
   const double t_all = now_ms() - t0;
@@ -554,8 +640,9 @@ int main(int argc, char** argv) {
   if (device_bench > 0)
     for (int r = 0; r < R; ++r)
       printf("DEVICE STAGE (share %d: %d chunks of %d pairs, %d in flight): %.1f pairs/s (upload of the 8-bit frames, pyramids, flow, upsample, "
-             "download of the full-resolution flow; no decoding, no .flo)\n", r, shares[r].chunks_done, shares[r].chunk_pairs, depth,
-             shares[r].ms_compute > 0 ? shares[r].chunks_done * (double)shares[r].chunk_pairs / (shares[r].ms_compute * 1e-3) : 0.0);
+             "download of the full-resolution flow%s%s; no decoding, no .flo)\n", r, shares[r].chunks_done, shares[r].chunk_pairs, depth,
+             shares[r].ms_compute > 0 ? shares[r].chunks_done * (double)shares[r].chunk_pairs / (shares[r].ms_compute * 1e-3) : 0.0,
+             link.type == OFDIS_ENC_F32 ? "" : " as ", link.type == OFDIS_ENC_F32 ? "" : link_name.c_str());
   if (verbosity > 0)
     printf("TIME (%d pairs on %d device share(s), chunk %d, incl. image decoding and .flo writing by %d worker(s) each per share) (ms): %3g  (%.1f pairs/s; start-up %3g ms)\n",
            (int)pairs.size(), R, chunk, io_threads, t_all, pairs.size() / (t_all * 1e-3), t0 - t_start);

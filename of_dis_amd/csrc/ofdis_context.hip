@@ -538,6 +538,51 @@ int ofdis_batch_upsample(ofdis_batch* b, float* out_dev, int width_org, int heig
   return ofdis_batch_upsample_frames(b, 0, b->nframes, out_dev, width_org, height_org, stream);
 }
 
+// ------------------------------------------------------------------------------------ compact output encodings
+size_t ofdis_encoding_bytes(int type) {
+  switch (type) {
+    case OFDIS_ENC_F32: return 4;
+    case OFDIS_ENC_F16: case OFDIS_ENC_U16: return 2;
+    case OFDIS_ENC_U8: return 1;
+  }
+  return 0;
+}
+
+static int encoding_check(const ofdis_encoding* enc) {
+  if (!enc) return fail(OFDIS_ERR_INVALID, "encoding is NULL");
+  if (!ofdis_encoding_bytes(enc->type)) return fail(OFDIS_ERR_INVALID, "unknown encoding type");
+  if (enc->type == OFDIS_ENC_U16 || enc->type == OFDIS_ENC_U8) {
+    if (!std::isfinite(enc->scale) || enc->scale == 0.0f) return fail(OFDIS_ERR_INVALID, "encoding scale must be finite and not zero");
+    if (!std::isfinite(enc->offset)) return fail(OFDIS_ERR_INVALID, "encoding offset must be finite");
+  }
+  return OFDIS_OK;
+}
+
+int ofdis_encode(const float* src, void* dst, size_t n, const ofdis_encoding* enc, void* stream) {
+  if (!src || !dst) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if ((const void*)src == dst) return fail(OFDIS_ERR_INVALID, "ofdis_encode does not work in place");
+  if (int rc = encoding_check(enc)) return rc;
+  if (n == 0) return OFDIS_OK;
+  HIPCHK(launch_encode(src, dst, n, enc->type, enc->scale, enc->offset, (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+int ofdis_batch_upsample_frames_enc(ofdis_batch* b, int first_frame, int count, void* out, int width_org, int height_org,
+                                    const ofdis_encoding* enc, void* stream) {
+  if (!b || !out) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (first_frame < 0 || count < 1 || first_frame > b->nframes - count) return fail(OFDIS_ERR_INVALID, "frame range outside the batch");
+  const ofdis_params& p = b->p;
+  if (width_org < 1 || height_org < 1 || width_org > p.width || height_org > p.height)
+    return fail(OFDIS_ERR_INVALID, "original size exceeds the padded size");
+  if (int rc = encoding_check(enc)) return rc;
+  const LevelGeom& g = b->geom[0];
+  if (int rc = ofdis_batch_join(b, stream)) return rc;
+  HIPCHK(launch_upsample_crop_enc(frame_at(*b, b->flow[0], first_frame), out, count, g.w, g.h, p.sc_l,
+                                  (p.width - width_org) / 2, (p.height - height_org) / 2, width_org, height_org, b->nop,
+                                  enc->type, enc->scale, enc->offset, (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
 // ------------------------------------------------------------------------------------ reverse direction (OFDIS_BATCH_REVERSE)
 const float* ofdis_batch_flow_reverse(const ofdis_batch* b) { return b && b->reverse ? b->flow_rev[0] : nullptr; }
 const float* ofdis_batch_level_flow_reverse(const ofdis_batch* b, int level) {

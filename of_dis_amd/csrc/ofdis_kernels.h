@@ -176,6 +176,12 @@ bool pyr_planes_fuses_down(int w, int h, int noc, int pad);
 // x 2^sc_l, bilinear upsample (cv::resize INTER_LINEAR) and crop of the AoS result (run_dense.cpp:406-414)
 hipError_t launch_upsample_crop(const float* flow, float* out, int nframes, int sw, int sh, int sc_l, int left, int top,
                                 int wo, int ho, int channels, hipStream_t s);
+// the same, written in an output encoding (include/ofdis.h: ofdis_encoding; `type` already validated): out = [nframes][ho][wo]
+// [channels] elements.  OFDIS_ENC_F32 with two channels is launch_upsample_crop.
+hipError_t launch_upsample_crop_enc(const float* flow, void* out, int nframes, int sw, int sh, int sc_l, int left, int top,
+                                    int wo, int ho, int channels, int type, float scale, float offset, hipStream_t s);
+// n fp32 values of a materialised array into that encoding (ofdis_encode)
+hipError_t launch_encode(const float* src, void* dst, size_t n, int type, float scale, float offset, hipStream_t s);
 // forward-backward consistency test (include/ofdis.h: ofdis_fb_check) on full-resolution AoS flows
 hipError_t launch_fb_check(const float* flow, const float* other, uint8_t* mask, int nframes, int w, int h, float alpha,
                            float beta, hipStream_t s);

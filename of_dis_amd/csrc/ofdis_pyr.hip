@@ -382,6 +382,176 @@ hipError_t launch_upsample_crop(const float* flow, float* out, int nframes, int 
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------ result to full resolution, encoded
+// ofdis_batch_upsample_frames_enc: the values of the two kernels above, encoded in registers (include/ofdis.h: ofdis_encoding)
+// and written once.  The kernel is its stores, so a lane still issues ONE 16-byte non-temporal store per output row: it owns
+// the NV = 16 / element size adjacent values of a row -- NV / C columns (C = 2: 4 / 8 columns of 2- / 1-byte elements, C = 1
+// twice as many) -- interpolates them horizontally on the two source rows once and reuses them over the <= 2^sc_l rows of the
+// group, like upsample_crop_kernel.  Lanes are numbered over (row group, 16-byte chunk of the row) so that rows shorter than a
+// workgroup's 4 KB leave no lanes idle.  `align` = the largest power of two <= 16 that divides both the row's byte length and
+// the address of `out`: below 16 (odd widths and the like) a lane writes its chunk in pieces of that size.
+__device__ __forceinline__ void store_chunk16(uint8_t* o, const unsigned (&w)[4], int nb, int align) {
+  if (align >= 16) {  // (then every chunk of a row is whole: nb == 16)
+    __builtin_nontemporal_store((u4){w[0], w[1], w[2], w[3]}, reinterpret_cast<u4*>(o));
+  } else if (align >= 8) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+      if (8 * i < nb) *reinterpret_cast<uint2*>(o + 8 * i) = make_uint2(w[2 * i], w[2 * i + 1]);
+  } else if (align >= 4) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (4 * i < nb) *reinterpret_cast<unsigned*>(o + 4 * i) = w[i];
+  } else if (align >= 2) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+      if (2 * i < nb) *reinterpret_cast<unsigned short*>(o + 2 * i) = (unsigned short)(w[i >> 1] >> (16 * (i & 1)));
+  } else {
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+      if (i < nb) o[i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
+  }
+}
+
+template <int TYPE, int C>
+__global__ __launch_bounds__(256) void upsample_crop_enc_kernel(const float* __restrict__ flow, uint8_t* __restrict__ out,
+                                                                int sw, int sh, int sc_l, int left, int top, int wo, int ho,
+                                                                int chunks, int align, float scale, float offset) {
+  constexpr int NV = EncTraits<TYPE>::per16, NCOL = NV / C;
+  const int f = blockIdx.y;
+  const unsigned id = blockIdx.x * 256u + threadIdx.x;
+  const int grp = (int)(id / (unsigned)chunks), ch = (int)(id - (unsigned)grp * (unsigned)chunks);
+  if (grp > sh) return;
+  const int x = ch * NCOL;  // first column of the lane (< wo: chunks = ceil(wo / NCOL))
+  const int s = 1 << sc_l;
+  const float scf = (float)s, inv = 1.0f / scf;
+  // row groups as in upsample_crop_kernel: k = -1 .. sh-1 (k = 0 .. sh for s = 1, the last one empty)
+  const int k = grp - (s > 1 ? 1 : 0);
+  const int Y0 = max(k * s + s / 2, top), Y1 = min(k * s + s / 2 + s, top + ho);
+  if (Y0 >= Y1) return;
+  const float fy0 = ((float)Y0 + 0.5f) * inv - 0.5f;
+  int sy = (int)floorf(fy0);
+  const bool clamp_lo = sy < 0, clamp_hi = sy >= sh - 1;
+  if (clamp_lo) sy = 0;
+  if (clamp_hi) sy = sh - 1;
+  const int sy1 = min(sy + 1, sh - 1);
+  const float* fl = flow + (size_t)f * sw * sh * C;
+  float r0[NV], r1[NV];  // the lane's values on the two source rows, in memory order
+#pragma unroll
+  for (int c = 0; c < NCOL; ++c) {
+    const int X = min(x + c, wo - 1) + left;  // (columns past the row's end repeat the last one; they are not stored)
+    if constexpr (C == 2) {
+      float2 a0, a1;
+      upsample_h(reinterpret_cast<const float2*>(fl), sw, sy, sy1, X, inv, scf, sc_l > 0, a0, a1);
+      r0[2 * c] = a0.x; r0[2 * c + 1] = a0.y;
+      r1[2 * c] = a1.x; r1[2 * c + 1] = a1.y;
+    } else {
+      upsample_h1(fl, sw, sy, sy1, X, inv, scf, sc_l > 0, r0[c], r1[c]);
+    }
+  }
+  const int row_bytes = wo * C * EncTraits<TYPE>::bytes;
+  const int nb = min(16, row_bytes - ch * 16);
+  for (int Y = Y0; Y < Y1; ++Y) {
+    float fy = ((float)Y + 0.5f) * inv - 0.5f;
+    fy -= floorf(fy);
+    if (clamp_lo || clamp_hi) fy = 0.0f;
+    const float ay = 1.0f - fy;
+    float v[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) v[i] = r0[i] * ay + r1[i] * fy;
+    unsigned w[4];
+    enc_pack16<TYPE>(v, scale, offset, w);
+    store_chunk16(out + ((size_t)f * ho + (Y - top)) * row_bytes + (size_t)ch * 16, w, nb, align);
+  }
+}
+
+// largest power of two <= 16 dividing the address and the byte length of a row
+static int store_align(const void* p, size_t row_bytes) {
+  const size_t v = (size_t)(uintptr_t)p | row_bytes | 16;
+  return (int)(v & (~v + 1));
+}
+
+template <int TYPE>
+static hipError_t launch_upsample_crop_enc_t(const float* flow, void* out, int nframes, int sw, int sh, int sc_l, int left,
+                                             int top, int wo, int ho, int channels, float scale, float offset, hipStream_t s) {
+  const int ncol = EncTraits<TYPE>::per16 / channels;
+  const int chunks = (wo + ncol - 1) / ncol;
+  const long long lanes = (long long)chunks * (sh + 1);
+  const long long row_bytes = (long long)wo * channels * EncTraits<TYPE>::bytes;
+  if (nframes > 65535 || lanes >= (1ll << 31) || row_bytes >= (1ll << 31)) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((lanes + 255) / 256), (unsigned)nframes);
+  const int align = store_align(out, (size_t)row_bytes);
+  if (channels == 1)
+    hipLaunchKernelGGL((upsample_crop_enc_kernel<TYPE, 1>), grid, dim3(256), 0, s, flow, (uint8_t*)out, sw, sh, sc_l, left, top,
+                       wo, ho, chunks, align, scale, offset);
+  else
+    hipLaunchKernelGGL((upsample_crop_enc_kernel<TYPE, 2>), grid, dim3(256), 0, s, flow, (uint8_t*)out, sw, sh, sc_l, left, top,
+                       wo, ho, chunks, align, scale, offset);
+  return hipGetLastError();
+}
+
+hipError_t launch_upsample_crop_enc(const float* flow, void* out, int nframes, int sw, int sh, int sc_l, int left, int top,
+                                    int wo, int ho, int channels, int type, float scale, float offset, hipStream_t s) {
+  switch (type) {
+    case ENC_F32:
+      // the bits unchanged.  Two channels: upsample_crop_kernel itself, which already has this mapping.  One channel: this
+      // file's kernel -- upsample_crop1_kernel stores 4 bytes per lane and row and interpolates every row anew (4.07 against
+      // 1.34 ms per 4096 frames of 1024x436 for the same bits: profiles/README.md)
+      if (channels == 1)
+        return launch_upsample_crop_enc_t<ENC_F32>(flow, out, nframes, sw, sh, sc_l, left, top, wo, ho, channels, scale, offset, s);
+      return launch_upsample_crop(flow, (float*)out, nframes, sw, sh, sc_l, left, top, wo, ho, channels, s);
+    case ENC_F16: return launch_upsample_crop_enc_t<ENC_F16>(flow, out, nframes, sw, sh, sc_l, left, top, wo, ho, channels, scale, offset, s);
+    case ENC_U16: return launch_upsample_crop_enc_t<ENC_U16>(flow, out, nframes, sw, sh, sc_l, left, top, wo, ho, channels, scale, offset, s);
+    case ENC_U8: return launch_upsample_crop_enc_t<ENC_U8>(flow, out, nframes, sw, sh, sc_l, left, top, wo, ho, channels, scale, offset, s);
+  }
+  return hipErrorInvalidValue;
+}
+
+// ofdis_encode on a materialised array: a lane converts the 16 / element size values of one 16-byte store per step (16-byte
+// loads), grid-stride; the values past the last whole store -- every value when src or dst is not 16-byte aligned -- one by one.
+template <int TYPE>
+__global__ __launch_bounds__(256) void encode_kernel(const float* __restrict__ src, uint8_t* __restrict__ dst, size_t n,
+                                                     size_t nvec, float scale, float offset) {
+  constexpr int NV = EncTraits<TYPE>::per16, EB = EncTraits<TYPE>::bytes;
+  const size_t t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = t0; i < nvec; i += stride) {
+    float v[NV];
+#pragma unroll
+    for (int q = 0; q < NV / 4; ++q) {
+      const f4p t = reinterpret_cast<const f4p*>(src)[i * (NV / 4) + q];
+      v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
+    }
+    unsigned w[4];
+    enc_pack16<TYPE>(v, scale, offset, w);
+    reinterpret_cast<u4*>(dst)[i] = (u4){w[0], w[1], w[2], w[3]};
+  }
+  for (size_t i = nvec * NV + t0; i < n; i += stride) {
+    const unsigned q = enc_bits<TYPE>(src[i], scale, offset);
+    if constexpr (EB == 4) reinterpret_cast<unsigned*>(dst)[i] = q;
+    else if constexpr (EB == 2) reinterpret_cast<unsigned short*>(dst)[i] = (unsigned short)q;
+    else dst[i] = (uint8_t)q;
+  }
+}
+
+template <int TYPE>
+static hipError_t launch_encode_t(const float* src, void* dst, size_t n, float scale, float offset, hipStream_t s) {
+  const bool aligned = (((uintptr_t)src | (uintptr_t)dst) & 15) == 0;
+  const size_t nvec = aligned ? n / EncTraits<TYPE>::per16 : 0;
+  const size_t work = nvec > n - nvec * EncTraits<TYPE>::per16 ? nvec : n - nvec * EncTraits<TYPE>::per16;
+  hipLaunchKernelGGL(encode_kernel<TYPE>, dim3(grid_for((long long)work)), dim3(256), 0, s, src, (uint8_t*)dst, n, nvec, scale,
+                     offset);
+  return hipGetLastError();
+}
+
+hipError_t launch_encode(const float* src, void* dst, size_t n, int type, float scale, float offset, hipStream_t s) {
+  switch (type) {
+    case ENC_F32: return launch_encode_t<ENC_F32>(src, dst, n, scale, offset, s);
+    case ENC_F16: return launch_encode_t<ENC_F16>(src, dst, n, scale, offset, s);
+    case ENC_U16: return launch_encode_t<ENC_U16>(src, dst, n, scale, offset, s);
+    case ENC_U8: return launch_encode_t<ENC_U8>(src, dst, n, scale, offset, s);
+  }
+  return hipErrorInvalidValue;
+}
+
 // ------------------------------------------------------------------------------------ forward-backward consistency
 // materialised flows: one pixel per thread, grid-stride over all frames
 __global__ __launch_bounds__(256) void fb_check_kernel(const float2* __restrict__ flow, const float2* __restrict__ other,
