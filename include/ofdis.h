@@ -306,6 +306,43 @@ int ofdis_batch_build_pyramids_u8(ofdis_batch* b, const uint8_t* img_a, const ui
 int ofdis_batch_upload_b_gradients(ofdis_batch* b, int frame, const float* const* im_b_dx, const float* const* im_b_dy,
                                    void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Video sequences: nframes + 1 consecutive frames give nframes pairs, and every frame's planes are built and held once.
+ * ------------------------------------------------------------------------------------------- */
+#define OFDIS_BATCH_SEQUENCE 16u        /* flag of ofdis_batch_create_ex */
+/* An OFDIS_BATCH_SEQUENCE context of `nframes` (still the number of PAIRS, 1..65534; more: OFDIS_ERR_UNSUPPORTED) holds
+ * nframes + 1 frame slots; pair k is (frame k, frame k + 1).  Per level it allocates three input arrays of nframes + 1 frames
+ * -- image, dx, dy -- and nothing for B: ofdis_batch_input kinds 3, 4, 5 are kinds 0, 1, 2 one frame further on
+ * (ofdis_batch_input(b, l, 3 + j) == ofdis_batch_input(b, l, j) + ofdis_batch_input_elems(b, l)), and all six kinds are
+ * returned whatever usefbcon says.  Everything downstream sees ordinary A and B planes: ofdis_batch_run (pipelined
+ * sub-batches, graph replay, the warm start, ofdis_batch_status) and every result call work as on a plain context and give the
+ * bits a plain context gives for img_a = frames[0 .. nframes), img_b = frames[1 .. nframes].  ofdis_batch_interpolate takes
+ * `frames` and `frames + one frame` as img_a and img_b.
+ * Valid with OFDIS_BATCH_REVERSE (the reverse flow of pair k is frame k + 1 -> frame k; B's gradient planes cost nothing
+ * here) and with usefbcon.  OFDIS_ERR_INVALID with OFDIS_BATCH_STEREO_LR and with selectmode 2: a stereo pair is no sequence.
+ * The pair-wise entry points would write a shared slot twice: ofdis_batch_build_pyramids_u8, ofdis_batch_upload and
+ * ofdis_batch_upload_b_gradients return OFDIS_ERR_INVALID on a sequence context; the two calls below return it on any other. */
+/* frame slots of the input arrays: nframes + 1 for a sequence context, nframes for every other, 0 for NULL */
+int ofdis_batch_input_frames(const ofdis_batch* b);
+/* one frame's host pyramid (image, dx, dy in the ofdis_flow() layout) into frame slot 0 .. nframes; enqueues as
+ * ofdis_batch_upload does */
+int ofdis_batch_upload_frame(ofdis_batch* b, int slot, const float* const* im, const float* const* im_dx,
+                             const float* const* im_dy, void* stream);
+/* ofdis_batch_build_pyramids_u8 for the nframes + 1 frames of a sequence, each through the pyramid once, read as a decoder
+ * delivers them: `frames` is a device pointer, row y of frame f starts at frames + f * frame_stride + y * row_pitch and holds
+ * width_org pixels of noc interleaved bytes.  row_pitch = 0 means width_org * noc, frame_stride = 0 means row_pitch *
+ * height_org (both 0: the packed layout of ofdis_batch_build_pyramids_u8).  The luma plane of an NV12 surface is
+ * row_pitch = the surface pitch, frame_stride = pitch * surface height * 3 / 2.  Only the width_org * noc bytes of a row are
+ * ever read: the padding may be uninitialised or belong to another surface.  Gray frames whose width_org, left padding,
+ * `frames`, row_pitch and frame_stride are all multiples of 16 take the 16-byte streaming kernel, as packed frames do.
+ * Same bits as the packed call on the same pixels.  OFDIS_ERR_INVALID: row_pitch < width_org * noc, frame_stride <
+ * row_pitch * height_org, sizes as ofdis_batch_build_pyramids_u8; OFDIS_ERR_UNSUPPORTED: sc_f > 7. */
+int ofdis_batch_build_pyramids_u8_seq(ofdis_batch* b, const uint8_t* frames, size_t row_pitch, size_t frame_stride,
+                                      int width_org, int height_org, void* stream);
+/* Bytes of device memory in the arrays the context holds right now (any context; lazily allocated scratch counts once it
+ * exists; the up to 255 bytes of alignment after each array do not).  0 for NULL. */
+size_t ofdis_batch_device_bytes(const ofdis_batch* b);
+
 /* Warm start (the reference's `initflow`, oflow.cpp:217-220; e.g. the previous frame pair's flow of a video):
  * per frame (w >> (sc_f+1)) x (h >> (sc_f+1)) x 2 floats, AoS.  set_initflow borrows a device array
  * [nframes][ofdis_batch_initflow_elems] (NULL switches the warm start off again); upload_initflow copies one

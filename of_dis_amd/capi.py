@@ -40,9 +40,11 @@ ABI_SYMBOLS = [
     "ofdis_interpolate", "ofdis_batch_interpolate",
     "ofdis_batch_flow_mirror", "ofdis_batch_level_flow_mirror", "ofdis_lr_check", "ofdis_disparity_fill", "ofdis_batch_upsample_lr",
     "ofdis_encoding_bytes", "ofdis_encode", "ofdis_batch_upsample_frames_enc",
+    "ofdis_batch_input_frames", "ofdis_batch_upload_frame", "ofdis_batch_build_pyramids_u8_seq", "ofdis_batch_device_bytes",
 ]
 BATCH_REVERSE = 1  # include/ofdis.h: OFDIS_BATCH_REVERSE
 BATCH_STEREO_LR = 2  # OFDIS_BATCH_STEREO_LR
+BATCH_SEQUENCE = 16  # OFDIS_BATCH_SEQUENCE
 FILL_NONE, FILL_INVALIDATE, FILL_BACKGROUND = 0, 1, 2  # OFDIS_FILL_*
 LR_FUSED_MAX_WIDTH = 4096  # OFDIS_LR_FUSED_MAX_WIDTH
 FB_ALPHA, FB_BETA = 0.01, 0.5  # OFDIS_FB_ALPHA / OFDIS_FB_BETA
@@ -184,6 +186,11 @@ def lib():
         L.ofdis_encoding_bytes.argtypes = [C.c_int]
         L.ofdis_encode.argtypes = [VP, VP, C.c_size_t, C.POINTER(Encoding), VP]
         L.ofdis_batch_upsample_frames_enc.argtypes = [VP, C.c_int, C.c_int, VP, C.c_int, C.c_int, C.POINTER(Encoding), VP]
+        L.ofdis_batch_input_frames.argtypes = [VP]
+        L.ofdis_batch_upload_frame.argtypes = [VP, C.c_int, C.POINTER(FP), C.POINTER(FP), C.POINTER(FP), VP]
+        L.ofdis_batch_build_pyramids_u8_seq.argtypes = [VP, VP, C.c_size_t, C.c_size_t, C.c_int, C.c_int, VP]
+        L.ofdis_batch_device_bytes.restype = C.c_size_t
+        L.ofdis_batch_device_bytes.argtypes = [VP]
         _lib = L
     return _lib
 
@@ -521,15 +528,19 @@ def interpolate(img_a, img_b, flow_fw, flow_rev, times, mask_fw=None, mask_rev=N
 class Batch:
     """ofdis_batch: `nframes` frame pairs of one geometry resident in HBM.  reverse=True: ofdis_batch_create_ex with
     OFDIS_BATCH_REVERSE (every pass also computes the flow B -> A of each pair).  stereo_lr=True: OFDIS_BATCH_STEREO_LR
-    (stereo-depth mode: every pass also runs on the mirrored, swapped pair, which gives the right view's disparity)."""
+    (stereo-depth mode: every pass also runs on the mirrored, swapped pair, which gives the right view's disparity).
+    sequence=True: OFDIS_BATCH_SEQUENCE (nframes + 1 consecutive frames, each held once; pair k = frames k, k + 1; filled
+    through build_pyramids_u8_seq or upload_frame)."""
 
-    def __init__(self, p, nframes, reverse=False, stereo_lr=False):
+    def __init__(self, p, nframes, reverse=False, stereo_lr=False, sequence=False):
         self.p = p.copy()
         self.nframes = nframes
         self.reverse = bool(reverse)
         self.stereo_lr = bool(stereo_lr)
+        self.sequence = bool(sequence)
         self.h = VP()
-        flags = (BATCH_REVERSE if reverse else 0) | (BATCH_STEREO_LR if stereo_lr else 0)
+        flags = ((BATCH_REVERSE if reverse else 0) | (BATCH_STEREO_LR if stereo_lr else 0) |
+                 (BATCH_SEQUENCE if sequence else 0))
         check(lib().ofdis_batch_create_ex(C.byref(self.h), C.byref(self.p), nframes, flags))
 
     def close(self):
@@ -548,6 +559,22 @@ class Batch:
 
     def input_elems(self, level):
         return lib().ofdis_batch_input_elems(self.h, level)
+
+    def input_frames(self):
+        """ofdis_batch_input_frames: frame slots of the input arrays (nframes + 1 for a sequence context)."""
+        return lib().ofdis_batch_input_frames(self.h)
+
+    def device_bytes(self):
+        """ofdis_batch_device_bytes: bytes of device memory in the arrays the context holds right now."""
+        return lib().ofdis_batch_device_bytes(self.h)
+
+    def upload_frame(self, slot, pyr, pyr_dx, pyr_dy, stream=None):
+        """ofdis_batch_upload_frame: one frame's host pyramid (lists over levels 0..sc_f) into frame slot 0..nframes."""
+        n = self.p.sc_f + 1
+        keep = [[_f(x) if x is not None else None for x in pl] for pl in (pyr, pyr_dx, pyr_dy)]
+        check(lib().ofdis_batch_upload_frame(self.h, slot, _ptr_array(keep[0], n), _ptr_array(keep[1], n),
+                                             _ptr_array(keep[2], n), stream))
+        check(lib().ofdis_sync(stream))
 
     def upload(self, frame, pyr_a, pyr_a_dx, pyr_a_dy, pyr_b, stream=None):
         n = self.p.sc_f + 1
@@ -579,6 +606,11 @@ class Batch:
 
     def build_pyramids_u8(self, img_a_ptr, img_b_ptr, width_org, height_org, stream=None):
         check(lib().ofdis_batch_build_pyramids_u8(self.h, img_a_ptr, img_b_ptr, width_org, height_org, stream))
+
+    def build_pyramids_u8_seq(self, frames_ptr, width_org, height_org, row_pitch=0, frame_stride=0, stream=None):
+        """ofdis_batch_build_pyramids_u8_seq: frames_ptr = device pointer to nframes + 1 frames, row y of frame f at
+        frames_ptr + f * frame_stride + y * row_pitch (0, 0: packed)."""
+        check(lib().ofdis_batch_build_pyramids_u8_seq(self.h, frames_ptr, row_pitch, frame_stride, width_org, height_org, stream))
 
     def run(self, stream=None):
         check(lib().ofdis_batch_run(self.h, stream))

@@ -4,7 +4,7 @@
 // "img1 img2 out.pfm" per line).
 //
 //   run_OF_INT_seq pairs.txt [--gpus N | --devices d0,d1,..] [--chunk C] [--depth D] [--link FORMAT] [--dry-run 1]
-//                  [oppoint 1-4 | p1 .. p20]
+//                  [--sequence 1] [oppoint 1-4 | p1 .. p20]
 //
 // pairs.txt: one pair per line, "img1 img2 out.flo" (blank lines and lines starting with # are skipped); all images of one
 // size.  The parameter block after the options is the single-pair binaries' (README.md:48-88).
@@ -31,6 +31,14 @@
 // with values rounded to half precision.  u8:BOUND = {U8, 255 / (2 BOUND), 127.5}, u16:SCALE:OFFSET, kitti = {U16, 64, 32768}
 // (run_DE_*_seq: {U16, -256, 0}, the KITTI disparity of the left view): binary PGM planes <out>.u.pgm and <out>.v.pgm (stereo
 // depth: <out>.pgm), maxval 255 or 65535, 16-bit samples big-endian; of_dis_amd/encoding.py decodes them.
+//
+// --sequence 1 (run_OF_*_seq only): the list is a video, one line per FRAME, "img out.flo" -- out.flo is the flow from this
+// frame to the next -- and the last line "img" alone: N + 1 lines are the N pairs (line k, line k + 1).  Shares are cut over
+// pairs as above.  A chunk of C pairs then decodes and uploads its C + 1 frames once each (pinned buffer and device buffer of
+// C + 1 frames, no second set) into an OFDIS_BATCH_SEQUENCE context, which builds every frame's planes once
+// (ofdis_batch_build_pyramids_u8_seq); the frame two consecutive chunks of a share have in common is copied on the host from
+// the previous chunk's pinned buffer instead of being decoded again.  Same bits, so the same files as the pairs list of the
+// same pairs.
 //
 // --devices 0,0 puts two shares on one device (how the two-GPU split is tested on a one-GPU box).
 // --dry-run 1 prints the partition ("share r: device d pairs lo..hi") and exits without touching a device or a file
@@ -122,8 +130,10 @@ struct Chunk {
   // images, results never used).  The buffers are not zero-filled up front -- a gigabyte of page faults for nothing -- only the
   // slots that would otherwise go to the device undefined are (init_upto: slots below it have been written at least once)
   // (pinned: ofdis_host_alloc -- the asynchronous copies are DMAs only from / to page-locked memory)
+  // --sequence: ha holds the chunk's C + 1 frames (pair k = frames k, k + 1; fok: which were readable) and hb stays null
   uint8_t *ha = nullptr, *hb = nullptr;
   int init_upto = 0;
+  std::vector<char> fok;
   uint8_t* full = nullptr;          // [C][h][w][2] full-resolution flows, in the encoding of the link
   std::vector<char> ok;
 };
@@ -170,7 +180,7 @@ class ChunkQueue {  // a blocking FIFO of chunk pointers
 // device stage N times, no .flo is written -- what the device stage (link + kernels) sustains when neither the decoder nor
 // the file system holds it back (tools/seq_probe.py).
 void run_share(const std::vector<Pair>& pairs, const ofdis_params& p0, int width_org, int height_org, int chunk, int depth,
-               int device_bench, int io_threads, const ofdis_encoding& link, Share* sh) {
+               int device_bench, int io_threads, const ofdis_encoding& link, bool sequence, Share* sh) {
   const int n_share = sh->hi - sh->lo;
   if (n_share < 1) return;
   auto bail = [&](const char* what) { sh->error = std::string(what) + ": " + ofdis_last_error(); sh->failed = n_share; };
@@ -183,6 +193,7 @@ void run_share(const std::vector<Pair>& pairs, const ofdis_params& p0, int width
   p.verbosity = 0;  // (the per-level TIME lines synchronise between stages; the driver prints its own summary)
   const int C = std::min(chunk, n_share);
   sh->chunk_pairs = C;
+  const int F = sequence ? C + 1 : C;  // frames of a chunk's first (--sequence: only) frame buffer
   const int D = std::max(1, std::min(depth, device_bench > 0 ? device_bench : (n_share + C - 1) / C));  // slots in flight on the device
   const size_t img_bytes = (size_t)width_org * height_org * OFDIS_NOC;
   const size_t flo_floats = (size_t)OFDIS_NCH * width_org * height_org;
@@ -196,27 +207,28 @@ void run_share(const std::vector<Pair>& pairs, const ofdis_params& p0, int width
   if (!s_in || !s_out) { bail("ofdis_stream_create"); ok = false; }
   for (Slot& sl : slots) {
     if (!ok) break;
-    if (ofdis_batch_create(&sl.b, &p, C) != OFDIS_OK) { bail("ofdis_batch_create"); ok = false; break; }
+    if (ofdis_batch_create_ex(&sl.b, &p, C, sequence ? OFDIS_BATCH_SEQUENCE : 0u) != OFDIS_OK) { bail("ofdis_batch_create"); ok = false; break; }
     sl.stream = ofdis_stream_create();
     sl.ev_up = ofdis_event_create();
     sl.ev_done = ofdis_event_create();
     sl.ev_down = ofdis_event_create();
     if (!sl.ev_up || !sl.ev_done || !sl.ev_down) { bail("ofdis_event_create"); ok = false; break; }
-    sl.da = ofdis_dev_alloc(img_bytes * C);
-    sl.db = ofdis_dev_alloc(img_bytes * C);
+    sl.da = ofdis_dev_alloc(img_bytes * F);
+    if (!sequence) sl.db = ofdis_dev_alloc(img_bytes * C);
     sl.dfull = ofdis_dev_alloc(flo_bytes * C);
-    if (!sl.stream || !sl.da || !sl.db || !sl.dfull) { bail("slot allocation"); ok = false; break; }
+    if (!sl.stream || !sl.da || (!sequence && !sl.db) || !sl.dfull) { bail("slot allocation"); ok = false; break; }
   }
   // (page-locking memory costs ~0.25 ms per MB, a 64-pair chunk of 1024x436 frames is 285 MB: the buffers are allocated by the
   // reader thread when it first needs them, beside the device work on the chunks before)
   std::atomic<bool> alloc_failed{false};
   auto chunk_alloc = [&](Chunk& c) {
     if (c.ha) return true;
-    c.ha = (uint8_t*)ofdis_host_alloc(img_bytes * C);
-    c.hb = (uint8_t*)ofdis_host_alloc(img_bytes * C);
+    c.ha = (uint8_t*)ofdis_host_alloc(img_bytes * F);
+    if (!sequence) c.hb = (uint8_t*)ofdis_host_alloc(img_bytes * C);
     c.full = (uint8_t*)ofdis_host_alloc(flo_bytes * C);
     c.ok.assign(C, 0);
-    return c.ha && c.hb && c.full;
+    c.fok.assign(F, 0);
+    return c.ha && (sequence || c.hb) && c.full;
   };
   const int n_chunks = device_bench > 0 ? device_bench : (n_share + C - 1) / C;
   if (ok) {
@@ -226,6 +238,11 @@ void run_share(const std::vector<Pair>& pairs, const ofdis_params& p0, int width
     std::atomic<bool> stop{false};  // the device stage gave up: the reader stops feeding it
     std::thread reader([&] {  // decode (cv::imread in the reference, run_dense.cpp:208-209)
       (void)ofdis_set_device(sh->device);  // (this thread page-locks the chunk buffers: on the share's device, not on device 0)
+      // --sequence: the last frame of the chunk decoded before (only this thread writes frame buffers, one chunk at a time, so
+      // it is still there -- even when the buffer has come round and is the one being filled now)
+      const uint8_t* carry = nullptr;
+      int carry_c0 = -1;
+      char carry_ok = 0;
       for (int ci = 0; ci < n_chunks && !stop; ++ci) {
         const int c0 = device_bench > 0 ? sh->lo : sh->lo + ci * C;
         Chunk* c = free_q.pop();
@@ -237,7 +254,44 @@ void run_share(const std::vector<Pair>& pairs, const ofdis_params& p0, int width
         }
         c->c0 = c0;
         c->m = std::min(C, sh->hi - c0);
-        if (device_bench > 0 && c->init_upto >= C) {  // (measurement mode: this buffer already holds the decoded first chunk)
+        if (device_bench > 0 && c->init_upto >= F) {  // (measurement mode: this buffer already holds the decoded first chunk)
+          ready_q.push(c);
+          continue;
+        }
+        if (sequence) {  // frames c0 .. c0 + m, each once: frame k is pairs[c0 + k].a (the last one: the last pair's b)
+          const int nf = c->m + 1;
+          int first = 0;
+          if (carry && carry_c0 == c0) {
+            memmove(c->ha, carry, img_bytes);
+            c->fok[0] = carry_ok;
+            first = 1;
+          }
+          parallel_for(nf - first, io_threads, [&](int j) {
+            const int k = first + j;
+            const std::string& name = k < c->m ? pairs[c0 + k].a : pairs[c0 + k - 1].b;
+            ofdis_host::Image8 im;
+            std::string err;
+            c->fok[k] = ofdis_host::read_image(name, OFDIS_NOC, &im, &err);
+            if (c->fok[k] && (im.width != width_org || im.height != height_org)) {
+              c->fok[k] = 0;
+              err = name + ": not " + std::to_string(width_org) + "x" + std::to_string(height_org) + " like the first readable frame";
+            }
+            if (!c->fok[k]) {
+              fprintf(stderr, "%s\n", err.c_str());
+              if (k >= c->init_upto) memset(c->ha + k * img_bytes, 0, img_bytes);  // never written: a defined (black) frame
+              return;
+            }
+            memcpy(c->ha + k * img_bytes, im.data.data(), img_bytes);
+          });
+          for (int k = 0; k < c->m; ++k) c->ok[k] = c->fok[k] && c->fok[k + 1];
+          if (c->init_upto < F) {  // the slots of a short chunk that were never written
+            const int from = std::max(c->init_upto, nf);
+            if (from < F) memset(c->ha + from * img_bytes, 0, (F - from) * img_bytes);
+            c->init_upto = F;
+          }
+          carry = c->ha + c->m * img_bytes;
+          carry_c0 = c0 + c->m;
+          carry_ok = c->fok[c->m];
           ready_q.push(c);
           continue;
         }
@@ -321,11 +375,12 @@ void run_share(const std::vector<Pair>& pairs, const ofdis_params& p0, int width
       int rc = OFDIS_OK;
       if (with_upload) {
         // (the slot's device buffers are free: retire() waited for the download that followed the kernels that last read them)
-        rc = ofdis_memcpy_h2d_async(sl.da, c->ha, img_bytes * C, s_in);
-        if (!rc) rc = ofdis_memcpy_h2d_async(sl.db, c->hb, img_bytes * C, s_in);
+        rc = ofdis_memcpy_h2d_async(sl.da, c->ha, img_bytes * F, s_in);
+        if (!rc && !sequence) rc = ofdis_memcpy_h2d_async(sl.db, c->hb, img_bytes * C, s_in);
         if (!rc) rc = ofdis_event_record(sl.ev_up, s_in);
         if (!rc) rc = ofdis_stream_wait_event(sl.stream, sl.ev_up);
-        if (!rc) rc = ofdis_batch_build_pyramids_u8(sl.b, (const uint8_t*)sl.da, (const uint8_t*)sl.db, width_org, height_org, sl.stream);
+        if (!rc && sequence) rc = ofdis_batch_build_pyramids_u8_seq(sl.b, (const uint8_t*)sl.da, 0, 0, width_org, height_org, sl.stream);
+        if (!rc && !sequence) rc = ofdis_batch_build_pyramids_u8(sl.b, (const uint8_t*)sl.da, (const uint8_t*)sl.db, width_org, height_org, sl.stream);
       }
       if (!rc) rc = ofdis_batch_run(sl.b, sl.stream);
       if (!rc) rc = ofdis_batch_upsample_frames_enc(sl.b, 0, c->m, sl.dfull, width_org, height_org, &link, sl.stream);
@@ -443,9 +498,10 @@ void run_share(const std::vector<Pair>& pairs, const ofdis_params& p0, int width
 
 int usage(const char* argv0) {
   fprintf(stderr, "usage: %s pairs.txt [--gpus N | --devices d0,d1,..] [--chunk C] [--depth D] [--size W H] [--device-bench N] [--io-threads T] "
-                  "[--link f32|f16|u8:BOUND|u16:SCALE:OFFSET|kitti] [--dry-run 1] [oppoint 1-4 | lv_f lv_l maxiter miniter "
+                  "[--link f32|f16|u8:BOUND|u16:SCALE:OFFSET|kitti] [--dry-run 1] [--sequence 1] [oppoint 1-4 | lv_f lv_l maxiter miniter "
                   "mindprate mindrrate minimgerr patchsz poverl usefbcon patnorm costfct usetvref tv_alpha tv_gamma tv_delta "
-                  "tv_innerit tv_solverit tv_sor verbosity]\n  pairs.txt: one \"img1 img2 out.flo\" per line\n", argv0);
+                  "tv_innerit tv_solverit tv_sor verbosity]\n  pairs.txt: one \"img1 img2 out.flo\" per line (--sequence 1, optical flow only: "
+                  "one \"img out.flo\" per frame, the last line \"img\" alone)\n", argv0);
   return 2;
 }
 
@@ -494,6 +550,13 @@ int main(int argc, char** argv) {
   const double t_start = now_ms();
   if (argc < 2) return usage(argv[0]);
   std::vector<Pair> pairs;
+  bool sequence = false;  // --sequence 1 decides how the list reads, so it is looked for ahead of the option loop below
+  for (int i = 2; i + 1 < argc; ++i)
+    if (!strcmp(argv[i], "--sequence")) sequence = atoi(argv[i + 1]) != 0;
+  if (sequence && OFDIS_MODE == 2) {
+    fprintf(stderr, "--sequence: a list of stereo pairs is not a sequence\n");
+    return 2;
+  }
   {
     std::ifstream f(argv[1]);
     if (!f) {
@@ -501,15 +564,30 @@ int main(int argc, char** argv) {
       return 1;
     }
     std::string line;
+    std::vector<Pair> frames;  // --sequence: a = the frame, out = the flow to the next frame (the last frame: empty)
     while (std::getline(f, line)) {
       std::istringstream ss(line);
       Pair pr;
       if (!(ss >> pr.a) || pr.a[0] == '#') continue;
+      if (sequence) {
+        ss >> pr.out;
+        frames.push_back(pr);
+        continue;
+      }
       if (!(ss >> pr.b >> pr.out)) {
         fprintf(stderr, "%s: expected \"img1 img2 out.flo\", got \"%s\"\n", argv[1], line.c_str());
         return 2;
       }
       pairs.push_back(pr);
+    }
+    for (size_t i = 0; i < frames.size(); ++i) {
+      const bool last = i + 1 == frames.size();
+      if (frames[i].out.empty() != last) {
+        fprintf(stderr, "%s: --sequence expects \"img out.flo\" per frame and the last line \"img\" alone, got \"%s %s\"%s\n", argv[1],
+                frames[i].a.c_str(), frames[i].out.c_str(), last ? " as the last line" : "");
+        return 2;
+      }
+      if (!last) pairs.push_back({frames[i].a, frames[i + 1].a, frames[i].out});
     }
   }
   if (pairs.empty()) {
@@ -566,6 +644,8 @@ int main(int argc, char** argv) {
       link_name = val;
     } else if (opt == "--dry-run") {
       dry_run = atoi(val) != 0;
+    } else if (opt == "--sequence") {
+      // (read above, before the list)
     } else {
       fprintf(stderr, "unknown option %s\n", opt.c_str());
       return 2;
@@ -625,7 +705,7 @@ int main(int argc, char** argv) {
   for (int r = 0; r < R; ++r) {
     shares[r].device = devices[r];
     frame_range((int)pairs.size(), r, R, &shares[r].lo, &shares[r].hi);
-    threads.emplace_back(run_share, std::cref(pairs), std::cref(p), width_org, height_org, chunk, depth, device_bench, io_threads, std::cref(link), &shares[r]);
+    threads.emplace_back(run_share, std::cref(pairs), std::cref(p), width_org, height_org, chunk, depth, device_bench, io_threads, std::cref(link), sequence, &shares[r]);
   }
   for (auto& t : threads) t.join();
   const double t_all = now_ms() - t0;

@@ -142,6 +142,8 @@ struct ofdis_batch {
   // Device arrays.  Every one is a float* MEMBER of this struct (per-level ones: fixed arrays, index = level - sc_l) and is
   // described once, where it is requested (dalloc): its size per frame.  Frame views and per-frame addresses derive from that.
   float* in[6][MAX_LEVELS] = {};     // A, A_dx, A_dy, B per level (+ B_dx, B_dy when usefbcon)
+  bool sequence = false;             // OFDIS_BATCH_SEQUENCE: in[0..2] hold nframes + 1 frames (pair k = frames k, k + 1) and
+                                     // in[3 + j] = in[j] + one frame: B's planes are A's, one frame further on (never allocated)
   float* flow_bw[MAX_LEVELS] = {};   // usefbcon: backward dense flow per level (oflow.cpp:162)
   float* pvec_bw = nullptr;          // usefbcon: backward grid results
   float* pweight_bw = nullptr;
@@ -170,8 +172,10 @@ struct ofdis_batch {
   // device memory: requests are collected (dalloc) and served from ONE hipMalloc per commit (dcommit) -- a context is
   // one allocation (two with the u8 pyramid scratch), and the input planes form one contiguous region [in_base,
   // in_base + in_bytes) in (level, kind) order so that a single-frame context is uploaded with one copy (ofdis_flow)
-  struct Array { size_t slot, per_frame; bool view; };  // the member's byte offset in this struct; floats per frame (the array
-                                                         // holds nframes times as many); does a frame view get its share?
+  struct Array { size_t slot, per_frame; bool view; int extra; };  // the member's byte offset in this struct; floats per frame
+                                                         // (the array holds nframes + extra times as many: the frame slots of
+                                                         // a sequence context are one more than its pairs); does a frame view
+                                                         // get its share?
   std::vector<Array> arrays;  // in request order; [0, committed) are served
   size_t committed = 0;
   std::vector<void*> allocs;
@@ -229,7 +233,7 @@ LevelGeom make_geom(const ofdis_params& p, int sl);
 int check_params(const ofdis_params* p);
 void context_init(ofdis_batch* b, const ofdis_params& p, int nframes, const ofdis_tuning& tn, int first_level, int last_level);
 void context_release(ofdis_batch* b);  // everything the context owns; not the struct itself
-void dalloc(ofdis_batch* b, float** member, size_t per_frame, bool view = true);  // request; served by dcommit()
+void dalloc(ofdis_batch* b, float** member, size_t per_frame, bool view = true, int extra_frames = 0);  // request; served by dcommit()
 int dcommit(ofdis_batch* b);
 void dalloc_tv_scratch(ofdis_batch* b, const Scratch& sc);
 int xcu_arm(ofdis_batch* b, hipStream_t s);

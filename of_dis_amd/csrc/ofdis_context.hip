@@ -138,15 +138,17 @@ void context_init(ofdis_batch* b, const ofdis_params& p, int nframes, const ofdi
 }
 
 static float*& member(const ofdis_batch& b, const ofdis_batch::Array& a) { return *(float**)((char*)&b + a.slot); }
-static size_t array_bytes(const ofdis_batch& b, const ofdis_batch::Array& a) {
-  const size_t elems = a.per_frame * b.nframes;
+static size_t array_elems(const ofdis_batch& b, const ofdis_batch::Array& a) { return a.per_frame * ((size_t)b.nframes + a.extra); }
+static size_t array_bytes(const ofdis_batch& b, const ofdis_batch::Array& a) {  // (every array starts on a 256-byte boundary)
+  const size_t elems = array_elems(b, a);
   return ((elems ? elems : 1) * sizeof(float) + 255) & ~(size_t)255;
 }
 
-// THE description of a device array: `per_frame` floats for each of the context's frames, at `slot` (a float* member of *b).
-void dalloc(ofdis_batch* b, float** slot, size_t per_frame, bool view) {
+// THE description of a device array: `per_frame` floats for each of the context's frames (and `extra_frames` more), at `slot`
+// (a float* member of *b).
+void dalloc(ofdis_batch* b, float** slot, size_t per_frame, bool view, int extra_frames) {
   *slot = nullptr;
-  b->arrays.push_back({(size_t)((char*)slot - (char*)b), per_frame, view});
+  b->arrays.push_back({(size_t)((char*)slot - (char*)b), per_frame, view, extra_frames});
 }
 // Test hook OFDIS_POISON_SCRATCH=1: fresh device memory holds NaN patterns instead of zeros.  Read at every allocation (never
 // on a launch path): the tests switch it while the library is loaded.
@@ -216,6 +218,10 @@ ofdis_batch frame_view(const ofdis_batch& b, int f0, int n) {
     if (!a.view) ptr = nullptr;
     else if (ptr) ptr += (size_t)f0 * a.per_frame;
   }
+  if (b.sequence)  // kinds 3..5 are no arrays of their own (the same planes one frame further on): they move with the others
+    for (int i = 0; i < b.nlevels; ++i)
+      for (int k = 3; k < 6; ++k)
+        if (v.in[k][i]) v.in[k][i] += (size_t)f0 * b.geom[i].plane_elems;
   if (v.initflow) v.initflow += (size_t)f0 * ofdis_batch_initflow_elems(&b);
   if (v.initflow_rev) v.initflow_rev += (size_t)f0 * ofdis_batch_initflow_elems(&b);
   return v;
@@ -267,7 +273,7 @@ void context_release(ofdis_batch* b) {
     }
 }
 
-// host pyramids src[0 .. nkinds) into frame `frame` of the input planes in[first_kind ..]
+// host pyramids src[0 .. nkinds) into frame `frame` of the input planes in[first_kind ..] (a sequence context: frame slot)
 static int upload_planes(ofdis_batch* b, int frame, int first_kind, int nkinds, const float* const* const* src, hipStream_t s) {
   for (int l = b->p.sc_l; l <= b->p.sc_f; ++l)
     for (int k = 0; k < nkinds; ++k) {
@@ -276,6 +282,12 @@ static int upload_planes(ofdis_batch* b, int frame, int first_kind, int nkinds, 
       HIPCHK(hipMemcpyAsync(frame_at(*b, plane, frame), src[k][l], frame_elems(*b, plane) * sizeof(float), hipMemcpyHostToDevice, s));
     }
   return OFDIS_OK;
+}
+
+static const char* const kSeqOnly = "not a context created with OFDIS_BATCH_SEQUENCE";
+static int seq_refuses(const char* what, const char* instead) {
+  return fail(OFDIS_ERR_INVALID, std::string(what) + " takes frame pairs; an OFDIS_BATCH_SEQUENCE context shares its frame slots "
+                                                     "between pairs and is filled through " + instead);
 }
 
 // the forward / reverse halves of the result accessors
@@ -352,22 +364,29 @@ int ofdis_batch_create_ex(ofdis_batch** out, const ofdis_params* p, int nframes,
   int rc = check_params(p);
   if (rc) return rc;
   if (nframes < 1) return fail(OFDIS_ERR_INVALID, "nframes must be >= 1");
-  if (flags & ~(OFDIS_BATCH_REVERSE | OFDIS_BATCH_STEREO_LR)) return fail(OFDIS_ERR_INVALID, "unknown flag bits");
+  if (flags & ~(OFDIS_BATCH_REVERSE | OFDIS_BATCH_STEREO_LR | OFDIS_BATCH_SEQUENCE)) return fail(OFDIS_ERR_INVALID, "unknown flag bits");
   const bool reverse = (flags & OFDIS_BATCH_REVERSE) != 0, stereo_lr = (flags & OFDIS_BATCH_STEREO_LR) != 0;
+  const bool sequence = (flags & OFDIS_BATCH_SEQUENCE) != 0;
   if (reverse && p->selectmode == 2)
     return fail(OFDIS_ERR_UNSUPPORTED, "OFDIS_BATCH_REVERSE: no reverse direction in stereo-depth mode (selectmode 2); the "
                                        "right view is OFDIS_BATCH_STEREO_LR");
   if (stereo_lr && p->selectmode != 2) return fail(OFDIS_ERR_INVALID, "OFDIS_BATCH_STEREO_LR needs stereo-depth mode (selectmode 2)");
+  if (sequence && (stereo_lr || p->selectmode == 2))
+    return fail(OFDIS_ERR_INVALID, "OFDIS_BATCH_SEQUENCE: a stereo pair is not a sequence (selectmode 2, OFDIS_BATCH_STEREO_LR)");
   if (nframes > 65535)  // launch_warp / launch_upsample_crop carry the frame in grid.z
     return fail(OFDIS_ERR_UNSUPPORTED, "at most 65535 frames per batch context");
+  if (sequence && nframes > 65534)  // launch_pyr_planes carries the nframes + 1 frame slots in grid.y
+    return fail(OFDIS_ERR_UNSUPPORTED, "at most 65534 pairs (65535 frames) per OFDIS_BATCH_SEQUENCE context");
   ofdis_batch* b = new ofdis_batch();
   const ofdis_tuning tn = tuning();  // ONE snapshot decides the contract and the scratch
   context_init(b, *p, nframes, tn, p->sc_l, p->sc_f);
   b->reverse = reverse;
   b->stereo_lr = stereo_lr;
-  const int nin = (p->usefbcon || reverse) ? 6 : 4;  // (the reverse pass reads B's gradients as its A's)
+  b->sequence = sequence;
+  // (the reverse pass reads B's gradients as its A's.)  A sequence: image, dx, dy of nframes + 1 frame slots; kinds 3..5 derive
+  const int nin = sequence ? 3 : (p->usefbcon || reverse) ? 6 : 4;
   for (int i = 0; i < b->nlevels; ++i)  // the input planes first: one contiguous region in (level, kind) order
-    for (int k = 0; k < nin; ++k) dalloc(b, &b->in[k][i], b->geom[i].plane_elems);
+    for (int k = 0; k < nin; ++k) dalloc(b, &b->in[k][i], b->geom[i].plane_elems, true, sequence ? 1 : 0);
   for (const ofdis_batch::Array& a : b->arrays) b->in_bytes += array_bytes(*b, a);
   if (stereo_lr)  // the mirrored pair's planes: the same sizes, stated by the same expression
     for (int i = 0; i < b->nlevels; ++i)
@@ -390,6 +409,9 @@ int ofdis_batch_create_ex(ofdis_batch** out, const ofdis_params* p, int nframes,
   if (p->usetvref) dalloc_tv_scratch(b, sc);
   rc = dcommit(b);
   if (!rc) b->in_base = (char*)b->in[0][0];
+  if (!rc && sequence)  // B of pair k is frame k + 1: the same arrays, one frame further on
+    for (int i = 0; i < b->nlevels; ++i)
+      for (int k = 0; k < 3; ++k) b->in[3 + k][i] = b->in[k][i] + b->geom[i].plane_elems;
   if (!rc) rc = xcu_arm(b, nullptr);
   if (!rc && b->xcu) {
     const hipError_t e = hipStreamSynchronize(nullptr);  // (the zeroing)
@@ -414,7 +436,7 @@ void ofdis_batch_destroy(ofdis_batch* b) {
 
 float* ofdis_batch_input(ofdis_batch* b, int level, int kind) {
   if (!b || level < b->p.sc_l || level > b->p.sc_f || kind < 0) return nullptr;
-  const int nin = (b->p.usefbcon || b->reverse) ? 6 : 4;
+  const int nin = (b->p.usefbcon || b->reverse || b->sequence) ? 6 : 4;
   if (kind < nin) return b->in[kind][level - b->p.sc_l];
   if (b->stereo_lr && kind >= 6 && kind < 6 + nin) return b->in_mir[kind - 6][level - b->p.sc_l];  // the mirrored pair's
   return nullptr;
@@ -423,11 +445,19 @@ size_t ofdis_batch_input_elems(const ofdis_batch* b, int level) {
   if (!b || level < b->p.sc_l || level > b->p.sc_f) return 0;
   return b->g(level).plane_elems;
 }
+int ofdis_batch_input_frames(const ofdis_batch* b) { return b ? b->nframes + (b->sequence ? 1 : 0) : 0; }
+size_t ofdis_batch_device_bytes(const ofdis_batch* b) {
+  size_t total = 0;
+  if (b)
+    for (size_t i = 0; i < b->committed; ++i) total += array_elems(*b, b->arrays[i]) * sizeof(float);
+  return total;
+}
 
 int ofdis_batch_upload(ofdis_batch* b, int frame, const float* const* im_a, const float* const* im_a_dx,
                        const float* const* im_a_dy, const float* const* im_b, void* stream) {
   if (!b || frame < 0 || frame >= b->nframes || !im_a || !im_a_dx || !im_a_dy || !im_b)
     return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (b->sequence) return seq_refuses("ofdis_batch_upload", "ofdis_batch_upload_frame");
   const float* const* src[4] = {im_a, im_a_dx, im_a_dy, im_b};
   return upload_planes(b, frame, 0, 4, src, (hipStream_t)stream);
 }
@@ -435,14 +465,38 @@ int ofdis_batch_upload(ofdis_batch* b, int frame, const float* const* im_a, cons
 int ofdis_batch_upload_b_gradients(ofdis_batch* b, int frame, const float* const* im_b_dx, const float* const* im_b_dy,
                                    void* stream) {
   if (!b || frame < 0 || frame >= b->nframes || !im_b_dx || !im_b_dy) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (b->sequence) return seq_refuses("ofdis_batch_upload_b_gradients", "ofdis_batch_upload_frame");
   if (!b->p.usefbcon && !b->reverse) return OFDIS_OK;  // never read (patch.cpp:90-97)
   const float* const* src[2] = {im_b_dx, im_b_dy};
   return upload_planes(b, frame, 4, 2, src, (hipStream_t)stream);
 }
 
-int ofdis_batch_build_pyramids_u8(ofdis_batch* b, const uint8_t* img_a, const uint8_t* img_b, int width_org,
-                                  int height_org, void* stream) {
-  if (!b || !img_a || !img_b) return fail(OFDIS_ERR_INVALID, "bad arguments");
+int ofdis_batch_upload_frame(ofdis_batch* b, int slot, const float* const* im, const float* const* im_dx,
+                             const float* const* im_dy, void* stream) {
+  if (!b || !b->sequence) return fail(OFDIS_ERR_INVALID, kSeqOnly);
+  if (slot < 0 || slot > b->nframes || !im || !im_dx || !im_dy) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  const float* const* src[3] = {im, im_dx, im_dy};
+  return upload_planes(b, slot, 0, 3, src, (hipStream_t)stream);
+}
+
+// One frame set of `count` 8-bit frames (row y of frame f at src + f * stride + y * pitch) through the pyramid schedule: the
+// base level, then per level the planes -- image, and the gradients where the set has them (non-null) -- plus the next
+// level's unpadded image.
+static int build_frame_set(ofdis_batch* b, const uint8_t* src, size_t pitch, size_t stride, int count,
+                           float* (*planes)[ofdis_batch::MAX_LEVELS], int width_org, int height_org, hipStream_t s) {
+  const ofdis_params& p = b->p;
+  HIPCHK(launch_pyr_base(src, b->pyr_tmp[0], count, width_org, height_org, p.width, p.height, p.noc, p.sc_l, pitch, stride, s));
+  for (int i = 0; i < b->nlevels; ++i) {
+    const LevelGeom& g = b->geom[i];
+    // the planes of level i and, in the same launch where the geometry allows, the unpadded image of level i + 1
+    // (2x2 means: cv::resize(.5,.5), run_dense.cpp:150)
+    float* down = i + 1 < b->nlevels ? b->pyr_tmp[i + 1] : nullptr;
+    HIPCHK(launch_pyr_planes(b->pyr_tmp[i], planes[0][i], planes[1][i], planes[2][i], count, g.w, g.h, p.noc, g.pad, s, down));
+  }
+  return OFDIS_OK;
+}
+// the checks both 8-bit entry points share, and the unpadded level images (lazily; a frame view never sees them)
+static int build_prepare(ofdis_batch* b, int width_org, int height_org) {
   const ofdis_params& p = b->p;
   // the padded size must be what run_dense.cpp:298-305 derives from the original size
   const int sc = 1 << p.sc_f;
@@ -451,23 +505,41 @@ int ofdis_batch_build_pyramids_u8(ofdis_batch* b, const uint8_t* img_a, const ui
     return fail(OFDIS_ERR_INVALID, "params.width/height are not the 2^sc_f padding of the original size");
   // level l images need 8+2l bits, the Sobel partial sums 10+2l: exact in fp32 up to l = 7 (ofdis_pyr.hip)
   if (p.sc_f > 7) return fail(OFDIS_ERR_UNSUPPORTED, "exact fp32 pyramid needs sc_f <= 7");
-  hipStream_t s = (hipStream_t)stream;
-  if (!b->pyr_tmp[0]) {  // (a frame view never sees them)
-    for (int i = 0; i < b->nlevels; ++i) dalloc(b, &b->pyr_tmp[i], (size_t)b->geom[i].w * b->geom[i].h * b->geom[i].noc, false);
+  if (!b->pyr_tmp[0]) {
+    for (int i = 0; i < b->nlevels; ++i)
+      dalloc(b, &b->pyr_tmp[i], (size_t)b->geom[i].w * b->geom[i].h * b->geom[i].noc, false, b->sequence ? 1 : 0);
     if (b->stereo_lr) dalloc(b, &b->mir_u8, ((size_t)p.width * p.height * p.noc + 3) / 4, false);
     if (int rc = dcommit(b)) return rc;
   }
-  // the planes of one frame set: image, and the gradients where the set has them (B's only exist, non-null, with usefbcon)
+  return OFDIS_OK;
+}
+
+int ofdis_batch_build_pyramids_u8_seq(ofdis_batch* b, const uint8_t* frames, size_t row_pitch, size_t frame_stride,
+                                      int width_org, int height_org, void* stream) {
+  if (!b || !b->sequence) return fail(OFDIS_ERR_INVALID, kSeqOnly);
+  if (!frames) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (width_org < 1 || height_org < 1) return fail(OFDIS_ERR_INVALID, "params.width/height are not the 2^sc_f padding of the original size");
+  const size_t row_bytes = (size_t)width_org * b->p.noc;
+  if (!row_pitch) row_pitch = row_bytes;
+  if (row_pitch < row_bytes) return fail(OFDIS_ERR_INVALID, "row_pitch is shorter than a row (width_org * noc bytes)");
+  if (!frame_stride) frame_stride = row_pitch * height_org;
+  if (frame_stride < row_pitch * height_org) return fail(OFDIS_ERR_INVALID, "frame_stride is shorter than a frame (row_pitch * height_org bytes)");
+  if (int rc = build_prepare(b, width_org, height_org)) return rc;
+  // every frame once: its planes are B's of the pair before it and A's of the pair after it
+  return build_frame_set(b, frames, row_pitch, frame_stride, b->nframes + 1, &b->in[0], width_org, height_org, (hipStream_t)stream);
+}
+
+int ofdis_batch_build_pyramids_u8(ofdis_batch* b, const uint8_t* img_a, const uint8_t* img_b, int width_org,
+                                  int height_org, void* stream) {
+  if (!b || !img_a || !img_b) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (b->sequence) return seq_refuses("ofdis_batch_build_pyramids_u8", "ofdis_batch_build_pyramids_u8_seq");
+  const ofdis_params& p = b->p;
+  if (int rc = build_prepare(b, width_org, height_org)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t pitch = (size_t)width_org * p.noc, stride = pitch * height_org;  // packed frames
+  // (B's gradients only exist, non-null, with usefbcon or OFDIS_BATCH_REVERSE)
   auto build = [&](const uint8_t* src, float* (*planes)[ofdis_batch::MAX_LEVELS]) -> int {
-    HIPCHK(launch_pyr_base(src, b->pyr_tmp[0], b->nframes, width_org, height_org, p.width, p.height, p.noc, p.sc_l, s));
-    for (int i = 0; i < b->nlevels; ++i) {
-      const LevelGeom& g = b->geom[i];
-      // the planes of level i and, in the same launch where the geometry allows, the unpadded image of level i + 1
-      // (2x2 means: cv::resize(.5,.5), run_dense.cpp:150)
-      float* down = i + 1 < b->nlevels ? b->pyr_tmp[i + 1] : nullptr;
-      HIPCHK(launch_pyr_planes(b->pyr_tmp[i], planes[0][i], planes[1][i], planes[2][i], b->nframes, g.w, g.h, p.noc, g.pad, s, down));
-    }
-    return OFDIS_OK;
+    return build_frame_set(b, src, pitch, stride, b->nframes, planes, width_org, height_org, s);
   };
   if (int rc = build(img_a, &b->in[0])) return rc;
   if (int rc = build(img_b, &b->in[3])) return rc;

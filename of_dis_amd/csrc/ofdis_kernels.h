@@ -164,8 +164,9 @@ struct FusedXcu {
 
 
 // on-device pyramid (ofdis_pyr.hip; run_dense.cpp:130-178,298-311 restated)
+// row y of frame f starts at src + f * stride + y * pitch (bytes; packed frames: pitch = wo * noc, stride = pitch * ho)
 hipError_t launch_pyr_base(const uint8_t* src, float* dst, int nframes, int wo, int ho, int W, int H, int noc, int l,
-                           hipStream_t s);
+                           size_t pitch, size_t stride, hipStream_t s);
 hipError_t launch_pyr_down(const float* src, float* dst, int nframes, int w, int h, int noc, hipStream_t s);
 // `down` (optional): also the next coarser level's unpadded image [B][h/2][w/2][noc] (what launch_pyr_down computes), in the
 // same launch where the geometry allows (pyr_planes_fuses_down), else by a launch of its own

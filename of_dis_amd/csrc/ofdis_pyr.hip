@@ -18,9 +18,12 @@
 
 namespace ofdis {
 
-// level `l` image (unpadded, [B][h][w][noc] float) straight from the u8 frames
+// level `l` image (unpadded, [B][h][w][noc] float) straight from the u8 frames.  Row y of frame f starts at
+// src + f * stride + y * pitch (packed frames: pitch = wo * noc, stride = pitch * ho); only the wo * noc bytes of a row are
+// ever read -- what lies between rows and between frames may be uninitialised or somebody else's.
 __global__ __launch_bounds__(256) void pyr_base_kernel(const uint8_t* __restrict__ src, float* __restrict__ dst,
-                                                       int nframes, int wo, int ho, int W, int H, int noc, int l) {
+                                                       int nframes, int wo, int ho, int W, int H, int noc, int l,
+                                                       size_t pitch, size_t stride) {
   const int w = W >> l, h = H >> l;
   const int left = (W - wo) / 2, top = (H - ho) / 2;  // floor(pad/2) on the left/top (run_dense.cpp:308)
   const long long total = (long long)nframes * h * w * noc;
@@ -34,15 +37,15 @@ __global__ __launch_bounds__(256) void pyr_base_kernel(const uint8_t* __restrict
     r /= w;
     const int y = (int)(r % h);
     const int f = (int)(r / h);
-    const uint8_t* s = src + (size_t)f * wo * ho * noc;
+    const uint8_t* s = src + (size_t)f * stride;
     unsigned sum = 0;
     // fast path (gray, block of at least 4 columns entirely inside the frame, 4-byte aligned rows): whole words,
     // v_sad_u8 against 0 adds the four bytes of a word in one instruction; neighbouring threads read neighbouring words
     const int bx0 = x * bs - left, by0 = y * bs - top;
-    if (noc == 1 && bs >= 4 && ((wo | bx0) & 3) == 0 && bx0 >= 0 && bx0 + bs <= wo && by0 >= 0 && by0 + bs <= ho &&
-        (((size_t)f * wo * ho) & 3) == 0 && ((uintptr_t)src & 3) == 0) {
-      const unsigned* s32 = reinterpret_cast<const unsigned*>(s + (size_t)by0 * wo + bx0);
-      const int wpr = wo >> 2;
+    if (noc == 1 && bs >= 4 && ((pitch | (size_t)bx0) & 3) == 0 && bx0 >= 0 && bx0 + bs <= wo && by0 >= 0 && by0 + bs <= ho &&
+        (((size_t)f * stride) & 3) == 0 && ((uintptr_t)src & 3) == 0) {
+      const unsigned* s32 = reinterpret_cast<const unsigned*>(s + (size_t)by0 * pitch + bx0);
+      const size_t wpr = pitch >> 2;
       for (int yy = 0; yy < bs; ++yy)
         for (int q = 0; q < (bs >> 2); ++q) sum = __builtin_amdgcn_sad_u8(s32[(size_t)yy * wpr + q], 0u, sum);
       dst[idx] = (float)sum * scale;
@@ -52,14 +55,14 @@ __global__ __launch_bounds__(256) void pyr_base_kernel(const uint8_t* __restrict
       const int sy = clampi(y * bs + yy - top, 0, ho - 1);
       for (int xx = 0; xx < bs; ++xx) {
         const int sx = clampi(x * bs + xx - left, 0, wo - 1);
-        sum += s[((size_t)sy * wo + sx) * noc + c];
+        sum += s[(size_t)sy * pitch + (size_t)sx * noc + c];
       }
     }
     dst[idx] = (float)sum * scale;
   }
 }
 
-// Streaming variant of pyr_base_kernel for gray frames whose rows and left padding are multiples of 16 bytes: a lane reads
+// Streaming variant of pyr_base_kernel for gray frames whose width, pitch, stride and left padding are multiples of 16 bytes: a lane reads
 // 16 bytes per source row (one wavefront = 1 KB of a row per instruction), sums them per output block with v_sad_u8
 // (four bytes per instruction) over the BS rows of the block -- rows are clamped individually, so the replicate padding
 // at the top and bottom costs nothing -- and writes 16/BS adjacent outputs.  Same integers, same power-of-two scale:
@@ -67,7 +70,8 @@ __global__ __launch_bounds__(256) void pyr_base_kernel(const uint8_t* __restrict
 typedef unsigned u4 __attribute__((ext_vector_type(4)));
 template <int BS>
 __global__ __launch_bounds__(256) void pyr_base16_kernel(const uint8_t* __restrict__ src, float* __restrict__ dst,
-                                                         int nframes, int wo, int ho, int W, int H, int l) {
+                                                         int nframes, int wo, int ho, int W, int H, int l,
+                                                         size_t pitch, size_t stride) {
   constexpr int NOUT = 16 / BS;  // outputs per lane
   const int w = W >> l, h = H >> l;
   const int left = (W - wo) / 2, top = (H - ho) / 2;
@@ -83,7 +87,7 @@ __global__ __launch_bounds__(256) void pyr_base16_kernel(const uint8_t* __restri
     // padded columns [16 ch, 16 ch + 16) = source columns clamped to the frame (whole chunk inside or outside)
     int sx = ch * 16 - left;
     const bool inside = sx >= 0 && sx + 16 <= wo;
-    const uint8_t* s = src + (size_t)f * wo * ho;
+    const uint8_t* s = src + (size_t)f * stride;
     unsigned sum[NOUT];
 #pragma unroll
     for (int q = 0; q < NOUT; ++q) sum[q] = 0;
@@ -91,7 +95,7 @@ __global__ __launch_bounds__(256) void pyr_base16_kernel(const uint8_t* __restri
 #pragma unroll
       for (int yy = 0; yy < BS; ++yy) {
         const int sy = clampi(y * BS + yy - top, 0, ho - 1);
-        const u4 v = __builtin_nontemporal_load(reinterpret_cast<const u4*>(s + (size_t)sy * wo + sx));
+        const u4 v = __builtin_nontemporal_load(reinterpret_cast<const u4*>(s + (size_t)sy * pitch + sx));
         const unsigned wd[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
         for (int q = 0; q < 4; ++q) sum[q * 4 / BS] = __builtin_amdgcn_sad_u8(wd[q], 0u, sum[q * 4 / BS]);
@@ -99,7 +103,7 @@ __global__ __launch_bounds__(256) void pyr_base16_kernel(const uint8_t* __restri
     } else {  // chunk in the replicated left / right border: every column is the frame's first / last column
       sx = sx < 0 ? 0 : wo - 1;
       unsigned c = 0;
-      for (int yy = 0; yy < BS; ++yy) c += s[(size_t)clampi(y * BS + yy - top, 0, ho - 1) * wo + sx];
+      for (int yy = 0; yy < BS; ++yy) c += s[(size_t)clampi(y * BS + yy - top, 0, ho - 1) * pitch + sx];
 #pragma unroll
       for (int q = 0; q < NOUT; ++q) sum[q] = c * BS;
     }
@@ -242,19 +246,21 @@ static unsigned grid_for(long long total) {
 }
 
 hipError_t launch_pyr_base(const uint8_t* src, float* dst, int nframes, int wo, int ho, int W, int H, int noc, int l,
-                           hipStream_t s) {
+                           size_t pitch, size_t stride, hipStream_t s) {
   const long long total = (long long)nframes * (H >> l) * (W >> l) * noc;
   const int left = (W - wo) / 2;
-  // 16-byte streaming variant: gray, rows / left padding / frame size / base address multiples of 16 bytes
+  // 16-byte streaming variant: gray, width / left padding / row pitch / frame stride / base address multiples of 16 bytes
+  // (packed frames: pitch = wo, stride = wo * ho)
   if (noc == 1 && (l == 2 || l == 3 || l == 4) && (wo & 15) == 0 && (left & 15) == 0 && (W & 15) == 0 &&
-      (((size_t)wo * ho) & 15) == 0 && ((uintptr_t)src & 15) == 0) {
+      (pitch & 15) == 0 && (stride & 15) == 0 && ((uintptr_t)src & 15) == 0) {
     const long long lanes = (long long)nframes * (H >> l) * (W / 16);
-    if (l == 2) hipLaunchKernelGGL(pyr_base16_kernel<4>, dim3(grid_for(lanes)), dim3(256), 0, s, src, dst, nframes, wo, ho, W, H, l);
-    else if (l == 3) hipLaunchKernelGGL(pyr_base16_kernel<8>, dim3(grid_for(lanes)), dim3(256), 0, s, src, dst, nframes, wo, ho, W, H, l);
-    else hipLaunchKernelGGL(pyr_base16_kernel<16>, dim3(grid_for(lanes)), dim3(256), 0, s, src, dst, nframes, wo, ho, W, H, l);
+    if (l == 2) hipLaunchKernelGGL(pyr_base16_kernel<4>, dim3(grid_for(lanes)), dim3(256), 0, s, src, dst, nframes, wo, ho, W, H, l, pitch, stride);
+    else if (l == 3) hipLaunchKernelGGL(pyr_base16_kernel<8>, dim3(grid_for(lanes)), dim3(256), 0, s, src, dst, nframes, wo, ho, W, H, l, pitch, stride);
+    else hipLaunchKernelGGL(pyr_base16_kernel<16>, dim3(grid_for(lanes)), dim3(256), 0, s, src, dst, nframes, wo, ho, W, H, l, pitch, stride);
     return hipGetLastError();
   }
-  hipLaunchKernelGGL(pyr_base_kernel, dim3(grid_for(total)), dim3(256), 0, s, src, dst, nframes, wo, ho, W, H, noc, l);
+  hipLaunchKernelGGL(pyr_base_kernel, dim3(grid_for(total)), dim3(256), 0, s, src, dst, nframes, wo, ho, W, H, noc, l, pitch,
+                     stride);
   return hipGetLastError();
 }
 // the quad kernel also produces the next level's image (even sizes, gray, quads inside or outside the image)

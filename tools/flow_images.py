@@ -4,6 +4,7 @@ run_DE_* binaries do (run_dense.cpp:185-431), for a list of pairs at once and wi
 (.pfm with --stereo).
 
     python tools/flow_images.py [--rgb] [--stereo [--lr [--fill MODE]]] [--op 1..4] [--fused] [--reverse] img1a img1b out1.flo [img2a img2b out2.flo ...]
+    python tools/flow_images.py --sequence [--rgb] [--op 1..4] [--fused] [--reverse] img0 img1 ... imgN stem
 
 All pairs must have one size.  --fused selects the FMA / fast-reciprocal arithmetic contract (default: the exact one, bit for
 bit what run_OF_INT / run_OF_RGB write).  --reverse (optical flow only) also writes, next to <stem>.flo, the reverse flow
@@ -13,7 +14,10 @@ with the default alpha 0.01 and beta 0.5).  --stereo --lr (the third argument of
 views of a stereo pair through an OFDIS_BATCH_STEREO_LR context and ofdis_batch_upsample_lr: <name>_left.pfm and
 <name>_right.pfm (disparity magnitudes as Middlebury stores them, rows bottom-up, +inf = unknown) and the left-right masks
 <name>_left_mask.pgm / <name>_right_mask.pgm (the same codes).  --fill none | invalidate | background (default none) says what
-happens to the pixels the masks flag (ofdis_disparity_fill)."""
+happens to the pixels the masks flag (ofdis_disparity_fill).  --sequence (optical flow only, --reverse allowed): the arguments
+are the N + 1 frames of a clip and a stem; the flow from frame k to frame k + 1 goes to <stem>_<k as 000>.flo.  Every frame is
+uploaded and built once, into an OFDIS_BATCH_SEQUENCE context (ofdis_batch_build_pyramids_u8_seq); the files are the ones the
+pair-wise call writes for (img0, img1), (img1, img2), ..."""
 import os
 import struct
 import sys
@@ -71,7 +75,7 @@ def write_pgm(path, mask):
 
 
 def main(argv):
-    opts = {"--rgb": False, "--stereo": False, "--fused": False, "--reverse": False, "--lr": False}
+    opts = {"--rgb": False, "--stereo": False, "--fused": False, "--reverse": False, "--lr": False, "--sequence": False}
     op = 2
     fill = "none"
     args = []
@@ -85,6 +89,12 @@ def main(argv):
             fill = next(it)
         else:
             args.append(a)
+    if opts["--sequence"]:
+        if opts["--stereo"]:
+            sys.exit("--sequence: a stereo pair is not a sequence")
+        if len(args) < 3:
+            sys.exit(__doc__)
+        args = [x for k in range(len(args) - 2) for x in (args[k], args[k + 1], f"{args[-1]}_{k:03d}.flo")]
     if not args or len(args) % 3:
         sys.exit(__doc__)
     if opts["--reverse"] and opts["--stereo"]:
@@ -97,16 +107,19 @@ def main(argv):
     noc = 3 if opts["--rgb"] else 1
     trip = [args[k:k + 3] for k in range(0, len(args), 3)]
     frames_a = [load(t[0], noc) for t in trip]
-    frames_b = [load(t[1], noc) for t in trip]
+    frames_b = [load(trip[-1][1], noc)] if opts["--sequence"] else [load(t[1], noc) for t in trip]
     h, w = frames_a[0].shape[:2]
     if any(f.shape != frames_a[0].shape for f in frames_a + frames_b):
         sys.exit("all images must have one size")
     capi.set_tuning(contract=1 if opts["--fused"] else 0)
     p = oppoint(op, w, h, noc=noc).copy(selectmode=2 if opts["--stereo"] else 1)
     p.width, p.height = padded_size(w, h, p.sc_f)
-    b = capi.Batch(p, len(trip), reverse=opts["--reverse"], stereo_lr=opts["--lr"])
-    da, db = capi.Dev(np.stack(frames_a)), capi.Dev(np.stack(frames_b))
-    b.build_pyramids_u8(da.ptr, db.ptr, w, h)
+    b = capi.Batch(p, len(trip), reverse=opts["--reverse"], stereo_lr=opts["--lr"], sequence=opts["--sequence"])
+    da, db = capi.Dev(np.stack(frames_a + frames_b if opts["--sequence"] else frames_a)), capi.Dev(np.stack(frames_b))
+    if opts["--sequence"]:  # the clip's frames, each once
+        b.build_pyramids_u8_seq(da.ptr, w, h)
+    else:
+        b.build_pyramids_u8(da.ptr, db.ptr, w, h)
     b.run()
     if opts["--lr"]:                 # both views and both masks in one launch
         left, right, mask_l, mask_r = b.upsample_lr(w, h, fills[fill])
