@@ -423,9 +423,8 @@ int ofdis_encode(const float* src, void* dst, size_t n, const ofdis_encoding* en
  * the same arguments, for both contracts and every kind of context (of an OFDIS_BATCH_REVERSE or OFDIS_BATCH_STEREO_LR
  * context: the forward result); the fp32 array is never written.  A lane encodes in registers and issues one 16-byte store per
  * output row where the rows' byte length and `out` are multiples of 16 bytes; other sizes take narrower stores, same bytes.
- * `out` is aligned to its element size (OFDIS_ENC_F32 with two channels: to 16 bytes, as for ofdis_batch_upsample_frames,
- * whose kernel that route is); nothing outside it is written.  Joins a pipelined pass by itself.  Argument errors: those of
- * ofdis_batch_upsample_frames and of the encoding. */
+ * `out` is aligned to its element size; nothing outside it is written.  Joins a pipelined pass by itself.  Argument errors:
+ * those of ofdis_batch_upsample_frames and of the encoding. */
 int ofdis_batch_upsample_frames_enc(ofdis_batch* b, int first_frame, int count, void* out, int width_org, int height_org,
                                     const ofdis_encoding* enc, void* stream);
 

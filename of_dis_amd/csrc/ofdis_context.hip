@@ -590,18 +590,31 @@ int ofdis_batch_upload_initflow(ofdis_batch* b, int frame, const float* initflow
   return OFDIS_OK;
 }
 
-int ofdis_batch_upsample_frames(ofdis_batch* b, int first_frame, int count, float* out_dev, int width_org,
-                                int height_org, void* stream) {
-  if (!b || !out_dev) return fail(OFDIS_ERR_INVALID, "bad arguments");
+// What every full-resolution finish of a context starts with: the frame range and the original size checked, the pass joined
+// (ofdis_batch_join), then the finish's geometry and where frames [first_frame, ...) start in a finest-level result array
+// (flow[0], flow_rev[0]).
+struct Finish {
+  UpGeom g;
+  size_t off;
+};
+static int finish_begin(ofdis_batch* b, int first_frame, int count, int width_org, int height_org, void* stream, Finish& fin) {
   if (first_frame < 0 || count < 1 || first_frame > b->nframes - count) return fail(OFDIS_ERR_INVALID, "frame range outside the batch");
   const ofdis_params& p = b->p;
   if (width_org < 1 || height_org < 1 || width_org > p.width || height_org > p.height)
     return fail(OFDIS_ERR_INVALID, "original size exceeds the padded size");
-  const LevelGeom& g = b->geom[0];
   if (int rc = ofdis_batch_join(b, stream)) return rc;
-  HIPCHK(launch_upsample_crop(frame_at(*b, b->flow[0], first_frame), out_dev, count, g.w, g.h, p.sc_l,
-                              (p.width - width_org) / 2, (p.height - height_org) / 2, width_org, height_org, b->nop,
-                              (hipStream_t)stream));
+  const LevelGeom& g = b->geom[0];
+  fin.g = UpGeom{g.w, g.h, p.sc_l, (p.width - width_org) / 2, (p.height - height_org) / 2, width_org, height_org};
+  fin.off = (size_t)first_frame * frame_elems(*b, b->flow[0]);
+  return OFDIS_OK;
+}
+
+int ofdis_batch_upsample_frames(ofdis_batch* b, int first_frame, int count, float* out_dev, int width_org,
+                                int height_org, void* stream) {
+  if (!b || !out_dev) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  Finish fin;
+  if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
+  HIPCHK(launch_upsample_crop(b->flow[0] + fin.off, out_dev, count, fin.g, b->nop, (hipStream_t)stream));
   return OFDIS_OK;
 }
 
@@ -642,16 +655,11 @@ int ofdis_encode(const float* src, void* dst, size_t n, const ofdis_encoding* en
 int ofdis_batch_upsample_frames_enc(ofdis_batch* b, int first_frame, int count, void* out, int width_org, int height_org,
                                     const ofdis_encoding* enc, void* stream) {
   if (!b || !out) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  if (first_frame < 0 || count < 1 || first_frame > b->nframes - count) return fail(OFDIS_ERR_INVALID, "frame range outside the batch");
-  const ofdis_params& p = b->p;
-  if (width_org < 1 || height_org < 1 || width_org > p.width || height_org > p.height)
-    return fail(OFDIS_ERR_INVALID, "original size exceeds the padded size");
   if (int rc = encoding_check(enc)) return rc;
-  const LevelGeom& g = b->geom[0];
-  if (int rc = ofdis_batch_join(b, stream)) return rc;
-  HIPCHK(launch_upsample_crop_enc(frame_at(*b, b->flow[0], first_frame), out, count, g.w, g.h, p.sc_l,
-                                  (p.width - width_org) / 2, (p.height - height_org) / 2, width_org, height_org, b->nop,
-                                  enc->type, enc->scale, enc->offset, (hipStream_t)stream));
+  Finish fin;
+  if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
+  HIPCHK(launch_upsample_crop_enc(b->flow[0] + fin.off, out, count, fin.g, b->nop, enc->type, enc->scale, enc->offset,
+                                  (hipStream_t)stream));
   return OFDIS_OK;
 }
 
@@ -677,17 +685,12 @@ int ofdis_batch_upsample_bidir(ofdis_batch* b, int first_frame, int count, float
                                uint8_t* mask_fw, uint8_t* mask_rev, int width_org, int height_org,
                                float alpha, float beta, void* stream) {
   if (!b || !b->reverse) return fail(OFDIS_ERR_INVALID, "not a context created with OFDIS_BATCH_REVERSE");
-  if (first_frame < 0 || count < 1 || first_frame > b->nframes - count) return fail(OFDIS_ERR_INVALID, "frame range outside the batch");
-  const ofdis_params& p = b->p;
-  if (width_org < 1 || height_org < 1 || width_org > p.width || height_org > p.height)
-    return fail(OFDIS_ERR_INVALID, "original size exceeds the padded size");
   if (!fb_constants_ok(alpha, beta)) return fail(OFDIS_ERR_INVALID, "alpha and beta must be finite and >= 0");
-  const LevelGeom& g = b->geom[0];
-  if (int rc = ofdis_batch_join(b, stream)) return rc;
+  Finish fin;
+  if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
   if (!out_fw && !out_rev && !mask_fw && !mask_rev) return OFDIS_OK;
-  HIPCHK(launch_upsample_bidir(frame_at(*b, b->flow[0], first_frame), frame_at(*b, b->flow_rev[0], first_frame), out_fw, out_rev,
-                               mask_fw, mask_rev, count, g.w, g.h, p.sc_l, (p.width - width_org) / 2,
-                               (p.height - height_org) / 2, width_org, height_org, alpha, beta, (hipStream_t)stream));
+  HIPCHK(launch_upsample_bidir(b->flow[0] + fin.off, b->flow_rev[0] + fin.off, out_fw, out_rev, mask_fw, mask_rev, count, fin.g,
+                               alpha, beta, (hipStream_t)stream));
   return OFDIS_OK;
 }
 
@@ -733,22 +736,17 @@ int ofdis_batch_upsample_lr(ofdis_batch* b, int first_frame, int count, float* o
                             uint8_t* mask_left, uint8_t* mask_right, int fill_mode, int width_org, int height_org,
                             float alpha, float beta, void* stream) {
   if (!b || !b->stereo_lr) return fail(OFDIS_ERR_INVALID, "not a context created with OFDIS_BATCH_STEREO_LR");
-  if (first_frame < 0 || count < 1 || first_frame > b->nframes - count) return fail(OFDIS_ERR_INVALID, "frame range outside the batch");
-  const ofdis_params& p = b->p;
-  if (width_org < 1 || height_org < 1 || width_org > p.width || height_org > p.height)
-    return fail(OFDIS_ERR_INVALID, "original size exceeds the padded size");
   if (!fill_mode_ok(fill_mode)) return fail(OFDIS_ERR_INVALID, "fill mode must be OFDIS_FILL_NONE, _INVALIDATE or _BACKGROUND");
   if (!fb_constants_ok(alpha, beta)) return fail(OFDIS_ERR_INVALID, "alpha and beta must be finite and >= 0");
-  const LevelGeom& g = b->geom[0];
   hipStream_t s = (hipStream_t)stream;
-  if (int rc = ofdis_batch_join(b, stream)) return rc;
+  Finish fin;
+  if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
   if (!out_left && !out_right && !mask_left && !mask_right) return OFDIS_OK;
-  const float* fw = frame_at(*b, b->flow[0], first_frame);
-  const float* mir = frame_at(*b, b->flow_rev[0], first_frame);
-  const int left = (p.width - width_org) / 2, top = (p.height - height_org) / 2;
+  const ofdis_params& p = b->p;
+  const float* fw = b->flow[0] + fin.off;
+  const float* mir = b->flow_rev[0] + fin.off;
   if (upsample_lr_fuses(width_org)) {
-    HIPCHK(launch_upsample_lr(fw, mir, out_left, out_right, mask_left, mask_right, count, g.w, g.h, p.sc_l, left, top, width_org,
-                              height_org, fill_mode, alpha, beta, s));
+    HIPCHK(launch_upsample_lr(fw, mir, out_left, out_right, mask_left, mask_right, count, fin.g, fill_mode, alpha, beta, s));
     return OFDIS_OK;
   }
   // wider than the fused kernel's rows: the composition itself, through staging owned by the context
@@ -762,7 +760,7 @@ int ofdis_batch_upsample_lr(ofdis_batch* b, int first_frame, int count, float* o
   const size_t n = (size_t)count * width_org * height_org;  // (count <= nframes, original size <= padded size)
   uint8_t* ml = mask_left ? mask_left : reinterpret_cast<uint8_t*>(b->lr_mask);
   uint8_t* mr = mask_right ? mask_right : reinterpret_cast<uint8_t*>(b->lr_mask) + n;
-  HIPCHK(launch_lr_materialise(fw, mir, b->lr_u, b->lr_dr, count, g.w, g.h, p.sc_l, left, top, width_org, height_org, s));
+  HIPCHK(launch_lr_materialise(fw, mir, b->lr_u, b->lr_dr, count, fin.g, s));
   if (mask_left || out_left) HIPCHK(launch_lr_check(b->lr_u, b->lr_dr, ml, count, width_org, height_org, alpha, beta, s));
   if (mask_right || out_right) HIPCHK(launch_lr_check(b->lr_dr, b->lr_u, mr, count, width_org, height_org, alpha, beta, s));
   if (out_left) HIPCHK(launch_disparity_fill(b->lr_u, ml, out_left, count, width_org, height_org, fill_mode, s));
@@ -792,19 +790,14 @@ int ofdis_batch_interpolate(ofdis_batch* b, const uint8_t* img_a, const uint8_t*
   if (!img_a || !img_b || !out) return fail(OFDIS_ERR_INVALID, "bad arguments");
   InterpTimes ts;
   if (int rc = interp_times(times, ntimes, ts)) return rc;
-  if (first_frame < 0 || count < 1 || first_frame > b->nframes - count) return fail(OFDIS_ERR_INVALID, "frame range outside the batch");
   const ofdis_params& p = b->p;
   if (p.noc != 1 && p.noc != 3) return fail(OFDIS_ERR_INVALID, "noc must be 1 or 3");
-  if (width_org < 1 || height_org < 1 || width_org > p.width || height_org > p.height)
-    return fail(OFDIS_ERR_INVALID, "original size exceeds the padded size");
   if (!fb_constants_ok(alpha, beta)) return fail(OFDIS_ERR_INVALID, "alpha and beta must be finite and >= 0");
-  const LevelGeom& g = b->geom[0];
-  if (int rc = ofdis_batch_join(b, stream)) return rc;
+  Finish fin;
+  if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
   const size_t img_off = (size_t)first_frame * width_org * height_org * p.noc;
-  HIPCHK(launch_interp_bidir(img_a + img_off, img_b + img_off, frame_at(*b, b->flow[0], first_frame),
-                             frame_at(*b, b->flow_rev[0], first_frame), out, count, g.w, g.h, p.sc_l,
-                             (p.width - width_org) / 2, (p.height - height_org) / 2, width_org, height_org, p.noc, ts, alpha,
-                             beta, (hipStream_t)stream));
+  HIPCHK(launch_interp_bidir(img_a + img_off, img_b + img_off, b->flow[0] + fin.off, b->flow_rev[0] + fin.off, out, count, fin.g,
+                             p.noc, ts, alpha, beta, (hipStream_t)stream));
   return OFDIS_OK;
 }
 

@@ -4,7 +4,7 @@
 //
 // Compiled under the exact contract only (-ffp-contract=off): every operation of the header's definition is a separately
 // rounded fp32 operation, so the output is a fixed function of the inputs and the fused kernel below -- which recomputes
-// the full-resolution flows and the masks from the level flows with the arithmetic of ofdis_batch_upsample_bidir
+// the full-resolution flows and the masks from the level flows with the helpers of ofdis_batch_upsample_bidir
 // (ofdis_upsample.h) -- writes the bits the standalone kernel writes on that function's materialised outputs.
 //
 // Mapping (both kernels): one lane owns a quad of 4 adjacent output pixels of one row; it evaluates the two flows at its
@@ -131,53 +131,30 @@ __global__ __launch_bounds__(256) void interp_frames_kernel(const uint8_t* __res
                    [&](int d, int nx, int ny) { return !mk[d] || mk[d][(size_t)ny * W + nx] == FB_CONSISTENT; });
 }
 
-// An OFDIS_BATCH_REVERSE context's level flows (sw x sh, 2^sc_l below the padded size; the output is the crop at
-// (left, top) of wo x ho): the flows at the quad's pixels and the fb codes at the sampled pixels recomputed with the
-// arithmetic of upsample_bidir_kernel (ofdis_pyr.hip), the codes per time at the two pixels the warps land nearest to.
+// An OFDIS_BATCH_REVERSE context's level flows (UpGeom): the flows at the quad's pixels and the fb codes at the sampled pixels
+// recomputed with the helpers upsample_bidir_kernel (ofdis_upsample.hip) uses -- upsample_at, fb_code on UpNeighbours -- the
+// codes per time at the two pixels the warps land nearest to.
 template <int NOC>
 __global__ __launch_bounds__(256) void interp_bidir_kernel(const uint8_t* __restrict__ img_a, const uint8_t* __restrict__ img_b,
                                                            const float2* __restrict__ fw, const float2* __restrict__ rev,
-                                                           uint8_t* __restrict__ out, int nframes, int sw, int sh, int sc_l,
-                                                           int left, int top, int wo, int ho, int bpf, InterpTimes ts,
-                                                           float alpha, float beta, bool vec_ok) {
+                                                           uint8_t* __restrict__ out, int nframes, UpGeom g, int bpf,
+                                                           InterpTimes ts, float alpha, float beta, bool vec_ok) {
   int f, blk;
   xcd_frame_map(blockIdx.x, bpf, nframes, f, blk);
+  const int wo = g.wo, ho = g.ho;
   const int qpr = (wo + 3) >> 2;
   const int qi = blk * 256 + threadIdx.x;
   if (f >= nframes || qi >= qpr * ho) return;
   const int y = qi / qpr, x = (qi - y * qpr) * 4;
-  const float scf = (float)(1 << sc_l), inv = 1.0f / scf;
-  const bool scale = sc_l > 0;
-  const float2* flw[2] = {fw + (size_t)f * sw * sh, rev + (size_t)f * sw * sh};
-  // direction d's full-resolution flow at pixel (xx, yy) of the crop
-  auto up_at = [&](int d, int xx, const UpRow& r) {
-    float2 a0, a1;
-    upsample_h(flw[d], sw, r.sy, r.sy1, xx + left, inv, scf, scale, a0, a1);
-    return up_mix(a0, a1, r.fy);
-  };
-  const UpRow ry = up_row(y + top, sh, inv);
+  const float2* flw[2] = {fw + (size_t)f * g.plane(), rev + (size_t)f * g.plane()};
+  const UpRow ry = up_row(y + g.top, g);
   const size_t plane = (size_t)wo * ho;
   uint8_t* out_row = out + ((size_t)f * ts.n * ho + y) * wo * NOC;
   interp_quad<NOC>(img_a + f * plane * NOC, img_b + f * plane * NOC, out_row, plane * NOC, x, y, wo, ho, ts,
-                   vec_ok && x + 4 <= wo, [&](int d, int xx) { return up_at(d, xx, ry); },
+                   vec_ok && x + 4 <= wo, [&](int d, int xx) { return upsample_at(flw[d], g, xx + g.left, ry); },
                    [&](int d, int nx, int ny) {
-                     const float2 val = up_at(d, nx, up_row(ny + top, sh, inv));
-                     const float2* oth = flw[1 - d];
-                     return fb_code(val.x, val.y, nx, ny, wo, ho, alpha, beta,
-                                    [&](int x0, int x1, int y0, int y1, float2& r00, float2& r01, float2& r10, float2& r11) {
-                                      const UpRow q0 = up_row(y0 + top, sh, inv), q1 = up_row(y1 + top, sh, inv);
-                                      float2 p0, p1, n0, n1;  // row pair of y0 at columns x0 and x1
-                                      upsample_h(oth, sw, q0.sy, q0.sy1, x0 + left, inv, scf, scale, p0, p1);
-                                      upsample_h(oth, sw, q0.sy, q0.sy1, x1 + left, inv, scf, scale, n0, n1);
-                                      r00 = up_mix(p0, p1, q0.fy);
-                                      r01 = up_mix(n0, n1, q0.fy);
-                                      if (q1.sy != q0.sy) {  // (sy1 is a function of sy)
-                                        upsample_h(oth, sw, q1.sy, q1.sy1, x0 + left, inv, scf, scale, p0, p1);
-                                        upsample_h(oth, sw, q1.sy, q1.sy1, x1 + left, inv, scf, scale, n0, n1);
-                                      }
-                                      r10 = up_mix(p0, p1, q1.fy);
-                                      r11 = up_mix(n0, n1, q1.fy);
-                                    }) == FB_CONSISTENT;
+                     const float2 val = upsample_at(flw[d], g, nx + g.left, ny + g.top);
+                     return fb_code(val.x, val.y, nx, ny, wo, ho, alpha, beta, UpNeighbours{flw[1 - d], g}) == FB_CONSISTENT;
                    });
 }
 
@@ -226,11 +203,10 @@ hipError_t launch_interp_frames(const uint8_t* img_a, const uint8_t* img_b, cons
 }
 
 hipError_t launch_interp_bidir(const uint8_t* img_a, const uint8_t* img_b, const float* fw, const float* rev, uint8_t* out,
-                               int nframes, int sw, int sh, int sc_l, int left, int top, int wo, int ho, int noc,
-                               const InterpTimes& ts, float alpha, float beta, hipStream_t s) {
-  const InterpGrid g = interp_grid(nframes, wo, ho);
-  const bool vec = (wo & 3) == 0 && ((uintptr_t)out & 3) == 0;
-  const size_t plane = (size_t)wo * ho, lplane = (size_t)sw * sh;
+                               int nframes, UpGeom ug, int noc, const InterpTimes& ts, float alpha, float beta, hipStream_t s) {
+  const InterpGrid g = interp_grid(nframes, ug.wo, ug.ho);
+  const bool vec = (ug.wo & 3) == 0 && ((uintptr_t)out & 3) == 0;
+  const size_t plane = (size_t)ug.wo * ug.ho, lplane = ug.plane();
   for (int f0 = 0; f0 < nframes; f0 += g.chunk) {
     const int n = std::min(g.chunk, nframes - f0);
     const float2* ff = (const float2*)fw + (size_t)f0 * lplane;
@@ -238,11 +214,10 @@ hipError_t launch_interp_bidir(const uint8_t* img_a, const uint8_t* img_b, const
     uint8_t* o = out + (size_t)f0 * plane * noc * ts.n;
     if (noc == 3)
       hipLaunchKernelGGL(interp_bidir_kernel<3>, dim3(interp_blocks(n, g.bpf)), dim3(256), 0, s, img_a + (size_t)f0 * plane * 3,
-                         img_b + (size_t)f0 * plane * 3, ff, fr, o, n, sw, sh, sc_l, left, top, wo, ho, g.bpf, ts, alpha, beta,
-                         vec);
+                         img_b + (size_t)f0 * plane * 3, ff, fr, o, n, ug, g.bpf, ts, alpha, beta, vec);
     else
       hipLaunchKernelGGL(interp_bidir_kernel<1>, dim3(interp_blocks(n, g.bpf)), dim3(256), 0, s, img_a + (size_t)f0 * plane,
-                         img_b + (size_t)f0 * plane, ff, fr, o, n, sw, sh, sc_l, left, top, wo, ho, g.bpf, ts, alpha, beta, vec);
+                         img_b + (size_t)f0 * plane, ff, fr, o, n, ug, g.bpf, ts, alpha, beta, vec);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }

@@ -51,6 +51,24 @@ struct TvGeom {
   int w, h, noc, nframes;
 };
 
+// The full-resolution finish (ofdis_upsample.h): the level flow, sw x sh and a factor 2^sc_l below the padded size, goes to
+// the crop of wo x ho pixels at (left, top) of the padded full-resolution image.
+struct UpGeom {
+  int sw, sh, sc_l, left, top, wo, ho;
+  __host__ __device__ float scf() const { return (float)(1 << sc_l); }
+  __host__ __device__ float inv() const { return 1.0f / scf(); }  // (a power of two: exact)
+  __host__ __device__ bool scale() const { return sc_l > 0; }
+  __host__ __device__ size_t plane() const { return (size_t)sw * sh; }  // pixels of one frame's level flow
+};
+
+// blocks of 256 threads for a grid-stride loop over `total` elements
+inline unsigned grid_for(long long total) {
+  long long b = (total + 255) / 256;
+  if (b > (1 << 20)) b = 1 << 20;
+  if (b < 1) b = 1;
+  return (unsigned)b;
+}
+
 // image_warp.  src: either the padded interleaved pyramid plane (src_padded=1: [B][tmp_h][tmp_w][noc],
 // pad/tmp_w given) or packed planar [B][noc][h][w] (src_padded=0).  dst: [B][noc][h][w], mask [B][h][w].
 struct WarpArgs {
@@ -174,13 +192,13 @@ hipError_t launch_pyr_planes(const float* src, float* img, float* dx, float* dy,
                              int pad, hipStream_t s, float* down = nullptr);
 bool pyr_planes_fuses_down(int w, int h, int noc, int pad);
 
-// x 2^sc_l, bilinear upsample (cv::resize INTER_LINEAR) and crop of the AoS result (run_dense.cpp:406-414)
-hipError_t launch_upsample_crop(const float* flow, float* out, int nframes, int sw, int sh, int sc_l, int left, int top,
-                                int wo, int ho, int channels, hipStream_t s);
+// result to full resolution (ofdis_upsample.hip).  x 2^sc_l, bilinear upsample (cv::resize INTER_LINEAR) and crop of the AoS
+// result (run_dense.cpp:406-414): the OFDIS_ENC_F32 kernel of launch_upsample_crop_enc
+hipError_t launch_upsample_crop(const float* flow, float* out, int nframes, UpGeom g, int channels, hipStream_t s);
 // the same, written in an output encoding (include/ofdis.h: ofdis_encoding; `type` already validated): out = [nframes][ho][wo]
 // [channels] elements.  OFDIS_ENC_F32 with two channels is launch_upsample_crop.
-hipError_t launch_upsample_crop_enc(const float* flow, void* out, int nframes, int sw, int sh, int sc_l, int left, int top,
-                                    int wo, int ho, int channels, int type, float scale, float offset, hipStream_t s);
+hipError_t launch_upsample_crop_enc(const float* flow, void* out, int nframes, UpGeom g, int channels, int type, float scale,
+                                    float offset, hipStream_t s);
 // n fp32 values of a materialised array into that encoding (ofdis_encode)
 hipError_t launch_encode(const float* src, void* dst, size_t n, int type, float scale, float offset, hipStream_t s);
 // forward-backward consistency test (include/ofdis.h: ofdis_fb_check) on full-resolution AoS flows
@@ -188,8 +206,7 @@ hipError_t launch_fb_check(const float* flow, const float* other, uint8_t* mask,
                            float beta, hipStream_t s);
 // both directions' level flows to full resolution plus both masks in one launch (ofdis_batch_upsample_bidir); outputs may be null
 hipError_t launch_upsample_bidir(const float* fw, const float* rev, float* out_fw, float* out_rev, uint8_t* mask_fw,
-                                 uint8_t* mask_rev, int nframes, int sw, int sh, int sc_l, int left, int top, int wo, int ho,
-                                 float alpha, float beta, hipStream_t s);
+                                 uint8_t* mask_rev, int nframes, UpGeom g, float alpha, float beta, hipStream_t s);
 // stereo left-right step (include/ofdis.h; ofdis_stereo_lr.hip).  mir(I)[y][x] = I[y][w-1-x] on [n][h][w][noc] 8-bit frames:
 hipError_t launch_mirror_u8(const uint8_t* src, uint8_t* dst, int nframes, int w, int h, int noc, hipStream_t s);
 hipError_t launch_lr_check(const float* disp, const float* other, uint8_t* mask, int nframes, int w, int h, float alpha,
@@ -201,11 +218,9 @@ hipError_t launch_disparity_fill(const float* disp, const uint8_t* mask, float* 
 bool upsample_lr_fuses(int wo);
 size_t upsample_lr_row_bytes(int wo);  // LDS per output row
 hipError_t launch_upsample_lr(const float* fw, const float* mir, float* out_l, float* out_r, uint8_t* mask_l, uint8_t* mask_r,
-                              int nframes, int sw, int sh, int sc_l, int left, int top, int wo, int ho, int fill_mode,
-                              float alpha, float beta, hipStream_t s);
+                              int nframes, UpGeom g, int fill_mode, float alpha, float beta, hipStream_t s);
 // ... and, above them, the first step of the composition: U and DR = -Dm un-mirrored, materialised
-hipError_t launch_lr_materialise(const float* fw, const float* mir, float* u, float* dr, int nframes, int sw, int sh, int sc_l,
-                                 int left, int top, int wo, int ho, hipStream_t s);
+hipError_t launch_lr_materialise(const float* fw, const float* mir, float* u, float* dr, int nframes, UpGeom g, hipStream_t s);
 // frame interpolation (include/ofdis.h: ofdis_interpolate; ofdis_interp.hip).  The times travel by value in the launch.
 struct InterpTimes {
   float t[16];  // OFDIS_INTERP_MAX_TIMES
@@ -217,8 +232,7 @@ hipError_t launch_interp_frames(const uint8_t* img_a, const uint8_t* img_b, cons
                                 int noc, const InterpTimes& ts, hipStream_t s);
 // straight from both directions' level flows (ofdis_batch_interpolate): flows and masks as launch_upsample_bidir computes them
 hipError_t launch_interp_bidir(const uint8_t* img_a, const uint8_t* img_b, const float* fw, const float* rev, uint8_t* out,
-                               int nframes, int sw, int sh, int sc_l, int left, int top, int wo, int ho, int noc,
-                               const InterpTimes& ts, float alpha, float beta, hipStream_t s);
+                               int nframes, UpGeom g, int noc, const InterpTimes& ts, float alpha, float beta, hipStream_t s);
 
 // ---- stereo-depth mode (SELECTMODE=2; ofdis_de.hip)
 struct DeSystemArgs {

@@ -1,34 +1,11 @@
 // ofdis_lr.h -- device helpers of the stereo left-right step (ofdis_stereo_lr.hip, compiled under the exact contract only, so
-// every kernel that uses them computes the same bits): the one-channel level disparity to full resolution, the left-right
-// consistency test of include/ofdis.h (ofdis_lr_check) and the row scan of ofdis_disparity_fill.  Each is written once here
-// for the standalone kernels and for the fused finish (upsample_lr_kernel).
+// every kernel that uses them computes the same bits): the left-right consistency test of include/ofdis.h (ofdis_lr_check) and
+// the row scan of ofdis_disparity_fill.  Each is written once here for the standalone kernels and for the fused finish
+// (upsample_lr_kernel); the one-channel level disparity to full resolution is upsample_at<float> of ofdis_upsample.h.
 #pragma once
 #include "ofdis_upsample.h"
 
 namespace ofdis {
-
-// One pixel of what upsample_crop1_kernel (ofdis_pyr.hip) writes: the level disparity `fl` (sw x sh) at padded full-resolution
-// pixel (X, Y), cv::resize INTER_LINEAR with the values times 2^sc_l.  The same expressions in the same order: the same bits.
-__device__ __forceinline__ float upsample1(const float* __restrict__ fl, int sw, int sh, float scf, float inv, bool scale, int X,
-                                           int Y) {
-  float fy = ((float)Y + 0.5f) * inv - 0.5f;
-  int sy = (int)floorf(fy);
-  fy -= (float)sy;
-  if (sy < 0) { sy = 0; fy = 0.0f; }
-  if (sy >= sh - 1) { sy = sh - 1; fy = 0.0f; }
-  const int sy1 = min(sy + 1, sh - 1);
-  float fx = ((float)X + 0.5f) * inv - 0.5f;
-  int sx = (int)floorf(fx);
-  fx -= (float)sx;
-  if (sx < 0) { sx = 0; fx = 0.0f; }
-  if (sx >= sw - 1) { sx = sw - 1; fx = 0.0f; }
-  const int sx1 = min(sx + 1, sw - 1);
-  float v00 = fl[sy * sw + sx], v01 = fl[sy * sw + sx1], v10 = fl[sy1 * sw + sx], v11 = fl[sy1 * sw + sx1];
-  if (scale) { v00 *= scf; v01 *= scf; v10 *= scf; v11 *= scf; }
-  const float ax = 1.0f - fx, ay = 1.0f - fy;
-  const float r0 = v00 * ax + v01 * fx, r1 = v10 * ax + v11 * fx;
-  return r0 * ay + r1 * fy;
-}
 
 // The left-right test for the pixel at column x with displacement d towards the other view; `R(xx)` returns the other view's
 // displacement at an integer column of the same row.  fb_code (ofdis_upsample.h) with v = 0 and the vertical blend dropped.

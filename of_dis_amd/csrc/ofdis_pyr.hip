@@ -14,7 +14,6 @@
 // all of 0..sc_f, run_dense.cpp:132, and never reads the rest), and image B gets no gradients (never
 // read when usefbcon == 0).
 #include "ofdis_kernels.h"
-#include "ofdis_upsample.h"
 
 namespace ofdis {
 
@@ -238,13 +237,6 @@ __global__ __launch_bounds__(256) void pyr_planes_gray4_kernel(const float* __re
   }
 }
 
-static unsigned grid_for(long long total) {
-  long long b = (total + 255) / 256;
-  if (b > (1 << 20)) b = 1 << 20;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
-
 hipError_t launch_pyr_base(const uint8_t* src, float* dst, int nframes, int wo, int ho, int W, int H, int noc, int l,
                            size_t pitch, size_t stride, hipStream_t s) {
   const long long total = (long long)nframes * (H >> l) * (W >> l) * noc;
@@ -291,360 +283,5 @@ hipError_t launch_pyr_planes(const float* src, float* img, float* dx, float* dy,
   return hipGetLastError();
 }
 
-// ------------------------------------------------------------------------------------ result to full resolution
-// run_dense.cpp:406-414: flowout *= 2^lv_l; cv::resize(flowout, x 2^lv_l, INTER_LINEAR); crop the padding.
-// cv::resize bilinear for CV_32FC2: half-pixel centres, source index clamped with the fraction forced to 0 at
-// the borders, horizontal interpolation first.  2^lv_l is a power of two, so (X + 0.5) / s - 0.5 is exact in fp32.
-// One thread per output pixel, 8-byte stores; the source (57 KB per frame at op-point 2) is L2 resident.
-// grid = (x chunks of 512 pixels, groups of 2^sc_l output rows that share their two source rows, frame); a thread owns
-// two adjacent output columns (16 bytes per store): it interpolates them horizontally on the two source rows ONCE and then
-// writes the <= 2^sc_l rows of the group, which differ only in the vertical weight.  The output is written once
-// and never read by this library: non-temporal stores.
-typedef float f4v __attribute__((ext_vector_type(4)));
-typedef float f2v __attribute__((ext_vector_type(2)));
-__global__ __launch_bounds__(256) void upsample_crop_kernel(const float2* __restrict__ flow, float2* __restrict__ out,
-                                                            int sw, int sh, int sc_l, int left, int top, int wo, int ho) {
-  const int f = blockIdx.z;
-  const int x = (blockIdx.x * 256 + threadIdx.x) * 2;
-  if (x >= wo) return;
-  const int s = 1 << sc_l;
-  const float scf = (float)s, inv = 1.0f / scf;
-  // the padded rows with floor((Y + 0.5) / s - 0.5) = k are [k*s + s/2, k*s + s/2 + s); k = -1 (s > 1 only) and k = sh-1
-  // are the half groups at the borders, where the source row is clamped and the weight forced to 0
-  const int k = (int)blockIdx.y - (s > 1 ? 1 : 0);
-  const int Y0 = max(k * s + s / 2, top), Y1 = min(k * s + s / 2 + s, top + ho);  // rows of the group inside the crop
-  if (Y0 >= Y1) return;
-  float fy0 = ((float)Y0 + 0.5f) * inv - 0.5f;
-  int sy = (int)floorf(fy0);
-  const bool clamp_lo = sy < 0, clamp_hi = sy >= sh - 1;
-  if (clamp_lo) sy = 0;
-  if (clamp_hi) sy = sh - 1;
-  const int sy1 = min(sy + 1, sh - 1);
-  const float2* fl = flow + (size_t)f * sw * sh;
-  float2 a0, a1, b0, b1;
-  upsample_h(fl, sw, sy, sy1, x + left, inv, scf, sc_l > 0, a0, a1);
-  const bool two = x + 1 < wo;
-  if (two) upsample_h(fl, sw, sy, sy1, x + 1 + left, inv, scf, sc_l > 0, b0, b1);
-  const bool vec = two && (wo & 1) == 0;  // rows are 16-byte aligned when wo is even
-  for (int Y = Y0; Y < Y1; ++Y) {
-    float fy = ((float)Y + 0.5f) * inv - 0.5f;
-    fy -= floorf(fy);
-    if (clamp_lo || clamp_hi) fy = 0.0f;
-    const float ay = 1.0f - fy;
-    float2* o = out + ((size_t)f * ho + (Y - top)) * wo + x;
-    const float2 a = make_float2(a0.x * ay + a1.x * fy, a0.y * ay + a1.y * fy);
-    if (two) {
-      const float2 b = make_float2(b0.x * ay + b1.x * fy, b0.y * ay + b1.y * fy);
-      if (vec) {
-        __builtin_nontemporal_store((f4v){a.x, a.y, b.x, b.y}, reinterpret_cast<f4v*>(o));
-      } else {
-        o[0] = a;
-        o[1] = b;
-      }
-    } else {
-      o[0] = a;
-    }
-  }
-}
-
-// one-channel result of the stereo-depth mode (CV_32FC1, same resize): one pixel per thread
-__global__ __launch_bounds__(256) void upsample_crop1_kernel(const float* __restrict__ flow, float* __restrict__ out,
-                                                             int sw, int sh, int sc_l, int left, int top, int wo, int ho) {
-  const int f = blockIdx.z, y = blockIdx.y;
-  const int x = blockIdx.x * 256 + threadIdx.x;
-  if (x >= wo) return;
-  const float scf = (float)(1 << sc_l), inv = 1.0f / scf;
-  float fy = ((float)(y + top) + 0.5f) * inv - 0.5f;
-  int sy = (int)floorf(fy);
-  fy -= (float)sy;
-  if (sy < 0) { sy = 0; fy = 0.0f; }
-  if (sy >= sh - 1) { sy = sh - 1; fy = 0.0f; }
-  const int sy1 = min(sy + 1, sh - 1);
-  float fx = ((float)(x + left) + 0.5f) * inv - 0.5f;
-  int sx = (int)floorf(fx);
-  fx -= (float)sx;
-  if (sx < 0) { sx = 0; fx = 0.0f; }
-  if (sx >= sw - 1) { sx = sw - 1; fx = 0.0f; }
-  const int sx1 = min(sx + 1, sw - 1);
-  const float* fl = flow + (size_t)f * sw * sh;
-  float v00 = fl[sy * sw + sx], v01 = fl[sy * sw + sx1], v10 = fl[sy1 * sw + sx], v11 = fl[sy1 * sw + sx1];
-  if (sc_l > 0) { v00 *= scf; v01 *= scf; v10 *= scf; v11 *= scf; }
-  const float ax = 1.0f - fx, ay = 1.0f - fy;
-  const float r0 = v00 * ax + v01 * fx, r1 = v10 * ax + v11 * fx;
-  out[((size_t)f * ho + y) * wo + x] = r0 * ay + r1 * fy;
-}
-
-hipError_t launch_upsample_crop(const float* flow, float* out, int nframes, int sw, int sh, int sc_l, int left, int top,
-                                int wo, int ho, int channels, hipStream_t s) {
-  if (ho > 65535 || nframes > 65535) return hipErrorInvalidValue;
-  if (channels == 1) {
-    hipLaunchKernelGGL(upsample_crop1_kernel, dim3((wo + 255) / 256, ho, nframes), dim3(256), 0, s, flow, out, sw, sh,
-                       sc_l, left, top, wo, ho);
-    return hipGetLastError();
-  }
-  // row groups k = -1 .. sh-1 (k = 0 .. sh for sc_l = 0, the last one empty)
-  hipLaunchKernelGGL(upsample_crop_kernel, dim3((wo + 511) / 512, sh + 1, nframes), dim3(256), 0, s, (const float2*)flow,
-                     (float2*)out, sw, sh, sc_l, left, top, wo, ho);
-  return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------ result to full resolution, encoded
-// ofdis_batch_upsample_frames_enc: the values of the two kernels above, encoded in registers (include/ofdis.h: ofdis_encoding)
-// and written once.  The kernel is its stores, so a lane still issues ONE 16-byte non-temporal store per output row: it owns
-// the NV = 16 / element size adjacent values of a row -- NV / C columns (C = 2: 4 / 8 columns of 2- / 1-byte elements, C = 1
-// twice as many) -- interpolates them horizontally on the two source rows once and reuses them over the <= 2^sc_l rows of the
-// group, like upsample_crop_kernel.  Lanes are numbered over (row group, 16-byte chunk of the row) so that rows shorter than a
-// workgroup's 4 KB leave no lanes idle.  `align` = the largest power of two <= 16 that divides both the row's byte length and
-// the address of `out`: below 16 (odd widths and the like) a lane writes its chunk in pieces of that size.
-__device__ __forceinline__ void store_chunk16(uint8_t* o, const unsigned (&w)[4], int nb, int align) {
-  if (align >= 16) {  // (then every chunk of a row is whole: nb == 16)
-    __builtin_nontemporal_store((u4){w[0], w[1], w[2], w[3]}, reinterpret_cast<u4*>(o));
-  } else if (align >= 8) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-      if (8 * i < nb) *reinterpret_cast<uint2*>(o + 8 * i) = make_uint2(w[2 * i], w[2 * i + 1]);
-  } else if (align >= 4) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (4 * i < nb) *reinterpret_cast<unsigned*>(o + 4 * i) = w[i];
-  } else if (align >= 2) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-      if (2 * i < nb) *reinterpret_cast<unsigned short*>(o + 2 * i) = (unsigned short)(w[i >> 1] >> (16 * (i & 1)));
-  } else {
-#pragma unroll
-    for (int i = 0; i < 16; ++i)
-      if (i < nb) o[i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
-  }
-}
-
-template <int TYPE, int C>
-__global__ __launch_bounds__(256) void upsample_crop_enc_kernel(const float* __restrict__ flow, uint8_t* __restrict__ out,
-                                                                int sw, int sh, int sc_l, int left, int top, int wo, int ho,
-                                                                int chunks, int align, float scale, float offset) {
-  constexpr int NV = EncTraits<TYPE>::per16, NCOL = NV / C;
-  const int f = blockIdx.y;
-  const unsigned id = blockIdx.x * 256u + threadIdx.x;
-  const int grp = (int)(id / (unsigned)chunks), ch = (int)(id - (unsigned)grp * (unsigned)chunks);
-  if (grp > sh) return;
-  const int x = ch * NCOL;  // first column of the lane (< wo: chunks = ceil(wo / NCOL))
-  const int s = 1 << sc_l;
-  const float scf = (float)s, inv = 1.0f / scf;
-  // row groups as in upsample_crop_kernel: k = -1 .. sh-1 (k = 0 .. sh for s = 1, the last one empty)
-  const int k = grp - (s > 1 ? 1 : 0);
-  const int Y0 = max(k * s + s / 2, top), Y1 = min(k * s + s / 2 + s, top + ho);
-  if (Y0 >= Y1) return;
-  const float fy0 = ((float)Y0 + 0.5f) * inv - 0.5f;
-  int sy = (int)floorf(fy0);
-  const bool clamp_lo = sy < 0, clamp_hi = sy >= sh - 1;
-  if (clamp_lo) sy = 0;
-  if (clamp_hi) sy = sh - 1;
-  const int sy1 = min(sy + 1, sh - 1);
-  const float* fl = flow + (size_t)f * sw * sh * C;
-  float r0[NV], r1[NV];  // the lane's values on the two source rows, in memory order
-#pragma unroll
-  for (int c = 0; c < NCOL; ++c) {
-    const int X = min(x + c, wo - 1) + left;  // (columns past the row's end repeat the last one; they are not stored)
-    if constexpr (C == 2) {
-      float2 a0, a1;
-      upsample_h(reinterpret_cast<const float2*>(fl), sw, sy, sy1, X, inv, scf, sc_l > 0, a0, a1);
-      r0[2 * c] = a0.x; r0[2 * c + 1] = a0.y;
-      r1[2 * c] = a1.x; r1[2 * c + 1] = a1.y;
-    } else {
-      upsample_h1(fl, sw, sy, sy1, X, inv, scf, sc_l > 0, r0[c], r1[c]);
-    }
-  }
-  const int row_bytes = wo * C * EncTraits<TYPE>::bytes;
-  const int nb = min(16, row_bytes - ch * 16);
-  for (int Y = Y0; Y < Y1; ++Y) {
-    float fy = ((float)Y + 0.5f) * inv - 0.5f;
-    fy -= floorf(fy);
-    if (clamp_lo || clamp_hi) fy = 0.0f;
-    const float ay = 1.0f - fy;
-    float v[NV];
-#pragma unroll
-    for (int i = 0; i < NV; ++i) v[i] = r0[i] * ay + r1[i] * fy;
-    unsigned w[4];
-    enc_pack16<TYPE>(v, scale, offset, w);
-    store_chunk16(out + ((size_t)f * ho + (Y - top)) * row_bytes + (size_t)ch * 16, w, nb, align);
-  }
-}
-
-// largest power of two <= 16 dividing the address and the byte length of a row
-static int store_align(const void* p, size_t row_bytes) {
-  const size_t v = (size_t)(uintptr_t)p | row_bytes | 16;
-  return (int)(v & (~v + 1));
-}
-
-template <int TYPE>
-static hipError_t launch_upsample_crop_enc_t(const float* flow, void* out, int nframes, int sw, int sh, int sc_l, int left,
-                                             int top, int wo, int ho, int channels, float scale, float offset, hipStream_t s) {
-  const int ncol = EncTraits<TYPE>::per16 / channels;
-  const int chunks = (wo + ncol - 1) / ncol;
-  const long long lanes = (long long)chunks * (sh + 1);
-  const long long row_bytes = (long long)wo * channels * EncTraits<TYPE>::bytes;
-  if (nframes > 65535 || lanes >= (1ll << 31) || row_bytes >= (1ll << 31)) return hipErrorInvalidValue;
-  const dim3 grid((unsigned)((lanes + 255) / 256), (unsigned)nframes);
-  const int align = store_align(out, (size_t)row_bytes);
-  if (channels == 1)
-    hipLaunchKernelGGL((upsample_crop_enc_kernel<TYPE, 1>), grid, dim3(256), 0, s, flow, (uint8_t*)out, sw, sh, sc_l, left, top,
-                       wo, ho, chunks, align, scale, offset);
-  else
-    hipLaunchKernelGGL((upsample_crop_enc_kernel<TYPE, 2>), grid, dim3(256), 0, s, flow, (uint8_t*)out, sw, sh, sc_l, left, top,
-                       wo, ho, chunks, align, scale, offset);
-  return hipGetLastError();
-}
-
-hipError_t launch_upsample_crop_enc(const float* flow, void* out, int nframes, int sw, int sh, int sc_l, int left, int top,
-                                    int wo, int ho, int channels, int type, float scale, float offset, hipStream_t s) {
-  switch (type) {
-    case ENC_F32:
-      // the bits unchanged.  Two channels: upsample_crop_kernel itself, which already has this mapping.  One channel: this
-      // file's kernel -- upsample_crop1_kernel stores 4 bytes per lane and row and interpolates every row anew (4.07 against
-      // 1.34 ms per 4096 frames of 1024x436 for the same bits: profiles/README.md)
-      if (channels == 1)
-        return launch_upsample_crop_enc_t<ENC_F32>(flow, out, nframes, sw, sh, sc_l, left, top, wo, ho, channels, scale, offset, s);
-      return launch_upsample_crop(flow, (float*)out, nframes, sw, sh, sc_l, left, top, wo, ho, channels, s);
-    case ENC_F16: return launch_upsample_crop_enc_t<ENC_F16>(flow, out, nframes, sw, sh, sc_l, left, top, wo, ho, channels, scale, offset, s);
-    case ENC_U16: return launch_upsample_crop_enc_t<ENC_U16>(flow, out, nframes, sw, sh, sc_l, left, top, wo, ho, channels, scale, offset, s);
-    case ENC_U8: return launch_upsample_crop_enc_t<ENC_U8>(flow, out, nframes, sw, sh, sc_l, left, top, wo, ho, channels, scale, offset, s);
-  }
-  return hipErrorInvalidValue;
-}
-
-// ofdis_encode on a materialised array: a lane converts the 16 / element size values of one 16-byte store per step (16-byte
-// loads), grid-stride; the values past the last whole store -- every value when src or dst is not 16-byte aligned -- one by one.
-template <int TYPE>
-__global__ __launch_bounds__(256) void encode_kernel(const float* __restrict__ src, uint8_t* __restrict__ dst, size_t n,
-                                                     size_t nvec, float scale, float offset) {
-  constexpr int NV = EncTraits<TYPE>::per16, EB = EncTraits<TYPE>::bytes;
-  const size_t t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = t0; i < nvec; i += stride) {
-    float v[NV];
-#pragma unroll
-    for (int q = 0; q < NV / 4; ++q) {
-      const f4p t = reinterpret_cast<const f4p*>(src)[i * (NV / 4) + q];
-      v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
-    }
-    unsigned w[4];
-    enc_pack16<TYPE>(v, scale, offset, w);
-    reinterpret_cast<u4*>(dst)[i] = (u4){w[0], w[1], w[2], w[3]};
-  }
-  for (size_t i = nvec * NV + t0; i < n; i += stride) {
-    const unsigned q = enc_bits<TYPE>(src[i], scale, offset);
-    if constexpr (EB == 4) reinterpret_cast<unsigned*>(dst)[i] = q;
-    else if constexpr (EB == 2) reinterpret_cast<unsigned short*>(dst)[i] = (unsigned short)q;
-    else dst[i] = (uint8_t)q;
-  }
-}
-
-template <int TYPE>
-static hipError_t launch_encode_t(const float* src, void* dst, size_t n, float scale, float offset, hipStream_t s) {
-  const bool aligned = (((uintptr_t)src | (uintptr_t)dst) & 15) == 0;
-  const size_t nvec = aligned ? n / EncTraits<TYPE>::per16 : 0;
-  const size_t work = nvec > n - nvec * EncTraits<TYPE>::per16 ? nvec : n - nvec * EncTraits<TYPE>::per16;
-  hipLaunchKernelGGL(encode_kernel<TYPE>, dim3(grid_for((long long)work)), dim3(256), 0, s, src, (uint8_t*)dst, n, nvec, scale,
-                     offset);
-  return hipGetLastError();
-}
-
-hipError_t launch_encode(const float* src, void* dst, size_t n, int type, float scale, float offset, hipStream_t s) {
-  switch (type) {
-    case ENC_F32: return launch_encode_t<ENC_F32>(src, dst, n, scale, offset, s);
-    case ENC_F16: return launch_encode_t<ENC_F16>(src, dst, n, scale, offset, s);
-    case ENC_U16: return launch_encode_t<ENC_U16>(src, dst, n, scale, offset, s);
-    case ENC_U8: return launch_encode_t<ENC_U8>(src, dst, n, scale, offset, s);
-  }
-  return hipErrorInvalidValue;
-}
-
-// ------------------------------------------------------------------------------------ forward-backward consistency
-// materialised flows: one pixel per thread, grid-stride over all frames
-__global__ __launch_bounds__(256) void fb_check_kernel(const float2* __restrict__ flow, const float2* __restrict__ other,
-                                                       uint8_t* __restrict__ mask, long long total, int w, int h,
-                                                       float alpha, float beta) {
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-    const int x = (int)(i % w);
-    const long long r = i / w;
-    const int y = (int)(r % h);
-    const float2* R = other + (i - (long long)y * w - x);  // the frame's first pixel
-    const float2 uv = flow[i];
-    mask[i] = fb_code(uv.x, uv.y, x, y, w, h, alpha, beta,
-                      [&](int x0, int x1, int y0, int y1, float2& r00, float2& r01, float2& r10, float2& r11) {
-                        r00 = R[(size_t)y0 * w + x0]; r01 = R[(size_t)y0 * w + x1];
-                        r10 = R[(size_t)y1 * w + x0]; r11 = R[(size_t)y1 * w + x1];
-                      });
-  }
-}
-
-hipError_t launch_fb_check(const float* flow, const float* other, uint8_t* mask, int nframes, int w, int h, float alpha,
-                           float beta, hipStream_t s) {
-  const long long total = (long long)nframes * w * h;
-  hipLaunchKernelGGL(fb_check_kernel, dim3(grid_for(total)), dim3(256), 0, s, (const float2*)flow, (const float2*)other, mask,
-                     total, w, h, alpha, beta);
-  return hipGetLastError();
-}
-
-// Both directions to full resolution and both masks, one pixel per thread (grid = (x chunks of 256, output rows, frames)).
-// The masks need the OTHER direction's upsampled flow at the four integer neighbours of a non-integer target: recomputed
-// from the level flow with upsample_h / up_row / up_mix -- the arithmetic of upsample_crop_kernel, so the values are the
-// bits ofdis_batch_upsample_frames writes -- instead of read back from HBM.  Neighbour rows y0 and y1 usually share their
-// source rows (for s > 1): then the two horizontal interpolations are reused.  The level flows (57 KB per frame and
-// direction at operating point 2, 2 MB at 1080p) are gathered through the caches.
-typedef float f2n __attribute__((ext_vector_type(2)));
-__global__ __launch_bounds__(256) void upsample_bidir_kernel(const float2* __restrict__ fw, const float2* __restrict__ rev,
-                                                             float2* __restrict__ out_fw, float2* __restrict__ out_rev,
-                                                             uint8_t* __restrict__ mask_fw, uint8_t* __restrict__ mask_rev,
-                                                             int sw, int sh, int sc_l, int left, int top, int wo, int ho,
-                                                             float alpha, float beta) {
-  const int f = blockIdx.z, y = blockIdx.y;
-  const int x = blockIdx.x * 256 + threadIdx.x;
-  if (x >= wo) return;
-  const float scf = (float)(1 << sc_l), inv = 1.0f / scf;
-  const bool scale = sc_l > 0;
-  const float2* flw[2] = {fw + (size_t)f * sw * sh, rev + (size_t)f * sw * sh};
-  const UpRow ry = up_row(y + top, sh, inv);
-  float2 val[2];
-#pragma unroll
-  for (int d = 0; d < 2; ++d) {
-    float2 a0, a1;
-    upsample_h(flw[d], sw, ry.sy, ry.sy1, x + left, inv, scf, scale, a0, a1);
-    val[d] = up_mix(a0, a1, ry.fy);
-  }
-  const size_t o = ((size_t)f * ho + y) * wo + x;
-  if (out_fw) __builtin_nontemporal_store((f2n){val[0].x, val[0].y}, reinterpret_cast<f2n*>(out_fw + o));
-  if (out_rev) __builtin_nontemporal_store((f2n){val[1].x, val[1].y}, reinterpret_cast<f2n*>(out_rev + o));
-  uint8_t* masks[2] = {mask_fw, mask_rev};
-#pragma unroll
-  for (int d = 0; d < 2; ++d) {
-    if (!masks[d]) continue;
-    const float2* oth = flw[1 - d];
-    masks[d][o] = fb_code(val[d].x, val[d].y, x, y, wo, ho, alpha, beta,
-                          [&](int x0, int x1, int y0, int y1, float2& r00, float2& r01, float2& r10, float2& r11) {
-                            const UpRow q0 = up_row(y0 + top, sh, inv), q1 = up_row(y1 + top, sh, inv);
-                            float2 p0, p1, n0, n1;  // row pair of y0 at columns x0 and x1
-                            upsample_h(oth, sw, q0.sy, q0.sy1, x0 + left, inv, scf, scale, p0, p1);
-                            upsample_h(oth, sw, q0.sy, q0.sy1, x1 + left, inv, scf, scale, n0, n1);
-                            r00 = up_mix(p0, p1, q0.fy);
-                            r01 = up_mix(n0, n1, q0.fy);
-                            if (q1.sy != q0.sy) {  // (sy1 is a function of sy)
-                              upsample_h(oth, sw, q1.sy, q1.sy1, x0 + left, inv, scf, scale, p0, p1);
-                              upsample_h(oth, sw, q1.sy, q1.sy1, x1 + left, inv, scf, scale, n0, n1);
-                            }
-                            r10 = up_mix(p0, p1, q1.fy);
-                            r11 = up_mix(n0, n1, q1.fy);
-                          });
-  }
-}
-
-hipError_t launch_upsample_bidir(const float* fw, const float* rev, float* out_fw, float* out_rev, uint8_t* mask_fw,
-                                 uint8_t* mask_rev, int nframes, int sw, int sh, int sc_l, int left, int top, int wo, int ho,
-                                 float alpha, float beta, hipStream_t s) {
-  if (ho > 65535 || nframes > 65535) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(upsample_bidir_kernel, dim3((wo + 255) / 256, ho, nframes), dim3(256), 0, s, (const float2*)fw,
-                     (const float2*)rev, (float2*)out_fw, (float2*)out_rev, mask_fw, mask_rev, sw, sh, sc_l, left, top, wo, ho,
-                     alpha, beta);
-  return hipGetLastError();
-}
 
 }  // namespace ofdis

@@ -1,7 +1,7 @@
 // ofdis_stereo_lr.hip -- the stereo left-right step of include/ofdis.h: the 8-bit mirror that feeds the mirror pass's pyramid,
 // the left-right consistency test (ofdis_lr_check), the occlusion fill (ofdis_disparity_fill) and the fused finish of an
 // OFDIS_BATCH_STEREO_LR context (ofdis_batch_upsample_lr).  Compiled under the exact contract only (-ffp-contract=off), like
-// ofdis_pyr.hip and ofdis_interp.hip: masks and filled disparities are fixed functions of their inputs.
+// ofdis_upsample.hip and ofdis_interp.hip: masks and filled disparities are fixed functions of their inputs.
 //
 // In stereo everything is row-local: the consistency test of a pixel reads the other view along its own row, and the fill takes
 // the nearest consistent pixels of the row.  Every row kernel here gives a row to ONE wavefront, which walks it in chunks of 64
@@ -13,13 +13,6 @@
 #include "ofdis_lr.h"
 
 namespace ofdis {
-
-static unsigned lr_grid_for(long long total) {
-  long long b = (total + 255) / 256;
-  if (b > (1 << 20)) b = 1 << 20;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
 
 // mir(I)[y][x] = I[y][W-1-x], all channels of a pixel together, for [n][h][w][noc] 8-bit frames
 __global__ __launch_bounds__(256) void mirror_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, long long total,
@@ -33,7 +26,7 @@ __global__ __launch_bounds__(256) void mirror_u8_kernel(const uint8_t* __restric
 }
 hipError_t launch_mirror_u8(const uint8_t* src, uint8_t* dst, int nframes, int w, int h, int noc, hipStream_t s) {
   const long long total = (long long)nframes * h * w * noc;
-  hipLaunchKernelGGL(mirror_u8_kernel, dim3(lr_grid_for(total)), dim3(256), 0, s, src, dst, total, w, noc);
+  hipLaunchKernelGGL(mirror_u8_kernel, dim3(grid_for(total)), dim3(256), 0, s, src, dst, total, w, noc);
   return hipGetLastError();
 }
 
@@ -50,7 +43,7 @@ __global__ __launch_bounds__(256) void lr_check_kernel(const float* __restrict__
 hipError_t launch_lr_check(const float* disp, const float* other, uint8_t* mask, int nframes, int w, int h, float alpha,
                            float beta, hipStream_t s) {
   const long long total = (long long)nframes * w * h;
-  hipLaunchKernelGGL(lr_check_kernel, dim3(lr_grid_for(total)), dim3(256), 0, s, disp, other, mask, total, w, alpha, beta);
+  hipLaunchKernelGGL(lr_check_kernel, dim3(grid_for(total)), dim3(256), 0, s, disp, other, mask, total, w, alpha, beta);
   return hipGetLastError();
 }
 
@@ -115,7 +108,7 @@ hipError_t launch_disparity_fill(const float* disp, const uint8_t* mask, float* 
     hipLaunchKernelGGL(fill_background_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, disp, mask, out, rows, w);
   } else {
     if (mode == OFDIS_FILL_NONE && out == disp) return hipSuccess;
-    hipLaunchKernelGGL(fill_pixelwise_kernel, dim3(lr_grid_for(total)), dim3(256), 0, s, disp, mask, out, total,
+    hipLaunchKernelGGL(fill_pixelwise_kernel, dim3(grid_for(total)), dim3(256), 0, s, disp, mask, out, total,
                        mode == OFDIS_FILL_INVALIDATE ? 1 : 0);
   }
   return hipGetLastError();
@@ -123,7 +116,7 @@ hipError_t launch_disparity_fill(const float* disp, const uint8_t* mask, float* 
 
 // ------------------------------------------------------------------------------------ ofdis_batch_upsample_lr
 // The fused finish.  A workgroup of `rows` wavefronts (1 .. 4) takes `rows` output rows of one frame, a wavefront per row.  Per
-// row in LDS: U (the forward disparity at full resolution, what upsample_crop1_kernel writes), DR (the mirror pass's, negated
+// row in LDS: U (the forward disparity at full resolution, what ofdis_batch_upsample_frames writes), DR (the mirror pass's, negated
 // and un-mirrored), the 64-bit ballots of "consistent" per chunk and view, and the left carries per chunk and view:
 //     8 wo + 1536 bytes per row  (LR_ROW_EXTRA floats beside the two rows), dynamic; at most 64 KB per workgroup.
 //   1  both rows from the level disparities (four cached loads per value)
@@ -138,9 +131,9 @@ typedef unsigned long long u64;
 
 __global__ __launch_bounds__(256) void upsample_lr_kernel(const float* __restrict__ fw, const float* __restrict__ mir,
                                                           float* __restrict__ out_l, float* __restrict__ out_r,
-                                                          uint8_t* __restrict__ mask_l, uint8_t* __restrict__ mask_r, int sw,
-                                                          int sh, int sc_l, int left, int top, int wo, int ho, int fill_mode,
-                                                          float alpha, float beta) {
+                                                          uint8_t* __restrict__ mask_l, uint8_t* __restrict__ mask_r, UpGeom g,
+                                                          int fill_mode, float alpha, float beta) {
+  const int wo = g.wo, ho = g.ho;
   extern __shared__ __attribute__((aligned(16))) float lr_lds[];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int f = blockIdx.y;
@@ -152,13 +145,12 @@ __global__ __launch_bounds__(256) void upsample_lr_kernel(const float* __restric
   row[1] = row[0] + wo;
   u64* mb = reinterpret_cast<u64*>(row[1] + wo);  // [2][LR_MAX_CHUNKS]   (wo floats twice: 8-byte aligned)
   int* cl = reinterpret_cast<int*>(mb + 2 * LR_MAX_CHUNKS);  // [2][LR_MAX_CHUNKS]
-  const float scf = (float)(1 << sc_l), inv = 1.0f / scf;
-  const bool scale = sc_l > 0;
-  const float* flw = fw + (size_t)f * sw * sh;
-  const float* flm = mir + (size_t)f * sw * sh;
+  const float* flw = fw + (size_t)f * g.plane();
+  const float* flm = mir + (size_t)f * g.plane();
+  const UpRow ry = up_row(y + g.top, g);
   for (int x = lane; x < wo; x += 64) {
-    row[0][x] = upsample1(flw, sw, sh, scf, inv, scale, x + left, y + top);
-    row[1][x] = -upsample1(flm, sw, sh, scf, inv, scale, (wo - 1 - x) + left, y + top);
+    row[0][x] = upsample_at(flw, g, x + g.left, ry);
+    row[1][x] = -upsample_at(flm, g, (wo - 1 - x) + g.left, ry);
   }
   __syncthreads();
   float* outs[2] = {out_l, out_r};
@@ -213,33 +205,28 @@ __global__ __launch_bounds__(256) void upsample_lr_kernel(const float* __restric
 bool upsample_lr_fuses(int wo) { return wo <= LR_FUSED_MAX_WIDTH; }
 size_t upsample_lr_row_bytes(int wo) { return ((size_t)2 * wo + LR_ROW_EXTRA) * sizeof(float); }
 hipError_t launch_upsample_lr(const float* fw, const float* mir, float* out_l, float* out_r, uint8_t* mask_l, uint8_t* mask_r,
-                              int nframes, int sw, int sh, int sc_l, int left, int top, int wo, int ho, int fill_mode,
-                              float alpha, float beta, hipStream_t s) {
-  if (!upsample_lr_fuses(wo) || nframes > 65535) return hipErrorInvalidValue;
-  const size_t per_row = upsample_lr_row_bytes(wo);
+                              int nframes, UpGeom g, int fill_mode, float alpha, float beta, hipStream_t s) {
+  if (!upsample_lr_fuses(g.wo) || nframes > 65535) return hipErrorInvalidValue;
+  const size_t per_row = upsample_lr_row_bytes(g.wo);
   const int rows = (int)std::min<size_t>(4, (64 * 1024) / per_row);  // >= 1 up to LR_FUSED_MAX_WIDTH
-  hipLaunchKernelGGL(upsample_lr_kernel, dim3((ho + rows - 1) / rows, nframes), dim3(64 * rows), rows * per_row, s, fw, mir, out_l,
-                     out_r, mask_l, mask_r, sw, sh, sc_l, left, top, wo, ho, fill_mode, alpha, beta);
+  hipLaunchKernelGGL(upsample_lr_kernel, dim3((g.ho + rows - 1) / rows, nframes), dim3(64 * rows), rows * per_row, s, fw, mir,
+                     out_l, out_r, mask_l, mask_r, g, fill_mode, alpha, beta);
   return hipGetLastError();
 }
 
 // The composition's first step for widths above LR_FUSED_MAX_WIDTH: U and DR materialised, one pixel per thread
 __global__ __launch_bounds__(256) void lr_materialise_kernel(const float* __restrict__ fw, const float* __restrict__ mir,
-                                                             float* __restrict__ u, float* __restrict__ dr, int sw, int sh,
-                                                             int sc_l, int left, int top, int wo, int ho) {
+                                                             float* __restrict__ u, float* __restrict__ dr, UpGeom g) {
   const int f = blockIdx.z, y = blockIdx.y;
   const int x = blockIdx.x * 256 + threadIdx.x;
-  if (x >= wo) return;
-  const float scf = (float)(1 << sc_l), inv = 1.0f / scf;
-  const size_t o = ((size_t)f * ho + y) * wo + x;
-  u[o] = upsample1(fw + (size_t)f * sw * sh, sw, sh, scf, inv, sc_l > 0, x + left, y + top);
-  dr[o] = -upsample1(mir + (size_t)f * sw * sh, sw, sh, scf, inv, sc_l > 0, (wo - 1 - x) + left, y + top);
+  if (x >= g.wo) return;
+  const size_t o = ((size_t)f * g.ho + y) * g.wo + x;
+  u[o] = upsample_at(fw + (size_t)f * g.plane(), g, x + g.left, y + g.top);
+  dr[o] = -upsample_at(mir + (size_t)f * g.plane(), g, (g.wo - 1 - x) + g.left, y + g.top);
 }
-hipError_t launch_lr_materialise(const float* fw, const float* mir, float* u, float* dr, int nframes, int sw, int sh, int sc_l,
-                                 int left, int top, int wo, int ho, hipStream_t s) {
-  if (ho > 65535 || nframes > 65535) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(lr_materialise_kernel, dim3((wo + 255) / 256, ho, nframes), dim3(256), 0, s, fw, mir, u, dr, sw, sh, sc_l,
-                     left, top, wo, ho);
+hipError_t launch_lr_materialise(const float* fw, const float* mir, float* u, float* dr, int nframes, UpGeom g, hipStream_t s) {
+  if (g.ho > 65535 || nframes > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(lr_materialise_kernel, dim3((g.wo + 255) / 256, g.ho, nframes), dim3(256), 0, s, fw, mir, u, dr, g);
   return hipGetLastError();
 }
 

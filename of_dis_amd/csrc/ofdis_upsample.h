@@ -1,46 +1,99 @@
-// ofdis_upsample.h -- device helpers shared by the exact-only units ofdis_pyr.hip and ofdis_interp.hip: the arithmetic of
-// the level flow to full resolution (upsample_crop_kernel, run_dense.cpp:406-414), the forward-backward consistency test and
-// the compact output encodings (include/ofdis.h: ofdis_encoding).
-// Both units are compiled with -ffp-contract=off only, so every kernel that uses these computes the same bits.
+// ofdis_upsample.h -- device helpers of the full-resolution finish, shared by the exact-only units ofdis_upsample.hip,
+// ofdis_interp.hip and ofdis_stereo_lr.hip: the arithmetic of the level flow to full resolution (run_dense.cpp:406-414, UpGeom
+// in ofdis_kernels.h), the forward-backward consistency test and the compact output encodings (include/ofdis.h:
+// ofdis_encoding).  These units are compiled with -ffp-contract=off only and every finish kernel takes its values from the
+// helpers below -- upsample_h, up_row / up_group, up_mix -- so every one of them computes the same bits.
 #pragma once
 #include "ofdis_kernels.h"
 
 namespace ofdis {
 
-// cv::resize INTER_LINEAR, horizontal step: the two source rows sy, sy1 of the level flow `fl` (sw columns) interpolated at
-// padded full-resolution column X, times 2^sc_l when `scale`.
-__device__ __forceinline__ void upsample_h(const float2* __restrict__ fl, int sw, int sy, int sy1, int X, float inv,
-                                           float scf, bool scale, float2& r0, float2& r1) {
-  float fx = ((float)X + 0.5f) * inv - 0.5f;
-  int sx = (int)floorf(fx);
-  fx -= (float)sx;
-  if (sx < 0) { sx = 0; fx = 0.0f; }
-  if (sx >= sw - 1) { sx = sw - 1; fx = 0.0f; }
-  const int sx1 = min(sx + 1, sw - 1);
-  float2 v00 = fl[sy * sw + sx], v01 = fl[sy * sw + sx1], v10 = fl[sy1 * sw + sx], v11 = fl[sy1 * sw + sx1];
-  if (scale) {
-    v00.x *= scf; v00.y *= scf; v01.x *= scf; v01.y *= scf;
-    v10.x *= scf; v10.y *= scf; v11.x *= scf; v11.y *= scf;
-  }
-  const float ax = 1.0f - fx;
-  r0 = make_float2(v00.x * ax + v01.x * fx, v00.y * ax + v01.y * fx);
-  r1 = make_float2(v10.x * ax + v11.x * fx, v10.y * ax + v11.y * fx);
+// ------------------------------------------------------------------------------------ level flow to full resolution
+// flowout *= 2^lv_l; cv::resize(flowout, x 2^lv_l, INTER_LINEAR); crop the padding.  cv::resize bilinear for CV_32FC1 / C2:
+// half-pixel centres, source index clamped with the fraction forced to 0 at the borders, horizontal interpolation first.
+// 2^lv_l is a power of two, so (X + 0.5) / s - 0.5 is exact in fp32.  T is float2 (flow) or float (stereo disparity).
+__device__ __forceinline__ float up_scaled(float v, float s) { return v * s; }
+__device__ __forceinline__ float2 up_scaled(float2 v, float s) { return make_float2(v.x * s, v.y * s); }
+// a * (1 - f) + b * f, each product and the sum separately rounded
+__device__ __forceinline__ float up_mix(float a, float b, float f) { return a * (1.0f - f) + b * f; }
+__device__ __forceinline__ float2 up_mix(float2 a, float2 b, float f) {
+  const float e = 1.0f - f;
+  return make_float2(a.x * e + b.x * f, a.y * e + b.y * f);
 }
 
-// The same step for the one-channel result of the stereo-depth mode: the expressions of upsample_crop1_kernel.
-__device__ __forceinline__ void upsample_h1(const float* __restrict__ fl, int sw, int sy, int sy1, int X, float inv, float scf,
-                                            bool scale, float& r0, float& r1) {
-  float fx = ((float)X + 0.5f) * inv - 0.5f;
+// Horizontal step: the two source rows sy, sy1 of the level flow `fl` interpolated at padded full-resolution column X, times
+// 2^sc_l.
+template <class T>
+__device__ __forceinline__ void upsample_h(const T* __restrict__ fl, const UpGeom& g, int sy, int sy1, int X, T& r0, T& r1) {
+  const int sw = g.sw;
+  float fx = ((float)X + 0.5f) * g.inv() - 0.5f;
   int sx = (int)floorf(fx);
   fx -= (float)sx;
   if (sx < 0) { sx = 0; fx = 0.0f; }
   if (sx >= sw - 1) { sx = sw - 1; fx = 0.0f; }
   const int sx1 = min(sx + 1, sw - 1);
-  float v00 = fl[sy * sw + sx], v01 = fl[sy * sw + sx1], v10 = fl[sy1 * sw + sx], v11 = fl[sy1 * sw + sx1];
-  if (scale) { v00 *= scf; v01 *= scf; v10 *= scf; v11 *= scf; }
-  const float ax = 1.0f - fx;
-  r0 = v00 * ax + v01 * fx;
-  r1 = v10 * ax + v11 * fx;
+  T v00 = fl[sy * sw + sx], v01 = fl[sy * sw + sx1], v10 = fl[sy1 * sw + sx], v11 = fl[sy1 * sw + sx1];
+  if (g.scale()) {
+    const float scf = g.scf();
+    v00 = up_scaled(v00, scf); v01 = up_scaled(v01, scf); v10 = up_scaled(v10, scf); v11 = up_scaled(v11, scf);
+  }
+  r0 = up_mix(v00, v01, fx);
+  r1 = up_mix(v10, v11, fx);
+}
+
+// Vertical step for one padded full-resolution row Y: its two source rows and weight.
+struct UpRow {
+  int sy, sy1;
+  float fy;
+};
+__device__ __forceinline__ UpRow up_row(int Y, const UpGeom& g) {
+  UpRow r;
+  const float fy = ((float)Y + 0.5f) * g.inv() - 0.5f;
+  r.sy = (int)floorf(fy);
+  const bool clamp = r.sy < 0 || r.sy >= g.sh - 1;
+  r.fy = clamp ? 0.0f : fy - floorf(fy);
+  r.sy = r.sy < 0 ? 0 : (r.sy >= g.sh - 1 ? g.sh - 1 : r.sy);
+  r.sy1 = min(r.sy + 1, g.sh - 1);
+  return r;
+}
+// One pixel of the full-resolution result: the level flow at padded column X of a row / at padded pixel (X, Y).
+template <class T>
+__device__ __forceinline__ T upsample_at(const T* __restrict__ fl, const UpGeom& g, int X, const UpRow& r) {
+  T a0, a1;
+  upsample_h(fl, g, r.sy, r.sy1, X, a0, a1);
+  return up_mix(a0, a1, r.fy);
+}
+template <class T>
+__device__ __forceinline__ T upsample_at(const T* __restrict__ fl, const UpGeom& g, int X, int Y) {
+  return upsample_at(fl, g, X, up_row(Y, g));
+}
+
+// The same vertical step for a row group: the s = 2^sc_l padded rows with floor((Y + 0.5) / s - 0.5) = k are
+// [k*s + s/2, k*s + s/2 + s) and share their source rows, so a kernel interpolates horizontally once per group.  Groups are
+// numbered grp = 0 .. sh: k = -1 .. sh-1 (k = 0 .. sh for s = 1, the last one empty); k = -1 and k = sh-1 are the half groups
+// at the borders, where the source row is clamped and the weight forced to 0.  [Y0, Y1) are the group's rows inside the crop
+// (empty: nothing to do); floor((Y + 0.5) / s - 0.5) is exact, so fy(Y) is up_row's value.
+struct UpGroup {
+  int Y0, Y1, sy, sy1;
+  bool clamp;
+  float inv;
+  __device__ __forceinline__ float fy(int Y) const {
+    const float f = ((float)Y + 0.5f) * inv - 0.5f;
+    return clamp ? 0.0f : f - floorf(f);
+  }
+};
+__device__ __forceinline__ UpGroup up_group(int grp, const UpGeom& g) {
+  UpGroup r;
+  const int s = 1 << g.sc_l;
+  const int k = grp - (s > 1 ? 1 : 0);
+  r.Y0 = max(k * s + s / 2, g.top);
+  r.Y1 = min(k * s + s / 2 + s, g.top + g.ho);
+  r.inv = g.inv();
+  const int sy = (int)floorf(((float)r.Y0 + 0.5f) * r.inv - 0.5f);
+  r.clamp = sy < 0 || sy >= g.sh - 1;
+  r.sy = sy < 0 ? 0 : (sy >= g.sh - 1 ? g.sh - 1 : sy);
+  r.sy1 = min(r.sy + 1, g.sh - 1);
+  return r;
 }
 
 // ------------------------------------------------------------------------------------ forward-backward consistency
@@ -69,26 +122,28 @@ __device__ __forceinline__ uint8_t fb_code(float u, float v, int x, int y, int W
   return lhs <= rhs ? FB_CONSISTENT : FB_INCONSISTENT;
 }
 
-// Vertical source rows and weight of padded full-resolution row Y: the vertical step of upsample_crop_kernel for one row.
-// (There the rows of a group share sy; floor((Y + 0.5) / s - 0.5) is exact, so per row it is the same value.)
-struct UpRow {
-  int sy, sy1;
-  float fy;
+// `R` for a direction whose full-resolution flow is not materialised: the four neighbours recomputed from its level flow
+// `fl`, the bits ofdis_batch_upsample_frames writes.  Neighbour rows y0 and y1 usually share their source rows (for s > 1): then
+// the two horizontal interpolations are reused.
+struct UpNeighbours {
+  const float2* fl;
+  const UpGeom& g;
+  __device__ __forceinline__ void operator()(int x0, int x1, int y0, int y1, float2& r00, float2& r01, float2& r10,
+                                             float2& r11) const {
+    const UpRow q0 = up_row(y0 + g.top, g), q1 = up_row(y1 + g.top, g);
+    float2 p0, p1, n0, n1;  // row pair of y0 at columns x0 and x1
+    upsample_h(fl, g, q0.sy, q0.sy1, x0 + g.left, p0, p1);
+    upsample_h(fl, g, q0.sy, q0.sy1, x1 + g.left, n0, n1);
+    r00 = up_mix(p0, p1, q0.fy);
+    r01 = up_mix(n0, n1, q0.fy);
+    if (q1.sy != q0.sy) {  // (sy1 is a function of sy)
+      upsample_h(fl, g, q1.sy, q1.sy1, x0 + g.left, p0, p1);
+      upsample_h(fl, g, q1.sy, q1.sy1, x1 + g.left, n0, n1);
+    }
+    r10 = up_mix(p0, p1, q1.fy);
+    r11 = up_mix(n0, n1, q1.fy);
+  }
 };
-__device__ __forceinline__ UpRow up_row(int Y, int sh, float inv) {
-  UpRow r;
-  const float fy = ((float)Y + 0.5f) * inv - 0.5f;
-  r.sy = (int)floorf(fy);
-  const bool clamp = r.sy < 0 || r.sy >= sh - 1;
-  r.fy = clamp ? 0.0f : fy - floorf(fy);
-  r.sy = r.sy < 0 ? 0 : (r.sy >= sh - 1 ? sh - 1 : r.sy);
-  r.sy1 = min(r.sy + 1, sh - 1);
-  return r;
-}
-__device__ __forceinline__ float2 up_mix(float2 a0, float2 a1, float fy) {
-  const float ay = 1.0f - fy;
-  return make_float2(a0.x * ay + a1.x * fy, a0.y * ay + a1.y * fy);
-}
 
 // ------------------------------------------------------------------------------------ compact output encodings
 // The arithmetic of include/ofdis.h (ofdis_encoding), written once for ofdis_encode and the encoding upsample kernels.  TYPE is

@@ -156,9 +156,7 @@ def _check_context(gpu, b, w, h, first, count, what, names=None, offsets=(0,)):
         _same_bits(want, encoding.encode(ref, enc), f"{what}: ofdis_encode {name} vs the numpy model")
         _same_bits(b.upsample_frames_enc(first, count, w, h, enc), want, f"{what}: fused {name} vs the composition")
         for off in offsets:
-            # (`out` is aligned to its element; two-channel fp32 is the existing kernel, which takes 16-byte aligned
-            # arrays like ofdis_batch_upsample_frames: offset 0 only)
-            if off and (off % enc.dtype.itemsize or (enc.type == gpu.ENC_F32 and b.p.nop == 2)):
+            if off % enc.dtype.itemsize:  # (`out` is aligned to its element)
                 continue
             got, guards = _fused_with_guards(gpu, b, first, count, w, h, enc, off)
             _same_bits(got, want, f"{what}: fused {name} (guarded, offset {off}) vs the composition")

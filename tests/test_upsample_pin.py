@@ -15,11 +15,13 @@ ofdis_batch_upsample) is pinned two ways that do not go through it:
     align_corners=False), documented as OpenCV-compatible, on random data, to within a few ulp (its rounding order
     differs).
 """
+import ctypes as C
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
+from of_dis_amd import encoding
 from of_dis_amd.params import oppoint, padded_size
 
 _f32 = np.float32
@@ -94,6 +96,18 @@ def test_oracle_upsample_matches_hand_vectors(orc, w, h, lv):
         assert np.array_equal(got[0, : s // 2], np.repeat(flow[:1, 0] * s, s // 2, 0))
 
 
+@pytest.mark.parametrize("w,h,lv", PIN_CASES)
+def test_oracle_upsample_is_channelwise(orc, w, h, lv):
+    """The resize treats channels independently: channel 0 twice gives the hand vector's channel 0 twice -- the expectation
+    of the one-channel (stereo-depth) device test below."""
+    p, flow, left, top = _case(w, h, lv, 31 + w)
+    expect = _exact_f32(_hand_upsample(flow, 1 << p.sc_l, left, top, w, h))
+    assert p.selectmode == 0
+    got = orc.upsample_crop(p, np.ascontiguousarray(np.stack([flow[..., 0], flow[..., 0]], axis=-1)), w, h)
+    for c in range(2):
+        assert np.array_equal(got[..., c].view(np.uint32), expect[..., 0].view(np.uint32))
+
+
 def test_oracle_upsample_matches_torch_convention(orc):
     """Random (non-integer) data against torch's align_corners=False bilinear, the OpenCV-compatible convention."""
     import torch
@@ -126,3 +140,32 @@ def test_device_upsample_matches_hand_vectors(gpu, w, h, lv):
     b.close()
     assert np.array_equal(full[0].view(np.uint32), expect.view(np.uint32))
     assert np.array_equal(full[1], -expect)  # by value: the negated plant holds -0.0, whose sign a sum may drop
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("w,h,lv", PIN_CASES)
+def test_device_upsample_one_channel_matches_hand_vectors(gpu, w, h, lv):
+    """The one-channel result of a stereo-depth context (selectmode 2): ofdis_batch_upsample, and the fp32 encoding of
+    ofdis_batch_upsample_frames_enc written 4 bytes off the 16-byte grid (its narrow stores), against channel 0 of the same
+    exact hand vectors."""
+    p, flow, left, top = _case(w, h, lv, 31 + w)
+    expect = np.ascontiguousarray(_exact_f32(_hand_upsample(flow, 1 << p.sc_l, left, top, w, h))[..., :1])
+    b = gpu.Batch(p.copy(selectmode=2), 2)
+    assert b.p.nop == 1
+    L = gpu.lib()
+    one = flow[..., :1]
+    both = np.ascontiguousarray(np.stack([one, -one]))
+    gpu.check(L.ofdis_memcpy_h2d(b.flow_ptr(), both.ctypes.data, both.nbytes))
+    full = b.upsample(w, h)
+    G, off, nbytes = 4096, 4, 2 * h * w * 4
+    d = gpu.Dev(np.full(nbytes + 2 * G, 0xC3, np.uint8))
+    gpu.check(L.ofdis_batch_upsample_frames_enc(b.h, 0, 2, d.ptr + G + off, w, h, C.byref(encoding.F32), None))
+    gpu.check(L.ofdis_sync(None))
+    raw = d.get((nbytes + 2 * G,), np.uint8)
+    b.close()
+    assert full.shape == (2, h, w, 1)
+    assert np.array_equal(full[0].view(np.uint32), expect.view(np.uint32))
+    assert np.array_equal(full[1], -expect)  # by value: the negated plant holds -0.0, whose sign a sum may drop
+    enc = raw[G + off:G + off + nbytes].copy().view(_f32).reshape(2, h, w, 1)
+    assert np.array_equal(enc.view(np.uint32), full.view(np.uint32))
+    assert (raw[:G + off] == 0xC3).all() and (raw[G + off + nbytes:] == 0xC3).all(), "wrote outside `out`"
