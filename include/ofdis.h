@@ -343,6 +343,50 @@ int ofdis_batch_build_pyramids_u8_seq(ofdis_batch* b, const uint8_t* frames, siz
  * exists; the up to 255 bytes of alignment after each array do not).  0 for NULL. */
 size_t ofdis_batch_device_bytes(const ofdis_batch* b);
 
+/* ---------------------------------------------------------------------------------------------
+ * Point trajectories through a clip: the flows of consecutive pairs chained from a seed, each track ended where it leaves the
+ * image or fails the forward-backward test (Sundaram, Brox and Keutzer, 2010: the use that test was made for).
+ *
+ * W x H is the frame size; npairs consecutive pairs cover frames 0 .. npairs.  Ffw[k] and Frev[k] are the full-resolution
+ * flows of pair k, frame k -> k+1 and frame k+1 -> k, each [H][W][2] fp32.  Point i has the seed (sx, sy) = seeds[i] and the
+ * seed frame s = seed_frame[i] (0 when seed_frame is NULL).  Every operation is a separately rounded fp32 operation in this
+ * order, independent of the arithmetic contract:
+ *   inside(p) = 0 <= px <= W-1 and 0 <= py <= H-1                                                        (NaN: false)
+ *   bil(F, p):  x0 = min((int)floorf(px), W-2), ax = px - x0   (x0 = 0, ax = 0 when W == 1); y0, ay likewise;
+ *       x1 = min(x0+1, W-1), y1 = min(y0+1, H-1);  bx = 1-ax, by = 1-ay
+ *       (F[y0][x0]*bx + F[y0][x1]*ax) * by + (F[y1][x0]*bx + F[y1][x1]*ax) * ay                        per component
+ *       (the expression of ofdis_fb_check, of_dis_amd/csrc/ofdis_upsample.h: fb_bilinear, at a real position)
+ *   s < 0, s > npairs or not inside(seed): count = 0.  Otherwise p_s = seed, copied bit for bit, count = 1, and for
+ *   k = s, s+1, ... while k < npairs and (max_steps == 0 or k - s < max_steps):
+ *     1. (u, v) = bil(Ffw[k], p_k);  q = (px + u, py + v);  not inside(q): the track ends
+ *     2. with Frev:  (ru, rv) = bil(Frev[k], q);  du = u + ru, dv = v + rv;  lhs = du*du + dv*dv;
+ *        rhs = alpha * ((u*u + v*v) + (ru*ru + rv*rv)) + beta;  the track ends unless lhs <= rhs        (NaN ends it)
+ *     3. p_{k+1} = q, count += 1
+ * tracks = [npairs+1][npoints][2] fp32, frame-major (the lanes of a wavefront store adjacent 8-byte values):
+ * tracks[f][i] = p_f for s <= f < s + count; every other entry holds the NaN with the bits 0x7FC00000 in both components.  The
+ * call writes every entry exactly once and relies on no memset.  counts = [npoints] int32, may be NULL.
+ * of_dis_amd/tracking.py states the same arithmetic in numpy.
+ * ------------------------------------------------------------------------------------------- */
+#define OFDIS_TRACK_MAX_POINTS (1 << 24)
+/* device arrays: flow_fw, flow_rev [npairs][height][width][2] (flow_rev NULL: no consistency test); seeds [npoints][2];
+ * seed_frame [npoints] int32 or NULL; tracks, counts as above.  One lane per point; enqueues on `stream`.
+ * OFDIS_ERR_INVALID before any device work: a NULL flow_fw, seeds or tracks; npoints outside 1..OFDIS_TRACK_MAX_POINTS;
+ * max_steps < 0; npairs < 1; sizes, alpha and beta as ofdis_fb_check rejects them. */
+int ofdis_track_points(const float* flow_fw, const float* flow_rev /* NULL: no consistency test */, int npairs,
+                       int width, int height, const float* seeds /* [npoints][2] */, const int* seed_frame /* or NULL */,
+                       int npoints, int max_steps, float alpha, float beta, float* tracks, int* counts, void* stream);
+/* OFDIS_BATCH_SEQUENCE contexts: the pairs [first_frame, first_frame+count) of the context, straight from its level flows
+ * (the full-resolution flows are never written); seed_frame is relative to first_frame, tracks = [count+1][npoints][2].
+ * fb_check = 1: bit-identical to ofdis_track_points applied to out_fw and out_rev of ofdis_batch_upsample_bidir(b,
+ * first_frame, count, ...); fb_check = 0: to ofdis_track_points applied to what ofdis_batch_upsample_frames writes, with
+ * flow_rev = NULL -- under both contracts (the kernel is contract-independent, the level flows are not).  Joins a pipelined
+ * pass by itself.  OFDIS_ERR_INVALID as ofdis_track_points, and for a NULL context, a context created without
+ * OFDIS_BATCH_SEQUENCE (the pairs of any other context are no chain), fb_check not 0 or 1, fb_check = 1 on a context created
+ * without OFDIS_BATCH_REVERSE, a pair range outside the batch, an original size above the padded size. */
+int ofdis_batch_track_points(ofdis_batch* b, int first_frame, int count, const float* seeds, const int* seed_frame,
+                             int npoints, int max_steps, int fb_check, float alpha, float beta, float* tracks,
+                             int* counts, int width_org, int height_org, void* stream);
+
 /* Warm start (the reference's `initflow`, oflow.cpp:217-220; e.g. the previous frame pair's flow of a video):
  * per frame (w >> (sc_f+1)) x (h >> (sc_f+1)) x 2 floats, AoS.  set_initflow borrows a device array
  * [nframes][ofdis_batch_initflow_elems] (NULL switches the warm start off again); upload_initflow copies one

@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "ofdis_batch_flow_mirror", "ofdis_batch_level_flow_mirror", "ofdis_lr_check", "ofdis_disparity_fill", "ofdis_batch_upsample_lr",
     "ofdis_encoding_bytes", "ofdis_encode", "ofdis_batch_upsample_frames_enc",
     "ofdis_batch_input_frames", "ofdis_batch_upload_frame", "ofdis_batch_build_pyramids_u8_seq", "ofdis_batch_device_bytes",
+    "ofdis_track_points", "ofdis_batch_track_points",
 ]
 BATCH_REVERSE = 1  # include/ofdis.h: OFDIS_BATCH_REVERSE
 BATCH_STEREO_LR = 2  # OFDIS_BATCH_STEREO_LR
@@ -51,6 +52,7 @@ FB_ALPHA, FB_BETA = 0.01, 0.5  # OFDIS_FB_ALPHA / OFDIS_FB_BETA
 FB_CONSISTENT, FB_INCONSISTENT, FB_OUTSIDE = 0, 1, 2
 INTERP_MAX_TIMES = 16  # OFDIS_INTERP_MAX_TIMES
 ENC_F32, ENC_F16, ENC_U16, ENC_U8 = 0, 1, 2, 3  # OFDIS_ENC_*
+TRACK_MAX_POINTS = 1 << 24  # OFDIS_TRACK_MAX_POINTS
 OFDIS_VERSION = 3  # include/ofdis.h: the struct layouts below (OfdisTuning: 20 ints) belong to this ABI version
 
 
@@ -191,6 +193,10 @@ def lib():
         L.ofdis_batch_build_pyramids_u8_seq.argtypes = [VP, VP, C.c_size_t, C.c_size_t, C.c_int, C.c_int, VP]
         L.ofdis_batch_device_bytes.restype = C.c_size_t
         L.ofdis_batch_device_bytes.argtypes = [VP]
+        L.ofdis_track_points.argtypes = [VP, VP, C.c_int, C.c_int, C.c_int, VP, VP, C.c_int, C.c_int, C.c_float, C.c_float, VP,
+                                         VP, VP]
+        L.ofdis_batch_track_points.argtypes = [VP, C.c_int, C.c_int, VP, VP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                               VP, VP, C.c_int, C.c_int, VP]
         _lib = L
     return _lib
 
@@ -525,6 +531,37 @@ def interpolate(img_a, img_b, flow_fw, flow_rev, times, mask_fw=None, mask_rev=N
     return do.get(shape, np.uint8)
 
 
+def _track_inputs(seeds, seed_frame):
+    seeds = _f(seeds)
+    assert seeds.ndim == 2 and seeds.shape[1] == 2, seeds.shape
+    if seed_frame is not None:
+        seed_frame = np.ascontiguousarray(seed_frame, np.int32)
+        assert seed_frame.shape == (seeds.shape[0],), (seed_frame.shape, seeds.shape)
+    return seeds, seed_frame
+
+
+def track_points(flow_fw, flow_rev, seeds, seed_frame=None, max_steps=0, alpha=FB_ALPHA, beta=FB_BETA):
+    """ofdis_track_points on the device: flow_fw [npairs, h, w, 2] float32 (frame k -> k + 1), flow_rev the same shape
+    (frame k + 1 -> k) or None (no consistency test), seeds [npoints, 2] float32 (x, y), seed_frame [npoints] int32 or None
+    (all 0) -> (tracks [npairs + 1, npoints, 2] float32, counts [npoints] int32).  of_dis_amd/tracking.py: track_ref is the
+    numpy statement of the same arithmetic."""
+    flow_fw = _f(flow_fw)
+    assert flow_fw.ndim == 4 and flow_fw.shape[-1] == 2, flow_fw.shape
+    npairs, h, w = flow_fw.shape[:3]
+    if flow_rev is not None:
+        flow_rev = _f(flow_rev)
+        assert flow_rev.shape == flow_fw.shape, (flow_rev.shape, flow_fw.shape)
+    seeds, seed_frame = _track_inputs(seeds, seed_frame)
+    n = seeds.shape[0]
+    dfw, drev = Dev(flow_fw), Dev(flow_rev) if flow_rev is not None else None
+    dseeds, dsf = Dev(seeds), Dev(seed_frame) if seed_frame is not None else None
+    dtracks, dcounts = Dev(nbytes=max(8, (npairs + 1) * n * 8)), Dev(nbytes=max(4, n * 4))
+    check(lib().ofdis_track_points(dfw.ptr, drev.ptr if drev else None, npairs, w, h, dseeds.ptr, dsf.ptr if dsf else None, n,
+                                   max_steps, alpha, beta, dtracks.ptr, dcounts.ptr, None))
+    check(lib().ofdis_sync(None))
+    return dtracks.get((npairs + 1, n, 2), _f32), dcounts.get((n,), np.int32)
+
+
 class Batch:
     """ofdis_batch: `nframes` frame pairs of one geometry resident in HBM.  reverse=True: ofdis_batch_create_ex with
     OFDIS_BATCH_REVERSE (every pass also computes the flow B -> A of each pair).  stereo_lr=True: OFDIS_BATCH_STEREO_LR
@@ -770,6 +807,21 @@ class Batch:
             return None
         check(lib().ofdis_sync(stream))
         return d.get(shape, np.uint8)
+
+    def track_points(self, seeds, width_org, height_org, seed_frame=None, max_steps=0, fb_check=True, first=0, count=None,
+                     alpha=FB_ALPHA, beta=FB_BETA, stream=None):
+        """ofdis_batch_track_points over the pairs [first, first + count) of a sequence=True context, straight from its level
+        flows: seeds [npoints, 2] float32, seed_frame [npoints] int32 relative to `first` or None -> (tracks [count + 1,
+        npoints, 2] float32, counts [npoints] int32).  fb_check=True needs reverse=True."""
+        count = self.nframes - first if count is None else count
+        seeds, seed_frame = _track_inputs(seeds, seed_frame)
+        n = seeds.shape[0]
+        dseeds, dsf = Dev(seeds), Dev(seed_frame) if seed_frame is not None else None
+        dtracks, dcounts = Dev(nbytes=max(8, (max(count, 0) + 1) * n * 8)), Dev(nbytes=max(4, n * 4))
+        check(lib().ofdis_batch_track_points(self.h, first, count, dseeds.ptr, dsf.ptr if dsf else None, n, max_steps,
+                                             int(fb_check), alpha, beta, dtracks.ptr, dcounts.ptr, width_org, height_org, stream))
+        check(lib().ofdis_sync(stream))
+        return dtracks.get((count + 1, n, 2), _f32), dcounts.get((n,), np.int32)
 
     def timing(self, enable=True):
         check(lib().ofdis_batch_timing(self.h, int(enable)))

@@ -801,4 +801,40 @@ int ofdis_batch_interpolate(ofdis_batch* b, const uint8_t* img_a, const uint8_t*
   return OFDIS_OK;
 }
 
+// ------------------------------------------------------------------------------------ point trajectories (ofdis_track.hip)
+static int track_args_check(const float* seeds, int npoints, int max_steps, float alpha, float beta, const float* tracks) {
+  if (!seeds || !tracks) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (npoints < 1 || npoints > OFDIS_TRACK_MAX_POINTS) return fail(OFDIS_ERR_INVALID, "npoints outside 1..OFDIS_TRACK_MAX_POINTS");
+  if (max_steps < 0) return fail(OFDIS_ERR_INVALID, "max_steps is negative");
+  if (!fb_constants_ok(alpha, beta)) return fail(OFDIS_ERR_INVALID, "alpha and beta must be finite and >= 0");
+  return OFDIS_OK;
+}
+
+int ofdis_track_points(const float* flow_fw, const float* flow_rev, int npairs, int width, int height, const float* seeds,
+                       const int* seed_frame, int npoints, int max_steps, float alpha, float beta, float* tracks, int* counts,
+                       void* stream) {
+  if (!flow_fw) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (int rc = track_args_check(seeds, npoints, max_steps, alpha, beta, tracks)) return rc;
+  if (npairs < 1 || width < 1 || height < 1 || (long long)width * height > (1ll << 30))
+    return fail(OFDIS_ERR_INVALID, "bad sizes");
+  HIPCHK(launch_track_points(flow_fw, flow_rev, npairs, width, height, seeds, seed_frame, npoints, max_steps, alpha, beta, tracks,
+                             counts, (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+int ofdis_batch_track_points(ofdis_batch* b, int first_frame, int count, const float* seeds, const int* seed_frame, int npoints,
+                             int max_steps, int fb_check, float alpha, float beta, float* tracks, int* counts, int width_org,
+                             int height_org, void* stream) {
+  if (!b || !b->sequence)  // (the pairs of any other context are no chain)
+    return fail(OFDIS_ERR_INVALID, "not a context created with OFDIS_BATCH_SEQUENCE");
+  if (fb_check != 0 && fb_check != 1) return fail(OFDIS_ERR_INVALID, "fb_check must be 0 or 1");
+  if (fb_check && !b->reverse) return fail(OFDIS_ERR_INVALID, "fb_check needs a context created with OFDIS_BATCH_REVERSE");
+  if (int rc = track_args_check(seeds, npoints, max_steps, alpha, beta, tracks)) return rc;
+  Finish fin;
+  if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
+  HIPCHK(launch_track_level(b->flow[0] + fin.off, fb_check ? b->flow_rev[0] + fin.off : nullptr, count, fin.g, seeds, seed_frame,
+                            npoints, max_steps, alpha, beta, tracks, counts, (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
 }  // extern "C"

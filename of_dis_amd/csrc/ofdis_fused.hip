@@ -84,8 +84,9 @@ constexpr int SP_MAX_ITERS = 6;  // MODE 2: 2 wavefronts per iteration, 12 per w
 //         the slot of row t+1 and consuming the slot of row t -- and the solver hands the finished du/dv row to the next
 //         iteration's producer through the same LDS ring MODE 1 uses.  A lone wavefront issues one instruction per ~6
 //         clocks (dependent-issue latency), so halving the instructions per wavefront and step nearly halves the step.
-// NOC = 3 (round 6, MODE 0 only): RGB levels of at most 64 rows -- three derivative record arrays [c][records][8] (written by
-// derivatives_kernel in its record form, ofdis_tv.hip), the data term of opticalflow_aux.c:383-427; everything else is shared.
+// NOC = 3 (round 6; MODE 0, and MODE 1 where launch_tv_fused takes the tp_pipe mapping): RGB levels of at most 64 rows --
+// three derivative record arrays [c][records][8] (written by derivatives_kernel in its record form, ofdis_tv.hip), the data
+// term of opticalflow_aux.c:383-427; everything else is shared.
 template <int NS, bool BRIGHT, int MODE, int NOC = 1>
 // MODE 1 is held to 168 registers = three wavefronts per SIMD (amdgpu_waves_per_eu): three workgroups of four iterations per
 // compute unit instead of two.  That only pays without scratch: with the (wx, wy) ring and the run buffer of the wavefront that

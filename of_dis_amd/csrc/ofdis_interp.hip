@@ -36,10 +36,6 @@ __device__ __forceinline__ void interp_sample(const uint8_t* __restrict__ I, int
   }
 }
 
-__device__ __forceinline__ bool interp_inside(float px, float py, int W, int H) {
-  return px >= 0.0f && px <= (float)(W - 1) && py >= 0.0f && py <= (float)(H - 1);  // (NaN: false)
-}
-
 // The header's definition for the quad of pixels x .. x+3 of row y (those < W).  `flow(d, xx)` gives direction d's flow at
 // pixel (xx, y) of the frame; `consistent(d, nx, ny)` whether direction d's mask at (nx, ny) is OFDIS_FB_CONSISTENT.
 // `out_row` points at pixel (0, y) of time 0's output frame, `tstride` is the size of one output frame in bytes.
@@ -74,9 +70,9 @@ __device__ __forceinline__ void interp_quad(const uint8_t* __restrict__ A, const
       interp_sample(B, W, H, NOC, p1xc, p1yc, c1);
       float w0 = s, w1 = t;
       if (need_masks) {
-        const bool m0 = interp_inside(p0x, p0y, W, H) &&
+        const bool m0 = fb_inside(p0x, p0y, W, H) &&
                         consistent(0, min((int)floorf(p0xc + 0.5f), W - 1), min((int)floorf(p0yc + 0.5f), H - 1));
-        const bool m1 = interp_inside(p1x, p1y, W, H) &&
+        const bool m1 = fb_inside(p1x, p1y, W, H) &&
                         consistent(1, min((int)floorf(p1xc + 0.5f), W - 1), min((int)floorf(p1yc + 0.5f), H - 1));
         if (m0 != m1) {  // t is inside (0, 1) here: the consistent side alone
           w0 = m0 ? 1.0f : 0.0f;

@@ -233,6 +233,16 @@ hipError_t launch_interp_frames(const uint8_t* img_a, const uint8_t* img_b, cons
 // straight from both directions' level flows (ofdis_batch_interpolate): flows and masks as launch_upsample_bidir computes them
 hipError_t launch_interp_bidir(const uint8_t* img_a, const uint8_t* img_b, const float* fw, const float* rev, uint8_t* out,
                                int nframes, UpGeom g, int noc, const InterpTimes& ts, float alpha, float beta, hipStream_t s);
+// point trajectories (include/ofdis.h: ofdis_track_points; ofdis_track.hip).  On materialised full-resolution flows
+// [npairs][h][w][2] (rev null: no consistency test); seeds [npoints][2], seed_frame [npoints] or null, tracks
+// [npairs + 1][npoints][2], counts [npoints] or null
+hipError_t launch_track_points(const float* fw, const float* rev, int npairs, int w, int h, const float* seeds,
+                               const int* seed_frame, int npoints, int max_steps, float alpha, float beta, float* tracks,
+                               int* counts, hipStream_t s);
+// straight from the level flows of npairs consecutive pairs (ofdis_batch_track_points): the flows as launch_upsample_bidir /
+// launch_upsample_crop compute them
+hipError_t launch_track_level(const float* fw, const float* rev, int npairs, UpGeom g, const float* seeds, const int* seed_frame,
+                              int npoints, int max_steps, float alpha, float beta, float* tracks, int* counts, hipStream_t s);
 
 // ---- stereo-depth mode (SELECTMODE=2; ofdis_de.hip)
 struct DeSystemArgs {

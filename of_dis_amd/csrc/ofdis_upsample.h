@@ -1,5 +1,5 @@
 // ofdis_upsample.h -- device helpers of the full-resolution finish, shared by the exact-only units ofdis_upsample.hip,
-// ofdis_interp.hip and ofdis_stereo_lr.hip: the arithmetic of the level flow to full resolution (run_dense.cpp:406-414, UpGeom
+// ofdis_interp.hip, ofdis_stereo_lr.hip and ofdis_track.hip: the arithmetic of the level flow to full resolution (run_dense.cpp:406-414, UpGeom
 // in ofdis_kernels.h), the forward-backward consistency test and the compact output encodings (include/ofdis.h:
 // ofdis_encoding).  These units are compiled with -ffp-contract=off only and every finish kernel takes its values from the
 // helpers below -- upsample_h, up_row / up_group, up_mix -- so every one of them computes the same bits.
@@ -100,27 +100,53 @@ __device__ __forceinline__ UpGroup up_group(int grp, const UpGeom& g) {
 // The test of include/ofdis.h (ofdis_fb_check), written once for every kernel that evaluates it.  The units that include this
 // header are compiled under the exact contract only (-ffp-contract=off): every operation is separately rounded, so the mask is
 // a fixed function of the two flows.
-// `R(xx, yy)` returns the other direction's flow at an integer pixel of the full-resolution image.
+// The pieces are stated once -- fb_inside, fb_bilinear, fb_consistent -- and shared by the mask kernels (fb_code), frame
+// interpolation (ofdis_interp.hip) and the point trajectories of ofdis_track.hip, which walk a REAL position through them.
 enum : uint8_t { FB_CONSISTENT = 0, FB_INCONSISTENT = 1, FB_OUTSIDE = 2 };
-template <class Other>
-__device__ __forceinline__ uint8_t fb_code(float u, float v, int x, int y, int W, int H, float alpha, float beta, Other R) {
-  const float xb = (float)x + u, yb = (float)y + v;
-  if (!(xb >= 0.0f && xb <= (float)(W - 1) && yb >= 0.0f && yb <= (float)(H - 1))) return FB_OUTSIDE;  // (NaN lands here)
+// 0 <= px <= W-1 and 0 <= py <= H-1 (NaN: false)
+__device__ __forceinline__ bool fb_inside(float px, float py, int W, int H) {
+  return px >= 0.0f && px <= (float)(W - 1) && py >= 0.0f && py <= (float)(H - 1);
+}
+// A full-resolution flow sampled bilinearly at the real position (px, py) inside the image.  `R(x0, x1, y0, y1, r00, r01, r10,
+// r11)` returns that flow at the four integer pixels around it.
+template <class Taps>
+__device__ __forceinline__ float2 fb_bilinear(float px, float py, int W, int H, Taps R) {
   int x0 = 0, y0 = 0;
   float ax = 0.0f, ay = 0.0f;
-  if (W > 1) { x0 = min((int)floorf(xb), W - 2); ax = xb - (float)x0; }
-  if (H > 1) { y0 = min((int)floorf(yb), H - 2); ay = yb - (float)y0; }
+  if (W > 1) { x0 = min((int)floorf(px), W - 2); ax = px - (float)x0; }
+  if (H > 1) { y0 = min((int)floorf(py), H - 2); ay = py - (float)y0; }
   const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
   float2 r00, r01, r10, r11;
   R(x0, x1, y0, y1, r00, r01, r10, r11);
   const float bx = 1.0f - ax, by = 1.0f - ay;
-  const float ru = (r00.x * bx + r01.x * ax) * by + (r10.x * bx + r11.x * ax) * ay;
-  const float rv = (r00.y * bx + r01.y * ax) * by + (r10.y * bx + r11.y * ax) * ay;
+  return make_float2((r00.x * bx + r01.x * ax) * by + (r10.x * bx + r11.x * ax) * ay,
+                     (r00.y * bx + r01.y * ax) * by + (r10.y * bx + r11.y * ax) * ay);
+}
+// the inequality on a flow (u, v) and the other direction's flow (ru, rv) at its target (a NaN on either side: false)
+__device__ __forceinline__ bool fb_consistent(float u, float v, float ru, float rv, float alpha, float beta) {
   const float du = u + ru, dv = v + rv;
   const float lhs = du * du + dv * dv;
   const float rhs = alpha * ((u * u + v * v) + (ru * ru + rv * rv)) + beta;
-  return lhs <= rhs ? FB_CONSISTENT : FB_INCONSISTENT;
+  return lhs <= rhs;
 }
+// The code of integer pixel (x, y) with flow (u, v); `R` gives the other direction's flow (fb_bilinear).
+template <class Other>
+__device__ __forceinline__ uint8_t fb_code(float u, float v, int x, int y, int W, int H, float alpha, float beta, Other R) {
+  const float xb = (float)x + u, yb = (float)y + v;
+  if (!fb_inside(xb, yb, W, H)) return FB_OUTSIDE;  // (NaN lands here)
+  const float2 r = fb_bilinear(xb, yb, W, H, R);
+  return fb_consistent(u, v, r.x, r.y, alpha, beta) ? FB_CONSISTENT : FB_INCONSISTENT;
+}
+// `R` for a materialised full-resolution flow F [H][W][2]
+struct FlowTaps {
+  const float2* F;
+  int W;
+  __device__ __forceinline__ void operator()(int x0, int x1, int y0, int y1, float2& r00, float2& r01, float2& r10,
+                                             float2& r11) const {
+    r00 = F[(size_t)y0 * W + x0]; r01 = F[(size_t)y0 * W + x1];
+    r10 = F[(size_t)y1 * W + x0]; r11 = F[(size_t)y1 * W + x1];
+  }
+};
 
 // `R` for a direction whose full-resolution flow is not materialised: the four neighbours recomputed from its level flow
 // `fl`, the bits ofdis_batch_upsample_frames writes.  Neighbour rows y0 and y1 usually share their source rows (for s > 1): then

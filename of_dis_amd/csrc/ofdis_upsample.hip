@@ -182,11 +182,7 @@ __global__ __launch_bounds__(256) void fb_check_kernel(const float2* __restrict_
     const int y = (int)(r % h);
     const float2* R = other + (i - (long long)y * w - x);  // the frame's first pixel
     const float2 uv = flow[i];
-    mask[i] = fb_code(uv.x, uv.y, x, y, w, h, alpha, beta,
-                      [&](int x0, int x1, int y0, int y1, float2& r00, float2& r01, float2& r10, float2& r11) {
-                        r00 = R[(size_t)y0 * w + x0]; r01 = R[(size_t)y0 * w + x1];
-                        r10 = R[(size_t)y1 * w + x0]; r11 = R[(size_t)y1 * w + x1];
-                      });
+    mask[i] = fb_code(uv.x, uv.y, x, y, w, h, alpha, beta, FlowTaps{R, w});
   }
 }
 

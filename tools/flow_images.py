@@ -4,7 +4,7 @@ run_DE_* binaries do (run_dense.cpp:185-431), for a list of pairs at once and wi
 (.pfm with --stereo).
 
     python tools/flow_images.py [--rgb] [--stereo [--lr [--fill MODE]]] [--op 1..4] [--fused] [--reverse] img1a img1b out1.flo [img2a img2b out2.flo ...]
-    python tools/flow_images.py --sequence [--rgb] [--op 1..4] [--fused] [--reverse] img0 img1 ... imgN stem
+    python tools/flow_images.py --sequence [--rgb] [--op 1..4] [--fused] [--reverse [--tracks STRIDE]] img0 img1 ... imgN stem
 
 All pairs must have one size.  --fused selects the FMA / fast-reciprocal arithmetic contract (default: the exact one, bit for
 bit what run_OF_INT / run_OF_RGB write).  --reverse (optical flow only) also writes, next to <stem>.flo, the reverse flow
@@ -17,7 +17,9 @@ views of a stereo pair through an OFDIS_BATCH_STEREO_LR context and ofdis_batch_
 happens to the pixels the masks flag (ofdis_disparity_fill).  --sequence (optical flow only, --reverse allowed): the arguments
 are the N + 1 frames of a clip and a stem; the flow from frame k to frame k + 1 goes to <stem>_<k as 000>.flo.  Every frame is
 uploaded and built once, into an OFDIS_BATCH_SEQUENCE context (ofdis_batch_build_pyramids_u8_seq); the files are the ones the
-pair-wise call writes for (img0, img1), (img1, img2), ..."""
+pair-wise call writes for (img0, img1), (img1, img2), ...  --sequence --reverse --tracks STRIDE also writes the trajectories of
+the grid of that stride seeded at frame 0 (ofdis_batch_track_points with the default alpha and beta): <stem>_tracks.npy,
+float32 [N + 1][points][2] (x, y; NaN where a track has ended), and <stem>_counts.npy, int32 [points]."""
 import os
 import struct
 import sys
@@ -26,7 +28,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from of_dis_amd import capi  # noqa: E402
+from of_dis_amd import capi, tracking  # noqa: E402
 from of_dis_amd.params import oppoint, padded_size  # noqa: E402
 
 
@@ -78,6 +80,7 @@ def main(argv):
     opts = {"--rgb": False, "--stereo": False, "--fused": False, "--reverse": False, "--lr": False, "--sequence": False}
     op = 2
     fill = "none"
+    track_stride = 0
     args = []
     it = iter(argv)
     for a in it:
@@ -87,8 +90,13 @@ def main(argv):
             op = int(next(it))
         elif a == "--fill":
             fill = next(it)
+        elif a == "--tracks":
+            track_stride = int(next(it))
         else:
             args.append(a)
+    if track_stride < 0 or (track_stride and not (opts["--sequence"] and opts["--reverse"])):
+        sys.exit("--tracks STRIDE (>= 1) needs --sequence --reverse")
+    stem = args[-1] if args else None
     if opts["--sequence"]:
         if opts["--stereo"]:
             sys.exit("--sequence: a stereo pair is not a sequence")
@@ -134,6 +142,12 @@ def main(argv):
             print(f"{t[2]}_left.pfm, _right.pfm, _left_mask.pgm, _right_mask.pgm: {w}x{h}, fill {fill}, consistent "
                   f"{np.mean(mask_l[k] == 0):.3f} / {np.mean(mask_r[k] == 0):.3f} of the pixels")
         return
+    if track_stride:                 # straight from the level flows; the full-resolution flows below are for the files only
+        tracks, counts = b.track_points(tracking.grid_seeds(w, h, track_stride), w, h)
+        np.save(stem + "_tracks.npy", tracks)
+        np.save(stem + "_counts.npy", counts)
+        print(f"{stem}_tracks.npy, _counts.npy: {len(counts)} points, {np.mean(counts == len(trip) + 1):.3f} of the tracks "
+              f"reach the last frame")
     if opts["--reverse"]:            # both directions and both masks in one launch; the forward flow is upsample()'s
         full, rev, mask_fw, mask_rev = b.upsample_bidir(w, h)
     else:
