@@ -387,6 +387,62 @@ int ofdis_batch_track_points(ofdis_batch* b, int first_frame, int count, const f
                              int npoints, int max_steps, int fb_check, float alpha, float beta, float* tracks,
                              int* counts, int width_org, int height_org, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Motion-compensated temporal filtering of a clip: every frame averaged with its two neighbours warped onto it by the flow
+ * (motion compensation), a neighbour left out where the forward-backward test flags the pixel, where its sample falls outside
+ * the image and -- with a finite tau -- faded out as it differs from the pixel it would be averaged with.  The classical use
+ * is video denoising (three frames with independent noise: the noise drops towards 1 / sqrt(3)).
+ *
+ * A clip has npairs + 1 frames I_0 .. I_npairs, 8-bit, W x H x noc (noc 1 or 3, channels interleaved).  Ffw[k] is the flow
+ * from frame k to k+1 and Frev[k] the flow from frame k+1 to k, each [H][W][2] fp32; the optional masks Mfw[k], Mrev[k] hold
+ * OFDIS_FB_* codes as ofdis_batch_upsample_bidir writes them.  wn is the neighbour strength, 0 <= wn <= 1; tau the
+ * photometric gate in grey levels, +inf (no gate) or a positive float that is not subnormal.  For output frame f and pixel
+ * (x, y), every operation is a separately rounded fp32 operation in this order, independent of the arithmetic contract:
+ *   c[ch] = (float) I_f[y][x][ch]
+ *   candidate(J, F, M):                    J = the neighbouring frame, F = the flow from frame f to J, M = its mask or NULL
+ *       (u, v) = F[y][x];  p = ((float)x + u, (float)y + v)
+ *       valid  = inside(p) and (M == NULL or M[y][x] == OFDIS_FB_CONSISTENT)      inside: 0 <= px <= W-1 and 0 <= py <= H-1,
+ *                                                                                 as in ofdis_fb_check (NaN: false)
+ *       not valid: w = 0, s[ch] = 0
+ *       valid:  s[ch] = sample(J, p)[ch]   the bilinear expression of ofdis_interpolate above, at p itself (p is inside:
+ *                                          the clamp changes nothing)
+ *               d = max over ch of fabsf(s[ch] - c[ch])
+ *               g = fmaxf(1 - d / tau, 0)  IEEE division; tau = +inf gives g = 1
+ *               w = wn * g
+ *   next = candidate(I_{f+1}, Ffw[f],    Mfw[f])      when f < npairs, else w_n = 0, s_n = 0
+ *   prev = candidate(I_{f-1}, Frev[f-1], Mrev[f-1])   when f > 0,      else w_p = 0, s_p = 0
+ *   num[ch] = (c[ch] + w_p * s_p[ch]) + w_n * s_n[ch];   den = (1 + w_p) + w_n
+ *   out[ch] = (uint8) clamp((int)floorf(num[ch] / den + 0.5f), 0, 255)
+ *   support = (w_p > 0 ? 1 : 0) | (w_n > 0 ? 2 : 0)
+ * Consequences: wn = 0 returns the clip bit for bit (num = c, den = 1), and a clip of identical frames with zero flows returns
+ * itself (every sample is the pixel, d = 0, and (c + w_p*c + w_n*c) / (1 + w_p + w_n) lies within a few ulp of the integer c).
+ * The first frame has support & 1 == 0 and the last support & 2 == 0 everywhere.
+ * of_dis_amd/temporal.py states the same arithmetic in numpy.
+ * ------------------------------------------------------------------------------------------- */
+/* device arrays: frames, out [npairs+1][height][width][noc] u8; flow_fw, flow_rev [npairs][height][width][2] f32; mask_fw,
+ * mask_rev [npairs][height][width] u8 or NULL (all consistent); support [npairs+1][height][width] u8 or NULL (not written).
+ * One lane per quad of four adjacent pixels; 4-byte stores where width is a multiple of 4 and the array is 4-byte aligned, byte
+ * stores of the same bytes otherwise; nothing outside `out` and `support` is written.  Enqueues on `stream`.
+ * OFDIS_ERR_INVALID before any device work: a NULL frames, flow or out pointer; out == frames; noc not 1 or 3; npairs < 1;
+ * sizes as ofdis_fb_check rejects them; wn outside [0, 1] or NaN; tau not positive, subnormal or NaN. */
+int ofdis_temporal_filter(const uint8_t* frames, const float* flow_fw, const float* flow_rev, const uint8_t* mask_fw,
+                          const uint8_t* mask_rev, uint8_t* out, uint8_t* support, int npairs, int width, int height, int noc,
+                          float wn, float tau, void* stream);
+/* OFDIS_BATCH_SEQUENCE | OFDIS_BATCH_REVERSE contexts: frames first_frame .. first_frame + count of the context (count + 1
+ * output frames), straight from its level flows.  `frames` is the whole packed clip [nframes+1][height_org][width_org][noc]
+ * given to ofdis_batch_build_pyramids_u8_seq (pitched surfaces: copy them, as for ofdis_batch_interpolate); out =
+ * [count+1][height_org][width_org][noc], support = [count+1][height_org][width_org] or NULL.  Only the pairs [first_frame,
+ * first_frame + count) are used: the first and the last frame of the range have ONE neighbour, even where the context holds
+ * more pairs.  Bit-identical to ofdis_temporal_filter applied to the four outputs of ofdis_batch_upsample_bidir(b,
+ * first_frame, count, ..., alpha, beta) and to frames + first_frame frames, under both contracts (the kernel is
+ * contract-independent, the level flows are not); the flows and masks are never written.  Joins a pipelined pass by itself.
+ * OFDIS_ERR_INVALID as ofdis_temporal_filter, and for a NULL context, a context created without OFDIS_BATCH_SEQUENCE or
+ * without OFDIS_BATCH_REVERSE, a pair range outside the batch, an original size above the padded size, alpha / beta as
+ * ofdis_fb_check rejects them. */
+int ofdis_batch_temporal_filter(ofdis_batch* b, const uint8_t* frames, int first_frame, int count, uint8_t* out,
+                                uint8_t* support, int width_org, int height_org, float wn, float tau,
+                                float alpha, float beta, void* stream);
+
 /* Warm start (the reference's `initflow`, oflow.cpp:217-220; e.g. the previous frame pair's flow of a video):
  * per frame (w >> (sc_f+1)) x (h >> (sc_f+1)) x 2 floats, AoS.  set_initflow borrows a device array
  * [nframes][ofdis_batch_initflow_elems] (NULL switches the warm start off again); upload_initflow copies one

@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
     "ofdis_encoding_bytes", "ofdis_encode", "ofdis_batch_upsample_frames_enc",
     "ofdis_batch_input_frames", "ofdis_batch_upload_frame", "ofdis_batch_build_pyramids_u8_seq", "ofdis_batch_device_bytes",
     "ofdis_track_points", "ofdis_batch_track_points",
+    "ofdis_temporal_filter", "ofdis_batch_temporal_filter",
 ]
 BATCH_REVERSE = 1  # include/ofdis.h: OFDIS_BATCH_REVERSE
 BATCH_STEREO_LR = 2  # OFDIS_BATCH_STEREO_LR
@@ -197,6 +198,10 @@ def lib():
                                          VP, VP]
         L.ofdis_batch_track_points.argtypes = [VP, C.c_int, C.c_int, VP, VP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                                VP, VP, C.c_int, C.c_int, VP]
+        L.ofdis_temporal_filter.argtypes = [VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                            VP]
+        L.ofdis_batch_temporal_filter.argtypes = [VP, VP, C.c_int, C.c_int, VP, VP, C.c_int, C.c_int, C.c_float, C.c_float,
+                                                  C.c_float, C.c_float, VP]
         _lib = L
     return _lib
 
@@ -562,6 +567,32 @@ def track_points(flow_fw, flow_rev, seeds, seed_frame=None, max_steps=0, alpha=F
     return dtracks.get((npairs + 1, n, 2), _f32), dcounts.get((n,), np.int32)
 
 
+def temporal_filter(frames, flow_fw, flow_rev, mask_fw=None, mask_rev=None, wn=1.0, tau=np.inf, support=True):
+    """ofdis_temporal_filter on the device: frames uint8 [npairs + 1, h, w] (gray) or [npairs + 1, h, w, 3]; flow_fw / flow_rev
+    [npairs, h, w, 2] float32 (frame k -> k + 1 and frame k + 1 -> k); masks uint8 [npairs, h, w] or None (all consistent).
+    Returns (out, the shape of frames; support uint8 [npairs + 1, h, w], or None with support=False: passed as NULL).
+    of_dis_amd/temporal.py: temporal_filter_ref is the numpy statement of the same arithmetic."""
+    flow_fw, flow_rev = _f(flow_fw), _f(flow_rev)
+    assert flow_fw.shape == flow_rev.shape and flow_fw.ndim == 4 and flow_fw.shape[-1] == 2, (flow_fw.shape, flow_rev.shape)
+    npairs, h, w = flow_fw.shape[:3]
+    frames = np.ascontiguousarray(frames, np.uint8)
+    noc = 1 if frames.ndim == 3 else 3
+    assert frames.shape == (npairs + 1, h, w) + ((3,) if noc == 3 else ()), (frames.shape, flow_fw.shape)
+    devs = [Dev(x) for x in (frames, flow_fw, flow_rev)]
+    masks = []
+    for m in (mask_fw, mask_rev):
+        if m is not None:
+            m = np.ascontiguousarray(m, np.uint8)
+            assert m.shape == (npairs, h, w), (m.shape, flow_fw.shape)
+        masks.append(Dev(m) if m is not None else None)
+    do = Dev(nbytes=frames.nbytes)
+    ds = Dev(nbytes=(npairs + 1) * h * w) if support else None
+    check(lib().ofdis_temporal_filter(*[d.ptr for d in devs], *[m.ptr if m else None for m in masks], do.ptr,
+                                      ds.ptr if ds else None, npairs, w, h, noc, wn, tau, None))
+    check(lib().ofdis_sync(None))
+    return do.get(frames.shape, np.uint8), ds.get((npairs + 1, h, w), np.uint8) if ds else None
+
+
 class Batch:
     """ofdis_batch: `nframes` frame pairs of one geometry resident in HBM.  reverse=True: ofdis_batch_create_ex with
     OFDIS_BATCH_REVERSE (every pass also computes the flow B -> A of each pair).  stereo_lr=True: OFDIS_BATCH_STEREO_LR
@@ -822,6 +853,31 @@ class Batch:
                                              int(fb_check), alpha, beta, dtracks.ptr, dcounts.ptr, width_org, height_org, stream))
         check(lib().ofdis_sync(stream))
         return dtracks.get((count + 1, n, 2), _f32), dcounts.get((n,), np.int32)
+
+    def temporal_filter(self, frames_ptr, width_org, height_org, wn=1.0, tau=np.inf, first=0, count=None, alpha=FB_ALPHA,
+                        beta=FB_BETA, out_ptr=None, support=False, stream=None):
+        """ofdis_batch_temporal_filter over the frames first .. first + count of a sequence=True, reverse=True context, straight
+        from its level flows: frames_ptr is the whole packed device clip given to build_pyramids_u8_seq.  out_ptr None: returns
+        the host array [count + 1][height_org][width_org] (+ [noc] for RGB), with support=True the pair (out, support
+        [count + 1][height_org][width_org]); else writes the device array out_ptr (and, if `support` is a device pointer, that
+        array) on `stream` and returns None."""
+        count = self.nframes - first if count is None else count
+        shape = (max(count, 0) + 1, height_org, width_org)
+        oshape = shape + ((self.p.noc,) if self.p.noc > 1 else ())
+        d = ds = None
+        if out_ptr is None:
+            d = Dev(nbytes=max(1, int(np.prod(oshape, dtype=np.int64))))
+            ds = Dev(nbytes=max(1, int(np.prod(shape, dtype=np.int64)))) if support else None
+            out_ptr, sup_ptr = d.ptr, ds.ptr if ds else None
+        else:
+            sup_ptr = support if support else None
+        check(lib().ofdis_batch_temporal_filter(self.h, frames_ptr, first, count, out_ptr, sup_ptr, width_org, height_org, wn,
+                                                tau, alpha, beta, stream))
+        if d is None:
+            return None
+        check(lib().ofdis_sync(stream))
+        out = d.get(oshape, np.uint8)
+        return (out, ds.get(shape, np.uint8)) if ds else out
 
     def timing(self, enable=True):
         check(lib().ofdis_batch_timing(self.h, int(enable)))

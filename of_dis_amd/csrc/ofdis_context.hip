@@ -1,5 +1,6 @@
 // ofdis_context.hip -- the batch context's own half of the C ABI of include/ofdis.h: kernel-selection knobs, parameter
 // handling, the context's device memory (array descriptions, frame views), creation, inputs and result accessors.
+#include <cfloat>
 #include <cmath>
 
 #include "ofdis_context.h"
@@ -834,6 +835,47 @@ int ofdis_batch_track_points(ofdis_batch* b, int first_frame, int count, const f
   if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
   HIPCHK(launch_track_level(b->flow[0] + fin.off, fb_check ? b->flow_rev[0] + fin.off : nullptr, count, fin.g, seeds, seed_frame,
                             npoints, max_steps, alpha, beta, tracks, counts, (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+// ------------------------------------------------------------------------------------ temporal filter (ofdis_tfilter.hip)
+static int tfilter_args_check(const uint8_t* frames, const uint8_t* out, int noc, float wn, float tau) {
+  if (!frames || !out) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (out == frames) return fail(OFDIS_ERR_INVALID, "the temporal filter does not work in place");
+  if (noc != 1 && noc != 3) return fail(OFDIS_ERR_INVALID, "noc must be 1 or 3");
+  if (!(wn >= 0.0f && wn <= 1.0f)) return fail(OFDIS_ERR_INVALID, "wn must be inside [0, 1]");
+  if (!(tau >= FLT_MIN)) return fail(OFDIS_ERR_INVALID, "tau must be +inf or a positive float that is not subnormal");
+  return OFDIS_OK;
+}
+
+int ofdis_temporal_filter(const uint8_t* frames, const float* flow_fw, const float* flow_rev, const uint8_t* mask_fw,
+                          const uint8_t* mask_rev, uint8_t* out, uint8_t* support, int npairs, int width, int height, int noc,
+                          float wn, float tau, void* stream) {
+  if (!flow_fw || !flow_rev) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (int rc = tfilter_args_check(frames, out, noc, wn, tau)) return rc;
+  if (npairs < 1 || width < 1 || height < 1 || (long long)width * height > (1ll << 30))
+    return fail(OFDIS_ERR_INVALID, "bad sizes");
+  HIPCHK(launch_tfilter_frames(frames, flow_fw, flow_rev, mask_fw, mask_rev, out, support, npairs, width, height, noc, wn, tau,
+                               (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+int ofdis_batch_temporal_filter(ofdis_batch* b, const uint8_t* frames, int first_frame, int count, uint8_t* out,
+                                uint8_t* support, int width_org, int height_org, float wn, float tau, float alpha, float beta,
+                                void* stream) {
+  if (!b) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (!b->sequence)  // (the pairs of any other context share no frames)
+    return fail(OFDIS_ERR_INVALID, b->reverse ? "not a context created with OFDIS_BATCH_SEQUENCE"
+                                              : "not a context created with OFDIS_BATCH_SEQUENCE | OFDIS_BATCH_REVERSE");
+  if (!b->reverse) return fail(OFDIS_ERR_INVALID, "not a context created with OFDIS_BATCH_REVERSE");
+  const ofdis_params& p = b->p;
+  if (int rc = tfilter_args_check(frames, out, p.noc, wn, tau)) return rc;
+  if (!fb_constants_ok(alpha, beta)) return fail(OFDIS_ERR_INVALID, "alpha and beta must be finite and >= 0");
+  Finish fin;
+  if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
+  HIPCHK(launch_tfilter_level(frames + (size_t)first_frame * width_org * height_org * p.noc, b->flow[0] + fin.off,
+                              b->flow_rev[0] + fin.off, out, support, count, fin.g, p.noc, wn, tau, alpha, beta,
+                              (hipStream_t)stream));
   return OFDIS_OK;
 }
 

@@ -11,30 +11,9 @@
 // pixels once and then loops over all times, writing the quad's 4 * noc bytes per time (one dword for gray, three for RGB,
 // non-temporal: the output is never read by this library).  The workgroups of a frame stay on one XCD (xcd_frame_map), so a
 // frame's flows and u8 frames are read into one L2.
-#include <algorithm>
-
 #include "ofdis_upsample.h"
 
 namespace ofdis {
-
-// frame I (W x H x noc bytes) sampled bilinearly at p, clamped into the frame: c[0 .. noc-1]
-__device__ __forceinline__ void interp_sample(const uint8_t* __restrict__ I, int W, int H, int noc, float pxc, float pyc,
-                                              float (&c)[3]) {
-  int x0 = 0, y0 = 0;
-  float ax = 0.0f, ay = 0.0f;
-  if (W > 1) { x0 = min((int)floorf(pxc), W - 2); ax = pxc - (float)x0; }
-  if (H > 1) { y0 = min((int)floorf(pyc), H - 2); ay = pyc - (float)y0; }
-  const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
-  const float bx = 1.0f - ax, by = 1.0f - ay;
-  const uint8_t* r0 = I + (size_t)y0 * W * noc;
-  const uint8_t* r1 = I + (size_t)y1 * W * noc;
-#pragma unroll
-  for (int ch = 0; ch < noc; ++ch) {
-    const float i00 = (float)r0[x0 * noc + ch], i01 = (float)r0[x1 * noc + ch];
-    const float i10 = (float)r1[x0 * noc + ch], i11 = (float)r1[x1 * noc + ch];
-    c[ch] = (i00 * bx + i01 * ax) * by + (i10 * bx + i11 * ax) * ay;
-  }
-}
 
 // The header's definition for the quad of pixels x .. x+3 of row y (those < W).  `flow(d, xx)` gives direction d's flow at
 // pixel (xx, y) of the frame; `consistent(d, nx, ny)` whether direction d's mask at (nx, ny) is OFDIS_FB_CONSISTENT.
@@ -154,28 +133,10 @@ __global__ __launch_bounds__(256) void interp_bidir_kernel(const uint8_t* __rest
                    });
 }
 
-// Blocks of 256 quads per frame, and the frames of one launch: a launch covers at most 2^22 blocks (2^30 lanes), a multiple
-// of 8 frames where it can (xcd_frame_map), and the launcher walks the frames in such chunks.
-struct InterpGrid {
-  int bpf, chunk;
-};
-static InterpGrid interp_grid(int nframes, int w, int h) {
-  InterpGrid g;
-  g.bpf = (int)(((long long)((w + 3) >> 2) * h + 255) / 256);
-  long long c = (1ll << 22) / g.bpf;
-  if (c >= 8) c &= ~7ll;
-  g.chunk = (int)std::max(1ll, std::min(c, (long long)nframes));
-  return g;
-}
-static unsigned interp_blocks(int frames, int bpf) {
-  const long long fr = frames < 8 ? frames : (frames + 7) / 8 * 8;
-  return (unsigned)(fr * bpf);
-}
-
 hipError_t launch_interp_frames(const uint8_t* img_a, const uint8_t* img_b, const float* flow_fw, const float* flow_rev,
                                 const uint8_t* mask_fw, const uint8_t* mask_rev, uint8_t* out, int nframes, int w, int h,
                                 int noc, const InterpTimes& ts, hipStream_t s) {
-  const InterpGrid g = interp_grid(nframes, w, h);
+  const QuadGrid g = quad_grid(nframes, w, h);
   const bool vec = (w & 3) == 0 && ((uintptr_t)out & 3) == 0;
   const size_t plane = (size_t)w * h;
   for (int f0 = 0; f0 < nframes; f0 += g.chunk) {
@@ -187,10 +148,10 @@ hipError_t launch_interp_frames(const uint8_t* img_a, const uint8_t* img_b, cons
     const float2* fr = (const float2*)flow_rev + fo;
     uint8_t* o = out + fo * noc * ts.n;
     if (noc == 3)
-      hipLaunchKernelGGL(interp_frames_kernel<3>, dim3(interp_blocks(n, g.bpf)), dim3(256), 0, s, img_a + fo * 3, img_b + fo * 3,
+      hipLaunchKernelGGL(interp_frames_kernel<3>, dim3(quad_blocks(n, g.bpf)), dim3(256), 0, s, img_a + fo * 3, img_b + fo * 3,
                          ff, fr, mf, mr, o, n, w, h, g.bpf, ts, vec);
     else
-      hipLaunchKernelGGL(interp_frames_kernel<1>, dim3(interp_blocks(n, g.bpf)), dim3(256), 0, s, img_a + fo, img_b + fo, ff,
+      hipLaunchKernelGGL(interp_frames_kernel<1>, dim3(quad_blocks(n, g.bpf)), dim3(256), 0, s, img_a + fo, img_b + fo, ff,
                          fr, mf, mr, o, n, w, h, g.bpf, ts, vec);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -200,7 +161,7 @@ hipError_t launch_interp_frames(const uint8_t* img_a, const uint8_t* img_b, cons
 
 hipError_t launch_interp_bidir(const uint8_t* img_a, const uint8_t* img_b, const float* fw, const float* rev, uint8_t* out,
                                int nframes, UpGeom ug, int noc, const InterpTimes& ts, float alpha, float beta, hipStream_t s) {
-  const InterpGrid g = interp_grid(nframes, ug.wo, ug.ho);
+  const QuadGrid g = quad_grid(nframes, ug.wo, ug.ho);
   const bool vec = (ug.wo & 3) == 0 && ((uintptr_t)out & 3) == 0;
   const size_t plane = (size_t)ug.wo * ug.ho, lplane = ug.plane();
   for (int f0 = 0; f0 < nframes; f0 += g.chunk) {
@@ -209,10 +170,10 @@ hipError_t launch_interp_bidir(const uint8_t* img_a, const uint8_t* img_b, const
     const float2* fr = (const float2*)rev + (size_t)f0 * lplane;
     uint8_t* o = out + (size_t)f0 * plane * noc * ts.n;
     if (noc == 3)
-      hipLaunchKernelGGL(interp_bidir_kernel<3>, dim3(interp_blocks(n, g.bpf)), dim3(256), 0, s, img_a + (size_t)f0 * plane * 3,
+      hipLaunchKernelGGL(interp_bidir_kernel<3>, dim3(quad_blocks(n, g.bpf)), dim3(256), 0, s, img_a + (size_t)f0 * plane * 3,
                          img_b + (size_t)f0 * plane * 3, ff, fr, o, n, ug, g.bpf, ts, alpha, beta, vec);
     else
-      hipLaunchKernelGGL(interp_bidir_kernel<1>, dim3(interp_blocks(n, g.bpf)), dim3(256), 0, s, img_a + (size_t)f0 * plane,
+      hipLaunchKernelGGL(interp_bidir_kernel<1>, dim3(quad_blocks(n, g.bpf)), dim3(256), 0, s, img_a + (size_t)f0 * plane,
                          img_b + (size_t)f0 * plane, ff, fr, o, n, ug, g.bpf, ts, alpha, beta, vec);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

@@ -243,6 +243,16 @@ hipError_t launch_track_points(const float* fw, const float* rev, int npairs, in
 // launch_upsample_crop compute them
 hipError_t launch_track_level(const float* fw, const float* rev, int npairs, UpGeom g, const float* seeds, const int* seed_frame,
                               int npoints, int max_steps, float alpha, float beta, float* tracks, int* counts, hipStream_t s);
+// motion-compensated temporal filter (include/ofdis.h: ofdis_temporal_filter; ofdis_tfilter.hip).  On materialised arrays:
+// frames, out [npairs + 1][h][w][noc] u8, AoS flows [npairs][h][w][2], masks [npairs][h][w] or null, support
+// [npairs + 1][h][w] or null
+hipError_t launch_tfilter_frames(const uint8_t* frames, const float* flow_fw, const float* flow_rev, const uint8_t* mask_fw,
+                                 const uint8_t* mask_rev, uint8_t* out, uint8_t* support, int npairs, int w, int h, int noc,
+                                 float wn, float tau, hipStream_t s);
+// straight from the level flows of npairs consecutive pairs (ofdis_batch_temporal_filter): flows and masks as
+// launch_upsample_bidir computes them
+hipError_t launch_tfilter_level(const uint8_t* frames, const float* fw, const float* rev, uint8_t* out, uint8_t* support,
+                                int npairs, UpGeom g, int noc, float wn, float tau, float alpha, float beta, hipStream_t s);
 
 // ---- stereo-depth mode (SELECTMODE=2; ofdis_de.hip)
 struct DeSystemArgs {

@@ -1,9 +1,11 @@
 // ofdis_upsample.h -- device helpers of the full-resolution finish, shared by the exact-only units ofdis_upsample.hip,
-// ofdis_interp.hip, ofdis_stereo_lr.hip and ofdis_track.hip: the arithmetic of the level flow to full resolution (run_dense.cpp:406-414, UpGeom
+// ofdis_interp.hip, ofdis_stereo_lr.hip, ofdis_track.hip and ofdis_tfilter.hip: the arithmetic of the level flow to full resolution (run_dense.cpp:406-414, UpGeom
 // in ofdis_kernels.h), the forward-backward consistency test and the compact output encodings (include/ofdis.h:
 // ofdis_encoding).  These units are compiled with -ffp-contract=off only and every finish kernel takes its values from the
 // helpers below -- upsample_h, up_row / up_group, up_mix -- so every one of them computes the same bits.
 #pragma once
+#include <algorithm>
+
 #include "ofdis_kernels.h"
 
 namespace ofdis {
@@ -170,6 +172,46 @@ struct UpNeighbours {
     r11 = up_mix(n0, n1, q1.fy);
   }
 };
+
+// ------------------------------------------------------------------------------------ 8-bit frames at a real position
+// frame I (W x H x noc bytes) sampled bilinearly at p, clamped into the frame: c[0 .. noc-1]
+__device__ __forceinline__ void interp_sample(const uint8_t* __restrict__ I, int W, int H, int noc, float pxc, float pyc,
+                                              float (&c)[3]) {
+  int x0 = 0, y0 = 0;
+  float ax = 0.0f, ay = 0.0f;
+  if (W > 1) { x0 = min((int)floorf(pxc), W - 2); ax = pxc - (float)x0; }
+  if (H > 1) { y0 = min((int)floorf(pyc), H - 2); ay = pyc - (float)y0; }
+  const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
+  const float bx = 1.0f - ax, by = 1.0f - ay;
+  const uint8_t* r0 = I + (size_t)y0 * W * noc;
+  const uint8_t* r1 = I + (size_t)y1 * W * noc;
+#pragma unroll
+  for (int ch = 0; ch < noc; ++ch) {
+    const float i00 = (float)r0[x0 * noc + ch], i01 = (float)r0[x1 * noc + ch];
+    const float i10 = (float)r1[x0 * noc + ch], i11 = (float)r1[x1 * noc + ch];
+    c[ch] = (i00 * bx + i01 * ax) * by + (i10 * bx + i11 * ax) * ay;
+  }
+}
+
+// The launch geometry of the kernels in which one lane owns a quad of 4 adjacent pixels of one row of one frame
+// (ofdis_interp.hip, ofdis_tfilter.hip).  Blocks of 256 quads per frame, and the frames of one launch: a launch covers at most
+// 2^22 blocks (2^30 lanes), a multiple of 8 frames where it can (xcd_frame_map), and the launcher walks the frames in such
+// chunks.
+struct QuadGrid {
+  int bpf, chunk;
+};
+inline QuadGrid quad_grid(int nframes, int w, int h) {
+  QuadGrid g;
+  g.bpf = (int)(((long long)((w + 3) >> 2) * h + 255) / 256);
+  long long c = (1ll << 22) / g.bpf;
+  if (c >= 8) c &= ~7ll;
+  g.chunk = (int)std::max(1ll, std::min(c, (long long)nframes));
+  return g;
+}
+inline unsigned quad_blocks(int frames, int bpf) {
+  const long long fr = frames < 8 ? frames : (frames + 7) / 8 * 8;
+  return (unsigned)(fr * bpf);
+}
 
 // ------------------------------------------------------------------------------------ compact output encodings
 // The arithmetic of include/ofdis.h (ofdis_encoding), written once for ofdis_encode and the encoding upsample kernels.  TYPE is
