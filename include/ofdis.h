@@ -443,6 +443,96 @@ int ofdis_batch_temporal_filter(ofdis_batch* b, const uint8_t* frames, int first
                                 uint8_t* support, int width_org, int height_org, float wn, float tau,
                                 float alpha, float beta, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Global (camera) motion models and motion-compensated flow: per pair, a translation or a 6-parameter affine model of the flow
+ * field fitted by trimmed least squares -- a least-squares fit, then rounds - 1 re-fits on the pixels whose residual under the
+ * previous model is within thresh pixels -- and, given the models, the residual flow (flow minus model) with a label per pixel:
+ * inlier (background, moves with the camera), outlier (moves on its own) or invalid.  The uses: subtracting the camera motion
+ * before a two-stream quantisation, the input of a stabiliser, foreground / background segmentation, scene-change statistics.
+ * Not provided: homography and similarity models, warping frames along a smoothed camera path (stabilisation itself), models
+ * of the reverse direction, the C++ sequence driver.
+ *
+ * The frame is W x H with both sides <= OFDIS_GM_MAX_SIDE.  F is the flow [H][W][2] fp32 of one pair, M its mask of OFDIS_FB_*
+ * codes or NULL.  Centred, doubled coordinates are integers: X = 2x - (W-1), Y = 2y - (H-1).
+ *   valid(x, y) = (M == NULL or M[y][x] == OFDIS_FB_CONSISTENT) and fabsf(u) <= OFDIS_GM_MAX_FLOW and fabsf(v) <= OFDIS_GM_MAX_FLOW
+ *                                                           ((u, v) = F[y][x]; a NaN or an infinity fails the comparison)
+ *   qu = (int)rintf(u * 256.0f), qv likewise                the product is exact, rintf rounds to nearest even; |q| <= 2^20
+ * Sums over a pixel set S, twelve exact 64-bit integers:
+ *   n = |S|, SX, SY, SXX, SXY, SYY,  Squ, SXqu, SYqu,  Sqv, SXqv, SYqv          (SXqu = sum of X * qu, and so on)
+ * Bounds: a set has at most W * H pixels, |X| < W, |Y| < H and |q| <= 2^20, so |SXqu| < W * 2^20 * W * H = W^2 * H * 2^20 and,
+ * with W, H <= 8192 = 2^13, every one of the twelve is below 2^13 * 2^13 * 2^13 * 2^20 = 2^59 (the second moments below
+ * 2^52): int64 never overflows.
+ * Integer addition is associative, so any mapping of pixels to lanes and any order of summation gives the same twelve numbers:
+ * this is what lets the fused kernel use a different mapping from the standalone one and still return the same bits.
+ * Solve, in fp64, every operation separately rounded (no contraction), int64 -> double the ordinary round-to-nearest
+ * conversion; n, Sx ... are the sums as doubles, Su / Sxu / Syu those of qu, Sv / Sxv / Syv those of qv:
+ *   c00 = Sxx*Syy - Sxy*Sxy   c01 = Sxy*Sy - Sx*Syy   c02 = Sx*Sxy - Sxx*Sy
+ *   c11 = n*Syy - Sy*Sy       c12 = Sx*Sy - n*Sxy     c22 = n*Sxx - Sx*Sx
+ *   det = (n*c00 + Sx*c01) + Sy*c02
+ *   affine (model == OFDIS_GM_AFFINE and n >= 3 and det > 0):
+ *       b0 = ((c00*Su + c01*Sxu) + c02*Syu) / det      a0 = b0 / 256
+ *       b1 = ((c01*Su + c11*Sxu) + c12*Syu) / det      a1 = b1 / 128
+ *       b2 = ((c02*Su + c12*Sxu) + c22*Syu) / det      a2 = b2 / 128
+ *       and the same with Sv, Sxv, Syv for a3, a4, a5                          status OFDIS_GM_OK_AFFINE
+ *   translation (asked for, or the fallback from affine, n >= 1):
+ *       a0 = (Su / n) / 256, a3 = (Sv / n) / 256, the rest 0                   status OFDIS_GM_TRANSLATION
+ *   n == 0: the model is all zeros                                             status OFDIS_GM_EMPTY
+ * The model means u(x, y) = a0 + a1*(x - cx) + a2*(y - cy), v(x, y) = a3 + a4*(x - cx) + a5*(y - cy), cx = (W-1)/2, cy = (H-1)/2.
+ * Caveat: on small sets every product above is exact, so a collinear set (one row, one diagonal) gives det == 0 exactly and
+ * falls back to the translation; on very large collinear sets the products round and det is only approximately 0.
+ * Residual, in fp32, every operation separately rounded:
+ *   af_k = (float) a_k;  xc = (float)X * 0.5f;  yc = (float)Y * 0.5f
+ *   mu = (af0 + af1*xc) + af2*yc;  mv = (af3 + af4*xc) + af5*yc;  ru = u - mu;  rv = v - mv
+ *   r2 = ru*ru + rv*rv;  t2 = thresh*thresh (computed once);  near = valid and r2 <= t2      (a NaN gives false)
+ * Rounds: S_0 = valid; for r >= 1, S_r = near under the model of round r-1.  Each round sums over its set and solves.  An empty
+ * S_r with r >= 1 ends the process: the model and status of round r-1 stay.
+ * of_dis_amd/gmotion.py states the same arithmetic in numpy.
+ * ------------------------------------------------------------------------------------------- */
+#define OFDIS_GM_MAX_SIDE   8192
+#define OFDIS_GM_MAX_FLOW   4096.0f
+#define OFDIS_GM_MAX_ROUNDS 8
+enum { OFDIS_GM_TRANSLATION_ONLY = 0, OFDIS_GM_AFFINE = 1 };                    /* model */
+enum { OFDIS_GM_OK_AFFINE = 0, OFDIS_GM_TRANSLATION = 1, OFDIS_GM_EMPTY = 2 };  /* status */
+enum { OFDIS_GM_INLIER = 0, OFDIS_GM_OUTLIER = 1, OFDIS_GM_INVALID = 2 };       /* label */
+/* bytes of the work buffer ofdis_global_motion needs (one 96-byte record of sums per workgroup and pair); 0 for sizes that
+ * function rejects */
+size_t ofdis_global_motion_work_bytes(int npairs, int width, int height);
+/* device arrays: flow [npairs][height][width][2] f32; mask [npairs][height][width] u8 or NULL (all consistent); models
+ * [npairs][6] f64; stats [npairs][3] int64 or NULL: |S_0|, the size of the last set used, the status; work: 8-byte aligned,
+ * at least ofdis_global_motion_work_bytes.  All rounds are enqueued on `stream` without a host synchronisation: per round one
+ * launch that sums all pairs (a workgroup writes one record into its own slot of `work` with plain stores; no atomics, no
+ * waiting between workgroups) and one that solves (one wavefront per pair).  OFDIS_ERR_INVALID before any device work: a NULL
+ * flow, models or work pointer; model not OFDIS_GM_TRANSLATION_ONLY or OFDIS_GM_AFFINE; rounds outside 1 ..
+ * OFDIS_GM_MAX_ROUNDS; thresh not finite or <= 0; sizes as ofdis_fb_check rejects them or a side above OFDIS_GM_MAX_SIDE; a
+ * work buffer that is too small or not 8-byte aligned. */
+int ofdis_global_motion(const float* flow, const uint8_t* mask, int npairs, int width, int height, int model, int rounds,
+                        float thresh, double* models, long long* stats, void* work, size_t work_bytes, void* stream);
+/* One pass: residual[y][x] = (ru, rv) under the pair's model (NaN and infinities propagate), label[y][x] = OFDIS_GM_INLIER for
+ * near, OFDIS_GM_OUTLIER for valid but not near, OFDIS_GM_INVALID otherwise.  residual [npairs][height][width][2] f32 and label
+ * [npairs][height][width] u8: either may be NULL (not written), not both; residual may be `flow` itself.  16-byte stores of the
+ * residual where width is even and the array 16-byte aligned, 4-byte stores of the labels where width is a multiple of 4 and
+ * the array 4-byte aligned, narrower stores of the same bytes otherwise; nothing outside the two outputs is written.
+ * OFDIS_ERR_INVALID before any device work: a NULL flow or models pointer, both outputs NULL, thresh and sizes as above. */
+int ofdis_motion_compensate(const float* flow, const uint8_t* mask, const double* models, int npairs, int width, int height,
+                            float thresh, float* residual, uint8_t* label, void* stream);
+/* The same straight from the level flows of the pairs [first_frame, first_frame + count) of an optical-flow context (any kind:
+ * plain, OFDIS_BATCH_REVERSE, OFDIS_BATCH_SEQUENCE); the full-resolution flow and the masks are never written.  models
+ * [count][6], stats [count][3] or NULL, residual / label [count][height_org][width_org]([2]).
+ * fb_check = 0: bit-identical to the standalone calls on what ofdis_batch_upsample_frames writes, with mask = NULL.
+ * fb_check = 1 (needs OFDIS_BATCH_REVERSE): bit-identical to the standalone calls on out_fw and mask_fw of
+ * ofdis_batch_upsample_bidir(b, first_frame, count, ..., alpha, beta).  Both under both contracts (the kernels are
+ * contract-independent, the level flows are not).  The work buffer belongs to the context: allocated at the first call,
+ * counted by ofdis_batch_device_bytes from then on.  Joins a pipelined pass by itself.  OFDIS_ERR_INVALID as the standalone
+ * calls, and for a NULL context, a stereo-depth context, fb_check not 0 or 1, fb_check = 1 on a context created without
+ * OFDIS_BATCH_REVERSE, alpha / beta as ofdis_fb_check rejects them, a pair range outside the batch, an original size above the
+ * padded size or above OFDIS_GM_MAX_SIDE. */
+int ofdis_batch_global_motion(ofdis_batch* b, int first_frame, int count, int model, int rounds, float thresh, int fb_check,
+                              float alpha, float beta, double* models, long long* stats, int width_org, int height_org,
+                              void* stream);
+int ofdis_batch_motion_compensate(ofdis_batch* b, int first_frame, int count, const double* models, float thresh, int fb_check,
+                                  float alpha, float beta, float* residual, uint8_t* label, int width_org, int height_org,
+                                  void* stream);
+
 /* Warm start (the reference's `initflow`, oflow.cpp:217-220; e.g. the previous frame pair's flow of a video):
  * per frame (w >> (sc_f+1)) x (h >> (sc_f+1)) x 2 floats, AoS.  set_initflow borrows a device array
  * [nframes][ofdis_batch_initflow_elems] (NULL switches the warm start off again); upload_initflow copies one

@@ -43,6 +43,8 @@ ABI_SYMBOLS = [
     "ofdis_batch_input_frames", "ofdis_batch_upload_frame", "ofdis_batch_build_pyramids_u8_seq", "ofdis_batch_device_bytes",
     "ofdis_track_points", "ofdis_batch_track_points",
     "ofdis_temporal_filter", "ofdis_batch_temporal_filter",
+    "ofdis_global_motion_work_bytes", "ofdis_global_motion", "ofdis_motion_compensate", "ofdis_batch_global_motion",
+    "ofdis_batch_motion_compensate",
 ]
 BATCH_REVERSE = 1  # include/ofdis.h: OFDIS_BATCH_REVERSE
 BATCH_STEREO_LR = 2  # OFDIS_BATCH_STEREO_LR
@@ -54,6 +56,10 @@ FB_CONSISTENT, FB_INCONSISTENT, FB_OUTSIDE = 0, 1, 2
 INTERP_MAX_TIMES = 16  # OFDIS_INTERP_MAX_TIMES
 ENC_F32, ENC_F16, ENC_U16, ENC_U8 = 0, 1, 2, 3  # OFDIS_ENC_*
 TRACK_MAX_POINTS = 1 << 24  # OFDIS_TRACK_MAX_POINTS
+GM_MAX_SIDE, GM_MAX_FLOW, GM_MAX_ROUNDS = 8192, 4096.0, 8  # OFDIS_GM_MAX_*
+GM_TRANSLATION_ONLY, GM_AFFINE = 0, 1  # OFDIS_GM_* model
+GM_OK_AFFINE, GM_TRANSLATION, GM_EMPTY = 0, 1, 2  # OFDIS_GM_* status
+GM_INLIER, GM_OUTLIER, GM_INVALID = 0, 1, 2  # OFDIS_GM_* label
 OFDIS_VERSION = 3  # include/ofdis.h: the struct layouts below (OfdisTuning: 20 ints) belong to this ABI version
 
 
@@ -202,6 +208,15 @@ def lib():
                                             VP]
         L.ofdis_batch_temporal_filter.argtypes = [VP, VP, C.c_int, C.c_int, VP, VP, C.c_int, C.c_int, C.c_float, C.c_float,
                                                   C.c_float, C.c_float, VP]
+        L.ofdis_global_motion_work_bytes.restype = C.c_size_t
+        L.ofdis_global_motion_work_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.ofdis_global_motion.argtypes = [VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, VP, VP, VP, C.c_size_t,
+                                          VP]
+        L.ofdis_motion_compensate.argtypes = [VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_float, VP, VP, VP]
+        L.ofdis_batch_global_motion.argtypes = [VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float,
+                                                VP, VP, C.c_int, C.c_int, VP]
+        L.ofdis_batch_motion_compensate.argtypes = [VP, C.c_int, C.c_int, VP, C.c_float, C.c_int, C.c_float, C.c_float, VP, VP,
+                                                    C.c_int, C.c_int, VP]
         _lib = L
     return _lib
 
@@ -593,6 +608,48 @@ def temporal_filter(frames, flow_fw, flow_rev, mask_fw=None, mask_rev=None, wn=1
     return do.get(frames.shape, np.uint8), ds.get((npairs + 1, h, w), np.uint8) if ds else None
 
 
+def _gm_inputs(flow, mask):
+    flow = _f(flow)
+    assert flow.ndim == 4 and flow.shape[-1] == 2, flow.shape
+    if mask is not None:
+        mask = np.ascontiguousarray(mask, np.uint8)
+        assert mask.shape == flow.shape[:3], (mask.shape, flow.shape)
+    return flow, mask
+
+
+def global_motion(flow, mask=None, model=GM_AFFINE, rounds=3, thresh=1.0):
+    """ofdis_global_motion on the device: flow [npairs, h, w, 2] float32, mask uint8 [npairs, h, w] or None (all consistent)
+    -> (models [npairs, 6] float64, stats [npairs, 3] int64: |S_0|, the size of the last set used, the status).
+    of_dis_amd/gmotion.py: global_motion_ref is the numpy statement of the same arithmetic."""
+    flow, mask = _gm_inputs(flow, mask)
+    npairs, h, w = flow.shape[:3]
+    df, dm = Dev(flow), Dev(mask) if mask is not None else None
+    dmodels, dstats = Dev(nbytes=max(8, npairs * 48)), Dev(nbytes=max(8, npairs * 24))
+    wb = lib().ofdis_global_motion_work_bytes(npairs, w, h)
+    dwork = Dev(nbytes=max(8, wb))
+    check(lib().ofdis_global_motion(df.ptr, dm.ptr if dm else None, npairs, w, h, model, rounds, thresh, dmodels.ptr, dstats.ptr,
+                                    dwork.ptr, wb, None))
+    check(lib().ofdis_sync(None))
+    return dmodels.get((npairs, 6), np.float64), dstats.get((npairs, 3), np.int64)
+
+
+def motion_compensate(flow, models, mask=None, thresh=1.0, residual=True, label=True, in_place=False):
+    """ofdis_motion_compensate on the device: flow [npairs, h, w, 2] float32, models [npairs, 6] float64, mask as above ->
+    (residual [npairs, h, w, 2] float32, label [npairs, h, w] uint8); residual=False / label=False pass NULL and return None in
+    that place.  in_place: `residual` is the flow's own device array (the library allows it)."""
+    flow, mask = _gm_inputs(flow, mask)
+    npairs, h, w = flow.shape[:3]
+    models = np.ascontiguousarray(models, np.float64)
+    assert models.shape == (npairs, 6), models.shape
+    df, dm, dmodels = Dev(flow), Dev(mask) if mask is not None else None, Dev(models)
+    dr = (df if in_place else Dev(nbytes=max(8, flow.nbytes))) if residual else None
+    dl = Dev(nbytes=max(1, npairs * h * w)) if label else None
+    check(lib().ofdis_motion_compensate(df.ptr, dm.ptr if dm else None, dmodels.ptr, npairs, w, h, thresh, dr.ptr if dr else None,
+                                        dl.ptr if dl else None, None))
+    check(lib().ofdis_sync(None))
+    return dr.get(flow.shape, _f32) if dr else None, dl.get((npairs, h, w), np.uint8) if dl else None
+
+
 class Batch:
     """ofdis_batch: `nframes` frame pairs of one geometry resident in HBM.  reverse=True: ofdis_batch_create_ex with
     OFDIS_BATCH_REVERSE (every pass also computes the flow B -> A of each pair).  stereo_lr=True: OFDIS_BATCH_STEREO_LR
@@ -878,6 +935,56 @@ class Batch:
         check(lib().ofdis_sync(stream))
         out = d.get(oshape, np.uint8)
         return (out, ds.get(shape, np.uint8)) if ds else out
+
+    def global_motion(self, width_org, height_org, model=GM_AFFINE, rounds=3, thresh=1.0, fb_check=False, first=0, count=None,
+                      alpha=FB_ALPHA, beta=FB_BETA, models_ptr=None, stats_ptr=None, stream=None):
+        """ofdis_batch_global_motion over the pairs [first, first + count) of an optical-flow context, straight from its level
+        flows.  fb_check=True (needs reverse=True) honours the forward mask of upsample_bidir.  models_ptr None: returns the
+        host arrays (models [count, 6] float64, stats [count, 3] int64); else writes the device array models_ptr (and stats_ptr,
+        if given) on `stream` and returns None."""
+        count = self.nframes - first if count is None else count
+        n = max(count, 1)
+        dm = ds = None
+        if models_ptr is None:
+            dm, ds = Dev(nbytes=n * 48), Dev(nbytes=n * 24)
+            models_ptr, stats_ptr = dm.ptr, ds.ptr
+        check(lib().ofdis_batch_global_motion(self.h, first, count, model, rounds, thresh, int(fb_check), alpha, beta, models_ptr,
+                                              stats_ptr, width_org, height_org, stream))
+        if dm is None:
+            return None
+        check(lib().ofdis_sync(stream))
+        return dm.get((count, 6), np.float64), ds.get((count, 3), np.int64)
+
+    def motion_compensate(self, models, width_org, height_org, thresh=1.0, fb_check=False, first=0, count=None, alpha=FB_ALPHA,
+                          beta=FB_BETA, residual=True, label=True, out_ptr=None, stream=None):
+        """ofdis_batch_motion_compensate over the pairs [first, first + count): models is a host array [count, 6] float64 or a
+        device pointer.  out_ptr None: returns the host arrays (residual [count, height_org, width_org, 2] float32, label
+        [count, height_org, width_org] uint8; None where residual=False / label=False); else out_ptr = (residual device pointer
+        or None, label device pointer or None), written on `stream`, and the call returns None."""
+        count = self.nframes - first if count is None else count
+        n = max(count, 1)
+        keep = None
+        if not isinstance(models, (int, type(None))):
+            models = np.ascontiguousarray(models, np.float64)
+            assert models.shape == (n, 6), models.shape
+            keep = Dev(models)
+            models = keep.ptr
+        rshape, lshape = (n, height_org, width_org, 2), (n, height_org, width_org)
+        dr = dl = None
+        if out_ptr is None:
+            dr = Dev(nbytes=max(8, int(np.prod(rshape, dtype=np.int64)) * 4)) if residual else None
+            dl = Dev(nbytes=max(1, int(np.prod(lshape, dtype=np.int64)))) if label else None
+            rptr, lptr = dr.ptr if dr else None, dl.ptr if dl else None
+        else:
+            rptr, lptr = out_ptr
+        check(lib().ofdis_batch_motion_compensate(self.h, first, count, models, thresh, int(fb_check), alpha, beta, rptr, lptr,
+                                                  width_org, height_org, stream))
+        if out_ptr is not None:
+            if keep is not None:
+                check(lib().ofdis_sync(stream))  # the uploaded models must outlive the launch
+            return None
+        check(lib().ofdis_sync(stream))
+        return dr.get(rshape, _f32) if dr else None, dl.get(lshape, np.uint8) if dl else None
 
     def timing(self, enable=True):
         check(lib().ofdis_batch_timing(self.h, int(enable)))

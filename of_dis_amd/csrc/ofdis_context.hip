@@ -879,4 +879,87 @@ int ofdis_batch_temporal_filter(ofdis_batch* b, const uint8_t* frames, int first
   return OFDIS_OK;
 }
 
+// ------------------------------------------------------------------------------------ global motion (ofdis_gmotion.hip)
+static bool gm_sizes_ok(int npairs, int width, int height) {
+  return npairs >= 1 && width >= 1 && height >= 1 && width <= OFDIS_GM_MAX_SIDE && height <= OFDIS_GM_MAX_SIDE;
+}
+static int gm_thresh_check(float thresh) {
+  if (!(std::isfinite(thresh) && thresh > 0.0f)) return fail(OFDIS_ERR_INVALID, "thresh must be finite and > 0");
+  return OFDIS_OK;
+}
+static int gm_fit_check(int model, int rounds, float thresh) {
+  if (model != OFDIS_GM_TRANSLATION_ONLY && model != OFDIS_GM_AFFINE)
+    return fail(OFDIS_ERR_INVALID, "model must be OFDIS_GM_TRANSLATION_ONLY or OFDIS_GM_AFFINE");
+  if (rounds < 1 || rounds > OFDIS_GM_MAX_ROUNDS) return fail(OFDIS_ERR_INVALID, "rounds outside 1..OFDIS_GM_MAX_ROUNDS");
+  return gm_thresh_check(thresh);
+}
+static const char* const kGmSizes = "bad sizes (a side above OFDIS_GM_MAX_SIDE?)";
+// what both batch calls check about the context and the mask they are asked for
+static int gm_batch_check(const ofdis_batch* b, int fb_check, float alpha, float beta, int width_org, int height_org) {
+  if (!b) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (b->p.selectmode == 2) return fail(OFDIS_ERR_INVALID, "not an optical-flow context (stereo-depth mode has no flow field)");
+  if (fb_check != 0 && fb_check != 1) return fail(OFDIS_ERR_INVALID, "fb_check must be 0 or 1");
+  if (fb_check && !b->reverse) return fail(OFDIS_ERR_INVALID, "fb_check needs a context created with OFDIS_BATCH_REVERSE");
+  if (!fb_constants_ok(alpha, beta)) return fail(OFDIS_ERR_INVALID, "alpha and beta must be finite and >= 0");
+  if (width_org > OFDIS_GM_MAX_SIDE || height_org > OFDIS_GM_MAX_SIDE) return fail(OFDIS_ERR_INVALID, kGmSizes);
+  return OFDIS_OK;
+}
+
+size_t ofdis_global_motion_work_bytes(int npairs, int width, int height) {
+  return gm_sizes_ok(npairs, width, height) ? gmotion_work_bytes(npairs, width, height) : 0;
+}
+
+int ofdis_global_motion(const float* flow, const uint8_t* mask, int npairs, int width, int height, int model, int rounds,
+                        float thresh, double* models, long long* stats, void* work, size_t work_bytes, void* stream) {
+  if (!flow || !models) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (int rc = gm_fit_check(model, rounds, thresh)) return rc;
+  if (!gm_sizes_ok(npairs, width, height)) return fail(OFDIS_ERR_INVALID, kGmSizes);
+  if (!work || ((uintptr_t)work & 7) || work_bytes < gmotion_work_bytes(npairs, width, height))
+    return fail(OFDIS_ERR_INVALID, "work buffer is NULL, not 8-byte aligned or smaller than ofdis_global_motion_work_bytes");
+  HIPCHK(launch_gmotion_frames(flow, mask, npairs, width, height, model, rounds, thresh, models, stats, work,
+                               (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+int ofdis_motion_compensate(const float* flow, const uint8_t* mask, const double* models, int npairs, int width, int height,
+                            float thresh, float* residual, uint8_t* label, void* stream) {
+  if (!flow || !models || (!residual && !label)) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (int rc = gm_thresh_check(thresh)) return rc;
+  if (!gm_sizes_ok(npairs, width, height)) return fail(OFDIS_ERR_INVALID, kGmSizes);
+  HIPCHK(launch_gmotion_compensate_frames(flow, mask, models, npairs, width, height, thresh, residual, label,
+                                          (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+int ofdis_batch_global_motion(ofdis_batch* b, int first_frame, int count, int model, int rounds, float thresh, int fb_check,
+                              float alpha, float beta, double* models, long long* stats, int width_org, int height_org,
+                              void* stream) {
+  if (int rc = gm_batch_check(b, fb_check, alpha, beta, width_org, height_org)) return rc;
+  if (!models) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (int rc = gm_fit_check(model, rounds, thresh)) return rc;
+  Finish fin;
+  if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
+  if (!b->gm_slab) {  // records for every pair at the padded size (no original size needs more), held as floats
+    dalloc(b, &b->gm_slab, gmotion_work_bytes(1, std::min(b->p.width, OFDIS_GM_MAX_SIDE), std::min(b->p.height, OFDIS_GM_MAX_SIDE)) /
+                               sizeof(float), false);
+    if (int rc = dcommit(b)) return rc;
+  }
+  HIPCHK(launch_gmotion_level(b->flow[0] + fin.off, fb_check ? b->flow_rev[0] + fin.off : nullptr, count, fin.g, model, rounds,
+                              thresh, alpha, beta, models, stats, b->gm_slab, (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+int ofdis_batch_motion_compensate(ofdis_batch* b, int first_frame, int count, const double* models, float thresh, int fb_check,
+                                  float alpha, float beta, float* residual, uint8_t* label, int width_org, int height_org,
+                                  void* stream) {
+  if (int rc = gm_batch_check(b, fb_check, alpha, beta, width_org, height_org)) return rc;
+  if (!models || (!residual && !label)) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (int rc = gm_thresh_check(thresh)) return rc;
+  Finish fin;
+  if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
+  HIPCHK(launch_gmotion_compensate_level(b->flow[0] + fin.off, fb_check ? b->flow_rev[0] + fin.off : nullptr, models, count, fin.g,
+                                         thresh, alpha, beta, residual, label, (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
 }  // extern "C"

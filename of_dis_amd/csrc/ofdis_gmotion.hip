@@ -1,0 +1,408 @@
+// ofdis_gmotion.hip -- per-pair global (camera) motion models of a flow field and the motion-compensated flow (include/ofdis.h:
+// ofdis_global_motion / ofdis_motion_compensate on materialised arrays, ofdis_batch_global_motion /
+// ofdis_batch_motion_compensate straight from the level flows of a context): a translation or 6-parameter affine model per
+// pair by trimmed least squares, then the residual flow and an inlier / outlier / invalid label per pixel.
+//
+// Compiled under the exact contract only (-ffp-contract=off).  The twelve sums of a fit are exact 64-bit integers -- integer
+// addition is associative, so the mapping of pixels to lanes, workgroups and slab records cannot change them -- the solve is a
+// fixed sequence of separately rounded fp64 operations (the divisions are the compiler's correctly rounded expansion) and the
+// residual a fixed sequence of fp32 ones.  The level-flow kernels take flows and codes only from the helpers of
+// ofdis_batch_upsample_bidir / _upsample_frames (ofdis_upsample.h: upsample_at, fb_code on UpNeighbours), so they see the
+// bits the standalone kernels read from that function's materialised outputs: both routes give the same models and labels.
+//
+// Accumulate (one launch per round, all pairs): one lane owns a quad of 4 adjacent pixels of one row of one pair (QuadGrid,
+// xcd_frame_map: the workgroups of a pair stay on one XCD).  A lane's partial sums are reduced over its wavefront by
+// shuffles (64-bit values as two halves), over the workgroup's four wavefronts through LDS, and the workgroup writes ONE
+// 96-byte record into its own slab slot [pair][block] with plain stores.  No atomics, no flags, no waiting between
+// workgroups: the solve kernel, behind it on the stream, sums a pair's records with one wavefront and one lane solves.  The
+// next round's accumulate launch reads that model from device memory.
+//
+// Widths of the partial sums, with |X|, |Y| <= 8191 < 2^13 (OFDIS_GM_MAX_SIDE) and |qu|, |qv| <= 2^20 (OFDIS_GM_MAX_FLOW * 256):
+//   per lane (4 pixels)       n <= 4, |SX|, |SY| < 2^15, SXX, |SXY|, SYY < 2^28, |Squ|, |Sqv| <= 2^22: int32;
+//                             |SXqu| ... < 2^35: int64 (one product alone needs 34 bits)
+//   per workgroup (256 lanes) n <= 2^10, |SX|, |SY| < 2^23, |Squ|, |Sqv| <= 2^30: these five stay int32 through the wavefront
+//                             reduction and are widened in LDS; SXX, SXY, SYY < 2^36: widened before the wavefront reduction
+//   per pair                  every sum < W^2 * H * 2^20 <= 2^59 (include/ofdis.h): int64 never overflows
+#include "ofdis_upsample.h"
+
+namespace ofdis {
+
+typedef float gm_f4 __attribute__((ext_vector_type(4)));
+
+enum { GM_INLIER = 0, GM_OUTLIER = 1, GM_INVALID = 2 };
+enum { GM_NSUMS = 12 };  // n, SX, SY, SXX, SXY, SYY, Squ, SXqu, SYqu, Sqv, SXqv, SYqv: one slab record
+
+// what the accumulate and compensate kernels are launched with: the pairs [f0, f0 + n) of this launch
+struct GmArgs {
+  const double* models;  // [npairs][6]: the previous round's models (gated accumulate), the models to subtract (compensate)
+  long long* slab;       // [npairs][bpf][GM_NSUMS] (accumulate)
+  float2* residual;      // [npairs][H][W] or null (compensate)
+  uint8_t* label;        // [npairs][H][W] or null (compensate)
+  int f0, n;
+  int bpf;               // blocks per pair (QuadGrid)
+  float t2;              // thresh * thresh
+  int res_align;         // compensate: 16 / 8 / 4-byte stores of the residual
+  bool vec_label;        // ... and 4-byte stores of the labels
+};
+
+// the model of a pair in fp32 and the header's residual
+struct GmModel {
+  float a[6];
+};
+__device__ __forceinline__ GmModel gm_model(const double* models, int pair) {
+  GmModel m;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) m.a[k] = (float)models[(size_t)pair * 6 + k];
+  return m;
+}
+__device__ __forceinline__ float2 gm_residual(const GmModel& m, int X, int Y, float2 uv) {
+  const float xc = (float)X * 0.5f, yc = (float)Y * 0.5f;
+  const float mu = (m.a[0] + m.a[1] * xc) + m.a[2] * yc;
+  const float mv = (m.a[3] + m.a[4] * xc) + m.a[5] * yc;
+  return make_float2(uv.x - mu, uv.y - mv);
+}
+__device__ __forceinline__ bool gm_near(float2 r, float t2) { return r.x * r.x + r.y * r.y <= t2; }  // (NaN: false)
+// u and v finite and within OFDIS_GM_MAX_FLOW (NaN: false)
+__device__ __forceinline__ bool gm_in_range(float2 uv) { return fabsf(uv.x) <= 4096.0f && fabsf(uv.y) <= 4096.0f; }
+
+// the lane's pair (relative to the call) and quad; false: the whole workgroup has nothing to do (xcd_frame_map's padding)
+struct GmLane {
+  int pair, blk, x, y;
+  bool active;  // false: a lane past the last quad of the pair (x = y = 0, nothing is read)
+};
+__device__ __forceinline__ bool gm_lane(const GmArgs& a, int W, int H, GmLane& l) {
+  int lf;
+  xcd_frame_map(blockIdx.x, a.bpf, a.n, lf, l.blk);
+  if (lf >= a.n) return false;
+  l.pair = a.f0 + lf;
+  const int qpr = (W + 3) >> 2;
+  const int qi = l.blk * 256 + threadIdx.x;
+  l.active = qi < qpr * H;
+  l.y = l.active ? qi / qpr : 0;
+  l.x = l.active ? (qi - l.y * qpr) * 4 : 0;
+  return true;
+}
+
+__device__ __forceinline__ int gm_wave_sum(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ long long gm_wave_sum(long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, o);
+    const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)((unsigned long long)v >> 32), o);
+    v += (long long)(((unsigned long long)hi << 32) | lo);
+  }
+  return v;
+}
+
+// One round's sums of a workgroup's 256 quads into its slab record.  `flow(xx)` gives the flow at pixel (xx, y) of the lane's
+// row, `consistent(xx, uv)` whether the mask there is OFDIS_FB_CONSISTENT (asked only where the flow is in range and, GATED,
+// near).  GATED: the set is `near` under the model of the previous round.  Every lane of the workgroup gets here.
+template <bool GATED, class Flow, class Consistent>
+__device__ __forceinline__ void gm_block_sums(const GmArgs& a, const GmLane& l, int W, int H, Flow flow, Consistent consistent) {
+  __shared__ long long part[4][GM_NSUMS];
+  GmModel m;
+  if constexpr (GATED) m = gm_model(a.models, l.pair);
+  const int np = l.active ? min(4, W - l.x) : 0;
+  const int Y = 2 * l.y - (H - 1);
+  int n = 0, sx = 0, sy = 0, sxx = 0, sxy = 0, syy = 0, su = 0, sv = 0;
+  long long sxu = 0, syu = 0, sxv = 0, syv = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    if (i >= np) continue;
+    const int xx = l.x + i;
+    const float2 uv = flow(xx);
+    const int X = 2 * xx - (W - 1);
+    bool in = gm_in_range(uv);
+    if constexpr (GATED) in = in && gm_near(gm_residual(m, X, Y, uv), a.t2);
+    if (!in || !consistent(xx, uv)) continue;  // (the code last: the level-flow kernel computes it only for pixels still in)
+    const int qu = (int)rintf(uv.x * 256.0f), qv = (int)rintf(uv.y * 256.0f);
+    n += 1; sx += X; sy += Y; sxx += X * X; sxy += X * Y; syy += Y * Y;
+    su += qu; sv += qv;
+    sxu += (long long)X * qu; syu += (long long)Y * qu;
+    sxv += (long long)X * qv; syv += (long long)Y * qv;
+  }
+  long long s[GM_NSUMS];
+  s[0] = gm_wave_sum(n); s[1] = gm_wave_sum(sx); s[2] = gm_wave_sum(sy);
+  s[3] = gm_wave_sum((long long)sxx); s[4] = gm_wave_sum((long long)sxy); s[5] = gm_wave_sum((long long)syy);
+  s[6] = gm_wave_sum(su); s[7] = gm_wave_sum(sxu); s[8] = gm_wave_sum(syu);
+  s[9] = gm_wave_sum(sv); s[10] = gm_wave_sum(sxv); s[11] = gm_wave_sum(syv);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < GM_NSUMS; ++k) part[wave][k] = s[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < GM_NSUMS) {
+    const int k = threadIdx.x;
+    a.slab[((size_t)l.pair * a.bpf + l.blk) * GM_NSUMS + k] = (part[0][k] + part[1][k]) + (part[2][k] + part[3][k]);
+  }
+}
+
+// Materialised arrays: flow [npairs][H][W][2], mask [npairs][H][W] or null.
+template <bool GATED>
+__global__ __launch_bounds__(256) void gm_sums_frames_kernel(const float2* __restrict__ flow, const uint8_t* __restrict__ mask,
+                                                             int W, int H, GmArgs a) {
+  GmLane l;
+  if (!gm_lane(a, W, H, l)) return;
+  const size_t row = ((size_t)l.pair * H + l.y) * W;
+  const float2* fl = flow + row;
+  const uint8_t* mk = mask ? mask + row : nullptr;
+  gm_block_sums<GATED>(a, l, W, H, [&](int xx) { return fl[xx]; },
+                       [&](int xx, float2) { return !mk || mk[xx] == FB_CONSISTENT; });
+}
+
+// A context's level flows (UpGeom): the flow at the quad's pixels as ofdis_batch_upsample_frames writes it and, with `rev`
+// (fb_check = 1), the forward code of ofdis_batch_upsample_bidir recomputed as tfilter_level_kernel does.
+template <bool GATED>
+__global__ __launch_bounds__(256) void gm_sums_level_kernel(const float2* __restrict__ fw, const float2* __restrict__ rev,
+                                                            UpGeom g, float alpha, float beta, GmArgs a) {
+  GmLane l;
+  if (!gm_lane(a, g.wo, g.ho, l)) return;
+  const float2* fl = fw + (size_t)l.pair * g.plane();
+  const float2* other = rev ? rev + (size_t)l.pair * g.plane() : nullptr;
+  const UpRow ry = up_row(l.y + g.top, g);
+  gm_block_sums<GATED>(a, l, g.wo, g.ho, [&](int xx) { return upsample_at(fl, g, xx + g.left, ry); },
+                       [&](int xx, float2 uv) {
+                         return !other ||
+                                fb_code(uv.x, uv.y, xx, l.y, g.wo, g.ho, alpha, beta, UpNeighbours{other, g}) == FB_CONSISTENT;
+                       });
+}
+
+// The header's solve on the twelve sums `s`: the model a[6] and the status.
+__device__ __forceinline__ int gm_solve(const long long (&s)[GM_NSUMS], int model, double (&a)[6]) {
+#pragma unroll
+  for (int k = 0; k < 6; ++k) a[k] = 0.0;
+  if (s[0] == 0) return 2;  // OFDIS_GM_EMPTY
+  const double n = (double)s[0], Sx = (double)s[1], Sy = (double)s[2], Sxx = (double)s[3], Sxy = (double)s[4], Syy = (double)s[5];
+  const double Su[2] = {(double)s[6], (double)s[9]}, Sxu[2] = {(double)s[7], (double)s[10]}, Syu[2] = {(double)s[8], (double)s[11]};
+  if (model == 1 && s[0] >= 3) {
+    const double c00 = Sxx * Syy - Sxy * Sxy;
+    const double c01 = Sxy * Sy - Sx * Syy;
+    const double c02 = Sx * Sxy - Sxx * Sy;
+    const double c11 = n * Syy - Sy * Sy;
+    const double c12 = Sx * Sy - n * Sxy;
+    const double c22 = n * Sxx - Sx * Sx;
+    const double det = (n * c00 + Sx * c01) + Sy * c02;
+    if (det > 0.0) {
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        const double b0 = ((c00 * Su[c] + c01 * Sxu[c]) + c02 * Syu[c]) / det;
+        const double b1 = ((c01 * Su[c] + c11 * Sxu[c]) + c12 * Syu[c]) / det;
+        const double b2 = ((c02 * Su[c] + c12 * Sxu[c]) + c22 * Syu[c]) / det;
+        a[3 * c] = b0 / 256.0;
+        a[3 * c + 1] = b1 / 128.0;
+        a[3 * c + 2] = b2 / 128.0;
+      }
+      return 0;  // OFDIS_GM_OK_AFFINE
+    }
+  }
+  a[0] = (Su[0] / n) / 256.0;
+  a[3] = (Su[1] / n) / 256.0;
+  return 1;  // OFDIS_GM_TRANSLATION
+}
+
+// One wavefront per pair: the pair's slab records summed (lanes stride over the records, then the wavefront reduction), lane 0
+// solves and writes.  ROUND0 writes always (an empty set: the zero model, OFDIS_GM_EMPTY); a later round with an empty set
+// leaves the previous round's model, set size and status as they are.
+template <bool ROUND0>
+__global__ __launch_bounds__(64) void gm_solve_kernel(const long long* __restrict__ slab, int bpf, int model,
+                                                      double* __restrict__ models, long long* __restrict__ stats) {
+  const int pair = blockIdx.x;
+  const long long* rec = slab + (size_t)pair * bpf * GM_NSUMS;
+  long long s[GM_NSUMS];
+#pragma unroll
+  for (int k = 0; k < GM_NSUMS; ++k) s[k] = 0;
+  for (int r = threadIdx.x; r < bpf; r += 64) {
+#pragma unroll
+    for (int k = 0; k < GM_NSUMS; ++k) s[k] += rec[(size_t)r * GM_NSUMS + k];
+  }
+#pragma unroll
+  for (int k = 0; k < GM_NSUMS; ++k) s[k] = gm_wave_sum(s[k]);
+  if (threadIdx.x != 0) return;
+  if (!ROUND0 && s[0] == 0) return;
+  double a[6];
+  const int status = gm_solve(s, model, a);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) models[(size_t)pair * 6 + k] = a[k];
+  if (!stats) return;
+  if (ROUND0) stats[(size_t)pair * 3] = s[0];
+  stats[(size_t)pair * 3 + 1] = s[0];
+  stats[(size_t)pair * 3 + 2] = status;
+}
+
+// ------------------------------------------------------------------------------------ compensate
+// The quad's residuals and labels.  The residual may alias the flow: a lane reads its own four pixels before it writes them.
+template <class Flow, class Consistent>
+__device__ __forceinline__ void gm_compensate_quad(const GmArgs& a, const GmLane& l, int W, int H, Flow flow, Consistent consistent) {
+  const GmModel m = gm_model(a.models, l.pair);
+  const int np = min(4, W - l.x);
+  const int Y = 2 * l.y - (H - 1);
+  float2 r[4];
+  uint8_t lab[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    r[i] = make_float2(0.0f, 0.0f);
+    lab[i] = GM_INVALID;
+    if (i >= np) continue;
+    const int xx = l.x + i;
+    const float2 uv = flow(xx);
+    r[i] = gm_residual(m, 2 * xx - (W - 1), Y, uv);
+    if (gm_in_range(uv) && consistent(xx, uv)) lab[i] = gm_near(r[i], a.t2) ? GM_INLIER : GM_OUTLIER;
+  }
+  const size_t px0 = ((size_t)l.pair * H + l.y) * W + l.x;  // the quad's first pixel in a [pairs][H][W] array
+  if (a.residual) {
+    float2* o = a.residual + px0;
+    if (a.res_align >= 16) {  // (W even and the array 16-byte aligned: pixels px0, px0 + 2 start a 16-byte unit)
+#pragma unroll
+      for (int i = 0; i < 4; i += 2) {
+        if (i + 1 < np) __builtin_nontemporal_store((gm_f4){r[i].x, r[i].y, r[i + 1].x, r[i + 1].y}, reinterpret_cast<gm_f4*>(o + i));
+        else if (i < np) o[i] = r[i];
+      }
+    } else if (a.res_align >= 8) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (i < np) o[i] = r[i];
+    } else {
+      float* of = reinterpret_cast<float*>(o);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (i < np) { of[2 * i] = r[i].x; of[2 * i + 1] = r[i].y; }
+    }
+  }
+  if (a.label) {
+    uint8_t* lo = a.label + px0;
+    if (a.vec_label && np == 4) {
+      const unsigned wd = (unsigned)lab[0] | ((unsigned)lab[1] << 8) | ((unsigned)lab[2] << 16) | ((unsigned)lab[3] << 24);
+      __builtin_nontemporal_store(wd, reinterpret_cast<unsigned*>(lo));
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (i < np) lo[i] = lab[i];
+    }
+  }
+}
+
+// (no __restrict__ on the flow: the residual may be the same array)
+__global__ __launch_bounds__(256) void gm_compensate_frames_kernel(const float2* flow, const uint8_t* __restrict__ mask, int W, int H,
+                                                                   GmArgs a) {
+  GmLane l;
+  if (!gm_lane(a, W, H, l) || !l.active) return;
+  const size_t row = ((size_t)l.pair * H + l.y) * W;
+  const float2* fl = flow + row;
+  const uint8_t* mk = mask ? mask + row : nullptr;
+  gm_compensate_quad(a, l, W, H, [&](int xx) { return fl[xx]; }, [&](int xx, float2) { return !mk || mk[xx] == FB_CONSISTENT; });
+}
+
+__global__ __launch_bounds__(256) void gm_compensate_level_kernel(const float2* __restrict__ fw, const float2* __restrict__ rev,
+                                                                  UpGeom g, float alpha, float beta, GmArgs a) {
+  GmLane l;
+  if (!gm_lane(a, g.wo, g.ho, l) || !l.active) return;
+  const float2* fl = fw + (size_t)l.pair * g.plane();
+  const float2* other = rev ? rev + (size_t)l.pair * g.plane() : nullptr;
+  const UpRow ry = up_row(l.y + g.top, g);
+  gm_compensate_quad(a, l, g.wo, g.ho, [&](int xx) { return upsample_at(fl, g, xx + g.left, ry); },
+                     [&](int xx, float2 uv) {
+                       return !other ||
+                              fb_code(uv.x, uv.y, xx, l.y, g.wo, g.ho, alpha, beta, UpNeighbours{other, g}) == FB_CONSISTENT;
+                     });
+}
+
+// ------------------------------------------------------------------------------------ launchers
+size_t gmotion_work_bytes(int npairs, int w, int h) {
+  return (size_t)npairs * quad_grid(npairs, w, h).bpf * GM_NSUMS * sizeof(long long);
+}
+
+// the launches of one pass over all pairs: `launch(GmArgs, blocks)` once per chunk of pairs
+template <class Launch>
+static hipError_t gm_chunks(GmArgs a, int npairs, int w, int h, Launch launch) {
+  const QuadGrid g = quad_grid(npairs, w, h);
+  a.bpf = g.bpf;
+  for (a.f0 = 0; a.f0 < npairs; a.f0 += g.chunk) {
+    a.n = std::min(g.chunk, npairs - a.f0);
+    launch(a, dim3(quad_blocks(a.n, g.bpf)));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// `rounds` times (accumulate, solve) on the stream; `sums(gated, GmArgs, blocks)` launches one accumulate kernel
+template <class Sums>
+static hipError_t gm_rounds(int npairs, int w, int h, int model, int rounds, float thresh, double* models, long long* stats,
+                            void* work, hipStream_t s, Sums sums) {
+  GmArgs a{};
+  a.models = models;
+  a.slab = (long long*)work;
+  a.t2 = thresh * thresh;
+  const int bpf = quad_grid(npairs, w, h).bpf;
+  for (int r = 0; r < rounds; ++r) {
+    const bool gated = r > 0;
+    hipError_t e = gm_chunks(a, npairs, w, h, [&](const GmArgs& c, dim3 blocks) { sums(gated, c, blocks); });
+    if (e != hipSuccess) return e;
+    if (gated)
+      hipLaunchKernelGGL(gm_solve_kernel<false>, dim3(npairs), dim3(64), 0, s, (const long long*)work, bpf, model, models, stats);
+    else
+      hipLaunchKernelGGL(gm_solve_kernel<true>, dim3(npairs), dim3(64), 0, s, (const long long*)work, bpf, model, models, stats);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+hipError_t launch_gmotion_frames(const float* flow, const uint8_t* mask, int npairs, int w, int h, int model, int rounds,
+                                 float thresh, double* models, long long* stats, void* work, hipStream_t s) {
+  const float2* fl = (const float2*)flow;
+  return gm_rounds(npairs, w, h, model, rounds, thresh, models, stats, work, s, [&](bool gated, const GmArgs& a, dim3 blocks) {
+    if (gated)
+      hipLaunchKernelGGL(gm_sums_frames_kernel<true>, blocks, dim3(256), 0, s, fl, mask, w, h, a);
+    else
+      hipLaunchKernelGGL(gm_sums_frames_kernel<false>, blocks, dim3(256), 0, s, fl, mask, w, h, a);
+  });
+}
+
+hipError_t launch_gmotion_level(const float* fw, const float* rev, int npairs, UpGeom ug, int model, int rounds, float thresh,
+                                float alpha, float beta, double* models, long long* stats, void* work, hipStream_t s) {
+  const float2 *ff = (const float2*)fw, *fr = (const float2*)rev;
+  return gm_rounds(npairs, ug.wo, ug.ho, model, rounds, thresh, models, stats, work, s,
+                   [&](bool gated, const GmArgs& a, dim3 blocks) {
+                     if (gated)
+                       hipLaunchKernelGGL(gm_sums_level_kernel<true>, blocks, dim3(256), 0, s, ff, fr, ug, alpha, beta, a);
+                     else
+                       hipLaunchKernelGGL(gm_sums_level_kernel<false>, blocks, dim3(256), 0, s, ff, fr, ug, alpha, beta, a);
+                   });
+}
+
+// the compensate kernels' store widths: see GmArgs
+static GmArgs gm_compensate_args(const double* models, float thresh, float* residual, uint8_t* label, int w) {
+  GmArgs a{};
+  a.models = models;
+  a.residual = (float2*)residual;
+  a.label = label;
+  a.t2 = thresh * thresh;
+  const uintptr_t ra = (uintptr_t)residual;
+  a.res_align = (w & 1) == 0 && (ra & 15) == 0 ? 16 : ((ra & 7) == 0 ? 8 : 4);
+  a.vec_label = (w & 3) == 0 && ((uintptr_t)label & 3) == 0;
+  return a;
+}
+
+hipError_t launch_gmotion_compensate_frames(const float* flow, const uint8_t* mask, const double* models, int npairs, int w, int h,
+                                            float thresh, float* residual, uint8_t* label, hipStream_t s) {
+  return gm_chunks(gm_compensate_args(models, thresh, residual, label, w), npairs, w, h, [&](const GmArgs& a, dim3 blocks) {
+    hipLaunchKernelGGL(gm_compensate_frames_kernel, blocks, dim3(256), 0, s, (const float2*)flow, mask, w, h, a);
+  });
+}
+
+hipError_t launch_gmotion_compensate_level(const float* fw, const float* rev, const double* models, int npairs, UpGeom ug,
+                                           float thresh, float alpha, float beta, float* residual, uint8_t* label, hipStream_t s) {
+  return gm_chunks(gm_compensate_args(models, thresh, residual, label, ug.wo), npairs, ug.wo, ug.ho,
+                   [&](const GmArgs& a, dim3 blocks) {
+                     hipLaunchKernelGGL(gm_compensate_level_kernel, blocks, dim3(256), 0, s, (const float2*)fw, (const float2*)rev,
+                                        ug, alpha, beta, a);
+                   });
+}
+
+}  // namespace ofdis

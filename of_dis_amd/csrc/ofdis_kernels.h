@@ -253,6 +253,20 @@ hipError_t launch_tfilter_frames(const uint8_t* frames, const float* flow_fw, co
 // launch_upsample_bidir computes them
 hipError_t launch_tfilter_level(const uint8_t* frames, const float* fw, const float* rev, uint8_t* out, uint8_t* support,
                                 int npairs, UpGeom g, int noc, float wn, float tau, float alpha, float beta, hipStream_t s);
+// global motion models and motion-compensated flow (include/ofdis.h: ofdis_global_motion; ofdis_gmotion.hip).  `work`: one
+// record of sums per workgroup and pair, gmotion_work_bytes(npairs, w, h) bytes; `rounds` x (accumulate, solve) on the stream.
+// On materialised arrays: flow [npairs][h][w][2], mask [npairs][h][w] or null, models [npairs][6], stats [npairs][3] or null
+size_t gmotion_work_bytes(int npairs, int w, int h);
+hipError_t launch_gmotion_frames(const float* flow, const uint8_t* mask, int npairs, int w, int h, int model, int rounds,
+                                 float thresh, double* models, long long* stats, void* work, hipStream_t s);
+hipError_t launch_gmotion_compensate_frames(const float* flow, const uint8_t* mask, const double* models, int npairs, int w, int h,
+                                            float thresh, float* residual, uint8_t* label, hipStream_t s);
+// straight from the level flows of npairs pairs: the flow as launch_upsample_crop computes it; with `rev` the forward mask of
+// launch_upsample_bidir, without (null) no mask
+hipError_t launch_gmotion_level(const float* fw, const float* rev, int npairs, UpGeom g, int model, int rounds, float thresh,
+                                float alpha, float beta, double* models, long long* stats, void* work, hipStream_t s);
+hipError_t launch_gmotion_compensate_level(const float* fw, const float* rev, const double* models, int npairs, UpGeom g,
+                                           float thresh, float alpha, float beta, float* residual, uint8_t* label, hipStream_t s);
 
 // ---- stereo-depth mode (SELECTMODE=2; ofdis_de.hip)
 struct DeSystemArgs {

@@ -1,0 +1,536 @@
+"""-m gpu: global motion models and motion-compensated flow (include/ofdis.h: ofdis_global_motion / ofdis_motion_compensate on
+materialised arrays, ofdis_batch_global_motion / ofdis_batch_motion_compensate straight from the level flows of a context).
+
+The standalone kernels are compared bit for bit -- models as raw 64-bit patterns, stats, residual (NaN payloads included) and
+label -- with of_dis_amd/gmotion.py, the header's definition in numpy; the fused kernels bit for bit with the standalone ones
+applied to the outputs of ofdis_batch_upsample_bidir (fb_check = 1) or ofdis_batch_upsample_frames (fb_check = 0).  Conditions
+on the generated inputs are checked on the restatement or the standalone result, never on the kernel under test."""
+import functools
+import math
+
+import numpy as np
+import pytest
+
+import gen_synth
+from of_dis_amd import gmotion
+from of_dis_amd.gmotion import (GM_AFFINE, GM_EMPTY, GM_INLIER, GM_INVALID, GM_OK_AFFINE, GM_OUTLIER, GM_TRANSLATION,
+                                GM_TRANSLATION_ONLY, global_motion_ref, motion_compensate_ref)
+from of_dis_amd.params import oppoint, padded_size
+
+pytestmark = pytest.mark.gpu
+_f32 = np.float32
+INVALID = -1
+
+
+def assert_bits_equal(got, want, what):
+    """arrays of one dtype compared as raw bit patterns"""
+    assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape, got.dtype, want.dtype)
+    bits = {1: np.uint8, 4: np.uint32, 8: np.uint64}[got.dtype.itemsize]
+    g, w = np.ascontiguousarray(got).view(bits), np.ascontiguousarray(want).view(bits)
+    if not np.array_equal(g, w):
+        bad = np.argwhere(g != w)
+        i = tuple(bad[0])
+        raise AssertionError(f"{what}: {len(bad)} of {g.size} elements differ; first at {i}: {got[i]!r} ({g[i]:#x}) vs "
+                             f"{want[i]!r} ({w[i]:#x})")
+
+
+def assert_fit_equal(got, want, what):
+    assert_bits_equal(got[0], want[0], what + ", models")
+    assert_bits_equal(got[1], want[1], what + ", stats")
+
+
+def assert_compensated_equal(got, want, what):
+    assert_bits_equal(got[0], want[0], what + ", residual")
+    assert_bits_equal(got[1], want[1], what + ", label")
+
+
+# ------------------------------------------------------------------ 1. standalone kernels against the restatement
+# (300, 70): several workgroups per pair, so the slab sum is real; (8192, 2): |X| at its bound
+SIZES = [(37, 11), (64, 16), (1, 9), (13, 1), (1, 1), (6, 5), (33, 7), (257, 3), (300, 70), (8192, 2)]
+# (model, rounds, thresh)
+FITS = [(GM_AFFINE, 1, 1.0), (GM_AFFINE, 2, 0.5), (GM_AFFINE, 4, 1.0), (GM_AFFINE, 4, 1e-3), (GM_TRANSLATION_ONLY, 1, 0.5),
+        (GM_TRANSLATION_ONLY, 2, 1.0), (GM_TRANSLATION_ONLY, 4, 0.5), (GM_TRANSLATION_ONLY, 2, 1e-3)]
+JUST_ABOVE = np.nextafter(_f32(4096.0), _f32(np.inf))
+
+
+@functools.lru_cache(maxsize=None)
+def _random_case(n, w, h, kind):
+    """npairs = n.  "smooth": an affine camera flow of a few pixels per pair plus noise of 0.3 px, a fifth of the pixels with
+    flows of 3 px of their own (what the gate removes) and some that stay put.  "wild": the same with large, infinite, NaN
+    (default, with a payload, negative), image-sized values and values of exactly +-4096 and just above mixed in, as _random_case
+    of tests/test_gpu_tfilter.py mixes them.  Masks with all three codes."""
+    rng = np.random.default_rng(w * 1000 + h * 10 + 100 * n + (5 if kind == "wild" else 0))
+    F = np.empty((n, h, w, 2), _f32)
+    for k in range(n):
+        a = rng.normal(0.0, 1.0, 6) * np.array([3.0, 0.02, 0.02, 3.0, 0.02, 0.02])
+        F[k] = (gmotion.model_flow(a, w, h) + rng.normal(0.0, 0.3, (h, w, 2))).astype(_f32)
+    own = rng.random((n, h, w)) < 0.2
+    F[own] = (rng.standard_normal((int(own.sum()), 2)) * 3).astype(_f32)
+    F[rng.random((n, h, w)) < 0.05] = 0.0
+    if kind == "wild":
+        pick = rng.random((n, h, w, 2))
+        F[pick < 0.04] = (rng.standard_normal(int((pick < 0.04).sum())) * 1e4).astype(_f32)
+        F[(pick >= 0.04) & (pick < 0.05)] = np.inf
+        F[(pick >= 0.05) & (pick < 0.06)] = -np.inf
+        F[(pick >= 0.06) & (pick < 0.07)] = np.nan
+        F[(pick >= 0.07) & (pick < 0.08)] = np.array([0x7FC12345], np.uint32).view(_f32)[0]
+        F[(pick >= 0.08) & (pick < 0.09)] = np.array([0xFFC00001], np.uint32).view(_f32)[0]
+        sized = (pick >= 0.09) & (pick < 0.10)
+        F[sized] = (rng.uniform(-2, 2, int(sized.sum())) * max(w, h)).astype(_f32)
+        F[(pick >= 0.130) & (pick < 0.133)] = 4096.0      # (rare: a valid flow of 4096 px pulls the whole fit)
+        F[(pick >= 0.133) & (pick < 0.136)] = -4096.0
+        F[(pick >= 0.14) & (pick < 0.15)] = JUST_ABOVE
+        F[(pick >= 0.15) & (pick < 0.16)] = -JUST_ABOVE
+    M = rng.integers(0, 3, (n, h, w), dtype=np.uint8)
+    M[rng.random((n, h, w)) < 0.5] = 0
+    return F, M
+
+
+@pytest.mark.parametrize("w,h", SIZES, ids=[f"{w}x{h}" for w, h in SIZES])
+@pytest.mark.parametrize("kind", ["smooth", "wild"])
+def test_standalone_matches_the_definition(gpu, w, h, kind):
+    gated_away = 0
+    for npairs in (1, 3):
+        flow, mask = _random_case(npairs, w, h, kind)
+        for mk in (mask, None):
+            for model, rounds, thresh in FITS:
+                what = f"{w}x{h}, {kind}, {npairs} pairs, mask {mk is not None}, model {model}, rounds {rounds}, thresh {thresh}"
+                want = global_motion_ref(flow, mk, model=model, rounds=rounds, thresh=thresh)
+                assert_fit_equal(gpu.global_motion(flow, mk, model=model, rounds=rounds, thresh=thresh), want, what)
+                if rounds > 1:
+                    gated_away += int((want[1][:, 1] < want[1][:, 0]).sum())
+                if rounds in (1, 4):   # the pass with the models just compared
+                    wantc = motion_compensate_ref(flow, want[0], mk, thresh=thresh)
+                    assert_compensated_equal(gpu.motion_compensate(flow, want[0], mk, thresh=thresh), wantc, what)
+    if kind == "smooth" and w * h >= 9:   # the gate really removes pixels in this case (condition on the restatement)
+        assert gated_away > 0
+
+
+def test_either_output_alone_and_the_residual_in_place(gpu):
+    flow, mask = _random_case(3, 37, 11, "wild")
+    models, _ = global_motion_ref(flow, mask, rounds=2, thresh=1.0)
+    want = motion_compensate_ref(flow, models, mask, thresh=1.0)
+    assert np.isnan(want[0]).any() and np.isinf(want[0]).any() and len(np.unique(want[1])) == 3
+    res, none = gpu.motion_compensate(flow, models, mask, thresh=1.0, label=False)
+    assert none is None
+    assert_bits_equal(res, want[0], "label = NULL")
+    none, label = gpu.motion_compensate(flow, models, mask, thresh=1.0, residual=False)
+    assert none is None
+    assert_bits_equal(label, want[1], "residual = NULL")
+    for w, h in ((37, 11), (64, 16)):   # 4-byte and 16-byte stores over the array they were read from
+        flow, mask = _random_case(3, w, h, "wild")
+        models, _ = global_motion_ref(flow, mask, rounds=2, thresh=1.0)
+        assert_compensated_equal(gpu.motion_compensate(flow, models, mask, thresh=1.0, in_place=True),
+                                 motion_compensate_ref(flow, models, mask, thresh=1.0), f"residual aliases flow, {w}x{h}")
+    # stats = NULL: the same models
+    flow, mask = _random_case(3, 64, 16, "smooth")
+    npairs, h, w = flow.shape[:3]
+    df, dm, dmod = gpu.Dev(flow), gpu.Dev(mask), gpu.Dev(nbytes=npairs * 48)
+    wb = gpu.lib().ofdis_global_motion_work_bytes(npairs, w, h)
+    dwork = gpu.Dev(nbytes=wb)
+    gpu.check(gpu.lib().ofdis_global_motion(df.ptr, dm.ptr, npairs, w, h, GM_AFFINE, 3, 1.0, dmod.ptr, None, dwork.ptr, wb, None))
+    gpu.check(gpu.lib().ofdis_sync(None))
+    assert_bits_equal(dmod.get((npairs, 6), np.float64), global_motion_ref(flow, mask, rounds=3, thresh=1.0)[0], "stats = NULL")
+
+
+def test_more_pairs_than_xcds(gpu):
+    """10 pairs: the pair-to-XCD mapping with its padded last group, every pair with its own records and its own model"""
+    for w, h in ((33, 7), (300, 70)):
+        flow, mask = _random_case(10, w, h, "smooth")
+        want = global_motion_ref(flow, mask, rounds=3, thresh=1.0)
+        assert len({m.tobytes() for m in want[0]}) == 10
+        assert_fit_equal(gpu.global_motion(flow, mask, rounds=3, thresh=1.0), want, f"10 pairs {w}x{h}")
+        assert_compensated_equal(gpu.motion_compensate(flow, want[0], mask, thresh=1.0),
+                                 motion_compensate_ref(flow, want[0], mask, thresh=1.0), f"10 pairs {w}x{h}")
+
+
+def test_the_largest_products(gpu):
+    """8192 x 2 with |u| = 4096 everywhere: X * qu reaches 8191 * 2^20, past 32 bits, in every lane"""
+    w, h = 8192, 2
+    flow = np.empty((2, h, w, 2), _f32)
+    flow[0, ..., 0], flow[0, ..., 1] = 4096.0, -4096.0
+    flow[1, :, : w // 2, 0], flow[1, :, w // 2:, 0] = -4096.0, 4096.0    # SXqu = sum |X| * 2^20
+    flow[1, ..., 1] = np.where(np.arange(w) % 2 == 0, 4096.0, -4096.0)[None, :]
+    for model in (GM_AFFINE, GM_TRANSLATION_ONLY):
+        want = global_motion_ref(flow, None, model=model, rounds=2, thresh=1.0)
+        assert_fit_equal(gpu.global_motion(flow, None, model=model, rounds=2, thresh=1.0), want, f"model {model}")
+    s = gmotion.sums(flow[1], np.ones((h, w), bool))
+    assert s[7] == 2 * sum(abs(2 * x - (w - 1)) for x in range(w)) << 20 > 1 << 45
+
+
+def _keep_only(shape, sel):
+    mask = np.full(shape, 1, np.uint8)
+    mask[sel] = 0
+    return mask
+
+
+def test_degenerate_sets(gpu):
+    """the degenerate cases of tests/test_gmotion_ref.py on the kernels: collinear sets (det == 0.0 exactly: translation), a
+    single pixel, an all-masked frame and a set that empties -- one pair each of ONE call, so that the pairs take different paths
+    side by side"""
+    import test_gmotion_ref as R
+    H, W = R.H, R.W
+    flow = np.repeat(R.block_scene()[0], 5, axis=0)
+    sel = np.zeros((5, H, W), bool)
+    sel[0, 40, :] = True
+    sel[1, np.arange(H), np.arange(H) + 17] = True
+    sel[2, 7, 200] = True
+    sel[4] = True          # pair 3: nothing; pair 4: everything
+    mask = _keep_only((5, H, W), sel)
+    mask[3] = np.random.default_rng(3).integers(1, 3, (H, W), dtype=np.uint8)
+    want = global_motion_ref(flow, mask, rounds=3, thresh=1.0)
+    assert want[1][:, 2].tolist() == [GM_TRANSLATION, GM_TRANSLATION, GM_TRANSLATION, GM_EMPTY, GM_OK_AFFINE]
+    assert want[1][:, 0].tolist() == [W, H, 1, 0, H * W]
+    assert_fit_equal(gpu.global_motion(flow, mask, rounds=3, thresh=1.0), want, "degenerate sets")
+    wantc = motion_compensate_ref(flow, want[0], mask, thresh=1.0)
+    assert (wantc[1][3] == GM_INVALID).all()
+    assert_compensated_equal(gpu.motion_compensate(flow, want[0], mask, thresh=1.0), wantc, "degenerate sets")
+    # a set that empties at round 1 keeps round 0's model, set size and status (next to a pair that goes on)
+    two = np.zeros((2, 16, 24, 2), _f32)
+    two[:, :, :12, 0], two[:, :, 12:, 0] = -20.0, 20.0
+    two[1, :, :, 0] = 1.5
+    want = global_motion_ref(two, None, rounds=4, thresh=1e-3)
+    first = global_motion_ref(two, None, rounds=1, thresh=1e-3)
+    assert np.array_equal(want[0][0], first[0][0]) and want[1][0].tolist() == [384, 384, GM_OK_AFFINE]
+    assert (motion_compensate_ref(two, first[0], None, thresh=1e-3)[1][0] == GM_OUTLIER).all()
+    assert_fit_equal(gpu.global_motion(two, None, rounds=4, thresh=1e-3), want, "a set that empties")
+
+
+@pytest.mark.parametrize("w,h", [(64, 16), (37, 11), (6, 5)], ids=["64x16", "37x11", "6x5"])
+def test_unaligned_outputs_take_narrower_stores_with_the_same_bytes(gpu, w, h):
+    """the residual one element (4 bytes) and the labels one byte into their buffers: the same bytes as the aligned call, and the
+    guard bytes around both stay"""
+    npairs = 3
+    flow, mask = _random_case(npairs, w, h, "wild")
+    models, _ = global_motion_ref(flow, mask, rounds=2, thresh=1.0)
+    want = motion_compensate_ref(flow, models, mask, thresh=1.0)
+    rbytes, lbytes = flow.nbytes, npairs * h * w
+    devs = [gpu.Dev(x) for x in (flow, mask, models)]
+    for roff, loff in ((260, 257), (264, 258), (272, 260)):   # residual 4 / 8 / 16-byte aligned, labels 1 / 2 / 4-byte aligned
+        dr = gpu.Dev(np.full(rbytes + 2 * roff, 0xAB, np.uint8))
+        dl = gpu.Dev(np.full(lbytes + 2 * loff, 0xAB, np.uint8))
+        gpu.check(gpu.lib().ofdis_motion_compensate(devs[0].ptr, devs[1].ptr, devs[2].ptr, npairs, w, h, 1.0, dr.ptr + roff,
+                                                    dl.ptr + loff, None))
+        gpu.check(gpu.lib().ofdis_sync(None))
+        r, l = dr.get((rbytes + 2 * roff,), np.uint8), dl.get((lbytes + 2 * loff,), np.uint8)
+        for buf, off, n in ((r, roff, rbytes), (l, loff, lbytes)):
+            assert (buf[:off] == 0xAB).all() and (buf[off + n:] == 0xAB).all(), (roff, loff)
+        assert_bits_equal(r[roff:roff + rbytes].copy().view(_f32).reshape(flow.shape), want[0], f"residual at offset {roff}")
+        assert_bits_equal(l[loff:loff + lbytes].reshape(npairs, h, w), want[1], f"labels at offset {loff}")
+
+
+# ------------------------------------------------------------------ 2. the block scene
+def test_block_scene_on_the_kernel(gpu):
+    """the scene of tests/test_gmotion_ref.py through the standalone kernel: the restatement's bits, which carry its < 0.01 px"""
+    import test_gmotion_ref as R
+    flow, _ = R.block_scene()
+    for rounds in (1, 3, 5):
+        want = global_motion_ref(flow, None, rounds=rounds, thresh=1.0)
+        assert_fit_equal(gpu.global_motion(flow, None, rounds=rounds, thresh=1.0), want, f"block scene, rounds {rounds}")
+        if rounds == 3:
+            assert max(R.errors(want[0][0])) < 0.01
+            wantc = motion_compensate_ref(flow, want[0], None, thresh=1.0)
+            assert (wantc[1][0][R.BLOCK] == GM_OUTLIER).all() and (wantc[1] == GM_INLIER).sum() == want[1][0, 1]
+            assert_compensated_equal(gpu.motion_compensate(flow, want[0], None, thresh=1.0), wantc, "block scene")
+
+
+# ------------------------------------------------------------------ 3. fused kernels against the standalone ones
+CLIP_STEP = 0.15  # of gen_synth's flow (up to 12 px) per frame: at most 1.8 px per pair
+
+
+@functools.lru_cache(maxsize=None)
+def _clip(w, h, noc, nframes, seed=6200):
+    """nframes frames of one scene in smooth motion, as _clip of tests/test_gpu_tfilter.py makes them"""
+    frames = [gen_synth.make_pair(w, h, seed, noc)[0]]
+    frames += [gen_synth.make_pair(w, h, seed, noc, flow_scale=CLIP_STEP * k)[1] for k in range(1, nframes)]
+    return np.ascontiguousarray(np.stack(frames))
+
+
+def _context(gpu, clip, kind="seq_rev", opp=2, contract=0, pipeline=1):
+    """a context over the pairs of the clip [n + 1][h][w] (+ [3]), built and run.  kind: "plain" and "reverse" hold every pair's
+    two frames (A = clip[:-1], B = clip[1:]), "seq_rev" is SEQUENCE | REVERSE.  Returns (context, the device arrays it reads)."""
+    n, h, w = clip.shape[0] - 1, clip.shape[1], clip.shape[2]
+    noc = 1 if clip.ndim == 3 else 3
+    p = oppoint(opp, w, h, noc=noc, verbosity=0)
+    p.width, p.height = padded_size(w, h, p.sc_f)
+    old = gpu.set_tuning(contract=contract)
+    try:
+        if kind == "seq_rev":
+            devs = [gpu.Dev(clip)]
+            b = gpu.Batch(p, n, sequence=True, reverse=True)
+        else:
+            devs = [gpu.Dev(clip[:-1]), gpu.Dev(clip[1:])]
+            b = gpu.Batch(p, n, reverse=kind == "reverse")
+        if pipeline > 1:
+            b.set_pipeline(pipeline)
+        if kind == "seq_rev":
+            b.build_pyramids_u8_seq(devs[0].ptr, w, h)
+        else:
+            b.build_pyramids_u8(devs[0].ptr, devs[1].ptr, w, h)
+        b.run()
+    finally:
+        gpu.restore_tuning(old)
+    return b, devs
+
+
+FUSED_FITS = [(GM_AFFINE, 3, 1.0), (GM_TRANSLATION_ONLY, 2, 0.5)]
+
+# (kind, noc, op, w, h, n pairs, first, count, pipeline, contract, alpha, beta)
+FUSED_CASES = [
+    pytest.param("seq_rev", 1, 2, 256, 112, 3, 0, 3, 1, 0, 0.01, 0.5, id="gray-op2-scl1"),
+    pytest.param("seq_rev", 3, 2, 256, 112, 3, 0, 3, 1, 0, 0.01, 0.5, id="rgb-op2-scl1"),
+    pytest.param("seq_rev", 1, 4, 256, 112, 2, 0, 2, 1, 0, 0.01, 0.5, id="gray-op4-scl0"),
+    pytest.param("reverse", 3, 4, 256, 112, 2, 0, 2, 1, 0, 0.01, 0.5, id="rgb-op4-scl0-reverse"),
+    pytest.param("seq_rev", 1, 2, 250, 110, 3, 0, 3, 1, 0, 0.01, 0.5, id="gray-crop-250x110"),
+    pytest.param("seq_rev", 3, 2, 243, 107, 2, 0, 2, 1, 0, 0.01, 0.5, id="rgb-crop-243x107"),
+    pytest.param("reverse", 1, 2, 243, 107, 3, 0, 3, 1, 0, 0.01, 0.5, id="gray-crop-243x107-reverse"),
+    pytest.param("plain", 1, 2, 250, 110, 3, 0, 3, 1, 0, 0.01, 0.5, id="gray-crop-250x110-plain"),
+    pytest.param("plain", 3, 2, 256, 112, 3, 1, 2, 1, 0, 0.01, 0.5, id="rgb-plain-subrange-1-2-of-3"),
+    pytest.param("seq_rev", 1, 2, 256, 112, 5, 1, 3, 1, 0, 0.01, 0.5, id="gray-subrange-1-3-of-5"),
+    pytest.param("reverse", 3, 2, 250, 110, 4, 3, 1, 1, 0, 0.01, 0.5, id="rgb-subrange-3-1-of-4"),
+    pytest.param("seq_rev", 1, 2, 256, 112, 16, 0, 16, 2, 0, 0.01, 0.5, id="gray-16-pairs-pipelined"),
+    pytest.param("seq_rev", 1, 2, 256, 112, 3, 0, 3, 1, 1, 0.01, 0.5, id="gray-fused-contract"),
+    pytest.param("reverse", 3, 2, 256, 112, 2, 0, 2, 1, 1, 0.01, 0.5, id="rgb-fused-contract"),
+    pytest.param("plain", 1, 2, 256, 112, 3, 0, 3, 1, 1, 0.01, 0.5, id="gray-plain-fused-contract"),
+    pytest.param("seq_rev", 1, 2, 256, 112, 3, 0, 3, 1, 0, 0.0, 0.0, id="gray-alpha0-beta0"),
+]
+
+
+@pytest.mark.parametrize("kind,noc,opp,w,h,n,first,count,pipeline,contract,alpha,beta", FUSED_CASES)
+def test_fused_matches_standalone(gpu, kind, noc, opp, w, h, n, first, count, pipeline, contract, alpha, beta):
+    """fb_check = 0 against the standalone calls on upsample_frames' output with mask NULL; fb_check = 1 (contexts with the
+    reverse direction) against them on out_fw and mask_fw of upsample_bidir"""
+    clip = _clip(w, h, noc, n + 1)
+    b, devs = _context(gpu, clip, kind, opp, contract, pipeline)
+    fused = {}
+    try:
+        bytes_before = b.device_bytes()
+        for fb in ((0, 1) if kind != "plain" else (0,)):
+            for model, rounds, thresh in FUSED_FITS:
+                fit = b.global_motion(w, h, model=model, rounds=rounds, thresh=thresh, fb_check=fb, first=first, count=count,
+                                      alpha=alpha, beta=beta)
+                comp = b.motion_compensate(fit[0], w, h, thresh=thresh, fb_check=fb, first=first, count=count, alpha=alpha,
+                                           beta=beta)
+                fused[fb, model, rounds, thresh] = fit, comp
+        # the slab belongs to the context: allocated once, counted from then on
+        slab = b.device_bytes() - bytes_before
+        assert slab >= gpu.lib().ofdis_global_motion_work_bytes(n, w, h) > 0
+        plain = b.upsample_frames(first, count, w, h)
+        fw, mf = b.upsample_bidir(w, h, alpha, beta, first=first, count=count, outputs=(True, False, True, False))[0::2] \
+            if kind != "plain" else (None, None)
+        assert b.device_bytes() - bytes_before == slab
+    finally:
+        b.close()
+    for (fb, model, rounds, thresh), (fit, comp) in fused.items():
+        flow, mask = (fw, mf) if fb else (plain, None)
+        what = f"fb_check {fb}, model {model}, rounds {rounds}, thresh {thresh}"
+        standalone = gpu.global_motion(flow, mask, model=model, rounds=rounds, thresh=thresh)
+        assert_fit_equal(fit, standalone, "fused vs standalone, " + what)
+        assert_compensated_equal(comp, gpu.motion_compensate(flow, standalone[0], mask, thresh=thresh),
+                                 "fused vs standalone, " + what)
+        if count <= 3:
+            want = global_motion_ref(flow, mask, model=model, rounds=rounds, thresh=thresh)
+            assert_fit_equal(standalone, want, "standalone vs the definition, " + what)
+        if not (fb and alpha == 0.0 and beta == 0.0):   # something was fitted in the comparison
+            assert (standalone[1][:, 0] > 0).all()
+    if kind != "plain":
+        assert_bits_equal(fw, plain, "upsample_bidir's forward flow is upsample_frames'")
+        if alpha == 0.0 and beta == 0.0:   # (a test nothing but an exact round trip passes: most pixels are masked here)
+            assert (mf != 0).mean() > 0.5
+        else:
+            assert (mf != 0).mean() < 0.5
+
+
+def test_fused_into_device_buffers_on_a_stream(gpu):
+    """models_ptr / stats_ptr / out_ptr / stream: the same bytes as the host-array form; stats = NULL and one output alone"""
+    w, h, n = 256, 112, 2
+    clip = _clip(w, h, 1, n + 1)
+    b, devs = _context(gpu, clip)
+    s = gpu.Stream()
+    try:
+        want_fit = b.global_motion(w, h, rounds=3, thresh=1.0, fb_check=True)
+        want = b.motion_compensate(want_fit[0], w, h, thresh=1.0, fb_check=True)
+        dm, dst = gpu.Dev(nbytes=n * 48), gpu.Dev(nbytes=n * 24)
+        dr, dl = gpu.Dev(nbytes=want[0].nbytes), gpu.Dev(nbytes=want[1].nbytes)
+        assert b.global_motion(w, h, rounds=3, thresh=1.0, fb_check=True, models_ptr=dm.ptr, stats_ptr=dst.ptr, stream=s.ptr) is None
+        # (the models are read from the device buffer the fit just wrote, on the same stream: no host round trip)
+        assert b.motion_compensate(dm.ptr, w, h, thresh=1.0, fb_check=True, out_ptr=(dr.ptr, dl.ptr), stream=s.ptr) is None
+        gpu.check(gpu.lib().ofdis_sync(s.ptr))
+        assert_bits_equal(dm.get((n, 6), np.float64), want_fit[0], "device-buffer form, models")
+        assert_bits_equal(dst.get((n, 3), np.int64), want_fit[1], "device-buffer form, stats")
+        assert_bits_equal(dr.get(want[0].shape, _f32), want[0], "device-buffer form, residual")
+        assert_bits_equal(dl.get(want[1].shape, np.uint8), want[1], "device-buffer form, label")
+        dm2 = gpu.Dev(nbytes=n * 48)
+        assert b.global_motion(w, h, rounds=3, thresh=1.0, fb_check=True, models_ptr=dm2.ptr, stream=s.ptr) is None
+        gpu.check(gpu.lib().ofdis_sync(s.ptr))
+        assert_bits_equal(dm2.get((n, 6), np.float64), want_fit[0], "stats = NULL")
+        res, none = b.motion_compensate(want_fit[0], w, h, thresh=1.0, fb_check=True, label=False)
+        assert none is None
+        assert_bits_equal(res, want[0], "label = NULL")
+        none, label = b.motion_compensate(want_fit[0], w, h, thresh=1.0, fb_check=True, residual=False)
+        assert none is None
+        assert_bits_equal(label, want[1], "residual = NULL")
+    finally:
+        b.close()
+        s.close()
+
+
+# ------------------------------------------------------------------ 4. checks that need a context
+@pytest.fixture(scope="module")
+def contexts(gpu):
+    p = oppoint(2, 256, 112)
+    made = dict(plain=gpu.Batch(p, 3), reverse=gpu.Batch(p, 3, reverse=True), seq=gpu.Batch(p, 3, sequence=True),
+                seq_rev=gpu.Batch(p, 3, sequence=True, reverse=True), stereo=gpu.Batch(p.copy(selectmode=2), 3),
+                stereo_lr=gpu.Batch(p.copy(selectmode=2), 3, stereo_lr=True))
+    yield made
+    for b in made.values():
+        b.close()
+
+
+def _fit_call(gpu, b, first=0, count=3, model=1, rounds=3, thresh=1.0, fb=0, alpha=0.01, beta=0.5, models=True, wo=256, ho=112):
+    """host buffers stand in for the device arrays: every call returns before it would launch"""
+    m, s = np.zeros((4, 6), np.float64), np.zeros((4, 3), np.int64)
+    return gpu.lib().ofdis_batch_global_motion(b.h, first, count, model, rounds, thresh, fb, alpha, beta,
+                                               m.ctypes.data if models else None, s.ctypes.data, wo, ho, None)
+
+
+def _comp_call(gpu, b, first=0, count=3, thresh=1.0, fb=0, alpha=0.01, beta=0.5, models=True, outputs=True, wo=256, ho=112):
+    m = np.zeros((4, 6), np.float64)
+    r, l = np.zeros((4, 112, 256, 2), _f32), np.zeros((4, 112, 256), np.uint8)
+    return gpu.lib().ofdis_batch_motion_compensate(b.h, first, count, m.ctypes.data if models else None, thresh, fb, alpha, beta,
+                                                   r.ctypes.data if outputs else None, l.ctypes.data if outputs else None, wo, ho,
+                                                   None)
+
+
+@pytest.mark.parametrize("which", ["stereo", "stereo_lr"])
+def test_batch_calls_reject_stereo_contexts(gpu, contexts, which):
+    for call in (_fit_call, _comp_call):
+        assert call(gpu, contexts[which]) == INVALID
+        assert "stereo" in gpu.lib().ofdis_last_error().decode()
+
+
+@pytest.mark.parametrize("which", ["plain", "seq"])
+def test_fb_check_names_the_missing_flag(gpu, contexts, which):
+    for call in (_fit_call, _comp_call):
+        assert call(gpu, contexts[which], fb=1) == INVALID
+        assert "OFDIS_BATCH_REVERSE" in gpu.lib().ofdis_last_error().decode()
+
+
+COMMON_REJECTS = [
+    dict(models=False), dict(first=-1), dict(count=0), dict(count=-1), dict(first=1, count=3), dict(first=3, count=1), dict(count=4),
+    dict(wo=0), dict(ho=0), dict(wo=257), dict(ho=113),
+    dict(thresh=0.0), dict(thresh=-1.0), dict(thresh=math.nan), dict(thresh=math.inf),
+    dict(fb=2), dict(fb=-1), dict(alpha=-0.01), dict(beta=-0.5), dict(alpha=math.nan), dict(beta=math.inf),
+]
+_ids = lambda kw: ",".join(f"{k}={v}" for k, v in kw.items())
+
+
+@pytest.mark.parametrize("kw", COMMON_REJECTS + [dict(model=-1), dict(model=2), dict(rounds=0), dict(rounds=9), dict(rounds=-1)],
+                         ids=_ids)
+def test_batch_global_motion_rejects(gpu, contexts, kw):
+    assert _fit_call(gpu, contexts["seq_rev"], **kw) == INVALID
+    assert gpu.lib().ofdis_last_error()
+
+
+@pytest.mark.parametrize("kw", COMMON_REJECTS + [dict(outputs=False)], ids=_ids)
+def test_batch_motion_compensate_rejects(gpu, contexts, kw):
+    assert _comp_call(gpu, contexts["seq_rev"], **kw) == INVALID
+    assert gpu.lib().ofdis_last_error()
+
+
+def test_batch_calls_reject_sides_above_the_limit(gpu, contexts):
+    """an original side above OFDIS_GM_MAX_SIDE is named as such (whatever the context's padded size)"""
+    for call in (_fit_call, _comp_call):
+        for kw in (dict(wo=8193), dict(ho=8193)):
+            assert call(gpu, contexts["seq_rev"], **kw) == INVALID
+            assert "OFDIS_GM_MAX_SIDE" in gpu.lib().ofdis_last_error().decode()
+
+
+# ------------------------------------------------------------------ 5. end to end
+def _moving_block_pair(w, h, cam, blk, side, at, seed=77):
+    """A: a window of a gen_synth texture of (w + 64) x (h + 64); B: the same window displaced by the integer vector `cam`, so
+    the background's true model is exactly that translation.  A square of a second texture (side x side at `at` in A) is
+    pasted on and moves by the integer vector `blk`.  Returns (A, B, the square in A as a bool map)."""
+    bg = gen_synth._texture(np.random.default_rng(seed), h - 64, w - 64)
+    fg = gen_synth._texture(np.random.default_rng(seed + 1), side - 128, side - 128)
+    assert bg.shape == (h + 64, w + 64) and fg.shape == (side, side)
+    to_u8 = lambda t: np.clip(np.rint(t), 0, 255).astype(np.uint8)
+    A = to_u8(bg[32:32 + h, 32:32 + w]).copy()
+    B = to_u8(bg[32 - cam[1]:32 - cam[1] + h, 32 - cam[0]:32 - cam[0] + w]).copy()
+    x0, y0 = at
+    A[y0:y0 + side, x0:x0 + side] = to_u8(fg)
+    B[y0 + blk[1]:y0 + blk[1] + side, x0 + blk[0]:x0 + blk[0] + side] = to_u8(fg)
+    inside = np.zeros((h, w), bool)
+    inside[y0:y0 + side, x0:x0 + side] = True
+    return A, B, inside
+
+
+def test_end_to_end_camera_and_moving_block(gpu):
+    """A 256x128 gray pair whose background moves by exactly (3, -2) and on which a 70x70 square (15 % of the frame) moves by
+    (-5, 4): Batch.global_motion at operating point 2, affine, thresh 1.0, forward-backward test on.  The trimmed fit (rounds =
+    3) must be strictly closer to the background's translation than the plain least-squares fit (rounds = 1); more than half of
+    the square's pixels eroded by 8 px must be labelled OUTLIER and more than half of the background pixels at least 16 px from
+    the square and the border INLIER.
+    Measured on an MI355X: translation error 1.4068 px with rounds = 1 and 0.1622 px with rounds = 3 (29312 valid pixels, 15066
+    in the last fit); OUTLIER on 1.000 of the eroded square, INLIER on 0.990 of the far background.  The absolute bound below is
+    twice the measured rounds = 3 error."""
+    from scipy.ndimage import binary_dilation, binary_erosion
+    w, h, cam, blk, side, at = 256, 128, (3, -2), (-5, 4), 70, (120, 30)
+    A, B, inside = _moving_block_pair(w, h, cam, blk, side, at)
+    b, devs = _context(gpu, np.stack([A, B]), "reverse")
+    try:
+        fits = {r: b.global_motion(w, h, model=GM_AFFINE, rounds=r, thresh=1.0, fb_check=True) for r in (1, 3)}
+        label = b.motion_compensate(fits[3][0], w, h, thresh=1.0, fb_check=True, residual=False)[1][0]
+    finally:
+        b.close()
+    err = {r: max(abs(fits[r][0][0, 0] - cam[0]), abs(fits[r][0][0, 3] - cam[1])) for r in (1, 3)}
+    core = binary_erosion(inside, iterations=8)
+    far = ~binary_dilation(inside, iterations=16)
+    far[:16], far[-16:], far[:, :16], far[:, -16:] = False, False, False, False
+    out_share, in_share = (label[core] == GM_OUTLIER).mean(), (label[far] == GM_INLIER).mean()
+    print(f"translation error: rounds 1 {err[1]:.4f} px, rounds 3 {err[3]:.4f} px; stats {fits[1][1][0].tolist()} "
+          f"{fits[3][1][0].tolist()}; OUTLIER on the eroded square {out_share:.3f}, INLIER on the far background {in_share:.3f}")
+    assert core.sum() > 2000 and far.sum() > 5000
+    assert err[3] < err[1]
+    assert err[3] < 0.33
+    assert out_share > 0.5
+    assert in_share > 0.5
+
+
+# ------------------------------------------------------------------ 6. the command-line tool
+def test_camera_motion_tool(gpu, tmp_path):
+    """tools/camera_motion.py on three PNGs: the CSV holds what Batch.global_motion returns for the same clip, the label PNGs
+    what Batch.motion_compensate returns"""
+    import os
+    import subprocess
+    import sys
+    from PIL import Image
+    w, h, n = 250, 107, 2
+    clip = _clip(w, h, 1, n + 1)
+    paths = []
+    for k, f in enumerate(clip):
+        paths.append(str(tmp_path / f"f{k}.png"))
+        Image.fromarray(f).save(paths[-1])
+    tool = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "camera_motion.py")
+    csv, stem = str(tmp_path / "cam.csv"), str(tmp_path / "lab")
+    res = subprocess.run([sys.executable, tool, "--rounds", "2", "--thresh", "0.75", "--labels", stem] + paths + [csv],
+                         capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0, (res.stdout, res.stderr)
+    b, devs = _context(gpu, clip)
+    try:
+        models, stats = b.global_motion(w, h, rounds=2, thresh=0.75, fb_check=True)
+        label = b.motion_compensate(models, w, h, thresh=0.75, fb_check=True, residual=False)[1]
+    finally:
+        b.close()
+    rows = [line.split(",") for line in open(csv).read().splitlines()]
+    assert len(rows) == n and all(len(r) == 9 for r in rows)
+    got_models = np.array([[float(v) for v in r[:6]] for r in rows], np.float64)
+    got_stats = np.array([[int(v) for v in r[6:]] for r in rows], np.int64)
+    assert_bits_equal(got_models, models, "the tool's models")
+    assert_bits_equal(got_stats, stats, "the tool's stats")
+    assert (stats[:, 2] == GM_OK_AFFINE).all() and (stats[:, 1] > 0).all()
+    grey = np.array([0, 127, 255], np.uint8)
+    for k in range(n):
+        assert_bits_equal(np.asarray(Image.open(f"{stem}_{k:03d}.png")), grey[label[k]], f"label map {k}")
+    res = subprocess.run([sys.executable, tool, "--rounds", "9"] + paths, capture_output=True, text=True, timeout=300)
+    assert res.returncode != 0 and "--rounds" in (res.stderr + res.stdout)
