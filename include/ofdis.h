@@ -449,8 +449,8 @@ int ofdis_batch_temporal_filter(ofdis_batch* b, const uint8_t* frames, int first
  * previous model is within thresh pixels -- and, given the models, the residual flow (flow minus model) with a label per pixel:
  * inlier (background, moves with the camera), outlier (moves on its own) or invalid.  The uses: subtracting the camera motion
  * before a two-stream quantisation, the input of a stabiliser, foreground / background segmentation, scene-change statistics.
- * Not provided: homography and similarity models, warping frames along a smoothed camera path (stabilisation itself), models
- * of the reverse direction, the C++ sequence driver.
+ * Warping frames along a smoothed camera path -- stabilisation itself -- is the next section, "Video stabilisation".
+ * Not provided: homography and similarity models, models of the reverse direction, the C++ sequence driver.
  *
  * The frame is W x H with both sides <= OFDIS_GM_MAX_SIDE.  F is the flow [H][W][2] fp32 of one pair, M its mask of OFDIS_FB_*
  * codes or NULL.  Centred, doubled coordinates are integers: X = 2x - (W-1), Y = 2y - (H-1).
@@ -532,6 +532,96 @@ int ofdis_batch_global_motion(ofdis_batch* b, int first_frame, int count, int mo
 int ofdis_batch_motion_compensate(ofdis_batch* b, int first_frame, int count, const double* models, float thresh, int fb_check,
                                   float alpha, float beta, float* residual, uint8_t* label, int width_org, int height_org,
                                   void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Video stabilisation: the per-pair camera models of a clip turned into one correcting warp per frame -- the classical
+ * Gaussian motion filter: the motions relative to a frame averaged over a window around it -- and the frames resampled by their
+ * warps.  Two operations, each stated below one step at a time, both independent of the arithmetic contract.
+ * Not provided: homography and similarity models, rolling-shutter correction, automatic crop or zoom selection, inpainting of
+ * the exposed border, the C++ sequence driver, stereo contexts.
+ *
+ * Conventions.  A warp is six doubles b0 .. b5 in the parametrisation of a model of ofdis_global_motion: the displacement field
+ * (b0 + b1*xc + b2*yc, b3 + b4*xc + b5*yc) in centred coordinates xc = x - (W-1)/2, yc = y - (H-1)/2; all zeros is the
+ * identity.  A map M = (a, b, c, d, tx, ty) means x' = a*xc + b*yc + tx, y' = c*xc + d*yc + ty.  The model a0 .. a5 of pair k
+ * is read as the map T_k = (1 + a1, a2, a4, 1 + a5, a0, a3): it takes a position in frame k to the same scene point in frame
+ * k+1.
+ *
+ * Camera path: models [npairs][6] fp64 and the window w_0 .. w_radius -> warps [npairs+1][6] fp64, one per frame.  Every
+ * operation is a separately rounded fp64 operation (no contraction) in this order:
+ *   det(M) = M.a*M.d - M.b*M.c
+ *   ok(det) = OFDIS_STAB_MIN_DET <= det <= OFDIS_STAB_MAX_DET                                       (a NaN fails the test)
+ *   usable(k) = all six numbers of the model finite and ok(det(T_k)).  An unusable pair is a break -- a scene cut, a failed
+ *       fit -- and no window reaches across it.
+ *   T o M (M first):  a = T.a*M.a + T.b*M.c   b = T.a*M.b + T.b*M.d   c = T.c*M.a + T.d*M.c   d = T.c*M.b + T.d*M.d
+ *                     tx = (T.a*M.tx + T.b*M.ty) + T.tx               ty = (T.c*M.tx + T.d*M.ty) + T.ty
+ *   inv(T), D = det(T):  a = T.d / D   b = (0 - T.b) / D   c = (0 - T.c) / D   d = T.a / D       (0 - x: a zero stays +0)
+ *                     tx = 0 - (a*T.tx + b*T.ty)   ty = 0 - (c*T.tx + d*T.ty)                   (a, b, c, d: the new ones)
+ *   For frame f:  acc = (w_0, 0, 0, w_0, 0, 0) (w_0 times the identity), sw = w_0, Mf = Mb = identity, and for j = 1, 2, ...
+ *   while j <= radius and f + j - 1 < npairs and f - j >= 0 and usable(f + j - 1) and usable(f - j):
+ *       Mf = T_{f+j-1} o Mf;   Mb = inv(T_{f-j}) o Mb                      the motions from frame f to frames f + j and f - j
+ *       acc.e = acc.e + (w_j*Mf.e + w_j*Mb.e)  for each of the six numbers e;   sw = sw + (w_j + w_j)
+ *   The walk stops at the first j that fails: the reach is r_f = min(radius, fwd_f, back_f) with fwd_f / back_f the numbers
+ *   of consecutive usable pairs f, f+1, ... / f-1, f-2, ...; the window is truncated symmetrically, so a uniform pan is left
+ *   alone wherever the window is truncated, and the first frame, the last frame and the frames at a break get Q = identity.
+ *   Motions are relative to frame f, not a path accumulated from frame 0: rounding error does not grow with the length of the
+ *   clip and every frame is an independent piece of work.
+ *       Q = acc / sw  (six divisions);   D = det(Q)
+ *       W = inv(Q) where ok(D) and all six numbers of inv(Q) are finite, else the identity          the backward map:
+ *                                                                                                   out_f(x) = I_f(W x)
+ *       s = 1 / zoom;  the zoom about the centre, W o scale(s), hides the border a correction exposes:
+ *       b0 = W.tx   b1 = W.a*s - 1   b2 = W.b*s   b3 = W.ty   b4 = W.c*s   b5 = W.d*s - 1
+ *   The weights are a HOST array of radius + 1 doubles, copied into the launch as the times of ofdis_interpolate are: finite,
+ *   w_0 > 0, the others >= 0, 0 <= radius <= OFDIS_STAB_MAX_RADIUS.  Their shape is the caller's (a Gaussian:
+ *   of_dis_amd/stabilize.py: gaussian_weights); no transcendental function runs on the device.  1 <= zoom <= OFDIS_STAB_MAX_ZOOM.
+ *
+ * Frame warp: frames [n][H][W][noc] u8 and warps [n][6] fp64 -> out, the same shape, and inside [n][H][W] u8 (optional).  For
+ * pixel (x, y) of frame f, every operation is a separately rounded fp32 operation in this order; positions are built as the
+ * residual of ofdis_motion_compensate is, every pixel from its own expression and never by an increment from its neighbour:
+ *   bf_k = (float) b_k;   X = 2x - (W-1), Y = 2y - (H-1);   xc = (float)X * 0.5f, yc = (float)Y * 0.5f
+ *   mu = (bf0 + bf1*xc) + bf2*yc;   mv = (bf3 + bf4*xc) + bf5*yc;   p = ((float)x + mu, (float)y + mv)
+ *   ins = inside(p)       0 <= px <= W-1 and 0 <= py <= H-1, as in ofdis_fb_check (a NaN gives false)
+ *   c[ch] = sample(I_f, pc)[ch], pc = (fminf(fmaxf(px, 0), W-1), fminf(fmaxf(py, 0), H-1)): the clamped bilinear expression of
+ *       ofdis_interpolate above (a NaN coordinate clamps to 0)
+ *   OFDIS_BORDER_CONSTANT: where not ins, c[ch] = 0.   OFDIS_BORDER_REPLICATE: c as sampled, everywhere.
+ *   out[ch] = (uint8) clamp((int)floorf(c[ch] + 0.5f), 0, 255);   inside = ins ? 1 : 0
+ * Consequences: a zero warp returns the frame bit for bit (p = (x, y), the sample is the pixel), and a warp that is an integer
+ * translation (b0, b3 integers, the rest 0) returns the frame shifted by it bit for bit (p is an integer position: the
+ * bilinear weights are 0 and 1), under OFDIS_BORDER_CONSTANT with zeros on the uncovered border.
+ * of_dis_amd/stabilize.py states the same arithmetic in numpy.
+ * ------------------------------------------------------------------------------------------- */
+#define OFDIS_STAB_MAX_RADIUS 64
+#define OFDIS_STAB_MIN_DET    0.25
+#define OFDIS_STAB_MAX_DET    4.0
+#define OFDIS_STAB_MAX_ZOOM   16.0
+enum { OFDIS_BORDER_CONSTANT = 0, OFDIS_BORDER_REPLICATE = 1 };                 /* border */
+/* device arrays: models [npairs][6] f64, warps [npairs+1][6] f64; weights: HOST, radius + 1 doubles.  One lane per frame, one
+ * launch on `stream`, no host synchronisation.  OFDIS_ERR_INVALID before any device work: a NULL models, weights or warps
+ * pointer; radius, the weights or zoom outside the ranges above; npairs < 1. */
+int ofdis_camera_path(const double* models, int npairs, const double* weights /* host */, int radius, double zoom,
+                      double* warps, void* stream);
+/* device arrays: frames, out [nframes][height][width][noc] u8; warps [nframes][6] f64; inside [nframes][height][width] u8 or
+ * NULL (not written).  One lane per quad of four adjacent pixels; 4-byte stores where width is a multiple of 4 and the array is
+ * 4-byte aligned, byte stores of the same bytes otherwise; nothing outside `out` and `inside` is written.  Enqueues on
+ * `stream`.  OFDIS_ERR_INVALID before any device work: a NULL frames, warps or out pointer; out == frames; noc not 1 or 3; a
+ * border that is not OFDIS_BORDER_CONSTANT or OFDIS_BORDER_REPLICATE; nframes < 1; sizes as ofdis_fb_check rejects them or a
+ * side above OFDIS_GM_MAX_SIDE. */
+int ofdis_warp_frames(const uint8_t* frames, const double* warps, uint8_t* out, uint8_t* inside /* or NULL */, int nframes,
+                      int width, int height, int noc, int border, void* stream);
+/* OFDIS_BATCH_SEQUENCE contexts: frames first_frame .. first_frame + count of the context (count + 1 output frames)
+ * stabilised over the pairs [first_frame, first_frame + count).  `frames` is the whole packed clip
+ * [nframes+1][height_org][width_org][noc] given to ofdis_batch_build_pyramids_u8_seq; out = [count+1][height_org][width_org]
+ * [noc], inside = [count+1][height_org][width_org] or NULL, warps = device [count+1][6] or NULL.  The composition, all enqueued
+ * on `stream`: ofdis_batch_global_motion(b, first_frame, count, model, rounds, thresh, fb_check, alpha, beta, ...), then
+ * ofdis_camera_path on its models, then ofdis_warp_frames on frames + first_frame frames -- bit-identical to those three calls
+ * made separately, under both contracts (the kernels are contract-independent, the level flows are not).  Models and warps
+ * live in an array of the context: allocated at the first call, counted by ofdis_batch_device_bytes from then on; the warps are
+ * copied to `warps` when one is given.  Joins a pipelined pass by itself.  OFDIS_ERR_INVALID as the two calls above and as
+ * ofdis_batch_global_motion (fb_check = 1 needs OFDIS_BATCH_REVERSE), and for a NULL context or a context created without
+ * OFDIS_BATCH_SEQUENCE (the pairs of any other context are no chain). */
+int ofdis_batch_stabilize(ofdis_batch* b, const uint8_t* frames, int first_frame, int count, int model, int rounds,
+                          float thresh, int fb_check, float alpha, float beta, const double* weights /* host */, int radius,
+                          double zoom, int border, uint8_t* out, uint8_t* inside /* or NULL */,
+                          double* warps /* device [count+1][6] or NULL */, int width_org, int height_org, void* stream);
 
 /* Warm start (the reference's `initflow`, oflow.cpp:217-220; e.g. the previous frame pair's flow of a video):
  * per frame (w >> (sc_f+1)) x (h >> (sc_f+1)) x 2 floats, AoS.  set_initflow borrows a device array

@@ -45,6 +45,7 @@ ABI_SYMBOLS = [
     "ofdis_temporal_filter", "ofdis_batch_temporal_filter",
     "ofdis_global_motion_work_bytes", "ofdis_global_motion", "ofdis_motion_compensate", "ofdis_batch_global_motion",
     "ofdis_batch_motion_compensate",
+    "ofdis_camera_path", "ofdis_warp_frames", "ofdis_batch_stabilize",
 ]
 BATCH_REVERSE = 1  # include/ofdis.h: OFDIS_BATCH_REVERSE
 BATCH_STEREO_LR = 2  # OFDIS_BATCH_STEREO_LR
@@ -60,6 +61,8 @@ GM_MAX_SIDE, GM_MAX_FLOW, GM_MAX_ROUNDS = 8192, 4096.0, 8  # OFDIS_GM_MAX_*
 GM_TRANSLATION_ONLY, GM_AFFINE = 0, 1  # OFDIS_GM_* model
 GM_OK_AFFINE, GM_TRANSLATION, GM_EMPTY = 0, 1, 2  # OFDIS_GM_* status
 GM_INLIER, GM_OUTLIER, GM_INVALID = 0, 1, 2  # OFDIS_GM_* label
+STAB_MAX_RADIUS, STAB_MIN_DET, STAB_MAX_DET, STAB_MAX_ZOOM = 64, 0.25, 4.0, 16.0  # OFDIS_STAB_*
+BORDER_CONSTANT, BORDER_REPLICATE = 0, 1  # OFDIS_BORDER_*
 OFDIS_VERSION = 3  # include/ofdis.h: the struct layouts below (OfdisTuning: 20 ints) belong to this ABI version
 
 
@@ -217,6 +220,10 @@ def lib():
                                                 VP, VP, C.c_int, C.c_int, VP]
         L.ofdis_batch_motion_compensate.argtypes = [VP, C.c_int, C.c_int, VP, C.c_float, C.c_int, C.c_float, C.c_float, VP, VP,
                                                     C.c_int, C.c_int, VP]
+        L.ofdis_camera_path.argtypes = [VP, C.c_int, VP, C.c_int, C.c_double, VP, VP]
+        L.ofdis_warp_frames.argtypes = [VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP]
+        L.ofdis_batch_stabilize.argtypes = [VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float,
+                                            VP, C.c_int, C.c_double, C.c_int, VP, VP, VP, C.c_int, C.c_int, VP]
         _lib = L
     return _lib
 
@@ -650,6 +657,44 @@ def motion_compensate(flow, models, mask=None, thresh=1.0, residual=True, label=
     return dr.get(flow.shape, _f32) if dr else None, dl.get((npairs, h, w), np.uint8) if dl else None
 
 
+def _stab_weights(weights):
+    """the window as a host array of radius + 1 doubles: (array, radius)"""
+    weights = np.ascontiguousarray(weights, np.float64)
+    assert weights.ndim == 1 and weights.size >= 1, weights.shape
+    return weights, weights.size - 1
+
+
+def camera_path(models, weights, zoom=1.0):
+    """ofdis_camera_path on the device: models [npairs, 6] float64 (global_motion's), weights [radius + 1] float64 (host; e.g.
+    of_dis_amd.stabilize.gaussian_weights) -> warps [npairs + 1, 6] float64, one per frame.
+    of_dis_amd/stabilize.py: camera_path_ref is the numpy statement of the same arithmetic."""
+    models = np.ascontiguousarray(models, np.float64)
+    assert models.ndim == 2 and models.shape[1] == 6, models.shape
+    npairs = models.shape[0]
+    weights, radius = _stab_weights(weights)
+    dm, dw = Dev(models), Dev(nbytes=(npairs + 1) * 48)
+    check(lib().ofdis_camera_path(dm.ptr, npairs, weights.ctypes.data, radius, zoom, dw.ptr, None))
+    check(lib().ofdis_sync(None))
+    return dw.get((npairs + 1, 6), np.float64)
+
+
+def warp_frames(frames, warps, border=BORDER_CONSTANT, inside=True):
+    """ofdis_warp_frames on the device: frames uint8 [n, h, w] (gray) or [n, h, w, 3], warps [n, 6] float64 -> (out, the shape
+    of frames; inside uint8 [n, h, w], or None with inside=False: passed as NULL).
+    of_dis_amd/stabilize.py: warp_frames_ref is the numpy statement of the same arithmetic."""
+    frames = np.ascontiguousarray(frames, np.uint8)
+    noc = 1 if frames.ndim == 3 else 3
+    n, h, w = frames.shape[:3]
+    assert frames.shape == (n, h, w) + ((3,) if noc == 3 else ()), frames.shape
+    warps = np.ascontiguousarray(warps, np.float64)
+    assert warps.shape == (n, 6), warps.shape
+    df, dw, do = Dev(frames), Dev(warps), Dev(nbytes=frames.nbytes)
+    di = Dev(nbytes=n * h * w) if inside else None
+    check(lib().ofdis_warp_frames(df.ptr, dw.ptr, do.ptr, di.ptr if di else None, n, w, h, noc, border, None))
+    check(lib().ofdis_sync(None))
+    return do.get(frames.shape, np.uint8), di.get((n, h, w), np.uint8) if di else None
+
+
 class Batch:
     """ofdis_batch: `nframes` frame pairs of one geometry resident in HBM.  reverse=True: ofdis_batch_create_ex with
     OFDIS_BATCH_REVERSE (every pass also computes the flow B -> A of each pair).  stereo_lr=True: OFDIS_BATCH_STEREO_LR
@@ -985,6 +1030,35 @@ class Batch:
             return None
         check(lib().ofdis_sync(stream))
         return dr.get(rshape, _f32) if dr else None, dl.get(lshape, np.uint8) if dl else None
+
+    def stabilize(self, frames_ptr, width_org, height_org, weights, zoom=1.0, border=BORDER_CONSTANT, model=GM_AFFINE, rounds=3,
+                  thresh=1.0, fb_check=False, first=0, count=None, alpha=FB_ALPHA, beta=FB_BETA, inside=False, out_ptr=None,
+                  warps_ptr=None, stream=None):
+        """ofdis_batch_stabilize over the frames first .. first + count of a sequence=True context: the models of
+        global_motion(model, rounds, thresh, fb_check) smoothed over the window `weights` (host, radius + 1 doubles) and the
+        frames warped.  frames_ptr is the whole packed device clip given to build_pyramids_u8_seq.  out_ptr None: returns (out
+        [count + 1][height_org][width_org] (+ [noc] for RGB), inside [count + 1][height_org][width_org] or None with
+        inside=False, warps [count + 1, 6] float64); else writes the device arrays out_ptr, `inside` (if a device pointer) and
+        warps_ptr (if given) on `stream` and returns None."""
+        count = self.nframes - first if count is None else count
+        weights, radius = _stab_weights(weights)
+        shape = (max(count, 0) + 1, height_org, width_org)
+        oshape = shape + ((self.p.noc,) if self.p.noc > 1 else ())
+        d = di = dw = None
+        if out_ptr is None:
+            d = Dev(nbytes=max(1, int(np.prod(oshape, dtype=np.int64))))
+            di = Dev(nbytes=max(1, int(np.prod(shape, dtype=np.int64)))) if inside else None
+            dw = Dev(nbytes=shape[0] * 48)
+            out_ptr, ins_ptr, warps_ptr = d.ptr, di.ptr if di else None, dw.ptr
+        else:
+            ins_ptr = inside if inside else None
+        check(lib().ofdis_batch_stabilize(self.h, frames_ptr, first, count, model, rounds, thresh, int(fb_check), alpha, beta,
+                                          weights.ctypes.data, radius, zoom, border, out_ptr, ins_ptr, warps_ptr, width_org,
+                                          height_org, stream))
+        if d is None:
+            return None
+        check(lib().ofdis_sync(stream))
+        return d.get(oshape, np.uint8), di.get(shape, np.uint8) if di else None, dw.get((shape[0], 6), np.float64)
 
     def timing(self, enable=True):
         check(lib().ofdis_batch_timing(self.h, int(enable)))

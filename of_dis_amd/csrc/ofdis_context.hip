@@ -962,4 +962,79 @@ int ofdis_batch_motion_compensate(ofdis_batch* b, int first_frame, int count, co
   return OFDIS_OK;
 }
 
+// ------------------------------------------------------------------------------------ video stabilisation (ofdis_stabilize.hip)
+static_assert(sizeof(StabWindow::w) / sizeof(double) == OFDIS_STAB_MAX_RADIUS + 1, "StabWindow holds OFDIS_STAB_MAX_RADIUS + 1 weights");
+static int stab_window(const double* weights, int radius, double zoom, StabWindow& win) {
+  if (!weights) return fail(OFDIS_ERR_INVALID, "weights is NULL");
+  if (radius < 0 || radius > OFDIS_STAB_MAX_RADIUS) return fail(OFDIS_ERR_INVALID, "radius outside 0..OFDIS_STAB_MAX_RADIUS");
+  memset(&win, 0, sizeof(win));
+  for (int j = 0; j <= radius; ++j) {
+    if (!(std::isfinite(weights[j]) && weights[j] >= 0.0 && (j > 0 || weights[j] > 0.0)))
+      return fail(OFDIS_ERR_INVALID, "weights must be finite, w_0 > 0 and the others >= 0");
+    win.w[j] = weights[j];
+  }
+  if (!(std::isfinite(zoom) && zoom >= 1.0 && zoom <= OFDIS_STAB_MAX_ZOOM))
+    return fail(OFDIS_ERR_INVALID, "zoom must be inside [1, OFDIS_STAB_MAX_ZOOM]");
+  win.zoom = zoom;
+  win.radius = radius;
+  return OFDIS_OK;
+}
+static int stab_warp_check(const uint8_t* frames, const uint8_t* out, int noc, int border) {
+  if (!frames || !out) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (out == frames) return fail(OFDIS_ERR_INVALID, "the frame warp does not work in place");
+  if (noc != 1 && noc != 3) return fail(OFDIS_ERR_INVALID, "noc must be 1 or 3");
+  if (border != OFDIS_BORDER_CONSTANT && border != OFDIS_BORDER_REPLICATE)
+    return fail(OFDIS_ERR_INVALID, "border must be OFDIS_BORDER_CONSTANT or OFDIS_BORDER_REPLICATE");
+  return OFDIS_OK;
+}
+
+int ofdis_camera_path(const double* models, int npairs, const double* weights, int radius, double zoom, double* warps,
+                      void* stream) {
+  if (!models || !warps) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  StabWindow win;
+  if (int rc = stab_window(weights, radius, zoom, win)) return rc;
+  if (npairs < 1) return fail(OFDIS_ERR_INVALID, "bad sizes (npairs < 1)");
+  HIPCHK(launch_camera_path(models, npairs, win, warps, (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+int ofdis_warp_frames(const uint8_t* frames, const double* warps, uint8_t* out, uint8_t* inside, int nframes, int width,
+                      int height, int noc, int border, void* stream) {
+  if (!warps) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (int rc = stab_warp_check(frames, out, noc, border)) return rc;
+  if (!gm_sizes_ok(nframes, width, height)) return fail(OFDIS_ERR_INVALID, kGmSizes);
+  HIPCHK(launch_warp_frames(frames, warps, out, inside, nframes, width, height, noc, border == OFDIS_BORDER_REPLICATE,
+                            (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+int ofdis_batch_stabilize(ofdis_batch* b, const uint8_t* frames, int first_frame, int count, int model, int rounds, float thresh,
+                          int fb_check, float alpha, float beta, const double* weights, int radius, double zoom, int border,
+                          uint8_t* out, uint8_t* inside, double* warps, int width_org, int height_org, void* stream) {
+  if (int rc = gm_batch_check(b, fb_check, alpha, beta, width_org, height_org)) return rc;
+  if (!b->sequence) return fail(OFDIS_ERR_INVALID, kSeqOnly);  // (the pairs of any other context are no chain)
+  if (int rc = gm_fit_check(model, rounds, thresh)) return rc;
+  StabWindow win;
+  if (int rc = stab_window(weights, radius, zoom, win)) return rc;
+  const ofdis_params& p = b->p;
+  if (int rc = stab_warp_check(frames, out, p.noc, border)) return rc;
+  Finish fin;
+  if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
+  if (!b->stab_path) {  // 6 + 6 doubles per pair and 6 more for the last frame, held as floats
+    dalloc(b, &b->stab_path, 24, false, 1);
+    if (int rc = dcommit(b)) return rc;
+  }
+  double* models = reinterpret_cast<double*>(b->stab_path);
+  double* path = models + (size_t)b->nframes * 6;
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = ofdis_batch_global_motion(b, first_frame, count, model, rounds, thresh, fb_check, alpha, beta, models, nullptr,
+                                         width_org, height_org, stream))
+    return rc;
+  HIPCHK(launch_camera_path(models, count, win, path, s));
+  HIPCHK(launch_warp_frames(frames + (size_t)first_frame * width_org * height_org * p.noc, path, out, inside, count + 1, width_org,
+                            height_org, p.noc, border == OFDIS_BORDER_REPLICATE, s));
+  if (warps) HIPCHK(hipMemcpyAsync(warps, path, (size_t)(count + 1) * 6 * sizeof(double), hipMemcpyDeviceToDevice, s));
+  return OFDIS_OK;
+}
+
 }  // extern "C"

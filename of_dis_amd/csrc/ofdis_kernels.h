@@ -267,6 +267,18 @@ hipError_t launch_gmotion_level(const float* fw, const float* rev, int npairs, U
                                 float alpha, float beta, double* models, long long* stats, void* work, hipStream_t s);
 hipError_t launch_gmotion_compensate_level(const float* fw, const float* rev, const double* models, int npairs, UpGeom g,
                                            float thresh, float alpha, float beta, float* residual, uint8_t* label, hipStream_t s);
+// video stabilisation (include/ofdis.h: ofdis_camera_path, ofdis_warp_frames; ofdis_stabilize.hip).  The window travels in
+// the launch, as InterpTimes does: w[0 .. radius], the rest zero
+struct StabWindow {
+  double w[65];  // OFDIS_STAB_MAX_RADIUS + 1
+  double zoom;
+  int radius;
+};
+// models [npairs][6] -> warps [npairs + 1][6], one lane per frame, one launch
+hipError_t launch_camera_path(const double* models, int npairs, const StabWindow& win, double* warps, hipStream_t s);
+// frames, out [nframes][h][w][noc] u8, warps [nframes][6], inside [nframes][h][w] u8 or null; replicate: OFDIS_BORDER_REPLICATE
+hipError_t launch_warp_frames(const uint8_t* frames, const double* warps, uint8_t* out, uint8_t* inside, int nframes, int w,
+                              int h, int noc, bool replicate, hipStream_t s);
 
 // ---- stereo-depth mode (SELECTMODE=2; ofdis_de.hip)
 struct DeSystemArgs {
