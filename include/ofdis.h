@@ -444,6 +444,76 @@ int ofdis_batch_temporal_filter(ofdis_batch* b, const uint8_t* frames, int first
                                 float alpha, float beta, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Temporal filtering along flow trajectories over 2R + 1 frames: the filter above averages a frame with its two neighbours
+ * only, which caps the noise gain at 1 / sqrt(3).  Here every output pixel walks `radius` steps forward and `radius` steps
+ * back through the flows of consecutive pairs -- the walk of ofdis_track_points -- and samples the frame at every stop; a
+ * direction ends where the path leaves the image or fails the forward-backward test.
+ *
+ * A clip has npairs + 1 frames I_0 .. I_npairs, 8-bit, W x H x noc (noc 1 or 3, channels interleaved).  Ffw[k] is the flow
+ * from frame k to k+1 and Frev[k] the flow from frame k+1 to k, each [H][W][2] fp32; both are required.  `weights` is a HOST
+ * array of `radius` floats w_1 .. w_R, 1 <= radius <= OFDIS_TRAJ_MAX_RADIUS, each inside [0, 1]; it is copied into the launch
+ * as the times of ofdis_interpolate are.  tau is the photometric gate of ofdis_temporal_filter; fb_check is 0 or 1; alpha and
+ * beta are those of ofdis_fb_check.  Every operation is a separately rounded fp32 operation in this order, independent of the
+ * arithmetic contract; inside, bil and the inequality are those of ofdis_track_points, sample that of ofdis_temporal_filter
+ * (of_dis_amd/csrc/ofdis_upsample.h: fb_inside, fb_bilinear, fb_consistent, interp_sample).  For output frame f, pixel (x, y)
+ * and c[ch] = (float) I_f[y][x][ch]:
+ *   walk(dir):  p_0 = ((float)x, (float)y), alive; for j = 1 .. R while alive:
+ *       forward:  k = f + j - 1, F = Ffw[k],  O = Frev[k], J = I_{f+j};  the direction ends when k >= npairs
+ *       backward: k = f - j,     F = Frev[k], O = Ffw[k],  J = I_{f-j};  the direction ends when k < 0
+ *       (u, v) = F[y][x] when j == 1 (read directly, as ofdis_temporal_filter does), else bil(F, p_{j-1})
+ *       q = (p.x + u, p.y + v);  not inside(q): the direction ends                                      (NaN lands here)
+ *       fb_check: (ru, rv) = bil(O, q);  du = u + ru, dv = v + rv;  lhs = du*du + dv*dv;
+ *                 rhs = alpha * ((u*u + v*v) + (ru*ru + rv*rv)) + beta;  the direction ends unless lhs <= rhs
+ *       p_j = q;  s_j[ch] = sample(J, q)[ch];  d = max over ch of fabsf(s_j[ch] - c[ch])
+ *       g = fmaxf(1 - d / tau, 0);  w_j^dir = w_j * g
+ *     every step not reached: w_j^dir = 0, s_j = 0
+ *   num[ch] = c[ch]; den = 1; for j = 1 .. R:
+ *       num[ch] = (num[ch] + w_j^back * s_j^back[ch]) + w_j^fwd * s_j^fwd[ch]
+ *       den     = (den + w_j^back) + w_j^fwd
+ *   out[ch] = (uint8) clamp((int)floorf(num[ch] / den + 0.5f), 0, 255)
+ *   support = nf | (nb << 4),  nf / nb = how many forward / backward steps have w_j^dir > 0
+ * A photometric gate of 0 does not end a direction: only leaving the image or failing the inequality does.
+ * Consequences:
+ *   - Radius 1 matches the existing filter.  With radius 1 and w_1 = wn, `out` holds the bytes of ofdis_temporal_filter on the
+ *     same frames and flows -- with fb_check = 1 for mask_fw = ofdis_fb_check(Ffw, Frev) and mask_rev = ofdis_fb_check(Frev,
+ *     Ffw), with fb_check = 0 for NULL masks -- for any flows, non-finite ones included, because step 1 reads the flow
+ *     directly.  `support` differs only in format: bit 0 here is the old bit 1, bit 4 the old bit 0.
+ *   - Zero weights return the clip.  All weights 0 returns the clip bit for bit (num = c, den = 1) with support 0.
+ *   - Identical frames with zero flows return themselves (every sample is the pixel, d = 0, and the quotient lies within a few
+ *     ulp of the integer c).
+ *   - Reach matches a track.  For finite flows, the forward reach nf of pixel (x, y) of frame f with tau = +inf and all
+ *     weights > 0 is count - 1 of the track that ofdis_track_points gives the seed (x, y) at seed frame f with max_steps = R
+ *     (with flow_rev = Frev for fb_check = 1, NULL for 0).
+ * The first frame has nb = 0 and the last nf = 0 everywhere.  of_dis_amd/temporal.py states the same arithmetic in numpy
+ * (trajectory_filter_ref).
+ * ------------------------------------------------------------------------------------------- */
+#define OFDIS_TRAJ_MAX_RADIUS 8
+/* device arrays: frames, out [npairs+1][height][width][noc] u8; flow_fw, flow_rev [npairs][height][width][2] f32; support
+ * [npairs+1][height][width] u8 or NULL (not written).  weights: HOST, [radius].  One lane per quad of four adjacent pixels;
+ * 4-byte stores where width is a multiple of 4 and the array is 4-byte aligned, byte stores of the same bytes otherwise;
+ * nothing outside `out` and `support` is written, and no device memory is allocated.  Enqueues on `stream`.
+ * OFDIS_ERR_INVALID before any device work: a NULL frames, flow, out or weights pointer; out == frames; noc not 1 or 3; radius
+ * outside 1..OFDIS_TRAJ_MAX_RADIUS; a weight outside [0, 1] or NaN; tau not positive, subnormal or NaN; fb_check not 0 or 1;
+ * alpha or beta as ofdis_fb_check rejects them; npairs < 1; sizes as ofdis_fb_check rejects them. */
+int ofdis_trajectory_filter(const uint8_t* frames, const float* flow_fw, const float* flow_rev, uint8_t* out,
+                            uint8_t* support /* or NULL */, int npairs, int width, int height, int noc,
+                            const float* weights /* host */, int radius, float tau, int fb_check, float alpha, float beta,
+                            void* stream);
+/* OFDIS_BATCH_SEQUENCE | OFDIS_BATCH_REVERSE contexts (both flags whatever fb_check is: walking back takes the reverse flows):
+ * frames first_frame .. first_frame + count of the context (count + 1 output frames), straight from its level flows.
+ * `frames`, out and support as for ofdis_batch_temporal_filter.  Only the pairs [first_frame, first_frame + count) are used:
+ * a walk ends at the range's first and last frame even where the context holds more pairs, so a caller who filters a long
+ * clip in ranges overlaps them by `radius` pairs on either side and keeps the frames in between.  Bit-identical to
+ * ofdis_trajectory_filter applied to out_fw and out_rev of ofdis_batch_upsample_bidir(b, first_frame, count, ...) and to
+ * frames + first_frame frames, under both contracts (the kernel is contract-independent, the level flows are not); the
+ * full-resolution flows are never written.  Joins a pipelined pass by itself.
+ * OFDIS_ERR_INVALID as ofdis_trajectory_filter, and for a NULL context, a context created without OFDIS_BATCH_SEQUENCE or
+ * without OFDIS_BATCH_REVERSE, a pair range outside the batch, an original size above the padded size. */
+int ofdis_batch_trajectory_filter(ofdis_batch* b, const uint8_t* frames, int first_frame, int count, uint8_t* out,
+                                  uint8_t* support, int width_org, int height_org, const float* weights /* host */,
+                                  int radius, float tau, int fb_check, float alpha, float beta, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Global (camera) motion models and motion-compensated flow: per pair, a translation or a 6-parameter affine model of the flow
  * field fitted by trimmed least squares -- a least-squares fit, then rounds - 1 re-fits on the pixels whose residual under the
  * previous model is within thresh pixels -- and, given the models, the residual flow (flow minus model) with a label per pixel:

@@ -43,6 +43,7 @@ ABI_SYMBOLS = [
     "ofdis_batch_input_frames", "ofdis_batch_upload_frame", "ofdis_batch_build_pyramids_u8_seq", "ofdis_batch_device_bytes",
     "ofdis_track_points", "ofdis_batch_track_points",
     "ofdis_temporal_filter", "ofdis_batch_temporal_filter",
+    "ofdis_trajectory_filter", "ofdis_batch_trajectory_filter",
     "ofdis_global_motion_work_bytes", "ofdis_global_motion", "ofdis_motion_compensate", "ofdis_batch_global_motion",
     "ofdis_batch_motion_compensate",
     "ofdis_camera_path", "ofdis_warp_frames", "ofdis_batch_stabilize",
@@ -57,6 +58,7 @@ FB_CONSISTENT, FB_INCONSISTENT, FB_OUTSIDE = 0, 1, 2
 INTERP_MAX_TIMES = 16  # OFDIS_INTERP_MAX_TIMES
 ENC_F32, ENC_F16, ENC_U16, ENC_U8 = 0, 1, 2, 3  # OFDIS_ENC_*
 TRACK_MAX_POINTS = 1 << 24  # OFDIS_TRACK_MAX_POINTS
+TRAJ_MAX_RADIUS = 8  # OFDIS_TRAJ_MAX_RADIUS
 GM_MAX_SIDE, GM_MAX_FLOW, GM_MAX_ROUNDS = 8192, 4096.0, 8  # OFDIS_GM_MAX_*
 GM_TRANSLATION_ONLY, GM_AFFINE = 0, 1  # OFDIS_GM_* model
 GM_OK_AFFINE, GM_TRANSLATION, GM_EMPTY = 0, 1, 2  # OFDIS_GM_* status
@@ -211,6 +213,10 @@ def lib():
                                             VP]
         L.ofdis_batch_temporal_filter.argtypes = [VP, VP, C.c_int, C.c_int, VP, VP, C.c_int, C.c_int, C.c_float, C.c_float,
                                                   C.c_float, C.c_float, VP]
+        L.ofdis_trajectory_filter.argtypes = [VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, VP, C.c_int, C.c_float,
+                                              C.c_int, C.c_float, C.c_float, VP]
+        L.ofdis_batch_trajectory_filter.argtypes = [VP, VP, C.c_int, C.c_int, VP, VP, C.c_int, C.c_int, VP, C.c_int, C.c_float,
+                                                    C.c_int, C.c_float, C.c_float, VP]
         L.ofdis_global_motion_work_bytes.restype = C.c_size_t
         L.ofdis_global_motion_work_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
         L.ofdis_global_motion.argtypes = [VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, VP, VP, VP, C.c_size_t,
@@ -615,6 +621,33 @@ def temporal_filter(frames, flow_fw, flow_rev, mask_fw=None, mask_rev=None, wn=1
     return do.get(frames.shape, np.uint8), ds.get((npairs + 1, h, w), np.uint8) if ds else None
 
 
+def _weights(weights):
+    w = np.ascontiguousarray(np.atleast_1d(np.asarray(weights, _f32)).ravel())
+    return w, w.ctypes.data
+
+
+def trajectory_filter(frames, flow_fw, flow_rev, weights, tau=np.inf, fb_check=True, alpha=FB_ALPHA, beta=FB_BETA, support=True):
+    """ofdis_trajectory_filter on the device: frames uint8 [npairs + 1, h, w] (gray) or [npairs + 1, h, w, 3]; flow_fw / flow_rev
+    [npairs, h, w, 2] float32 (frame k -> k + 1 and frame k + 1 -> k); weights: a sequence of 1..TRAJ_MAX_RADIUS values in
+    [0, 1], its length is the radius.  Returns (out, the shape of frames; support uint8 [npairs + 1, h, w] = nf | nb << 4, or
+    None with support=False: passed as NULL).  of_dis_amd/temporal.py: trajectory_filter_ref is the numpy statement of the same
+    arithmetic, trajectory_weights makes the weights and reach splits the support."""
+    flow_fw, flow_rev = _f(flow_fw), _f(flow_rev)
+    assert flow_fw.shape == flow_rev.shape and flow_fw.ndim == 4 and flow_fw.shape[-1] == 2, (flow_fw.shape, flow_rev.shape)
+    npairs, h, w = flow_fw.shape[:3]
+    frames = np.ascontiguousarray(frames, np.uint8)
+    noc = 1 if frames.ndim == 3 else 3
+    assert frames.shape == (npairs + 1, h, w) + ((3,) if noc == 3 else ()), (frames.shape, flow_fw.shape)
+    wts, wp = _weights(weights)
+    devs = [Dev(x) for x in (frames, flow_fw, flow_rev)]
+    do = Dev(nbytes=frames.nbytes)
+    ds = Dev(nbytes=(npairs + 1) * h * w) if support else None
+    check(lib().ofdis_trajectory_filter(*[d.ptr for d in devs], do.ptr, ds.ptr if ds else None, npairs, w, h, noc, wp, wts.size,
+                                        tau, int(fb_check), alpha, beta, None))
+    check(lib().ofdis_sync(None))
+    return do.get(frames.shape, np.uint8), ds.get((npairs + 1, h, w), np.uint8) if ds else None
+
+
 def _gm_inputs(flow, mask):
     flow = _f(flow)
     assert flow.ndim == 4 and flow.shape[-1] == 2, flow.shape
@@ -975,6 +1008,33 @@ class Batch:
             sup_ptr = support if support else None
         check(lib().ofdis_batch_temporal_filter(self.h, frames_ptr, first, count, out_ptr, sup_ptr, width_org, height_org, wn,
                                                 tau, alpha, beta, stream))
+        if d is None:
+            return None
+        check(lib().ofdis_sync(stream))
+        out = d.get(oshape, np.uint8)
+        return (out, ds.get(shape, np.uint8)) if ds else out
+
+    def trajectory_filter(self, frames_ptr, width_org, height_org, weights, tau=np.inf, fb_check=True, first=0, count=None,
+                          alpha=FB_ALPHA, beta=FB_BETA, out_ptr=None, support=False, stream=None):
+        """ofdis_batch_trajectory_filter over the frames first .. first + count of a sequence=True, reverse=True context,
+        straight from its level flows: frames_ptr is the whole packed device clip given to build_pyramids_u8_seq; weights: a
+        sequence of 1..TRAJ_MAX_RADIUS values in [0, 1], its length is the radius.  Returns and writes what temporal_filter
+        does: out_ptr None: the host array [count + 1][height_org][width_org] (+ [noc] for RGB), with support=True the pair
+        (out, support [count + 1][height_org][width_org] = nf | nb << 4); else the device array out_ptr (and, if `support` is a
+        device pointer, that array) on `stream`, and None."""
+        count = self.nframes - first if count is None else count
+        shape = (max(count, 0) + 1, height_org, width_org)
+        oshape = shape + ((self.p.noc,) if self.p.noc > 1 else ())
+        wts, wp = _weights(weights)
+        d = ds = None
+        if out_ptr is None:
+            d = Dev(nbytes=max(1, int(np.prod(oshape, dtype=np.int64))))
+            ds = Dev(nbytes=max(1, int(np.prod(shape, dtype=np.int64)))) if support else None
+            out_ptr, sup_ptr = d.ptr, ds.ptr if ds else None
+        else:
+            sup_ptr = support if support else None
+        check(lib().ofdis_batch_trajectory_filter(self.h, frames_ptr, first, count, out_ptr, sup_ptr, width_org, height_org, wp,
+                                                  wts.size, tau, int(fb_check), alpha, beta, stream))
         if d is None:
             return None
         check(lib().ofdis_sync(stream))

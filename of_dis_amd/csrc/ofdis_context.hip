@@ -879,6 +879,60 @@ int ofdis_batch_temporal_filter(ofdis_batch* b, const uint8_t* frames, int first
   return OFDIS_OK;
 }
 
+// ------------------------------------------------------------------------------------ trajectory filter (ofdis_trajfilter.hip)
+static_assert(sizeof(TrajWeights::w) / sizeof(float) == OFDIS_TRAJ_MAX_RADIUS, "TrajWeights holds OFDIS_TRAJ_MAX_RADIUS");
+static int trajfilter_args_check(const uint8_t* frames, const uint8_t* out, int noc, const float* weights, int radius, float tau,
+                                 int fb_check, float alpha, float beta, TrajWeights& tw) {
+  if (!frames || !out) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (out == frames) return fail(OFDIS_ERR_INVALID, "the trajectory filter does not work in place");
+  if (noc != 1 && noc != 3) return fail(OFDIS_ERR_INVALID, "noc must be 1 or 3");
+  if (!weights) return fail(OFDIS_ERR_INVALID, "weights is NULL");
+  if (radius < 1 || radius > OFDIS_TRAJ_MAX_RADIUS) return fail(OFDIS_ERR_INVALID, "radius must be 1..OFDIS_TRAJ_MAX_RADIUS");
+  memset(&tw, 0, sizeof(tw));
+  for (int j = 0; j < radius; ++j) {
+    if (!(weights[j] >= 0.0f && weights[j] <= 1.0f)) return fail(OFDIS_ERR_INVALID, "every weight must be inside [0, 1]");
+    tw.w[j] = weights[j];
+  }
+  tw.radius = radius;
+  if (!(tau >= FLT_MIN)) return fail(OFDIS_ERR_INVALID, "tau must be +inf or a positive float that is not subnormal");
+  if (fb_check != 0 && fb_check != 1) return fail(OFDIS_ERR_INVALID, "fb_check must be 0 or 1");
+  if (!fb_constants_ok(alpha, beta)) return fail(OFDIS_ERR_INVALID, "alpha and beta must be finite and >= 0");
+  return OFDIS_OK;
+}
+
+int ofdis_trajectory_filter(const uint8_t* frames, const float* flow_fw, const float* flow_rev, uint8_t* out, uint8_t* support,
+                            int npairs, int width, int height, int noc, const float* weights, int radius, float tau,
+                            int fb_check, float alpha, float beta, void* stream) {
+  if (!flow_fw || !flow_rev) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  TrajWeights tw;
+  if (int rc = trajfilter_args_check(frames, out, noc, weights, radius, tau, fb_check, alpha, beta, tw)) return rc;
+  if (npairs < 1 || width < 1 || height < 1 || (long long)width * height > (1ll << 30))
+    return fail(OFDIS_ERR_INVALID, "bad sizes");
+  HIPCHK(launch_trajfilter_frames(frames, flow_fw, flow_rev, out, support, npairs, width, height, noc, tw, tau, fb_check != 0,
+                                  alpha, beta, (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+int ofdis_batch_trajectory_filter(ofdis_batch* b, const uint8_t* frames, int first_frame, int count, uint8_t* out,
+                                  uint8_t* support, int width_org, int height_org, const float* weights, int radius, float tau,
+                                  int fb_check, float alpha, float beta, void* stream) {
+  if (!b) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (!b->sequence)  // (the pairs of any other context share no frames)
+    return fail(OFDIS_ERR_INVALID, b->reverse ? "not a context created with OFDIS_BATCH_SEQUENCE"
+                                              : "not a context created with OFDIS_BATCH_SEQUENCE | OFDIS_BATCH_REVERSE");
+  if (!b->reverse)  // (whatever fb_check is: walking back takes the reverse flows)
+    return fail(OFDIS_ERR_INVALID, "not a context created with OFDIS_BATCH_REVERSE");
+  const ofdis_params& p = b->p;
+  TrajWeights tw;
+  if (int rc = trajfilter_args_check(frames, out, p.noc, weights, radius, tau, fb_check, alpha, beta, tw)) return rc;
+  Finish fin;
+  if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
+  HIPCHK(launch_trajfilter_level(frames + (size_t)first_frame * width_org * height_org * p.noc, b->flow[0] + fin.off,
+                                 b->flow_rev[0] + fin.off, out, support, count, fin.g, p.noc, tw, tau, fb_check != 0, alpha, beta,
+                                 (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
 // ------------------------------------------------------------------------------------ global motion (ofdis_gmotion.hip)
 static bool gm_sizes_ok(int npairs, int width, int height) {
   return npairs >= 1 && width >= 1 && height >= 1 && width <= OFDIS_GM_MAX_SIDE && height <= OFDIS_GM_MAX_SIDE;

@@ -253,6 +253,22 @@ hipError_t launch_tfilter_frames(const uint8_t* frames, const float* flow_fw, co
 // launch_upsample_bidir computes them
 hipError_t launch_tfilter_level(const uint8_t* frames, const float* fw, const float* rev, uint8_t* out, uint8_t* support,
                                 int npairs, UpGeom g, int noc, float wn, float tau, float alpha, float beta, hipStream_t s);
+// temporal filter along flow trajectories (include/ofdis.h: ofdis_trajectory_filter; ofdis_trajfilter.hip).  The weights travel
+// by value in the launch, as InterpTimes does: w[0 .. radius), the rest zero
+struct TrajWeights {
+  float w[8];  // OFDIS_TRAJ_MAX_RADIUS
+  int radius;
+};
+// on materialised arrays: frames, out [npairs + 1][h][w][noc] u8, AoS flows [npairs][h][w][2], support [npairs + 1][h][w] or
+// null; fb: with the consistency test
+hipError_t launch_trajfilter_frames(const uint8_t* frames, const float* flow_fw, const float* flow_rev, uint8_t* out,
+                                    uint8_t* support, int npairs, int w, int h, int noc, const TrajWeights& tw, float tau,
+                                    bool fb, float alpha, float beta, hipStream_t s);
+// straight from the level flows of npairs consecutive pairs (ofdis_batch_trajectory_filter): the flows as
+// launch_upsample_bidir computes them
+hipError_t launch_trajfilter_level(const uint8_t* frames, const float* fw, const float* rev, uint8_t* out, uint8_t* support,
+                                   int npairs, UpGeom g, int noc, const TrajWeights& tw, float tau, bool fb, float alpha,
+                                   float beta, hipStream_t s);
 // global motion models and motion-compensated flow (include/ofdis.h: ofdis_global_motion; ofdis_gmotion.hip).  `work`: one
 // record of sums per workgroup and pair, gmotion_work_bytes(npairs, w, h) bytes; `rounds` x (accumulate, solve) on the stream.
 // On materialised arrays: flow [npairs][h][w][2], mask [npairs][h][w] or null, models [npairs][6], stats [npairs][3] or null

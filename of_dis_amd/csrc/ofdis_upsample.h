@@ -1,5 +1,5 @@
 // ofdis_upsample.h -- device helpers of the full-resolution finish, shared by the exact-only units ofdis_upsample.hip,
-// ofdis_interp.hip, ofdis_stereo_lr.hip, ofdis_track.hip and ofdis_tfilter.hip: the arithmetic of the level flow to full resolution (run_dense.cpp:406-414, UpGeom
+// ofdis_interp.hip, ofdis_stereo_lr.hip, ofdis_track.hip, ofdis_tfilter.hip and ofdis_trajfilter.hip: the arithmetic of the level flow to full resolution (run_dense.cpp:406-414, UpGeom
 // in ofdis_kernels.h), the forward-backward consistency test and the compact output encodings (include/ofdis.h:
 // ofdis_encoding).  These units are compiled with -ffp-contract=off only and every finish kernel takes its values from the
 // helpers below -- upsample_h, up_row / up_group, up_mix -- so every one of them computes the same bits.
@@ -194,7 +194,7 @@ __device__ __forceinline__ void interp_sample(const uint8_t* __restrict__ I, int
 }
 
 // The launch geometry of the kernels in which one lane owns a quad of 4 adjacent pixels of one row of one frame
-// (ofdis_interp.hip, ofdis_tfilter.hip).  Blocks of 256 quads per frame, and the frames of one launch: a launch covers at most
+// (ofdis_interp.hip, ofdis_tfilter.hip, ofdis_trajfilter.hip).  Blocks of 256 quads per frame, and the frames of one launch: a launch covers at most
 // 2^22 blocks (2^30 lanes), a multiple of 8 frames where it can (xcd_frame_map), and the launcher walks the frames in such
 // chunks.
 struct QuadGrid {

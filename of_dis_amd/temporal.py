@@ -5,8 +5,17 @@ only (no GPU, no library): the tests compare the kernels against `temporal_filte
     from of_dis_amd import temporal
     out, support = temporal.temporal_filter_ref(frames, flow_fw, flow_rev, mask_fw, mask_rev, wn=1.0, tau=24.0)
     both = support == temporal.SUPPORT_PREV | temporal.SUPPORT_NEXT               # pixels averaged over three frames
+
+and of the filter along flow trajectories over 2R + 1 frames (ofdis_trajectory_filter, ofdis_batch_trajectory_filter), built on
+the pieces of of_dis_amd/tracking.py:
+
+    w = temporal.trajectory_weights(2)                                            # flat: [1, 1]
+    out, support = temporal.trajectory_filter_ref(frames, flow_fw, flow_rev, w, tau=24.0, fb_check=True)
+    nb, nf = temporal.reach(support)                                              # steps back / forward that entered
 """
 import numpy as np
+
+from . import tracking
 
 SUPPORT_PREV, SUPPORT_NEXT = 1, 2  # bits of `support`: frame f-1 / frame f+1 entered the average with a weight > 0
 FB_CONSISTENT = 0  # include/ofdis.h: OFDIS_FB_CONSISTENT (capi.FB_CONSISTENT)
@@ -93,4 +102,88 @@ def temporal_filter_ref(frames, flow_fw, flow_rev, mask_fw=None, mask_rev=None, 
         assert r.dtype == _f32
         out[f] = np.clip(r.astype(np.int64), 0, 255).astype(np.uint8)
         support[f] = np.where(wp > 0, SUPPORT_PREV, 0) | np.where(wn_ > 0, SUPPORT_NEXT, 0)
+    return (out[..., 0] if gray else out), support
+
+
+# ------------------------------------------------------------------------------------ along trajectories over 2R + 1 frames
+TRAJ_MAX_RADIUS = 8  # include/ofdis.h: OFDIS_TRAJ_MAX_RADIUS (capi.TRAJ_MAX_RADIUS)
+
+
+def trajectory_weights(radius, wn=1.0, sigma=None):
+    """w_1 .. w_radius as float32: flat (every w_j = wn), or wn * exp(-j^2 / (2 sigma^2)) rounded to float32"""
+    j = np.arange(1, radius + 1, dtype=np.float64)
+    w = np.full(radius, float(wn)) if sigma is None else float(wn) * np.exp(-j * j / (2.0 * float(sigma) ** 2))
+    return w.astype(_f32)
+
+
+def reach(support):
+    """support of the trajectory filter -> (nb, nf): how many steps back / forward entered the average with a weight > 0"""
+    support = np.asarray(support, np.uint8)
+    return support >> 4, support & 15
+
+
+def _walk(I, c, f, forward, flow_fw, flow_rev, weights, tau, fb_check, alpha, beta):
+    """one direction of frame f: (w [R][h][w], s [R][h][w][noc]) float32, zero where a step is not reached"""
+    npairs, h, w = flow_fw.shape[:3]
+    R, noc = len(weights), I.shape[-1]
+    wgt, s = np.zeros((R, h, w), _f32), np.zeros((R, h, w, noc), _f32)
+    ys, xs = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
+    iy, ix = ys.ravel(), xs.ravel()                       # the walks still alive: their pixels ...
+    px, py = ix.astype(_f32), iy.astype(_f32)             # ... and where they stand
+    cf = c.reshape(-1, noc)
+    for j in range(1, R + 1):
+        k = f + j - 1 if forward else f - j
+        if k < 0 or k >= npairs or ix.size == 0:
+            break
+        F, O = (flow_fw[k], flow_rev[k]) if forward else (flow_rev[k], flow_fw[k])
+        J = I[f + j] if forward else I[f - j]
+        u, v = (F[iy, ix, 0], F[iy, ix, 1]) if j == 1 else tracking.bilinear(F, px, py)
+        with np.errstate(all="ignore"):
+            qx, qy = px + u, py + v
+        ok = tracking.inside(qx, qy, w, h)
+        if fb_check:
+            i = np.flatnonzero(ok)
+            ru, rv = tracking.bilinear(O, qx[i], qy[i])
+            ok[i] = tracking.consistent(u[i], v[i], ru, rv, alpha, beta)
+        iy, ix, px, py = iy[ok], ix[ok], qx[ok], qy[ok]
+        if ix.size == 0:
+            break
+        sv = sample(J, px, py)
+        d = np.abs(sv - cf[iy * w + ix]).max(axis=1)
+        with np.errstate(over="ignore", under="ignore"):
+            g = np.fmax(_f32(1) - d / _f32(tau), _f32(0))
+        assert d.dtype == _f32 and g.dtype == _f32
+        wgt[j - 1, iy, ix], s[j - 1, iy, ix] = _f32(weights[j - 1]) * g, sv
+    return wgt, s
+
+
+def trajectory_filter_ref(frames, flow_fw, flow_rev, weights, tau=np.inf, fb_check=True, alpha=tracking.FB_ALPHA,
+                          beta=tracking.FB_BETA):
+    """frames [npairs + 1][h][w] (gray) or [npairs + 1][h][w][3] uint8, flow_fw / flow_rev [npairs][h][w][2] float32 (frame k ->
+    k + 1 and frame k + 1 -> k), weights [radius] with 1 <= radius <= TRAJ_MAX_RADIUS and every weight in [0, 1], tau +inf or a
+    positive normal float -> (out, the shape of frames, uint8; support [npairs + 1][h][w] uint8 = nf | nb << 4), the arrays
+    ofdis_trajectory_filter writes."""
+    frames = np.asarray(frames, np.uint8)
+    flow_fw, flow_rev = np.asarray(flow_fw, _f32), np.asarray(flow_rev, _f32)
+    weights = np.asarray(weights, _f32).ravel()
+    npairs, h, w = flow_fw.shape[:3]
+    gray = frames.ndim == 3
+    I = frames[..., None] if gray else frames
+    assert I.shape[:3] == (npairs + 1, h, w) and flow_rev.shape == flow_fw.shape == (npairs, h, w, 2), (frames.shape, flow_fw.shape)
+    assert 1 <= weights.size <= TRAJ_MAX_RADIUS and ((weights >= 0) & (weights <= 1)).all(), weights
+    assert tau >= np.finfo(_f32).tiny, tau
+    out, support = np.empty_like(I), np.empty((npairs + 1, h, w), np.uint8)
+    half = _f32(0.5)
+    for f in range(npairs + 1):
+        c = I[f].astype(_f32)
+        wb, sb = _walk(I, c, f, False, flow_fw, flow_rev, weights, tau, fb_check, alpha, beta)
+        wf, sf = _walk(I, c, f, True, flow_fw, flow_rev, weights, tau, fb_check, alpha, beta)
+        num, den = c.copy(), np.ones((h, w), _f32)
+        for j in range(weights.size):
+            num = (num + wb[j][..., None] * sb[j]) + wf[j][..., None] * sf[j]
+            den = (den + wb[j]) + wf[j]
+        r = np.floor(num / den[..., None] + half)
+        assert r.dtype == _f32
+        out[f] = np.clip(r.astype(np.int64), 0, 255).astype(np.uint8)
+        support[f] = (wf > 0).sum(axis=0).astype(np.uint8) | ((wb > 0).sum(axis=0).astype(np.uint8) << 4)
     return (out[..., 0] if gray else out), support
