@@ -388,6 +388,92 @@ int ofdis_batch_track_points(ofdis_batch* b, int first_frame, int count, const f
                              int* counts, int width_org, int height_org, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Dense trajectories: the walk of ofdis_track_points from seeds the library places itself -- the textured centres of a grid,
+ * and in every frame again the centres of the cells that hold no live track -- with every track capped at a length (Sundaram,
+ * Brox and Keutzer, 2010; Wang, Klaeser, Schmid and Liu, "Dense trajectories and motion boundary descriptors", 2013).  One
+ * call runs a clip end to end: everything is enqueued on `stream`, nothing synchronises with the host.
+ *
+ * A clip has npairs + 1 frames I_0 .. I_npairs, 8-bit, W x H x noc (noc 1 or 3, channels interleaved); Ffw[k], Frev[k] as for
+ * ofdis_track_points.  stride s: 2 .. OFDIS_DT_MAX_STRIDE, W >= s and H >= s; window wr: 0 .. OFDIS_DT_MAX_WINDOW; min_eig T >= 0;
+ * max_len >= 0; max_tracks: 1 .. OFDIS_DT_MAX_TRACKS; alpha, beta as for ofdis_fb_check.
+ *
+ * Grid.  off = s / 2, ncx = (W-1-off)/s + 1, ncy = (H-1-off)/s + 1 (integer divisions).  Cell (cx, cy) has the centre pixel
+ * (off + cx*s, off + cy*s), always inside the image; cells are numbered row by row, c = cy*ncx + cx.  A position p inside the
+ * image lies in cell (min((int)floorf(px) / s, ncx-1), min((int)floorf(py) / s, ncy-1)).
+ *
+ * Texture test.  textured(f, sx, sy) is exact integer arithmetic on frame f.  The window pixels are (x', y') = (clamp(sx+i, 0,
+ * W-1), clamp(sy+j, 0, H-1)) for i, j = -wr .. wr, a clamped pixel counted once per (i, j).  Per channel
+ *     gx = I[y'][min(x'+1, W-1)] - I[y'][max(x'-1, 0)],   gy = I[min(y'+1, H-1)][x'] - I[max(y'-1, 0)][x']
+ * a = sum gx*gx, b = sum gx*gy, c = sum gy*gy over the window and the channels (a, c <= 255^2 * 3 * 15^2 < 2^26), and
+ *     textured = a >= T and c >= T and (a-T)*(c-T) >= b*b                                   (int64; products below 2^52)
+ * which is exactly lambda_min([[a, b], [b, c]]) >= T: T = 0 holds for every pixel, a constant window fails every T >= 1.
+ * Scale: the tensor is a SUM of DOUBLED central differences, so the mean structure tensor of true gradients has the
+ * eigenvalues lambda / (4 * (2wr+1)^2 * noc).  A threshold relative to the frame's largest (Wang) or mean (Sundaram) eigenvalue
+ * is not provided: that is a choice of T on the host.
+ *
+ * Process.  Lmax = max_len ? min(max_len, npairs) : npairs; a track is complete once it covers Lmax + 1 frames.  For
+ * f = 0 .. npairs, in this order:
+ *   1. advance (f >= 1): every live track takes steps 1 - 3 of the ofdis_track_points loop with pair f-1 (the consistency test
+ *      with Frev only).  A track that fails ends and has no entry for frame f; one that passes records its position, len += 1;
+ *      a track that is now complete stops being live.
+ *   2. occupancy (f < npairs): a cell is occupied if a live track has its frame-f position in it.
+ *   3. seed (f < npairs): the unoccupied cells in ascending cell number; each with textured(f, centre) starts a track at
+ *      ((float)sx, (float)sy) with start = f, len = 1, live, in slot ntracks++.  With ntracks == max_tracks the seed is dropped
+ *      instead: dropped++, no track starts, the cell stays unoccupied.  The last frame seeds nothing.
+ *
+ * Outputs.  tracks = [Lmax+1][max_tracks][2] fp32, step-major (adjacent slots are adjacent 8-byte values): tracks[j][i] is track
+ * i in frame start[i] + j for j < len[i]; for len[i] <= j <= Lmax both components hold the NaN 0x7FC00000.  start, len =
+ * [max_tracks] int32 (len may be NULL); info = {ntracks, dropped}.  The call writes every entry of the slots < ntracks and both
+ * info values, reads and writes nothing of the slots >= ntracks and relies on no memset.
+ *
+ * Consequences.
+ *   Replay: for every slot i, ofdis_track_points(Ffw, Frev, ..., seeds = tracks[0][i], seed_frame = start[i], max_steps = Lmax)
+ *     gives the same len[i] positions bit for bit, and counts == len[i].
+ *   Coverage: with dropped == 0, after step 3 of every frame f < npairs every textured cell holds the position of a live track.
+ *   Slot order: the slots are ordered by (start, cell of the seed).
+ *   Known count: with T = 0, zero flows and Frev zero, ntracks = ncx*ncy*ceil(npairs/Lmax); every track is complete except
+ *     those of the last generation when Lmax does not divide npairs.
+ * of_dis_amd/tracking.py states the same process in numpy (dense_tracks_ref, seed_texture_ref).
+ * ------------------------------------------------------------------------------------------- */
+#define OFDIS_DT_MAX_TRACKS (1 << 24)
+#define OFDIS_DT_MAX_STRIDE 64
+#define OFDIS_DT_MAX_WINDOW 7
+/* the grid of a width x height frame: returns ncx * ncy and writes ncx, ncy (either may be NULL); 0, and zeros, for a stride
+ * outside its range, a side smaller than the stride and sizes ofdis_fb_check rejects */
+int ofdis_dense_tracks_cells(int width, int height, int stride, int* ncx, int* ncy);
+/* bytes of the work buffer ofdis_dense_tracks needs for any max_len and max_tracks: the texture bits of every frame and cell,
+ * per-frame counts, and position and start frame of min(npairs * cells, OFDIS_DT_MAX_TRACKS) slots; 0 for rejected sizes */
+size_t ofdis_dense_tracks_work_bytes(int npairs, int width, int height, int stride);
+/* the texture test on its own, at every cell centre of every frame: device arrays frames [nframes][height][width][noc], out
+ * [nframes][ncy][ncx] u8, 1 / 0.  OFDIS_ERR_INVALID as ofdis_dense_tracks, and for nframes < 1 */
+int ofdis_seed_texture(const uint8_t* frames, int nframes, int width, int height, int noc, int stride, int window,
+                       int min_eig, uint8_t* out, void* stream);
+/* device arrays: frames [npairs+1][height][width][noc]; flow_fw, flow_rev [npairs][height][width][2] (flow_rev NULL: no
+ * consistency test); tracks, start, len, info as above; work: 8-byte aligned, at least ofdis_dense_tracks_work_bytes.  One
+ * launch tests the texture of every frame; then per frame one launch advances the tracks (one lane per slot of the live
+ * window) and two number the seeds (a prefix sum over the cells: slot numbers involve no atomic).  OFDIS_ERR_INVALID before
+ * any device work: a NULL frames, flow_fw, tracks, start, info or work; noc not 1 or 3; stride, window or max_tracks outside
+ * their ranges; min_eig < 0 or max_len < 0; a side smaller than stride; sizes, alpha and beta as ofdis_fb_check rejects them;
+ * npairs < 1; a work buffer that is too small or not 8-byte aligned. */
+int ofdis_dense_tracks(const uint8_t* frames, const float* flow_fw, const float* flow_rev /* NULL: no test */, int npairs,
+                       int width, int height, int noc, int stride, int window, int min_eig, int max_len, float alpha,
+                       float beta, int max_tracks, float* tracks, int* start, int* len /* or NULL */, long long* info,
+                       void* work, size_t work_bytes, void* stream);
+/* OFDIS_BATCH_SEQUENCE contexts: the pairs [first_frame, first_frame+count) of the context, straight from its level flows (the
+ * full-resolution flows are never written); `frames` is the packed clip given to ofdis_batch_build_pyramids_u8_seq, `start` is
+ * relative to first_frame, Lmax = max_len ? min(max_len, count) : count.  fb_check = 1: bit-identical to ofdis_dense_tracks
+ * applied to frames + first_frame frames and to out_fw and out_rev of ofdis_batch_upsample_bidir(b, first_frame, count, ...);
+ * fb_check = 0: to what ofdis_batch_upsample_frames writes, with flow_rev = NULL -- under both contracts.  The work buffer
+ * belongs to the context: allocated at the first call for what that call needs (a later call that needs more allocates
+ * again) and counted by ofdis_batch_device_bytes.  Joins a pipelined pass by itself.  OFDIS_ERR_INVALID as ofdis_dense_tracks,
+ * and for a NULL context, a context created without OFDIS_BATCH_SEQUENCE, fb_check not 0 or 1, fb_check = 1 on a context
+ * created without OFDIS_BATCH_REVERSE, a pair range outside the batch, an original size above the padded size. */
+int ofdis_batch_dense_tracks(ofdis_batch* b, const uint8_t* frames, int first_frame, int count, int stride, int window,
+                             int min_eig, int max_len, int fb_check, float alpha, float beta, int max_tracks,
+                             float* tracks, int* start, int* len, long long* info, int width_org, int height_org,
+                             void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Motion-compensated temporal filtering of a clip: every frame averaged with its two neighbours warped onto it by the flow
  * (motion compensation), a neighbour left out where the forward-backward test flags the pixel, where its sample falls outside
  * the image and -- with a finite tau -- faded out as it differs from the pixel it would be averaged with.  The classical use

@@ -42,6 +42,8 @@ ABI_SYMBOLS = [
     "ofdis_encoding_bytes", "ofdis_encode", "ofdis_batch_upsample_frames_enc",
     "ofdis_batch_input_frames", "ofdis_batch_upload_frame", "ofdis_batch_build_pyramids_u8_seq", "ofdis_batch_device_bytes",
     "ofdis_track_points", "ofdis_batch_track_points",
+    "ofdis_dense_tracks_cells", "ofdis_dense_tracks_work_bytes", "ofdis_seed_texture", "ofdis_dense_tracks",
+    "ofdis_batch_dense_tracks",
     "ofdis_temporal_filter", "ofdis_batch_temporal_filter",
     "ofdis_trajectory_filter", "ofdis_batch_trajectory_filter",
     "ofdis_global_motion_work_bytes", "ofdis_global_motion", "ofdis_motion_compensate", "ofdis_batch_global_motion",
@@ -58,6 +60,7 @@ FB_CONSISTENT, FB_INCONSISTENT, FB_OUTSIDE = 0, 1, 2
 INTERP_MAX_TIMES = 16  # OFDIS_INTERP_MAX_TIMES
 ENC_F32, ENC_F16, ENC_U16, ENC_U8 = 0, 1, 2, 3  # OFDIS_ENC_*
 TRACK_MAX_POINTS = 1 << 24  # OFDIS_TRACK_MAX_POINTS
+DT_MAX_TRACKS, DT_MAX_STRIDE, DT_MAX_WINDOW = 1 << 24, 64, 7  # OFDIS_DT_MAX_*
 TRAJ_MAX_RADIUS = 8  # OFDIS_TRAJ_MAX_RADIUS
 GM_MAX_SIDE, GM_MAX_FLOW, GM_MAX_ROUNDS = 8192, 4096.0, 8  # OFDIS_GM_MAX_*
 GM_TRANSLATION_ONLY, GM_AFFINE = 0, 1  # OFDIS_GM_* model
@@ -209,6 +212,14 @@ def lib():
                                          VP, VP]
         L.ofdis_batch_track_points.argtypes = [VP, C.c_int, C.c_int, VP, VP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                                VP, VP, C.c_int, C.c_int, VP]
+        L.ofdis_dense_tracks_cells.argtypes = [C.c_int, C.c_int, C.c_int, VP, VP]
+        L.ofdis_dense_tracks_work_bytes.restype = C.c_size_t
+        L.ofdis_dense_tracks_work_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+        L.ofdis_seed_texture.argtypes = [VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP]
+        L.ofdis_dense_tracks.argtypes = [VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_float, C.c_float, C.c_int, VP, VP, VP, VP, VP, C.c_size_t, VP]
+        L.ofdis_batch_dense_tracks.argtypes = [VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                               C.c_float, C.c_int, VP, VP, VP, VP, C.c_int, C.c_int, VP]
         L.ofdis_temporal_filter.argtypes = [VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                             VP]
         L.ofdis_batch_temporal_filter.argtypes = [VP, VP, C.c_int, C.c_int, VP, VP, C.c_int, C.c_int, C.c_float, C.c_float,
@@ -593,6 +604,81 @@ def track_points(flow_fw, flow_rev, seeds, seed_frame=None, max_steps=0, alpha=F
                                    max_steps, alpha, beta, dtracks.ptr, dcounts.ptr, None))
     check(lib().ofdis_sync(None))
     return dtracks.get((npairs + 1, n, 2), _f32), dcounts.get((n,), np.int32)
+
+
+def dense_tracks_cells(width, height, stride):
+    """ofdis_dense_tracks_cells: (ncx, ncy) of the seed grid, (0, 0) for rejected sizes"""
+    ncx, ncy = C.c_int(-1), C.c_int(-1)
+    n = lib().ofdis_dense_tracks_cells(width, height, stride, C.byref(ncx), C.byref(ncy))
+    assert n == ncx.value * ncy.value, (n, ncx.value, ncy.value)
+    return ncx.value, ncy.value
+
+
+def _clip_frames(frames, n, h, w):
+    frames = np.ascontiguousarray(frames, np.uint8)
+    noc = 1 if frames.ndim == 3 else 3
+    assert frames.shape == (n, h, w) + ((3,) if noc == 3 else ()), (frames.shape, (n, h, w))
+    return frames, noc
+
+
+def seed_texture(frames, stride, window, min_eig):
+    """ofdis_seed_texture on the device: frames uint8 [n, h, w] (gray) or [n, h, w, 3] -> uint8 [n, ncy, ncx], 1 where the cell
+    centre passes the texture test.  of_dis_amd/tracking.py: seed_texture_ref is the numpy statement of the same arithmetic."""
+    frames = np.ascontiguousarray(frames, np.uint8)
+    n, h, w = frames.shape[:3]
+    frames, noc = _clip_frames(frames, n, h, w)
+    ncx, ncy = dense_tracks_cells(w, h, stride)
+    df, do = Dev(frames), Dev(nbytes=max(1, n * ncx * ncy))
+    check(lib().ofdis_seed_texture(df.ptr, n, w, h, noc, stride, window, min_eig, do.ptr, None))
+    check(lib().ofdis_sync(None))
+    return do.get((n, ncy, ncx), np.uint8)
+
+
+def _dense_lmax(max_len, npairs):
+    return min(max_len, npairs) if max_len else npairs
+
+
+def _dense_outputs(lmax, max_tracks):
+    """device arrays of a dense_tracks call: tracks, start, len, info"""
+    return (Dev(nbytes=(lmax + 1) * max_tracks * 8), Dev(nbytes=max_tracks * 4), Dev(nbytes=max_tracks * 4), Dev(nbytes=16))
+
+
+def _dense_results(devs, lmax, max_tracks):
+    """(tracks [lmax + 1, ntracks, 2], start [ntracks], len [ntracks], info [2]): the slots the call wrote"""
+    dt, ds, dl, di = devs
+    info = di.get((2,), np.int64)
+    n = int(info[0])
+    assert 0 <= n <= max_tracks, info
+    tracks = dt.get((lmax + 1, max_tracks, 2), _f32)[:, :n]
+    return np.ascontiguousarray(tracks), ds.get((max_tracks,), np.int32)[:n].copy(), dl.get((max_tracks,), np.int32)[:n].copy(), info
+
+
+def dense_tracks(frames, flow_fw, flow_rev, stride, window, min_eig, max_len=15, max_tracks=None, alpha=FB_ALPHA, beta=FB_BETA):
+    """ofdis_dense_tracks on the device: frames uint8 [npairs + 1, h, w] (gray) or [npairs + 1, h, w, 3], flow_fw / flow_rev
+    [npairs, h, w, 2] float32 (flow_rev None: no consistency test) -> (tracks [Lmax + 1, ntracks, 2] float32, start [ntracks]
+    int32, len [ntracks] int32, info int64 [2] = (ntracks, dropped)): the slots below ntracks.  max_tracks None: room for every
+    seed (npairs x cells, at most DT_MAX_TRACKS).  of_dis_amd/tracking.py: dense_tracks_ref is the numpy statement of the same
+    process."""
+    flow_fw = _f(flow_fw)
+    assert flow_fw.ndim == 4 and flow_fw.shape[-1] == 2, flow_fw.shape
+    npairs, h, w = flow_fw.shape[:3]
+    if flow_rev is not None:
+        flow_rev = _f(flow_rev)
+        assert flow_rev.shape == flow_fw.shape, (flow_rev.shape, flow_fw.shape)
+    frames, noc = _clip_frames(frames, npairs + 1, h, w)
+    ncx, ncy = dense_tracks_cells(w, h, stride)
+    if max_tracks is None:
+        max_tracks = max(1, min(npairs * ncx * ncy, DT_MAX_TRACKS))
+    lmax = _dense_lmax(max_len, npairs)
+    dfr, dfw, drev = Dev(frames), Dev(flow_fw), Dev(flow_rev) if flow_rev is not None else None
+    outs = _dense_outputs(lmax, max(1, min(max_tracks, DT_MAX_TRACKS)))
+    wb = lib().ofdis_dense_tracks_work_bytes(npairs, w, h, stride)
+    dwork = Dev(nbytes=max(8, wb))
+    check(lib().ofdis_dense_tracks(dfr.ptr, dfw.ptr, drev.ptr if drev else None, npairs, w, h, noc, stride, window, min_eig,
+                                   max_len, alpha, beta, max_tracks, outs[0].ptr, outs[1].ptr, outs[2].ptr, outs[3].ptr,
+                                   dwork.ptr, wb, None))
+    check(lib().ofdis_sync(None))
+    return _dense_results(outs, lmax, max_tracks)
 
 
 def temporal_filter(frames, flow_fw, flow_rev, mask_fw=None, mask_rev=None, wn=1.0, tau=np.inf, support=True):
@@ -988,6 +1074,23 @@ class Batch:
                                              int(fb_check), alpha, beta, dtracks.ptr, dcounts.ptr, width_org, height_org, stream))
         check(lib().ofdis_sync(stream))
         return dtracks.get((count + 1, n, 2), _f32), dcounts.get((n,), np.int32)
+
+    def dense_tracks(self, frames_ptr, width_org, height_org, stride, window, min_eig, max_len=15, fb_check=True,
+                     max_tracks=None, first=0, count=None, alpha=FB_ALPHA, beta=FB_BETA, stream=None):
+        """ofdis_batch_dense_tracks over the pairs [first, first + count) of a sequence=True context, straight from its level
+        flows: frames_ptr is the whole packed device clip given to build_pyramids_u8_seq.  Returns what capi.dense_tracks
+        returns, `start` relative to `first`.  fb_check=True needs reverse=True; max_tracks None: room for every seed."""
+        count = self.nframes - first if count is None else count
+        ncx, ncy = dense_tracks_cells(width_org, height_org, stride)
+        if max_tracks is None:
+            max_tracks = max(1, min(max(count, 1) * ncx * ncy, DT_MAX_TRACKS))
+        lmax = _dense_lmax(max_len, max(count, 1))
+        outs = _dense_outputs(lmax, max(1, min(max_tracks, DT_MAX_TRACKS)))
+        check(lib().ofdis_batch_dense_tracks(self.h, frames_ptr, first, count, stride, window, min_eig, max_len, int(fb_check),
+                                             alpha, beta, max_tracks, outs[0].ptr, outs[1].ptr, outs[2].ptr, outs[3].ptr,
+                                             width_org, height_org, stream))
+        check(lib().ofdis_sync(stream))
+        return _dense_results(outs, lmax, max_tracks)
 
     def temporal_filter(self, frames_ptr, width_org, height_org, wn=1.0, tau=np.inf, first=0, count=None, alpha=FB_ALPHA,
                         beta=FB_BETA, out_ptr=None, support=False, stream=None):

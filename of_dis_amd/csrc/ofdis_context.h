@@ -171,6 +171,8 @@ struct ofdis_batch {
   float *lr_u = nullptr, *lr_dr = nullptr, *lr_mask = nullptr;  // staging of ofdis_batch_upsample_lr above its fused width, lazy
   float* gm_slab = nullptr;          // records of sums of ofdis_batch_global_motion (ofdis_gmotion.hip; int64, held as floats), lazy
   float* stab_path = nullptr;        // models [nframes][6] then warps [nframes + 1][6] of ofdis_batch_stabilize (fp64, held as floats), lazy
+  float* dt_slab = nullptr;          // work buffer of ofdis_batch_dense_tracks (ofdis_dense_tracks.hip; held as floats), lazy: a
+  size_t dt_slab_bytes = 0;          // call that needs more than dt_slab_bytes requests a larger one
   // device memory: requests are collected (dalloc) and served from ONE hipMalloc per commit (dcommit) -- a context is
   // one allocation (two with the u8 pyramid scratch), and the input planes form one contiguous region [in_base,
   // in_base + in_bytes) in (level, kind) order so that a single-frame context is uploaded with one copy (ofdis_flow)

@@ -838,6 +838,92 @@ int ofdis_batch_track_points(ofdis_batch* b, int first_frame, int count, const f
   return OFDIS_OK;
 }
 
+// ------------------------------------------------------------------------------------ dense trajectories (ofdis_dense_tracks.hip)
+static int dense_grid_check(int width, int height, int stride) {
+  if (stride < 2 || stride > OFDIS_DT_MAX_STRIDE) return fail(OFDIS_ERR_INVALID, "stride outside 2..OFDIS_DT_MAX_STRIDE");
+  if (width < 1 || height < 1 || (long long)width * height > (1ll << 30)) return fail(OFDIS_ERR_INVALID, "bad sizes");
+  if (width < stride || height < stride) return fail(OFDIS_ERR_INVALID, "bad sizes (a side smaller than the stride)");
+  return OFDIS_OK;
+}
+static int dense_texture_check(const uint8_t* frames, int noc, int window, int min_eig) {
+  if (!frames) return fail(OFDIS_ERR_INVALID, "frames is NULL");
+  if (noc != 1 && noc != 3) return fail(OFDIS_ERR_INVALID, "noc must be 1 or 3");
+  if (window < 0 || window > OFDIS_DT_MAX_WINDOW) return fail(OFDIS_ERR_INVALID, "window outside 0..OFDIS_DT_MAX_WINDOW");
+  if (min_eig < 0) return fail(OFDIS_ERR_INVALID, "min_eig is negative");
+  return OFDIS_OK;
+}
+static int dense_args_check(const uint8_t* frames, int noc, int window, int min_eig, int max_len, float alpha, float beta,
+                            int max_tracks, const float* tracks, const int* start, const long long* info) {
+  if (int rc = dense_texture_check(frames, noc, window, min_eig)) return rc;
+  if (!tracks || !start || !info) return fail(OFDIS_ERR_INVALID, "tracks, start or info is NULL");
+  if (max_len < 0) return fail(OFDIS_ERR_INVALID, "max_len is negative");
+  if (max_tracks < 1 || max_tracks > OFDIS_DT_MAX_TRACKS) return fail(OFDIS_ERR_INVALID, "max_tracks outside 1..OFDIS_DT_MAX_TRACKS");
+  if (!fb_constants_ok(alpha, beta)) return fail(OFDIS_ERR_INVALID, "alpha and beta must be finite and >= 0");
+  return OFDIS_OK;
+}
+
+int ofdis_dense_tracks_cells(int width, int height, int stride, int* ncx, int* ncy) {
+  if (ncx) *ncx = 0;
+  if (ncy) *ncy = 0;
+  if (dense_grid_check(width, height, stride)) return 0;
+  return dense_tracks_cells(width, height, stride, ncx, ncy);
+}
+
+size_t ofdis_dense_tracks_work_bytes(int npairs, int width, int height, int stride) {
+  if (npairs < 1 || dense_grid_check(width, height, stride)) return 0;
+  return dense_tracks_work_bytes(npairs, width, height, stride, 0, OFDIS_DT_MAX_TRACKS);
+}
+
+int ofdis_seed_texture(const uint8_t* frames, int nframes, int width, int height, int noc, int stride, int window, int min_eig,
+                       uint8_t* out, void* stream) {
+  if (int rc = dense_texture_check(frames, noc, window, min_eig)) return rc;
+  if (!out) return fail(OFDIS_ERR_INVALID, "out is NULL");
+  if (int rc = dense_grid_check(width, height, stride)) return rc;
+  if (nframes < 1) return fail(OFDIS_ERR_INVALID, "bad sizes (nframes < 1)");
+  HIPCHK(launch_seed_texture(frames, nframes, width, height, noc, stride, window, min_eig, out, (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+int ofdis_dense_tracks(const uint8_t* frames, const float* flow_fw, const float* flow_rev, int npairs, int width, int height,
+                       int noc, int stride, int window, int min_eig, int max_len, float alpha, float beta, int max_tracks,
+                       float* tracks, int* start, int* len, long long* info, void* work, size_t work_bytes, void* stream) {
+  if (!flow_fw) return fail(OFDIS_ERR_INVALID, "flow_fw is NULL");
+  if (int rc = dense_args_check(frames, noc, window, min_eig, max_len, alpha, beta, max_tracks, tracks, start, info)) return rc;
+  if (int rc = dense_grid_check(width, height, stride)) return rc;
+  if (npairs < 1) return fail(OFDIS_ERR_INVALID, "bad sizes (npairs < 1)");
+  if (!work || ((uintptr_t)work & 7) || work_bytes < ofdis_dense_tracks_work_bytes(npairs, width, height, stride))
+    return fail(OFDIS_ERR_INVALID, "work buffer is NULL, not 8-byte aligned or smaller than ofdis_dense_tracks_work_bytes");
+  HIPCHK(launch_dense_tracks(frames, flow_fw, flow_rev, npairs, width, height, noc, stride, window, min_eig, max_len, alpha, beta,
+                             max_tracks, tracks, start, len, info, work, (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+int ofdis_batch_dense_tracks(ofdis_batch* b, const uint8_t* frames, int first_frame, int count, int stride, int window,
+                             int min_eig, int max_len, int fb_check, float alpha, float beta, int max_tracks, float* tracks,
+                             int* start, int* len, long long* info, int width_org, int height_org, void* stream) {
+  if (!b || !b->sequence)  // (the pairs of any other context are no chain)
+    return fail(OFDIS_ERR_INVALID, kSeqOnly);
+  if (fb_check != 0 && fb_check != 1) return fail(OFDIS_ERR_INVALID, "fb_check must be 0 or 1");
+  if (fb_check && !b->reverse) return fail(OFDIS_ERR_INVALID, "fb_check needs a context created with OFDIS_BATCH_REVERSE");
+  const ofdis_params& p = b->p;
+  if (int rc = dense_args_check(frames, p.noc, window, min_eig, max_len, alpha, beta, max_tracks, tracks, start, info)) return rc;
+  if (int rc = dense_grid_check(width_org, height_org, stride)) return rc;
+  Finish fin;
+  if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
+  const size_t need = dense_tracks_work_bytes(count, width_org, height_org, stride, max_len, max_tracks);
+  if (need > b->dt_slab_bytes) {  // what this call needs; an earlier, smaller buffer stays with the context until it is destroyed
+    const size_t per_frame = (need + sizeof(float) * b->nframes - 1) / (sizeof(float) * b->nframes);
+    b->dt_slab_bytes = 0;
+    dalloc(b, &b->dt_slab, per_frame, false);
+    if (int rc = dcommit(b)) return rc;
+    b->dt_slab_bytes = per_frame * b->nframes * sizeof(float);
+  }
+  HIPCHK(launch_dense_tracks_level(frames + (size_t)first_frame * width_org * height_org * p.noc, b->flow[0] + fin.off,
+                                   fb_check ? b->flow_rev[0] + fin.off : nullptr, count, fin.g, p.noc, stride, window, min_eig,
+                                   max_len, alpha, beta, max_tracks, tracks, start, len, info, b->dt_slab, (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
 // ------------------------------------------------------------------------------------ temporal filter (ofdis_tfilter.hip)
 static int tfilter_args_check(const uint8_t* frames, const uint8_t* out, int noc, float wn, float tau) {
   if (!frames || !out) return fail(OFDIS_ERR_INVALID, "bad arguments");

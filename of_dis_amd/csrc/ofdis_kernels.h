@@ -243,6 +243,22 @@ hipError_t launch_track_points(const float* fw, const float* rev, int npairs, in
 // launch_upsample_crop compute them
 hipError_t launch_track_level(const float* fw, const float* rev, int npairs, UpGeom g, const float* seeds, const int* seed_frame,
                               int npoints, int max_steps, float alpha, float beta, float* tracks, int* counts, hipStream_t s);
+// dense trajectories (include/ofdis.h: ofdis_dense_tracks; ofdis_dense_tracks.hip).  The grid of a w x h frame (returns its
+// cells), and the bytes of the work buffer of a call (max_len 0 and max_tracks OFDIS_DT_MAX_TRACKS: of any call on that clip)
+int dense_tracks_cells(int w, int h, int stride, int* ncx, int* ncy);
+size_t dense_tracks_work_bytes(int npairs, int w, int h, int stride, int max_len, int max_tracks);
+// frames [nframes][h][w][noc] u8 -> out [nframes][ncy][ncx] u8
+hipError_t launch_seed_texture(const uint8_t* frames, int nframes, int w, int h, int noc, int stride, int window, int min_eig,
+                               uint8_t* out, hipStream_t s);
+// on materialised flows [npairs][h][w][2] (rev null: no consistency test): the texture launch, then per frame advance, count and
+// assign, all on the stream; tracks [Lmax + 1][max_tracks][2], start, len (or null) [max_tracks], info [2]
+hipError_t launch_dense_tracks(const uint8_t* frames, const float* fw, const float* rev, int npairs, int w, int h, int noc,
+                               int stride, int window, int min_eig, int max_len, float alpha, float beta, int max_tracks,
+                               float* tracks, int* start, int* len, long long* info, void* work, hipStream_t s);
+// straight from the level flows of npairs consecutive pairs (ofdis_batch_dense_tracks), as launch_track_level
+hipError_t launch_dense_tracks_level(const uint8_t* frames, const float* fw, const float* rev, int npairs, UpGeom g, int noc,
+                                     int stride, int window, int min_eig, int max_len, float alpha, float beta, int max_tracks,
+                                     float* tracks, int* start, int* len, long long* info, void* work, hipStream_t s);
 // motion-compensated temporal filter (include/ofdis.h: ofdis_temporal_filter; ofdis_tfilter.hip).  On materialised arrays:
 // frames, out [npairs + 1][h][w][noc] u8, AoS flows [npairs][h][w][2], masks [npairs][h][w] or null, support
 // [npairs + 1][h][w] or null

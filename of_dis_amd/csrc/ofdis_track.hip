@@ -4,10 +4,10 @@
 // Keutzer, "Dense point trajectories by GPU-accelerated large displacement optical flow", ECCV 2010).
 //
 // Compiled under the exact contract only (-ffp-contract=off): every operation of the header's definition is a separately
-// rounded fp32 operation, stated once in ofdis_upsample.h (fb_inside, fb_bilinear, fb_consistent), so the tracks are a fixed
-// function of the flows and the fused kernel -- which takes the four neighbours of a sample from the pair's level flow with
-// the helpers of every other finish kernel (UpNeighbours) -- writes the bits the standalone kernel writes on the
-// materialised flows.
+// rounded fp32 operation, stated once in ofdis_upsample.h (fb_track_step: fb_inside, fb_bilinear, fb_consistent), so the
+// tracks are a fixed function of the flows and the fused kernel -- which takes the four neighbours of a sample from the pair's
+// level flow with the helpers of every other finish kernel (UpNeighbours) -- writes the bits the standalone kernel writes on
+// the materialised flows.
 //
 // Mapping (both kernels): one lane per point, one wavefront per workgroup -- a wavefront marches in lock step and shares
 // nothing with its neighbours, so a few thousand points already spread over every compute unit.  The loop over the frames is
@@ -57,13 +57,8 @@ __device__ __forceinline__ void track_walk(const TrackArgs& a, Taps taps) {
     ++count;
     live = f < last;
     if (!live) continue;
-    const float2 uv = fb_bilinear(p.x, p.y, a.W, a.H, taps(f, 0));
-    const float2 q = make_float2(p.x + uv.x, p.y + uv.y);
-    live = fb_inside(q.x, q.y, a.W, a.H);
-    if (FB && live) {
-      const float2 r = fb_bilinear(q.x, q.y, a.W, a.H, taps(f, 1));
-      live = fb_consistent(uv.x, uv.y, r.x, r.y, a.alpha, a.beta);
-    }
+    float2 q;
+    live = fb_track_step<FB>(p, f, a.W, a.H, a.alpha, a.beta, taps, q);
     p = q;
   }
   if (a.counts) a.counts[i] = count;

@@ -1,5 +1,5 @@
 // ofdis_upsample.h -- device helpers of the full-resolution finish, shared by the exact-only units ofdis_upsample.hip,
-// ofdis_interp.hip, ofdis_stereo_lr.hip, ofdis_track.hip, ofdis_tfilter.hip and ofdis_trajfilter.hip: the arithmetic of the level flow to full resolution (run_dense.cpp:406-414, UpGeom
+// ofdis_interp.hip, ofdis_stereo_lr.hip, ofdis_track.hip, ofdis_dense_tracks.hip, ofdis_tfilter.hip and ofdis_trajfilter.hip: the arithmetic of the level flow to full resolution (run_dense.cpp:406-414, UpGeom
 // in ofdis_kernels.h), the forward-backward consistency test and the compact output encodings (include/ofdis.h:
 // ofdis_encoding).  These units are compiled with -ffp-contract=off only and every finish kernel takes its values from the
 // helpers below -- upsample_h, up_row / up_group, up_mix -- so every one of them computes the same bits.
@@ -130,6 +130,21 @@ __device__ __forceinline__ bool fb_consistent(float u, float v, float ru, float 
   const float lhs = du * du + dv * dv;
   const float rhs = alpha * ((u * u + v * v) + (ru * ru + rv * rv)) + beta;
   return lhs <= rhs;
+}
+// One step of a trajectory (include/ofdis.h: ofdis_track_points, steps 1 and 2) from the position p in frame k: q = p + the
+// forward flow of pair k at p.  False where the track ends: q outside the image or, with FB, the inequality on the reverse flow
+// at q.  `taps(k, d)` gives pair k's flow of direction d (0: frame k -> k + 1, 1: the reverse) at four integer pixels
+// (fb_bilinear's R).  Stated once for the walks of ofdis_track.hip and ofdis_dense_tracks.hip.
+template <bool FB, class Taps>
+__device__ __forceinline__ bool fb_track_step(float2 p, int k, int W, int H, float alpha, float beta, Taps taps, float2& q) {
+  const float2 uv = fb_bilinear(p.x, p.y, W, H, taps(k, 0));
+  q = make_float2(p.x + uv.x, p.y + uv.y);
+  bool live = fb_inside(q.x, q.y, W, H);
+  if (FB && live) {
+    const float2 r = fb_bilinear(q.x, q.y, W, H, taps(k, 1));
+    live = fb_consistent(uv.x, uv.y, r.x, r.y, alpha, beta);
+  }
+  return live;
 }
 // The code of integer pixel (x, y) with flow (u, v); `R` gives the other direction's flow (fb_bilinear).
 template <class Other>

@@ -4,7 +4,8 @@ run_DE_* binaries do (run_dense.cpp:185-431), for a list of pairs at once and wi
 (.pfm with --stereo).
 
     python tools/flow_images.py [--rgb] [--stereo [--lr [--fill MODE]]] [--op 1..4] [--fused] [--reverse] img1a img1b out1.flo [img2a img2b out2.flo ...]
-    python tools/flow_images.py --sequence [--rgb] [--op 1..4] [--fused] [--reverse [--tracks STRIDE]] img0 img1 ... imgN stem
+    python tools/flow_images.py --sequence [--rgb] [--op 1..4] [--fused] [--reverse [--tracks STRIDE]
+                                [--dense-tracks STRIDE[:WINDOW[:MIN_EIG[:MAX_LEN]]]]] img0 img1 ... imgN stem
 
 All pairs must have one size.  --fused selects the FMA / fast-reciprocal arithmetic contract (default: the exact one, bit for
 bit what run_OF_INT / run_OF_RGB write).  --reverse (optical flow only) also writes, next to <stem>.flo, the reverse flow
@@ -19,7 +20,11 @@ are the N + 1 frames of a clip and a stem; the flow from frame k to frame k + 1 
 uploaded and built once, into an OFDIS_BATCH_SEQUENCE context (ofdis_batch_build_pyramids_u8_seq); the files are the ones the
 pair-wise call writes for (img0, img1), (img1, img2), ...  --sequence --reverse --tracks STRIDE also writes the trajectories of
 the grid of that stride seeded at frame 0 (ofdis_batch_track_points with the default alpha and beta): <stem>_tracks.npy,
-float32 [N + 1][points][2] (x, y; NaN where a track has ended), and <stem>_counts.npy, int32 [points]."""
+float32 [N + 1][points][2] (x, y; NaN where a track has ended), and <stem>_counts.npy, int32 [points].  --sequence --reverse
+--dense-tracks STRIDE[:WINDOW[:MIN_EIG[:MAX_LEN]]] (defaults 2, 0 and 15) writes the dense trajectories of the clip
+(ofdis_batch_dense_tracks: the textured centres of a grid of that stride, the cells that lose their track seeded again in every
+frame, a track at most MAX_LEN + 1 frames long): <stem>_dtracks.npy, float32 [Lmax + 1][tracks][2], step-major (entry [j][i] is
+track i in frame start[i] + j; NaN beyond its length), <stem>_dstart.npy and <stem>_dlen.npy, int32 [tracks]."""
 import os
 import struct
 import sys
@@ -81,6 +86,7 @@ def main(argv):
     op = 2
     fill = "none"
     track_stride = 0
+    dense = None
     args = []
     it = iter(argv)
     for a in it:
@@ -92,10 +98,20 @@ def main(argv):
             fill = next(it)
         elif a == "--tracks":
             track_stride = int(next(it))
+        elif a == "--dense-tracks":
+            try:
+                dense = [int(x) for x in next(it).split(":")]
+            except ValueError:
+                dense = []
+            if not 1 <= len(dense) <= 4:
+                sys.exit("--dense-tracks STRIDE[:WINDOW[:MIN_EIG[:MAX_LEN]]]")
+            dense += [2, 0, 15][len(dense) - 1:]
         else:
             args.append(a)
     if track_stride < 0 or (track_stride and not (opts["--sequence"] and opts["--reverse"])):
         sys.exit("--tracks STRIDE (>= 1) needs --sequence --reverse")
+    if dense and not (opts["--sequence"] and opts["--reverse"]):
+        sys.exit("--dense-tracks needs --sequence --reverse")
     stem = args[-1] if args else None
     if opts["--sequence"]:
         if opts["--stereo"]:
@@ -148,6 +164,13 @@ def main(argv):
         np.save(stem + "_counts.npy", counts)
         print(f"{stem}_tracks.npy, _counts.npy: {len(counts)} points, {np.mean(counts == len(trip) + 1):.3f} of the tracks "
               f"reach the last frame")
+    if dense:                        # likewise; one call for the clip
+        dtracks, dstart, dlen, info = b.dense_tracks(da.ptr, w, h, *dense)
+        np.save(stem + "_dtracks.npy", dtracks)
+        np.save(stem + "_dstart.npy", dstart)
+        np.save(stem + "_dlen.npy", dlen)
+        print(f"{stem}_dtracks.npy, _dstart.npy, _dlen.npy: {info[0]} tracks ({int((dstart > 0).sum())} seeded after frame 0, "
+              f"{info[1]} seeds dropped), mean length {dlen.mean() if len(dlen) else 0:.2f} frames")
     if opts["--reverse"]:            # both directions and both masks in one launch; the forward flow is upsample()'s
         full, rev, mask_fw, mask_rev = b.upsample_bidir(w, h)
     else:
