@@ -61,6 +61,88 @@ __device__ __forceinline__ float dpp_mov0(float x) {
 __device__ __forceinline__ float wave_from_prev(float x) { return dpp_mov0<0x138>(x); }  // wave_shr:1, lane 0 <- 0
 __device__ __forceinline__ float wave_from_next(float x) { return dpp_mov0<0x130>(x); }  // wave_shl:1, lane 63 <- 0
 
+// A lane shift TOGETHER WITH ITS SINGLE CONSUMER, as one VOP2 DPP instruction: where a shifted value feeds exactly one
+// multiply, add or subtract, the v_mov_b32_dpp of wave_from_prev / wave_from_next (an 8-byte encoding of its own) is not
+// needed -- the consumer reads its first operand through the same lane shift, with the same zero fill at the wavefront's
+// ends (bound_ctrl, row and bank mask 0xf, as dpp_mov0).  The compiler's own DPP combine only folds such a pair when it
+// finds the consumer within twenty instructions after the move in the order instruction selection leaves, which in
+// the long straight-line step loops of the TV kernels happens for two to four of about twenty; hence
+// inline assembly.
+// Hazard: the ISA wants two wait states between a VALU write of a register and a DPP instruction that reads it, and the
+// compiler's hazard recogniser does not look into an asm statement.  Every statement below therefore OPENS with s_nop 1
+// (two wait states against whatever precedes it, whichever operand that wrote), and no instruction of a statement reads
+// what an earlier one of the same statement wrote.  Shifts that do not depend on each other share ONE statement -- the
+// (u, v) pairs of all sweeps of a step, the five vertical neighbour terms of a pixel's system -- so a step pays three
+// s_nop for fifteen moves.  The other DPP hazard (a VALU write of EXEC, five wait states) needs a v_cmpx, which the
+// compiler does not emit for gfx9 (it masks with SALU instructions; tests/test_isa_tv_shifts.py checks the TV kernels).
+// What a statement writes is a VALU result the hazard recogniser does not know of: do not feed one DIRECTLY into another
+// lane shift (no caller does: every result goes into plain arithmetic first).
+// The statements are not volatile: the scheduler moves them like any arithmetic and unused ones disappear.  Do not call
+// them inside a conditional expression -- the compiler cannot speculate an asm statement and branches around it; compute,
+// then select.
+// Arithmetic: every instruction is ONE correctly rounded fp32 operation on the shifted value, so a helper has the bits of
+// the wave_from_* expression it replaces; fmac_pairs_from_next follows the contract of the translation unit like the
+// a + b * c it stands for -- exact: product and sum rounded separately (v_mul_f32_dpp, then a plain add); fused: one
+// v_fmac_f32_dpp, the v_fmac_f32 the compiler contracts that expression into.
+#define OFDIS_DPP_PREV " wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"  // lane l <- lane l-1, lane 0 <- 0
+#define OFDIS_DPP_NEXT " wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"  // lane l <- lane l+1, lane 63 <- 0
+// K pairs (u, v) with one weight per pair, K <= 3 (the sweeps of a step):  op (pu[i], pv[i]), shift(xu[i], xv[i]), w[i]
+#define OFDIS_PAIR_OPS(op, ctrl, i) \
+  op " %[pu" #i "], %[xu" #i "], %[w" #i "]" ctrl op " %[pv" #i "], %[xv" #i "], %[w" #i "]" ctrl
+#define OFDIS_PAIR_OUT(c, i) [pu##i] c(pu[i]), [pv##i] c(pv[i])
+#define OFDIS_PAIR_IN(i) [xu##i] "v"(xu[i]), [xv##i] "v"(xv[i]), [w##i] "v"(w[i])
+#define OFDIS_DPP_PAIRS(name, op, ctrl, c)                                                                             \
+  template <int K>                                                                                                     \
+  __device__ __forceinline__ void name(float (&pu)[K], float (&pv)[K], const float (&xu)[K], const float (&xv)[K],      \
+                                       const float (&w)[K]) {                                                          \
+    static_assert(K >= 1 && K <= 3, "one asm statement holds at most three pairs");                                    \
+    if constexpr (K == 1)                                                                                              \
+      asm("s_nop 1\n\t" OFDIS_PAIR_OPS(op, ctrl, 0) : OFDIS_PAIR_OUT(c, 0) : OFDIS_PAIR_IN(0));                        \
+    else if constexpr (K == 2)                                                                                         \
+      asm("s_nop 1\n\t" OFDIS_PAIR_OPS(op, ctrl, 0) OFDIS_PAIR_OPS(op, ctrl, 1)                                        \
+          : OFDIS_PAIR_OUT(c, 0), OFDIS_PAIR_OUT(c, 1) : OFDIS_PAIR_IN(0), OFDIS_PAIR_IN(1));                          \
+    else                                                                                                               \
+      asm("s_nop 1\n\t" OFDIS_PAIR_OPS(op, ctrl, 0) OFDIS_PAIR_OPS(op, ctrl, 1) OFDIS_PAIR_OPS(op, ctrl, 2)            \
+          : OFDIS_PAIR_OUT(c, 0), OFDIS_PAIR_OUT(c, 1), OFDIS_PAIR_OUT(c, 2)                                           \
+          : OFDIS_PAIR_IN(0), OFDIS_PAIR_IN(1), OFDIS_PAIR_IN(2));                                                     \
+  }
+// (pu, pv)[i] = (prev(xu[i]) * w[i], prev(xv[i]) * w[i]); the same with next(); outputs are written before the later
+// pairs' inputs are read: early clobber
+OFDIS_DPP_PAIRS(mul_pairs_from_prev, "v_mul_f32_dpp", OFDIS_DPP_PREV, "=&v")
+OFDIS_DPP_PAIRS(mul_pairs_from_next, "v_mul_f32_dpp", OFDIS_DPP_NEXT, "=&v")
+OFDIS_DPP_PAIRS(fma_pairs_from_next, "v_fmac_f32_dpp", OFDIS_DPP_NEXT, "+v")  // fused contract only, through:
+#undef OFDIS_DPP_PAIRS
+#undef OFDIS_PAIR_IN
+#undef OFDIS_PAIR_OUT
+#undef OFDIS_PAIR_OPS
+// (pu, pv)[i] += (next(xu[i]) * w[i], next(xv[i]) * w[i]): the contract's a + b * c (see above)
+template <int K>
+__device__ __forceinline__ void fmac_pairs_from_next(float (&pu)[K], float (&pv)[K], const float (&xu)[K], const float (&xv)[K],
+                                                     const float (&w)[K]) {
+  if constexpr (kFusedContract) {
+    fma_pairs_from_next(pu, pv, xu, xv, w);
+  } else {
+    float qu[K], qv[K];
+    mul_pairs_from_next(qu, qv, xu, xv, w);
+#pragma unroll
+    for (int i = 0; i < K; ++i) { pu[i] = pu[i] + qu[i]; pv[i] = pv[i] + qv[i]; }
+  }
+}
+// The vertical neighbour terms of a pixel's TV system, five shifts in one statement: with c = (cx, cy) the pixel's own
+// vector, m / p the vectors of the diag rows before / after it and s, sn two scalars,
+//   up = c - prev(m)      dn = next(p) - c      sum = s + next(sn)
+__device__ __forceinline__ void vertical_terms(float& upx, float& upy, float& dnx, float& dny, float& sum, float cx, float cy,
+                                               float mx, float my, float px, float py, float s, float sn) {
+  asm("s_nop 1\n\t"
+      "v_subrev_f32_dpp %[upx], %[mx], %[cx]" OFDIS_DPP_PREV "v_subrev_f32_dpp %[upy], %[my], %[cy]" OFDIS_DPP_PREV
+      "v_sub_f32_dpp %[dnx], %[px], %[cx]" OFDIS_DPP_NEXT "v_sub_f32_dpp %[dny], %[py], %[cy]" OFDIS_DPP_NEXT
+      "v_add_f32_dpp %[sum], %[sn], %[s]" OFDIS_DPP_NEXT
+      : [upx] "=&v"(upx), [upy] "=&v"(upy), [dnx] "=&v"(dnx), [dny] "=&v"(dny), [sum] "=&v"(sum)
+      : [cx] "v"(cx), [cy] "v"(cy), [mx] "v"(mx), [my] "v"(my), [px] "v"(px), [py] "v"(py), [s] "v"(s), [sn] "v"(sn));
+}
+#undef OFDIS_DPP_PREV
+#undef OFDIS_DPP_NEXT
+
 // 64-lane butterfly all-reduce.  Order of the additions (this IS the documented reduction order,
 // mirrored by oracle/eigen_shim -DOFDIS_SHIM_WAVE64 and oracle_set_reduce_order(1)):
 //   pairs at lane distance 1, then 2, 4, 8, 16, 32; every lane ends with the same bits.

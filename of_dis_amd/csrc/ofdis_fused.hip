@@ -371,17 +371,19 @@ __attribute__((amdgpu_waves_per_eu(NOC == 3 ? 2 : (MODE == 1 ? 3 : 1)))) void tv
         {
           const float sc = sm[(u + 1) % 3];
           const float s_r = sm[(u + 2) % 3];
-          const float s_d = from_next(sm[(u + 2) % 3]);
           const float sh_c = x1_last ? 0.0f : sc + s_r;
-          const float sv_c = has_bot ? sc + s_d : 0.0f;
           const FRow& rc = W[(u + 1) % 6];
           const FRow& rm = W[u % 6];        // row tau-1
           const FRow& rp = W[(u + 2) % 6];  // row tau+1
           float a11, a12, a22, b1, b2;
           if constexpr (NOC == 1) data_term_gray<BRIGHT>(D[(u + 1) % PDD][0], rc.du, rc.dv, hd3, hg3, a11, a12, a22, b1, b2);
           else data_term_rgb<BRIGHT>(D[(u + 1) % PDD], rc.du, rc.dv, hd3, hg3, a11, a12, a22, b1, b2);
-          const float wx_u = from_prev(rm.wx), wy_u = from_prev(rm.wy);
-          const float wx_d = from_next(rp.wx), wy_d = from_next(rp.wy);
+          // (x, y-1) is in lane j-1 of row tau-1, (x, y+1) in lane j+1 of row tau+1: the differences of (wx, wy) to both,
+          // (udx, udy) = rc - w_u and (ddx, ddy) = w_d - rc, and sc + s_d (s_d = smoothness of (x, y+1)), each shift folded
+          // into its one consumer (ofdis_dev.h)
+          float udx, udy, ddx, ddy, sv_s;
+          vertical_terms(udx, udy, ddx, ddy, sv_s, rc.wx, rc.wy, rm.wx, rm.wy, rp.wx, rp.wy, sc, sm[(u + 2) % 3]);
+          const float sv_c = has_bot ? sv_s : 0.0f;
           const float sh_l = slot[u % 6].sh;         // (s_l + sc), 0 on column 0
           const float sv_t = from_prev(slot[u % 6].sv);  // (s_u + sc), 0 on row 0
           // (the difference to the left neighbour is the previous step's difference to the right neighbour)
@@ -395,10 +397,10 @@ __attribute__((amdgpu_waves_per_eu(NOC == 3 ? 2 : (MODE == 1 ? 3 : 1)))) void tv
           if constexpr (MODE == 1) {
             if (it == n_iters - 1) wdring[((u + 1) % 6) * 64 + lane] = make_float2(rc.wx, rc.wy);
           }
-          b1 -= sv_t * (rc.wx - wx_u);
-          b2 -= sv_t * (rc.wy - wy_u);
-          b1 += sv_c * (wx_d - rc.wx);
-          b2 += sv_c * (wy_d - rc.wy);
+          b1 -= sv_t * udx;
+          b2 -= sv_t * udy;
+          b1 += sv_c * ddx;
+          b2 += sv_c * ddy;
           FSlot& o = slot[(u + 1) % 6];
           o.a11 = a11; o.a12 = a12; o.a22 = a22; o.b1 = b1; o.b2 = b2; o.sh = sh_c; o.sv = sv_c;
           o.dur = rp.du; o.dvr = rp.dv;
@@ -431,30 +433,40 @@ __attribute__((amdgpu_waves_per_eu(NOC == 3 ? 2 : (MODE == 1 ? 3 : 1)))) void tv
           c.a22 = fdiv_by(A22, dd);
           c.a12 = -fdiv_by(c.a12, dd);
         }
-        float nu[NS], nv[NS];
+        // c.sh * rg + c.vt * t + c.sv * b + c.b, summed from the left, for every sweep s: rg = (x+1, y) and b = (x, y+1) of the
+        // sweep before (the old du, dv for sweep 0), t = (x, y-1) of this sweep.  t is in lane j-1 of the row sweep s left
+        // one step ago, b in lane j+1 of the row rg comes from; both shifts are folded into their products, those of all
+        // sweeps in one statement each (ofdis_dev.h) -- the sweeps of a step do not depend on each other.
+        float nu[NS], nv[NS], ou[NS], ov[NS], rgu[NS], rgv[NS], wvt[NS], wsv[NS], s1[NS], s2[NS];
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
           const FSlot& c = slot[(u - 2 * s + 12) % 6];
-          float ou, ov, rgu, rgv, bu, bv;
           if (s == 0) {
             const FSlot& p = slot[(u + 5) % 6];
-            ou = p.dur; ov = p.dvr;
-            rgu = c.dur; rgv = c.dvr;
-            bu = from_next(c.dur);
-            bv = from_next(c.dvr);
+            ou[s] = p.dur; ov[s] = p.dvr;
+            rgu[s] = c.dur; rgv[s] = c.dvr;
           } else {
-            ou = ru2[s - 1]; ov = rv2[s - 1];
-            rgu = ru[s - 1]; rgv = rv[s - 1];
-            bu = from_next(ru[s - 1]);
-            bv = from_next(rv[s - 1]);
+            ou[s] = ru2[s - 1]; ov[s] = rv2[s - 1];
+            rgu[s] = ru[s - 1]; rgv[s] = rv[s - 1];
           }
-          const float tu = from_prev(ru[s]), tv = from_prev(rv[s]);
+          wvt[s] = c.vt; wsv[s] = c.sv;
+        }
+        mul_pairs_from_prev(s1, s2, ru, rv, wvt);
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+          const FSlot& c = slot[(u - 2 * s + 12) % 6];
+          s1[s] = c.sh * rgu[s] + s1[s];
+          s2[s] = c.sh * rgv[s] + s2[s];
+        }
+        fmac_pairs_from_next(s1, s2, rgu, rgv, wsv);
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+          const FSlot& c = slot[(u - 2 * s + 12) % 6];
           const float lu = ru[s], lv = rv[s];
-          const float s1 = c.sh * rgu + c.vt * tu + c.sv * bu + c.b1;
-          const float s2 = c.sh * rgv + c.vt * tv + c.sv * bv + c.b2;
-          const float B1 = c.hl * lu + s1, B2 = c.hl * lv + s2;
-          nu[s] = ou + omega * (c.a11 * B1 + c.a12 * B2 - ou);
-          nv[s] = ov + omega * (c.a12 * B1 + c.a22 * B2 - ov);
+          const float t1 = s1[s] + c.b1, t2 = s2[s] + c.b2;
+          const float B1 = c.hl * lu + t1, B2 = c.hl * lv + t2;
+          nu[s] = ou[s] + omega * (c.a11 * B1 + c.a12 * B2 - ou[s]);
+          nv[s] = ov[s] + omega * (c.a12 * B1 + c.a22 * B2 - ov[s]);
         }
         {
           if (!MW) {  // for the next step's row: its column is in the first iteration, or PAST the last one -- nothing the

@@ -194,22 +194,22 @@ __global__ __launch_bounds__(256) void tv_fused_xcu_kernel(const FusedArgs a, co
         {
           const float sc = sm[(u + 1) % 3];
           const float s_r = sm[(u + 2) % 3];
-          const float s_d = from_next(sm[(u + 2) % 3]);
           const float sh_c = x1_last ? 0.0f : sc + s_r;
-          const float sv_c = has_bot ? sc + s_d : 0.0f;
           const FRow& rc = W[(u + 1) % 6];
           const FRow& rm = W[u % 6];
           const FRow& rp = W[(u + 2) % 6];
-          const float wx_u = from_prev(rm.wx), wy_u = from_prev(rm.wy);
-          const float wx_d = from_next(rp.wx), wy_d = from_next(rp.wy);
+          // rc - w_u, w_d - rc and sc + s_d with the lane shifts folded in (ofdis_dev.h; see the throughput kernel)
+          float udx, udy, ddx, ddy, sv_s;
+          vertical_terms(udx, udy, ddx, ddy, sv_s, rc.wx, rc.wy, rm.wx, rm.wy, rp.wx, rp.wy, sc, sm[(u + 2) % 3]);
+          const float sv_c = has_bot ? sv_s : 0.0f;
           const float sh_l = shp;
           const float sv_t = from_prev(svp);
           const float rdx = rp.wx - rc.wx, rdy = rp.wy - rc.wy;
           q1x = sh_l * ldx; q1y = sh_l * ldy;
           q2x = sh_c * rdx; q2y = sh_c * rdy;
           ldx = rdx; ldy = rdy;
-          q3x = sv_t * (rc.wx - wx_u); q3y = sv_t * (rc.wy - wy_u);
-          q4x = sv_c * (wx_d - rc.wx); q4y = sv_c * (wy_d - rc.wy);
+          q3x = sv_t * udx; q3y = sv_t * udy;
+          q4x = sv_c * ddx; q4y = sv_c * ddy;
           p_sh = sh_c; p_sv = sv_c; p_hl = sh_l; p_vt = sv_t; p_dur = rp.du; p_dvr = rp.dv;
           shp = sh_c; svp = sv_c;
           // du, dv of row t+2 for the data wave's next step
@@ -399,31 +399,34 @@ __global__ __launch_bounds__(256) void tv_fused_xcu_kernel(const FusedArgs a, co
             c.a11 = sr[0 * 64]; c.a12 = sr[1 * 64]; c.a22 = sr[2 * 64]; c.b1 = sr[3 * 64]; c.b2 = sr[4 * 64]; c.sh = sr[5 * 64];
             c.sv = sr[6 * 64]; c.dur = sr[7 * 64]; c.dvr = sr[8 * 64]; c.hl = sr[9 * 64]; c.vt = sr[10 * 64];
           }
-          float nu[NS], nv[NS];
+          // the upper neighbours' products c.vt * t of all sweeps (t = lane j-1 of the row sweep s left one step ago: nothing
+          // of this step) in one statement, each lower neighbour's c.sv * b in one of its own sweep: b is what sweep s-1
+          // produced in this very step (lane shifts folded into the products, ofdis_dev.h)
+          float nu[NS], nv[NS], wvt[NS], tpu[NS], tpv[NS];
+#pragma unroll
+          for (int s = 0; s < NS; ++s) wvt[s] = slot[(us - XC_SD * s + 12) % 6].vt;
+          mul_pairs_from_prev(tpu, tpv, ru, rv, wvt);
 #pragma unroll
           for (int s = 0; s < NS; ++s) {
             const FSlot& c = slot[(us - XC_SD * s + 12) % 6];
-            float ou, ov, rgu, rgv, bu, bv;
+            float ou, ov, rgu, rgv;
             if (s == 0) {
               const FSlot& p = slot[(us + 5) % 6];
               ou = p.dur; ov = p.dvr;
               rgu = c.dur; rgv = c.dvr;
-              bu = from_next(c.dur);
-              bv = from_next(c.dvr);
             } else {
               // sweep s trails sweep s-1 by ONE row: its right / lower neighbours are what sweep s-1 produced earlier in this
               // very step, its own old value what sweep s-1 produced one step ago (the throughput kernel keeps two rows between
               // sweeps so that the three are independent instructions streams; here every row of lag costs more than that)
               ou = ru[s - 1]; ov = rv[s - 1];
               rgu = nu[s - 1]; rgv = nv[s - 1];
-              bu = from_next(nu[s - 1]);
-              bv = from_next(nv[s - 1]);
             }
-            const float tu = from_prev(ru[s]), tv = from_prev(rv[s]);
             const float lu = ru[s], lv = rv[s];
-            const float s1 = c.sh * rgu + c.vt * tu + c.sv * bu + c.b1;
-            const float s2 = c.sh * rgv + c.vt * tv + c.sv * bv + c.b2;
-            const float B1 = c.hl * lu + s1, B2 = c.hl * lv + s2;
+            float s1[1] = {c.sh * rgu + tpu[s]}, s2[1] = {c.sh * rgv + tpv[s]};
+            const float xu[1] = {rgu}, xv[1] = {rgv}, wsv[1] = {c.sv};
+            fmac_pairs_from_next(s1, s2, xu, xv, wsv);
+            const float t1 = s1[0] + c.b1, t2 = s2[0] + c.b2;
+            const float B1 = c.hl * lu + t1, B2 = c.hl * lv + t2;
             nu[s] = ou + omega * (c.a11 * B1 + c.a12 * B2 - ou);
             nv[s] = ov + omega * (c.a12 * B1 + c.a22 * B2 - ov);
           }
