@@ -474,6 +474,75 @@ int ofdis_batch_dense_tracks(ofdis_batch* b, const uint8_t* frames, int first_fr
                              void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Trajectory-aligned descriptors of dense tracks: in the space-time tube around every track of ofdis_dense_tracks the histograms
+ * of gradient orientation (HOG), of flow orientation (HOF) and of the motion boundaries (MBHx, MBHy: the orientation of the
+ * gradient of each flow component), and the track's normalised displacements (trajectory shape) -- the second half of Wang,
+ * Klaeser, Schmid and Liu, "Dense trajectories and motion boundary descriptors", 2013.  Every histogram entry is a sum of
+ * integers, so its bits depend neither on the order of the sum nor on the kernel's mapping nor on the arithmetic contract.
+ *
+ * Inputs: the arrays of ofdis_dense_tracks.  frames [npairs+1][H][W][noc] u8, noc 1 or 3; Ffw = flow_fw [npairs][H][W][2] fp32
+ * -- or equally the residual flow of ofdis_motion_compensate, the camera-compensated flow "improved trajectories" feed into HOF
+ * and MBH; tracks [lmax+1][max_tracks][2], start, len [max_tracks]; info = the device array {ntracks, dropped} exactly as
+ * ofdis_dense_tracks wrote it (ntracks never reaches the host).  Parameters: lmax >= 1, the Lmax the tracks array was made
+ * with; patch N: even, 2 .. OFDIS_DESC_MAX_PATCH; nxy: 1 .. 4 with N % nxy == 0; nt: 1 .. 8 with nt <= lmax; min_flow finite and
+ * >= 0; and N*N*lmax <= 65536, so that no sum of addends <= 65535 reaches 2^32.
+ *
+ * Features, per pixel (x, y) of frame k / pair k.  "Clamped": neighbour indices clamp to the image, as in the texture test.
+ * Every float operation is a separately rounded fp32 operation, sqrtf is IEEE.
+ *   oct(a, b), the octant of a vector by comparisons only:
+ *     Q = 0 if a > 0 && b >= 0, (p, q) = (a, b);     Q = 1 if a <= 0 && b > 0, (p, q) = (b, -a);
+ *     Q = 2 if a < 0 && b <= 0, (p, q) = (-a, -b);   Q = 3 if a >= 0 && b < 0, (p, q) = (-b, a);
+ *     bin = 2*Q + (q >= p ? 1 : 0).  No case holds (zero vector, NaN): the pixel contributes nothing to that channel.
+ *   quant(m, s): m not finite: the pixel contributes nothing; else (int)floorf(fminf(m*s, 65535.f) + 0.5f).
+ *   HOG  (8 bins): g = the pixel value (noc 1) or the integer sum of the three channels (noc 3);
+ *        gx = g[y][x+1] - g[y][x-1], gy = g[y+1][x] - g[y-1][x] (clamped, doubled central differences, integers);
+ *        m = sqrtf((float)(gx*gx + gy*gy)) (the argument is below 2^24: exact); bin = oct(gx, gy), q = quant(m, 16).
+ *   HOF  (9 bins): (u, v) = Ffw[k][y][x], m = sqrtf(u*u + v*v).  m not finite: nothing.  m < min_flow: bin 8 with q = 256, the
+ *        "no motion" bin, counted as one pixel of motion as Wang's implementation does (this takes precedence over the
+ *        zero-vector rule).  Otherwise bin = oct(u, v), q = quant(m, 256).  With min_flow = 0 bin 8 stays empty.
+ *   MBHx (8 bins): gx = u[y][x+1] - u[y][x-1], gy = u[y+1][x] - u[y-1][x] (clamped); m = sqrtf(gx*gx + gy*gy);
+ *        bin = oct(gx, gy), q = quant(m, 4096).
+ *   MBHy (8 bins): the same on v.
+ *
+ * Tube.  For slot i < ntracks and step j = 0 .. len[i]-2, the pairs the track crossed (a track of length 1 has all-zero
+ * histograms; j < lmax always): k = start[i] + j, (px, py) = tracks[j][i], cx = (int)floorf(px + 0.5f), cy likewise.  The
+ * window pixels are x = cx - N/2 + a, y = cy - N/2 + b for a, b = 0 .. N-1; pixels outside the image contribute nothing.  The
+ * spatial cell of a pixel is (a / (N/nxy), b / (N/nxy)) (column, row), its temporal cell t = j*nt / lmax (integer division).
+ *
+ * Outputs.  hist = [max_tracks][D] u32, D = 33*nxy*nxy*nt, in the index order channel (HOG, HOF, MBHx, MBHy), t, cell row,
+ * cell column, bin: the channels start at 0, 8*C, 17*C and 25*C with C = nxy*nxy*nt.  Each entry is the sum of the q of its
+ * cell and bin.  shape = [max_tracks][lmax][2] fp32 or NULL: d_j = tracks[j+1][i] - tracks[j][i] for j < len[i]-1, S = the
+ * sequential sum over ascending j of sqrtf(dx*dx + dy*dy), shape[i][j] = (dx/S, dy/S) (IEEE division); (0, 0) when S == 0 and
+ * for j >= len[i]-1.  The call writes every entry of the slots < ntracks exactly once, reads and writes nothing of the slots
+ * >= ntracks, relies on no memset and does not synchronise with the host.
+ *
+ * Consequences.
+ *   Known value: zero flows and min_flow > 0 put all of HOF in bin 8: each cell holds 256 x (its pixels inside the image) x
+ *     (the steps of its temporal cell); MBHx and MBHy are all zero.  A constant frame has HOG all zero.
+ *   Translation: adding a constant vector to Ffw leaves MBHx and MBHy unchanged wherever the sums stay finite and no rounding
+ *     occurs -- stated for integer-valued test flows only.
+ *   Contract independence: integer sums of separately rounded values; one unit, compiled once, serves both contracts.
+ * Not provided: interpolation of a vote between neighbouring bins; normalisation on the device (of_dis_amd/tracking.py:
+ * normalize_descriptors, on the host); filtering of static or erratic tracks; a form that reads a sequence context's level
+ * flows directly -- every window pixel needs five flow values and is visited by about 40 overlapping windows, and rebuilding
+ * flow values from level flows already loses when each is used a handful of times (README: trajectory filter, global motion).
+ * The route is ofdis_batch_upsample_bidir -> ofdis_dense_tracks -> this call.
+ * of_dis_amd/tracking.py states the same definition in numpy (track_descriptors_ref).
+ * ------------------------------------------------------------------------------------------- */
+#define OFDIS_DESC_MAX_PATCH 64
+/* D = 33 * nxy * nxy * nt, or 0 for a patch, nxy or nt outside its range or a patch nxy does not divide */
+int ofdis_track_descriptor_dims(int patch, int nxy, int nt);
+/* device arrays as above; shape may be NULL.  One launch: one wavefront per slot, sized by max_tracks, the slots >= ntracks
+ * return at once.  OFDIS_ERR_INVALID before any device work: a NULL frames, flow_fw, tracks, start, len, info or hist; noc not 1
+ * or 3; sizes as ofdis_fb_check rejects them; npairs < 1; lmax < 1 or lmax > npairs; max_tracks outside
+ * 1 .. OFDIS_DT_MAX_TRACKS; patch, nxy or nt outside their ranges, patch odd or not a multiple of nxy, nt > lmax,
+ * patch*patch*lmax > 65536; min_flow negative or not finite. */
+int ofdis_track_descriptors(const uint8_t* frames, const float* flow_fw, int npairs, int width, int height, int noc,
+                            const float* tracks, const int* start, const int* len, const long long* info,
+                            int lmax, int max_tracks, int patch, int nxy, int nt, float min_flow,
+                            uint32_t* hist, float* shape /* or NULL */, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Motion-compensated temporal filtering of a clip: every frame averaged with its two neighbours warped onto it by the flow
  * (motion compensation), a neighbour left out where the forward-backward test flags the pixel, where its sample falls outside
  * the image and -- with a finite tau -- faded out as it differs from the pixel it would be averaged with.  The classical use

@@ -44,6 +44,7 @@ ABI_SYMBOLS = [
     "ofdis_track_points", "ofdis_batch_track_points",
     "ofdis_dense_tracks_cells", "ofdis_dense_tracks_work_bytes", "ofdis_seed_texture", "ofdis_dense_tracks",
     "ofdis_batch_dense_tracks",
+    "ofdis_track_descriptor_dims", "ofdis_track_descriptors",
     "ofdis_temporal_filter", "ofdis_batch_temporal_filter",
     "ofdis_trajectory_filter", "ofdis_batch_trajectory_filter",
     "ofdis_global_motion_work_bytes", "ofdis_global_motion", "ofdis_motion_compensate", "ofdis_batch_global_motion",
@@ -61,6 +62,7 @@ INTERP_MAX_TIMES = 16  # OFDIS_INTERP_MAX_TIMES
 ENC_F32, ENC_F16, ENC_U16, ENC_U8 = 0, 1, 2, 3  # OFDIS_ENC_*
 TRACK_MAX_POINTS = 1 << 24  # OFDIS_TRACK_MAX_POINTS
 DT_MAX_TRACKS, DT_MAX_STRIDE, DT_MAX_WINDOW = 1 << 24, 64, 7  # OFDIS_DT_MAX_*
+DESC_MAX_PATCH = 64  # OFDIS_DESC_MAX_PATCH
 TRAJ_MAX_RADIUS = 8  # OFDIS_TRAJ_MAX_RADIUS
 GM_MAX_SIDE, GM_MAX_FLOW, GM_MAX_ROUNDS = 8192, 4096.0, 8  # OFDIS_GM_MAX_*
 GM_TRANSLATION_ONLY, GM_AFFINE = 0, 1  # OFDIS_GM_* model
@@ -220,6 +222,9 @@ def lib():
                                          C.c_float, C.c_float, C.c_int, VP, VP, VP, VP, VP, C.c_size_t, VP]
         L.ofdis_batch_dense_tracks.argtypes = [VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                                C.c_float, C.c_int, VP, VP, VP, VP, C.c_int, C.c_int, VP]
+        L.ofdis_track_descriptor_dims.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.ofdis_track_descriptors.argtypes = [VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int,
+                                              C.c_int, C.c_int, C.c_float, VP, VP, VP]
         L.ofdis_temporal_filter.argtypes = [VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                             VP]
         L.ofdis_batch_temporal_filter.argtypes = [VP, VP, C.c_int, C.c_int, VP, VP, C.c_int, C.c_int, C.c_float, C.c_float,
@@ -679,6 +684,47 @@ def dense_tracks(frames, flow_fw, flow_rev, stride, window, min_eig, max_len=15,
                                    dwork.ptr, wb, None))
     check(lib().ofdis_sync(None))
     return _dense_results(outs, lmax, max_tracks)
+
+
+def track_descriptor_dims(patch, nxy, nt):
+    """ofdis_track_descriptor_dims: D = 33 * nxy^2 * nt, 0 for rejected parameters"""
+    return lib().ofdis_track_descriptor_dims(patch, nxy, nt)
+
+
+def track_descriptors_dev(frames_ptr, flow_ptr, npairs, width, height, noc, tracks_ptr, start_ptr, len_ptr, info_ptr, lmax,
+                          max_tracks, patch, nxy, nt, min_flow, hist_ptr, shape_ptr=None, stream=None):
+    """ofdis_track_descriptors on device pointers: the arrays ofdis_dense_tracks wrote (tracks [lmax + 1][max_tracks][2], start,
+    len [max_tracks], info) stay where they are; hist [max_tracks][D] uint32 and shape [max_tracks][lmax][2] float32 (or None)
+    are the caller's.  Enqueues on `stream` and returns; nothing synchronises with the host."""
+    check(lib().ofdis_track_descriptors(frames_ptr, flow_ptr, npairs, width, height, noc, tracks_ptr, start_ptr, len_ptr, info_ptr,
+                                        lmax, max_tracks, patch, nxy, nt, min_flow, hist_ptr, shape_ptr, stream))
+
+
+def track_descriptors(frames, flow_fw, tracks, start, length, patch, nxy, nt, min_flow, shape=True):
+    """ofdis_track_descriptors on host arrays: frames uint8 [npairs + 1, h, w] (gray) or [npairs + 1, h, w, 3], flow_fw
+    [npairs, h, w, 2] float32 (or the residual flow of motion_compensate), tracks [Lmax + 1, ntracks, 2], start, length
+    [ntracks] as dense_tracks returns them -> (hist uint32 [ntracks, D], shape float32 [ntracks, Lmax, 2] or None with
+    shape=False).  of_dis_amd/tracking.py: track_descriptors_ref is the numpy statement of the same definition."""
+    flow_fw = _f(flow_fw)
+    assert flow_fw.ndim == 4 and flow_fw.shape[-1] == 2, flow_fw.shape
+    npairs, h, w = flow_fw.shape[:3]
+    frames, noc = _clip_frames(frames, npairs + 1, h, w)
+    tracks = _f(tracks)
+    assert tracks.ndim == 3 and tracks.shape[0] >= 2 and tracks.shape[2] == 2, tracks.shape
+    lmax, n = tracks.shape[0] - 1, tracks.shape[1]
+    start, length = np.ascontiguousarray(start, np.int32), np.ascontiguousarray(length, np.int32)
+    assert start.shape == length.shape == (n,), (start.shape, length.shape, n)
+    D = track_descriptor_dims(patch, nxy, nt)
+    slots = max(n, 1)  # (the library takes no empty array)
+    dfr, dfw = Dev(frames), Dev(flow_fw)
+    dt = Dev(tracks if n else np.zeros((lmax + 1, 1, 2), _f32))
+    ds, dl = (Dev(a if n else np.zeros(1, np.int32)) for a in (start, length))
+    di = Dev(np.array([n, 0], np.int64))
+    dh, dsh = Dev(nbytes=max(1, slots * D * 4)), Dev(nbytes=slots * lmax * 8) if shape else None
+    track_descriptors_dev(dfr.ptr, dfw.ptr, npairs, w, h, noc, dt.ptr, ds.ptr, dl.ptr, di.ptr, lmax, slots, patch, nxy, nt,
+                          min_flow, dh.ptr, dsh.ptr if dsh else None)
+    check(lib().ofdis_sync(None))
+    return (dh.get((slots, D), np.uint32)[:n].copy(), dsh.get((slots, lmax, 2), _f32)[:n].copy() if dsh else None)
 
 
 def temporal_filter(frames, flow_fw, flow_rev, mask_fw=None, mask_rev=None, wn=1.0, tau=np.inf, support=True):

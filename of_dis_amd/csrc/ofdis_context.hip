@@ -924,6 +924,38 @@ int ofdis_batch_dense_tracks(ofdis_batch* b, const uint8_t* frames, int first_fr
   return OFDIS_OK;
 }
 
+// ------------------------------------------------------------------------------------ track descriptors (ofdis_descriptors.hip)
+static int desc_params_check(int patch, int nxy, int nt) {
+  if (patch < 2 || patch > OFDIS_DESC_MAX_PATCH || patch % 2) return fail(OFDIS_ERR_INVALID, "patch must be even, 2..OFDIS_DESC_MAX_PATCH");
+  if (nxy < 1 || nxy > 4 || patch % nxy) return fail(OFDIS_ERR_INVALID, "nxy must be 1..4 and divide patch");
+  if (nt < 1 || nt > 8) return fail(OFDIS_ERR_INVALID, "nt outside 1..8");
+  return OFDIS_OK;
+}
+
+int ofdis_track_descriptor_dims(int patch, int nxy, int nt) { return desc_params_check(patch, nxy, nt) ? 0 : 33 * nxy * nxy * nt; }
+
+int ofdis_track_descriptors(const uint8_t* frames, const float* flow_fw, int npairs, int width, int height, int noc,
+                            const float* tracks, const int* start, const int* len, const long long* info, int lmax,
+                            int max_tracks, int patch, int nxy, int nt, float min_flow, uint32_t* hist, float* shape,
+                            void* stream) {
+  if (!frames) return fail(OFDIS_ERR_INVALID, "frames is NULL");
+  if (!flow_fw) return fail(OFDIS_ERR_INVALID, "flow_fw is NULL");
+  if (!tracks || !start || !len || !info) return fail(OFDIS_ERR_INVALID, "tracks, start, len or info is NULL");
+  if (!hist) return fail(OFDIS_ERR_INVALID, "hist is NULL");
+  if (noc != 1 && noc != 3) return fail(OFDIS_ERR_INVALID, "noc must be 1 or 3");
+  if (width < 1 || height < 1 || (long long)width * height > (1ll << 30)) return fail(OFDIS_ERR_INVALID, "bad sizes");
+  if (npairs < 1) return fail(OFDIS_ERR_INVALID, "bad sizes (npairs < 1)");
+  if (lmax < 1 || lmax > npairs) return fail(OFDIS_ERR_INVALID, "lmax outside 1..npairs");
+  if (max_tracks < 1 || max_tracks > OFDIS_DT_MAX_TRACKS) return fail(OFDIS_ERR_INVALID, "max_tracks outside 1..OFDIS_DT_MAX_TRACKS");
+  if (int rc = desc_params_check(patch, nxy, nt)) return rc;
+  if (nt > lmax) return fail(OFDIS_ERR_INVALID, "nt above lmax");
+  if ((long long)patch * patch * lmax > 65536) return fail(OFDIS_ERR_INVALID, "patch * patch * lmax above 65536");
+  if (!(min_flow >= 0.f) || std::isinf(min_flow)) return fail(OFDIS_ERR_INVALID, "min_flow must be finite and >= 0");
+  HIPCHK(launch_track_descriptors(frames, flow_fw, npairs, width, height, noc, tracks, start, len, info, lmax, max_tracks, patch,
+                                  nxy, nt, min_flow, hist, shape, (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
 // ------------------------------------------------------------------------------------ temporal filter (ofdis_tfilter.hip)
 static int tfilter_args_check(const uint8_t* frames, const uint8_t* out, int noc, float wn, float tau) {
   if (!frames || !out) return fail(OFDIS_ERR_INVALID, "bad arguments");

@@ -259,6 +259,12 @@ hipError_t launch_dense_tracks(const uint8_t* frames, const float* fw, const flo
 hipError_t launch_dense_tracks_level(const uint8_t* frames, const float* fw, const float* rev, int npairs, UpGeom g, int noc,
                                      int stride, int window, int min_eig, int max_len, float alpha, float beta, int max_tracks,
                                      float* tracks, int* start, int* len, long long* info, void* work, hipStream_t s);
+// trajectory-aligned descriptors (include/ofdis.h: ofdis_track_descriptors; ofdis_descriptors.hip): the arrays of
+// launch_dense_tracks in, hist [max_tracks][33 nxy^2 nt] u32 and shape [max_tracks][lmax][2] (or null) out; one wavefront per
+// slot, the slots >= info[0] return at once
+hipError_t launch_track_descriptors(const uint8_t* frames, const float* flow, int npairs, int w, int h, int noc, const float* tracks,
+                                    const int* start, const int* len, const long long* info, int lmax, int max_tracks, int patch,
+                                    int nxy, int nt, float min_flow, uint32_t* hist, float* shape, hipStream_t s);
 // motion-compensated temporal filter (include/ofdis.h: ofdis_temporal_filter; ofdis_tfilter.hip).  On materialised arrays:
 // frames, out [npairs + 1][h][w][noc] u8, AoS flows [npairs][h][w][2], masks [npairs][h][w] or null, support
 // [npairs + 1][h][w] or null

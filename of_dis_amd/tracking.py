@@ -2,7 +2,9 @@
 definition operation by operation in float32, one rounding at a time.  Needs numpy only (no GPU, no library): the tests compare
 the kernels against `track_ref` bit for bit, and a user can read a track array with `ended`.  Below it, the dense trajectories
 (ofdis_seed_texture, ofdis_dense_tracks, ofdis_batch_dense_tracks): the grid, the integer texture test and the frame loop of
-advance, occupancy and seeding (`dense_tracks_ref`).
+advance, occupancy and seeding (`dense_tracks_ref`), and the descriptors of those tracks (ofdis_track_descriptors): HOG, HOF, MBH
+and trajectory shape (`track_descriptors_ref`), where their channels lie (`descriptor_layout`) and their normalisation on the
+host (`normalize_descriptors`).
 
     from of_dis_amd import tracking
     tracks, counts = batch.track_points(tracking.grid_seeds(w, h, 5), w, h)       # [n + 1][npoints][2], [npoints]
@@ -10,6 +12,8 @@ advance, occupancy and seeding (`dense_tracks_ref`).
     T = tracking.min_eig_from_gradient(4.0, window=2, noc=1)                     # mean-tensor eigenvalue 4 -> the test's units
     dtracks, start, length, info = batch.dense_tracks(frames_ptr, w, h, 5, 2, T)  # [Lmax + 1][ntracks][2], step-major
     by_frame = tracking.to_frame_major(dtracks, start, length, n)                # [n + 1][ntracks][2], the layout above
+    hist, shape = capi.track_descriptors(frames, flow_fw, dtracks, start, length, 32, 2, 3, 0.4)   # [ntracks][396] u32
+    desc = tracking.normalize_descriptors(hist, tracking.descriptor_layout(32, 2, 3), "rootsift")   # float64, per channel
 """
 import numpy as np
 
@@ -251,4 +255,161 @@ def to_frame_major(tracks, start, length, npairs):
     for j in range(tracks.shape[0]):
         i = np.flatnonzero(length > j)
         out[start[i] + j, i] = tracks[j, i]
+    return out
+
+
+# ------------------------------------------------------------------ trajectory-aligned descriptors (ofdis_track_descriptors)
+DESC_MAX_PATCH = 64  # include/ofdis.h: OFDIS_DESC_MAX_PATCH
+DESC_CHANNELS = (("hog", 8, 16.0), ("hof", 9, 256.0), ("mbhx", 8, 4096.0), ("mbhy", 8, 4096.0))  # name, bins, scale of quant
+DESC_Q_MAX = 65535
+
+
+def descriptor_layout(patch, nxy, nt):
+    """Where the channels lie in a descriptor: {"dims": D = 33 * nxy^2 * nt, "cells": (nt, nxy, nxy), "channels": {name:
+    (offset, bins)}} for "hog", "hof", "mbhx", "mbhy"; a channel is the block [offset, offset + bins * nt * nxy^2) of a hist row,
+    shaped [nt][cell row][cell column][bin].  ValueError for the parameters ofdis_track_descriptor_dims answers with 0."""
+    if not (2 <= patch <= DESC_MAX_PATCH and patch % 2 == 0 and 1 <= nxy <= 4 and patch % nxy == 0 and 1 <= nt <= 8):
+        raise ValueError(f"patch {patch} (even, 2..{DESC_MAX_PATCH}), nxy {nxy} (1..4, dividing patch), nt {nt} (1..8)")
+    cells = nt * nxy * nxy
+    channels, at = {}, 0
+    for name, bins, _ in DESC_CHANNELS:
+        channels[name] = (at, bins)
+        at += bins * cells
+    return {"dims": at, "cells": (nt, nxy, nxy), "channels": channels}
+
+
+def _octant(a, b):
+    """oct(a, b) of include/ofdis.h by comparisons only: the bin 0..7, -1 where no case holds (zero vector, NaN)"""
+    with np.errstate(invalid="ignore"):
+        cases = [(a > 0) & (b >= 0), (a <= 0) & (b > 0), (a < 0) & (b <= 0), (a >= 0) & (b < 0)]
+        pq = [(a, b), (b, -a), (-a, -b), (-b, a)]
+        out = np.full(np.shape(a), -1, np.int64)
+        for Q in (3, 2, 1, 0):  # (the first case that holds wins)
+            p, q = pq[Q]
+            out = np.where(cases[Q], 2 * Q + (q >= p), out)
+    return out
+
+
+def _quant(m, s):
+    """quant(m, s) for finite float32 m: (values int64, clamped bool)"""
+    with np.errstate(over="ignore"):
+        ms = m * _f32(s)
+    assert ms.dtype == _f32
+    return np.floor(np.minimum(ms, _f32(DESC_Q_MAX)) + _f32(0.5)).astype(np.int64), ms > _f32(DESC_Q_MAX)
+
+
+def _central(a):
+    """(a[y][x+1] - a[y][x-1], a[y+1][x] - a[y-1][x]) with clamped neighbours"""
+    h, w = a.shape
+    xi, yi = np.arange(w), np.arange(h)
+    with np.errstate(all="ignore"):
+        return a[:, np.minimum(xi + 1, w - 1)] - a[:, np.maximum(xi - 1, 0)], a[np.minimum(yi + 1, h - 1)] - a[np.maximum(yi - 1, 0)]
+
+
+def descriptor_features(frame, flow, min_flow):
+    """frame uint8 [h][w] or [h][w][noc], flow float32 [h][w][2] -> per channel of DESC_CHANNELS (bin int64 [h][w], -1 where the
+    pixel contributes nothing; q int64 [h][w]; clamped bool [h][w]): the votes of include/ofdis.h, one rounding at a time"""
+    frame, flow = np.asarray(frame), np.asarray(flow, _f32)
+    g = frame.astype(np.int64) if frame.ndim == 2 else frame.astype(np.int64).sum(-1)
+    out = []
+    gx, gy = _central(g)
+    m = np.sqrt((gx * gx + gy * gy).astype(_f32))
+    q, cl = _quant(m, 16.0)
+    out.append((_octant(gx, gy), q, cl))
+    u, v = flow[..., 0], flow[..., 1]
+    with np.errstate(all="ignore"):
+        m = np.sqrt(u * u + v * v)
+        finite = np.isfinite(m)
+        still = finite & (m < _f32(min_flow))
+        q, cl = _quant(np.where(finite, m, _f32(0)), 256.0)
+    out.append((np.where(still, 8, np.where(finite, _octant(u, v), -1)), np.where(still, 256, q), cl & finite & ~still))
+    for c in (u, v):
+        gx, gy = _central(c)
+        with np.errstate(all="ignore"):
+            m = np.sqrt(gx * gx + gy * gy)
+            finite = np.isfinite(m)
+            q, cl = _quant(np.where(finite, m, _f32(0)), 4096.0)
+        assert m.dtype == _f32
+        out.append((np.where(finite, _octant(gx, gy), -1), q, cl & finite))
+    return out
+
+
+def track_descriptors_ref(frames, flow_fw, tracks, start, length, patch, nxy, nt, min_flow, stats=None):
+    """The definition of ofdis_track_descriptors in numpy.  frames uint8 [npairs + 1][h][w] (+ [noc]), flow_fw float32
+    [npairs][h][w][2], tracks [lmax + 1][ntracks][2], start, length [ntracks] as dense_tracks_ref returns them -> (hist uint32
+    [ntracks][D], shape float32 [ntracks][lmax][2]).  stats: an optional dict that receives "windows" (the windows visited: one
+    per track and step), "cut" (those with a pixel outside the image), and over the window pixels inside the image and the four
+    channels "clamped" (values quant clamped to 65535) and "skipped" (pixels that contribute nothing: no octant, not finite)."""
+    frames, flow_fw = np.asarray(frames), np.asarray(flow_fw, _f32)
+    tracks, start, length = np.asarray(tracks, _f32), np.asarray(start, np.int64), np.asarray(length, np.int64)
+    npairs, h, w = flow_fw.shape[:3]
+    lmax, n = tracks.shape[0] - 1, tracks.shape[1]
+    layout = descriptor_layout(patch, nxy, nt)
+    assert 1 <= nt <= lmax <= npairs and patch * patch * lmax <= 65536 and len(frames) == npairs + 1
+    assert min_flow >= 0 and np.isfinite(min_flow)
+    assert n == 0 or (length.min() >= 1 and length.max() <= lmax + 1 and start.min() >= 0 and (start + length - 1).max() <= npairs)
+    D, cs = layout["dims"], patch // nxy
+    hist = np.zeros(n * D, np.float64)  # (sums of integers below 2^32: exact)
+    count = {"windows": 0, "cut": 0, "clamped": 0, "skipped": 0}
+    feats = {}
+    ab = np.arange(patch)
+    b_, a_ = np.meshgrid(ab, ab, indexing="ij")  # window row b, column a
+    cell = ((b_ // cs) * nxy + a_ // cs).ravel()
+    a_, b_ = a_.ravel(), b_.ravel()
+    for j in range(lmax):
+        t = j * nt // lmax
+        idx = np.flatnonzero(length - 1 > j)
+        for k in np.unique(start[idx] + j):
+            i = idx[start[idx] + j == k]
+            if k not in feats:
+                feats[k] = descriptor_features(frames[k], flow_fw[k], min_flow)
+            cx = np.floor(tracks[j, i, 0] + _f32(0.5)).astype(np.int64)
+            cy = np.floor(tracks[j, i, 1] + _f32(0.5)).astype(np.int64)
+            x, y = cx[:, None] - patch // 2 + a_[None], cy[:, None] - patch // 2 + b_[None]
+            ok = (x >= 0) & (x < w) & (y >= 0) & (y < h)
+            count["windows"] += len(i)
+            count["cut"] += int((~ok.all(1)).sum())
+            x, y = x[ok], y[ok]
+            row = np.broadcast_to(i[:, None] * D, ok.shape)[ok]  # the slot's row of hist
+            tc = t * nxy * nxy + np.broadcast_to(cell[None], ok.shape)[ok]  # (t, cell row, cell column)
+            for (name, bins, _), (bn, q, cl) in zip(DESC_CHANNELS, feats[k]):
+                bv, qv = bn[y, x], q[y, x]
+                votes = bv >= 0
+                count["skipped"] += int((~votes).sum())
+                count["clamped"] += int(cl[y, x].sum())
+                at = row + layout["channels"][name][0] + tc * bins + bv
+                hist += np.bincount(at[votes], weights=qv[votes], minlength=n * D)
+    assert hist.max(initial=0) < 2 ** 32
+    # the trajectory shape: the sequential float32 sum of the step lengths, then IEEE divisions
+    shape = np.zeros((n, lmax, 2), _f32)
+    S = np.zeros(n, _f32)
+    with np.errstate(all="ignore"):
+        d = tracks[1:] - tracks[:-1]  # [lmax][n][2]
+        for j in range(lmax):
+            on = length - 1 > j
+            S[on] = S[on] + np.sqrt(d[j, on, 0] * d[j, on, 0] + d[j, on, 1] * d[j, on, 1])
+        for j in range(lmax):
+            on = (length - 1 > j) & (S != 0)
+            shape[on, j] = d[j, on] / S[on, None]
+    if stats is not None:
+        stats.update(count)
+    return hist.reshape(n, D).astype(np.uint32), shape
+
+
+def normalize_descriptors(hist, layout, how="l2"):
+    """hist [ntracks][D] (uint32 as the library writes it) -> float64 [ntracks][D], every channel of `layout`
+    (descriptor_layout) normalised on its own: "l2": divided by its Euclidean norm; "rootsift": divided by its sum, then the
+    square root (Arandjelovic and Zisserman 2012, as Wang et al. use it).  An all-zero channel stays zero."""
+    if how not in ("l2", "rootsift"):
+        raise ValueError(f"how = {how!r}: 'l2' or 'rootsift'")
+    hist = np.asarray(hist)
+    assert hist.ndim == 2 and hist.shape[1] == layout["dims"], (hist.shape, layout["dims"])
+    out = hist.astype(np.float64)
+    cells = int(np.prod(layout["cells"]))
+    for off, bins in layout["channels"].values():
+        v = out[:, off:off + bins * cells]
+        norm = np.sqrt((v * v).sum(1)) if how == "l2" else v.sum(1)
+        v /= np.where(norm > 0, norm, 1.0)[:, None]
+        if how == "rootsift":
+            np.sqrt(v, out=v)
     return out

@@ -5,7 +5,8 @@ run_DE_* binaries do (run_dense.cpp:185-431), for a list of pairs at once and wi
 
     python tools/flow_images.py [--rgb] [--stereo [--lr [--fill MODE]]] [--op 1..4] [--fused] [--reverse] img1a img1b out1.flo [img2a img2b out2.flo ...]
     python tools/flow_images.py --sequence [--rgb] [--op 1..4] [--fused] [--reverse [--tracks STRIDE]
-                                [--dense-tracks STRIDE[:WINDOW[:MIN_EIG[:MAX_LEN]]]]] img0 img1 ... imgN stem
+                                [--dense-tracks STRIDE[:WINDOW[:MIN_EIG[:MAX_LEN]]] [--descriptors N:NXY:NT:MIN_FLOW]]]
+                                img0 img1 ... imgN stem
 
 All pairs must have one size.  --fused selects the FMA / fast-reciprocal arithmetic contract (default: the exact one, bit for
 bit what run_OF_INT / run_OF_RGB write).  --reverse (optical flow only) also writes, next to <stem>.flo, the reverse flow
@@ -24,7 +25,11 @@ float32 [N + 1][points][2] (x, y; NaN where a track has ended), and <stem>_count
 --dense-tracks STRIDE[:WINDOW[:MIN_EIG[:MAX_LEN]]] (defaults 2, 0 and 15) writes the dense trajectories of the clip
 (ofdis_batch_dense_tracks: the textured centres of a grid of that stride, the cells that lose their track seeded again in every
 frame, a track at most MAX_LEN + 1 frames long): <stem>_dtracks.npy, float32 [Lmax + 1][tracks][2], step-major (entry [j][i] is
-track i in frame start[i] + j; NaN beyond its length), <stem>_dstart.npy and <stem>_dlen.npy, int32 [tracks]."""
+track i in frame start[i] + j; NaN beyond its length), <stem>_dstart.npy and <stem>_dlen.npy, int32 [tracks].  With
+--descriptors N:NXY:NT:MIN_FLOW (needs --dense-tracks) the descriptors of those tracks follow (ofdis_track_descriptors on the
+forward flows the run writes: an N x N window in NXY x NXY x NT cells, flows below MIN_FLOW in HOF's ninth bin):
+<stem>_dhist.npy, uint32 [tracks][33 * NXY^2 * NT] (HOG, HOF, MBHx, MBHy: of_dis_amd/tracking.py descriptor_layout), and
+<stem>_dshape.npy, float32 [tracks][Lmax][2]."""
 import os
 import struct
 import sys
@@ -87,6 +92,7 @@ def main(argv):
     fill = "none"
     track_stride = 0
     dense = None
+    desc = None
     args = []
     it = iter(argv)
     for a in it:
@@ -106,12 +112,20 @@ def main(argv):
             if not 1 <= len(dense) <= 4:
                 sys.exit("--dense-tracks STRIDE[:WINDOW[:MIN_EIG[:MAX_LEN]]]")
             dense += [2, 0, 15][len(dense) - 1:]
+        elif a == "--descriptors":
+            try:
+                n, nxy, nt, min_flow = next(it).split(":")
+                desc = [int(n), int(nxy), int(nt), float(min_flow)]
+            except ValueError:
+                sys.exit("--descriptors N:NXY:NT:MIN_FLOW")
         else:
             args.append(a)
     if track_stride < 0 or (track_stride and not (opts["--sequence"] and opts["--reverse"])):
         sys.exit("--tracks STRIDE (>= 1) needs --sequence --reverse")
     if dense and not (opts["--sequence"] and opts["--reverse"]):
         sys.exit("--dense-tracks needs --sequence --reverse")
+    if desc and not dense:
+        sys.exit("--descriptors needs --dense-tracks")
     stem = args[-1] if args else None
     if opts["--sequence"]:
         if opts["--stereo"]:
@@ -173,6 +187,14 @@ def main(argv):
               f"{info[1]} seeds dropped), mean length {dlen.mean() if len(dlen) else 0:.2f} frames")
     if opts["--reverse"]:            # both directions and both masks in one launch; the forward flow is upsample()'s
         full, rev, mask_fw, mask_rev = b.upsample_bidir(w, h)
+        if desc:                     # on the materialised forward flows (include/ofdis.h: no form on the level flows)
+            if not 1 <= desc[2] <= dtracks.shape[0] - 1 or not capi.track_descriptor_dims(*desc[:3]):
+                sys.exit("--descriptors: N even, 2..64; NXY 1..4, dividing N; NT 1..8 and at most the tracks' Lmax")
+            dhist, dshape = capi.track_descriptors(np.stack(frames_a + frames_b), full, dtracks, dstart, dlen, *desc)
+            np.save(stem + "_dhist.npy", dhist)
+            np.save(stem + "_dshape.npy", dshape)
+            print(f"{stem}_dhist.npy, _dshape.npy: {dhist.shape[0]} descriptors of {dhist.shape[1]} entries, largest "
+                  f"{int(dhist.max(initial=0))}")
     else:
         full = b.upsample(w, h)      # [pairs][h][w][2] (one channel in stereo mode)
     b.close()
