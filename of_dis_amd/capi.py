@@ -402,6 +402,25 @@ def _f(a):
     return np.ascontiguousarray(a, dtype=_f32)
 
 
+def _pair_flows(flow_fw, flow_rev=None):
+    """flow_fw [npairs, h, w, 2] float32 and its reverse partner, the same shape or None -> (flow_fw, flow_rev, npairs, h, w)"""
+    flow_fw = _f(flow_fw)
+    assert flow_fw.ndim == 4 and flow_fw.shape[-1] == 2, flow_fw.shape
+    if flow_rev is not None:
+        flow_rev = _f(flow_rev)
+        assert flow_rev.shape == flow_fw.shape, (flow_rev.shape, flow_fw.shape)
+    return (flow_fw, flow_rev) + flow_fw.shape[:3]
+
+
+def _mask_dev(mask, shape):
+    """an optional uint8 mask of `shape` on the device: a Dev, or None for None"""
+    if mask is None:
+        return None
+    mask = np.ascontiguousarray(mask, np.uint8)
+    assert mask.shape == shape, (mask.shape, shape)
+    return Dev(mask)
+
+
 # ------------------------------------------------------------------ per-function entry points (numpy in/out)
 def image_warp(src, wx, wy):
     """src [B,noc,h,w], wx/wy [B,h,w] -> dst [B,noc,h,w], mask [B,h,w]"""
@@ -566,12 +585,7 @@ def interpolate(img_a, img_b, flow_fw, flow_rev, times, mask_fw=None, mask_rev=N
     n = int(np.prod(lead, dtype=np.int64))
     t, tp = _times(times)
     devs = [Dev(x) for x in (img_a, img_b, flow_fw, flow_rev)]
-    masks = []
-    for m in (mask_fw, mask_rev):
-        if m is not None:
-            m = np.ascontiguousarray(m, np.uint8)
-            assert m.shape == flow_fw.shape[:-1], (m.shape, flow_fw.shape)
-        masks.append(Dev(m) if m is not None else None)
+    masks = [_mask_dev(m, flow_fw.shape[:-1]) for m in (mask_fw, mask_rev)]
     shape = lead + (t.size, h, w) + ((3,) if noc == 3 else ())
     do = Dev(nbytes=max(1, int(np.prod(shape, dtype=np.int64))))
     check(lib().ofdis_interpolate(*[d.ptr for d in devs], *[m.ptr if m else None for m in masks], do.ptr, n, w, h, noc, tp,
@@ -594,12 +608,7 @@ def track_points(flow_fw, flow_rev, seeds, seed_frame=None, max_steps=0, alpha=F
     (frame k + 1 -> k) or None (no consistency test), seeds [npoints, 2] float32 (x, y), seed_frame [npoints] int32 or None
     (all 0) -> (tracks [npairs + 1, npoints, 2] float32, counts [npoints] int32).  of_dis_amd/tracking.py: track_ref is the
     numpy statement of the same arithmetic."""
-    flow_fw = _f(flow_fw)
-    assert flow_fw.ndim == 4 and flow_fw.shape[-1] == 2, flow_fw.shape
-    npairs, h, w = flow_fw.shape[:3]
-    if flow_rev is not None:
-        flow_rev = _f(flow_rev)
-        assert flow_rev.shape == flow_fw.shape, (flow_rev.shape, flow_fw.shape)
+    flow_fw, flow_rev, npairs, h, w = _pair_flows(flow_fw, flow_rev)
     seeds, seed_frame = _track_inputs(seeds, seed_frame)
     n = seeds.shape[0]
     dfw, drev = Dev(flow_fw), Dev(flow_rev) if flow_rev is not None else None
@@ -664,12 +673,7 @@ def dense_tracks(frames, flow_fw, flow_rev, stride, window, min_eig, max_len=15,
     int32, len [ntracks] int32, info int64 [2] = (ntracks, dropped)): the slots below ntracks.  max_tracks None: room for every
     seed (npairs x cells, at most DT_MAX_TRACKS).  of_dis_amd/tracking.py: dense_tracks_ref is the numpy statement of the same
     process."""
-    flow_fw = _f(flow_fw)
-    assert flow_fw.ndim == 4 and flow_fw.shape[-1] == 2, flow_fw.shape
-    npairs, h, w = flow_fw.shape[:3]
-    if flow_rev is not None:
-        flow_rev = _f(flow_rev)
-        assert flow_rev.shape == flow_fw.shape, (flow_rev.shape, flow_fw.shape)
+    flow_fw, flow_rev, npairs, h, w = _pair_flows(flow_fw, flow_rev)
     frames, noc = _clip_frames(frames, npairs + 1, h, w)
     ncx, ncy = dense_tracks_cells(w, h, stride)
     if max_tracks is None:
@@ -705,9 +709,7 @@ def track_descriptors(frames, flow_fw, tracks, start, length, patch, nxy, nt, mi
     [npairs, h, w, 2] float32 (or the residual flow of motion_compensate), tracks [Lmax + 1, ntracks, 2], start, length
     [ntracks] as dense_tracks returns them -> (hist uint32 [ntracks, D], shape float32 [ntracks, Lmax, 2] or None with
     shape=False).  of_dis_amd/tracking.py: track_descriptors_ref is the numpy statement of the same definition."""
-    flow_fw = _f(flow_fw)
-    assert flow_fw.ndim == 4 and flow_fw.shape[-1] == 2, flow_fw.shape
-    npairs, h, w = flow_fw.shape[:3]
+    flow_fw, _, npairs, h, w = _pair_flows(flow_fw)
     frames, noc = _clip_frames(frames, npairs + 1, h, w)
     tracks = _f(tracks)
     assert tracks.ndim == 3 and tracks.shape[0] >= 2 and tracks.shape[2] == 2, tracks.shape
@@ -732,19 +734,10 @@ def temporal_filter(frames, flow_fw, flow_rev, mask_fw=None, mask_rev=None, wn=1
     [npairs, h, w, 2] float32 (frame k -> k + 1 and frame k + 1 -> k); masks uint8 [npairs, h, w] or None (all consistent).
     Returns (out, the shape of frames; support uint8 [npairs + 1, h, w], or None with support=False: passed as NULL).
     of_dis_amd/temporal.py: temporal_filter_ref is the numpy statement of the same arithmetic."""
-    flow_fw, flow_rev = _f(flow_fw), _f(flow_rev)
-    assert flow_fw.shape == flow_rev.shape and flow_fw.ndim == 4 and flow_fw.shape[-1] == 2, (flow_fw.shape, flow_rev.shape)
-    npairs, h, w = flow_fw.shape[:3]
-    frames = np.ascontiguousarray(frames, np.uint8)
-    noc = 1 if frames.ndim == 3 else 3
-    assert frames.shape == (npairs + 1, h, w) + ((3,) if noc == 3 else ()), (frames.shape, flow_fw.shape)
+    flow_fw, flow_rev, npairs, h, w = _pair_flows(flow_fw, _f(flow_rev))
+    frames, noc = _clip_frames(frames, npairs + 1, h, w)
     devs = [Dev(x) for x in (frames, flow_fw, flow_rev)]
-    masks = []
-    for m in (mask_fw, mask_rev):
-        if m is not None:
-            m = np.ascontiguousarray(m, np.uint8)
-            assert m.shape == (npairs, h, w), (m.shape, flow_fw.shape)
-        masks.append(Dev(m) if m is not None else None)
+    masks = [_mask_dev(m, (npairs, h, w)) for m in (mask_fw, mask_rev)]
     do = Dev(nbytes=frames.nbytes)
     ds = Dev(nbytes=(npairs + 1) * h * w) if support else None
     check(lib().ofdis_temporal_filter(*[d.ptr for d in devs], *[m.ptr if m else None for m in masks], do.ptr,
@@ -764,12 +757,8 @@ def trajectory_filter(frames, flow_fw, flow_rev, weights, tau=np.inf, fb_check=T
     [0, 1], its length is the radius.  Returns (out, the shape of frames; support uint8 [npairs + 1, h, w] = nf | nb << 4, or
     None with support=False: passed as NULL).  of_dis_amd/temporal.py: trajectory_filter_ref is the numpy statement of the same
     arithmetic, trajectory_weights makes the weights and reach splits the support."""
-    flow_fw, flow_rev = _f(flow_fw), _f(flow_rev)
-    assert flow_fw.shape == flow_rev.shape and flow_fw.ndim == 4 and flow_fw.shape[-1] == 2, (flow_fw.shape, flow_rev.shape)
-    npairs, h, w = flow_fw.shape[:3]
-    frames = np.ascontiguousarray(frames, np.uint8)
-    noc = 1 if frames.ndim == 3 else 3
-    assert frames.shape == (npairs + 1, h, w) + ((3,) if noc == 3 else ()), (frames.shape, flow_fw.shape)
+    flow_fw, flow_rev, npairs, h, w = _pair_flows(flow_fw, _f(flow_rev))
+    frames, noc = _clip_frames(frames, npairs + 1, h, w)
     wts, wp = _weights(weights)
     devs = [Dev(x) for x in (frames, flow_fw, flow_rev)]
     do = Dev(nbytes=frames.nbytes)
@@ -781,21 +770,17 @@ def trajectory_filter(frames, flow_fw, flow_rev, weights, tau=np.inf, fb_check=T
 
 
 def _gm_inputs(flow, mask):
-    flow = _f(flow)
-    assert flow.ndim == 4 and flow.shape[-1] == 2, flow.shape
-    if mask is not None:
-        mask = np.ascontiguousarray(mask, np.uint8)
-        assert mask.shape == flow.shape[:3], (mask.shape, flow.shape)
-    return flow, mask
+    """(flow [npairs, h, w, 2] float32, its optional mask on the device, npairs, h, w)"""
+    flow, _, npairs, h, w = _pair_flows(flow)
+    return flow, _mask_dev(mask, (npairs, h, w)), npairs, h, w
 
 
 def global_motion(flow, mask=None, model=GM_AFFINE, rounds=3, thresh=1.0):
     """ofdis_global_motion on the device: flow [npairs, h, w, 2] float32, mask uint8 [npairs, h, w] or None (all consistent)
     -> (models [npairs, 6] float64, stats [npairs, 3] int64: |S_0|, the size of the last set used, the status).
     of_dis_amd/gmotion.py: global_motion_ref is the numpy statement of the same arithmetic."""
-    flow, mask = _gm_inputs(flow, mask)
-    npairs, h, w = flow.shape[:3]
-    df, dm = Dev(flow), Dev(mask) if mask is not None else None
+    flow, dm, npairs, h, w = _gm_inputs(flow, mask)
+    df = Dev(flow)
     dmodels, dstats = Dev(nbytes=max(8, npairs * 48)), Dev(nbytes=max(8, npairs * 24))
     wb = lib().ofdis_global_motion_work_bytes(npairs, w, h)
     dwork = Dev(nbytes=max(8, wb))
@@ -809,11 +794,10 @@ def motion_compensate(flow, models, mask=None, thresh=1.0, residual=True, label=
     """ofdis_motion_compensate on the device: flow [npairs, h, w, 2] float32, models [npairs, 6] float64, mask as above ->
     (residual [npairs, h, w, 2] float32, label [npairs, h, w] uint8); residual=False / label=False pass NULL and return None in
     that place.  in_place: `residual` is the flow's own device array (the library allows it)."""
-    flow, mask = _gm_inputs(flow, mask)
-    npairs, h, w = flow.shape[:3]
+    flow, dm, npairs, h, w = _gm_inputs(flow, mask)
     models = np.ascontiguousarray(models, np.float64)
     assert models.shape == (npairs, 6), models.shape
-    df, dm, dmodels = Dev(flow), Dev(mask) if mask is not None else None, Dev(models)
+    df, dmodels = Dev(flow), Dev(models)
     dr = (df if in_place else Dev(nbytes=max(8, flow.nbytes))) if residual else None
     dl = Dev(nbytes=max(1, npairs * h * w)) if label else None
     check(lib().ofdis_motion_compensate(df.ptr, dm.ptr if dm else None, dmodels.ptr, npairs, w, h, thresh, dr.ptr if dr else None,
@@ -847,10 +831,8 @@ def warp_frames(frames, warps, border=BORDER_CONSTANT, inside=True):
     """ofdis_warp_frames on the device: frames uint8 [n, h, w] (gray) or [n, h, w, 3], warps [n, 6] float64 -> (out, the shape
     of frames; inside uint8 [n, h, w], or None with inside=False: passed as NULL).
     of_dis_amd/stabilize.py: warp_frames_ref is the numpy statement of the same arithmetic."""
-    frames = np.ascontiguousarray(frames, np.uint8)
-    noc = 1 if frames.ndim == 3 else 3
-    n, h, w = frames.shape[:3]
-    assert frames.shape == (n, h, w) + ((3,) if noc == 3 else ()), frames.shape
+    n, h, w = np.shape(frames)[:3]
+    frames, noc = _clip_frames(frames, n, h, w)
     warps = np.ascontiguousarray(warps, np.float64)
     assert warps.shape == (n, 6), warps.shape
     df, dw, do = Dev(frames), Dev(warps), Dev(nbytes=frames.nbytes)
@@ -1004,21 +986,37 @@ class Batch:
         check(lib().ofdis_sync(stream))
         return d.get(shape, enc.dtype)
 
-    def download_all(self):
-        w, h = self.p.level_size(self.p.sc_l)
-        out = np.zeros((self.nframes, h, w, self.p.nop), _f32)
-        self.join(None)
-        check(lib().ofdis_sync(None))
-        check(lib().ofdis_memcpy_d2h(out.ctypes.data, self.flow_ptr(), out.nbytes))
-        return out
-
-    def level_flow(self, level):
+    def _flow_array(self, ptr, level, missing=None):
+        """A level's flow array at device pointer `ptr` as a host array [nframes][h][w][nop], the pass joined first.  `missing`:
+        what a null `ptr` means."""
+        if missing and not ptr:
+            raise OfdisError(missing)
         w, h = self.p.level_size(level)
         out = np.zeros((self.nframes, h, w, self.p.nop), _f32)
         self.join(None)
         check(lib().ofdis_sync(None))
-        check(lib().ofdis_memcpy_d2h(out.ctypes.data, lib().ofdis_batch_level_flow(self.h, level), out.nbytes))
+        check(lib().ofdis_memcpy_d2h(out.ctypes.data, ptr, out.nbytes))
         return out
+
+    def _outputs(self, own, specs, call, stream):
+        """The outputs of a batch call, specs = [(want, shape, dtype), ...], through call(*device pointers).  own: the call
+        was given no device arrays: allocates every output with a true `want` (the others are passed as NULL), calls,
+        synchronises `stream` and returns the tuple of host arrays (None where not wanted).  Otherwise each `want` is the
+        caller's device pointer, or false for NULL: only enqueues and returns None."""
+        if not own:
+            call(*[want if want else None for want, _, _ in specs])
+            return None
+        devs = [Dev(nbytes=max(1, int(np.prod(shape, dtype=np.int64)) * np.dtype(t).itemsize)) if want else None
+                for want, shape, t in specs]
+        call(*[d.ptr if d else None for d in devs])
+        check(lib().ofdis_sync(stream))
+        return tuple(d.get(shape, t) if d else None for d, (_, shape, t) in zip(devs, specs))
+
+    def download_all(self):
+        return self._flow_array(self.flow_ptr(), self.p.sc_l)
+
+    def level_flow(self, level):
+        return self._flow_array(lib().ofdis_batch_level_flow(self.h, level), level)
 
     # ---- reverse direction (reverse=True contexts)
     def set_initflow_reverse(self, dev_ptr):
@@ -1031,15 +1029,8 @@ class Batch:
         return out
 
     def level_flow_reverse(self, level):
-        ptr = lib().ofdis_batch_level_flow_reverse(self.h, level)
-        if not ptr:
-            raise OfdisError("ofdis_batch_level_flow_reverse: not a reverse context, or no such level")
-        w, h = self.p.level_size(level)
-        out = np.zeros((self.nframes, h, w, self.p.nop), _f32)
-        self.join(None)
-        check(lib().ofdis_sync(None))
-        check(lib().ofdis_memcpy_d2h(out.ctypes.data, ptr, out.nbytes))
-        return out
+        return self._flow_array(lib().ofdis_batch_level_flow_reverse(self.h, level), level,
+                                "ofdis_batch_level_flow_reverse: not a reverse context, or no such level")
 
     def download_all_reverse(self):
         return self.level_flow_reverse(self.p.sc_l)
@@ -1047,15 +1038,8 @@ class Batch:
     # ---- stereo left-right (stereo_lr=True contexts)
     def level_flow_mirror(self, level):
         """The raw mirror-pass disparity of a level (mirrored coordinates, <= 0): for the parity tests."""
-        ptr = lib().ofdis_batch_level_flow_mirror(self.h, level)
-        if not ptr:
-            raise OfdisError("ofdis_batch_level_flow_mirror: not a stereo_lr context, or no such level")
-        w, h = self.p.level_size(level)
-        out = np.zeros((self.nframes, h, w, self.p.nop), _f32)
-        self.join(None)
-        check(lib().ofdis_sync(None))
-        check(lib().ofdis_memcpy_d2h(out.ctypes.data, ptr, out.nbytes))
-        return out
+        return self._flow_array(lib().ofdis_batch_level_flow_mirror(self.h, level), level,
+                                "ofdis_batch_level_flow_mirror: not a stereo_lr context, or no such level")
 
     def upsample_lr(self, width_org, height_org, fill=FILL_NONE, alpha=FB_ALPHA, beta=FB_BETA, first=0, count=None,
                     outputs=(True, True, True, True), stream=None):
@@ -1064,13 +1048,9 @@ class Batch:
         others are passed as NULL and returned as None)."""
         count = self.nframes - first if count is None else count
         shape = (count, height_org, width_org)
-        dtypes = [_f32, _f32, np.uint8, np.uint8]
-        devs = [Dev(nbytes=max(1, int(np.prod(shape)) * np.dtype(t).itemsize)) if want else None
-                for t, want in zip(dtypes, outputs)]
-        check(lib().ofdis_batch_upsample_lr(self.h, first, count, *[d.ptr if d else None for d in devs], fill, width_org,
-                                            height_org, alpha, beta, stream))
-        check(lib().ofdis_sync(stream))
-        return tuple(d.get(shape, t) if d else None for d, t in zip(devs, dtypes))
+        specs = [(want, shape, t) for want, t in zip(outputs, (_f32, _f32, np.uint8, np.uint8))]
+        return self._outputs(True, specs, lambda *ptrs: check(lib().ofdis_batch_upsample_lr(
+            self.h, first, count, *ptrs, fill, width_org, height_org, alpha, beta, stream)), stream)
 
     def upsample_bidir(self, width_org, height_org, alpha=FB_ALPHA, beta=FB_BETA, first=0, count=None,
                        outputs=(True, True, True, True), stream=None):
@@ -1079,13 +1059,9 @@ class Batch:
         four the library writes (the others are passed as NULL and returned as None)."""
         count = self.nframes - first if count is None else count
         shapes = [(count, height_org, width_org, 2)] * 2 + [(count, height_org, width_org)] * 2
-        dtypes = [_f32, _f32, np.uint8, np.uint8]
-        devs = [Dev(nbytes=max(1, int(np.prod(s)) * np.dtype(t).itemsize)) if want else None
-                for s, t, want in zip(shapes, dtypes, outputs)]
-        check(lib().ofdis_batch_upsample_bidir(self.h, first, count, *[d.ptr if d else None for d in devs], width_org,
-                                               height_org, alpha, beta, stream))
-        check(lib().ofdis_sync(stream))
-        return tuple(d.get(s, t) if d else None for d, s, t in zip(devs, shapes, dtypes))
+        specs = list(zip(outputs, shapes, (_f32, _f32, np.uint8, np.uint8)))
+        return self._outputs(True, specs, lambda *ptrs: check(lib().ofdis_batch_upsample_bidir(
+            self.h, first, count, *ptrs, width_org, height_org, alpha, beta, stream)), stream)
 
     def interpolate(self, img_a_ptr, img_b_ptr, width_org, height_org, times, first=0, count=None, alpha=FB_ALPHA,
                     beta=FB_BETA, out_ptr=None, stream=None):
@@ -1148,20 +1124,11 @@ class Batch:
         count = self.nframes - first if count is None else count
         shape = (max(count, 0) + 1, height_org, width_org)
         oshape = shape + ((self.p.noc,) if self.p.noc > 1 else ())
-        d = ds = None
-        if out_ptr is None:
-            d = Dev(nbytes=max(1, int(np.prod(oshape, dtype=np.int64))))
-            ds = Dev(nbytes=max(1, int(np.prod(shape, dtype=np.int64)))) if support else None
-            out_ptr, sup_ptr = d.ptr, ds.ptr if ds else None
-        else:
-            sup_ptr = support if support else None
-        check(lib().ofdis_batch_temporal_filter(self.h, frames_ptr, first, count, out_ptr, sup_ptr, width_org, height_org, wn,
-                                                tau, alpha, beta, stream))
-        if d is None:
-            return None
-        check(lib().ofdis_sync(stream))
-        out = d.get(oshape, np.uint8)
-        return (out, ds.get(shape, np.uint8)) if ds else out
+        res = self._outputs(out_ptr is None, [(out_ptr or True, oshape, np.uint8), (support, shape, np.uint8)],
+                            lambda out, sup: check(lib().ofdis_batch_temporal_filter(
+                                self.h, frames_ptr, first, count, out, sup, width_org, height_org, wn, tau, alpha, beta, stream)),
+                            stream)
+        return res if res is None or support else res[0]
 
     def trajectory_filter(self, frames_ptr, width_org, height_org, weights, tau=np.inf, fb_check=True, first=0, count=None,
                           alpha=FB_ALPHA, beta=FB_BETA, out_ptr=None, support=False, stream=None):
@@ -1175,20 +1142,12 @@ class Batch:
         shape = (max(count, 0) + 1, height_org, width_org)
         oshape = shape + ((self.p.noc,) if self.p.noc > 1 else ())
         wts, wp = _weights(weights)
-        d = ds = None
-        if out_ptr is None:
-            d = Dev(nbytes=max(1, int(np.prod(oshape, dtype=np.int64))))
-            ds = Dev(nbytes=max(1, int(np.prod(shape, dtype=np.int64)))) if support else None
-            out_ptr, sup_ptr = d.ptr, ds.ptr if ds else None
-        else:
-            sup_ptr = support if support else None
-        check(lib().ofdis_batch_trajectory_filter(self.h, frames_ptr, first, count, out_ptr, sup_ptr, width_org, height_org, wp,
-                                                  wts.size, tau, int(fb_check), alpha, beta, stream))
-        if d is None:
-            return None
-        check(lib().ofdis_sync(stream))
-        out = d.get(oshape, np.uint8)
-        return (out, ds.get(shape, np.uint8)) if ds else out
+        res = self._outputs(out_ptr is None, [(out_ptr or True, oshape, np.uint8), (support, shape, np.uint8)],
+                            lambda out, sup: check(lib().ofdis_batch_trajectory_filter(
+                                self.h, frames_ptr, first, count, out, sup, width_org, height_org, wp, wts.size, tau,
+                                int(fb_check), alpha, beta, stream)),
+                            stream)
+        return res if res is None or support else res[0]
 
     def global_motion(self, width_org, height_org, model=GM_AFFINE, rounds=3, thresh=1.0, fb_check=False, first=0, count=None,
                       alpha=FB_ALPHA, beta=FB_BETA, models_ptr=None, stats_ptr=None, stream=None):
@@ -1253,21 +1212,11 @@ class Batch:
         weights, radius = _stab_weights(weights)
         shape = (max(count, 0) + 1, height_org, width_org)
         oshape = shape + ((self.p.noc,) if self.p.noc > 1 else ())
-        d = di = dw = None
-        if out_ptr is None:
-            d = Dev(nbytes=max(1, int(np.prod(oshape, dtype=np.int64))))
-            di = Dev(nbytes=max(1, int(np.prod(shape, dtype=np.int64)))) if inside else None
-            dw = Dev(nbytes=shape[0] * 48)
-            out_ptr, ins_ptr, warps_ptr = d.ptr, di.ptr if di else None, dw.ptr
-        else:
-            ins_ptr = inside if inside else None
-        check(lib().ofdis_batch_stabilize(self.h, frames_ptr, first, count, model, rounds, thresh, int(fb_check), alpha, beta,
-                                          weights.ctypes.data, radius, zoom, border, out_ptr, ins_ptr, warps_ptr, width_org,
-                                          height_org, stream))
-        if d is None:
-            return None
-        check(lib().ofdis_sync(stream))
-        return d.get(oshape, np.uint8), di.get(shape, np.uint8) if di else None, dw.get((shape[0], 6), np.float64)
+        specs = [(out_ptr or True, oshape, np.uint8), (inside, shape, np.uint8),
+                 (warps_ptr or out_ptr is None, (shape[0], 6), np.float64)]
+        return self._outputs(out_ptr is None, specs, lambda out, ins, warps: check(lib().ofdis_batch_stabilize(
+            self.h, frames_ptr, first, count, model, rounds, thresh, int(fb_check), alpha, beta, weights.ctypes.data, radius, zoom,
+            border, out, ins, warps, width_org, height_org, stream)), stream)
 
     def timing(self, enable=True):
         check(lib().ofdis_batch_timing(self.h, int(enable)))

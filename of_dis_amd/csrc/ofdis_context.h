@@ -1,6 +1,7 @@
 // ofdis_context.h -- the batch context of include/ofdis.h (struct ofdis_batch: every HBM buffer of the hot path) and what the
-// host units share: ofdis_context.hip (memory, creation, accessors), ofdis_schedule.hip (the level plan and the launch
-// schedule) and ofdis_capi.hip (ofdis_flow, per-function entry points, runtime wrappers).
+// host units share: ofdis_context.hip (memory, creation, inputs, result accessors), ofdis_schedule.hip (the level plan and the
+// launch schedule), ofdis_products.hip (what is made from a context's flows: the finish, checks, interpolation, trajectories,
+// filters, global motion, stabilisation) and ofdis_capi.hip (ofdis_flow, per-function entry points, runtime wrappers).
 #pragma once
 #include <math.h>
 #include <stdio.h>
@@ -172,7 +173,8 @@ struct ofdis_batch {
   float* gm_slab = nullptr;          // records of sums of ofdis_batch_global_motion (ofdis_gmotion.hip; int64, held as floats), lazy
   float* stab_path = nullptr;        // models [nframes][6] then warps [nframes + 1][6] of ofdis_batch_stabilize (fp64, held as floats), lazy
   float* dt_slab = nullptr;          // work buffer of ofdis_batch_dense_tracks (ofdis_dense_tracks.hip; held as floats), lazy: a
-  size_t dt_slab_bytes = 0;          // call that needs more than dt_slab_bytes requests a larger one
+                                     // call that needs more than it holds requests a larger one (dstage)
+  float* retired = nullptr;          // always null: where the descriptions of outgrown staging buffers point (dstage)
   // device memory: requests are collected (dalloc) and served from ONE hipMalloc per commit (dcommit) -- a context is
   // one allocation (two with the u8 pyramid scratch), and the input planes form one contiguous region [in_base,
   // in_base + in_bytes) in (level, kind) order so that a single-frame context is uploaded with one copy (ofdis_flow)
@@ -239,6 +241,10 @@ void context_init(ofdis_batch* b, const ofdis_params& p, int nframes, const ofdi
 void context_release(ofdis_batch* b);  // everything the context owns; not the struct itself
 void dalloc(ofdis_batch* b, float** member, size_t per_frame, bool view = true, int extra_frames = 0);  // request; served by dcommit()
 int dcommit(ofdis_batch* b);
+struct Stage { float** member; size_t per_frame; int extra_frames = 0; };
+int dstage(ofdis_batch* b, const std::vector<Stage>& wants);  // staging made on first use: dalloc + dcommit of what is missing or too small
+constexpr unsigned kOpticalFlow = 1u << 31;                   // beside the OFDIS_BATCH_* flags: not a stereo-depth context
+int context_check(const ofdis_batch* b, unsigned needs);      // what a call needs of its context; fails naming what is missing
 void dalloc_tv_scratch(ofdis_batch* b, const Scratch& sc);
 int xcu_arm(ofdis_batch* b, hipStream_t s);
 size_t frame_elems(const ofdis_batch& b, float* const& member);       // floats per frame of a context array, e.g. b.flow[0]

@@ -1,8 +1,6 @@
 // ofdis_context.hip -- the batch context's own half of the C ABI of include/ofdis.h: kernel-selection knobs, parameter
-// handling, the context's device memory (array descriptions, frame views), creation, inputs and result accessors.
-#include <cfloat>
-#include <cmath>
-
+// handling, the context's device memory (array descriptions, frame views, staging made on first use), creation, inputs and the
+// result accessors of all three directions.  What is made from the results is ofdis_products.hip.
 #include "ofdis_context.h"
 
 using namespace ofdis;
@@ -182,6 +180,20 @@ int dcommit(ofdis_batch* b) {
   }
   return OFDIS_OK;
 }
+// Staging the context makes on first use (never seen by a frame view): every member of `wants` holds at least its floats per
+// frame afterwards.  One that is null or smaller is requested anew and the requests are served together (one allocation).
+// The buffer a member outgrows stays with the context until destroy, and in ofdis_batch_device_bytes: its description
+// moves to `retired`, so that the member keeps exactly one.
+int dstage(ofdis_batch* b, const std::vector<Stage>& wants) {
+  for (const Stage& w : wants) {
+    const size_t slot = (size_t)((char*)w.member - (char*)b);
+    auto have = std::find_if(b->arrays.begin(), b->arrays.end(), [&](const ofdis_batch::Array& a) { return a.slot == slot; });
+    if (have != b->arrays.end() && have->per_frame >= w.per_frame) continue;
+    if (have != b->arrays.end()) have->slot = (size_t)((char*)&b->retired - (char*)b);
+    dalloc(b, w.member, w.per_frame, false, w.extra_frames);
+  }
+  return dcommit(b);
+}
 // the TV scratch of `sc`: requests, which dcommit serves (or fails)
 void dalloc_tv_scratch(ofdis_batch* b, const Scratch& sc) {
   const size_t npx = (size_t)b->geom[0].w * b->geom[0].h, noc = b->p.noc;
@@ -285,7 +297,20 @@ static int upload_planes(ofdis_batch* b, int frame, int first_kind, int nkinds, 
   return OFDIS_OK;
 }
 
-static const char* const kSeqOnly = "not a context created with OFDIS_BATCH_SEQUENCE";
+// What a call needs of its context: creation flags (OFDIS_BATCH_*) and / or kOpticalFlow.  The message names what is missing; a
+// NULL context has none of it.
+int context_check(const ofdis_batch* b, unsigned needs) {
+  if ((needs & kOpticalFlow) && (!b || b->p.selectmode == 2))
+    return fail(OFDIS_ERR_INVALID, "not an optical-flow context (stereo-depth mode has no flow field)");
+  std::string missing;
+  auto need = [&](unsigned flag, bool has, const char* name) {
+    if ((needs & flag) && !has) missing += (missing.empty() ? "" : " | ") + std::string(name);
+  };
+  need(OFDIS_BATCH_SEQUENCE, b && b->sequence, "OFDIS_BATCH_SEQUENCE");
+  need(OFDIS_BATCH_REVERSE, b && b->reverse, "OFDIS_BATCH_REVERSE");
+  need(OFDIS_BATCH_STEREO_LR, b && b->stereo_lr, "OFDIS_BATCH_STEREO_LR");
+  return missing.empty() ? OFDIS_OK : fail(OFDIS_ERR_INVALID, "not a context created with " + missing);
+}
 static int seq_refuses(const char* what, const char* instead) {
   return fail(OFDIS_ERR_INVALID, std::string(what) + " takes frame pairs; an OFDIS_BATCH_SEQUENCE context shares its frame slots "
                                                      "between pairs and is filled through " + instead);
@@ -302,24 +327,6 @@ static int download(ofdis_batch* b, int frame, float* outflow_host, hipStream_t 
   HIPCHK(hipMemcpyAsync(outflow_host, frame_at(*b, flow, frame), frame_elems(*b, flow) * sizeof(float), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   return xcu_poll(b);
-}
-
-static bool fb_constants_ok(float alpha, float beta) {
-  return std::isfinite(alpha) && std::isfinite(beta) && alpha >= 0.0f && beta >= 0.0f;
-}
-
-static_assert(sizeof(InterpTimes::t) / sizeof(float) == OFDIS_INTERP_MAX_TIMES, "InterpTimes holds OFDIS_INTERP_MAX_TIMES");
-static int interp_times(const float* times, int ntimes, InterpTimes& ts) {
-  if (!times) return fail(OFDIS_ERR_INVALID, "times is NULL");
-  if (ntimes < 1 || ntimes > OFDIS_INTERP_MAX_TIMES) return fail(OFDIS_ERR_INVALID, "ntimes must be 1..OFDIS_INTERP_MAX_TIMES");
-  memset(&ts, 0, sizeof(ts));
-  for (int k = 0; k < ntimes; ++k) {
-    if (!(std::isfinite(times[k]) && times[k] >= 0.0f && times[k] <= 1.0f))
-      return fail(OFDIS_ERR_INVALID, "every time must be finite and inside [0, 1]");
-    ts.t[k] = times[k];
-  }
-  ts.n = ntimes;
-  return OFDIS_OK;
 }
 
 }  // namespace ofdis
@@ -474,7 +481,7 @@ int ofdis_batch_upload_b_gradients(ofdis_batch* b, int frame, const float* const
 
 int ofdis_batch_upload_frame(ofdis_batch* b, int slot, const float* const* im, const float* const* im_dx,
                              const float* const* im_dy, void* stream) {
-  if (!b || !b->sequence) return fail(OFDIS_ERR_INVALID, kSeqOnly);
+  if (int rc = context_check(b, OFDIS_BATCH_SEQUENCE)) return rc;
   if (slot < 0 || slot > b->nframes || !im || !im_dx || !im_dy) return fail(OFDIS_ERR_INVALID, "bad arguments");
   const float* const* src[3] = {im, im_dx, im_dy};
   return upload_planes(b, slot, 0, 3, src, (hipStream_t)stream);
@@ -506,18 +513,16 @@ static int build_prepare(ofdis_batch* b, int width_org, int height_org) {
     return fail(OFDIS_ERR_INVALID, "params.width/height are not the 2^sc_f padding of the original size");
   // level l images need 8+2l bits, the Sobel partial sums 10+2l: exact in fp32 up to l = 7 (ofdis_pyr.hip)
   if (p.sc_f > 7) return fail(OFDIS_ERR_UNSUPPORTED, "exact fp32 pyramid needs sc_f <= 7");
-  if (!b->pyr_tmp[0]) {
-    for (int i = 0; i < b->nlevels; ++i)
-      dalloc(b, &b->pyr_tmp[i], (size_t)b->geom[i].w * b->geom[i].h * b->geom[i].noc, false, b->sequence ? 1 : 0);
-    if (b->stereo_lr) dalloc(b, &b->mir_u8, ((size_t)p.width * p.height * p.noc + 3) / 4, false);
-    if (int rc = dcommit(b)) return rc;
-  }
-  return OFDIS_OK;
+  std::vector<Stage> tmp;
+  for (int i = 0; i < b->nlevels; ++i)
+    tmp.push_back({&b->pyr_tmp[i], (size_t)b->geom[i].w * b->geom[i].h * b->geom[i].noc, b->sequence ? 1 : 0});
+  if (b->stereo_lr) tmp.push_back({&b->mir_u8, ((size_t)p.width * p.height * p.noc + 3) / 4});
+  return dstage(b, tmp);
 }
 
 int ofdis_batch_build_pyramids_u8_seq(ofdis_batch* b, const uint8_t* frames, size_t row_pitch, size_t frame_stride,
                                       int width_org, int height_org, void* stream) {
-  if (!b || !b->sequence) return fail(OFDIS_ERR_INVALID, kSeqOnly);
+  if (int rc = context_check(b, OFDIS_BATCH_SEQUENCE)) return rc;
   if (!frames) return fail(OFDIS_ERR_INVALID, "bad arguments");
   if (width_org < 1 || height_org < 1) return fail(OFDIS_ERR_INVALID, "params.width/height are not the 2^sc_f padding of the original size");
   const size_t row_bytes = (size_t)width_org * b->p.noc;
@@ -563,6 +568,24 @@ int ofdis_batch_download(ofdis_batch* b, int frame, float* outflow_host, void* s
   return download(b, frame, outflow_host, (hipStream_t)stream, false);
 }
 
+// the reverse direction (OFDIS_BATCH_REVERSE)
+const float* ofdis_batch_flow_reverse(const ofdis_batch* b) { return b && b->reverse ? b->flow_rev[0] : nullptr; }
+const float* ofdis_batch_level_flow_reverse(const ofdis_batch* b, int level) {
+  return b && b->reverse ? level_flow(*b, level, true) : nullptr;
+}
+
+int ofdis_batch_download_reverse(ofdis_batch* b, int frame, float* outflow_host, void* stream) {
+  if (int rc = context_check(b, OFDIS_BATCH_REVERSE)) return rc;
+  if (frame < 0 || frame >= b->nframes || !outflow_host) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  return download(b, frame, outflow_host, (hipStream_t)stream, true);
+}
+
+// the mirror pass (OFDIS_BATCH_STEREO_LR)
+const float* ofdis_batch_flow_mirror(const ofdis_batch* b) { return b && b->stereo_lr ? b->flow_rev[0] : nullptr; }
+const float* ofdis_batch_level_flow_mirror(const ofdis_batch* b, int level) {
+  return b && b->stereo_lr ? level_flow(*b, level, true) : nullptr;
+}
+
 // Warm start (oflow.cpp:217-220): the coarsest level initialises its patches from this flow exactly as finer levels
 // do from the level above, i.e. it is indexed as a (w >> (sc_f+1)) x (h >> (sc_f+1)) AoS plane per frame.
 size_t ofdis_batch_initflow_elems(const ofdis_batch* b) {
@@ -576,636 +599,21 @@ int ofdis_batch_set_initflow(ofdis_batch* b, const float* initflow_dev) {
   b->initflow = initflow_dev;
   return OFDIS_OK;
 }
-
-int ofdis_batch_upload_initflow(ofdis_batch* b, int frame, const float* initflow_host, void* stream) {
-  if (!b || frame < 0 || frame >= b->nframes || !initflow_host) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  const size_t n = ofdis_batch_initflow_elems(b);
-  if (!b->initflow_own) {
-    dalloc(b, &b->initflow_own, n);
-    if (int rc = dcommit(b)) return rc;
-    HIPCHK(hipMemsetAsync(b->initflow_own, 0, n * b->nframes * sizeof(float), (hipStream_t)stream));
-  }
-  HIPCHK(hipMemcpyAsync(frame_at(*b, b->initflow_own, frame), initflow_host, n * sizeof(float), hipMemcpyHostToDevice,
-                        (hipStream_t)stream));
-  b->initflow = b->initflow_own;
-  return OFDIS_OK;
-}
-
-// What every full-resolution finish of a context starts with: the frame range and the original size checked, the pass joined
-// (ofdis_batch_join), then the finish's geometry and where frames [first_frame, ...) start in a finest-level result array
-// (flow[0], flow_rev[0]).
-struct Finish {
-  UpGeom g;
-  size_t off;
-};
-static int finish_begin(ofdis_batch* b, int first_frame, int count, int width_org, int height_org, void* stream, Finish& fin) {
-  if (first_frame < 0 || count < 1 || first_frame > b->nframes - count) return fail(OFDIS_ERR_INVALID, "frame range outside the batch");
-  const ofdis_params& p = b->p;
-  if (width_org < 1 || height_org < 1 || width_org > p.width || height_org > p.height)
-    return fail(OFDIS_ERR_INVALID, "original size exceeds the padded size");
-  if (int rc = ofdis_batch_join(b, stream)) return rc;
-  const LevelGeom& g = b->geom[0];
-  fin.g = UpGeom{g.w, g.h, p.sc_l, (p.width - width_org) / 2, (p.height - height_org) / 2, width_org, height_org};
-  fin.off = (size_t)first_frame * frame_elems(*b, b->flow[0]);
-  return OFDIS_OK;
-}
-
-int ofdis_batch_upsample_frames(ofdis_batch* b, int first_frame, int count, float* out_dev, int width_org,
-                                int height_org, void* stream) {
-  if (!b || !out_dev) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  Finish fin;
-  if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
-  HIPCHK(launch_upsample_crop(b->flow[0] + fin.off, out_dev, count, fin.g, b->nop, (hipStream_t)stream));
-  return OFDIS_OK;
-}
-
-int ofdis_batch_upsample(ofdis_batch* b, float* out_dev, int width_org, int height_org, void* stream) {
-  if (!b) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  return ofdis_batch_upsample_frames(b, 0, b->nframes, out_dev, width_org, height_org, stream);
-}
-
-// ------------------------------------------------------------------------------------ compact output encodings
-size_t ofdis_encoding_bytes(int type) {
-  switch (type) {
-    case OFDIS_ENC_F32: return 4;
-    case OFDIS_ENC_F16: case OFDIS_ENC_U16: return 2;
-    case OFDIS_ENC_U8: return 1;
-  }
-  return 0;
-}
-
-static int encoding_check(const ofdis_encoding* enc) {
-  if (!enc) return fail(OFDIS_ERR_INVALID, "encoding is NULL");
-  if (!ofdis_encoding_bytes(enc->type)) return fail(OFDIS_ERR_INVALID, "unknown encoding type");
-  if (enc->type == OFDIS_ENC_U16 || enc->type == OFDIS_ENC_U8) {
-    if (!std::isfinite(enc->scale) || enc->scale == 0.0f) return fail(OFDIS_ERR_INVALID, "encoding scale must be finite and not zero");
-    if (!std::isfinite(enc->offset)) return fail(OFDIS_ERR_INVALID, "encoding offset must be finite");
-  }
-  return OFDIS_OK;
-}
-
-int ofdis_encode(const float* src, void* dst, size_t n, const ofdis_encoding* enc, void* stream) {
-  if (!src || !dst) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  if ((const void*)src == dst) return fail(OFDIS_ERR_INVALID, "ofdis_encode does not work in place");
-  if (int rc = encoding_check(enc)) return rc;
-  if (n == 0) return OFDIS_OK;
-  HIPCHK(launch_encode(src, dst, n, enc->type, enc->scale, enc->offset, (hipStream_t)stream));
-  return OFDIS_OK;
-}
-
-int ofdis_batch_upsample_frames_enc(ofdis_batch* b, int first_frame, int count, void* out, int width_org, int height_org,
-                                    const ofdis_encoding* enc, void* stream) {
-  if (!b || !out) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  if (int rc = encoding_check(enc)) return rc;
-  Finish fin;
-  if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
-  HIPCHK(launch_upsample_crop_enc(b->flow[0] + fin.off, out, count, fin.g, b->nop, enc->type, enc->scale, enc->offset,
-                                  (hipStream_t)stream));
-  return OFDIS_OK;
-}
-
-// ------------------------------------------------------------------------------------ reverse direction (OFDIS_BATCH_REVERSE)
-const float* ofdis_batch_flow_reverse(const ofdis_batch* b) { return b && b->reverse ? b->flow_rev[0] : nullptr; }
-const float* ofdis_batch_level_flow_reverse(const ofdis_batch* b, int level) {
-  return b && b->reverse ? level_flow(*b, level, true) : nullptr;
-}
-
 int ofdis_batch_set_initflow_reverse(ofdis_batch* b, const float* initflow_dev) {
-  if (!b || !b->reverse) return fail(OFDIS_ERR_INVALID, "not a context created with OFDIS_BATCH_REVERSE");
+  if (int rc = context_check(b, OFDIS_BATCH_REVERSE)) return rc;
   b->initflow_rev = initflow_dev;
   return OFDIS_OK;
 }
 
-int ofdis_batch_download_reverse(ofdis_batch* b, int frame, float* outflow_host, void* stream) {
-  if (!b || !b->reverse) return fail(OFDIS_ERR_INVALID, "not a context created with OFDIS_BATCH_REVERSE");
-  if (frame < 0 || frame >= b->nframes || !outflow_host) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  return download(b, frame, outflow_host, (hipStream_t)stream, true);
-}
-
-int ofdis_batch_upsample_bidir(ofdis_batch* b, int first_frame, int count, float* out_fw, float* out_rev,
-                               uint8_t* mask_fw, uint8_t* mask_rev, int width_org, int height_org,
-                               float alpha, float beta, void* stream) {
-  if (!b || !b->reverse) return fail(OFDIS_ERR_INVALID, "not a context created with OFDIS_BATCH_REVERSE");
-  if (!fb_constants_ok(alpha, beta)) return fail(OFDIS_ERR_INVALID, "alpha and beta must be finite and >= 0");
-  Finish fin;
-  if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
-  if (!out_fw && !out_rev && !mask_fw && !mask_rev) return OFDIS_OK;
-  HIPCHK(launch_upsample_bidir(b->flow[0] + fin.off, b->flow_rev[0] + fin.off, out_fw, out_rev, mask_fw, mask_rev, count, fin.g,
-                               alpha, beta, (hipStream_t)stream));
-  return OFDIS_OK;
-}
-
-int ofdis_fb_check(const float* flow, const float* flow_other, uint8_t* mask, int nframes, int width, int height,
-                   float alpha, float beta, void* stream) {
-  if (!flow || !flow_other || !mask) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  if (nframes < 1 || width < 1 || height < 1 || (long long)width * height > (1ll << 30))
-    return fail(OFDIS_ERR_INVALID, "bad sizes");
-  if (!fb_constants_ok(alpha, beta)) return fail(OFDIS_ERR_INVALID, "alpha and beta must be finite and >= 0");
-  HIPCHK(launch_fb_check(flow, flow_other, mask, nframes, width, height, alpha, beta, (hipStream_t)stream));
-  return OFDIS_OK;
-}
-
-// ------------------------------------------------------------------------------------ stereo left-right (OFDIS_BATCH_STEREO_LR)
-const float* ofdis_batch_flow_mirror(const ofdis_batch* b) { return b && b->stereo_lr ? b->flow_rev[0] : nullptr; }
-const float* ofdis_batch_level_flow_mirror(const ofdis_batch* b, int level) {
-  return b && b->stereo_lr ? level_flow(*b, level, true) : nullptr;
-}
-
-int ofdis_lr_check(const float* disp, const float* disp_other, uint8_t* mask, int nframes, int width, int height,
-                   float alpha, float beta, void* stream) {
-  if (!disp || !disp_other || !mask) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  if (nframes < 1 || width < 1 || height < 1 || (long long)width * height > (1ll << 30))
-    return fail(OFDIS_ERR_INVALID, "bad sizes");
-  if (!fb_constants_ok(alpha, beta)) return fail(OFDIS_ERR_INVALID, "alpha and beta must be finite and >= 0");
-  HIPCHK(launch_lr_check(disp, disp_other, mask, nframes, width, height, alpha, beta, (hipStream_t)stream));
-  return OFDIS_OK;
-}
-
-static bool fill_mode_ok(int mode) { return mode == OFDIS_FILL_NONE || mode == OFDIS_FILL_INVALIDATE || mode == OFDIS_FILL_BACKGROUND; }
-
-int ofdis_disparity_fill(const float* disp, const uint8_t* mask, float* out, int nframes, int width, int height, int mode,
-                         void* stream) {
-  if (!fill_mode_ok(mode)) return fail(OFDIS_ERR_INVALID, "fill mode must be OFDIS_FILL_NONE, _INVALIDATE or _BACKGROUND");
-  if (!disp || !mask || !out) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  if (nframes < 1 || width < 1 || height < 1 || (long long)width * height > (1ll << 30))
-    return fail(OFDIS_ERR_INVALID, "bad sizes");
-  HIPCHK(launch_disparity_fill(disp, mask, out, nframes, width, height, mode, (hipStream_t)stream));
-  return OFDIS_OK;
-}
-
-int ofdis_batch_upsample_lr(ofdis_batch* b, int first_frame, int count, float* out_left, float* out_right,
-                            uint8_t* mask_left, uint8_t* mask_right, int fill_mode, int width_org, int height_org,
-                            float alpha, float beta, void* stream) {
-  if (!b || !b->stereo_lr) return fail(OFDIS_ERR_INVALID, "not a context created with OFDIS_BATCH_STEREO_LR");
-  if (!fill_mode_ok(fill_mode)) return fail(OFDIS_ERR_INVALID, "fill mode must be OFDIS_FILL_NONE, _INVALIDATE or _BACKGROUND");
-  if (!fb_constants_ok(alpha, beta)) return fail(OFDIS_ERR_INVALID, "alpha and beta must be finite and >= 0");
-  hipStream_t s = (hipStream_t)stream;
-  Finish fin;
-  if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
-  if (!out_left && !out_right && !mask_left && !mask_right) return OFDIS_OK;
-  const ofdis_params& p = b->p;
-  const float* fw = b->flow[0] + fin.off;
-  const float* mir = b->flow_rev[0] + fin.off;
-  if (upsample_lr_fuses(width_org)) {
-    HIPCHK(launch_upsample_lr(fw, mir, out_left, out_right, mask_left, mask_right, count, fin.g, fill_mode, alpha, beta, s));
-    return OFDIS_OK;
-  }
-  // wider than the fused kernel's rows: the composition itself, through staging owned by the context
-  const size_t px = (size_t)p.width * p.height;
-  if (!b->lr_u) {
-    dalloc(b, &b->lr_u, px, false);
-    dalloc(b, &b->lr_dr, px, false);
-    dalloc(b, &b->lr_mask, (2 * px + 3) / 4, false);
-    if (int rc = dcommit(b)) return rc;
-  }
-  const size_t n = (size_t)count * width_org * height_org;  // (count <= nframes, original size <= padded size)
-  uint8_t* ml = mask_left ? mask_left : reinterpret_cast<uint8_t*>(b->lr_mask);
-  uint8_t* mr = mask_right ? mask_right : reinterpret_cast<uint8_t*>(b->lr_mask) + n;
-  HIPCHK(launch_lr_materialise(fw, mir, b->lr_u, b->lr_dr, count, fin.g, s));
-  if (mask_left || out_left) HIPCHK(launch_lr_check(b->lr_u, b->lr_dr, ml, count, width_org, height_org, alpha, beta, s));
-  if (mask_right || out_right) HIPCHK(launch_lr_check(b->lr_dr, b->lr_u, mr, count, width_org, height_org, alpha, beta, s));
-  if (out_left) HIPCHK(launch_disparity_fill(b->lr_u, ml, out_left, count, width_org, height_org, fill_mode, s));
-  if (out_right) HIPCHK(launch_disparity_fill(b->lr_dr, mr, out_right, count, width_org, height_org, fill_mode, s));
-  return OFDIS_OK;
-}
-
-// ------------------------------------------------------------------------------------ frame interpolation (ofdis_interp.hip)
-int ofdis_interpolate(const uint8_t* img_a, const uint8_t* img_b, const float* flow_fw, const float* flow_rev,
-                      const uint8_t* mask_fw, const uint8_t* mask_rev, uint8_t* out, int nframes, int width, int height,
-                      int noc, const float* times, int ntimes, void* stream) {
-  if (!img_a || !img_b || !flow_fw || !flow_rev || !out) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  InterpTimes ts;
-  if (int rc = interp_times(times, ntimes, ts)) return rc;
-  if (noc != 1 && noc != 3) return fail(OFDIS_ERR_INVALID, "noc must be 1 or 3");
-  if (nframes < 1 || width < 1 || height < 1 || (long long)width * height > (1ll << 30))
-    return fail(OFDIS_ERR_INVALID, "bad sizes");
-  HIPCHK(launch_interp_frames(img_a, img_b, flow_fw, flow_rev, mask_fw, mask_rev, out, nframes, width, height, noc, ts,
-                              (hipStream_t)stream));
-  return OFDIS_OK;
-}
-
-int ofdis_batch_interpolate(ofdis_batch* b, const uint8_t* img_a, const uint8_t* img_b, int first_frame, int count,
-                            const float* times, int ntimes, uint8_t* out, int width_org, int height_org,
-                            float alpha, float beta, void* stream) {
-  if (!b || !b->reverse) return fail(OFDIS_ERR_INVALID, "not a context created with OFDIS_BATCH_REVERSE");
-  if (!img_a || !img_b || !out) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  InterpTimes ts;
-  if (int rc = interp_times(times, ntimes, ts)) return rc;
-  const ofdis_params& p = b->p;
-  if (p.noc != 1 && p.noc != 3) return fail(OFDIS_ERR_INVALID, "noc must be 1 or 3");
-  if (!fb_constants_ok(alpha, beta)) return fail(OFDIS_ERR_INVALID, "alpha and beta must be finite and >= 0");
-  Finish fin;
-  if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
-  const size_t img_off = (size_t)first_frame * width_org * height_org * p.noc;
-  HIPCHK(launch_interp_bidir(img_a + img_off, img_b + img_off, b->flow[0] + fin.off, b->flow_rev[0] + fin.off, out, count, fin.g,
-                             p.noc, ts, alpha, beta, (hipStream_t)stream));
-  return OFDIS_OK;
-}
-
-// ------------------------------------------------------------------------------------ point trajectories (ofdis_track.hip)
-static int track_args_check(const float* seeds, int npoints, int max_steps, float alpha, float beta, const float* tracks) {
-  if (!seeds || !tracks) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  if (npoints < 1 || npoints > OFDIS_TRACK_MAX_POINTS) return fail(OFDIS_ERR_INVALID, "npoints outside 1..OFDIS_TRACK_MAX_POINTS");
-  if (max_steps < 0) return fail(OFDIS_ERR_INVALID, "max_steps is negative");
-  if (!fb_constants_ok(alpha, beta)) return fail(OFDIS_ERR_INVALID, "alpha and beta must be finite and >= 0");
-  return OFDIS_OK;
-}
-
-int ofdis_track_points(const float* flow_fw, const float* flow_rev, int npairs, int width, int height, const float* seeds,
-                       const int* seed_frame, int npoints, int max_steps, float alpha, float beta, float* tracks, int* counts,
-                       void* stream) {
-  if (!flow_fw) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  if (int rc = track_args_check(seeds, npoints, max_steps, alpha, beta, tracks)) return rc;
-  if (npairs < 1 || width < 1 || height < 1 || (long long)width * height > (1ll << 30))
-    return fail(OFDIS_ERR_INVALID, "bad sizes");
-  HIPCHK(launch_track_points(flow_fw, flow_rev, npairs, width, height, seeds, seed_frame, npoints, max_steps, alpha, beta, tracks,
-                             counts, (hipStream_t)stream));
-  return OFDIS_OK;
-}
-
-int ofdis_batch_track_points(ofdis_batch* b, int first_frame, int count, const float* seeds, const int* seed_frame, int npoints,
-                             int max_steps, int fb_check, float alpha, float beta, float* tracks, int* counts, int width_org,
-                             int height_org, void* stream) {
-  if (!b || !b->sequence)  // (the pairs of any other context are no chain)
-    return fail(OFDIS_ERR_INVALID, "not a context created with OFDIS_BATCH_SEQUENCE");
-  if (fb_check != 0 && fb_check != 1) return fail(OFDIS_ERR_INVALID, "fb_check must be 0 or 1");
-  if (fb_check && !b->reverse) return fail(OFDIS_ERR_INVALID, "fb_check needs a context created with OFDIS_BATCH_REVERSE");
-  if (int rc = track_args_check(seeds, npoints, max_steps, alpha, beta, tracks)) return rc;
-  Finish fin;
-  if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
-  HIPCHK(launch_track_level(b->flow[0] + fin.off, fb_check ? b->flow_rev[0] + fin.off : nullptr, count, fin.g, seeds, seed_frame,
-                            npoints, max_steps, alpha, beta, tracks, counts, (hipStream_t)stream));
-  return OFDIS_OK;
-}
-
-// ------------------------------------------------------------------------------------ dense trajectories (ofdis_dense_tracks.hip)
-static int dense_grid_check(int width, int height, int stride) {
-  if (stride < 2 || stride > OFDIS_DT_MAX_STRIDE) return fail(OFDIS_ERR_INVALID, "stride outside 2..OFDIS_DT_MAX_STRIDE");
-  if (width < 1 || height < 1 || (long long)width * height > (1ll << 30)) return fail(OFDIS_ERR_INVALID, "bad sizes");
-  if (width < stride || height < stride) return fail(OFDIS_ERR_INVALID, "bad sizes (a side smaller than the stride)");
-  return OFDIS_OK;
-}
-static int dense_texture_check(const uint8_t* frames, int noc, int window, int min_eig) {
-  if (!frames) return fail(OFDIS_ERR_INVALID, "frames is NULL");
-  if (noc != 1 && noc != 3) return fail(OFDIS_ERR_INVALID, "noc must be 1 or 3");
-  if (window < 0 || window > OFDIS_DT_MAX_WINDOW) return fail(OFDIS_ERR_INVALID, "window outside 0..OFDIS_DT_MAX_WINDOW");
-  if (min_eig < 0) return fail(OFDIS_ERR_INVALID, "min_eig is negative");
-  return OFDIS_OK;
-}
-static int dense_args_check(const uint8_t* frames, int noc, int window, int min_eig, int max_len, float alpha, float beta,
-                            int max_tracks, const float* tracks, const int* start, const long long* info) {
-  if (int rc = dense_texture_check(frames, noc, window, min_eig)) return rc;
-  if (!tracks || !start || !info) return fail(OFDIS_ERR_INVALID, "tracks, start or info is NULL");
-  if (max_len < 0) return fail(OFDIS_ERR_INVALID, "max_len is negative");
-  if (max_tracks < 1 || max_tracks > OFDIS_DT_MAX_TRACKS) return fail(OFDIS_ERR_INVALID, "max_tracks outside 1..OFDIS_DT_MAX_TRACKS");
-  if (!fb_constants_ok(alpha, beta)) return fail(OFDIS_ERR_INVALID, "alpha and beta must be finite and >= 0");
-  return OFDIS_OK;
-}
-
-int ofdis_dense_tracks_cells(int width, int height, int stride, int* ncx, int* ncy) {
-  if (ncx) *ncx = 0;
-  if (ncy) *ncy = 0;
-  if (dense_grid_check(width, height, stride)) return 0;
-  return dense_tracks_cells(width, height, stride, ncx, ncy);
-}
-
-size_t ofdis_dense_tracks_work_bytes(int npairs, int width, int height, int stride) {
-  if (npairs < 1 || dense_grid_check(width, height, stride)) return 0;
-  return dense_tracks_work_bytes(npairs, width, height, stride, 0, OFDIS_DT_MAX_TRACKS);
-}
-
-int ofdis_seed_texture(const uint8_t* frames, int nframes, int width, int height, int noc, int stride, int window, int min_eig,
-                       uint8_t* out, void* stream) {
-  if (int rc = dense_texture_check(frames, noc, window, min_eig)) return rc;
-  if (!out) return fail(OFDIS_ERR_INVALID, "out is NULL");
-  if (int rc = dense_grid_check(width, height, stride)) return rc;
-  if (nframes < 1) return fail(OFDIS_ERR_INVALID, "bad sizes (nframes < 1)");
-  HIPCHK(launch_seed_texture(frames, nframes, width, height, noc, stride, window, min_eig, out, (hipStream_t)stream));
-  return OFDIS_OK;
-}
-
-int ofdis_dense_tracks(const uint8_t* frames, const float* flow_fw, const float* flow_rev, int npairs, int width, int height,
-                       int noc, int stride, int window, int min_eig, int max_len, float alpha, float beta, int max_tracks,
-                       float* tracks, int* start, int* len, long long* info, void* work, size_t work_bytes, void* stream) {
-  if (!flow_fw) return fail(OFDIS_ERR_INVALID, "flow_fw is NULL");
-  if (int rc = dense_args_check(frames, noc, window, min_eig, max_len, alpha, beta, max_tracks, tracks, start, info)) return rc;
-  if (int rc = dense_grid_check(width, height, stride)) return rc;
-  if (npairs < 1) return fail(OFDIS_ERR_INVALID, "bad sizes (npairs < 1)");
-  if (!work || ((uintptr_t)work & 7) || work_bytes < ofdis_dense_tracks_work_bytes(npairs, width, height, stride))
-    return fail(OFDIS_ERR_INVALID, "work buffer is NULL, not 8-byte aligned or smaller than ofdis_dense_tracks_work_bytes");
-  HIPCHK(launch_dense_tracks(frames, flow_fw, flow_rev, npairs, width, height, noc, stride, window, min_eig, max_len, alpha, beta,
-                             max_tracks, tracks, start, len, info, work, (hipStream_t)stream));
-  return OFDIS_OK;
-}
-
-int ofdis_batch_dense_tracks(ofdis_batch* b, const uint8_t* frames, int first_frame, int count, int stride, int window,
-                             int min_eig, int max_len, int fb_check, float alpha, float beta, int max_tracks, float* tracks,
-                             int* start, int* len, long long* info, int width_org, int height_org, void* stream) {
-  if (!b || !b->sequence)  // (the pairs of any other context are no chain)
-    return fail(OFDIS_ERR_INVALID, kSeqOnly);
-  if (fb_check != 0 && fb_check != 1) return fail(OFDIS_ERR_INVALID, "fb_check must be 0 or 1");
-  if (fb_check && !b->reverse) return fail(OFDIS_ERR_INVALID, "fb_check needs a context created with OFDIS_BATCH_REVERSE");
-  const ofdis_params& p = b->p;
-  if (int rc = dense_args_check(frames, p.noc, window, min_eig, max_len, alpha, beta, max_tracks, tracks, start, info)) return rc;
-  if (int rc = dense_grid_check(width_org, height_org, stride)) return rc;
-  Finish fin;
-  if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
-  const size_t need = dense_tracks_work_bytes(count, width_org, height_org, stride, max_len, max_tracks);
-  if (need > b->dt_slab_bytes) {  // what this call needs; an earlier, smaller buffer stays with the context until it is destroyed
-    const size_t per_frame = (need + sizeof(float) * b->nframes - 1) / (sizeof(float) * b->nframes);
-    b->dt_slab_bytes = 0;
-    dalloc(b, &b->dt_slab, per_frame, false);
-    if (int rc = dcommit(b)) return rc;
-    b->dt_slab_bytes = per_frame * b->nframes * sizeof(float);
-  }
-  HIPCHK(launch_dense_tracks_level(frames + (size_t)first_frame * width_org * height_org * p.noc, b->flow[0] + fin.off,
-                                   fb_check ? b->flow_rev[0] + fin.off : nullptr, count, fin.g, p.noc, stride, window, min_eig,
-                                   max_len, alpha, beta, max_tracks, tracks, start, len, info, b->dt_slab, (hipStream_t)stream));
-  return OFDIS_OK;
-}
-
-// ------------------------------------------------------------------------------------ track descriptors (ofdis_descriptors.hip)
-static int desc_params_check(int patch, int nxy, int nt) {
-  if (patch < 2 || patch > OFDIS_DESC_MAX_PATCH || patch % 2) return fail(OFDIS_ERR_INVALID, "patch must be even, 2..OFDIS_DESC_MAX_PATCH");
-  if (nxy < 1 || nxy > 4 || patch % nxy) return fail(OFDIS_ERR_INVALID, "nxy must be 1..4 and divide patch");
-  if (nt < 1 || nt > 8) return fail(OFDIS_ERR_INVALID, "nt outside 1..8");
-  return OFDIS_OK;
-}
-
-int ofdis_track_descriptor_dims(int patch, int nxy, int nt) { return desc_params_check(patch, nxy, nt) ? 0 : 33 * nxy * nxy * nt; }
-
-int ofdis_track_descriptors(const uint8_t* frames, const float* flow_fw, int npairs, int width, int height, int noc,
-                            const float* tracks, const int* start, const int* len, const long long* info, int lmax,
-                            int max_tracks, int patch, int nxy, int nt, float min_flow, uint32_t* hist, float* shape,
-                            void* stream) {
-  if (!frames) return fail(OFDIS_ERR_INVALID, "frames is NULL");
-  if (!flow_fw) return fail(OFDIS_ERR_INVALID, "flow_fw is NULL");
-  if (!tracks || !start || !len || !info) return fail(OFDIS_ERR_INVALID, "tracks, start, len or info is NULL");
-  if (!hist) return fail(OFDIS_ERR_INVALID, "hist is NULL");
-  if (noc != 1 && noc != 3) return fail(OFDIS_ERR_INVALID, "noc must be 1 or 3");
-  if (width < 1 || height < 1 || (long long)width * height > (1ll << 30)) return fail(OFDIS_ERR_INVALID, "bad sizes");
-  if (npairs < 1) return fail(OFDIS_ERR_INVALID, "bad sizes (npairs < 1)");
-  if (lmax < 1 || lmax > npairs) return fail(OFDIS_ERR_INVALID, "lmax outside 1..npairs");
-  if (max_tracks < 1 || max_tracks > OFDIS_DT_MAX_TRACKS) return fail(OFDIS_ERR_INVALID, "max_tracks outside 1..OFDIS_DT_MAX_TRACKS");
-  if (int rc = desc_params_check(patch, nxy, nt)) return rc;
-  if (nt > lmax) return fail(OFDIS_ERR_INVALID, "nt above lmax");
-  if ((long long)patch * patch * lmax > 65536) return fail(OFDIS_ERR_INVALID, "patch * patch * lmax above 65536");
-  if (!(min_flow >= 0.f) || std::isinf(min_flow)) return fail(OFDIS_ERR_INVALID, "min_flow must be finite and >= 0");
-  HIPCHK(launch_track_descriptors(frames, flow_fw, npairs, width, height, noc, tracks, start, len, info, lmax, max_tracks, patch,
-                                  nxy, nt, min_flow, hist, shape, (hipStream_t)stream));
-  return OFDIS_OK;
-}
-
-// ------------------------------------------------------------------------------------ temporal filter (ofdis_tfilter.hip)
-static int tfilter_args_check(const uint8_t* frames, const uint8_t* out, int noc, float wn, float tau) {
-  if (!frames || !out) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  if (out == frames) return fail(OFDIS_ERR_INVALID, "the temporal filter does not work in place");
-  if (noc != 1 && noc != 3) return fail(OFDIS_ERR_INVALID, "noc must be 1 or 3");
-  if (!(wn >= 0.0f && wn <= 1.0f)) return fail(OFDIS_ERR_INVALID, "wn must be inside [0, 1]");
-  if (!(tau >= FLT_MIN)) return fail(OFDIS_ERR_INVALID, "tau must be +inf or a positive float that is not subnormal");
-  return OFDIS_OK;
-}
-
-int ofdis_temporal_filter(const uint8_t* frames, const float* flow_fw, const float* flow_rev, const uint8_t* mask_fw,
-                          const uint8_t* mask_rev, uint8_t* out, uint8_t* support, int npairs, int width, int height, int noc,
-                          float wn, float tau, void* stream) {
-  if (!flow_fw || !flow_rev) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  if (int rc = tfilter_args_check(frames, out, noc, wn, tau)) return rc;
-  if (npairs < 1 || width < 1 || height < 1 || (long long)width * height > (1ll << 30))
-    return fail(OFDIS_ERR_INVALID, "bad sizes");
-  HIPCHK(launch_tfilter_frames(frames, flow_fw, flow_rev, mask_fw, mask_rev, out, support, npairs, width, height, noc, wn, tau,
-                               (hipStream_t)stream));
-  return OFDIS_OK;
-}
-
-int ofdis_batch_temporal_filter(ofdis_batch* b, const uint8_t* frames, int first_frame, int count, uint8_t* out,
-                                uint8_t* support, int width_org, int height_org, float wn, float tau, float alpha, float beta,
-                                void* stream) {
-  if (!b) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  if (!b->sequence)  // (the pairs of any other context share no frames)
-    return fail(OFDIS_ERR_INVALID, b->reverse ? "not a context created with OFDIS_BATCH_SEQUENCE"
-                                              : "not a context created with OFDIS_BATCH_SEQUENCE | OFDIS_BATCH_REVERSE");
-  if (!b->reverse) return fail(OFDIS_ERR_INVALID, "not a context created with OFDIS_BATCH_REVERSE");
-  const ofdis_params& p = b->p;
-  if (int rc = tfilter_args_check(frames, out, p.noc, wn, tau)) return rc;
-  if (!fb_constants_ok(alpha, beta)) return fail(OFDIS_ERR_INVALID, "alpha and beta must be finite and >= 0");
-  Finish fin;
-  if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
-  HIPCHK(launch_tfilter_level(frames + (size_t)first_frame * width_org * height_org * p.noc, b->flow[0] + fin.off,
-                              b->flow_rev[0] + fin.off, out, support, count, fin.g, p.noc, wn, tau, alpha, beta,
-                              (hipStream_t)stream));
-  return OFDIS_OK;
-}
-
-// ------------------------------------------------------------------------------------ trajectory filter (ofdis_trajfilter.hip)
-static_assert(sizeof(TrajWeights::w) / sizeof(float) == OFDIS_TRAJ_MAX_RADIUS, "TrajWeights holds OFDIS_TRAJ_MAX_RADIUS");
-static int trajfilter_args_check(const uint8_t* frames, const uint8_t* out, int noc, const float* weights, int radius, float tau,
-                                 int fb_check, float alpha, float beta, TrajWeights& tw) {
-  if (!frames || !out) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  if (out == frames) return fail(OFDIS_ERR_INVALID, "the trajectory filter does not work in place");
-  if (noc != 1 && noc != 3) return fail(OFDIS_ERR_INVALID, "noc must be 1 or 3");
-  if (!weights) return fail(OFDIS_ERR_INVALID, "weights is NULL");
-  if (radius < 1 || radius > OFDIS_TRAJ_MAX_RADIUS) return fail(OFDIS_ERR_INVALID, "radius must be 1..OFDIS_TRAJ_MAX_RADIUS");
-  memset(&tw, 0, sizeof(tw));
-  for (int j = 0; j < radius; ++j) {
-    if (!(weights[j] >= 0.0f && weights[j] <= 1.0f)) return fail(OFDIS_ERR_INVALID, "every weight must be inside [0, 1]");
-    tw.w[j] = weights[j];
-  }
-  tw.radius = radius;
-  if (!(tau >= FLT_MIN)) return fail(OFDIS_ERR_INVALID, "tau must be +inf or a positive float that is not subnormal");
-  if (fb_check != 0 && fb_check != 1) return fail(OFDIS_ERR_INVALID, "fb_check must be 0 or 1");
-  if (!fb_constants_ok(alpha, beta)) return fail(OFDIS_ERR_INVALID, "alpha and beta must be finite and >= 0");
-  return OFDIS_OK;
-}
-
-int ofdis_trajectory_filter(const uint8_t* frames, const float* flow_fw, const float* flow_rev, uint8_t* out, uint8_t* support,
-                            int npairs, int width, int height, int noc, const float* weights, int radius, float tau,
-                            int fb_check, float alpha, float beta, void* stream) {
-  if (!flow_fw || !flow_rev) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  TrajWeights tw;
-  if (int rc = trajfilter_args_check(frames, out, noc, weights, radius, tau, fb_check, alpha, beta, tw)) return rc;
-  if (npairs < 1 || width < 1 || height < 1 || (long long)width * height > (1ll << 30))
-    return fail(OFDIS_ERR_INVALID, "bad sizes");
-  HIPCHK(launch_trajfilter_frames(frames, flow_fw, flow_rev, out, support, npairs, width, height, noc, tw, tau, fb_check != 0,
-                                  alpha, beta, (hipStream_t)stream));
-  return OFDIS_OK;
-}
-
-int ofdis_batch_trajectory_filter(ofdis_batch* b, const uint8_t* frames, int first_frame, int count, uint8_t* out,
-                                  uint8_t* support, int width_org, int height_org, const float* weights, int radius, float tau,
-                                  int fb_check, float alpha, float beta, void* stream) {
-  if (!b) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  if (!b->sequence)  // (the pairs of any other context share no frames)
-    return fail(OFDIS_ERR_INVALID, b->reverse ? "not a context created with OFDIS_BATCH_SEQUENCE"
-                                              : "not a context created with OFDIS_BATCH_SEQUENCE | OFDIS_BATCH_REVERSE");
-  if (!b->reverse)  // (whatever fb_check is: walking back takes the reverse flows)
-    return fail(OFDIS_ERR_INVALID, "not a context created with OFDIS_BATCH_REVERSE");
-  const ofdis_params& p = b->p;
-  TrajWeights tw;
-  if (int rc = trajfilter_args_check(frames, out, p.noc, weights, radius, tau, fb_check, alpha, beta, tw)) return rc;
-  Finish fin;
-  if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
-  HIPCHK(launch_trajfilter_level(frames + (size_t)first_frame * width_org * height_org * p.noc, b->flow[0] + fin.off,
-                                 b->flow_rev[0] + fin.off, out, support, count, fin.g, p.noc, tw, tau, fb_check != 0, alpha, beta,
-                                 (hipStream_t)stream));
-  return OFDIS_OK;
-}
-
-// ------------------------------------------------------------------------------------ global motion (ofdis_gmotion.hip)
-static bool gm_sizes_ok(int npairs, int width, int height) {
-  return npairs >= 1 && width >= 1 && height >= 1 && width <= OFDIS_GM_MAX_SIDE && height <= OFDIS_GM_MAX_SIDE;
-}
-static int gm_thresh_check(float thresh) {
-  if (!(std::isfinite(thresh) && thresh > 0.0f)) return fail(OFDIS_ERR_INVALID, "thresh must be finite and > 0");
-  return OFDIS_OK;
-}
-static int gm_fit_check(int model, int rounds, float thresh) {
-  if (model != OFDIS_GM_TRANSLATION_ONLY && model != OFDIS_GM_AFFINE)
-    return fail(OFDIS_ERR_INVALID, "model must be OFDIS_GM_TRANSLATION_ONLY or OFDIS_GM_AFFINE");
-  if (rounds < 1 || rounds > OFDIS_GM_MAX_ROUNDS) return fail(OFDIS_ERR_INVALID, "rounds outside 1..OFDIS_GM_MAX_ROUNDS");
-  return gm_thresh_check(thresh);
-}
-static const char* const kGmSizes = "bad sizes (a side above OFDIS_GM_MAX_SIDE?)";
-// what both batch calls check about the context and the mask they are asked for
-static int gm_batch_check(const ofdis_batch* b, int fb_check, float alpha, float beta, int width_org, int height_org) {
-  if (!b) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  if (b->p.selectmode == 2) return fail(OFDIS_ERR_INVALID, "not an optical-flow context (stereo-depth mode has no flow field)");
-  if (fb_check != 0 && fb_check != 1) return fail(OFDIS_ERR_INVALID, "fb_check must be 0 or 1");
-  if (fb_check && !b->reverse) return fail(OFDIS_ERR_INVALID, "fb_check needs a context created with OFDIS_BATCH_REVERSE");
-  if (!fb_constants_ok(alpha, beta)) return fail(OFDIS_ERR_INVALID, "alpha and beta must be finite and >= 0");
-  if (width_org > OFDIS_GM_MAX_SIDE || height_org > OFDIS_GM_MAX_SIDE) return fail(OFDIS_ERR_INVALID, kGmSizes);
-  return OFDIS_OK;
-}
-
-size_t ofdis_global_motion_work_bytes(int npairs, int width, int height) {
-  return gm_sizes_ok(npairs, width, height) ? gmotion_work_bytes(npairs, width, height) : 0;
-}
-
-int ofdis_global_motion(const float* flow, const uint8_t* mask, int npairs, int width, int height, int model, int rounds,
-                        float thresh, double* models, long long* stats, void* work, size_t work_bytes, void* stream) {
-  if (!flow || !models) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  if (int rc = gm_fit_check(model, rounds, thresh)) return rc;
-  if (!gm_sizes_ok(npairs, width, height)) return fail(OFDIS_ERR_INVALID, kGmSizes);
-  if (!work || ((uintptr_t)work & 7) || work_bytes < gmotion_work_bytes(npairs, width, height))
-    return fail(OFDIS_ERR_INVALID, "work buffer is NULL, not 8-byte aligned or smaller than ofdis_global_motion_work_bytes");
-  HIPCHK(launch_gmotion_frames(flow, mask, npairs, width, height, model, rounds, thresh, models, stats, work,
-                               (hipStream_t)stream));
-  return OFDIS_OK;
-}
-
-int ofdis_motion_compensate(const float* flow, const uint8_t* mask, const double* models, int npairs, int width, int height,
-                            float thresh, float* residual, uint8_t* label, void* stream) {
-  if (!flow || !models || (!residual && !label)) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  if (int rc = gm_thresh_check(thresh)) return rc;
-  if (!gm_sizes_ok(npairs, width, height)) return fail(OFDIS_ERR_INVALID, kGmSizes);
-  HIPCHK(launch_gmotion_compensate_frames(flow, mask, models, npairs, width, height, thresh, residual, label,
-                                          (hipStream_t)stream));
-  return OFDIS_OK;
-}
-
-int ofdis_batch_global_motion(ofdis_batch* b, int first_frame, int count, int model, int rounds, float thresh, int fb_check,
-                              float alpha, float beta, double* models, long long* stats, int width_org, int height_org,
-                              void* stream) {
-  if (int rc = gm_batch_check(b, fb_check, alpha, beta, width_org, height_org)) return rc;
-  if (!models) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  if (int rc = gm_fit_check(model, rounds, thresh)) return rc;
-  Finish fin;
-  if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
-  if (!b->gm_slab) {  // records for every pair at the padded size (no original size needs more), held as floats
-    dalloc(b, &b->gm_slab, gmotion_work_bytes(1, std::min(b->p.width, OFDIS_GM_MAX_SIDE), std::min(b->p.height, OFDIS_GM_MAX_SIDE)) /
-                               sizeof(float), false);
-    if (int rc = dcommit(b)) return rc;
-  }
-  HIPCHK(launch_gmotion_level(b->flow[0] + fin.off, fb_check ? b->flow_rev[0] + fin.off : nullptr, count, fin.g, model, rounds,
-                              thresh, alpha, beta, models, stats, b->gm_slab, (hipStream_t)stream));
-  return OFDIS_OK;
-}
-
-int ofdis_batch_motion_compensate(ofdis_batch* b, int first_frame, int count, const double* models, float thresh, int fb_check,
-                                  float alpha, float beta, float* residual, uint8_t* label, int width_org, int height_org,
-                                  void* stream) {
-  if (int rc = gm_batch_check(b, fb_check, alpha, beta, width_org, height_org)) return rc;
-  if (!models || (!residual && !label)) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  if (int rc = gm_thresh_check(thresh)) return rc;
-  Finish fin;
-  if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
-  HIPCHK(launch_gmotion_compensate_level(b->flow[0] + fin.off, fb_check ? b->flow_rev[0] + fin.off : nullptr, models, count, fin.g,
-                                         thresh, alpha, beta, residual, label, (hipStream_t)stream));
-  return OFDIS_OK;
-}
-
-// ------------------------------------------------------------------------------------ video stabilisation (ofdis_stabilize.hip)
-static_assert(sizeof(StabWindow::w) / sizeof(double) == OFDIS_STAB_MAX_RADIUS + 1, "StabWindow holds OFDIS_STAB_MAX_RADIUS + 1 weights");
-static int stab_window(const double* weights, int radius, double zoom, StabWindow& win) {
-  if (!weights) return fail(OFDIS_ERR_INVALID, "weights is NULL");
-  if (radius < 0 || radius > OFDIS_STAB_MAX_RADIUS) return fail(OFDIS_ERR_INVALID, "radius outside 0..OFDIS_STAB_MAX_RADIUS");
-  memset(&win, 0, sizeof(win));
-  for (int j = 0; j <= radius; ++j) {
-    if (!(std::isfinite(weights[j]) && weights[j] >= 0.0 && (j > 0 || weights[j] > 0.0)))
-      return fail(OFDIS_ERR_INVALID, "weights must be finite, w_0 > 0 and the others >= 0");
-    win.w[j] = weights[j];
-  }
-  if (!(std::isfinite(zoom) && zoom >= 1.0 && zoom <= OFDIS_STAB_MAX_ZOOM))
-    return fail(OFDIS_ERR_INVALID, "zoom must be inside [1, OFDIS_STAB_MAX_ZOOM]");
-  win.zoom = zoom;
-  win.radius = radius;
-  return OFDIS_OK;
-}
-static int stab_warp_check(const uint8_t* frames, const uint8_t* out, int noc, int border) {
-  if (!frames || !out) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  if (out == frames) return fail(OFDIS_ERR_INVALID, "the frame warp does not work in place");
-  if (noc != 1 && noc != 3) return fail(OFDIS_ERR_INVALID, "noc must be 1 or 3");
-  if (border != OFDIS_BORDER_CONSTANT && border != OFDIS_BORDER_REPLICATE)
-    return fail(OFDIS_ERR_INVALID, "border must be OFDIS_BORDER_CONSTANT or OFDIS_BORDER_REPLICATE");
-  return OFDIS_OK;
-}
-
-int ofdis_camera_path(const double* models, int npairs, const double* weights, int radius, double zoom, double* warps,
-                      void* stream) {
-  if (!models || !warps) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  StabWindow win;
-  if (int rc = stab_window(weights, radius, zoom, win)) return rc;
-  if (npairs < 1) return fail(OFDIS_ERR_INVALID, "bad sizes (npairs < 1)");
-  HIPCHK(launch_camera_path(models, npairs, win, warps, (hipStream_t)stream));
-  return OFDIS_OK;
-}
-
-int ofdis_warp_frames(const uint8_t* frames, const double* warps, uint8_t* out, uint8_t* inside, int nframes, int width,
-                      int height, int noc, int border, void* stream) {
-  if (!warps) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  if (int rc = stab_warp_check(frames, out, noc, border)) return rc;
-  if (!gm_sizes_ok(nframes, width, height)) return fail(OFDIS_ERR_INVALID, kGmSizes);
-  HIPCHK(launch_warp_frames(frames, warps, out, inside, nframes, width, height, noc, border == OFDIS_BORDER_REPLICATE,
-                            (hipStream_t)stream));
-  return OFDIS_OK;
-}
-
-int ofdis_batch_stabilize(ofdis_batch* b, const uint8_t* frames, int first_frame, int count, int model, int rounds, float thresh,
-                          int fb_check, float alpha, float beta, const double* weights, int radius, double zoom, int border,
-                          uint8_t* out, uint8_t* inside, double* warps, int width_org, int height_org, void* stream) {
-  if (int rc = gm_batch_check(b, fb_check, alpha, beta, width_org, height_org)) return rc;
-  if (!b->sequence) return fail(OFDIS_ERR_INVALID, kSeqOnly);  // (the pairs of any other context are no chain)
-  if (int rc = gm_fit_check(model, rounds, thresh)) return rc;
-  StabWindow win;
-  if (int rc = stab_window(weights, radius, zoom, win)) return rc;
-  const ofdis_params& p = b->p;
-  if (int rc = stab_warp_check(frames, out, p.noc, border)) return rc;
-  Finish fin;
-  if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
-  if (!b->stab_path) {  // 6 + 6 doubles per pair and 6 more for the last frame, held as floats
-    dalloc(b, &b->stab_path, 24, false, 1);
-    if (int rc = dcommit(b)) return rc;
-  }
-  double* models = reinterpret_cast<double*>(b->stab_path);
-  double* path = models + (size_t)b->nframes * 6;
-  hipStream_t s = (hipStream_t)stream;
-  if (int rc = ofdis_batch_global_motion(b, first_frame, count, model, rounds, thresh, fb_check, alpha, beta, models, nullptr,
-                                         width_org, height_org, stream))
-    return rc;
-  HIPCHK(launch_camera_path(models, count, win, path, s));
-  HIPCHK(launch_warp_frames(frames + (size_t)first_frame * width_org * height_org * p.noc, path, out, inside, count + 1, width_org,
-                            height_org, p.noc, border == OFDIS_BORDER_REPLICATE, s));
-  if (warps) HIPCHK(hipMemcpyAsync(warps, path, (size_t)(count + 1) * 6 * sizeof(double), hipMemcpyDeviceToDevice, s));
+int ofdis_batch_upload_initflow(ofdis_batch* b, int frame, const float* initflow_host, void* stream) {
+  if (!b || frame < 0 || frame >= b->nframes || !initflow_host) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  const size_t n = ofdis_batch_initflow_elems(b);
+  const bool first_use = !b->initflow_own;
+  if (int rc = dstage(b, {{&b->initflow_own, n}})) return rc;
+  if (first_use) HIPCHK(hipMemsetAsync(b->initflow_own, 0, n * b->nframes * sizeof(float), (hipStream_t)stream));
+  HIPCHK(hipMemcpyAsync(frame_at(*b, b->initflow_own, frame), initflow_host, n * sizeof(float), hipMemcpyHostToDevice,
+                        (hipStream_t)stream));
+  b->initflow = b->initflow_own;
   return OFDIS_OK;
 }
 

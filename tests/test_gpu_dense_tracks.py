@@ -325,6 +325,31 @@ def test_batch_form_without_the_test_on_a_forward_only_sequence(gpu, contract):
     assert_dense_equal(got, gpu.dense_tracks(frames, fw, None, STRIDE, WINDOW, T, 2), "forward-only sequence context")
 
 
+def test_batch_form_grows_its_work_buffer(gpu):
+    """one pair first, then all n: the second call needs more than the first left, allocates again and gives what a context
+    that never held the smaller buffer gives; a call that needs no more allocates nothing"""
+    w, h, n = 250, 107, 3
+    T = _clip_threshold(_clip(w, h, 1, n + 1), STRIDE, WINDOW)
+    b, d = _sequence_context(gpu, w, h, 1, n, 0)
+    try:
+        sizes = [b.device_bytes()]
+        b.dense_tracks(d.ptr, w, h, STRIDE, WINDOW, T, first=0, count=1)
+        sizes.append(b.device_bytes())
+        grown = b.dense_tracks(d.ptr, w, h, STRIDE, WINDOW, T, first=0, count=n)
+        sizes.append(b.device_bytes())
+        b.dense_tracks(d.ptr, w, h, STRIDE, WINDOW, T, first=0, count=n)
+        sizes.append(b.device_bytes())
+    finally:
+        b.close()
+    assert sizes[0] < sizes[1] < sizes[2] == sizes[3], sizes
+    fresh, d = _sequence_context(gpu, w, h, 1, n, 0)
+    try:
+        want = fresh.dense_tracks(d.ptr, w, h, STRIDE, WINDOW, T, first=0, count=n)
+    finally:
+        fresh.close()
+    assert_dense_equal(grown, want, "after the work buffer grew")
+
+
 # ------------------------------------------------------------------ 6. checks that need a context
 @pytest.fixture(scope="module")
 def contexts(gpu):
