@@ -522,8 +522,9 @@ int ofdis_batch_dense_tracks(ofdis_batch* b, const uint8_t* frames, int first_fr
  *   Translation: adding a constant vector to Ffw leaves MBHx and MBHy unchanged wherever the sums stay finite and no rounding
  *     occurs -- stated for integer-valued test flows only.
  *   Contract independence: integer sums of separately rounded values; one unit, compiled once, serves both contracts.
- * Not provided: interpolation of a vote between neighbouring bins; normalisation on the device (of_dis_amd/tracking.py:
- * normalize_descriptors, on the host); filtering of static or erratic tracks; a form that reads a sequence context's level
+ * Not provided: interpolation of a vote between neighbouring bins; normalisation in floating point (of_dis_amd/tracking.py:
+ * normalize_descriptors, on the host -- the 8-bit RootSIFT form on the device and the bag of features made of it are the next
+ * section, ofdis_descriptor_normalize .. ofdis_track_bof); filtering of static or erratic tracks; a form that reads a sequence context's level
  * flows directly -- every window pixel needs five flow values and is visited by about 40 overlapping windows, and rebuilding
  * flow values from level flows already loses when each is used a handful of times (README: trajectory filter, global motion).
  * The route is ofdis_batch_upsample_bidir -> ofdis_dense_tracks -> this call.
@@ -541,6 +542,73 @@ int ofdis_track_descriptors(const uint8_t* frames, const float* flow_fw, int npa
                             const float* tracks, const int* start, const int* len, const long long* info,
                             int lmax, int max_tracks, int patch, int nxy, int nt, float min_flow,
                             uint32_t* hist, float* shape /* or NULL */, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Bag-of-features encoding of those descriptors, the last stage of Wang et al.'s pipeline: every histogram channel of a hist
+ * row becomes an 8-bit RootSIFT descriptor, each is matched against the words of a codebook by squared Euclidean distance, and
+ * the clip is described by how often every word was the nearest one.  Everything is integer arithmetic: a result is a pure
+ * function of its inputs, independent of the order of any sum, of the kernels' mapping and of the arithmetic contract.
+ *
+ * Notation of the section above: C = nxy*nxy*nt, D = 33*C; channel c = 0 .. 3 (HOG, HOF, MBHx, MBHy) is the segment of a row
+ * that starts at 0, 8*C, 17*C, 25*C and has n_c = 8*C, 9*C, 8*C, 8*C entries; nxy: 1 .. 4, nt: 1 .. 8 (the patch is no
+ * argument).  info = the device array {ntracks, dropped} of ofdis_dense_tracks; ntracks never reaches the host, and every call
+ * neither reads nor writes anything of the slots >= ntracks.  max_tracks: 1 .. OFDIS_DT_MAX_TRACKS.
+ *
+ * Normalisation (ofdis_descriptor_normalize): hist [max_tracks][D] u32 -> desc [max_tracks][D] u8, same index order.  Per slot
+ * and channel, with S the uint64 sum of the channel's entries h_e:
+ *   S == 0: desc_e = 0 for the whole channel.
+ *   otherwise desc_e = min(255, max{ q >= 0 : q*q*S <= 510*510*h_e }), division-free uint64 arithmetic, every product < 2^62.
+ * Identity: max{ q : q*q*S <= T } = floor(sqrt(floor(T / S))) for integers T >= 0, S > 0 (q*q*S <= T <=> q*q <= T/S <=>
+ * q*q <= floor(T/S), q*q being an integer), so without the clamp desc_e = floor(sqrt(floor(510*510*h_e / S))): RootSIFT
+ * (divide by the L1 norm, take the square root; Arandjelovic and Zisserman 2012) in units of 1/OFDIS_BOF_SCALE, clamped at
+ * 255 -- the convention of 8-bit SIFT (x 512, clamp 255).  An entry reaches 255 where it holds a quarter of its channel's sum
+ * or more.
+ *
+ * Assignment (ofdis_codebook_assign): codebook [nwords][D] u8, row k holds word k of every channel in the index order of a
+ * hist row; nwords: 1 .. OFDIS_BOF_MAX_WORDS.  For slot i and channel c, d(k) = sum over the channel's entries e of
+ * (desc[i][e] - codebook[k][e])^2, at most 1152*255*255 < 2^31; words[i][c] = the smallest k that attains the minimum of d,
+ * dist[i][c] = that minimum.  words, dist = [max_tracks][4] int32; dist may be NULL.  An all-zero channel is assigned like any
+ * other.
+ *
+ * Counting (ofdis_bof_histogram): bof [4][nwords] u32, bof[c][k] = the number of slots i < ntracks with len[i] >= min_len and
+ * words[i][c] == k; min_len >= 1, and min_len = lmax + 1 counts complete tracks only, as Wang et al. do.  The call clears bof
+ * itself with a launch of its own and relies on no memset; it counts with integer atomics.  A words entry outside
+ * 0 .. nwords-1 (an array the caller filled) is not counted.
+ *
+ * Fused (ofdis_track_bof): hist -> bof in one pass, bit-identical to the three calls above in a row: it reads hist, normalises
+ * in registers, never writes desc, assigns, counts, and writes words where it is not NULL.
+ *
+ * Consequences.
+ *   Known value: a channel with one nonzero entry has that entry 255 and the rest 0; a channel of n equal nonzero entries has
+ *     every entry min(255, floor(sqrt(floor(260100 / n)))), e.g. 180 for n = 8.
+ *   Scale invariance: multiplying a channel's entries by a common factor leaves desc unchanged where no product overflows.
+ *   Ties: equal distances go to the lowest index, so a codebook with a duplicated row never uses the later copy; a codebook
+ *     drawn from the descriptors themselves gives dist 0 and the first copy.
+ *   Sums: every row of bof sums to the number of counted tracks; the four rows have the same sum.
+ *   Contract independence: integers only; one unit, compiled once, serves both contracts.
+ * Not provided: k-means training of the codebook; Fisher vectors; the shape channel (floats: it is not encoded); filtering
+ * of static tracks.  The route is ofdis_dense_tracks -> ofdis_track_descriptors -> ofdis_track_bof.  None of the calls
+ * synchronises with the host.  of_dis_amd/tracking.py states the same definitions in numpy (normalize_descriptors_u8,
+ * codebook_assign_ref, bof_ref).
+ * ------------------------------------------------------------------------------------------- */
+#define OFDIS_BOF_SCALE 510
+#define OFDIS_BOF_MAX_WORDS 16384
+/* One launch, one wavefront per slot.  OFDIS_ERR_INVALID before any device work (this and the three calls below): a NULL
+ * required pointer (all but dist, and words of ofdis_track_bof); max_tracks outside 1 .. OFDIS_DT_MAX_TRACKS; nxy or nt
+ * outside its range; nwords outside 1 .. OFDIS_BOF_MAX_WORDS; min_len < 1. */
+int ofdis_descriptor_normalize(const uint32_t* hist, const long long* info, int max_tracks, int nxy, int nt, uint8_t* desc,
+                               void* stream);
+/* One launch: v_mfma_i32_16x16x64_i8 on the bytes ^ 0x80 (both sides minus 128: differences unchanged), 64 to 512 slots of one
+ * channel per workgroup, the codebook through LDS in tiles. */
+int ofdis_codebook_assign(const uint8_t* desc, const long long* info, int max_tracks, int nxy, int nt, const uint8_t* codebook,
+                          int nwords, int* words, int* dist /* or NULL */, void* stream);
+/* Two launches: the clear, the count. */
+int ofdis_bof_histogram(const int* words, const int* len, const long long* info, int max_tracks, int nwords, int min_len,
+                        uint32_t* bof, void* stream);
+/* Two launches: the clear, then the assignment kernel reading hist. */
+int ofdis_track_bof(const uint32_t* hist, const int* len, const long long* info, int max_tracks, int nxy, int nt,
+                    const uint8_t* codebook, int nwords, int min_len, uint32_t* bof, int* words /* or NULL */,
+                    void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Motion-compensated temporal filtering of a clip: every frame averaged with its two neighbours warped onto it by the flow

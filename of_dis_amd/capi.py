@@ -45,6 +45,7 @@ ABI_SYMBOLS = [
     "ofdis_dense_tracks_cells", "ofdis_dense_tracks_work_bytes", "ofdis_seed_texture", "ofdis_dense_tracks",
     "ofdis_batch_dense_tracks",
     "ofdis_track_descriptor_dims", "ofdis_track_descriptors",
+    "ofdis_descriptor_normalize", "ofdis_codebook_assign", "ofdis_bof_histogram", "ofdis_track_bof",
     "ofdis_temporal_filter", "ofdis_batch_temporal_filter",
     "ofdis_trajectory_filter", "ofdis_batch_trajectory_filter",
     "ofdis_global_motion_work_bytes", "ofdis_global_motion", "ofdis_motion_compensate", "ofdis_batch_global_motion",
@@ -63,6 +64,7 @@ ENC_F32, ENC_F16, ENC_U16, ENC_U8 = 0, 1, 2, 3  # OFDIS_ENC_*
 TRACK_MAX_POINTS = 1 << 24  # OFDIS_TRACK_MAX_POINTS
 DT_MAX_TRACKS, DT_MAX_STRIDE, DT_MAX_WINDOW = 1 << 24, 64, 7  # OFDIS_DT_MAX_*
 DESC_MAX_PATCH = 64  # OFDIS_DESC_MAX_PATCH
+BOF_SCALE, BOF_MAX_WORDS = 510, 16384  # OFDIS_BOF_*
 TRAJ_MAX_RADIUS = 8  # OFDIS_TRAJ_MAX_RADIUS
 GM_MAX_SIDE, GM_MAX_FLOW, GM_MAX_ROUNDS = 8192, 4096.0, 8  # OFDIS_GM_MAX_*
 GM_TRANSLATION_ONLY, GM_AFFINE = 0, 1  # OFDIS_GM_* model
@@ -225,6 +227,10 @@ def lib():
         L.ofdis_track_descriptor_dims.argtypes = [C.c_int, C.c_int, C.c_int]
         L.ofdis_track_descriptors.argtypes = [VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int,
                                               C.c_int, C.c_int, C.c_float, VP, VP, VP]
+        L.ofdis_descriptor_normalize.argtypes = [VP, VP, C.c_int, C.c_int, C.c_int, VP, VP]
+        L.ofdis_codebook_assign.argtypes = [VP, VP, C.c_int, C.c_int, C.c_int, VP, C.c_int, VP, VP, VP]
+        L.ofdis_bof_histogram.argtypes = [VP, VP, VP, C.c_int, C.c_int, C.c_int, VP, VP]
+        L.ofdis_track_bof.argtypes = [VP, VP, VP, C.c_int, C.c_int, C.c_int, VP, C.c_int, C.c_int, VP, VP, VP]
         L.ofdis_temporal_filter.argtypes = [VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                             VP]
         L.ofdis_batch_temporal_filter.argtypes = [VP, VP, C.c_int, C.c_int, VP, VP, C.c_int, C.c_int, C.c_float, C.c_float,
@@ -727,6 +733,83 @@ def track_descriptors(frames, flow_fw, tracks, start, length, patch, nxy, nt, mi
                           min_flow, dh.ptr, dsh.ptr if dsh else None)
     check(lib().ofdis_sync(None))
     return (dh.get((slots, D), np.uint32)[:n].copy(), dsh.get((slots, lmax, 2), _f32)[:n].copy() if dsh else None)
+
+
+def _bof_inputs(rows, D, dtype):
+    """[ntracks, D] rows of `dtype` -> (the rows, ntracks, slots, a Dev of them with one idle slot for an empty array)"""
+    rows = np.ascontiguousarray(rows, dtype)
+    assert rows.ndim == 2 and rows.shape[1] == D, (rows.shape, D)
+    n = rows.shape[0]
+    return rows, n, max(n, 1), Dev(rows if n else np.zeros((1, D), dtype))
+
+
+def _bof_codebook(codebook, D):
+    codebook = np.ascontiguousarray(codebook, np.uint8)
+    assert codebook.ndim == 2 and codebook.shape[1] == D and 1 <= codebook.shape[0] <= BOF_MAX_WORDS, (codebook.shape, D)
+    return codebook
+
+
+def descriptor_normalize(hist, nxy, nt):
+    """ofdis_descriptor_normalize on host arrays: hist uint32 [ntracks, 33 * nxy^2 * nt] -> desc uint8 of the same shape, every
+    channel an 8-bit RootSIFT descriptor in units of 1 / BOF_SCALE.  of_dis_amd/tracking.py: normalize_descriptors_u8."""
+    D = 33 * nxy * nxy * nt
+    hist, n, slots, dh = _bof_inputs(hist, D, np.uint32)
+    di, dd = Dev(np.array([n, 0], np.int64)), Dev(nbytes=slots * D)
+    check(lib().ofdis_descriptor_normalize(dh.ptr, di.ptr, slots, nxy, nt, dd.ptr, None))
+    check(lib().ofdis_sync(None))
+    return dd.get((slots, D), np.uint8)[:n].copy()
+
+
+def codebook_assign(desc, codebook, nxy, nt):
+    """ofdis_codebook_assign on host arrays: desc uint8 [ntracks, D], codebook uint8 [nwords, D] -> (words, dist), each int32
+    [ntracks, 4]: per channel (HOG, HOF, MBHx, MBHy) the nearest word, the lowest index on a tie, and its squared distance.
+    of_dis_amd/tracking.py: codebook_assign_ref."""
+    D = 33 * nxy * nxy * nt
+    desc, n, slots, dd = _bof_inputs(desc, D, np.uint8)
+    codebook = _bof_codebook(codebook, D)
+    di, dc = Dev(np.array([n, 0], np.int64)), Dev(codebook)
+    dw, ds = Dev(nbytes=slots * 16), Dev(nbytes=slots * 16)
+    check(lib().ofdis_codebook_assign(dd.ptr, di.ptr, slots, nxy, nt, dc.ptr, len(codebook), dw.ptr, ds.ptr, None))
+    check(lib().ofdis_sync(None))
+    return dw.get((slots, 4), np.int32)[:n].copy(), ds.get((slots, 4), np.int32)[:n].copy()
+
+
+def bof_histogram(words, length, nwords, min_len=1):
+    """ofdis_bof_histogram on host arrays: words int32 [ntracks, 4], length int32 [ntracks] -> bof uint32 [4, nwords], the tracks
+    of at least min_len points counted by their words.  of_dis_amd/tracking.py: bof_ref."""
+    words, n, slots, dw = _bof_inputs(words, 4, np.int32)
+    length = np.ascontiguousarray(length, np.int32)
+    assert length.shape == (n,), (length.shape, n)
+    dl, di, db = Dev(length if n else np.zeros(1, np.int32)), Dev(np.array([n, 0], np.int64)), Dev(nbytes=16 * nwords)
+    check(lib().ofdis_bof_histogram(dw.ptr, dl.ptr, di.ptr, slots, nwords, min_len, db.ptr, None))
+    check(lib().ofdis_sync(None))
+    return db.get((4, nwords), np.uint32)
+
+
+def track_bof_dev(hist_ptr, len_ptr, info_ptr, max_tracks, nxy, nt, codebook_ptr, nwords, min_len, bof_ptr, words_ptr=None,
+                  stream=None):
+    """ofdis_track_bof on device pointers: hist [max_tracks][D] uint32 as ofdis_track_descriptors wrote it, len and info as
+    ofdis_dense_tracks did, codebook [nwords][D] uint8 -> bof [4][nwords] uint32 and, where asked for, words [max_tracks][4]
+    int32.  Enqueues on `stream` and returns; nothing synchronises with the host."""
+    check(lib().ofdis_track_bof(hist_ptr, len_ptr, info_ptr, max_tracks, nxy, nt, codebook_ptr, nwords, min_len, bof_ptr, words_ptr,
+                                stream))
+
+
+def track_bof(hist, length, codebook, nxy, nt, min_len=1, words=False):
+    """ofdis_track_bof on host arrays: hist uint32 [ntracks, D] and length [ntracks] (track_descriptors, dense_tracks), codebook
+    uint8 [nwords, D] -> bof uint32 [4, nwords], or (bof, words int32 [ntracks, 4]) with words=True: normalisation, assignment
+    and counting in one pass, bit-identical to descriptor_normalize -> codebook_assign -> bof_histogram."""
+    D = 33 * nxy * nxy * nt
+    hist, n, slots, dh = _bof_inputs(hist, D, np.uint32)
+    codebook = _bof_codebook(codebook, D)
+    length = np.ascontiguousarray(length, np.int32)
+    assert length.shape == (n,), (length.shape, n)
+    dl, di, dc = Dev(length if n else np.zeros(1, np.int32)), Dev(np.array([n, 0], np.int64)), Dev(codebook)
+    db, dw = Dev(nbytes=16 * len(codebook)), Dev(nbytes=slots * 16) if words else None
+    track_bof_dev(dh.ptr, dl.ptr, di.ptr, slots, nxy, nt, dc.ptr, len(codebook), min_len, db.ptr, dw.ptr if dw else None)
+    check(lib().ofdis_sync(None))
+    bof = db.get((4, len(codebook)), np.uint32)
+    return (bof, dw.get((slots, 4), np.int32)[:n].copy()) if words else bof
 
 
 def temporal_filter(frames, flow_fw, flow_rev, mask_fw=None, mask_rev=None, wn=1.0, tau=np.inf, support=True):

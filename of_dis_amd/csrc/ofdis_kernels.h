@@ -265,6 +265,18 @@ hipError_t launch_dense_tracks_level(const uint8_t* frames, const float* fw, con
 hipError_t launch_track_descriptors(const uint8_t* frames, const float* flow, int npairs, int w, int h, int noc, const float* tracks,
                                     const int* start, const int* len, const long long* info, int lmax, int max_tracks, int patch,
                                     int nxy, int nt, float min_flow, uint32_t* hist, float* shape, hipStream_t s);
+// bag-of-features encoding of those descriptors (include/ofdis.h: ofdis_descriptor_normalize ... ofdis_track_bof;
+// ofdis_bof.hip): hist -> desc u8 per slot and channel; desc against codebook [nwords][33 nxy^2 nt] u8 on the matrix cores ->
+// words, dist [max_tracks][4] (either may be null); words -> bof [4][nwords], cleared by a launch of its own; and the three in
+// one pass that never writes desc.  All sized by max_tracks, the slots >= info[0] neither read nor written
+hipError_t launch_descriptor_normalize(const uint32_t* hist, const long long* info, int max_tracks, int nxy, int nt, uint8_t* desc,
+                                       hipStream_t s);
+hipError_t launch_codebook_assign(const uint8_t* desc, const long long* info, int max_tracks, int nxy, int nt, const uint8_t* codebook,
+                                  int nwords, int* words, int* dist, hipStream_t s);
+hipError_t launch_bof_histogram(const int* words, const int* len, const long long* info, int max_tracks, int nwords, int min_len,
+                                uint32_t* bof, hipStream_t s);
+hipError_t launch_track_bof(const uint32_t* hist, const int* len, const long long* info, int max_tracks, int nxy, int nt,
+                            const uint8_t* codebook, int nwords, int min_len, uint32_t* bof, int* words, hipStream_t s);
 // motion-compensated temporal filter (include/ofdis.h: ofdis_temporal_filter; ofdis_tfilter.hip).  On materialised arrays:
 // frames, out [npairs + 1][h][w][noc] u8, AoS flows [npairs][h][w][2], masks [npairs][h][w] or null, support
 // [npairs + 1][h][w] or null

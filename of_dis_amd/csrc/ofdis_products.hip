@@ -1,6 +1,6 @@
 // ofdis_products.hip -- what is made from a context's flows, and the same steps on caller-supplied arrays: the full-resolution
-// finish and its encodings, forward-backward and left-right checks, interpolation, point and dense trajectories, descriptors,
-// the temporal filters, global motion and stabilisation.  Every entry point validates its arguments, joins the pass
+// finish and its encodings, forward-backward and left-right checks, interpolation, point and dense trajectories, descriptors and
+// their bag-of-features encoding, the temporal filters, global motion and stabilisation.  Every entry point validates its arguments, joins the pass
 // (finish_begin) and launches; the checks they share are stated once, below.  Reads no environment.
 #include <cfloat>
 #include <cmath>
@@ -377,6 +377,59 @@ int ofdis_track_descriptors(const uint8_t* frames, const float* flow_fw, int npa
   if (!(min_flow >= 0.f) || std::isinf(min_flow)) return fail(OFDIS_ERR_INVALID, "min_flow must be finite and >= 0");
   HIPCHK(launch_track_descriptors(frames, flow_fw, npairs, width, height, noc, tracks, start, len, info, lmax, max_tracks, patch,
                                   nxy, nt, min_flow, hist, shape, (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+// ------------------------------------------------------------------------------------ bag of features (ofdis_bof.hip)
+// what the four calls share: the slots, the cells of the descriptor and, where asked for (0: not an argument), the codebook's
+// size and the shortest track counted
+static int bof_check(const long long* info, int max_tracks, int nxy, int nt, bool codebook, int nwords, bool counts, int min_len) {
+  if (!info) return fail(OFDIS_ERR_INVALID, "info is NULL");
+  if (max_tracks < 1 || max_tracks > OFDIS_DT_MAX_TRACKS) return fail(OFDIS_ERR_INVALID, "max_tracks outside 1..OFDIS_DT_MAX_TRACKS");
+  if (nxy < 1 || nxy > 4) return fail(OFDIS_ERR_INVALID, "nxy outside 1..4");
+  if (nt < 1 || nt > 8) return fail(OFDIS_ERR_INVALID, "nt outside 1..8");
+  if (codebook && (nwords < 1 || nwords > OFDIS_BOF_MAX_WORDS)) return fail(OFDIS_ERR_INVALID, "nwords outside 1..OFDIS_BOF_MAX_WORDS");
+  if (counts && min_len < 1) return fail(OFDIS_ERR_INVALID, "min_len below 1");
+  return OFDIS_OK;
+}
+
+int ofdis_descriptor_normalize(const uint32_t* hist, const long long* info, int max_tracks, int nxy, int nt, uint8_t* desc,
+                               void* stream) {
+  if (!hist) return fail(OFDIS_ERR_INVALID, "hist is NULL");
+  if (!desc) return fail(OFDIS_ERR_INVALID, "desc is NULL");
+  if (int rc = bof_check(info, max_tracks, nxy, nt, false, 0, false, 0)) return rc;
+  HIPCHK(launch_descriptor_normalize(hist, info, max_tracks, nxy, nt, desc, (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+int ofdis_codebook_assign(const uint8_t* desc, const long long* info, int max_tracks, int nxy, int nt, const uint8_t* codebook,
+                          int nwords, int* words, int* dist, void* stream) {
+  if (!desc) return fail(OFDIS_ERR_INVALID, "desc is NULL");
+  if (!codebook) return fail(OFDIS_ERR_INVALID, "codebook is NULL");
+  if (!words) return fail(OFDIS_ERR_INVALID, "words is NULL");
+  if (int rc = bof_check(info, max_tracks, nxy, nt, true, nwords, false, 0)) return rc;
+  HIPCHK(launch_codebook_assign(desc, info, max_tracks, nxy, nt, codebook, nwords, words, dist, (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+int ofdis_bof_histogram(const int* words, const int* len, const long long* info, int max_tracks, int nwords, int min_len,
+                        uint32_t* bof, void* stream) {
+  if (!words) return fail(OFDIS_ERR_INVALID, "words is NULL");
+  if (!len) return fail(OFDIS_ERR_INVALID, "len is NULL");
+  if (!bof) return fail(OFDIS_ERR_INVALID, "bof is NULL");
+  if (int rc = bof_check(info, max_tracks, 1, 1, true, nwords, true, min_len)) return rc;
+  HIPCHK(launch_bof_histogram(words, len, info, max_tracks, nwords, min_len, bof, (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+int ofdis_track_bof(const uint32_t* hist, const int* len, const long long* info, int max_tracks, int nxy, int nt,
+                    const uint8_t* codebook, int nwords, int min_len, uint32_t* bof, int* words, void* stream) {
+  if (!hist) return fail(OFDIS_ERR_INVALID, "hist is NULL");
+  if (!len) return fail(OFDIS_ERR_INVALID, "len is NULL");
+  if (!codebook) return fail(OFDIS_ERR_INVALID, "codebook is NULL");
+  if (!bof) return fail(OFDIS_ERR_INVALID, "bof is NULL");
+  if (int rc = bof_check(info, max_tracks, nxy, nt, true, nwords, true, min_len)) return rc;
+  HIPCHK(launch_track_bof(hist, len, info, max_tracks, nxy, nt, codebook, nwords, min_len, bof, words, (hipStream_t)stream));
   return OFDIS_OK;
 }
 

@@ -4,7 +4,9 @@ the kernels against `track_ref` bit for bit, and a user can read a track array w
 (ofdis_seed_texture, ofdis_dense_tracks, ofdis_batch_dense_tracks): the grid, the integer texture test and the frame loop of
 advance, occupancy and seeding (`dense_tracks_ref`), and the descriptors of those tracks (ofdis_track_descriptors): HOG, HOF, MBH
 and trajectory shape (`track_descriptors_ref`), where their channels lie (`descriptor_layout`) and their normalisation on the
-host (`normalize_descriptors`).
+host (`normalize_descriptors`).  Last, the bag-of-features encoding (ofdis_descriptor_normalize, ofdis_codebook_assign,
+ofdis_bof_histogram, ofdis_track_bof): 8-bit RootSIFT descriptors, nearest words and their counts, integers throughout
+(`normalize_descriptors_u8`, `codebook_assign_ref`, `bof_ref`).
 
     from of_dis_amd import tracking
     tracks, counts = batch.track_points(tracking.grid_seeds(w, h, 5), w, h)       # [n + 1][npoints][2], [npoints]
@@ -14,6 +16,7 @@ host (`normalize_descriptors`).
     by_frame = tracking.to_frame_major(dtracks, start, length, n)                # [n + 1][ntracks][2], the layout above
     hist, shape = capi.track_descriptors(frames, flow_fw, dtracks, start, length, 32, 2, 3, 0.4)   # [ntracks][396] u32
     desc = tracking.normalize_descriptors(hist, tracking.descriptor_layout(32, 2, 3), "rootsift")   # float64, per channel
+    bof = capi.track_bof(hist, length, codebook, 2, 3, min_len=16)                # [4][nwords] u32; codebook [nwords][396] u8
 """
 import numpy as np
 
@@ -413,3 +416,70 @@ def normalize_descriptors(hist, layout, how="l2"):
         if how == "rootsift":
             np.sqrt(v, out=v)
     return out
+
+
+# ------------------------------------------------------------------ bag of features (ofdis_descriptor_normalize .. ofdis_track_bof)
+BOF_SCALE, BOF_MAX_WORDS = 510, 16384  # include/ofdis.h: OFDIS_BOF_*
+
+
+def _channel_slices(layout):
+    """the four channels of a row in the order HOG, HOF, MBHx, MBHy"""
+    cells = int(np.prod(layout["cells"]))
+    return [slice(off, off + bins * cells) for off, bins in (layout["channels"][name] for name, _, _ in DESC_CHANNELS)]
+
+
+def normalize_descriptors_u8(hist, layout):
+    """The definition of ofdis_descriptor_normalize in numpy, division-free as the header states it: hist uint32 [ntracks][D] ->
+    uint8 [ntracks][D], per channel of `layout` (descriptor_layout) with its uint64 sum S: desc = min(255, max{q >= 0 :
+    q * q * S <= 510 * 510 * h}), all zero where S == 0.  Every product is an exact uint64 below 2^62; float64 only proposes a q
+    that the exact comparisons then move."""
+    hist = np.asarray(hist)
+    assert hist.dtype == np.uint32 and hist.ndim == 2 and hist.shape[1] == layout["dims"], (hist.dtype, hist.shape, layout["dims"])
+    out = np.zeros(hist.shape, np.uint8)
+    one = np.uint64(1)
+    for seg in _channel_slices(layout):
+        h = hist[:, seg].astype(np.uint64)
+        S = np.broadcast_to(h.sum(1, dtype=np.uint64)[:, None], h.shape)
+        T = h * np.uint64(BOF_SCALE * BOF_SCALE)
+        q = np.floor(np.sqrt(T.astype(np.float64) / np.maximum(S, one).astype(np.float64))).astype(np.uint64)
+        while True:  # down while q q S > T, then up while (q + 1)^2 S <= T (q <= 510: h <= S)
+            high = (q * q * S > T) & (q > 0)
+            if not high.any():
+                break
+            q[high] -= one
+        while True:
+            low = ((q + one) * (q + one) * S <= T) & (S > 0)
+            if not low.any():
+                break
+            q[low] += one
+        out[:, seg] = np.minimum(np.where(S > 0, q, 0), 255).astype(np.uint8)
+    return out
+
+
+def codebook_assign_ref(desc, layout, codebook):
+    """The definition of ofdis_codebook_assign in numpy, by direct differences in int64: desc uint8 [ntracks][D], codebook uint8
+    [nwords][D] -> (words, dist), each int32 [ntracks][4]: per channel the lowest index of the nearest word (np.argmin returns the
+    first minimum) and its squared distance."""
+    desc, codebook = np.asarray(desc), np.asarray(codebook)
+    assert desc.dtype == codebook.dtype == np.uint8 and desc.ndim == codebook.ndim == 2, (desc.dtype, codebook.dtype)
+    assert desc.shape[1] == codebook.shape[1] == layout["dims"] and 1 <= len(codebook) <= BOF_MAX_WORDS, (desc.shape, codebook.shape)
+    n = len(desc)
+    words, dist = np.zeros((n, 4), np.int32), np.zeros((n, 4), np.int32)
+    for c, seg in enumerate(_channel_slices(layout)):
+        x, cb = desc[:, seg].astype(np.int64), codebook[:, seg].astype(np.int64)
+        step = max(1, (1 << 22) // max(1, cb.size))  # tracks at a time: about 32 MB of differences
+        for i in range(0, n, step):
+            diff = x[i:i + step, None, :] - cb[None]
+            d = (diff * diff).sum(-1)
+            k = d.argmin(1)
+            words[i:i + step, c], dist[i:i + step, c] = k, d[np.arange(len(k)), k]
+    return words, dist
+
+
+def bof_ref(words, length, nwords, min_len=1):
+    """The definition of ofdis_bof_histogram in numpy: words int [ntracks][4], length [ntracks] -> uint32 [4][nwords], row c the
+    count of every word of channel c over the tracks with length >= min_len; a word outside 0 .. nwords - 1 is not counted."""
+    words, length = np.asarray(words, np.int64), np.asarray(length, np.int64)
+    assert words.ndim == 2 and words.shape[1] == 4 and length.shape == (len(words),) and min_len >= 1 and nwords >= 1
+    w = words[length >= min_len]
+    return np.stack([np.bincount(col[(col >= 0) & (col < nwords)], minlength=nwords) for col in w.T]).astype(np.uint32)
