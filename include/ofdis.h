@@ -586,8 +586,9 @@ int ofdis_track_descriptors(const uint8_t* frames, const float* flow_fw, int npa
  *     drawn from the descriptors themselves gives dist 0 and the first copy.
  *   Sums: every row of bof sums to the number of counted tracks; the four rows have the same sum.
  *   Contract independence: integers only; one unit, compiled once, serves both contracts.
- * Not provided: k-means training of the codebook; Fisher vectors; the shape channel (floats: it is not encoded); filtering
- * of static tracks.  The route is ofdis_dense_tracks -> ofdis_track_descriptors -> ofdis_track_bof.  None of the calls
+ * Not provided: Fisher vectors; the shape channel (floats: it is not encoded); filtering of static tracks.  The codebook
+ * itself comes from the k-means training of the next section (ofdis_codebook_seed, ofdis_codebook_train) or from the caller.
+ * The route is ofdis_dense_tracks -> ofdis_track_descriptors -> ofdis_track_bof.  None of the calls
  * synchronises with the host.  of_dis_amd/tracking.py states the same definitions in numpy (normalize_descriptors_u8,
  * codebook_assign_ref, bof_ref).
  * ------------------------------------------------------------------------------------------- */
@@ -609,6 +610,85 @@ int ofdis_bof_histogram(const int* words, const int* len, const long long* info,
 int ofdis_track_bof(const uint32_t* hist, const int* len, const long long* info, int max_tracks, int nxy, int nt,
                     const uint8_t* codebook, int nwords, int min_len, uint32_t* bof, int* words /* or NULL */,
                     void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * K-means training of the bag-of-features codebook: Lloyd's algorithm on the desc rows of ofdis_descriptor_normalize, all
+ * integers, four independent clusterings in one pass (row k of a codebook holds word k of every channel).  The assignment step
+ * is ofdis_codebook_assign; the centre update is exact integer arithmetic, so a trained codebook is a pure function of its
+ * inputs: independent of the order of the slots, of any order of summation, of the kernels' mapping and of the arithmetic
+ * contract.
+ *
+ * Notation of the section above: C, D = 33*C, channel c with its offset off_c and its length n_c; desc [max_tracks][D] u8,
+ * codebook [nwords][D] u8, words [max_tracks][4] int32, info = {ntracks, dropped} on the device.  n = min(info[0], max_tracks);
+ * no call reads or writes anything of the slots >= n.
+ *
+ * Members.  Slot i < n is a member iff len == NULL or len[i] >= min_len (len [max_tracks] int32 of ofdis_dense_tracks);
+ * min_len >= 1 is checked either way, and min_len = lmax + 1 trains on complete tracks, the population ofdis_bof_histogram
+ * counts.
+ *
+ * Seeding (ofdis_codebook_seed).  For word k, s_k = floor((2k+1)*n / (2*nwords)).  Row k of codebook is the whole desc row, all
+ * four channels, of the first member at or after s_k, cyclically: of slot (s_k + t) mod n for the smallest t >= 0 that makes it
+ * a member.  With no member, which includes n == 0, every row is all zero.  With len == NULL and n >= nwords the rows come from
+ * nwords distinct, evenly spread slots.  Repeated rows are harmless: by the tie rule of the assignment a later copy is never
+ * used, and it stays an empty word.
+ *
+ * Update (ofdis_codebook_update).  For each channel c and word k, with M = {members i : words[i][c] == k}:
+ *   counts[c][k] = |M|                                                      counts [4][nwords] u32
+ *   |M| > 0:  codebook[k][off_c + e] = floor((2*S_e + |M|) / (2*|M|)),  S_e = sum over M of desc[i][off_c + e]
+ *             -- the mean rounded half up; S_e <= 2^24 * 255 < 2^32, and the result is <= 255 by construction
+ *   |M| == 0: the word keeps its bytes.
+ * A words entry outside 0 .. nwords-1 (an array the caller filled) belongs to no word.  The call writes every entry of counts
+ * itself and relies on no memset.
+ *
+ * Training (ofdis_codebook_train).  codebook is in/out: any uint8 array, from ofdis_codebook_seed or of the caller's own seeding
+ * (k-means++, say).  For t = 0 .. iters-1:
+ *   words, dist := ofdis_codebook_assign(desc, codebook): every slot < n is written, members or not, exactly as that call would
+ *   stats[t][c][0] := the number of members whose words[i][c] differs from iteration t-1; at t = 0 the number of members
+ *   stats[t][c][1] := the sum over the members of dist[i][c], in int64 (< 2^55)
+ *   codebook, counts := the update above
+ * stats = [iters][4][2] int64 on the device, or NULL.  On return words and counts belong to the last assignment, taken against
+ * the codebook before the last update; codebook is the result of the last update -- a caller who wants the words of the
+ * returned codebook calls ofdis_codebook_assign.  iters: 1 .. OFDIS_KMEANS_MAX_ITERS.
+ *
+ * Consequences.
+ *   Monotone: per channel, stats[t+1][c][1] <= stats[t][c][1].  The nearest integer to a mean minimises a sum of squares over
+ *     the integers, the previous centre was an integer, an empty word does not move, and the assignment cannot increase any
+ *     member's distance.
+ *   Fixed point: once stats[t][c][0] == 0, the channel's words, counts and codebook bytes stay the same in every later
+ *     iteration.
+ *   Order: the update depends neither on the order of the slots nor on any order of summation (integer sums).
+ *   Route: ofdis_codebook_train with iters = T is bit-identical to T rounds of ofdis_codebook_assign + ofdis_codebook_update.
+ *   Contract independence: integers only; one unit, compiled once, serves both contracts.
+ *   Known values: members {0, 1} give 1; members {0, 0, 1} give 0; members {254, 255} give 255; nwords = 1 gives the rounded
+ *     mean of the members after one iteration.
+ * Not provided: re-seeding of empty words (counts shows them); k-means++ seeding; subsampling (train on a desc array the caller
+ * thinned); an early exit (all iters are enqueued); Fisher vectors and the shape channel, as before.  None of the calls
+ * synchronises with the host.  of_dis_amd/tracking.py states the same definitions in numpy (codebook_seed_ref,
+ * codebook_update_ref, codebook_train_ref).
+ * ------------------------------------------------------------------------------------------- */
+#define OFDIS_KMEANS_MAX_ITERS 1000
+/* Bytes of the work buffer of ofdis_codebook_update and ofdis_codebook_train; 0 for rejected sizes.  With M = max_tracks and
+ * K = nwords it holds, in this order: the previous words and dist of the assignment, int32 [M][4] each (training with stats);
+ * every member's rank inside its word, u32 [M][4]; the offsets of the words' segments, u32 [4][K+1]; the slots ordered by word,
+ * u32 [4][M]; and two rows of partial sums per 256 ordered slots and channel, u32 [4][ceil(M/256)][2][RL], RL = the entries of
+ * the longest channel padded to the lanes that sum them (16 .. 1280).  About 64 + RL/8 bytes per slot. */
+size_t ofdis_codebook_train_work_bytes(int max_tracks, int nxy, int nt, int nwords);
+/* One launch, one wavefront per word: len is walked 64 slots per step.  OFDIS_ERR_INVALID before any device work (this and the
+ * two calls below): a NULL required pointer (all but len and stats); max_tracks outside 1 .. OFDIS_DT_MAX_TRACKS; nxy outside
+ * 1 .. 4; nt outside 1 .. 8; nwords outside 1 .. OFDIS_BOF_MAX_WORDS; min_len < 1; iters outside its range; a work buffer that
+ * is NULL, smaller than ofdis_codebook_train_work_bytes or not 8-byte aligned. */
+int ofdis_codebook_seed(const uint8_t* desc, const int* len /* or NULL */, const long long* info, int max_tracks, int nxy, int nt,
+                        int nwords, int min_len, uint8_t* codebook, void* stream);
+/* Six launches: bucket, then sum.  The members are counted per word (integer atomics whose arrival order reaches no result),
+ * the counts scanned, the slots scattered into their word's segment, the rows of every segment summed in registers (desc is
+ * read once) and divided; a segment longer than 256 members is summed in parts, by a last launch. */
+int ofdis_codebook_update(const uint8_t* desc, const int* words, const int* len /* or NULL */, const long long* info,
+                          int max_tracks, int nxy, int nt, int nwords, int min_len, uint8_t* codebook, uint32_t* counts,
+                          void* work, size_t work_bytes, void* stream);
+/* iters x (the assignment kernel + the six launches above), enqueued at once. */
+int ofdis_codebook_train(const uint8_t* desc, const int* len /* or NULL */, const long long* info, int max_tracks, int nxy, int nt,
+                         int nwords, int min_len, int iters, uint8_t* codebook, int* words, uint32_t* counts,
+                         long long* stats /* or NULL */, void* work, size_t work_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Motion-compensated temporal filtering of a clip: every frame averaged with its two neighbours warped onto it by the flow

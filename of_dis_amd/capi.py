@@ -46,6 +46,7 @@ ABI_SYMBOLS = [
     "ofdis_batch_dense_tracks",
     "ofdis_track_descriptor_dims", "ofdis_track_descriptors",
     "ofdis_descriptor_normalize", "ofdis_codebook_assign", "ofdis_bof_histogram", "ofdis_track_bof",
+    "ofdis_codebook_train_work_bytes", "ofdis_codebook_seed", "ofdis_codebook_update", "ofdis_codebook_train",
     "ofdis_temporal_filter", "ofdis_batch_temporal_filter",
     "ofdis_trajectory_filter", "ofdis_batch_trajectory_filter",
     "ofdis_global_motion_work_bytes", "ofdis_global_motion", "ofdis_motion_compensate", "ofdis_batch_global_motion",
@@ -65,6 +66,7 @@ TRACK_MAX_POINTS = 1 << 24  # OFDIS_TRACK_MAX_POINTS
 DT_MAX_TRACKS, DT_MAX_STRIDE, DT_MAX_WINDOW = 1 << 24, 64, 7  # OFDIS_DT_MAX_*
 DESC_MAX_PATCH = 64  # OFDIS_DESC_MAX_PATCH
 BOF_SCALE, BOF_MAX_WORDS = 510, 16384  # OFDIS_BOF_*
+KMEANS_MAX_ITERS = 1000  # OFDIS_KMEANS_MAX_ITERS
 TRAJ_MAX_RADIUS = 8  # OFDIS_TRAJ_MAX_RADIUS
 GM_MAX_SIDE, GM_MAX_FLOW, GM_MAX_ROUNDS = 8192, 4096.0, 8  # OFDIS_GM_MAX_*
 GM_TRANSLATION_ONLY, GM_AFFINE = 0, 1  # OFDIS_GM_* model
@@ -231,6 +233,12 @@ def lib():
         L.ofdis_codebook_assign.argtypes = [VP, VP, C.c_int, C.c_int, C.c_int, VP, C.c_int, VP, VP, VP]
         L.ofdis_bof_histogram.argtypes = [VP, VP, VP, C.c_int, C.c_int, C.c_int, VP, VP]
         L.ofdis_track_bof.argtypes = [VP, VP, VP, C.c_int, C.c_int, C.c_int, VP, C.c_int, C.c_int, VP, VP, VP]
+        L.ofdis_codebook_train_work_bytes.restype = C.c_size_t
+        L.ofdis_codebook_train_work_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+        L.ofdis_codebook_seed.argtypes = [VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP]
+        L.ofdis_codebook_update.argtypes = [VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP, C.c_size_t, VP]
+        L.ofdis_codebook_train.argtypes = [VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP, VP,
+                                           C.c_size_t, VP]
         L.ofdis_temporal_filter.argtypes = [VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                             VP]
         L.ofdis_batch_temporal_filter.argtypes = [VP, VP, C.c_int, C.c_int, VP, VP, C.c_int, C.c_int, C.c_float, C.c_float,
@@ -810,6 +818,80 @@ def track_bof(hist, length, codebook, nxy, nt, min_len=1, words=False):
     check(lib().ofdis_sync(None))
     bof = db.get((4, len(codebook)), np.uint32)
     return (bof, dw.get((slots, 4), np.int32)[:n].copy()) if words else bof
+
+
+def codebook_train_work_bytes(max_tracks, nxy, nt, nwords):
+    """ofdis_codebook_train_work_bytes: the work buffer of codebook_update / codebook_train_dev; 0 for rejected sizes."""
+    return int(lib().ofdis_codebook_train_work_bytes(max_tracks, nxy, nt, nwords))
+
+
+def _kmeans_len(length, n):
+    """length [ntracks] or None -> a Dev of it, or None: every track is a member"""
+    if length is None:
+        return None
+    length = np.ascontiguousarray(length, np.int32)
+    assert length.shape == (n,), (length.shape, n)
+    return Dev(length if n else np.zeros(1, np.int32))
+
+
+def codebook_seed(desc, nxy, nt, nwords, length=None, min_len=1):
+    """ofdis_codebook_seed on host arrays: desc uint8 [ntracks, D], length int32 [ntracks] or None -> codebook uint8 [nwords, D],
+    row k the descriptor of the first track of at least min_len points at or after slot floor((2 k + 1) ntracks / (2 nwords)),
+    cyclically; all zero without such a track.  of_dis_amd/tracking.py: codebook_seed_ref."""
+    D = 33 * nxy * nxy * nt
+    desc, n, slots, dd = _bof_inputs(desc, D, np.uint8)
+    dl, di, dc = _kmeans_len(length, n), Dev(np.array([n, 0], np.int64)), Dev(nbytes=nwords * D)
+    check(lib().ofdis_codebook_seed(dd.ptr, dl.ptr if dl else None, di.ptr, slots, nxy, nt, nwords, min_len, dc.ptr, None))
+    check(lib().ofdis_sync(None))
+    return dc.get((nwords, D), np.uint8)
+
+
+def codebook_update(desc, words, codebook, nxy, nt, length=None, min_len=1):
+    """ofdis_codebook_update on host arrays: desc uint8 [ntracks, D], words int32 [ntracks, 4], codebook uint8 [nwords, D] ->
+    (codebook, counts uint32 [4, nwords]): per channel every word with members becomes their mean, rounded half up; a word
+    without members keeps its bytes.  of_dis_amd/tracking.py: codebook_update_ref."""
+    D = 33 * nxy * nxy * nt
+    desc, n, slots, dd = _bof_inputs(desc, D, np.uint8)
+    codebook = _bof_codebook(codebook, D)
+    words = np.ascontiguousarray(words, np.int32)
+    assert words.shape == (n, 4), (words.shape, n)
+    dw, dl, di = Dev(words if n else np.zeros((1, 4), np.int32)), _kmeans_len(length, n), Dev(np.array([n, 0], np.int64))
+    nwords = len(codebook)
+    dc, dn = Dev(codebook), Dev(nbytes=16 * nwords)
+    work = Dev(nbytes=codebook_train_work_bytes(slots, nxy, nt, nwords))
+    check(lib().ofdis_codebook_update(dd.ptr, dw.ptr, dl.ptr if dl else None, di.ptr, slots, nxy, nt, nwords, min_len, dc.ptr, dn.ptr,
+                                      work.ptr, work.nbytes, None))
+    check(lib().ofdis_sync(None))
+    return dc.get((nwords, D), np.uint8), dn.get((4, nwords), np.uint32)
+
+
+def codebook_train_dev(desc_ptr, len_ptr, info_ptr, max_tracks, nxy, nt, nwords, min_len, iters, codebook_ptr, words_ptr, counts_ptr,
+                       stats_ptr, work_ptr, work_bytes, stream=None):
+    """ofdis_codebook_train on device pointers: desc [max_tracks][D] uint8 as ofdis_descriptor_normalize wrote it, len (or None)
+    and info as ofdis_dense_tracks did, codebook [nwords][D] uint8 in/out -> words [max_tracks][4] int32, counts [4][nwords]
+    uint32 and, where asked for, stats [iters][4][2] int64.  Enqueues iters x (assignment + update) on `stream` and returns;
+    nothing synchronises with the host."""
+    check(lib().ofdis_codebook_train(desc_ptr, len_ptr, info_ptr, max_tracks, nxy, nt, nwords, min_len, iters, codebook_ptr,
+                                     words_ptr, counts_ptr, stats_ptr, work_ptr, work_bytes, stream))
+
+
+def codebook_train(desc, codebook, nxy, nt, iters, length=None, min_len=1):
+    """ofdis_codebook_train on host arrays: desc uint8 [ntracks, D], codebook uint8 [nwords, D] (codebook_seed, or any seeding
+    of the caller's) -> (codebook, words int32 [ntracks, 4], counts uint32 [4, nwords], stats int64 [iters, 4, 2]) after iters
+    rounds of Lloyd's algorithm; stats[t][c] = (the members whose word changed, the sum of their squared distances).  words and
+    counts belong to the last assignment, taken before the last update.  of_dis_amd/tracking.py: codebook_train_ref."""
+    D = 33 * nxy * nxy * nt
+    desc, n, slots, dd = _bof_inputs(desc, D, np.uint8)
+    codebook = _bof_codebook(codebook, D)
+    nwords = len(codebook)
+    dl, di, dc = _kmeans_len(length, n), Dev(np.array([n, 0], np.int64)), Dev(codebook)
+    dw, dn, ds = Dev(nbytes=slots * 16), Dev(nbytes=16 * nwords), Dev(nbytes=iters * 64)
+    work = Dev(nbytes=codebook_train_work_bytes(slots, nxy, nt, nwords))
+    codebook_train_dev(dd.ptr, dl.ptr if dl else None, di.ptr, slots, nxy, nt, nwords, min_len, iters, dc.ptr, dw.ptr, dn.ptr, ds.ptr,
+                       work.ptr, work.nbytes)
+    check(lib().ofdis_sync(None))
+    return (dc.get((nwords, D), np.uint8), dw.get((slots, 4), np.int32)[:n].copy(), dn.get((4, nwords), np.uint32),
+            ds.get((iters, 4, 2), np.int64))
 
 
 def temporal_filter(frames, flow_fw, flow_rev, mask_fw=None, mask_rev=None, wn=1.0, tau=np.inf, support=True):

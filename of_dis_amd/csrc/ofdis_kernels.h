@@ -277,6 +277,18 @@ hipError_t launch_bof_histogram(const int* words, const int* len, const long lon
                                 uint32_t* bof, hipStream_t s);
 hipError_t launch_track_bof(const uint32_t* hist, const int* len, const long long* info, int max_tracks, int nxy, int nt,
                             const uint8_t* codebook, int nwords, int min_len, uint32_t* bof, int* words, hipStream_t s);
+// k-means training of that codebook (include/ofdis.h: ofdis_codebook_seed ... ofdis_codebook_train; ofdis_kmeans.hip): the seed
+// rows; one centre update (six launches: clear, count, scan, scatter, sum, finish) from words -> codebook, counts [4][nwords];
+// and iters x (launch_codebook_assign + update) with stats [iters][4][2] or null.  len may be null (every slot a member); work
+// holds codebook_train_work_bytes (the layout: ofdis_kmeans.hip), 8-byte aligned
+size_t codebook_train_work_bytes(int max_tracks, int nxy, int nt, int nwords);
+hipError_t launch_codebook_seed(const uint8_t* desc, const int* len, const long long* info, int max_tracks, int nxy, int nt, int nwords,
+                                int min_len, uint8_t* codebook, hipStream_t s);
+hipError_t launch_codebook_update(const uint8_t* desc, const int* words, const int* len, const long long* info, int max_tracks, int nxy,
+                                  int nt, int nwords, int min_len, uint8_t* codebook, uint32_t* counts, void* work, hipStream_t s);
+hipError_t launch_codebook_train(const uint8_t* desc, const int* len, const long long* info, int max_tracks, int nxy, int nt, int nwords,
+                                 int min_len, int iters, uint8_t* codebook, int* words, uint32_t* counts, long long* stats, void* work,
+                                 hipStream_t s);
 // motion-compensated temporal filter (include/ofdis.h: ofdis_temporal_filter; ofdis_tfilter.hip).  On materialised arrays:
 // frames, out [npairs + 1][h][w][noc] u8, AoS flows [npairs][h][w][2], masks [npairs][h][w] or null, support
 // [npairs + 1][h][w] or null

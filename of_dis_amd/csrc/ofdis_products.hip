@@ -1,7 +1,7 @@
 // ofdis_products.hip -- what is made from a context's flows, and the same steps on caller-supplied arrays: the full-resolution
-// finish and its encodings, forward-backward and left-right checks, interpolation, point and dense trajectories, descriptors and
-// their bag-of-features encoding, the temporal filters, global motion and stabilisation.  Every entry point validates its arguments, joins the pass
-// (finish_begin) and launches; the checks they share are stated once, below.  Reads no environment.
+// finish and its encodings, forward-backward and left-right checks, interpolation, point and dense trajectories, descriptors,
+// their bag-of-features encoding and the training of its codebook, the temporal filters, global motion and stabilisation.
+// Every entry point validates its arguments, joins the pass (finish_begin) and launches; the checks they share are stated once, below.  Reads no environment.
 #include <cfloat>
 #include <cmath>
 
@@ -381,7 +381,7 @@ int ofdis_track_descriptors(const uint8_t* frames, const float* flow_fw, int npa
 }
 
 // ------------------------------------------------------------------------------------ bag of features (ofdis_bof.hip)
-// what the four calls share: the slots, the cells of the descriptor and, where asked for (0: not an argument), the codebook's
+// what the four calls (and the three of the codebook training below) share: the slots, the cells of the descriptor and, where asked for (0: not an argument), the codebook's
 // size and the shortest track counted
 static int bof_check(const long long* info, int max_tracks, int nxy, int nt, bool codebook, int nwords, bool counts, int min_len) {
   if (!info) return fail(OFDIS_ERR_INVALID, "info is NULL");
@@ -430,6 +430,53 @@ int ofdis_track_bof(const uint32_t* hist, const int* len, const long long* info,
   if (!bof) return fail(OFDIS_ERR_INVALID, "bof is NULL");
   if (int rc = bof_check(info, max_tracks, nxy, nt, true, nwords, true, min_len)) return rc;
   HIPCHK(launch_track_bof(hist, len, info, max_tracks, nxy, nt, codebook, nwords, min_len, bof, words, (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+// ------------------------------------------------------------------------------------ codebook training (ofdis_kmeans.hip)
+size_t ofdis_codebook_train_work_bytes(int max_tracks, int nxy, int nt, int nwords) {
+  const bool ok = max_tracks >= 1 && max_tracks <= OFDIS_DT_MAX_TRACKS && nxy >= 1 && nxy <= 4 && nt >= 1 && nt <= 8 && nwords >= 1 &&
+                  nwords <= OFDIS_BOF_MAX_WORDS;
+  return ok ? codebook_train_work_bytes(max_tracks, nxy, nt, nwords) : 0;
+}
+
+int ofdis_codebook_seed(const uint8_t* desc, const int* len, const long long* info, int max_tracks, int nxy, int nt, int nwords,
+                        int min_len, uint8_t* codebook, void* stream) {
+  if (!desc) return fail(OFDIS_ERR_INVALID, "desc is NULL");
+  if (!codebook) return fail(OFDIS_ERR_INVALID, "codebook is NULL");
+  if (int rc = bof_check(info, max_tracks, nxy, nt, true, nwords, true, min_len)) return rc;
+  HIPCHK(launch_codebook_seed(desc, len, info, max_tracks, nxy, nt, nwords, min_len, codebook, (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+int ofdis_codebook_update(const uint8_t* desc, const int* words, const int* len, const long long* info, int max_tracks, int nxy,
+                          int nt, int nwords, int min_len, uint8_t* codebook, uint32_t* counts, void* work, size_t work_bytes,
+                          void* stream) {
+  if (!desc) return fail(OFDIS_ERR_INVALID, "desc is NULL");
+  if (!words) return fail(OFDIS_ERR_INVALID, "words is NULL");
+  if (!codebook) return fail(OFDIS_ERR_INVALID, "codebook is NULL");
+  if (!counts) return fail(OFDIS_ERR_INVALID, "counts is NULL");
+  if (int rc = bof_check(info, max_tracks, nxy, nt, true, nwords, true, min_len)) return rc;
+  if (int rc = work_check(work, work_bytes, codebook_train_work_bytes(max_tracks, nxy, nt, nwords), "ofdis_codebook_train_work_bytes"))
+    return rc;
+  HIPCHK(launch_codebook_update(desc, words, len, info, max_tracks, nxy, nt, nwords, min_len, codebook, counts, work,
+                                (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+int ofdis_codebook_train(const uint8_t* desc, const int* len, const long long* info, int max_tracks, int nxy, int nt, int nwords,
+                         int min_len, int iters, uint8_t* codebook, int* words, uint32_t* counts, long long* stats, void* work,
+                         size_t work_bytes, void* stream) {
+  if (!desc) return fail(OFDIS_ERR_INVALID, "desc is NULL");
+  if (!codebook) return fail(OFDIS_ERR_INVALID, "codebook is NULL");
+  if (!words) return fail(OFDIS_ERR_INVALID, "words is NULL");
+  if (!counts) return fail(OFDIS_ERR_INVALID, "counts is NULL");
+  if (int rc = bof_check(info, max_tracks, nxy, nt, true, nwords, true, min_len)) return rc;
+  if (iters < 1 || iters > OFDIS_KMEANS_MAX_ITERS) return fail(OFDIS_ERR_INVALID, "iters outside 1..OFDIS_KMEANS_MAX_ITERS");
+  if (int rc = work_check(work, work_bytes, codebook_train_work_bytes(max_tracks, nxy, nt, nwords), "ofdis_codebook_train_work_bytes"))
+    return rc;
+  HIPCHK(launch_codebook_train(desc, len, info, max_tracks, nxy, nt, nwords, min_len, iters, codebook, words, counts, stats, work,
+                               (hipStream_t)stream));
   return OFDIS_OK;
 }
 

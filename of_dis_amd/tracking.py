@@ -6,7 +6,9 @@ advance, occupancy and seeding (`dense_tracks_ref`), and the descriptors of thos
 and trajectory shape (`track_descriptors_ref`), where their channels lie (`descriptor_layout`) and their normalisation on the
 host (`normalize_descriptors`).  Last, the bag-of-features encoding (ofdis_descriptor_normalize, ofdis_codebook_assign,
 ofdis_bof_histogram, ofdis_track_bof): 8-bit RootSIFT descriptors, nearest words and their counts, integers throughout
-(`normalize_descriptors_u8`, `codebook_assign_ref`, `bof_ref`).
+(`normalize_descriptors_u8`, `codebook_assign_ref`, `bof_ref`), and the k-means training of its codebook (ofdis_codebook_seed,
+ofdis_codebook_update, ofdis_codebook_train): evenly spread seeds and Lloyd's algorithm with integer means (`codebook_seed_ref`,
+`codebook_update_ref`, `codebook_train_ref`).
 
     from of_dis_amd import tracking
     tracks, counts = batch.track_points(tracking.grid_seeds(w, h, 5), w, h)       # [n + 1][npoints][2], [npoints]
@@ -16,6 +18,8 @@ ofdis_bof_histogram, ofdis_track_bof): 8-bit RootSIFT descriptors, nearest words
     by_frame = tracking.to_frame_major(dtracks, start, length, n)                # [n + 1][ntracks][2], the layout above
     hist, shape = capi.track_descriptors(frames, flow_fw, dtracks, start, length, 32, 2, 3, 0.4)   # [ntracks][396] u32
     desc = tracking.normalize_descriptors(hist, tracking.descriptor_layout(32, 2, 3), "rootsift")   # float64, per channel
+    desc8 = capi.descriptor_normalize(hist, 2, 3)                                 # [ntracks][396] u8
+    codebook = capi.codebook_train(desc8, capi.codebook_seed(desc8, 2, 3, 4000, length, 16), 2, 3, 10, length, 16)[0]
     bof = capi.track_bof(hist, length, codebook, 2, 3, min_len=16)                # [4][nwords] u32; codebook [nwords][396] u8
 """
 import numpy as np
@@ -483,3 +487,77 @@ def bof_ref(words, length, nwords, min_len=1):
     assert words.ndim == 2 and words.shape[1] == 4 and length.shape == (len(words),) and min_len >= 1 and nwords >= 1
     w = words[length >= min_len]
     return np.stack([np.bincount(col[(col >= 0) & (col < nwords)], minlength=nwords) for col in w.T]).astype(np.uint32)
+
+
+# ------------------------------------------------------------------ codebook training (ofdis_codebook_seed .. ofdis_codebook_train)
+KMEANS_MAX_ITERS = 1000  # include/ofdis.h: OFDIS_KMEANS_MAX_ITERS
+
+
+def _members(length, n, min_len):
+    """bool [n]: the slots that train -- all of them without a length array, else the tracks of at least min_len points"""
+    assert min_len >= 1
+    if length is None:
+        return np.ones(n, bool)
+    length = np.asarray(length)
+    assert length.shape == (n,), (length.shape, n)
+    return length >= min_len
+
+
+def codebook_seed_ref(desc, length, nwords, min_len=1):
+    """The definition of ofdis_codebook_seed in numpy: desc uint8 [ntracks][D], length [ntracks] or None -> uint8 [nwords][D]: row
+    k is the desc row of the first member at or after slot s_k = floor((2 k + 1) ntracks / (2 nwords)), cyclically; all zero
+    where there is no member."""
+    desc = np.asarray(desc)
+    assert desc.dtype == np.uint8 and desc.ndim == 2 and 1 <= nwords <= BOF_MAX_WORDS, (desc.dtype, desc.shape, nwords)
+    n = len(desc)
+    out = np.zeros((nwords, desc.shape[1]), np.uint8)
+    at = np.flatnonzero(_members(length, n, min_len))
+    if len(at):
+        for k in range(nwords):
+            s = (2 * k + 1) * n // (2 * nwords)
+            j = np.searchsorted(at, s)              # the first member >= s_k, else the first one of all
+            out[k] = desc[at[j] if j < len(at) else at[0]]
+    return out
+
+
+def codebook_update_ref(desc, layout, words, length, codebook, min_len=1):
+    """The definition of ofdis_codebook_update in numpy: desc uint8 [ntracks][D], words int [ntracks][4], length [ntracks] or
+    None, codebook uint8 [nwords][D] -> (codebook, counts uint32 [4][nwords]).  Per channel, a word with members M becomes
+    floor((2 S + |M|) / (2 |M|)) of their int64 sums S, the mean rounded half up; a word without members keeps its bytes; a
+    words entry outside 0 .. nwords - 1 belongs to no word."""
+    desc, codebook, words = np.asarray(desc), np.asarray(codebook), np.asarray(words, np.int64)
+    assert desc.dtype == codebook.dtype == np.uint8 and desc.shape[1] == codebook.shape[1] == layout["dims"], (desc.shape, codebook.shape)
+    n, nwords = len(desc), len(codebook)
+    assert words.shape == (n, 4) and 1 <= nwords <= BOF_MAX_WORDS, (words.shape, nwords)
+    member = _members(length, n, min_len)
+    out, counts = codebook.copy(), np.zeros((4, nwords), np.uint32)
+    for c, seg in enumerate(_channel_slices(layout)):
+        w = words[:, c]
+        use = member & (w >= 0) & (w < nwords)
+        cnt = np.bincount(w[use], minlength=nwords).astype(np.int64)
+        S = np.zeros((nwords, seg.stop - seg.start), np.int64)
+        np.add.at(S, w[use], desc[use, seg].astype(np.int64))
+        has = cnt > 0
+        out[has, seg] = ((2 * S[has] + cnt[has, None]) // (2 * cnt[has, None])).astype(np.uint8)
+        counts[c] = cnt
+    return out, counts
+
+
+def codebook_train_ref(desc, layout, length, codebook, iters, min_len=1):
+    """The definition of ofdis_codebook_train in numpy: iters rounds of codebook_assign_ref + codebook_update_ref from `codebook`
+    -> (codebook, words int32 [ntracks][4], counts uint32 [4][nwords], stats int64 [iters][4][2]); stats[t][c] = (the members
+    whose word differs from round t - 1, all members at t = 0; the sum of the members' squared distances).  words and counts are
+    those of the last assignment, taken against the codebook before the last update."""
+    assert 1 <= iters <= KMEANS_MAX_ITERS, iters
+    codebook = np.asarray(codebook).copy()
+    member = _members(length, len(desc), min_len)
+    stats = np.zeros((iters, 4, 2), np.int64)
+    words = counts = None
+    for t in range(iters):
+        before = words
+        words, dist = codebook_assign_ref(desc, layout, codebook)
+        changed = np.ones(words.shape, bool) if before is None else words != before
+        stats[t, :, 0] = (changed & member[:, None]).sum(0)
+        stats[t, :, 1] = dist[member].astype(np.int64).sum(0)
+        codebook, counts = codebook_update_ref(desc, layout, words, length, codebook, min_len)
+    return codebook, words, counts, stats

@@ -4,8 +4,8 @@ ofdis_codebook_assign -> ofdis_bof_histogram cost, what the fused ofdis_track_bo
 The workload of tools/descriptors_probe.py: 1024x436, operating point 2, TV on, fused arithmetic contract for the flow passes (the
 encoding is integers and independent of the contract), one GPU, 1024 pairs, tracks of stride 5, window 2, max_len 15,
 descriptors N 32, nxy 2, nt 3 (D = 396; channels of 96, 108, 96, 96 entries) on the gray clip.  The codebook: nwords = 4000 rows
-drawn from the clip's own normalised descriptors (evenly spaced slots) -- a stand-in for a trained one (training is not
-provided); the work of the assignment does not depend on the words' values.  min_len = lmax + 1 (complete tracks).  HIP events
+drawn from the clip's own normalised descriptors (evenly spaced slots) -- a stand-in for a trained one (training:
+tools/kmeans_probe.py); the work of the assignment does not depend on the words' values.  min_len = lmax + 1 (complete tracks).  HIP events
 on one non-default stream, warm-up first, the two routes timed alternately in several rounds; the median round is reported.
 Both routes must give the same bytes, and the first tracks are compared with the numpy model.
 
