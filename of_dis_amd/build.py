@@ -46,6 +46,12 @@ PER_FILE_FLAGS = {"ofdis_dis.hip": _NO_SLP, "ofdis_tv.hip": _NO_SLP, "ofdis_prep
                   "ofdis_sor.hip": _NO_SLP}
 
 
+# The product's units the TEST library links as well (testhooks_path), compiled a second time with TESTHOOK_FLAGS.
+TESTHOOK_UNITS = ["ofdis_interp.hip", "ofdis_tfilter.hip", "ofdis_trajfilter.hip", "ofdis_gmotion.hip", "ofdis_stabilize.hip",
+                  "ofdis_upsample.hip", "ofdis_stereo_lr.hip", "ofdis_pyr.hip"]
+TESTHOOK_FLAGS = ["-DOFDIS_TEST_LAUNCH_LIMITS"]
+
+
 def _hipcc():
     for c in (shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):
         if c and os.path.exists(c):
@@ -120,14 +126,16 @@ def lib_path():
 
 
 def testhooks_path():
-    """The TEST library (tests/csrc/ofdis_testhooks.hip): kernels that expose header-only helpers to the parity tests.
+    """The TEST library: kernels that expose header-only helpers to the parity tests (tests/csrc/ofdis_testhooks.hip) and the
+    product's post-processing launchers with lowered launch limits (tests/csrc/ofdis_launch_hooks.hip, TESTHOOK_UNITS).
     Built next to the product, never linked into it."""
     return os.path.join(LIBDIR, "libofdis_testhooks.so")
 
 
-def compile_units(csrc, outdir, force=False, verbose=False, extra_flags=None):
+def compile_units(csrc, outdir, force=False, verbose=False, extra_flags=None, only=None):
     """Compile every translation unit of the library (kernel files once per contract) from `csrc` into `outdir`; returns
-    the object list.  extra_flags: {file name: [flags]} on top of PER_FILE_FLAGS (developer A/B builds, tools/ab_build.py)."""
+    the object list.  extra_flags: {file name: [flags]} on top of PER_FILE_FLAGS (developer A/B builds, tools/ab_build.py).
+    only: the file names to compile instead of all of them (the test library links a few of the product's units)."""
     hipcc = _hipcc()
     headers = [os.path.join(csrc, h) for h in os.listdir(csrc) if h.endswith((".h", ".inc"))]
     headers.append(os.path.join(ROOT, "include", "ofdis.h"))
@@ -135,6 +143,8 @@ def compile_units(csrc, outdir, force=False, verbose=False, extra_flags=None):
     build_id_h = _build_id_header(csrc, outdir, extra_flags)  # changes whenever any kernel source or flag does
     objs, jobs = [], []
     units = [(src, c) for c in ("exact", "fused") for src in KERNEL_SOURCES] + [(src, "exact") for src in COMMON_SOURCES]
+    if only is not None:
+        units = [(src, c) for src, c in units if src in only]
     for src, contract in units:
         sp = os.path.join(csrc, src)
         suffix = ".o" if contract == "exact" else "." + contract + ".o"
@@ -194,10 +204,23 @@ def build(force=False, verbose=False):
                      verbose)
         hooks = os.path.join(ROOT, "tests", "csrc", "ofdis_testhooks.hip")
         if os.path.exists(hooks):
+            # the launch hooks (tests/csrc/ofdis_launch_hooks.hip) call the product's own launchers: TESTHOOK_UNITS compiled
+            # with the product's flags plus the define that turns the two launch limits into variables of this library
+            # (csrc/ofdis_kernels.h), into an object directory of their own
+            tdir = os.path.join(LIBDIR, "testhooks")
+            os.makedirs(tdir, exist_ok=True)
+            tobjs, _ = compile_units(CSRC, tdir, force, verbose, {u: TESTHOOK_FLAGS for u in TESTHOOK_UNITS}, only=TESTHOOK_UNITS)
+            launch_hooks = os.path.join(ROOT, "tests", "csrc", "ofdis_launch_hooks.hip")
+            lobj = os.path.join(tdir, "ofdis_launch_hooks.o")
+            if force or _newer(lobj, [launch_hooks] + headers):
+                _run([hipcc] + HIPFLAGS + TESTHOOK_FLAGS + ["-c", launch_hooks, "-o", lobj], verbose)
+            hobj = os.path.join(tdir, "ofdis_testhooks.o")
+            if force or _newer(hobj, [hooks] + headers):
+                _run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-c", hooks, "-o", hobj],
+                     verbose)
             tso = testhooks_path()
-            if force or _newer(tso, [hooks] + headers):
-                _run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-                      hooks, "-o", tso], verbose)
+            if force or _newer(tso, [hobj, lobj] + tobjs):
+                _run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", tso, hobj, lobj] + tobjs, verbose)
     except RuntimeError as e:
         print("of_dis_amd.build: test artefacts not built:", str(e)[:2000], file=sys.stderr)
     return so

@@ -327,7 +327,7 @@ __host__ __device__ __forceinline__ size_t sdiag_index(int frame, int x, int y, 
 // Launch ((nframes+7)/8)*8*blocks_per_frame blocks and skip frame >= nframes.
 // With fewer than 8 frames that mapping would leave whole XCDs without work (one 1080p frame on 32 of the 256 CUs:
 // measured 8x slower), so there the blocks of a frame are simply consecutive and spread over all XCDs.
-__device__ __forceinline__ void xcd_frame_map(int n, int blocks_per_frame, int nframes, int& frame, int& blk) {
+__host__ __device__ __forceinline__ void xcd_frame_map(int n, int blocks_per_frame, int nframes, int& frame, int& blk) {
   if (nframes < 8) {
     frame = n / blocks_per_frame;
     blk = n - frame * blocks_per_frame;

@@ -61,10 +61,27 @@ struct UpGeom {
   __host__ __device__ size_t plane() const { return (size_t)sw * sh; }  // pixels of one frame's level flow
 };
 
+// The two launch limits, in workgroups of 256 lanes.  QUAD_MAX_BLOCKS: one launch of a kernel in which a lane owns a quad of
+// one frame (quad_grid, ofdis_upsample.h); the launcher walks the frames in chunks that stay below it.  GRID_MAX_BLOCKS: the
+// grid of a grid-stride kernel (grid_for); the kernel loops over what is beyond it.  Both are read in host code only.  The
+// product is built with the constants; the test library (tests/csrc/ofdis_launch_hooks.hip) compiles the same units with
+// OFDIS_TEST_LAUNCH_LIMITS, where they are two host variables of that library which a test lowers to reach the second chunk
+// and the second trip at test sizes.
+constexpr long long QUAD_MAX_BLOCKS = 1ll << 22;
+constexpr long long GRID_MAX_BLOCKS = 1ll << 20;
+#ifdef OFDIS_TEST_LAUNCH_LIMITS
+extern long long test_quad_max_blocks, test_grid_max_blocks;
+inline long long quad_max_blocks() { return test_quad_max_blocks; }
+inline long long grid_max_blocks() { return test_grid_max_blocks; }
+#else
+constexpr long long quad_max_blocks() { return QUAD_MAX_BLOCKS; }
+constexpr long long grid_max_blocks() { return GRID_MAX_BLOCKS; }
+#endif
+
 // blocks of 256 threads for a grid-stride loop over `total` elements
 inline unsigned grid_for(long long total) {
   long long b = (total + 255) / 256;
-  if (b > (1 << 20)) b = 1 << 20;
+  if (b > grid_max_blocks()) b = grid_max_blocks();
   if (b < 1) b = 1;
   return (unsigned)b;
 }

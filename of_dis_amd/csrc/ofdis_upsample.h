@@ -209,16 +209,16 @@ __device__ __forceinline__ void interp_sample(const uint8_t* __restrict__ I, int
 }
 
 // The launch geometry of the kernels in which one lane owns a quad of 4 adjacent pixels of one row of one frame
-// (ofdis_interp.hip, ofdis_tfilter.hip, ofdis_trajfilter.hip).  Blocks of 256 quads per frame, and the frames of one launch: a launch covers at most
-// 2^22 blocks (2^30 lanes), a multiple of 8 frames where it can (xcd_frame_map), and the launcher walks the frames in such
-// chunks.
+// (ofdis_interp.hip, ofdis_tfilter.hip, ofdis_trajfilter.hip, ofdis_gmotion.hip, ofdis_stabilize.hip).  Blocks of 256 quads
+// per frame, and the frames of one launch: a launch covers at most QUAD_MAX_BLOCKS = 2^22 blocks (2^30 lanes; ofdis_kernels.h),
+// a multiple of 8 frames where it can (xcd_frame_map), and the launcher walks the frames in such chunks.
 struct QuadGrid {
   int bpf, chunk;
 };
 inline QuadGrid quad_grid(int nframes, int w, int h) {
   QuadGrid g;
   g.bpf = (int)(((long long)((w + 3) >> 2) * h + 255) / 256);
-  long long c = (1ll << 22) / g.bpf;
+  long long c = quad_max_blocks() / g.bpf;
   if (c >= 8) c &= ~7ll;
   g.chunk = (int)std::max(1ll, std::min(c, (long long)nframes));
   return g;

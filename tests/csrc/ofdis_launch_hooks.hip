@@ -1,0 +1,148 @@
+// ofdis_launch_hooks.hip -- TEST LIBRARY (libofdis_testhooks.so), not part of the product: thin C wrappers around the
+// ofdis::launch_* functions of of_dis_amd/csrc/ofdis_kernels.h, and the two launch limits as variables a test can lower.
+//
+// The test library links the PRODUCT'S OWN units (ofdis_interp, ofdis_tfilter, ofdis_trajfilter, ofdis_gmotion, ofdis_stabilize,
+// ofdis_upsample, ofdis_stereo_lr, ofdis_pyr), compiled with the product's flags plus -DOFDIS_TEST_LAUNCH_LIMITS.  Under that
+// define quad_max_blocks() and grid_max_blocks() (ofdis_kernels.h) read the two variables below instead of returning the
+// product's constants.  Both are read in host code only (quad_grid, grid_for), so the kernels here are the product's kernels;
+// what changes is how many launches (quad_grid's chunks) or grid-stride trips (grid_for) cover the work.  With the limits at
+// their product values the launches are the product's.
+#include <hip/hip_runtime.h>
+
+#include "../../of_dis_amd/csrc/ofdis_upsample.h"
+
+#ifndef OFDIS_TEST_LAUNCH_LIMITS
+#error "the test library is compiled with -DOFDIS_TEST_LAUNCH_LIMITS"
+#endif
+
+namespace ofdis {
+long long test_quad_max_blocks = QUAD_MAX_BLOCKS;
+long long test_grid_max_blocks = GRID_MAX_BLOCKS;
+}  // namespace ofdis
+
+using namespace ofdis;
+
+#define HOOK extern "C" __attribute__((visibility("default")))
+// UpGeom travels as seven ints, in the order of its members
+#define UPG_PARAMS int sw, int sh, int sc_l, int left, int top, int wo, int ho
+#define UPG (UpGeom{sw, sh, sc_l, left, top, wo, ho})
+
+static InterpTimes interp_times(const float* times, int ntimes) {
+  InterpTimes ts{};
+  for (int k = 0; k < ntimes && k < 16; ++k) ts.t[k] = times[k];
+  ts.n = ntimes;
+  return ts;
+}
+static TrajWeights traj_weights(const float* weights, int radius) {
+  TrajWeights tw{};
+  for (int k = 0; k < radius && k < 8; ++k) tw.w[k] = weights[k];
+  tw.radius = radius;
+  return tw;
+}
+
+// ------------------------------------------------------------------------------------ the limits and the host-only geometry
+// 0 = the product's value
+HOOK void ofdis_test_set_launch_limits(long long quad_max_blocks, long long grid_max_blocks) {
+  test_quad_max_blocks = quad_max_blocks > 0 ? quad_max_blocks : QUAD_MAX_BLOCKS;
+  test_grid_max_blocks = grid_max_blocks > 0 ? grid_max_blocks : GRID_MAX_BLOCKS;
+}
+// host only, needs no GPU: quad_grid, quad_blocks, grid_for and xcd_frame_map for workgroups [n0, n0 + count)
+HOOK void ofdis_test_quad_grid(int nframes, int w, int h, int* bpf, int* chunk) {
+  const QuadGrid g = quad_grid(nframes, w, h);
+  *bpf = g.bpf;
+  *chunk = g.chunk;
+}
+HOOK unsigned ofdis_test_quad_blocks(int frames, int bpf) { return quad_blocks(frames, bpf); }
+HOOK unsigned ofdis_test_grid_for(long long total) { return grid_for(total); }
+HOOK void ofdis_test_xcd_frame_map(int n0, int count, int blocks_per_frame, int nframes, int* frame, int* blk) {
+  for (int i = 0; i < count; ++i) xcd_frame_map(n0 + i, blocks_per_frame, nframes, frame[i], blk[i]);
+}
+HOOK size_t ofdis_test_gmotion_work_bytes(int npairs, int w, int h) { return gmotion_work_bytes(npairs, w, h); }
+
+// ------------------------------------------------------------------------------------ launchers that walk quad_grid's chunks
+HOOK int ofdis_test_launch_interp_frames(const uint8_t* img_a, const uint8_t* img_b, const float* flow_fw, const float* flow_rev,
+                                         const uint8_t* mask_fw, const uint8_t* mask_rev, uint8_t* out, int nframes, int w, int h,
+                                         int noc, const float* times, int ntimes, void* stream) {
+  return (int)launch_interp_frames(img_a, img_b, flow_fw, flow_rev, mask_fw, mask_rev, out, nframes, w, h, noc,
+                                   interp_times(times, ntimes), (hipStream_t)stream);
+}
+HOOK int ofdis_test_launch_interp_bidir(const uint8_t* img_a, const uint8_t* img_b, const float* fw, const float* rev, uint8_t* out,
+                                        int nframes, UPG_PARAMS, int noc, const float* times, int ntimes, float alpha, float beta,
+                                        void* stream) {
+  return (int)launch_interp_bidir(img_a, img_b, fw, rev, out, nframes, UPG, noc, interp_times(times, ntimes), alpha, beta,
+                                  (hipStream_t)stream);
+}
+HOOK int ofdis_test_launch_tfilter_frames(const uint8_t* frames, const float* flow_fw, const float* flow_rev, const uint8_t* mask_fw,
+                                          const uint8_t* mask_rev, uint8_t* out, uint8_t* support, int npairs, int w, int h, int noc,
+                                          float wn, float tau, void* stream) {
+  return (int)launch_tfilter_frames(frames, flow_fw, flow_rev, mask_fw, mask_rev, out, support, npairs, w, h, noc, wn, tau,
+                                    (hipStream_t)stream);
+}
+HOOK int ofdis_test_launch_tfilter_level(const uint8_t* frames, const float* fw, const float* rev, uint8_t* out, uint8_t* support,
+                                         int npairs, UPG_PARAMS, int noc, float wn, float tau, float alpha, float beta,
+                                         void* stream) {
+  return (int)launch_tfilter_level(frames, fw, rev, out, support, npairs, UPG, noc, wn, tau, alpha, beta, (hipStream_t)stream);
+}
+HOOK int ofdis_test_launch_trajfilter_frames(const uint8_t* frames, const float* flow_fw, const float* flow_rev, uint8_t* out,
+                                             uint8_t* support, int npairs, int w, int h, int noc, const float* weights, int radius,
+                                             float tau, int fb, float alpha, float beta, void* stream) {
+  return (int)launch_trajfilter_frames(frames, flow_fw, flow_rev, out, support, npairs, w, h, noc, traj_weights(weights, radius),
+                                       tau, fb != 0, alpha, beta, (hipStream_t)stream);
+}
+HOOK int ofdis_test_launch_trajfilter_level(const uint8_t* frames, const float* fw, const float* rev, uint8_t* out,
+                                            uint8_t* support, int npairs, UPG_PARAMS, int noc, const float* weights, int radius,
+                                            float tau, int fb, float alpha, float beta, void* stream) {
+  return (int)launch_trajfilter_level(frames, fw, rev, out, support, npairs, UPG, noc, traj_weights(weights, radius), tau, fb != 0,
+                                      alpha, beta, (hipStream_t)stream);
+}
+HOOK int ofdis_test_launch_gmotion_frames(const float* flow, const uint8_t* mask, int npairs, int w, int h, int model, int rounds,
+                                          float thresh, double* models, long long* stats, void* work, void* stream) {
+  return (int)launch_gmotion_frames(flow, mask, npairs, w, h, model, rounds, thresh, models, stats, work, (hipStream_t)stream);
+}
+HOOK int ofdis_test_launch_gmotion_compensate_frames(const float* flow, const uint8_t* mask, const double* models, int npairs, int w,
+                                                     int h, float thresh, float* residual, uint8_t* label, void* stream) {
+  return (int)launch_gmotion_compensate_frames(flow, mask, models, npairs, w, h, thresh, residual, label, (hipStream_t)stream);
+}
+HOOK int ofdis_test_launch_gmotion_level(const float* fw, const float* rev, int npairs, UPG_PARAMS, int model, int rounds,
+                                         float thresh, float alpha, float beta, double* models, long long* stats, void* work,
+                                         void* stream) {
+  return (int)launch_gmotion_level(fw, rev, npairs, UPG, model, rounds, thresh, alpha, beta, models, stats, work,
+                                   (hipStream_t)stream);
+}
+HOOK int ofdis_test_launch_gmotion_compensate_level(const float* fw, const float* rev, const double* models, int npairs, UPG_PARAMS,
+                                                    float thresh, float alpha, float beta, float* residual, uint8_t* label,
+                                                    void* stream) {
+  return (int)launch_gmotion_compensate_level(fw, rev, models, npairs, UPG, thresh, alpha, beta, residual, label,
+                                              (hipStream_t)stream);
+}
+HOOK int ofdis_test_launch_warp_frames(const uint8_t* frames, const double* warps, uint8_t* out, uint8_t* inside, int nframes, int w,
+                                       int h, int noc, int replicate, void* stream) {
+  return (int)launch_warp_frames(frames, warps, out, inside, nframes, w, h, noc, replicate != 0, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------ launchers behind grid_for
+HOOK int ofdis_test_launch_pyr_base(const uint8_t* src, float* dst, int nframes, int wo, int ho, int W, int H, int noc, int l,
+                                    size_t pitch, size_t stride, void* stream) {
+  return (int)launch_pyr_base(src, dst, nframes, wo, ho, W, H, noc, l, pitch, stride, (hipStream_t)stream);
+}
+HOOK int ofdis_test_launch_pyr_down(const float* src, float* dst, int nframes, int w, int h, int noc, void* stream) {
+  return (int)launch_pyr_down(src, dst, nframes, w, h, noc, (hipStream_t)stream);
+}
+HOOK int ofdis_test_launch_encode(const float* src, void* dst, size_t n, int type, float scale, float offset, void* stream) {
+  return (int)launch_encode(src, dst, n, type, scale, offset, (hipStream_t)stream);
+}
+HOOK int ofdis_test_launch_fb_check(const float* flow, const float* other, uint8_t* mask, int nframes, int w, int h, float alpha,
+                                    float beta, void* stream) {
+  return (int)launch_fb_check(flow, other, mask, nframes, w, h, alpha, beta, (hipStream_t)stream);
+}
+HOOK int ofdis_test_launch_mirror_u8(const uint8_t* src, uint8_t* dst, int nframes, int w, int h, int noc, void* stream) {
+  return (int)launch_mirror_u8(src, dst, nframes, w, h, noc, (hipStream_t)stream);
+}
+HOOK int ofdis_test_launch_lr_check(const float* disp, const float* other, uint8_t* mask, int nframes, int w, int h, float alpha,
+                                    float beta, void* stream) {
+  return (int)launch_lr_check(disp, other, mask, nframes, w, h, alpha, beta, (hipStream_t)stream);
+}
+HOOK int ofdis_test_launch_disparity_fill(const float* disp, const uint8_t* mask, float* out, int nframes, int w, int h, int mode,
+                                          void* stream) {
+  return (int)launch_disparity_fill(disp, mask, out, nframes, w, h, mode, (hipStream_t)stream);
+}

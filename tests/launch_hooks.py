@@ -1,0 +1,108 @@
+"""The launch hooks of the TEST library (tests/csrc/ofdis_launch_hooks.hip): the product's own launchers behind thin C wrappers, and
+the two launch limits of of_dis_amd/csrc/ofdis_kernels.h -- QUAD_MAX_BLOCKS (workgroups of one launch of a quad kernel: the
+launcher walks the frames in chunks) and GRID_MAX_BLOCKS (grid of a grid-stride kernel: the kernel loops) -- as variables of
+that library which a test lowers.  Shared by tests/test_launch_geometry.py (CPU) and tests/test_gpu_launch_limits.py.
+
+libofdis_hip.so is a separate object with the limits compiled in as constants: nothing here changes what it does."""
+import contextlib
+import ctypes as C
+import functools
+
+import numpy as np
+
+QUAD_MAX_BLOCKS, GRID_MAX_BLOCKS = 1 << 22, 1 << 20   # the product's values
+_I, _F, _VP, _LL, _SZ = C.c_int, C.c_float, C.c_void_p, C.c_longlong, C.c_size_t
+_UPG = [_I] * 7   # UpGeom: sw, sh, sc_l, left, top, wo, ho
+
+_SIGNATURES = {
+    "interp_frames": [_VP] * 7 + [_I] * 4 + [_VP, _I, _VP],
+    "interp_bidir": [_VP] * 5 + [_I] + _UPG + [_I, _VP, _I, _F, _F, _VP],
+    "tfilter_frames": [_VP] * 7 + [_I] * 4 + [_F, _F, _VP],
+    "tfilter_level": [_VP] * 5 + [_I] + _UPG + [_I, _F, _F, _F, _F, _VP],
+    "trajfilter_frames": [_VP] * 5 + [_I] * 4 + [_VP, _I, _F, _I, _F, _F, _VP],
+    "trajfilter_level": [_VP] * 5 + [_I] + _UPG + [_I, _VP, _I, _F, _I, _F, _F, _VP],
+    "gmotion_frames": [_VP, _VP] + [_I] * 5 + [_F, _VP, _VP, _VP, _VP],
+    "gmotion_compensate_frames": [_VP] * 3 + [_I] * 3 + [_F, _VP, _VP, _VP],
+    "gmotion_level": [_VP, _VP, _I] + _UPG + [_I, _I, _F, _F, _F, _VP, _VP, _VP, _VP],
+    "gmotion_compensate_level": [_VP] * 3 + [_I] + _UPG + [_F, _F, _F, _VP, _VP, _VP],
+    "warp_frames": [_VP] * 4 + [_I] * 5 + [_VP],
+    "pyr_base": [_VP, _VP] + [_I] * 7 + [_SZ, _SZ, _VP],
+    "pyr_down": [_VP, _VP] + [_I] * 4 + [_VP],
+    "encode": [_VP, _VP, _SZ, _I, _F, _F, _VP],
+    "fb_check": [_VP] * 3 + [_I] * 3 + [_F, _F, _VP],
+    "mirror_u8": [_VP, _VP] + [_I] * 4 + [_VP],
+    "lr_check": [_VP] * 3 + [_I] * 3 + [_F, _F, _VP],
+    "disparity_fill": [_VP] * 3 + [_I] * 4 + [_VP],
+}
+
+
+@functools.lru_cache(maxsize=None)
+def hooks():
+    """libofdis_testhooks.so with the launch hooks' signatures.  No fallback: a library without them is a failure."""
+    from common import testhooks
+    L = testhooks()
+    for name, argtypes in _SIGNATURES.items():
+        fn = getattr(L, "ofdis_test_launch_" + name)
+        fn.argtypes, fn.restype = argtypes, _I
+    L.ofdis_test_set_launch_limits.argtypes, L.ofdis_test_set_launch_limits.restype = [_LL, _LL], None
+    L.ofdis_test_quad_grid.argtypes, L.ofdis_test_quad_grid.restype = [_I, _I, _I, C.POINTER(_I), C.POINTER(_I)], None
+    L.ofdis_test_quad_blocks.argtypes, L.ofdis_test_quad_blocks.restype = [_I, _I], C.c_uint
+    L.ofdis_test_grid_for.argtypes, L.ofdis_test_grid_for.restype = [_LL], C.c_uint
+    L.ofdis_test_xcd_frame_map.argtypes, L.ofdis_test_xcd_frame_map.restype = [_I, _I, _I, _I, _VP, _VP], None
+    L.ofdis_test_gmotion_work_bytes.argtypes, L.ofdis_test_gmotion_work_bytes.restype = [_I, _I, _I], _SZ
+    return L
+
+
+def launch(name, *args):
+    """ofdis_test_launch_<name>(*args) on the null stream; a hipError_t other than hipSuccess is a failure"""
+    rc = getattr(hooks(), "ofdis_test_launch_" + name)(*args, None)
+    assert rc == 0, f"ofdis_test_launch_{name}: hipError_t {rc}"
+
+
+@contextlib.contextmanager
+def launch_limits(quad_max_blocks=0, grid_max_blocks=0):
+    """the test library's limits lowered (0: the product's value), and back at the product's values afterwards whatever happens"""
+    L = hooks()
+    L.ofdis_test_set_launch_limits(quad_max_blocks, grid_max_blocks)
+    try:
+        yield
+    finally:
+        L.ofdis_test_set_launch_limits(0, 0)
+
+
+def quad_grid(nframes, w, h):
+    """(bpf, chunk) of quad_grid(nframes, w, h) under the limits in force"""
+    bpf, chunk = _I(), _I()
+    hooks().ofdis_test_quad_grid(nframes, w, h, C.byref(bpf), C.byref(chunk))
+    return bpf.value, chunk.value
+
+
+def quad_blocks(frames, bpf):
+    return int(hooks().ofdis_test_quad_blocks(frames, bpf))
+
+
+def grid_for(total):
+    return int(hooks().ofdis_test_grid_for(total))
+
+
+def xcd_frame_map(nblocks, bpf, nframes):
+    """(frame, blk) of workgroups 0 .. nblocks-1 of a launch over nframes frames, as xcd_frame_map gives them to the kernels"""
+    frame, blk = np.empty(nblocks, np.int32), np.empty(nblocks, np.int32)
+    hooks().ofdis_test_xcd_frame_map(0, nblocks, bpf, nframes, frame.ctypes.data, blk.ctypes.data)
+    return frame, blk
+
+
+def chunk_walk(nframes, w, h):
+    """the launches of one call as the launchers make them: [(f0, n, workgroups)] with f0 += chunk, n = min(chunk, nframes - f0)"""
+    bpf, chunk = quad_grid(nframes, w, h)
+    walk, f0 = [], 0
+    while f0 < nframes:
+        n = min(chunk, nframes - f0)
+        walk.append((f0, n, quad_blocks(n, bpf)))
+        f0 += chunk
+    return bpf, walk
+
+
+def trips(total):
+    """grid-stride trips of the busiest thread over `total` elements under the limits in force"""
+    return -(-total // (256 * grid_for(total)))
