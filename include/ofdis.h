@@ -39,7 +39,8 @@ extern "C" {
  * without a bump), ofdis_batch_status and ofdis_batch_upsample_frames were added.  3 (round 6): streams, pinned host memory
  * asynchronous copies and events (ofdis_stream_create, ofdis_host_alloc, ofdis_memcpy_h2d_async / _d2h_async,
  * ofdis_event_*), ofdis_build_id; ofdis_tuning grew to
- * 20 ints (fused_xcu_drop, prep_densify, fused_tall_group, fused_rgb_min) and fused_xcu_spin became a time in microseconds.  A caller checks ofdis_version() ==
+ * 20 ints (fused_xcu_drop, prep_densify, fused_tall_group, fused_rgb_min) and fused_xcu_spin became a time in microseconds
+ * (round 8 appended patch_window_reuse, 21 ints, without a bump: a caller compiled against the 20-int struct must be rebuilt).  A caller checks ofdis_version() ==
  * OFDIS_VERSION before passing structs (of_dis_amd/capi.py does at load). */
 #define OFDIS_VERSION 3
 
@@ -1156,6 +1157,10 @@ typedef struct ofdis_tuning {
                        * mode's levels of <= 64 rows take their fused kernel (de_fused_kernel) by the same knob; its own
                        * defaults: always under the fused contract, from 256 frames under the exact one
                        *                                                                            OFDIS_FUSED_RGB_MIN */
+  int patch_window_reuse; /* 1: the gray 8x8 patch kernel keeps the 9 x 3 tap window of an evaluation in registers and loads it
+                       * again only when its integer position has moved (a converged search fetches the same bytes in every
+                       * evaluation); 0: nine loads per lane in every evaluation.  Same values either way
+                       *                                                            OFDIS_NO_PATCH_WINDOW_REUSE -> 0 */
 } ofdis_tuning;
 int ofdis_get_tuning(ofdis_tuning* out);
 int ofdis_set_tuning(const ofdis_tuning* in);

@@ -74,7 +74,7 @@ GM_OK_AFFINE, GM_TRANSLATION, GM_EMPTY = 0, 1, 2  # OFDIS_GM_* status
 GM_INLIER, GM_OUTLIER, GM_INVALID = 0, 1, 2  # OFDIS_GM_* label
 STAB_MAX_RADIUS, STAB_MIN_DET, STAB_MAX_DET, STAB_MAX_ZOOM = 64, 0.25, 4.0, 16.0  # OFDIS_STAB_*
 BORDER_CONSTANT, BORDER_REPLICATE = 0, 1  # OFDIS_BORDER_*
-OFDIS_VERSION = 3  # include/ofdis.h: the struct layouts below (OfdisTuning: 20 ints) belong to this ABI version
+OFDIS_VERSION = 3  # include/ofdis.h: the struct layouts below (OfdisTuning: 21 ints) belong to this ABI version
 
 
 class OfdisTuning(C.Structure):
@@ -82,7 +82,8 @@ class OfdisTuning(C.Structure):
     (0 = exact arithmetic, 1 = the FMA / fast-reciprocal tolerance contract)."""
     _fields_ = [(n, C.c_int) for n in ("gray8", "rgb12", "rgb12_lpp", "fused_tv", "fused_mw_max", "fused_split",
                                        "finish_fusion", "fused_strip", "prep_band_rows", "graph", "flow_dma", "flow_whole",
-                                       "fused_xcu_max", "fused_tp_pipe", "fused_xcu_spin", "contract", "fused_xcu_drop", "prep_densify", "fused_tall_group", "fused_rgb_min")]
+                                       "fused_xcu_max", "fused_tp_pipe", "fused_xcu_spin", "contract", "fused_xcu_drop", "prep_densify", "fused_tall_group", "fused_rgb_min",
+                                       "patch_window_reuse")]
 
 
 class Encoding(C.Structure):

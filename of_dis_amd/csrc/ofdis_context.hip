@@ -50,6 +50,7 @@ static void tuning_init_locked() {
   g_tuning.prep_densify = !on("OFDIS_NO_PREP_DENSIFY");
   g_tuning.fused_tall_group = on("OFDIS_NO_TALL_GROUP") ? 0 : std::max(1, std::min(7, num("OFDIS_TALL_GROUP", 1)));
   g_tuning.fused_rgb_min = std::max(0, num("OFDIS_FUSED_RGB_MIN", 0));
+  g_tuning.patch_window_reuse = !on("OFDIS_NO_PATCH_WINDOW_REUSE");
   {  // arithmetic contract: "fused" / "1" = the tolerance contract, anything else (or unset) = exact
     const char* e = getenv("OFDIS_CONTRACT");
     g_tuning.contract = (e && (!strcmp(e, "fused") || !strcmp(e, "1"))) ? 1 : 0;
@@ -356,6 +357,7 @@ int ofdis_set_tuning(const ofdis_tuning* in) {
   if (in->prep_densify != 0 && in->prep_densify != 1) return fail(OFDIS_ERR_INVALID, "prep_densify must be 0 or 1");
   if (in->fused_tall_group < 0 || in->fused_tall_group > 7) return fail(OFDIS_ERR_INVALID, "fused_tall_group must be 0 .. 7");
   if (in->fused_rgb_min < 0) return fail(OFDIS_ERR_INVALID, "negative knob");
+  if (in->patch_window_reuse != 0 && in->patch_window_reuse != 1) return fail(OFDIS_ERR_INVALID, "patch_window_reuse must be 0 or 1");
   ofdis::tuning();  // initialise from the environment first
   std::lock_guard<std::mutex> lock(ofdis::g_tuning_mutex);
   ofdis::g_tuning = *in;

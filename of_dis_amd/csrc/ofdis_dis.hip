@@ -365,10 +365,22 @@ __global__ __launch_bounds__(256) void patch_optimize_kernel(const DisArgs a) {
 // The four bilinear taps of row r are
 //     a = I[row r][col]   b = I[row r][col-1]   c = I[row r-1][col]   d = I[row r-1][col-1]
 // so c,d of a row are a,b of the row above, and a lane's two columns need the three image columns 2pl-1, 2pl,
-// 2pl+1: ONE 12-byte buffer load per image row, 9 per iteration.  The four lanes of a patch then touch one
+// 2pl+1: ONE 12-byte buffer load per image row, 9 per window.  The four lanes of a patch then touch one
 // 36-byte span per instruction, i.e. one cache line (two when it straddles): the kernel is bound by L1 tag
-// lookups per distinct line as much as by VALU issue, and this is the minimum (9 rows) per patch evaluation.
+// lookups per distinct line as much as by VALU issue, and 9 rows is the minimum per window.
 // The row stride is a wave-uniform SGPR offset, the per-lane byte offset is computed once per iteration.
+//
+// The window depends on the INTEGER part of the patch position only (the fraction enters through the four bilinear
+// weights), and a search that has settled to within a pixel evaluates the same window again and again: at the
+// benchmark's level 3 the window of a wavefront's 16 patches is unchanged in 94 % of the evaluations after the first
+// (profiles/README.md round 8).  Under the fused contract the 27 floats therefore stay in registers together with the
+// byte offset they were loaded at, and the wavefront loads only when that offset differs in one of its lanes
+// (ofdis_tuning::patch_window_reuse; DisArgs::reload_window restores the nine loads per evaluation).  Every evaluation
+// goes through the same comparison -- the first one (no offset is -1), the one after a reset to the start position,
+// the idle lane groups -- and the registers hold what the loads would return: same bits.  No load is in flight across the branch: every
+// evaluation consumes what it loaded.  Under the exact contract the window would take the kernel from 120 to 146
+// registers and from four wavefronts per SIMD to three (separately rounded products keep more values alive): it
+// reloads in every evaluation as before.
 // A pair is two plain floats: gfx950's SIMDs are 32 lanes wide, a packed v_pk_*_f32 occupies the issue port twice as
 // long as a scalar op, so packing buys nothing and costs the moves that build register pairs.
 struct f2 {
@@ -408,6 +420,7 @@ __device__ __forceinline__ float gray8_abs_sum(const f2 (&x)[8]) {
 template <int COST, bool STEREO>
 __global__ __launch_bounds__(256) void patch_optimize_gray8_kernel(const DisArgs a) {
   constexpr int LPP = 4, Q = 16, R = 8;
+  constexpr bool kWindowReuse = kFusedContract;  // the tap window stays in registers between evaluations (see above)
   const int costfct = COST >= 0 ? COST : a.costfct;
   const LevelGeom& g = a.g;
   const int lane = threadIdx.x & 63;
@@ -535,6 +548,10 @@ __global__ __launch_bounds__(256) void patch_optimize_gray8_kernel(const DisArgs
     const float bsq = 5.0f * 5.0f, bsq2 = bsq * 2.0f;
     return copysignf(sqrtf((sqrtf(1.0f + (d * d) / bsq) - 1.0f) * bsq2), d);
   };
+  // The tap window of the latest evaluation (9 rows x 3 columns, as loaded) and the byte offset it was loaded at: see the
+  // comment at the kernel.  No offset is -1 (they are multiples of 4), so the first evaluation loads.
+  float win[9][3];
+  int win_voff = -1;
   auto compute_err = [&](bool stop) {  // patch.cpp:264-284, 335-402, 223-262
     int pos0 = (int)ceilf(ptx + .00001f), pos1 = (int)ceilf(pty + .00001f);
     const int pos2 = (int)floorf(ptx), pos3 = (int)floorf(pty);
@@ -545,16 +562,27 @@ __global__ __launch_bounds__(256) void patch_optimize_gray8_kernel(const DisArgs
     // byte offset of (row pos1-5, column pos0-5+2pl) = the left tap of the lane's first column; rows rr = 0..8
     // follow at rr*row_bytes
     const int voff = ((pos1 - 5) * tw + pos0 - 5 + 2 * pl) * 4;
+    // wavefront-uniform: all lanes load when the window of any of them has moved (a scalar branch; skipping the loads lane by
+    // lane under a divergent branch measured the same, profiles/README.md round 8)
+    bool fetch = true;
+    if constexpr (kWindowReuse) fetch = (__builtin_amdgcn_ballot_w64(voff != win_voff) != 0) | (a.reload_window != 0);
+    if (fetch) {
+      win_voff = voff;
+#pragma unroll
+      for (int rr = 0; rr < 9; ++rr) {
+        const auto t = __builtin_amdgcn_raw_buffer_load_b96(rsB, voff, rr * row_bytes, 0);
+        // (through a scalar: __builtin_bit_cast applied directly to a vector element reads element 0, ROCm 7.2)
+        const unsigned u0 = t[0], u1 = t[1], u2 = t[2];
+        win[rr][0] = __builtin_bit_cast(float, u0);
+        win[rr][1] = __builtin_bit_cast(float, u1);
+        win[rr][2] = __builtin_bit_cast(float, u2);
+      }
+    }
     f2 A[9], Bn[9];
 #pragma unroll
     for (int rr = 0; rr < 9; ++rr) {
-      const auto t = __builtin_amdgcn_raw_buffer_load_b96(rsB, voff, rr * row_bytes, 0);
-      // (through a scalar: __builtin_bit_cast applied directly to a vector element reads element 0, ROCm 7.2)
-      const unsigned u0 = t[0], u1 = t[1], u2 = t[2];
-      const float c0 = __builtin_bit_cast(float, u0), c1 = __builtin_bit_cast(float, u1),
-                  c2 = __builtin_bit_cast(float, u2);
-      A[rr] = f2{c1, c2};
-      Bn[rr] = f2{c0, c1};
+      A[rr] = f2{win[rr][1], win[rr][2]};
+      Bn[rr] = f2{win[rr][0], win[rr][1]};
     }
     f2 v[R];
     if constexpr (kFusedContract) {
@@ -1349,12 +1377,14 @@ hipError_t launch_patch_optimize(const DisArgs& a, hipStream_t s, const ofdis_tu
   const int blocks_per_frame = (wpf + wpb - 1) / wpb;
   const int grid = ((a.nframes + 7) / 8) * 8 * blocks_per_frame;
   const dim3 gd(grid), bd(wpb * 64);
+  DisArgs ag = a;  // the gray 8x8 kernel's copy
+  ag.reload_window = !tn.patch_window_reuse;
   if (M <= 1 && gray8 && a.stereo)
-    hipLaunchKernelGGL((patch_optimize_gray8_kernel<-1, true>), gd, bd, 0, s, a);
+    hipLaunchKernelGGL((patch_optimize_gray8_kernel<-1, true>), gd, bd, 0, s, ag);
   else if (M <= 1 && gray8 && a.costfct == 0)
-    hipLaunchKernelGGL((patch_optimize_gray8_kernel<0, false>), gd, bd, 0, s, a);
+    hipLaunchKernelGGL((patch_optimize_gray8_kernel<0, false>), gd, bd, 0, s, ag);
   else if (M <= 1 && gray8)
-    hipLaunchKernelGGL((patch_optimize_gray8_kernel<-1, false>), gd, bd, 0, s, a);
+    hipLaunchKernelGGL((patch_optimize_gray8_kernel<-1, false>), gd, bd, 0, s, ag);
   else if (M <= 1 && full && a.costfct == 0)
     hipLaunchKernelGGL((patch_optimize_kernel<1, 8, 64, 0>), gd, bd, 0, s, a);
   else if (M <= 1 && full)

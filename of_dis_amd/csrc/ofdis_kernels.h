@@ -16,6 +16,8 @@ struct DisArgs {
   // solver parameters (oflow.cpp:76-108)
   int max_iter, min_iter, costfct, patnorm;
   int stereo, camlr;  // SELECTMODE=2: one horizontal displacement per patch; camlr 0 -> p <= 0, 1 -> p >= 0 (patch.cpp:188-193)
+  int reload_window;  // set by launch_patch_optimize (!ofdis_tuning::patch_window_reuse): the gray 8x8 kernel fetches its tap
+                      // window in every evaluation, also where it has not moved
   float dp_thresh_sq, dr_thresh, res_thresh;
   float outlier_sq_max;  // largest x with sqrtf(x) <= outlierthresh (= P/2, oflow.cpp:82): outlier_sq_threshold()
   const float* im_a;     // [B][tmp_h][tmp_w][noc]
