@@ -10,12 +10,12 @@
 // ofdis_batch_upsample_bidir / _upsample_frames (ofdis_upsample.h: upsample_at, fb_code on UpNeighbours), so they see the
 // bits the standalone kernels read from that function's materialised outputs: both routes give the same models and labels.
 //
-// Accumulate (one launch per round, all pairs): one lane owns a quad of 4 adjacent pixels of one row of one pair (QuadGrid,
-// xcd_frame_map: the workgroups of a pair stay on one XCD).  A lane's partial sums are reduced over its wavefront by
-// shuffles (64-bit values as two halves), over the workgroup's four wavefronts through LDS, and the workgroup writes ONE
-// 96-byte record into its own slab slot [pair][block] with plain stores.  No atomics, no flags, no waiting between
-// workgroups: the solve kernel, behind it on the stream, sums a pair's records with one wavefront and one lane solves.  The
-// next round's accumulate launch reads that model from device memory.
+// Accumulate (one launch per round, all pairs): the quad mapping of ofdis_quad.h over the pairs; the lanes past a pair's last
+// quad stay for the workgroup's reduction.  A lane's partial sums are reduced over its wavefront by shuffles (64-bit values as
+// two halves), over the workgroup's four wavefronts through LDS, and the workgroup writes ONE 96-byte record into its own slab
+// slot [pair][block] with plain stores.  No atomics, no flags, no waiting between workgroups: the solve kernel, behind it on
+// the stream, sums a pair's records with one wavefront and one lane solves.  The next round's accumulate launch reads that
+// model from device memory.
 //
 // Widths of the partial sums, with |X|, |Y| <= 8191 < 2^13 (OFDIS_GM_MAX_SIDE) and |qu|, |qv| <= 2^20 (OFDIS_GM_MAX_FLOW * 256):
 //   per lane (4 pixels)       n <= 4, |SX|, |SY| < 2^15, SXX, |SXY|, SYY < 2^28, |Squ|, |Sqv| <= 2^22: int32;
@@ -32,17 +32,16 @@ typedef float gm_f4 __attribute__((ext_vector_type(4)));
 enum { GM_INLIER = 0, GM_OUTLIER = 1, GM_INVALID = 2 };
 enum { GM_NSUMS = 12 };  // n, SX, SY, SXX, SXY, SYY, Squ, SXqu, SYqu, Sqv, SXqv, SYqv: one slab record
 
-// what the accumulate and compensate kernels are launched with: the pairs [f0, f0 + n) of this launch
+// what the accumulate and compensate kernels are launched with: the pairs of this launch
 struct GmArgs {
   const double* models;  // [npairs][6]: the previous round's models (gated accumulate), the models to subtract (compensate)
   long long* slab;       // [npairs][bpf][GM_NSUMS] (accumulate)
   float2* residual;      // [npairs][H][W] or null (compensate)
   uint8_t* label;        // [npairs][H][W] or null (compensate)
-  int f0, n;
-  int bpf;               // blocks per pair (QuadGrid)
+  QuadLaunch q;
   float t2;              // thresh * thresh
   int res_align;         // compensate: 16 / 8 / 4-byte stores of the residual
-  bool vec_label;        // ... and 4-byte stores of the labels
+  bool vec_label;        // ... and quad_vec of the labels
 };
 
 // the model of a pair in fp32 and the header's residual
@@ -65,24 +64,6 @@ __device__ __forceinline__ bool gm_near(float2 r, float t2) { return r.x * r.x +
 // u and v finite and within OFDIS_GM_MAX_FLOW (NaN: false)
 __device__ __forceinline__ bool gm_in_range(float2 uv) { return fabsf(uv.x) <= 4096.0f && fabsf(uv.y) <= 4096.0f; }
 
-// the lane's pair (relative to the call) and quad; false: the whole workgroup has nothing to do (xcd_frame_map's padding)
-struct GmLane {
-  int pair, blk, x, y;
-  bool active;  // false: a lane past the last quad of the pair (x = y = 0, nothing is read)
-};
-__device__ __forceinline__ bool gm_lane(const GmArgs& a, int W, int H, GmLane& l) {
-  int lf;
-  xcd_frame_map(blockIdx.x, a.bpf, a.n, lf, l.blk);
-  if (lf >= a.n) return false;
-  l.pair = a.f0 + lf;
-  const int qpr = (W + 3) >> 2;
-  const int qi = l.blk * 256 + threadIdx.x;
-  l.active = qi < qpr * H;
-  l.y = l.active ? qi / qpr : 0;
-  l.x = l.active ? (qi - l.y * qpr) * 4 : 0;
-  return true;
-}
-
 __device__ __forceinline__ int gm_wave_sum(int v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -102,10 +83,10 @@ __device__ __forceinline__ long long gm_wave_sum(long long v) {
 // row, `consistent(xx, uv)` whether the mask there is OFDIS_FB_CONSISTENT (asked only where the flow is in range and, GATED,
 // near).  GATED: the set is `near` under the model of the previous round.  Every lane of the workgroup gets here.
 template <bool GATED, class Flow, class Consistent>
-__device__ __forceinline__ void gm_block_sums(const GmArgs& a, const GmLane& l, int W, int H, Flow flow, Consistent consistent) {
+__device__ __forceinline__ void gm_block_sums(const GmArgs& a, const QuadLane& l, int W, int H, Flow flow, Consistent consistent) {
   __shared__ long long part[4][GM_NSUMS];
   GmModel m;
-  if constexpr (GATED) m = gm_model(a.models, l.pair);
+  if constexpr (GATED) m = gm_model(a.models, l.f);
   const int np = l.active ? min(4, W - l.x) : 0;
   const int Y = 2 * l.y - (H - 1);
   int n = 0, sx = 0, sy = 0, sxx = 0, sxy = 0, syy = 0, su = 0, sv = 0;
@@ -138,7 +119,7 @@ __device__ __forceinline__ void gm_block_sums(const GmArgs& a, const GmLane& l, 
   __syncthreads();
   if (threadIdx.x < GM_NSUMS) {
     const int k = threadIdx.x;
-    a.slab[((size_t)l.pair * a.bpf + l.blk) * GM_NSUMS + k] = (part[0][k] + part[1][k]) + (part[2][k] + part[3][k]);
+    a.slab[((size_t)l.f * a.q.bpf + l.blk) * GM_NSUMS + k] = (part[0][k] + part[1][k]) + (part[2][k] + part[3][k]);
   }
 }
 
@@ -146,9 +127,9 @@ __device__ __forceinline__ void gm_block_sums(const GmArgs& a, const GmLane& l, 
 template <bool GATED>
 __global__ __launch_bounds__(256) void gm_sums_frames_kernel(const float2* __restrict__ flow, const uint8_t* __restrict__ mask,
                                                              int W, int H, GmArgs a) {
-  GmLane l;
-  if (!gm_lane(a, W, H, l)) return;
-  const size_t row = ((size_t)l.pair * H + l.y) * W;
+  QuadLane l;
+  if (!quad_lane(a.q, W, H, l)) return;
+  const size_t row = ((size_t)l.f * H + l.y) * W;
   const float2* fl = flow + row;
   const uint8_t* mk = mask ? mask + row : nullptr;
   gm_block_sums<GATED>(a, l, W, H, [&](int xx) { return fl[xx]; },
@@ -160,10 +141,10 @@ __global__ __launch_bounds__(256) void gm_sums_frames_kernel(const float2* __res
 template <bool GATED>
 __global__ __launch_bounds__(256) void gm_sums_level_kernel(const float2* __restrict__ fw, const float2* __restrict__ rev,
                                                             UpGeom g, float alpha, float beta, GmArgs a) {
-  GmLane l;
-  if (!gm_lane(a, g.wo, g.ho, l)) return;
-  const float2* fl = fw + (size_t)l.pair * g.plane();
-  const float2* other = rev ? rev + (size_t)l.pair * g.plane() : nullptr;
+  QuadLane l;
+  if (!quad_lane(a.q, g.wo, g.ho, l)) return;
+  const float2* fl = fw + (size_t)l.f * g.plane();
+  const float2* other = rev ? rev + (size_t)l.f * g.plane() : nullptr;
   const UpRow ry = up_row(l.y + g.top, g);
   gm_block_sums<GATED>(a, l, g.wo, g.ho, [&](int xx) { return upsample_at(fl, g, xx + g.left, ry); },
                        [&](int xx, float2 uv) {
@@ -237,8 +218,8 @@ __global__ __launch_bounds__(64) void gm_solve_kernel(const long long* __restric
 // ------------------------------------------------------------------------------------ compensate
 // The quad's residuals and labels.  The residual may alias the flow: a lane reads its own four pixels before it writes them.
 template <class Flow, class Consistent>
-__device__ __forceinline__ void gm_compensate_quad(const GmArgs& a, const GmLane& l, int W, int H, Flow flow, Consistent consistent) {
-  const GmModel m = gm_model(a.models, l.pair);
+__device__ __forceinline__ void gm_compensate_quad(const GmArgs& a, const QuadLane& l, int W, int H, Flow flow, Consistent consistent) {
+  const GmModel m = gm_model(a.models, l.f);
   const int np = min(4, W - l.x);
   const int Y = 2 * l.y - (H - 1);
   float2 r[4];
@@ -253,7 +234,7 @@ __device__ __forceinline__ void gm_compensate_quad(const GmArgs& a, const GmLane
     r[i] = gm_residual(m, 2 * xx - (W - 1), Y, uv);
     if (gm_in_range(uv) && consistent(xx, uv)) lab[i] = gm_near(r[i], a.t2) ? GM_INLIER : GM_OUTLIER;
   }
-  const size_t px0 = ((size_t)l.pair * H + l.y) * W + l.x;  // the quad's first pixel in a [pairs][H][W] array
+  const size_t px0 = ((size_t)l.f * H + l.y) * W + l.x;  // the quad's first pixel in a [pairs][H][W] array
   if (a.residual) {
     float2* o = a.residual + px0;
     if (a.res_align >= 16) {  // (W even and the array 16-byte aligned: pixels px0, px0 + 2 start a 16-byte unit)
@@ -273,25 +254,15 @@ __device__ __forceinline__ void gm_compensate_quad(const GmArgs& a, const GmLane
         if (i < np) { of[2 * i] = r[i].x; of[2 * i + 1] = r[i].y; }
     }
   }
-  if (a.label) {
-    uint8_t* lo = a.label + px0;
-    if (a.vec_label && np == 4) {
-      const unsigned wd = (unsigned)lab[0] | ((unsigned)lab[1] << 8) | ((unsigned)lab[2] << 16) | ((unsigned)lab[3] << 24);
-      __builtin_nontemporal_store(wd, reinterpret_cast<unsigned*>(lo));
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (i < np) lo[i] = lab[i];
-    }
-  }
+  if (a.label) quad_store<1>(a.label + px0, lab, np, a.vec_label);
 }
 
 // (no __restrict__ on the flow: the residual may be the same array)
 __global__ __launch_bounds__(256) void gm_compensate_frames_kernel(const float2* flow, const uint8_t* __restrict__ mask, int W, int H,
                                                                    GmArgs a) {
-  GmLane l;
-  if (!gm_lane(a, W, H, l) || !l.active) return;
-  const size_t row = ((size_t)l.pair * H + l.y) * W;
+  QuadLane l;
+  if (!quad_lane(a.q, W, H, l) || !l.active) return;
+  const size_t row = ((size_t)l.f * H + l.y) * W;
   const float2* fl = flow + row;
   const uint8_t* mk = mask ? mask + row : nullptr;
   gm_compensate_quad(a, l, W, H, [&](int xx) { return fl[xx]; }, [&](int xx, float2) { return !mk || mk[xx] == FB_CONSISTENT; });
@@ -299,10 +270,10 @@ __global__ __launch_bounds__(256) void gm_compensate_frames_kernel(const float2*
 
 __global__ __launch_bounds__(256) void gm_compensate_level_kernel(const float2* __restrict__ fw, const float2* __restrict__ rev,
                                                                   UpGeom g, float alpha, float beta, GmArgs a) {
-  GmLane l;
-  if (!gm_lane(a, g.wo, g.ho, l) || !l.active) return;
-  const float2* fl = fw + (size_t)l.pair * g.plane();
-  const float2* other = rev ? rev + (size_t)l.pair * g.plane() : nullptr;
+  QuadLane l;
+  if (!quad_lane(a.q, g.wo, g.ho, l) || !l.active) return;
+  const float2* fl = fw + (size_t)l.f * g.plane();
+  const float2* other = rev ? rev + (size_t)l.f * g.plane() : nullptr;
   const UpRow ry = up_row(l.y + g.top, g);
   gm_compensate_quad(a, l, g.wo, g.ho, [&](int xx) { return upsample_at(fl, g, xx + g.left, ry); },
                      [&](int xx, float2 uv) {
@@ -319,15 +290,11 @@ size_t gmotion_work_bytes(int npairs, int w, int h) {
 // the launches of one pass over all pairs: `launch(GmArgs, blocks)` once per chunk of pairs
 template <class Launch>
 static hipError_t gm_chunks(GmArgs a, int npairs, int w, int h, Launch launch) {
-  const QuadGrid g = quad_grid(npairs, w, h);
-  a.bpf = g.bpf;
-  for (a.f0 = 0; a.f0 < npairs; a.f0 += g.chunk) {
-    a.n = std::min(g.chunk, npairs - a.f0);
-    launch(a, dim3(quad_blocks(a.n, g.bpf)));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  return quad_chunks(npairs, w, h, [&](const QuadLaunch& q, dim3 blocks) {
+    a.q = q;
+    launch(a, blocks);
+    return hipGetLastError();
+  });
 }
 
 // `rounds` times (accumulate, solve) on the stream; `sums(gated, GmArgs, blocks)` launches one accumulate kernel
@@ -385,7 +352,7 @@ static GmArgs gm_compensate_args(const double* models, float thresh, float* resi
   a.t2 = thresh * thresh;
   const uintptr_t ra = (uintptr_t)residual;
   a.res_align = (w & 1) == 0 && (ra & 15) == 0 ? 16 : ((ra & 7) == 0 ? 8 : 4);
-  a.vec_label = (w & 3) == 0 && ((uintptr_t)label & 3) == 0;
+  a.vec_label = quad_vec(w, label);
   return a;
 }
 

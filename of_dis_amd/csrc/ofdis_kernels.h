@@ -64,7 +64,7 @@ struct UpGeom {
 };
 
 // The two launch limits, in workgroups of 256 lanes.  QUAD_MAX_BLOCKS: one launch of a kernel in which a lane owns a quad of
-// one frame (quad_grid, ofdis_upsample.h); the launcher walks the frames in chunks that stay below it.  GRID_MAX_BLOCKS: the
+// one frame (quad_chunks, ofdis_quad.h); the launcher walks the frames in chunks that stay below it.  GRID_MAX_BLOCKS: the
 // grid of a grid-stride kernel (grid_for); the kernel loops over what is beyond it.  Both are read in host code only.  The
 // product is built with the constants; the test library (tests/csrc/ofdis_launch_hooks.hip) compiles the same units with
 // OFDIS_TEST_LAUNCH_LIMITS, where they are two host variables of that library which a test lowers to reach the second chunk

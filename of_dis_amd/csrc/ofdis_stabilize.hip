@@ -11,11 +11,9 @@
 // two running maps and the accumulator are named scalars (StabMap): nothing is indexed dynamically, nothing goes to scratch.
 // At most 2 * radius models of 48 bytes per lane: the cost is negligible next to one frame of the warp.
 //
-// warp_frames_kernel<NOC>: the quad mapping of ofdis_tfilter.hip -- one lane owns 4 adjacent pixels of one row of one frame,
-// 256 quads per workgroup, a frame's workgroups on one XCD (xcd_frame_map), launches in quad_grid chunks.  The frame's six
-// coefficients are uniform per workgroup (scalar loads).  Four taps per pixel through interp_sample; an affine warp keeps the
-// lanes of a wavefront on neighbouring source bytes.  4 * NOC output bytes and 4 `inside` bytes per lane as 4-byte non-temporal
-// stores (neither array is read by this library), byte stores where the row or the array does not allow them.  No LDS.
+// warp_frames_kernel<NOC>: the quad mapping of ofdis_quad.h.  The frame's six coefficients are uniform per workgroup (scalar
+// loads).  Four taps per pixel through interp_sample; an affine warp keeps the lanes of a wavefront on neighbouring source
+// bytes.  4 * NOC output bytes and 4 `inside` bytes per lane (quad_store).  No LDS.
 #include "ofdis_upsample.h"
 
 namespace ofdis {
@@ -110,27 +108,22 @@ hipError_t launch_camera_path(const double* models, int npairs, const StabWindow
 }
 
 // ------------------------------------------------------------------------------------ frame warp
-// what the kernel is launched with: the frames [f0, f0 + n) of this launch
+// what the kernel is launched with: the frames of this launch
 struct StabWarpArgs {
   const uint8_t* frames;  // [nframes][H][W][NOC]
   const double* warps;    // [nframes][6]
   uint8_t* out;           // [nframes][H][W][NOC]
   uint8_t* inside;        // [nframes][H][W] or null
-  int f0, n;
-  int bpf;                // blocks per frame (QuadGrid)
+  QuadLaunch q;
   bool replicate;         // OFDIS_BORDER_REPLICATE
-  bool vec_out, vec_ins;  // 4-byte stores: rows a multiple of 4 pixels, the array 4-byte aligned
+  bool vec_out, vec_ins;  // quad_vec of out and inside
 };
 
 template <int NOC>
 __global__ __launch_bounds__(256) void warp_frames_kernel(int W, int H, StabWarpArgs a) {
-  int lf, blk;
-  xcd_frame_map(blockIdx.x, a.bpf, a.n, lf, blk);
-  const int qpr = (W + 3) >> 2;
-  const int qi = blk * 256 + threadIdx.x;
-  if (lf >= a.n || qi >= qpr * H) return;
-  const int f = a.f0 + lf;
-  const int y = qi / qpr, x = (qi - y * qpr) * 4;
+  QuadLane l;
+  if (!quad_lane(a.q, W, H, l) || !l.active) return;
+  const int f = l.f, x = l.x, y = l.y;
   const int np = min(4, W - x);
   const size_t plane = (size_t)W * H;
   const uint8_t* I = a.frames + f * plane * NOC;
@@ -154,53 +147,24 @@ __global__ __launch_bounds__(256) void warp_frames_kernel(int W, int H, StabWarp
         interp_sample(I, W, H, NOC, fminf(fmaxf(px, 0.0f), (float)(W - 1)), fminf(fmaxf(py, 0.0f), (float)(H - 1)), c);
     }
 #pragma unroll
-    for (int ch = 0; ch < NOC; ++ch) {
-      const int v = (int)floorf(c[ch] + 0.5f);
-      q[i * NOC + ch] = (uint8_t)min(max(v, 0), 255);
-    }
+    for (int ch = 0; ch < NOC; ++ch) q[i * NOC + ch] = quad_u8(c[ch]);
   }
   const size_t px0 = f * plane + (size_t)y * W + x;  // the quad's first pixel in a [frames][H][W] array
-  uint8_t* o = a.out + px0 * NOC;
-  if (a.vec_out && np == 4) {
-    unsigned wd[NOC];
-#pragma unroll
-    for (int j = 0; j < NOC; ++j)
-      wd[j] = (unsigned)q[4 * j] | ((unsigned)q[4 * j + 1] << 8) | ((unsigned)q[4 * j + 2] << 16) | ((unsigned)q[4 * j + 3] << 24);
-#pragma unroll
-    for (int j = 0; j < NOC; ++j) __builtin_nontemporal_store(wd[j], reinterpret_cast<unsigned*>(o) + j);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4 * NOC; ++j)
-      if (j < np * NOC) o[j] = q[j];
-  }
-  if (!a.inside) return;
-  uint8_t* io = a.inside + px0;
-  if (a.vec_ins && np == 4) {
-    const unsigned wd = (unsigned)ins[0] | ((unsigned)ins[1] << 8) | ((unsigned)ins[2] << 16) | ((unsigned)ins[3] << 24);
-    __builtin_nontemporal_store(wd, reinterpret_cast<unsigned*>(io));
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (j < np) io[j] = ins[j];
-  }
+  quad_store<NOC>(a.out + px0 * NOC, q, np, a.vec_out);
+  if (a.inside) quad_store<1>(a.inside + px0, ins, np, a.vec_ins);
 }
 
 hipError_t launch_warp_frames(const uint8_t* frames, const double* warps, uint8_t* out, uint8_t* inside, int nframes, int w,
                               int h, int noc, bool replicate, hipStream_t s) {
-  const QuadGrid g = quad_grid(nframes, w, h);
-  StabWarpArgs a{frames, warps, out, inside, 0, 0, g.bpf, replicate, (w & 3) == 0 && ((uintptr_t)out & 3) == 0,
-             (w & 3) == 0 && ((uintptr_t)inside & 3) == 0};
-  for (a.f0 = 0; a.f0 < nframes; a.f0 += g.chunk) {
-    a.n = std::min(g.chunk, nframes - a.f0);
-    const dim3 blocks(quad_blocks(a.n, g.bpf));
+  StabWarpArgs a{frames, warps, out, inside, QuadLaunch{}, replicate, quad_vec(w, out), quad_vec(w, inside)};
+  return quad_chunks(nframes, w, h, [&](const QuadLaunch& q, dim3 blocks) {
+    a.q = q;
     if (noc == 3)
       hipLaunchKernelGGL(warp_frames_kernel<3>, blocks, dim3(256), 0, s, w, h, a);
     else
       hipLaunchKernelGGL(warp_frames_kernel<1>, blocks, dim3(256), 0, s, w, h, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+    return hipGetLastError();
+  });
 }
 
 }  // namespace ofdis

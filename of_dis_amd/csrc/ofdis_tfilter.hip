@@ -9,24 +9,23 @@
 // with the helpers of ofdis_batch_upsample_bidir (ofdis_upsample.h: upsample_at, fb_code on UpNeighbours) -- writes the bits
 // the standalone kernel writes on that function's materialised outputs.
 //
-// Mapping (both kernels): one lane owns a quad of 4 adjacent pixels of one row of one OUTPUT frame: it reads the quad of
-// frame f, takes up to two flows per pixel, gathers the four taps of each valid sample and writes the quad's 4 * noc bytes
-// (one dword for gray, three for RGB) and its 4 support bytes (one dword), non-temporal: neither is read by this library.  The
-// workgroups of a frame stay on one XCD (xcd_frame_map): a frame is read three times -- as the centre of its own output and as
-// a neighbour of the two next to it, which the same launch works on at about the same time.
+// Mapping (both kernels): the quad mapping of ofdis_quad.h over the OUTPUT frames.  A lane reads the quad of frame f, takes up
+// to two flows per pixel, gathers the four taps of each valid sample and writes the quad's 4 * noc bytes and its 4 support
+// bytes (quad_store).  A frame is read three times -- as the centre of its own output and as a neighbour of the two next to
+// it, which the same launch works on at about the same time.
 #include "ofdis_upsample.h"
 
 namespace ofdis {
 
-// what both kernels are launched with: the clip, the outputs, the output frames [f0, f0 + n) of this launch
+// what both kernels are launched with: the clip, the outputs, the output frames of this launch
 struct TfArgs {
   const uint8_t* frames;  // [npairs + 1][H][W][NOC]
   uint8_t* out;           // [npairs + 1][H][W][NOC]
   uint8_t* support;       // [npairs + 1][H][W] or null
-  int f0, n, npairs;
-  int bpf;                // blocks per frame (QuadGrid)
+  QuadLaunch q;
+  int npairs;
   float wn, tau;
-  bool vec_out, vec_sup;  // 4-byte stores: rows a multiple of 4 pixels, the array 4-byte aligned
+  bool vec_out, vec_sup;  // quad_vec of out and support
 };
 
 // The header's definition for the quad of pixels x .. x+3 of row y (those < W) of output frame f.  Candidate d = 0 is the next
@@ -64,48 +63,13 @@ __device__ __forceinline__ void tfilter_quad(const TfArgs& a, int f, int x, int 
 #pragma unroll
     for (int ch = 0; ch < NOC; ++ch) {
       const float num = (c[ch] + w[1] * s[1][ch]) + w[0] * s[0][ch];
-      const int v = (int)floorf(num / den + 0.5f);
-      q[i * NOC + ch] = (uint8_t)min(max(v, 0), 255);
+      q[i * NOC + ch] = quad_u8(num / den);
     }
     sup[i] = (uint8_t)((w[1] > 0.0f ? 1 : 0) | (w[0] > 0.0f ? 2 : 0));
   }
   const size_t px0 = f * plane + (size_t)y * W + x;  // the quad's first pixel in a [frames][H][W] array
-  uint8_t* o = a.out + px0 * NOC;
-  if (a.vec_out && np == 4) {
-    unsigned wd[NOC];
-#pragma unroll
-    for (int j = 0; j < NOC; ++j)
-      wd[j] = (unsigned)q[4 * j] | ((unsigned)q[4 * j + 1] << 8) | ((unsigned)q[4 * j + 2] << 16) | ((unsigned)q[4 * j + 3] << 24);
-#pragma unroll
-    for (int j = 0; j < NOC; ++j) __builtin_nontemporal_store(wd[j], reinterpret_cast<unsigned*>(o) + j);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4 * NOC; ++j)
-      if (j < np * NOC) o[j] = q[j];
-  }
-  if (!a.support) return;
-  uint8_t* so = a.support + px0;
-  if (a.vec_sup && np == 4) {
-    const unsigned wd = (unsigned)sup[0] | ((unsigned)sup[1] << 8) | ((unsigned)sup[2] << 16) | ((unsigned)sup[3] << 24);
-    __builtin_nontemporal_store(wd, reinterpret_cast<unsigned*>(so));
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (j < np) so[j] = sup[j];
-  }
-}
-
-// the lane's output frame and quad; false: nothing to do
-__device__ __forceinline__ bool tfilter_lane(const TfArgs& a, int W, int H, int& f, int& x, int& y) {
-  int lf, blk;
-  xcd_frame_map(blockIdx.x, a.bpf, a.n, lf, blk);
-  const int qpr = (W + 3) >> 2;
-  const int qi = blk * 256 + threadIdx.x;
-  if (lf >= a.n || qi >= qpr * H) return false;
-  f = a.f0 + lf;
-  y = qi / qpr;
-  x = (qi - y * qpr) * 4;
-  return true;
+  quad_store<NOC>(a.out + px0 * NOC, q, np, a.vec_out);
+  if (a.support) quad_store<1>(a.support + px0, sup, np, a.vec_sup);
 }
 
 // Materialised arrays: flows [npairs][H][W][2], masks [npairs][H][W] or null.
@@ -113,8 +77,9 @@ template <int NOC>
 __global__ __launch_bounds__(256) void tfilter_frames_kernel(const float2* __restrict__ ffw, const float2* __restrict__ frev,
                                                              const uint8_t* __restrict__ mfw, const uint8_t* __restrict__ mrev,
                                                              int W, int H, TfArgs a) {
-  int f, x, y;
-  if (!tfilter_lane(a, W, H, f, x, y)) return;
+  QuadLane l;
+  if (!quad_lane(a.q, W, H, l) || !l.active) return;
+  const int f = l.f, x = l.x, y = l.y;
   const size_t plane = (size_t)W * H;
   // candidate 0 belongs to pair f, candidate 1 to pair f - 1 (a pair that does not exist is never read: tfilter_quad)
   const size_t row[2] = {min(f, a.npairs - 1) * plane + (size_t)y * W, max(f - 1, 0) * plane + (size_t)y * W};
@@ -130,8 +95,9 @@ __global__ __launch_bounds__(256) void tfilter_frames_kernel(const float2* __res
 template <int NOC>
 __global__ __launch_bounds__(256) void tfilter_level_kernel(const float2* __restrict__ fw, const float2* __restrict__ rev,
                                                             UpGeom g, float alpha, float beta, TfArgs a) {
-  int f, x, y;
-  if (!tfilter_lane(a, g.wo, g.ho, f, x, y)) return;
+  QuadLane l;
+  if (!quad_lane(a.q, g.wo, g.ho, l) || !l.active) return;
+  const int f = l.f, x = l.x, y = l.y;
   const size_t pair[2] = {(size_t)min(f, a.npairs - 1) * g.plane(), (size_t)max(f - 1, 0) * g.plane()};
   const float2* fl[2] = {fw + pair[0], rev + pair[1]};     // the flow from frame f to the neighbour ...
   const float2* other[2] = {rev + pair[0], fw + pair[1]};  // ... and the same pair's flow back
@@ -142,43 +108,36 @@ __global__ __launch_bounds__(256) void tfilter_level_kernel(const float2* __rest
                     });
 }
 
-// the launches of one call: `launch(TfArgs, blocks)` once per chunk of output frames
-template <class Launch>
-static hipError_t tfilter_chunks(const uint8_t* frames, uint8_t* out, uint8_t* support, int npairs, int w, int h, float wn,
-                                 float tau, Launch launch) {
-  const int nframes = npairs + 1;
-  const QuadGrid g = quad_grid(nframes, w, h);
-  TfArgs a{frames, out, support, 0, 0, npairs, g.bpf, wn, tau, (w & 3) == 0 && ((uintptr_t)out & 3) == 0,
-           (w & 3) == 0 && ((uintptr_t)support & 3) == 0};
-  for (a.f0 = 0; a.f0 < nframes; a.f0 += g.chunk) {
-    a.n = std::min(g.chunk, nframes - a.f0);
-    launch(a, dim3(quad_blocks(a.n, g.bpf)));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+static TfArgs tfilter_args(const uint8_t* frames, uint8_t* out, uint8_t* support, int npairs, int w, float wn, float tau) {
+  return TfArgs{frames, out, support, QuadLaunch{}, npairs, wn, tau, quad_vec(w, out), quad_vec(w, support)};
 }
 
 hipError_t launch_tfilter_frames(const uint8_t* frames, const float* flow_fw, const float* flow_rev, const uint8_t* mask_fw,
                                  const uint8_t* mask_rev, uint8_t* out, uint8_t* support, int npairs, int w, int h, int noc,
                                  float wn, float tau, hipStream_t s) {
   const float2 *ff = (const float2*)flow_fw, *fr = (const float2*)flow_rev;
-  return tfilter_chunks(frames, out, support, npairs, w, h, wn, tau, [&](const TfArgs& a, dim3 blocks) {
+  TfArgs a = tfilter_args(frames, out, support, npairs, w, wn, tau);
+  return quad_chunks(npairs + 1, w, h, [&](const QuadLaunch& q, dim3 blocks) {
+    a.q = q;
     if (noc == 3)
       hipLaunchKernelGGL(tfilter_frames_kernel<3>, blocks, dim3(256), 0, s, ff, fr, mask_fw, mask_rev, w, h, a);
     else
       hipLaunchKernelGGL(tfilter_frames_kernel<1>, blocks, dim3(256), 0, s, ff, fr, mask_fw, mask_rev, w, h, a);
+    return hipGetLastError();
   });
 }
 
 hipError_t launch_tfilter_level(const uint8_t* frames, const float* fw, const float* rev, uint8_t* out, uint8_t* support,
                                 int npairs, UpGeom ug, int noc, float wn, float tau, float alpha, float beta, hipStream_t s) {
   const float2 *ff = (const float2*)fw, *fr = (const float2*)rev;
-  return tfilter_chunks(frames, out, support, npairs, ug.wo, ug.ho, wn, tau, [&](const TfArgs& a, dim3 blocks) {
+  TfArgs a = tfilter_args(frames, out, support, npairs, ug.wo, wn, tau);
+  return quad_chunks(npairs + 1, ug.wo, ug.ho, [&](const QuadLaunch& q, dim3 blocks) {
+    a.q = q;
     if (noc == 3)
       hipLaunchKernelGGL(tfilter_level_kernel<3>, blocks, dim3(256), 0, s, ff, fr, ug, alpha, beta, a);
     else
       hipLaunchKernelGGL(tfilter_level_kernel<1>, blocks, dim3(256), 0, s, ff, fr, ug, alpha, beta, a);
+    return hipGetLastError();
   });
 }
 

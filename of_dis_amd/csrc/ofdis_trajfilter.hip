@@ -10,29 +10,27 @@
 // taps around a real position with UpNeighbours, as every other finish kernel does -- writes the bits the standalone kernel
 // writes on the materialised outputs of ofdis_batch_upsample_bidir.
 //
-// Mapping (both kernels): that of ofdis_tfilter.hip -- one lane owns a quad of 4 adjacent pixels of one row of one OUTPUT
-// frame, 256 quads per workgroup, launches in quad_grid chunks.  A step of a walk is a chain of dependent gathers (the flow
-// at p, the other direction's flow at q, the frame at q); the lane's four walks of one direction take each link of that chain
-// together and without a branch -- a walk that has ended goes on gathering at its last position, which is inside the image,
-// and its results are discarded -- so four independent gathers are in flight per lane and link, and the wavefronts of a CU
-// hide the rest.  The workgroups of a frame stay on one XCD (xcd_frame_map): a frame is read by the 2R + 1 output frames
-// around it, which one launch works on at about the same time.  out and support are written once and never read by this
-// library: non-temporal stores.  No LDS; the weights and the radius travel in the launch arguments.
+// Mapping (both kernels): the quad mapping of ofdis_quad.h over the OUTPUT frames.  A step of a walk is a chain of dependent
+// gathers (the flow at p, the other direction's flow at q, the frame at q); the lane's four walks of one direction take each
+// link of that chain together and without a branch -- a walk that has ended goes on gathering at its last position, which is
+// inside the image, and its results are discarded -- so four independent gathers are in flight per lane and link, and the
+// wavefronts of a CU hide the rest.  A frame is read by the 2R + 1 output frames around it, which one launch works on at
+// about the same time.  No LDS; the weights and the radius travel in the launch arguments.
 #include "ofdis_upsample.h"
 
 namespace ofdis {
 
-// what both kernels are launched with: the clip, the outputs, the output frames [f0, f0 + n) of this launch
+// what both kernels are launched with: the clip, the outputs, the output frames of this launch
 struct TrajArgs {
   const uint8_t* frames;  // [npairs + 1][H][W][NOC]
   uint8_t* out;           // [npairs + 1][H][W][NOC]
   uint8_t* support;       // [npairs + 1][H][W] or null
-  int f0, n, npairs;
-  int bpf;                // blocks per frame (QuadGrid)
+  QuadLaunch q;
+  int npairs;
   TrajWeights w;
   float tau, alpha, beta;
   bool fb;                // with the consistency test
-  bool vec_out, vec_sup;  // 4-byte stores: rows a multiple of 4 pixels, the array 4-byte aligned
+  bool vec_out, vec_sup;  // quad_vec of out and support
 };
 
 // The header's definition for the quad of pixels x .. x+3 of row y (those < W) of output frame f.  `first(k, r, xx)` gives
@@ -116,58 +114,25 @@ __device__ __forceinline__ void traj_quad(const TrajArgs& a, int f, int x, int y
       den[i] = (den[i] + wd[0][i]) + wd[1][i];
     }
   }
-  uint8_t o8[4 * NOC];
+  uint8_t o8[4 * NOC], sup[4];
 #pragma unroll
-  for (int i = 0; i < 4; ++i)
+  for (int i = 0; i < 4; ++i) {
 #pragma unroll
-    for (int ch = 0; ch < NOC; ++ch) {
-      const int v = (int)floorf(num[i][ch] / den[i] + 0.5f);
-      o8[i * NOC + ch] = (uint8_t)min(max(v, 0), 255);
-    }
+    for (int ch = 0; ch < NOC; ++ch) o8[i * NOC + ch] = quad_u8(num[i][ch] / den[i]);
+    sup[i] = (uint8_t)reach[i];
+  }
   const size_t px0 = f * plane + (size_t)y * W + x;  // the quad's first pixel in a [frames][H][W] array
-  uint8_t* o = a.out + px0 * NOC;
-  if (a.vec_out && np == 4) {
-#pragma unroll
-    for (int j = 0; j < NOC; ++j) {
-      const unsigned wd = (unsigned)o8[4 * j] | ((unsigned)o8[4 * j + 1] << 8) | ((unsigned)o8[4 * j + 2] << 16) |
-                          ((unsigned)o8[4 * j + 3] << 24);
-      __builtin_nontemporal_store(wd, reinterpret_cast<unsigned*>(o) + j);
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4 * NOC; ++j)
-      if (j < np * NOC) o[j] = o8[j];
-  }
-  if (!a.support) return;
-  uint8_t* so = a.support + px0;
-  if (a.vec_sup && np == 4) {
-    __builtin_nontemporal_store(reach[0] | (reach[1] << 8) | (reach[2] << 16) | (reach[3] << 24), reinterpret_cast<unsigned*>(so));
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (j < np) so[j] = (uint8_t)reach[j];
-  }
-}
-
-// the lane's output frame and quad; false: nothing to do
-__device__ __forceinline__ bool traj_lane(const TrajArgs& a, int W, int H, int& f, int& x, int& y) {
-  int lf, blk;
-  xcd_frame_map(blockIdx.x, a.bpf, a.n, lf, blk);
-  const int qpr = (W + 3) >> 2;
-  const int qi = blk * 256 + threadIdx.x;
-  if (lf >= a.n || qi >= qpr * H) return false;
-  f = a.f0 + lf;
-  y = qi / qpr;
-  x = (qi - y * qpr) * 4;
-  return true;
+  quad_store<NOC>(a.out + px0 * NOC, o8, np, a.vec_out);
+  if (a.support) quad_store<1>(a.support + px0, sup, np, a.vec_sup);
 }
 
 // materialised flows [npairs][H][W][2]: step 1 reads the pixel's flow directly, later steps its four taps (FlowTaps)
 template <int NOC>
 __global__ __launch_bounds__(256) void trajfilter_frames_kernel(const float2* __restrict__ fw, const float2* __restrict__ rev,
                                                                 int W, int H, TrajArgs a) {
-  int f, x, y;
-  if (!traj_lane(a, W, H, f, x, y)) return;
+  QuadLane l;
+  if (!quad_lane(a.q, W, H, l) || !l.active) return;
+  const int f = l.f, x = l.x, y = l.y;
   const size_t plane = (size_t)W * H;
   traj_quad<NOC>(a, f, x, y, W, H, [&](int k, int r, int xx) { return ((r ? rev : fw) + k * plane)[(size_t)y * W + xx]; },
                  [&](int k, int r) { return FlowTaps{(r ? rev : fw) + k * plane, W}; });
@@ -178,40 +143,32 @@ __global__ __launch_bounds__(256) void trajfilter_frames_kernel(const float2* __
 template <int NOC>
 __global__ __launch_bounds__(256) void trajfilter_level_kernel(const float2* __restrict__ fw, const float2* __restrict__ rev,
                                                                UpGeom g, TrajArgs a) {
-  int f, x, y;
-  if (!traj_lane(a, g.wo, g.ho, f, x, y)) return;
+  QuadLane l;
+  if (!quad_lane(a.q, g.wo, g.ho, l) || !l.active) return;
+  const int f = l.f, x = l.x, y = l.y;
   const UpRow ry = up_row(y + g.top, g);
   traj_quad<NOC>(a, f, x, y, g.wo, g.ho,
                  [&](int k, int r, int xx) { return upsample_at((r ? rev : fw) + k * g.plane(), g, xx + g.left, ry); },
                  [&](int k, int r) { return UpNeighbours{(r ? rev : fw) + k * g.plane(), g}; });
 }
 
-// the launches of one call: `launch(TrajArgs, blocks)` once per chunk of output frames
-template <class Launch>
-static hipError_t traj_chunks(const uint8_t* frames, uint8_t* out, uint8_t* support, int npairs, int w, int h,
-                              const TrajWeights& tw, float tau, bool fb, float alpha, float beta, Launch launch) {
-  const int nframes = npairs + 1;
-  const QuadGrid g = quad_grid(nframes, w, h);
-  TrajArgs a{frames, out, support, 0, 0, npairs, g.bpf, tw, tau, alpha, beta, fb, (w & 3) == 0 && ((uintptr_t)out & 3) == 0,
-             (w & 3) == 0 && ((uintptr_t)support & 3) == 0};
-  for (a.f0 = 0; a.f0 < nframes; a.f0 += g.chunk) {
-    a.n = std::min(g.chunk, nframes - a.f0);
-    launch(a, dim3(quad_blocks(a.n, g.bpf)));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+static TrajArgs traj_args(const uint8_t* frames, uint8_t* out, uint8_t* support, int npairs, int w, const TrajWeights& tw,
+                          float tau, bool fb, float alpha, float beta) {
+  return TrajArgs{frames, out, support, QuadLaunch{}, npairs, tw, tau, alpha, beta, fb, quad_vec(w, out), quad_vec(w, support)};
 }
 
 hipError_t launch_trajfilter_frames(const uint8_t* frames, const float* flow_fw, const float* flow_rev, uint8_t* out,
                                     uint8_t* support, int npairs, int w, int h, int noc, const TrajWeights& tw, float tau,
                                     bool fb, float alpha, float beta, hipStream_t s) {
   const float2 *ff = (const float2*)flow_fw, *fr = (const float2*)flow_rev;
-  return traj_chunks(frames, out, support, npairs, w, h, tw, tau, fb, alpha, beta, [&](const TrajArgs& a, dim3 blocks) {
+  TrajArgs a = traj_args(frames, out, support, npairs, w, tw, tau, fb, alpha, beta);
+  return quad_chunks(npairs + 1, w, h, [&](const QuadLaunch& q, dim3 blocks) {
+    a.q = q;
     if (noc == 3)
       hipLaunchKernelGGL(trajfilter_frames_kernel<3>, blocks, dim3(256), 0, s, ff, fr, w, h, a);
     else
       hipLaunchKernelGGL(trajfilter_frames_kernel<1>, blocks, dim3(256), 0, s, ff, fr, w, h, a);
+    return hipGetLastError();
   });
 }
 
@@ -219,11 +176,14 @@ hipError_t launch_trajfilter_level(const uint8_t* frames, const float* fw, const
                                    int npairs, UpGeom ug, int noc, const TrajWeights& tw, float tau, bool fb, float alpha,
                                    float beta, hipStream_t s) {
   const float2 *ff = (const float2*)fw, *fr = (const float2*)rev;
-  return traj_chunks(frames, out, support, npairs, ug.wo, ug.ho, tw, tau, fb, alpha, beta, [&](const TrajArgs& a, dim3 blocks) {
+  TrajArgs a = traj_args(frames, out, support, npairs, ug.wo, tw, tau, fb, alpha, beta);
+  return quad_chunks(npairs + 1, ug.wo, ug.ho, [&](const QuadLaunch& q, dim3 blocks) {
+    a.q = q;
     if (noc == 3)
       hipLaunchKernelGGL(trajfilter_level_kernel<3>, blocks, dim3(256), 0, s, ff, fr, ug, a);
     else
       hipLaunchKernelGGL(trajfilter_level_kernel<1>, blocks, dim3(256), 0, s, ff, fr, ug, a);
+    return hipGetLastError();
   });
 }
 

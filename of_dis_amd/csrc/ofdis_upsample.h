@@ -2,11 +2,13 @@
 // ofdis_interp.hip, ofdis_stereo_lr.hip, ofdis_track.hip, ofdis_dense_tracks.hip, ofdis_tfilter.hip and ofdis_trajfilter.hip: the arithmetic of the level flow to full resolution (run_dense.cpp:406-414, UpGeom
 // in ofdis_kernels.h), the forward-backward consistency test and the compact output encodings (include/ofdis.h:
 // ofdis_encoding).  These units are compiled with -ffp-contract=off only and every finish kernel takes its values from the
-// helpers below -- upsample_h, up_row / up_group, up_mix -- so every one of them computes the same bits.
+// helpers below -- upsample_h, up_row / up_group, up_mix -- so every one of them computes the same bits.  How the quad kernels
+// among them map lanes to pixels, walk the frames and store their bytes is ofdis_quad.h, included here.
 #pragma once
 #include <algorithm>
 
 #include "ofdis_kernels.h"
+#include "ofdis_quad.h"
 
 namespace ofdis {
 
@@ -206,26 +208,6 @@ __device__ __forceinline__ void interp_sample(const uint8_t* __restrict__ I, int
     const float i10 = (float)r1[x0 * noc + ch], i11 = (float)r1[x1 * noc + ch];
     c[ch] = (i00 * bx + i01 * ax) * by + (i10 * bx + i11 * ax) * ay;
   }
-}
-
-// The launch geometry of the kernels in which one lane owns a quad of 4 adjacent pixels of one row of one frame
-// (ofdis_interp.hip, ofdis_tfilter.hip, ofdis_trajfilter.hip, ofdis_gmotion.hip, ofdis_stabilize.hip).  Blocks of 256 quads
-// per frame, and the frames of one launch: a launch covers at most QUAD_MAX_BLOCKS = 2^22 blocks (2^30 lanes; ofdis_kernels.h),
-// a multiple of 8 frames where it can (xcd_frame_map), and the launcher walks the frames in such chunks.
-struct QuadGrid {
-  int bpf, chunk;
-};
-inline QuadGrid quad_grid(int nframes, int w, int h) {
-  QuadGrid g;
-  g.bpf = (int)(((long long)((w + 3) >> 2) * h + 255) / 256);
-  long long c = quad_max_blocks() / g.bpf;
-  if (c >= 8) c &= ~7ll;
-  g.chunk = (int)std::max(1ll, std::min(c, (long long)nframes));
-  return g;
-}
-inline unsigned quad_blocks(int frames, int bpf) {
-  const long long fr = frames < 8 ? frames : (frames + 7) / 8 * 8;
-  return (unsigned)(fr * bpf);
 }
 
 // ------------------------------------------------------------------------------------ compact output encodings

@@ -46,13 +46,28 @@ HOOK void ofdis_test_set_launch_limits(long long quad_max_blocks, long long grid
   test_quad_max_blocks = quad_max_blocks > 0 ? quad_max_blocks : QUAD_MAX_BLOCKS;
   test_grid_max_blocks = grid_max_blocks > 0 ? grid_max_blocks : GRID_MAX_BLOCKS;
 }
-// host only, needs no GPU: quad_grid, quad_blocks, grid_for and xcd_frame_map for workgroups [n0, n0 + count)
+// host only, needs no GPU: quad_grid, quad_blocks, quad_chunks, grid_for and xcd_frame_map for workgroups [n0, n0 + count)
 HOOK void ofdis_test_quad_grid(int nframes, int w, int h, int* bpf, int* chunk) {
   const QuadGrid g = quad_grid(nframes, w, h);
   *bpf = g.bpf;
   *chunk = g.chunk;
 }
 HOOK unsigned ofdis_test_quad_blocks(int frames, int bpf) { return quad_blocks(frames, bpf); }
+// quad_chunks with a callback that records instead of launching: (f0, n, workgroups) of the first `cap` launches into
+// walk[cap][3]; returns the number of launches, -1 for an error
+HOOK int ofdis_test_quad_chunks(int nframes, int w, int h, int cap, int* walk) {
+  int count = 0;
+  const hipError_t e = quad_chunks(nframes, w, h, [&](const QuadLaunch& q, dim3 blocks) {
+    if (count < cap) {
+      walk[3 * count] = q.f0;
+      walk[3 * count + 1] = q.n;
+      walk[3 * count + 2] = (int)blocks.x;
+    }
+    ++count;
+    return hipSuccess;
+  });
+  return e == hipSuccess ? count : -1;
+}
 HOOK unsigned ofdis_test_grid_for(long long total) { return grid_for(total); }
 HOOK void ofdis_test_xcd_frame_map(int n0, int count, int blocks_per_frame, int nframes, int* frame, int* blk) {
   for (int i = 0; i < count; ++i) xcd_frame_map(n0 + i, blocks_per_frame, nframes, frame[i], blk[i]);

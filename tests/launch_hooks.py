@@ -47,6 +47,7 @@ def hooks():
     L.ofdis_test_set_launch_limits.argtypes, L.ofdis_test_set_launch_limits.restype = [_LL, _LL], None
     L.ofdis_test_quad_grid.argtypes, L.ofdis_test_quad_grid.restype = [_I, _I, _I, C.POINTER(_I), C.POINTER(_I)], None
     L.ofdis_test_quad_blocks.argtypes, L.ofdis_test_quad_blocks.restype = [_I, _I], C.c_uint
+    L.ofdis_test_quad_chunks.argtypes, L.ofdis_test_quad_chunks.restype = [_I, _I, _I, _I, _VP], _I
     L.ofdis_test_grid_for.argtypes, L.ofdis_test_grid_for.restype = [_LL], C.c_uint
     L.ofdis_test_xcd_frame_map.argtypes, L.ofdis_test_xcd_frame_map.restype = [_I, _I, _I, _I, _VP, _VP], None
     L.ofdis_test_gmotion_work_bytes.argtypes, L.ofdis_test_gmotion_work_bytes.restype = [_I, _I, _I], _SZ
@@ -93,14 +94,12 @@ def xcd_frame_map(nblocks, bpf, nframes):
 
 
 def chunk_walk(nframes, w, h):
-    """the launches of one call as the launchers make them: [(f0, n, workgroups)] with f0 += chunk, n = min(chunk, nframes - f0)"""
-    bpf, chunk = quad_grid(nframes, w, h)
-    walk, f0 = [], 0
-    while f0 < nframes:
-        n = min(chunk, nframes - f0)
-        walk.append((f0, n, quad_blocks(n, bpf)))
-        f0 += chunk
-    return bpf, walk
+    """the launches of one call, recorded from the launchers' own loop (quad_chunks, ofdis_quad.h): bpf and [(f0, n, workgroups)]"""
+    bpf, _ = quad_grid(nframes, w, h)
+    walk = np.empty((nframes, 3), np.int32)   # (a chunk has at least one frame)
+    count = hooks().ofdis_test_quad_chunks(nframes, w, h, nframes, walk.ctypes.data)
+    assert 0 <= count <= nframes, f"ofdis_test_quad_chunks: {count}"
+    return bpf, [tuple(int(v) for v in row) for row in walk[:count]]
 
 
 def trips(total):

@@ -164,6 +164,25 @@ def test_end_times_return_the_frames(gpu, noc):
         assert_u8_equal(got[:, 1], B, "t = 1")
 
 
+@pytest.mark.parametrize("noc", [1, 3])
+@pytest.mark.parametrize("w,h", [(64, 16), (37, 11)], ids=["64x16", "37x11"])
+def test_unaligned_out_takes_byte_stores_with_the_same_bytes(gpu, noc, w, h):
+    """out one byte into its buffer: the same bytes as the aligned call, and the guard bytes around it stay.  64x16: rows a
+    multiple of 4 pixels, so the alignment alone decides the store; 37x11: an odd width with a ragged last quad."""
+    n, guard, times = 3, 257, [0.25, 0.5]   # (the array starts at byte 257 of its buffer: 1 mod 4)
+    A, B, F01, F10, M01, M10 = _random_case(np.random.default_rng(900 + w + noc), n, w, h, noc, "smooth")
+    want = gpu.interpolate(A, B, F01, F10, times, M01, M10)
+    t = np.asarray(times, _f32)
+    do = gpu.Dev(np.full(want.nbytes + 2 * guard, 0xAB, np.uint8))
+    devs = [gpu.Dev(x) for x in (A, B, F01, F10, M01, M10)]
+    gpu.check(gpu.lib().ofdis_interpolate(*[d.ptr for d in devs], do.ptr + guard, n, w, h, noc, t.ctypes.data_as(gpu.FP), t.size,
+                                          None))
+    gpu.check(gpu.lib().ofdis_sync(None))
+    o = do.get((want.nbytes + 2 * guard,), np.uint8)
+    assert (o[:guard] == 0xAB).all() and (o[guard + want.nbytes:] == 0xAB).all()
+    assert_u8_equal(o[guard:guard + want.nbytes].reshape(want.shape), want, "out, one byte off")
+
+
 @pytest.mark.parametrize("d", [(4, -2), (-6, 3), (2, 0)])
 def test_integer_translation(gpu, d):
     """F01 = d, F10 = -d: the output at t is A shifted by t*d wherever t*d is integral and the sample is inside"""

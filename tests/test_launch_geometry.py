@@ -1,10 +1,11 @@
-"""The launch geometry of the post-processing kernels on the host (no GPU): quad_grid / quad_blocks (ofdis_upsample.h) and
-xcd_frame_map (ofdis_dev.h) through the test library, whose two launch limits a test can lower (tests/launch_hooks.py).
+"""The launch geometry of the post-processing kernels on the host (no GPU): quad_grid / quad_blocks / quad_chunks (ofdis_quad.h)
+and xcd_frame_map (ofdis_dev.h) through the test library, whose two launch limits a test can lower (tests/launch_hooks.py).
 
 The launchers of ofdis_interp / tfilter / trajfilter / gmotion / stabilize walk the frames of a call in chunks of at most
-QUAD_MAX_BLOCKS workgroups, and their kernels turn a workgroup index into (frame of the chunk, block of the frame) with
-xcd_frame_map.  Walked here exactly as they do it, every (frame, block) of the clip must come up exactly once: for one launch
-and for many, for chunks below 8 frames (consecutive blocks) and from 8 (the XCD mapping with its padded last group)."""
+QUAD_MAX_BLOCKS workgroups (quad_chunks), and their kernels turn a workgroup index into (frame of the chunk, block of the
+frame) with xcd_frame_map.  Walked here by that loop itself, with a callback that records instead of launching, every (frame,
+block) of the clip must come up exactly once: for one launch and for many, for chunks below 8 frames (consecutive blocks) and
+from 8 (the XCD mapping with its padded last group)."""
 import numpy as np
 import pytest
 
