@@ -475,6 +475,106 @@ int ofdis_batch_dense_tracks(ofdis_batch* b, const uint8_t* frames, int first_fr
                              void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Track selection: the stage of Wang et al.'s pipeline between tracking and description.  Every slot of ofdis_dense_tracks is
+ * classified -- too short, not finite, static, erratic, one dominating jump and, for the "improved" trajectories (Wang and
+ * Schmid, "Action recognition with improved trajectories", 2013), moving only as the camera does -- and the kept slots are
+ * compacted, in their order, into a fresh (tracks, start, len, info) set of the same layout.  Every later stage
+ * (ofdis_track_descriptors, ofdis_track_bof, ofdis_codebook_*) reads ntracks from the device `info` array and pays per slot, so
+ * it takes the selected set unchanged and is cheaper in proportion.  Everything is enqueued on `stream`; nothing synchronises
+ * with the host, and nkept never reaches it.
+ *
+ * Inputs: the arrays of ofdis_dense_tracks.  tracks [lmax+1][max_tracks][2] fp32, start, len [max_tracks] int32, info = the
+ * device array {ntracks, dropped}; n = min(info[0], max_tracks) slots are looked at.  Optionally models [npairs][6] fp64 exactly
+ * as ofdis_global_motion writes them, with the frame size W x H they refer to; pair k of the models is pair k of the clip the
+ * tracks were made on (start counts from the same frame).
+ *
+ * Quantities, per slot i < n with L = clamp(len[i], 0, lmax+1) and (x_j, y_j) = tracks[j][i].  Every float operation is a
+ * separately rounded fp32 operation, every sum is sequential over ascending j starting from 0.0f, sqrtf and / are IEEE.  A
+ * "maximum" starts from 0.0f and takes m_j where m_j > maximum, so it passes over a NaN.
+ *   mean    mx = (sum over j < L of x_j) / (float)L;  my likewise
+ *   spread  sx = sqrtf((sum over j < L of (x_j - mx)*(x_j - mx)) / (float)L);  sy likewise
+ *   step    for j < L-1: d_j = tracks[j+1][i] - tracks[j][i] = (dx, dy), m_j = sqrtf(dx*dx + dy*dy);
+ *           S = the sum of the m_j, mmax = their maximum
+ *   residual step (models given), under the model a_0 .. a_5 of pair k = start[i] + j:
+ *           af_n = (float)a_n;  xc = x_j - (float)(W-1)*0.5f;  yc = y_j - (float)(H-1)*0.5f
+ *           mu = (af0 + af1*xc) + af2*yc;  mv = (af3 + af4*xc) + af5*yc;  r_j = (dx - mu, dy - mv) = (rx, ry)
+ *           rm_j = sqrtf(rx*rx + ry*ry);  Sr = the sum of the rm_j, rmax = their maximum
+ *           A k outside 0 .. npairs-1 makes the slot OFDIS_TS_INVALID; where that test is switched off such a step has r_j = d_j.
+ *           Without models r_j = d_j, Sr = S.
+ * The code of a slot is the FIRST test that holds, in this order; 0 (OFDIS_TS_KEPT) where none does.  A NaN in a comparison
+ * gives false, as elsewhere in this header.
+ *   1 OFDIS_TS_SHORT    L < max(min_len, 1)
+ *   2 OFDIS_TS_INVALID  one of the L positions has a component that is not finite, or a step has no model (above)
+ *   3 OFDIS_TS_STATIC   sx < min_std && sy < min_std
+ *   4 OFDIS_TS_ERRATIC  sx > max_std || sy > max_std
+ *   5 OFDIS_TS_JUMP     L >= 2 && mmax > max_step && mmax > S * max_step_share
+ *   6 OFDIS_TS_CAMERA   models != NULL && L >= 2 && rmax <= min_camera
+ * Bit (code - 1) of `tests` switches a test on; a cleared bit skips it, and the slot goes on to the next test.
+ *
+ * Outputs.  code [max_tracks] u8 or NULL: the code of every slot < n.  counts [7] int64 or NULL: the slots per code, kept ones
+ * (counts[0]) included.  The compacted set, with its own stride max_tracks_out and the same lmax: tracks_out
+ * [lmax+1][max_tracks_out][2], start_out, len_out [max_tracks_out], info_out = {nkept_written, dropped_out}, index
+ * [max_tracks_out] int32 or NULL, shape_out [max_tracks_out][lmax][2] fp32 or NULL.
+ *   Output slot r is the r-th kept input slot (the order is kept), index[r] its input slot.  All lmax+1 entries of the track
+ *   are copied bit for bit, the NaN tail beyond len included; start and len are copied.
+ *   nkept_written = min(nkept, max_tracks_out), dropped_out = nkept - nkept_written: kept slots beyond max_tracks_out are not
+ *   written.
+ *   shape_out[r][j] = (rx / Sr, ry / Sr) of r_j for j < L-1; (0, 0) when Sr == 0 and for j >= L-1.  With models this is the
+ *   camera-compensated trajectory shape; without, it is d_j / S, bit-identical to what ofdis_track_descriptors writes as
+ *   `shape` for the same track.  Where a non-finite position was kept (OFDIS_TS_INVALID switched off) a NaN entry has no defined
+ *   payload.
+ *   Only output slots < nkept_written are written, every entry of them exactly once; only code entries < n are written; counts
+ *   and info_out are written whole.  The call relies on no memset and reads nothing of the input slots >= n.  The outputs must not
+ *   overlap the inputs or each other: nothing checks it.
+ *
+ * Consequences.
+ *   Drop-in: ofdis_track_descriptors and ofdis_track_bof on the selected set give rows index[r] of the same calls on the
+ *     original set.
+ *   Identity: with tests == 0 and max_tracks_out >= n the selected set equals the first n slots of the input, index[r] == r.
+ *   Sums: counts sums to n; counts[0] == nkept_written + dropped_out.
+ *   Known values: a track that stands still is OFDIS_TS_STATIC; L positions one pixel apart along an axis have the
+ *     spread sqrt((L*L - 1) / 12), above sqrt(3) from L = 7 on; a track whose steps equal a translation model has every rm_j == 0 and
+ *     is OFDIS_TS_CAMERA with the model, kept without it.
+ *   Contract independence: one unit, compiled once with every operation separately rounded, serves both contracts.
+ * Improved trajectories on an OFDIS_BATCH_SEQUENCE context: ofdis_batch_dense_tracks -> ofdis_batch_global_motion -> this call
+ * -> ofdis_batch_upsample_bidir and, for the residual flow HOF and MBH are made of, ofdis_batch_motion_compensate ->
+ * ofdis_track_descriptors on the selected set -> ofdis_track_bof.  The tracks follow the full flow; the camera models change
+ * what is selected and what the descriptors see.  No context form is needed: no argument here belongs to a context.
+ * Not provided: homography models and RANSAC (the models are those of ofdis_global_motion); a bag-of-features channel for the
+ * shape.  of_dis_amd/tracking.py states the same definition in numpy (track_select_ref).
+ * ------------------------------------------------------------------------------------------- */
+enum { OFDIS_TS_KEPT = 0, OFDIS_TS_SHORT = 1, OFDIS_TS_INVALID = 2, OFDIS_TS_STATIC = 3, OFDIS_TS_ERRATIC = 4, OFDIS_TS_JUMP = 5,
+       OFDIS_TS_CAMERA = 6 };
+#define OFDIS_TS_ALL_TESTS 0x3Fu
+typedef struct ofdis_track_select_params {
+  int min_len;           /* 0 */
+  float min_std;         /* 1.7320508f = sqrtf(3), Wang's value */
+  float max_std;         /* 50 */
+  float max_step;        /* 20 */
+  float max_step_share;  /* 0.7f */
+  float min_camera;      /* 1 */
+  unsigned tests;        /* OFDIS_TS_ALL_TESTS */
+} ofdis_track_select_params;
+/* the values above; a NULL p is ignored */
+void ofdis_track_select_defaults(ofdis_track_select_params* p);
+/* bytes of the work buffer: one 64-byte record (the counts per code, the kept slots before it, the kept lanes) per 256 slots;
+ * 0 for max_tracks outside 1 .. OFDIS_DT_MAX_TRACKS */
+size_t ofdis_track_select_work_bytes(int max_tracks);
+/* device arrays as above; p is read on the host.  Three launches: classify (one lane per slot; one record per workgroup into
+ * `work`, plain stores), scan (one workgroup: the offsets of the workgroups, info_out, counts), scatter (the kept lanes copy).
+ * No atomics, no waiting between workgroups.  OFDIS_ERR_INVALID before any device work: a NULL tracks, start, len, info, p,
+ * tracks_out, start_out, len_out, info_out or work; lmax < 1; max_tracks or max_tracks_out outside 1 .. OFDIS_DT_MAX_TRACKS;
+ * models given with npairs < 1, with sizes ofdis_fb_check rejects or a side above OFDIS_GM_MAX_SIDE; min_std, max_std, max_step
+ * or min_camera NaN or negative (+infinity is accepted for max_std and max_step only); max_step_share outside [0, 1];
+ * min_len < 0; bits of tests outside OFDIS_TS_ALL_TESTS; a work buffer smaller than ofdis_track_select_work_bytes(max_tracks) or
+ * not 8-byte aligned. */
+int ofdis_track_select(const float* tracks, const int* start, const int* len, const long long* info, int lmax, int max_tracks,
+                       const double* models /* or NULL */, int npairs, int width, int height,
+                       const ofdis_track_select_params* p, uint8_t* code /* or NULL */, long long* counts /* or NULL */,
+                       int max_tracks_out, float* tracks_out, int* start_out, int* len_out, long long* info_out,
+                       int* index /* or NULL */, float* shape_out /* or NULL */, void* work, size_t work_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Trajectory-aligned descriptors of dense tracks: in the space-time tube around every track of ofdis_dense_tracks the histograms
  * of gradient orientation (HOG), of flow orientation (HOF) and of the motion boundaries (MBHx, MBHy: the orientation of the
  * gradient of each flow component), and the track's normalised displacements (trajectory shape) -- the second half of Wang,
@@ -525,7 +625,7 @@ int ofdis_batch_dense_tracks(ofdis_batch* b, const uint8_t* frames, int first_fr
  *   Contract independence: integer sums of separately rounded values; one unit, compiled once, serves both contracts.
  * Not provided: interpolation of a vote between neighbouring bins; normalisation in floating point (of_dis_amd/tracking.py:
  * normalize_descriptors, on the host -- the 8-bit RootSIFT form on the device and the bag of features made of it are the next
- * section, ofdis_descriptor_normalize .. ofdis_track_bof); filtering of static or erratic tracks; a form that reads a sequence context's level
+ * section, ofdis_descriptor_normalize .. ofdis_track_bof); a form that reads a sequence context's level
  * flows directly -- every window pixel needs five flow values and is visited by about 40 overlapping windows, and rebuilding
  * flow values from level flows already loses when each is used a handful of times (README: trajectory filter, global motion).
  * The route is ofdis_batch_upsample_bidir -> ofdis_dense_tracks -> this call.
@@ -587,8 +687,8 @@ int ofdis_track_descriptors(const uint8_t* frames, const float* flow_fw, int npa
  *     drawn from the descriptors themselves gives dist 0 and the first copy.
  *   Sums: every row of bof sums to the number of counted tracks; the four rows have the same sum.
  *   Contract independence: integers only; one unit, compiled once, serves both contracts.
- * Not provided: Fisher vectors; the shape channel (floats: it is not encoded); filtering of static tracks.  The codebook
- * itself comes from the k-means training of the next section (ofdis_codebook_seed, ofdis_codebook_train) or from the caller.
+ * Not provided: Fisher vectors; the shape channel (floats: it is not encoded).  Taking out static tracks, and erratic and
+ * camera-only ones, comes before this stage: ofdis_track_select.  The codebook itself comes from the k-means training of the next section (ofdis_codebook_seed, ofdis_codebook_train) or from the caller.
  * The route is ofdis_dense_tracks -> ofdis_track_descriptors -> ofdis_track_bof.  None of the calls
  * synchronises with the host.  of_dis_amd/tracking.py states the same definitions in numpy (normalize_descriptors_u8,
  * codebook_assign_ref, bof_ref).

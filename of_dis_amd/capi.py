@@ -44,6 +44,7 @@ ABI_SYMBOLS = [
     "ofdis_track_points", "ofdis_batch_track_points",
     "ofdis_dense_tracks_cells", "ofdis_dense_tracks_work_bytes", "ofdis_seed_texture", "ofdis_dense_tracks",
     "ofdis_batch_dense_tracks",
+    "ofdis_track_select_defaults", "ofdis_track_select_work_bytes", "ofdis_track_select",
     "ofdis_track_descriptor_dims", "ofdis_track_descriptors",
     "ofdis_descriptor_normalize", "ofdis_codebook_assign", "ofdis_bof_histogram", "ofdis_track_bof",
     "ofdis_codebook_train_work_bytes", "ofdis_codebook_seed", "ofdis_codebook_update", "ofdis_codebook_train",
@@ -64,6 +65,9 @@ INTERP_MAX_TIMES = 16  # OFDIS_INTERP_MAX_TIMES
 ENC_F32, ENC_F16, ENC_U16, ENC_U8 = 0, 1, 2, 3  # OFDIS_ENC_*
 TRACK_MAX_POINTS = 1 << 24  # OFDIS_TRACK_MAX_POINTS
 DT_MAX_TRACKS, DT_MAX_STRIDE, DT_MAX_WINDOW = 1 << 24, 64, 7  # OFDIS_DT_MAX_*
+TS_KEPT, TS_SHORT, TS_INVALID, TS_STATIC, TS_ERRATIC, TS_JUMP, TS_CAMERA = range(7)  # OFDIS_TS_*
+TS_ALL_TESTS = 0x3F  # OFDIS_TS_ALL_TESTS
+TRACK_SELECT_LANES = 256  # csrc/ofdis_track_select.hip: kTsLanes, the slots of a workgroup and the records of a trip of its scan
 DESC_MAX_PATCH = 64  # OFDIS_DESC_MAX_PATCH
 BOF_SCALE, BOF_MAX_WORDS = 510, 16384  # OFDIS_BOF_*
 KMEANS_MAX_ITERS = 1000  # OFDIS_KMEANS_MAX_ITERS
@@ -101,6 +105,27 @@ class Encoding(C.Structure):
 
     def __repr__(self):
         return f"Encoding(type={self.type}, scale={self.scale!r}, offset={self.offset!r})"
+
+
+class TrackSelectParams(C.Structure):
+    """include/ofdis.h: ofdis_track_select_params.  TrackSelectParams() holds the defaults (ofdis_track_select_defaults);
+    keywords replace single values.  of_dis_amd/tracking.py has the numpy counterpart of the same name."""
+    _fields_ = [("min_len", C.c_int), ("min_std", C.c_float), ("max_std", C.c_float), ("max_step", C.c_float),
+                ("max_step_share", C.c_float), ("min_camera", C.c_float), ("tests", C.c_uint)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().ofdis_track_select_defaults(C.byref(self))
+        for k, v in kw.items():
+            assert k in dict(self._fields_), k
+            setattr(self, k, v)
+
+    @classmethod
+    def of(cls, params):
+        """None (the defaults), a TrackSelectParams of this module or of tracking.py"""
+        if params is None or isinstance(params, cls):
+            return params or cls()
+        return cls(**{k: getattr(params, k) for k, _ in cls._fields_})
 
 
 class OfdisError(RuntimeError):
@@ -227,6 +252,12 @@ def lib():
                                          C.c_float, C.c_float, C.c_int, VP, VP, VP, VP, VP, C.c_size_t, VP]
         L.ofdis_batch_dense_tracks.argtypes = [VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                                C.c_float, C.c_int, VP, VP, VP, VP, C.c_int, C.c_int, VP]
+        L.ofdis_track_select_defaults.restype = None
+        L.ofdis_track_select_defaults.argtypes = [VP]
+        L.ofdis_track_select_work_bytes.restype = C.c_size_t
+        L.ofdis_track_select_work_bytes.argtypes = [C.c_int]
+        L.ofdis_track_select.argtypes = [VP, VP, VP, VP, C.c_int, C.c_int, VP, C.c_int, C.c_int, C.c_int, VP, VP, VP, C.c_int, VP, VP,
+                                         VP, VP, VP, VP, VP, C.c_size_t, VP]
         L.ofdis_track_descriptor_dims.argtypes = [C.c_int, C.c_int, C.c_int]
         L.ofdis_track_descriptors.argtypes = [VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int,
                                               C.c_int, C.c_int, C.c_float, VP, VP, VP]
@@ -703,6 +734,61 @@ def dense_tracks(frames, flow_fw, flow_rev, stride, window, min_eig, max_len=15,
                                    dwork.ptr, wb, None))
     check(lib().ofdis_sync(None))
     return _dense_results(outs, lmax, max_tracks)
+
+
+def track_select_work_bytes(max_tracks):
+    """ofdis_track_select_work_bytes: the work buffer of track_select_dev; 0 for rejected sizes."""
+    return lib().ofdis_track_select_work_bytes(max_tracks)
+
+
+def track_select_dev(tracks_ptr, start_ptr, len_ptr, info_ptr, lmax, max_tracks, max_tracks_out, tracks_out_ptr, start_out_ptr,
+                     len_out_ptr, info_out_ptr, work_ptr, work_bytes, models_ptr=None, npairs=0, width=0, height=0, params=None,
+                     code_ptr=None, counts_ptr=None, index_ptr=None, shape_out_ptr=None, stream=None):
+    """ofdis_track_select on device pointers: the arrays ofdis_dense_tracks wrote stay where they are; the selected set
+    (tracks_out [lmax + 1][max_tracks_out][2], start_out, len_out [max_tracks_out], info_out [2]) has the same layout and feeds
+    track_descriptors_dev, track_bof_dev and codebook_train_dev unchanged.  models [npairs][6] float64 of a width x height
+    clip, code [max_tracks] uint8, counts [7] int64, index [max_tracks_out] int32 and shape_out [max_tracks_out][lmax][2] are
+    optional.  Enqueues on `stream` and returns; nothing synchronises with the host."""
+    p = TrackSelectParams.of(params)
+    check(lib().ofdis_track_select(tracks_ptr, start_ptr, len_ptr, info_ptr, lmax, max_tracks, models_ptr, npairs, width, height,
+                                   C.byref(p), code_ptr, counts_ptr, max_tracks_out, tracks_out_ptr, start_out_ptr, len_out_ptr,
+                                   info_out_ptr, index_ptr, shape_out_ptr, work_ptr, work_bytes, stream))
+
+
+def track_select(tracks, start, length, models=None, size=None, params=None, max_out=None, shape=True):
+    """ofdis_track_select on host arrays: tracks [Lmax + 1, ntracks, 2], start, length [ntracks] as dense_tracks returns them;
+    models float64 [npairs, 6] as global_motion returns them with size = (width, height) of their frames, or None; params a
+    TrackSelectParams (None: the defaults); max_out the slots of the output set (None: room for every track) -> (code uint8
+    [ntracks], counts int64 [7], tracks_out [Lmax + 1, nkept, 2], start_out, len_out int32 [nkept], info_out int64 [2] =
+    (nkept written, dropped), index int32 [nkept], shape_out float32 [nkept, Lmax, 2] or None with shape=False): the outputs
+    cut to the slots the call wrote.  of_dis_amd/tracking.py: track_select_ref is the numpy statement of the same definition."""
+    tracks = _f(tracks)
+    assert tracks.ndim == 3 and tracks.shape[0] >= 2 and tracks.shape[2] == 2, tracks.shape
+    lmax, n = tracks.shape[0] - 1, tracks.shape[1]
+    start, length = np.ascontiguousarray(start, np.int32), np.ascontiguousarray(length, np.int32)
+    assert start.shape == length.shape == (n,), (start.shape, length.shape, n)
+    slots = max(n, 1)  # (the library takes no empty array)
+    out = slots if max_out is None else int(max_out)
+    dm, npairs, w, h = None, 0, 0, 0
+    if models is not None:
+        models = np.ascontiguousarray(models, np.float64).reshape(-1, 6)
+        dm, npairs, (w, h) = Dev(models), len(models), size
+    dt = Dev(tracks if n else np.zeros((lmax + 1, 1, 2), _f32))
+    ds, dl = (Dev(a if n else np.zeros(1, np.int32)) for a in (start, length))
+    di = Dev(np.array([n, 0], np.int64))
+    dcode, dcounts = Dev(nbytes=slots), Dev(nbytes=56)
+    outs = _dense_outputs(lmax, max(out, 1))
+    dindex, dshape = Dev(nbytes=max(out, 1) * 4), Dev(nbytes=max(out, 1) * lmax * 8) if shape else None
+    wb = track_select_work_bytes(slots)
+    dwork = Dev(nbytes=max(8, wb))
+    track_select_dev(dt.ptr, ds.ptr, dl.ptr, di.ptr, lmax, slots, out, outs[0].ptr, outs[1].ptr, outs[2].ptr, outs[3].ptr,
+                     dwork.ptr, wb, dm.ptr if dm else None, npairs, w, h, params, dcode.ptr, dcounts.ptr, dindex.ptr,
+                     dshape.ptr if dshape else None)
+    check(lib().ofdis_sync(None))
+    tracks_out, start_out, len_out, info = _dense_results(outs, lmax, out)
+    k = int(info[0])
+    return (dcode.get((slots,), np.uint8)[:n].copy(), dcounts.get((7,), np.int64), tracks_out, start_out, len_out, info,
+            dindex.get((out,), np.int32)[:k].copy(), dshape.get((out, lmax, 2), _f32)[:k].copy() if dshape else None)
 
 
 def track_descriptor_dims(patch, nxy, nt):

@@ -278,6 +278,16 @@ hipError_t launch_dense_tracks(const uint8_t* frames, const float* fw, const flo
 hipError_t launch_dense_tracks_level(const uint8_t* frames, const float* fw, const float* rev, int npairs, UpGeom g, int noc,
                                      int stride, int window, int min_eig, int max_len, float alpha, float beta, int max_tracks,
                                      float* tracks, int* start, int* len, long long* info, void* work, hipStream_t s);
+// track selection (include/ofdis.h: ofdis_track_select; ofdis_track_select.hip): the arrays of launch_dense_tracks in, code
+// [max_tracks] u8 and counts [7] (either may be null) and the compacted set of max_tracks_out slots out -- tracks_out, start_out,
+// len_out, info_out [2], index [max_tracks_out] and shape_out [max_tracks_out][lmax][2] (either may be null); models [npairs][6]
+// of launch_gmotion_frames for a w x h frame, or null.  Three launches (classify, scan, scatter); work holds
+// track_select_work_bytes(max_tracks): one 64-byte record per workgroup, 8-byte aligned
+size_t track_select_work_bytes(int max_tracks);
+hipError_t launch_track_select(const float* tracks, const int* start, const int* len, const long long* info, int lmax, int max_tracks,
+                               const double* models, int npairs, int w, int h, const ofdis_track_select_params& p, uint8_t* code,
+                               long long* counts, int max_tracks_out, float* tracks_out, int* start_out, int* len_out,
+                               long long* info_out, int* index, float* shape_out, void* work, hipStream_t s);
 // trajectory-aligned descriptors (include/ofdis.h: ofdis_track_descriptors; ofdis_descriptors.hip): the arrays of
 // launch_dense_tracks in, hist [max_tracks][33 nxy^2 nt] u32 and shape [max_tracks][lmax][2] (or null) out; one wavefront per
 // slot, the slots >= info[0] return at once

@@ -1,5 +1,5 @@
 // ofdis_products.hip -- what is made from a context's flows, and the same steps on caller-supplied arrays: the full-resolution
-// finish and its encodings, forward-backward and left-right checks, interpolation, point and dense trajectories, descriptors,
+// finish and its encodings, forward-backward and left-right checks, interpolation, point and dense trajectories, their selection, descriptors,
 // their bag-of-features encoding and the training of its codebook, the temporal filters, global motion and stabilisation.
 // Every entry point validates its arguments, joins the pass (finish_begin) and launches; the checks they share are stated once, below.  Reads no environment.
 #include <cfloat>
@@ -345,6 +345,41 @@ int ofdis_batch_dense_tracks(ofdis_batch* b, const uint8_t* frames, int first_fr
   if (int rc = dstage(b, {{&b->dt_slab, (need + sizeof(float) * b->nframes - 1) / (sizeof(float) * b->nframes)}})) return rc;
   HIPCHK(launch_dense_tracks_level(fin.clip(frames), fin.fw, fin.fb_rev, count, fin.g, b->p.noc, stride, window, min_eig, max_len,
                                    alpha, beta, max_tracks, tracks, start, len, info, b->dt_slab, (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+// ------------------------------------------------------------------------------------ track selection (ofdis_track_select.hip)
+void ofdis_track_select_defaults(ofdis_track_select_params* p) {
+  if (p) *p = ofdis_track_select_params{0, 1.7320508f, 50.0f, 20.0f, 0.7f, 1.0f, OFDIS_TS_ALL_TESTS};
+}
+
+size_t ofdis_track_select_work_bytes(int max_tracks) {
+  return max_tracks >= 1 && max_tracks <= OFDIS_DT_MAX_TRACKS ? track_select_work_bytes(max_tracks) : 0;
+}
+
+int ofdis_track_select(const float* tracks, const int* start, const int* len, const long long* info, int lmax, int max_tracks,
+                       const double* models, int npairs, int width, int height, const ofdis_track_select_params* p, uint8_t* code,
+                       long long* counts, int max_tracks_out, float* tracks_out, int* start_out, int* len_out, long long* info_out,
+                       int* index, float* shape_out, void* work, size_t work_bytes, void* stream) {
+  if (!tracks || !start || !len || !info) return fail(OFDIS_ERR_INVALID, "tracks, start, len or info is NULL");
+  if (!p) return fail(OFDIS_ERR_INVALID, "params is NULL");
+  if (!tracks_out || !start_out || !len_out || !info_out) return fail(OFDIS_ERR_INVALID, "tracks_out, start_out, len_out or info_out is NULL");
+  if (lmax < 1) return fail(OFDIS_ERR_INVALID, "lmax below 1");
+  if (max_tracks < 1 || max_tracks > OFDIS_DT_MAX_TRACKS) return fail(OFDIS_ERR_INVALID, "max_tracks outside 1..OFDIS_DT_MAX_TRACKS");
+  if (max_tracks_out < 1 || max_tracks_out > OFDIS_DT_MAX_TRACKS)
+    return fail(OFDIS_ERR_INVALID, "max_tracks_out outside 1..OFDIS_DT_MAX_TRACKS");
+  if (models && (npairs < 1 || width < 1 || height < 1 || width > OFDIS_GM_MAX_SIDE || height > OFDIS_GM_MAX_SIDE))
+    return fail(OFDIS_ERR_INVALID, "models with bad sizes (npairs < 1, a side above OFDIS_GM_MAX_SIDE?)");
+  if (p->min_len < 0) return fail(OFDIS_ERR_INVALID, "min_len is negative");
+  if (!(p->min_std >= 0.0f) || std::isinf(p->min_std)) return fail(OFDIS_ERR_INVALID, "min_std must be finite and >= 0");
+  if (!(p->max_std >= 0.0f)) return fail(OFDIS_ERR_INVALID, "max_std must be >= 0");
+  if (!(p->max_step >= 0.0f)) return fail(OFDIS_ERR_INVALID, "max_step must be >= 0");
+  if (!(p->max_step_share >= 0.0f && p->max_step_share <= 1.0f)) return fail(OFDIS_ERR_INVALID, "max_step_share outside [0, 1]");
+  if (!(p->min_camera >= 0.0f) || std::isinf(p->min_camera)) return fail(OFDIS_ERR_INVALID, "min_camera must be finite and >= 0");
+  if (p->tests & ~OFDIS_TS_ALL_TESTS) return fail(OFDIS_ERR_INVALID, "tests has bits outside OFDIS_TS_ALL_TESTS");
+  if (int rc = work_check(work, work_bytes, track_select_work_bytes(max_tracks), "ofdis_track_select_work_bytes")) return rc;
+  HIPCHK(launch_track_select(tracks, start, len, info, lmax, max_tracks, models, npairs, width, height, *p, code, counts,
+                             max_tracks_out, tracks_out, start_out, len_out, info_out, index, shape_out, work, (hipStream_t)stream));
   return OFDIS_OK;
 }
 

@@ -2,7 +2,8 @@
 definition operation by operation in float32, one rounding at a time.  Needs numpy only (no GPU, no library): the tests compare
 the kernels against `track_ref` bit for bit, and a user can read a track array with `ended`.  Below it, the dense trajectories
 (ofdis_seed_texture, ofdis_dense_tracks, ofdis_batch_dense_tracks): the grid, the integer texture test and the frame loop of
-advance, occupancy and seeding (`dense_tracks_ref`), and the descriptors of those tracks (ofdis_track_descriptors): HOG, HOF, MBH
+advance, occupancy and seeding (`dense_tracks_ref`), the selection of those tracks (ofdis_track_select): static, erratic, jumping
+and camera-only tracks taken out and the rest compacted (`track_select_ref`, `TrackSelectParams`), and the descriptors of those tracks (ofdis_track_descriptors): HOG, HOF, MBH
 and trajectory shape (`track_descriptors_ref`), where their channels lie (`descriptor_layout`) and their normalisation on the
 host (`normalize_descriptors`).  Last, the bag-of-features encoding (ofdis_descriptor_normalize, ofdis_codebook_assign,
 ofdis_bof_histogram, ofdis_track_bof): 8-bit RootSIFT descriptors, nearest words and their counts, integers throughout
@@ -16,6 +17,7 @@ ofdis_codebook_update, ofdis_codebook_train): evenly spread seeds and Lloyd's al
     T = tracking.min_eig_from_gradient(4.0, window=2, noc=1)                     # mean-tensor eigenvalue 4 -> the test's units
     dtracks, start, length, info = batch.dense_tracks(frames_ptr, w, h, 5, 2, T)  # [Lmax + 1][ntracks][2], step-major
     by_frame = tracking.to_frame_major(dtracks, start, length, n)                # [n + 1][ntracks][2], the layout above
+    code, counts, dtracks, start, length, _, index, _ = capi.track_select(dtracks, start, length, models, (w, h))  # the kept ones
     hist, shape = capi.track_descriptors(frames, flow_fw, dtracks, start, length, 32, 2, 3, 0.4)   # [ntracks][396] u32
     desc = tracking.normalize_descriptors(hist, tracking.descriptor_layout(32, 2, 3), "rootsift")   # float64, per channel
     desc8 = capi.descriptor_normalize(hist, 2, 3)                                 # [ntracks][396] u8
@@ -263,6 +265,113 @@ def to_frame_major(tracks, start, length, npairs):
         i = np.flatnonzero(length > j)
         out[start[i] + j, i] = tracks[j, i]
     return out
+
+
+# ------------------------------------------------------------------ track selection (ofdis_track_select)
+TS_KEPT, TS_SHORT, TS_INVALID, TS_STATIC, TS_ERRATIC, TS_JUMP, TS_CAMERA = range(7)  # include/ofdis.h: OFDIS_TS_*
+TS_NAMES = ("kept", "short", "invalid", "static", "erratic", "jump", "camera")
+TS_ALL_TESTS = 0x3F  # OFDIS_TS_ALL_TESTS
+
+
+class TrackSelectParams:
+    """include/ofdis.h: ofdis_track_select_params with the values of ofdis_track_select_defaults (Wang et al.'s)."""
+
+    def __init__(self, min_len=0, min_std=1.7320508, max_std=50.0, max_step=20.0, max_step_share=0.7, min_camera=1.0,
+                 tests=TS_ALL_TESTS):
+        self.min_len, self.tests = int(min_len), int(tests)
+        self.min_std, self.max_std, self.max_step = _f32(min_std), _f32(max_std), _f32(max_step)
+        self.max_step_share, self.min_camera = _f32(max_step_share), _f32(min_camera)
+
+    def __repr__(self):
+        return (f"TrackSelectParams(min_len={self.min_len}, min_std={self.min_std!r}, max_std={self.max_std!r}, "
+                f"max_step={self.max_step!r}, max_step_share={self.max_step_share!r}, min_camera={self.min_camera!r}, "
+                f"tests={self.tests:#x})")
+
+
+def _track_steps(tracks, start, models, size):
+    """per step j < lmax: (d [n][2], r [n][2], has a model [n]) of the header's "step" and "residual step", float32"""
+    lmax, n = tracks.shape[0] - 1, tracks.shape[1]
+    if models is not None:
+        models = np.asarray(models, np.float64).reshape(-1, 6)
+        af = models.astype(_f32)
+        cx, cy = _f32(size[0] - 1) * _f32(0.5), _f32(size[1] - 1) * _f32(0.5)
+    for j in range(lmax):
+        d = tracks[j + 1] - tracks[j]
+        r, known = d, np.ones(n, bool)
+        if models is not None:
+            k = start + j
+            known = (k >= 0) & (k < len(af))
+            a = af[np.where(known, k, 0)]
+            xc, yc = tracks[j, :, 0] - cx, tracks[j, :, 1] - cy
+            mu = (a[:, 0] + a[:, 1] * xc) + a[:, 2] * yc
+            mv = (a[:, 3] + a[:, 4] * xc) + a[:, 5] * yc
+            r = np.where(known[:, None], np.stack([d[:, 0] - mu, d[:, 1] - mv], 1), d)
+        yield j, d, r, known
+
+
+def track_select_ref(tracks, start, length, models=None, size=None, params=None, max_out=None):
+    """The definition of ofdis_track_select in numpy float32, operation by operation.  tracks [lmax + 1][ntracks][2], start,
+    length [ntracks] as dense_tracks_ref returns them; models float64 [npairs][6] as global_motion returns them with size =
+    (W, H) of their frames, or None; params a TrackSelectParams (None: the defaults); max_out the slots of the output set
+    (None: room for every track) -> (code uint8 [ntracks], counts int64 [7], tracks_out [lmax + 1][nkept_written][2], start_out,
+    len_out int32 [nkept_written], info_out int64 [2] = (nkept_written, dropped_out), index int32 [nkept_written], shape_out
+    float32 [nkept_written][lmax][2])."""
+    t = params if params is not None else TrackSelectParams()
+    tracks = np.ascontiguousarray(tracks, _f32)
+    start, length = np.asarray(start, np.int64), np.asarray(length, np.int64)
+    lmax, n = tracks.shape[0] - 1, tracks.shape[1]
+    assert lmax >= 1 and tracks.shape[2] == 2 and start.shape == length.shape == (n,), (tracks.shape, start.shape, length.shape)
+    assert (models is None) or size is not None
+    L = np.clip(length, 0, lmax + 1)
+    fl = L.astype(_f32)
+    with np.errstate(all="ignore"):
+        finite = np.ones(n, bool)
+        total = np.zeros((n, 2), _f32)
+        for j in range(lmax + 1):
+            on = L > j
+            finite[on] &= np.isfinite(tracks[j, on]).all(1)
+            total[on] = total[on] + tracks[j, on]
+        mean = total / fl[:, None]
+        var = np.zeros((n, 2), _f32)
+        for j in range(lmax + 1):
+            on = L > j
+            e = tracks[j, on] - mean[on]
+            var[on] = var[on] + e * e
+        spread = np.sqrt(var / fl[:, None])
+        S, Sr, mmax, rmax = (np.zeros(n, _f32) for _ in range(4))
+        steps = []
+        for j, d, r, known in _track_steps(tracks, start, models, size):
+            on = L - 1 > j
+            finite[on] &= known[on]
+            m = np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1])
+            rm = np.sqrt(r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1])
+            S[on], Sr[on] = S[on] + m[on], Sr[on] + rm[on]
+            mmax[on] = np.where(m[on] > mmax[on], m[on], mmax[on])
+            rmax[on] = np.where(rm[on] > rmax[on], rm[on], rmax[on])
+            steps.append(r)
+        sx, sy = spread[:, 0], spread[:, 1]
+        holds = [None,
+                 L < max(t.min_len, 1),
+                 ~finite,
+                 (sx < t.min_std) & (sy < t.min_std),
+                 (sx > t.max_std) | (sy > t.max_std),
+                 (L >= 2) & (mmax > t.max_step) & (mmax > S * t.max_step_share),
+                 (L >= 2) & (rmax <= t.min_camera) if models is not None else np.zeros(n, bool)]
+        code = np.zeros(n, np.uint8)
+        for c in range(6, 0, -1):  # the first test that holds: the later ones are overwritten
+            if (t.tests >> (c - 1)) & 1:
+                code[holds[c]] = c
+        counts = np.bincount(code, minlength=7).astype(np.int64)
+        kept = np.flatnonzero(code == 0)
+        room = len(kept) if max_out is None else int(max_out)
+        index = kept[:room].astype(np.int32)
+        shape = np.zeros((len(index), lmax, 2), _f32)
+        for j, r in enumerate(steps):
+            on = (L[index] - 1 > j) & (Sr[index] != 0)
+            shape[on, j] = r[index[on]] / Sr[index[on], None]
+    info = np.array([len(index), len(kept) - len(index)], np.int64)
+    return (code, counts, np.ascontiguousarray(tracks[:, index]), start[index].astype(np.int32), length[index].astype(np.int32),
+            info, index, shape)
 
 
 # ------------------------------------------------------------------ trajectory-aligned descriptors (ofdis_track_descriptors)

@@ -5,7 +5,9 @@ run_DE_* binaries do (run_dense.cpp:185-431), for a list of pairs at once and wi
 
     python tools/flow_images.py [--rgb] [--stereo [--lr [--fill MODE]]] [--op 1..4] [--fused] [--reverse] img1a img1b out1.flo [img2a img2b out2.flo ...]
     python tools/flow_images.py --sequence [--rgb] [--op 1..4] [--fused] [--reverse [--tracks STRIDE]
-                                [--dense-tracks STRIDE[:WINDOW[:MIN_EIG[:MAX_LEN]]] [--descriptors N:NXY:NT:MIN_FLOW]]]
+                                [--dense-tracks STRIDE[:WINDOW[:MIN_EIG[:MAX_LEN]]]
+                                 [--track-select [MIN_LEN[:MIN_STD:MAX_STD:MAX_STEP:SHARE[:MIN_CAMERA]]] [--global-motion]]
+                                 [--descriptors N:NXY:NT:MIN_FLOW]]]
                                 img0 img1 ... imgN stem
 
 All pairs must have one size.  --fused selects the FMA / fast-reciprocal arithmetic contract (default: the exact one, bit for
@@ -29,7 +31,13 @@ track i in frame start[i] + j; NaN beyond its length), <stem>_dstart.npy and <st
 --descriptors N:NXY:NT:MIN_FLOW (needs --dense-tracks) the descriptors of those tracks follow (ofdis_track_descriptors on the
 forward flows the run writes: an N x N window in NXY x NXY x NT cells, flows below MIN_FLOW in HOF's ninth bin):
 <stem>_dhist.npy, uint32 [tracks][33 * NXY^2 * NT] (HOG, HOF, MBHx, MBHy: of_dis_amd/tracking.py descriptor_layout), and
-<stem>_dshape.npy, float32 [tracks][Lmax][2]."""
+<stem>_dshape.npy, float32 [tracks][Lmax][2].  --track-select [MIN_LEN[:MIN_STD:MAX_STD:MAX_STEP:SHARE[:MIN_CAMERA]]] (needs
+--dense-tracks; defaults 0, sqrt(3), 50, 20, 0.7 and 1: ofdis_track_select_defaults) takes out the tracks that are too short, not
+finite, static, erratic or one jump (ofdis_track_select) and, with --global-motion, those that move only as the camera does under
+the clip's affine models (ofdis_batch_global_motion with the forward mask): <stem>_dcode.npy, uint8 [tracks], the code of every
+track (0 kept; of_dis_amd/tracking.py TS_NAMES), and <stem>_dindex.npy, int32 [kept], their slots.  The three track files and
+the descriptors then hold the kept tracks only."""
+import itertools
 import os
 import struct
 import sys
@@ -87,15 +95,20 @@ def write_pgm(path, mask):
 
 
 def main(argv):
-    opts = {"--rgb": False, "--stereo": False, "--fused": False, "--reverse": False, "--lr": False, "--sequence": False}
+    opts = {"--rgb": False, "--stereo": False, "--fused": False, "--reverse": False, "--lr": False, "--sequence": False,
+            "--global-motion": False}
     op = 2
     fill = "none"
     track_stride = 0
     dense = None
     desc = None
+    select = None
     args = []
     it = iter(argv)
-    for a in it:
+    while True:
+        a = next(it, None)
+        if a is None:
+            break
         if a in opts:
             opts[a] = True
         elif a == "--op":
@@ -112,6 +125,16 @@ def main(argv):
             if not 1 <= len(dense) <= 4:
                 sys.exit("--dense-tracks STRIDE[:WINDOW[:MIN_EIG[:MAX_LEN]]]")
             dense += [2, 0, 15][len(dense) - 1:]
+        elif a == "--track-select":        # the values are optional: what follows is one only if it reads as numbers
+            spec = next(it, None)
+            try:
+                values = [float(x) for x in spec.split(":")] if spec is not None else []
+            except ValueError:
+                values, it = [], itertools.chain([spec], it)
+            if len(values) not in (0, 1, 5, 6) or (values and not values[0].is_integer()):
+                sys.exit("--track-select [MIN_LEN[:MIN_STD:MAX_STD:MAX_STEP:SHARE[:MIN_CAMERA]]]")
+            names = ("min_len", "min_std", "max_std", "max_step", "max_step_share", "min_camera")
+            select = {k: int(v) if k == "min_len" else v for k, v in zip(names, values)}
         elif a == "--descriptors":
             try:
                 n, nxy, nt, min_flow = next(it).split(":")
@@ -126,6 +149,10 @@ def main(argv):
         sys.exit("--dense-tracks needs --sequence --reverse")
     if desc and not dense:
         sys.exit("--descriptors needs --dense-tracks")
+    if select is not None and not dense:
+        sys.exit("--track-select needs --dense-tracks")
+    if opts["--global-motion"] and select is None:
+        sys.exit("--global-motion needs --track-select")
     stem = args[-1] if args else None
     if opts["--sequence"]:
         if opts["--stereo"]:
@@ -180,10 +207,21 @@ def main(argv):
               f"reach the last frame")
     if dense:                        # likewise; one call for the clip
         dtracks, dstart, dlen, info = b.dense_tracks(da.ptr, w, h, *dense)
+        if select is not None:       # the files below hold the kept tracks
+            models = b.global_motion(w, h, fb_check=True)[0] if opts["--global-motion"] else None
+            try:
+                dcode, counts, dtracks, dstart, dlen, _, dindex, _ = capi.track_select(
+                    dtracks, dstart, dlen, models, (w, h), capi.TrackSelectParams(**select), shape=False)
+            except capi.OfdisError as e:
+                sys.exit(f"--track-select: {e}")
+            np.save(stem + "_dcode.npy", dcode)
+            np.save(stem + "_dindex.npy", dindex)
+            print(f"{stem}_dcode.npy, _dindex.npy: of {info[0]} tracks " +
+                  ", ".join(f"{c} {name}" for name, c in zip(tracking.TS_NAMES, counts) if c or name == "kept"))
         np.save(stem + "_dtracks.npy", dtracks)
         np.save(stem + "_dstart.npy", dstart)
         np.save(stem + "_dlen.npy", dlen)
-        print(f"{stem}_dtracks.npy, _dstart.npy, _dlen.npy: {info[0]} tracks ({int((dstart > 0).sum())} seeded after frame 0, "
+        print(f"{stem}_dtracks.npy, _dstart.npy, _dlen.npy: {len(dlen)} tracks ({int((dstart > 0).sum())} seeded after frame 0, "
               f"{info[1]} seeds dropped), mean length {dlen.mean() if len(dlen) else 0:.2f} frames")
     if opts["--reverse"]:            # both directions and both masks in one launch; the forward flow is upsample()'s
         full, rev, mask_fw, mask_rev = b.upsample_bidir(w, h)
