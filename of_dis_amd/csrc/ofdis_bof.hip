@@ -254,14 +254,18 @@ __global__ __launch_bounds__(kBofThreads) void bof_assign_kernel(BofArgs a) {
   }
 }
 
+BofShape bof_assign_shape(int C) {
+  const int nk = (9 * C + 63) / 64;  // the k-steps of the longest channel
+  return nk <= 2 ? BofShape{nk, 2, 8} : nk <= 6 ? BofShape{nk, 6, 3} : BofShape{nk, 18, 1};
+}
+
 template <bool FUSED>
 static hipError_t bof_assign_launch(const BofArgs& a, hipStream_t s) {
-  const int nk = (9 * a.C + 63) / 64;  // the k-steps of the longest channel
-  const int tg = nk <= 2 ? 8 : nk <= 6 ? 3 : 1;
-  const dim3 grid((unsigned)((a.max_tracks + 64 * tg - 1) / (64 * tg)), 4);
-  if (nk <= 2)
+  const BofShape sh = bof_assign_shape(a.C);
+  const dim3 grid((unsigned)((a.max_tracks + 64 * sh.TG - 1) / (64 * sh.TG)), 4);
+  if (sh.NK == 2)
     hipLaunchKernelGGL((bof_assign_kernel<2, 8, FUSED>), grid, dim3(kBofThreads), 0, s, a);
-  else if (nk <= 6)
+  else if (sh.NK == 6)
     hipLaunchKernelGGL((bof_assign_kernel<6, 3, FUSED>), grid, dim3(kBofThreads), 0, s, a);
   else
     hipLaunchKernelGGL((bof_assign_kernel<18, 1, FUSED>), grid, dim3(kBofThreads), 0, s, a);

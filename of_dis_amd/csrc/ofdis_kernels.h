@@ -306,11 +306,28 @@ hipError_t launch_bof_histogram(const int* words, const int* len, const long lon
                                 uint32_t* bof, hipStream_t s);
 hipError_t launch_track_bof(const uint32_t* hist, const int* len, const long long* info, int max_tracks, int nxy, int nt,
                             const uint8_t* codebook, int nwords, int min_len, uint32_t* bof, int* words, hipStream_t s);
+// which bof_assign_kernel<NK, TG, .> serves C = nxy^2 nt, by the k-steps nk = ceil(9 C / 64) of the longest channel: a
+// workgroup owns 64 TG slots and stages tiles of 16 TG words.  Host only; the launcher and the tests' layout classes read it
+struct BofShape {
+  int nk, NK, TG;
+};
+BofShape bof_assign_shape(int C);
 // k-means training of that codebook (include/ofdis.h: ofdis_codebook_seed ... ofdis_codebook_train; ofdis_kmeans.hip): the seed
 // rows; one centre update (six launches: clear, count, scan, scatter, sum, finish) from words -> codebook, counts [4][nwords];
 // and iters x (launch_codebook_assign + update) with stats [iters][4][2] or null.  len may be null (every slot a member); work
 // holds codebook_train_work_bytes (the layout: ofdis_kmeans.hip), 8-byte aligned
 size_t codebook_train_work_bytes(int max_tracks, int nxy, int nt, int nwords);
+// how the lanes of the update's sum are split for C = nxy^2 nt: np passes (1 or 5) of el lanes over the dwords of a channel;
+// rl = 4 el np, the uint32 entries of a slab row.  Host only
+struct KmGeom {
+  int np, el, log2el, rl;
+};
+KmGeom km_geom(int C);
+// km_finish_kernel's threads over a channel of n_c entries: 2^log2te entries x 256 >> log2te groups of chunks.  One statement
+// for the kernel and the host; a macro, since the kernel compiles to the same code only from the expression itself (through
+// an inlined function one scalar compare of it comes out unsigned)
+#define OFDIS_KM_FINISH_LOG2TE(n_c) ((n_c) <= 16 ? 4 : (n_c) <= 128 ? 7 : 8)
+inline int km_finish_log2te(int n_c) { return OFDIS_KM_FINISH_LOG2TE(n_c); }
 hipError_t launch_codebook_seed(const uint8_t* desc, const int* len, const long long* info, int max_tracks, int nxy, int nt, int nwords,
                                 int min_len, uint8_t* codebook, hipStream_t s);
 hipError_t launch_codebook_update(const uint8_t* desc, const int* words, const int* len, const long long* info, int max_tracks, int nxy,

@@ -48,11 +48,9 @@ __device__ __forceinline__ km_u64 km_xor_u64(km_u64 v, int m) {
   return ((km_u64)hi << 32) | lo;
 }
 
-// how the lanes of the sum are split: NP passes of EL lanes over the dwords of a channel (at most ceil(9 C / 4))
-struct KmGeom {
-  int np, el, log2el, rl;  // rl: uint32 entries of a slab row, 4 EL NP
-};
-static KmGeom km_geom(int C) {
+// how the lanes of the sum are split (KmGeom, ofdis_kernels.h): NP passes of EL lanes over the dwords of a channel (at most
+// ceil(9 C / 4))
+KmGeom km_geom(int C) {
   const int nd = (9 * C + 3) / 4;
   KmGeom g;
   g.np = nd <= 64 ? 1 : 5;  // (nd <= 288)
@@ -310,7 +308,7 @@ __global__ __launch_bounds__(kKmThreads) void km_finish_kernel(KmArgs a) {
   const unsigned j0 = a0 / kKmChunk, j1 = (b0 - 1) / kKmChunk, cnt = b0 - a0;
   if (j0 == j1) return;
   const int offc = km_ch_off(c, C), n_c = km_ch_len(c, C);
-  const int log2te = n_c <= 16 ? 4 : n_c <= 128 ? 7 : 8, te = 1 << log2te, jg = kKmThreads >> log2te;  // entries x chunk groups
+  const int log2te = OFDIS_KM_FINISH_LOG2TE(n_c), te = 1 << log2te, jg = kKmThreads >> log2te;  // entries x chunk groups
   const int e0 = tid & (te - 1), gj = tid >> log2te;
   const unsigned* slab = a.slab + (size_t)c * a.nch * 2 * a.rl;
   for (int eb = 0; eb < n_c; eb += te) {

@@ -2,7 +2,8 @@
 // ofdis::launch_* functions of of_dis_amd/csrc/ofdis_kernels.h, and the two launch limits as variables a test can lower.
 //
 // The test library links the PRODUCT'S OWN units (ofdis_interp, ofdis_tfilter, ofdis_trajfilter, ofdis_gmotion, ofdis_stabilize,
-// ofdis_upsample, ofdis_stereo_lr, ofdis_pyr), compiled with the product's flags plus -DOFDIS_TEST_LAUNCH_LIMITS.  Under that
+// ofdis_upsample, ofdis_stereo_lr, ofdis_pyr, ofdis_bof, ofdis_kmeans), compiled with the product's flags plus
+// -DOFDIS_TEST_LAUNCH_LIMITS.  Under that
 // define quad_max_blocks() and grid_max_blocks() (ofdis_kernels.h) read the two variables below instead of returning the
 // product's constants.  Both are read in host code only (quad_grid, grid_for), so the kernels here are the product's kernels;
 // what changes is how many launches (quad_grid's chunks) or grid-stride trips (grid_for) cover the work.  With the limits at
@@ -73,6 +74,21 @@ HOOK void ofdis_test_xcd_frame_map(int n0, int count, int blocks_per_frame, int 
   for (int i = 0; i < count; ++i) xcd_frame_map(n0 + i, blocks_per_frame, nframes, frame[i], blk[i]);
 }
 HOOK size_t ofdis_test_gmotion_work_bytes(int npairs, int w, int h) { return gmotion_work_bytes(npairs, w, h); }
+// host only, needs no GPU: the layout classes of the track-description chain for C = nxy^2 nt, as the launchers choose them
+// (bof_assign_shape, km_geom) and as km_finish_kernel splits its threads over a channel of n_c entries (km_finish_log2te)
+HOOK void ofdis_test_bof_shape(int C, int* nk, int* NK, int* TG) {
+  const BofShape s = bof_assign_shape(C);
+  *nk = s.nk;
+  *NK = s.NK;
+  *TG = s.TG;
+}
+HOOK void ofdis_test_km_geom(int C, int* np, int* el, int* rl) {
+  const KmGeom g = km_geom(C);
+  *np = g.np;
+  *el = g.el;
+  *rl = g.rl;
+}
+HOOK int ofdis_test_km_finish_split(int n_c) { return 1 << km_finish_log2te(n_c); }
 
 // ------------------------------------------------------------------------------------ launchers that walk quad_grid's chunks
 HOOK int ofdis_test_launch_interp_frames(const uint8_t* img_a, const uint8_t* img_b, const float* flow_fw, const float* flow_rev,

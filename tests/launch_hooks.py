@@ -51,6 +51,9 @@ def hooks():
     L.ofdis_test_grid_for.argtypes, L.ofdis_test_grid_for.restype = [_LL], C.c_uint
     L.ofdis_test_xcd_frame_map.argtypes, L.ofdis_test_xcd_frame_map.restype = [_I, _I, _I, _I, _VP, _VP], None
     L.ofdis_test_gmotion_work_bytes.argtypes, L.ofdis_test_gmotion_work_bytes.restype = [_I, _I, _I], _SZ
+    L.ofdis_test_bof_shape.argtypes, L.ofdis_test_bof_shape.restype = [_I] + [C.POINTER(_I)] * 3, None
+    L.ofdis_test_km_geom.argtypes, L.ofdis_test_km_geom.restype = [_I] + [C.POINTER(_I)] * 3, None
+    L.ofdis_test_km_finish_split.argtypes, L.ofdis_test_km_finish_split.restype = [_I], _I
     return L
 
 
@@ -100,6 +103,28 @@ def chunk_walk(nframes, w, h):
     count = hooks().ofdis_test_quad_chunks(nframes, w, h, nframes, walk.ctypes.data)
     assert 0 <= count <= nframes, f"ofdis_test_quad_chunks: {count}"
     return bpf, [tuple(int(v) for v in row) for row in walk[:count]]
+
+
+def _three(fn, C_):
+    a, b, c = _I(), _I(), _I()
+    fn(C_, C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
+
+
+def bof_shape(cells):
+    """(nk, NK, TG) of bof_assign_shape(C) (ofdis_bof.hip), C = nxy^2 nt: the k-steps of the longest channel and the
+    bof_assign_kernel<NK, TG, .> the launcher picks; a workgroup owns 64 TG slots and stages tiles of 16 TG words"""
+    return _three(hooks().ofdis_test_bof_shape, cells)
+
+
+def km_geom(cells):
+    """(np, el, rl) of km_geom(C) (ofdis_kmeans.hip): the passes and lanes of the update's sum, the entries of a slab row"""
+    return _three(hooks().ofdis_test_km_geom, cells)
+
+
+def km_finish_split(n_c):
+    """the entries km_finish_kernel's 256 threads take at a time on a channel of n_c entries: 16, 128 or 256"""
+    return int(hooks().ofdis_test_km_finish_split(n_c))
 
 
 def trips(total):

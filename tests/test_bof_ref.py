@@ -9,7 +9,9 @@ import pytest
 from of_dis_amd import tracking
 
 S2 = tracking.BOF_SCALE ** 2
-LAYOUTS = [(8, 1, 1), (8, 2, 3), (8, 4, 8)]  # (patch, nxy, nt): channels of 8/9, 96/108 and 1024/1152 entries
+# (patch, nxy, nt): channels of 8/9, 96/108 and 1024/1152 entries; of 24/27 in rows of 99 bytes (C = 3: odd, the channels start
+# at odd offsets) and of 216/243 in rows of 891 (C = 27: odd, and in the range of the middle assignment kernel)
+LAYOUTS = [(8, 1, 1), (8, 2, 3), (8, 4, 8), (8, 1, 3), (12, 3, 3)]
 
 
 def _isqrt_rows(hist, layout):
@@ -95,7 +97,17 @@ def _brute(desc, layout, codebook):
 
 
 def test_assignment_is_the_first_minimum():
-    layout = tracking.descriptor_layout(8, 2, 1)
+    _first_minimum((8, 2, 1))
+
+
+@pytest.mark.parametrize("case", [(8, 1, 3), (12, 3, 3)], ids=lambda c: f"{c[1]}x{c[1]}x{c[2]}")
+def test_assignment_is_the_first_minimum_in_rows_of_odd_length(case):
+    """the model's channel slicing where the rows are unaligned: 99 and 891 bytes"""
+    _first_minimum(case)
+
+
+def _first_minimum(case):
+    layout = tracking.descriptor_layout(*case)
     rng = np.random.default_rng(3)
     D = layout["dims"]
     desc = rng.integers(0, 256, (9, D)).astype(np.uint8)
@@ -120,7 +132,8 @@ def test_assignment_is_the_first_minimum():
     w, d = tracking.codebook_assign_ref(np.concatenate([lo, hi]), layout, np.concatenate([hi, lo]))
     assert w.tolist() == [[1] * 4, [0] * 4] and (d == 0).all()
     w, d = tracking.codebook_assign_ref(lo, layout, hi)
-    assert d.tolist() == [[32 * 255 ** 2, 36 * 255 ** 2, 32 * 255 ** 2, 32 * 255 ** 2]]
+    C = case[1] * case[1] * case[2]
+    assert d.tolist() == [[8 * C * 255 ** 2, 9 * C * 255 ** 2, 8 * C * 255 ** 2, 8 * C * 255 ** 2]]
 
 
 def test_bof_columns_sum_to_the_counted_tracks():

@@ -14,16 +14,74 @@ from of_dis_amd import tracking
 from test_gpu_descriptors import CASES as DESC_CASES, MIN_FLOW, _case as _desc_case
 
 pytestmark = pytest.mark.gpu
-LAYOUTS = [(1, 1), (2, 3), (4, 8)]   # channels of 8/9, 96/108 and 1024/1152 entries: 1, 2 and 16/18 k-steps, all three kernels
+# (nxy, nt) with channels of 8/9, 96/108 and 1024/1152 entries, C = nxy^2 nt = 1, 12 and 128: 1, 2 and 16/18 k-steps.  That is
+# bof_assign_kernel<2, 8> twice and <18, 1> at channels that are whole k-steps; <6, 3> is not among them (SWEEP_LAYOUTS)
+LAYOUTS = [(1, 1), (2, 3), (4, 8)]
 NWORDS = [1, 5, 16, 37, 300]         # below, at and above the 16 words of an MFMA; more than one staged tile of 16, 48 or 128
 NTRACKS = [1, 15, 17, 200]           # below and above the 16 tracks of an MFMA; more than one workgroup at 64 slots
 LMAX = 3
 GUARD = 256
 TOP = 2 ** 32 - 1
 
+# One (nxy, nt) for each of the 28 values of C the public ranges (nxy 1 .. 4, nt 1 .. 8) give: everything behind the
+# descriptors sees the layout through C alone.  Shared with tests/test_gpu_kmeans.py; tests/test_descriptor_layout_classes.py
+# (CPU) derives every layout's class from the launchers' own choices -- the assignment kernel, the k-steps of both channel
+# lengths and whether the last one and its last 16-byte fragment are cut, the lanes and passes of the k-means sum, 9 C mod 4,
+# the finish kernel's thread split -- and holds this list, and the subsets below, to a member of every class that occurs.
+# Behind each layout: C, and the seconds the numpy model took on one CPU core for its cases here (the six of
+# test_the_calls_match_the_model_at_every_layout, 200 rows against 5, 16 TG + 1 and 32 TG + 13 words) and in
+# tests/test_gpu_kmeans.py (its four of test_the_calls_match_the_model_at_every_layout), when the list was written.
+SWEEP_LAYOUTS = [
+    (1, 1),   # C 1: 0.06 + 0.01 s
+    (1, 2),   # C 2: 0.04 + 0.01 s
+    (1, 3),   # C 3: 0.06 + 0.01 s
+    (1, 4),   # C 4: 0.06 + 0.01 s
+    (1, 5),   # C 5: 0.08 + 0.01 s
+    (1, 6),   # C 6: 0.09 + 0.01 s
+    (1, 7),   # C 7: 0.11 + 0.02 s
+    (2, 2),   # C 8: 0.11 + 0.01 s
+    (3, 1),   # C 9: 0.15 + 0.02 s
+    (2, 3),   # C 12: 0.18 + 0.02 s
+    (4, 1),   # C 16: 0.10 + 0.03 s
+    (3, 2),   # C 18: 0.11 + 0.03 s
+    (2, 5),   # C 20: 0.14 + 0.03 s
+    (2, 6),   # C 24: 0.14 + 0.04 s
+    (3, 3),   # C 27: 0.17 + 0.04 s
+    (2, 7),   # C 28: 0.18 + 0.05 s
+    (2, 8),   # C 32: 0.19 + 0.06 s
+    (3, 4),   # C 36: 0.24 + 0.06 s
+    (3, 5),   # C 45: 0.14 + 0.07 s
+    (4, 3),   # C 48: 0.14 + 0.07 s
+    (3, 6),   # C 54: 0.16 + 0.10 s
+    (3, 7),   # C 63: 0.18 + 0.11 s
+    (4, 4),   # C 64: 0.19 + 0.10 s
+    (3, 8),   # C 72: 0.19 + 0.12 s
+    (4, 5),   # C 80: 0.23 + 0.13 s
+    (4, 6),   # C 96: 0.28 + 0.17 s
+    (4, 7),   # C 112: 0.30 + 0.22 s
+    (4, 8),   # C 128: 0.37 + 0.23 s
+]
+NEW_LAYOUTS = [s for s in SWEEP_LAYOUTS if s not in LAYOUTS]   # the 25 that LAYOUTS' full parametrisation does not run
+SWEEP_NTRACKS = [17, 200]
+SWEEP_NWORDS = ["5", "tile+1", "2tile+13"]   # with tile = 16 TG words: a tile with idle words, a second tile of one word, a third
+                                             # tile that ends inside a group of 16 -- 5, 49 and 109 for <6, 3>
+# one layout per assignment kernel for a second workgroup whose last wavefronts are partly or wholly idle (64 TG + 23 tracks):
+# <2, 8> with both k-steps, <6, 3> and <18, 1> with a cut last fragment
+SECOND_WORKGROUP_LAYOUTS = [(2, 3), (3, 3), (3, 5)]
+# <6, 3> and <18, 1> with a cut last fragment and k-step (C 27: 216/243 entries; C 45: 360/405), for the structured codebooks
+STRUCTURED_LAYOUTS = [(3, 3), (3, 5)]
+_id = lambda s: f"{s[0]}x{s[0]}x{s[1]}"
+
 
 def _layout(nxy, nt):
-    return tracking.descriptor_layout(8, nxy, nt)
+    return tracking.descriptor_layout(12, nxy, nt)   # (12: a patch every nxy divides; the layout depends on nxy and nt alone)
+
+
+def _nwords(size, which):
+    """a codebook size of SWEEP_NWORDS for the layout's assignment kernel, its tile as the launcher's own choice gives it"""
+    from launch_hooks import bof_shape
+    tile = 16 * bof_shape(size[0] * size[0] * size[1])[2]
+    return {"5": 5, "tile+1": tile + 1, "2tile+13": 2 * tile + 13}[which]
 
 
 def _edge_rows(hist, layout, rng):
@@ -113,8 +171,11 @@ def _padded(a):
 class _Run:
     """the four calls on the first ntracks rows with max_tracks = ntracks + 9 slots; every output pre-filled with 0xAB"""
 
-    def __init__(self, gpu, nxy, nt, ntracks, nwords, min_len, dropped=0, stream=None):
+    def __init__(self, gpu, nxy, nt, ntracks, nwords, min_len, dropped=0, stream=None, rows=None):
         layout, hist, length, _, codebook = _data(nxy, nt)
+        if rows is not None:   # (hist, length) of more rows than _data has
+            hist, length = rows
+        assert ntracks <= len(hist) and nwords <= len(codebook)
         hist, length, codebook = hist[:ntracks], length[:ntracks], codebook[:nwords]
         self.n, self.nwords, self.D, self.slots = ntracks, nwords, layout["dims"], ntracks + 9
         self.gpu, self.args, self.stream = gpu, (nxy, nt), stream
@@ -165,19 +226,17 @@ def _check(run, want_desc, want_words, want_dist, length, min_len, what):
         assert np.array_equal(got, want), (what, key, np.argwhere(got != want)[:3], got[got != want][:3], want[got != want][:3])
     want_bof = tracking.bof_ref(want_words, length, run.nwords, min_len)
     assert (want_bof.sum(1) == (length >= min_len).sum()).all()
-    for key in ("bof", "fbof", "nbof"):   # (no count is 0xABABABAB: at most 200 tracks)
+    for key in ("bof", "fbof", "nbof"):   # (no count is 0xABABABAB: a few hundred tracks)
         assert np.array_equal(run.counts(key), want_bof), (what, key)
 
 
 # ------------------------------------------------------------------ 1. the calls against the model, the fused route against the chain
-@pytest.mark.parametrize("ntracks", NTRACKS)
-@pytest.mark.parametrize("nwords", NWORDS)
-@pytest.mark.parametrize("size", LAYOUTS, ids=lambda s: f"{s[0]}x{s[0]}x{s[1]}")
-def test_the_calls_match_the_model(gpu, size, nwords, ntracks):
+def _model_conditions(size, nwords, ntracks):
+    """the conditions on the inputs of one case, asserted on the model: a tie resolved to the lower index, an unused word, entries
+    0 and 255, a zero channel, hist near 2^32.  One word is used by every track and cannot be tied or unused"""
     nxy, nt = size
     layout, hist, length, desc, codebook = _data(nxy, nt)
     words, dist, ties = _assigned(nxy, nt, nwords)
-    # conditions on the inputs, from the model.  One word is used by every track and cannot be tied or unused
     used = np.unique(words[:ntracks])
     assert len(used) >= 1
     if nwords > 1:
@@ -187,10 +246,63 @@ def test_the_calls_match_the_model(gpu, size, nwords, ntracks):
         assert (desc[:ntracks] == 255).any() and (desc[:ntracks] == 0).any() and (hist[:ntracks] >= TOP - 1000).any()
         assert not desc[2].any() and not desc[1, tracking._channel_slices(layout)[1]].any()
     assert dist.max() <= 1152 * 255 * 255
+    return length, desc, words, dist
+
+
+def _calls_match_the_model(gpu, size, nwords, ntracks):
+    nxy, nt = size
+    length, desc, words, dist = _model_conditions(size, nwords, ntracks)
     for min_len in (1, LMAX + 1):
         run = _Run(gpu, nxy, nt, ntracks, nwords, min_len, dropped=5 if ntracks == 17 else 0)
         _check(run, desc[:ntracks], words[:ntracks], dist[:ntracks], length[:ntracks], min_len, (size, nwords, ntracks, min_len))
         assert np.array_equal(run.di.get((2,), np.int64), [ntracks, 5 if ntracks == 17 else 0])   # the inputs are inputs
+
+
+@pytest.mark.parametrize("ntracks", NTRACKS)
+@pytest.mark.parametrize("nwords", NWORDS)
+@pytest.mark.parametrize("size", LAYOUTS, ids=_id)
+def test_the_calls_match_the_model(gpu, size, nwords, ntracks):
+    _calls_match_the_model(gpu, size, nwords, ntracks)
+
+
+@pytest.mark.parametrize("ntracks", SWEEP_NTRACKS)
+@pytest.mark.parametrize("nwords", SWEEP_NWORDS)
+@pytest.mark.parametrize("size", NEW_LAYOUTS, ids=_id)
+def test_the_calls_match_the_model_at_every_layout(gpu, size, nwords, ntracks):
+    """the other 25 values of C: normalize, assign, histogram and the fused route with and without words, guards, idle slots and
+    both min_len, at codebook sizes chosen from the tile of the layout's own assignment kernel"""
+    _calls_match_the_model(gpu, size, _nwords(size, nwords), ntracks)
+
+
+@functools.lru_cache(maxsize=None)
+def _more_rows(nxy, nt, ntracks):
+    """(hist, length, desc) of ntracks rows: the 200 of _data over and over, the later copies moved a little"""
+    layout, hist, length, _, _ = _data(nxy, nt)
+    copy = np.arange(ntracks) // len(hist)
+    at = np.arange(ntracks) % len(hist)
+    hist = hist[at] ^ (copy[:, None] * (1 + np.arange(hist.shape[1]) % 7)).astype(np.uint32)   # (low bits: no entry leaves uint32)
+    length = length[at]
+    desc = tracking.normalize_descriptors_u8(hist, layout)
+    for a in (hist, length, desc):
+        a.setflags(write=False)
+    return hist, length, desc
+
+
+@pytest.mark.parametrize("size", SECOND_WORKGROUP_LAYOUTS, ids=_id)
+def test_a_second_workgroup_with_idle_wavefronts(gpu, size):
+    """64 TG + 23 tracks (+ 9 idle slots): the second workgroup of every assignment kernel holds one full group of 16 tracks, one
+    of 7 live and 9 idle ones, and wavefronts with no track at all"""
+    from launch_hooks import bof_shape
+    nxy, nt = size
+    tg = bof_shape(nxy * nxy * nt)[2]
+    ntracks, nwords = 64 * tg + 23, _nwords(size, "2tile+13")
+    layout, _, _, _, codebook = _data(nxy, nt)
+    hist, length, desc = _more_rows(nxy, nt, ntracks)
+    words, dist = tracking.codebook_assign_ref(desc, layout, codebook[:nwords])
+    assert 64 * tg < ntracks and ntracks + 9 <= 2 * 64 * tg and len(np.unique(words // 16)) > 1   # two workgroups; words of more than one group of 16
+    for min_len in (1, LMAX + 1):
+        run = _Run(gpu, nxy, nt, ntracks, nwords, min_len, rows=(hist, length))
+        _check(run, desc, words, dist, length, min_len, (size, ntracks, nwords, min_len))
 
 
 # ------------------------------------------------------------------ 2. codebooks with structure, on descriptors given directly
@@ -202,7 +314,7 @@ def _assign(gpu, desc, codebook, nxy, nt):
     return words, dist
 
 
-@pytest.mark.parametrize("size", LAYOUTS, ids=lambda s: f"{s[0]}x{s[0]}x{s[1]}")
+@pytest.mark.parametrize("size", LAYOUTS + STRUCTURED_LAYOUTS, ids=_id)
 def test_a_codebook_drawn_from_the_descriptors(gpu, size):
     nxy, nt = size
     _, _, _, desc, _ = _data(nxy, nt)
@@ -217,7 +329,7 @@ def test_a_codebook_drawn_from_the_descriptors(gpu, size):
             assert words[i, c] == np.flatnonzero(same)[0], (i, c)
 
 
-@pytest.mark.parametrize("size", LAYOUTS, ids=lambda s: f"{s[0]}x{s[0]}x{s[1]}")
+@pytest.mark.parametrize("size", LAYOUTS + STRUCTURED_LAYOUTS, ids=_id)
 def test_an_asymmetric_codebook_and_the_corners_of_the_signed_domain(gpu, size):
     """word k differs from the base row only in entry k mod n_c of every channel; descriptor i differs from it in entry
     (3 i + 1) mod n_c by twice as much: its nearest words are exactly those with k = 3 i + 1 (mod n_c), at distance 1 -- a
@@ -252,8 +364,12 @@ def test_an_asymmetric_codebook_and_the_corners_of_the_signed_domain(gpu, size):
 
 
 # ------------------------------------------------------------------ 3. end to end behind ofdis_track_descriptors
-def test_end_to_end_behind_the_descriptors(gpu):
-    case = min(DESC_CASES, key=lambda c: c[0] * c[1])   # the smallest gray case of tests/test_gpu_descriptors.py
+END_TO_END_16_CELLS = (64, 48, 2, 1, 6, 3, 64, 4, 1)   # of tests/test_gpu_descriptors.py: C = 16, bof_assign_kernel<6, 3, true>
+assert END_TO_END_16_CELLS in DESC_CASES
+
+
+def _end_to_end(gpu, case, every):
+    """descriptors of the device -> ofdis_track_bof; the codebook: every `every`-th descriptor, noise, the descriptors behind them"""
     w, h, _, _, npairs, _, N, nxy, nt = case
     frames, fw, (tracks, start, length, info), want, _ = _desc_case(*case, 1)
     n, lmax = len(length), tracks.shape[0] - 1
@@ -261,7 +377,7 @@ def test_end_to_end_behind_the_descriptors(gpu):
     D = layout["dims"]
     desc = tracking.normalize_descriptors_u8(want[0], layout)   # the model's own hist
     rng = np.random.default_rng(97)
-    codebook = np.concatenate([desc[::3], rng.integers(0, 256, (7, D)).astype(np.uint8), desc[1::3]])
+    codebook = np.concatenate([desc[::every], rng.integers(0, 256, (7, D)).astype(np.uint8), desc[1::every]])
     words, _ = tracking.codebook_assign_ref(desc, layout, codebook)
     assert n >= 2 and (length >= 2).any() and want[0].any(), np.bincount(length)   # (a track of one point has a zero hist)
     dfr, dfw, dt, ds, dl, di = (gpu.Dev(a) for a in (frames, fw, tracks, start, length, info))
@@ -273,6 +389,16 @@ def test_end_to_end_behind_the_descriptors(gpu):
         gpu.check(gpu.lib().ofdis_sync(None))
         assert np.array_equal(dw.get((n, 4), np.int32), words)
         assert np.array_equal(db.get((4, len(codebook)), np.uint32), tracking.bof_ref(words, length, len(codebook), min_len))
+    return len(codebook)
+
+
+def test_end_to_end_behind_the_descriptors(gpu):
+    _end_to_end(gpu, min(DESC_CASES, key=lambda c: c[0] * c[1]), 3)   # the smallest gray case of tests/test_gpu_descriptors.py
+
+
+def test_end_to_end_behind_the_descriptors_of_16_cells(gpu):
+    """N 64, nxy 4, nt 1: the device's own hist through bof_assign_kernel<6, 3, true>, more than two of its tiles of 48 words"""
+    assert _end_to_end(gpu, END_TO_END_16_CELLS, 33) > 2 * 48
 
 
 # ------------------------------------------------------------------ 4. determinism and purity

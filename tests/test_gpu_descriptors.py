@@ -6,7 +6,9 @@ complete tracks exist, values are clamped and skipped) are checked on the model,
 
 What the model gave for the gray cases when the recipe was written (tracks, of length 1, complete, windows cut, largest entry):
 64x48 N 16: 1764, 773, 685, 1051, 149839; 37x11 N 8: 103, 51, 20, 56, 107276 (RGB: 109, 58, 19, 49); 67x45 N 32: 247, 119, 63,
-296, 635206; 64x48 N 64: every one of the 2524 windows cut, 926164.  Indicative only: the libm behind sin may move a last digit."""
+296, 635206; 64x48 N 64: every one of the 2524 windows cut, 926164.  The cases with other cell sides and more temporal cells (tracks, of
+length 1, complete): 64x48 stride 4 N 10 nt 8 of 8: 467, 264, 67; 37x11 N 6 nt 5 of 7: 122, 65, 7; 67x45 N 18: 247, 119, 63; 64x48
+stride 4 N 20: 432, 195, 159; every temporal cell of each is voted into.  Indicative only: the libm behind sin may move a last digit."""
 import functools
 import os
 import subprocess
@@ -87,7 +89,11 @@ def _case(w, h, stride, window, npairs, max_len, N, nxy, nt, noc, capacity=None)
 
 # (w, h, stride, window, npairs, max_len, N, nxy, nt)
 CASES = [(64, 48, 2, 1, 6, 3, 16, 2, 3), (37, 11, 3, 2, 5, 3, 8, 2, 2), (67, 45, 5, 2, 6, 4, 32, 2, 2), (9, 7, 4, 0, 3, 2, 8, 2, 1),
-         (64, 48, 2, 1, 6, 3, 64, 4, 1)]
+         (64, 48, 2, 1, 6, 3, 64, 4, 1),
+         # cell sides that are no power of two (the reciprocal of the cell side), every lane in one cell (nxy 1), nt > 3:
+         # nxy 1 with a side of 10 and nt = lmax = 8; nxy 2 with a side of 3 and nt 5 in lmax 7 (temporal cells of 1 and 2 steps);
+         # nxy 3 with a side of 6 and nt 3 in lmax 4; nxy 4 with a side of 5
+         (64, 48, 4, 1, 8, 8, 10, 1, 8), (37, 11, 3, 2, 7, 7, 6, 2, 5), (67, 45, 5, 2, 6, 4, 18, 3, 3), (64, 48, 4, 1, 6, 3, 20, 4, 2)]
 IDS = [f"{c[0]}x{c[1]}-s{c[2]}-L{c[5]}-N{c[6]}-{c[7]}x{c[7]}x{c[8]}" for c in CASES]
 
 

@@ -12,13 +12,23 @@ import numpy as np
 import pytest
 
 from of_dis_amd import tracking
-from test_gpu_bof import _data, _padded
+from test_gpu_bof import END_TO_END_16_CELLS, NEW_LAYOUTS, _data, _id, _padded
 from test_gpu_descriptors import CASES as DESC_CASES, MIN_FLOW, _case as _desc_case
 
 pytestmark = pytest.mark.gpu
-LAYOUTS = [(1, 1), (2, 3), (4, 8)]   # channels of 8/9, 96/108 and 1024/1152 bytes: all three assignment kernels, 4, 32 and 64 lanes
+# channels of 8/9, 96/108 and 1024/1152 bytes, C = 1, 12 and 128: the sum with 4 and 32 lanes in one pass and with 64 lanes in five
+# passes over all 288 dwords; the assignment kernels <2, 8> (twice) and <18, 1>.  The other 25 values of C: NEW_LAYOUTS
+LAYOUTS = [(1, 1), (2, 3), (4, 8)]
 NWORDS = [1, 5, 37, 300]             # one word owns everything; below and above the 16 words of an MFMA; more words than tracks
 NTRACKS = [1, 17, 200]
+SWEEP_CASES = [(5, 200), (37, 17)]   # (nwords, ntracks) of the layouts of NEW_LAYOUTS
+# segments longer than a chunk (700 slots): with LAYOUTS a layout of every class of the sum that occurs -- the lanes, the passes,
+# the passes either channel fills and whether its last one is cut, 9 C mod 4 -- and of every pair of thread splits of the finish
+# kernel (tests/test_descriptor_layout_classes.py holds the list to that).  C = 2 .. 7, 9, 16, 18, 27, 32, 36, 45, 54, 63, 64, 72,
+# 96, 112
+LONG_SEGMENT_LAYOUTS = [(1, 2), (1, 3), (1, 4), (1, 5), (1, 6), (1, 7), (3, 1), (4, 1), (3, 2), (3, 3), (2, 8), (3, 4), (3, 5), (3, 6),
+                        (3, 7), (4, 4), (3, 8), (4, 6), (4, 7)]
+TAIL_BYTES_LAYOUTS = [(1, 2), (3, 3)]   # 9 C mod 4 = 2 and 3: a channel whose last dword is cut, two and three bytes of it written
 MIN_LEN = 3                          # with the length array; without it every slot is a member
 ROUNDS = 4
 GUARD = 256
@@ -146,6 +156,16 @@ def _check_train(got, rounds, stats, iters, what, with_stats=True):
 @pytest.mark.parametrize("nwords", NWORDS)
 @pytest.mark.parametrize("size", LAYOUTS, ids=lambda s: f"{s[0]}x{s[0]}x{s[1]}")
 def test_the_calls_match_the_model(gpu, size, nwords, ntracks):
+    _calls_match_the_model(gpu, size, nwords, ntracks)
+
+
+@pytest.mark.parametrize("case", SWEEP_CASES, ids=lambda c: f"{c[0]}-{c[1]}")
+@pytest.mark.parametrize("size", NEW_LAYOUTS, ids=_id)
+def test_the_calls_match_the_model_at_every_layout(gpu, size, case):
+    _calls_match_the_model(gpu, size, *case)
+
+
+def _calls_match_the_model(gpu, size, nwords, ntracks):
     nxy, nt = size
     for filtered in (False, True):
         layout, desc, ln, min_len, seed, rounds, stats = _model(nxy, nt, nwords, ntracks, filtered)
@@ -167,7 +187,7 @@ def test_the_calls_match_the_model(gpu, size, nwords, ntracks):
 
 # ------------------------------------------------------------------ 2. segments longer than one chunk of the sum
 @pytest.mark.parametrize("nwords", [1, 5])
-@pytest.mark.parametrize("size", LAYOUTS, ids=lambda s: f"{s[0]}x{s[0]}x{s[1]}")
+@pytest.mark.parametrize("size", LAYOUTS + LONG_SEGMENT_LAYOUTS, ids=_id)
 def test_words_with_more_members_than_one_wavefront_sums(gpu, size, nwords):
     """700 slots: with one word its segment spans three chunks of 256 (a head, a middle and a tail part), with five the segments
     straddle the chunk borders; every part goes through the slab and the last launch"""
@@ -218,7 +238,7 @@ def test_no_member_at_all(gpu):
 
 
 # ------------------------------------------------------------------ 4. a words array of the caller
-@pytest.mark.parametrize("size", LAYOUTS, ids=lambda s: f"{s[0]}x{s[0]}x{s[1]}")
+@pytest.mark.parametrize("size", LAYOUTS + TAIL_BYTES_LAYOUTS, ids=_id)
 def test_a_words_array_of_the_caller_with_entries_outside_the_codebook(gpu, size):
     nxy, nt = size
     layout, _, length, desc, codebook = _data(nxy, nt)
@@ -264,7 +284,16 @@ def test_twice_the_same_bytes_on_a_stream_of_its_own(gpu):
 def test_end_to_end_behind_the_descriptors(gpu):
     """hist of the device -> normalise -> seed -> train 3 rounds -> ofdis_track_bof with the trained codebook, against bof_ref on
     the model's codebook"""
-    case = min(DESC_CASES, key=lambda c: c[0] * c[1])   # the smallest gray case of tests/test_gpu_descriptors.py
+    _end_to_end(gpu, min(DESC_CASES, key=lambda c: c[0] * c[1]))   # the smallest gray case of tests/test_gpu_descriptors.py
+
+
+def test_end_to_end_behind_the_descriptors_of_16_cells(gpu):
+    """the same at N 64, nxy 4, nt 1 (C = 16): the sum with 64 lanes in one pass, the finish split 128 and 256, and the device's
+    own hist through bof_assign_kernel<6, 3, true>"""
+    _end_to_end(gpu, END_TO_END_16_CELLS)
+
+
+def _end_to_end(gpu, case):
     w, h, _, _, npairs, _, N, nxy, nt = case
     frames, fw, (tracks, start, length, info), want, _ = _desc_case(*case, 1)
     n, lmax = len(length), tracks.shape[0] - 1

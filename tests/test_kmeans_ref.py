@@ -11,7 +11,7 @@ from test_gpu_bof import LMAX, _data
 
 
 def _layout(nxy=1, nt=1):
-    return tracking.descriptor_layout(8, nxy, nt)
+    return tracking.descriptor_layout(12, nxy, nt)   # (12: a patch every nxy divides)
 
 
 def _rows(values, layout=None):
@@ -31,7 +31,10 @@ def test_the_mean_is_rounded_half_up(members, mean):
     assert (cb == mean).all() and (counts == len(members)).all()
 
 
-@pytest.mark.parametrize("size", [(1, 1), (2, 3)])
+SIZES = [(1, 1), (2, 3), (1, 3), (3, 3)]   # C = 1, 12; 3 and 27: rows of odd length, 27 in the range of the middle assignment kernel
+
+
+@pytest.mark.parametrize("size", SIZES)
 def test_one_word_is_the_rounded_mean_of_the_members_after_one_iteration(size):
     layout, _, length, desc, _ = _data(*size)
     for ln, min_len in ((None, 1), (length, LMAX + 1)):
@@ -113,7 +116,7 @@ def test_an_empty_word_keeps_its_bytes_and_a_filtered_slot_is_no_member():
     assert np.array_equal(cb, cb0) and not counts.any()
 
 
-@pytest.mark.parametrize("size", [(1, 1), (2, 3)])
+@pytest.mark.parametrize("size", SIZES)
 def test_the_update_does_not_depend_on_the_order_of_the_slots(size):
     layout, _, length, desc, codebook = _data(*size)
     words, _ = tracking.codebook_assign_ref(desc, layout, codebook[:16])
@@ -134,7 +137,7 @@ def _train(size, nwords, filtered, iters=8):
 
 @pytest.mark.parametrize("filtered", [False, True])
 @pytest.mark.parametrize("nwords", [5, 16, 37])
-@pytest.mark.parametrize("size", [(1, 1), (2, 3)])
+@pytest.mark.parametrize("size", SIZES[:3])   # (at C = 27 eight rounds do not reach the fixed point)
 def test_the_distortion_is_monotone_and_a_fixed_point_stays(size, nwords, filtered):
     layout, desc, ln, min_len, seed, (cb, words, counts, stats) = _train(size, nwords, filtered)
     member = np.ones(len(desc), bool) if ln is None else ln >= min_len
