@@ -11,6 +11,8 @@ import shutil
 import subprocess
 import sys
 
+from .abi import prototypes
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
@@ -68,10 +70,7 @@ def _newer(target, deps):
 
 def abi_symbols():
     """Every function include/ofdis.h declares: the export list of the shared library."""
-    import re
-    src = open(os.path.join(ROOT, "include", "ofdis.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(ofdis_[a-z0-9_]+)\s*\(", src)))
+    return sorted(prototypes())
 
 
 def source_id(csrc=None, extra_flags=None):

@@ -10,7 +10,8 @@ import os
 
 import numpy as np
 
-from .params import OfdisParams
+from .abi import prototypes
+from .params import OfdisParams  # noqa: F401  (the struct callers pass by reference; stays a name of this module)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libofdis_hip.so")
@@ -22,38 +23,8 @@ VP = C.c_void_p
 K_WARP, K_DERIV, K_SYSTEM, K_SOR, K_PATCH, K_DENSIFY, K_UPDATE, K_FUSED, K_COUNT = range(9)
 K_NAMES = ["warp", "derivatives", "tv_system", "sor", "patch_optimize", "densify", "tv_finish", "tv_fused"]
 
-# every symbol include/ofdis.h declares (checked by tests/test_abi.py)
-ABI_SYMBOLS = [
-    "ofdis_params_oppoint", "ofdis_last_error", "ofdis_version", "ofdis_device_count", "ofdis_set_device",
-    "ofdis_flow", "ofdis_batch_create", "ofdis_batch_destroy", "ofdis_batch_input", "ofdis_batch_input_elems",
-    "ofdis_batch_upload", "ofdis_batch_upload_b_gradients", "ofdis_batch_initflow_elems", "ofdis_batch_set_initflow", "ofdis_batch_upload_initflow",
-    "ofdis_batch_build_pyramids_u8", "ofdis_batch_run", "ofdis_batch_set_pipeline", "ofdis_batch_join", "ofdis_batch_flow",
-    "ofdis_batch_level_flow", "ofdis_batch_download", "ofdis_batch_upsample", "ofdis_batch_timing", "ofdis_batch_kernel_time",
-    "ofdis_image_warp", "ofdis_get_derivatives", "ofdis_tv_system", "ofdis_sor_coupled", "ofdis_patchgrid_level",
-    "ofdis_varref_level", "ofdis_dev_alloc", "ofdis_dev_free", "ofdis_memcpy_h2d", "ofdis_memcpy_d2h", "ofdis_memcpy_d2d", "ofdis_sync",
-    "ofdis_batch_set_graph", "ofdis_batch_status", "ofdis_flow_cache_clear", "ofdis_get_tuning", "ofdis_set_tuning", "ofdis_batch_kernel_times", "ofdis_device_pci_bus_id",
-    "ofdis_batch_upsample_frames",
-    "ofdis_build_id", "ofdis_stream_create", "ofdis_stream_destroy", "ofdis_host_alloc", "ofdis_host_free", "ofdis_memcpy_h2d_async", "ofdis_memcpy_d2h_async",
-    "ofdis_event_create", "ofdis_event_destroy", "ofdis_event_record", "ofdis_stream_wait_event", "ofdis_event_sync",
-    "ofdis_batch_create_ex", "ofdis_batch_flow_reverse", "ofdis_batch_level_flow_reverse", "ofdis_batch_set_initflow_reverse",
-    "ofdis_batch_download_reverse", "ofdis_batch_upsample_bidir", "ofdis_fb_check",
-    "ofdis_interpolate", "ofdis_batch_interpolate",
-    "ofdis_batch_flow_mirror", "ofdis_batch_level_flow_mirror", "ofdis_lr_check", "ofdis_disparity_fill", "ofdis_batch_upsample_lr",
-    "ofdis_encoding_bytes", "ofdis_encode", "ofdis_batch_upsample_frames_enc",
-    "ofdis_batch_input_frames", "ofdis_batch_upload_frame", "ofdis_batch_build_pyramids_u8_seq", "ofdis_batch_device_bytes",
-    "ofdis_track_points", "ofdis_batch_track_points",
-    "ofdis_dense_tracks_cells", "ofdis_dense_tracks_work_bytes", "ofdis_seed_texture", "ofdis_dense_tracks",
-    "ofdis_batch_dense_tracks",
-    "ofdis_track_select_defaults", "ofdis_track_select_work_bytes", "ofdis_track_select",
-    "ofdis_track_descriptor_dims", "ofdis_track_descriptors",
-    "ofdis_descriptor_normalize", "ofdis_codebook_assign", "ofdis_bof_histogram", "ofdis_track_bof",
-    "ofdis_codebook_train_work_bytes", "ofdis_codebook_seed", "ofdis_codebook_update", "ofdis_codebook_train",
-    "ofdis_temporal_filter", "ofdis_batch_temporal_filter",
-    "ofdis_trajectory_filter", "ofdis_batch_trajectory_filter",
-    "ofdis_global_motion_work_bytes", "ofdis_global_motion", "ofdis_motion_compensate", "ofdis_batch_global_motion",
-    "ofdis_batch_motion_compensate",
-    "ofdis_camera_path", "ofdis_warp_frames", "ofdis_batch_stabilize",
-]
+# every constant of include/ofdis.h under its name without the OFDIS_ prefix (checked by tests/test_abi.py)
+OK, ERR_INVALID, ERR_UNSUPPORTED, ERR_DEVICE, ERR_NOMEM = 0, -1, -2, -3, -4  # OFDIS_OK / OFDIS_ERR_*
 BATCH_REVERSE = 1  # include/ofdis.h: OFDIS_BATCH_REVERSE
 BATCH_STEREO_LR = 2  # OFDIS_BATCH_STEREO_LR
 BATCH_SEQUENCE = 16  # OFDIS_BATCH_SEQUENCE
@@ -132,11 +103,21 @@ class OfdisError(RuntimeError):
     pass
 
 
+def _prototypes():
+    """include/ofdis.h as ctypes prototypes (abi.py).  The header is the tree's own: the library is only ever built in-tree."""
+    try:
+        return prototypes()
+    except OSError as e:
+        raise OfdisError(f"include/ofdis.h cannot be read ({e}): the binding takes every prototype from it") from e
+
+
+ABI_SYMBOLS = list(_prototypes())  # every function include/ofdis.h declares
 _lib = None
 
 
 def lib():
-    """Load libofdis_hip.so (built by of_dis_amd.build).  Fails loudly when it is missing."""
+    """Load libofdis_hip.so (built by of_dis_amd.build) and give every function the header's prototype.  Fails loudly when
+    the library is missing."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
@@ -145,153 +126,9 @@ def lib():
         if L.ofdis_version() != OFDIS_VERSION:  # a stale build: ofdis_get_tuning would write past / read garbage from our struct
             raise OfdisError(f"{LIB_PATH} has ABI version {L.ofdis_version()}, this binding expects {OFDIS_VERSION}: "
                              "rebuild with `python -m of_dis_amd.build`")
-        L.ofdis_last_error.restype = C.c_char_p
-        L.ofdis_build_id.restype = C.c_char_p
-        L.ofdis_dev_alloc.restype = VP
-        L.ofdis_dev_alloc.argtypes = [C.c_size_t]
-        L.ofdis_dev_free.argtypes = [VP]
-        L.ofdis_memcpy_h2d.argtypes = [VP, VP, C.c_size_t]
-        L.ofdis_memcpy_d2h.argtypes = [VP, VP, C.c_size_t]
-        L.ofdis_sync.argtypes = [VP]
-        L.ofdis_stream_create.restype = VP
-        L.ofdis_stream_create.argtypes = []
-        L.ofdis_stream_destroy.restype = None
-        L.ofdis_stream_destroy.argtypes = [VP]
-        L.ofdis_host_alloc.restype = VP
-        L.ofdis_host_alloc.argtypes = [C.c_size_t]
-        L.ofdis_host_free.restype = None
-        L.ofdis_host_free.argtypes = [VP]
-        L.ofdis_memcpy_h2d_async.argtypes = [VP, VP, C.c_size_t, VP]
-        L.ofdis_memcpy_d2h_async.argtypes = [VP, VP, C.c_size_t, VP]
-        L.ofdis_event_create.restype = VP
-        L.ofdis_event_create.argtypes = []
-        L.ofdis_event_destroy.restype = None
-        L.ofdis_event_destroy.argtypes = [VP]
-        L.ofdis_event_record.argtypes = [VP, VP]
-        L.ofdis_stream_wait_event.argtypes = [VP, VP]
-        L.ofdis_event_sync.argtypes = [VP]
-        L.ofdis_memcpy_d2d.argtypes = [VP, VP, C.c_size_t, VP]
-        L.ofdis_batch_create.argtypes = [C.POINTER(VP), C.POINTER(OfdisParams), C.c_int]
-        L.ofdis_batch_destroy.argtypes = [VP]
-        L.ofdis_batch_input.restype = VP
-        L.ofdis_batch_input.argtypes = [VP, C.c_int, C.c_int]
-        L.ofdis_batch_input_elems.restype = C.c_size_t
-        L.ofdis_batch_input_elems.argtypes = [VP, C.c_int]
-        L.ofdis_batch_upload.argtypes = [VP, C.c_int, C.POINTER(FP), C.POINTER(FP), C.POINTER(FP), C.POINTER(FP), VP]
-        L.ofdis_batch_build_pyramids_u8.argtypes = [VP, VP, VP, C.c_int, C.c_int, VP]
-        L.ofdis_batch_run.argtypes = [VP, VP]
-        L.ofdis_batch_status.argtypes = [VP]
-        L.ofdis_batch_flow.restype = VP
-        L.ofdis_batch_flow.argtypes = [VP]
-        L.ofdis_batch_level_flow.restype = VP
-        L.ofdis_batch_level_flow.argtypes = [VP, C.c_int]
-        L.ofdis_batch_download.argtypes = [VP, C.c_int, FP, VP]
-        L.ofdis_batch_timing.argtypes = [VP, C.c_int]
-        L.ofdis_batch_kernel_time.argtypes = [VP, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_long)]
-        L.ofdis_image_warp.argtypes = [VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, VP]
-        L.ofdis_get_derivatives.argtypes = [VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, VP]
-        L.ofdis_tv_system.argtypes = [VP, VP, VP, VP, VP, VP, VP, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int,
-                                      C.c_int, C.c_int, VP]
-        L.ofdis_sor_coupled.argtypes = [VP, VP, VP, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, VP]
-        L.ofdis_patchgrid_level.argtypes = [C.POINTER(OfdisParams), C.c_int, VP, VP, VP, VP, VP, VP, VP, C.c_int, VP]
-        L.ofdis_varref_level.argtypes = [C.POINTER(OfdisParams), C.c_int, VP, VP, VP, C.c_int, VP]
-        L.ofdis_flow.argtypes = [C.POINTER(OfdisParams)] + [C.POINTER(FP)] * 6 + [FP, FP]
-        L.ofdis_params_oppoint.argtypes = [C.POINTER(OfdisParams), C.c_int, C.c_int, C.c_int]
-        L.ofdis_batch_upsample.argtypes = [VP, VP, C.c_int, C.c_int, VP]
-        L.ofdis_batch_upsample_frames.argtypes = [VP, C.c_int, C.c_int, VP, C.c_int, C.c_int, VP]
-        L.ofdis_batch_set_pipeline.argtypes = [VP, C.c_int]
-        L.ofdis_batch_join.argtypes = [VP, VP]
-        L.ofdis_batch_set_graph.argtypes = [VP, C.c_int]
-        L.ofdis_flow_cache_clear.restype = None
-        L.ofdis_batch_upload_b_gradients.argtypes = [VP, C.c_int, C.POINTER(FP), C.POINTER(FP), VP]
-        L.ofdis_batch_initflow_elems.restype = C.c_size_t
-        L.ofdis_batch_initflow_elems.argtypes = [VP]
-        L.ofdis_batch_set_initflow.argtypes = [VP, VP]
-        L.ofdis_batch_upload_initflow.argtypes = [VP, C.c_int, FP, VP]
-        L.ofdis_batch_kernel_times.argtypes = [VP, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int)]
-        L.ofdis_get_tuning.argtypes = [C.POINTER(OfdisTuning)]
-        L.ofdis_set_tuning.argtypes = [C.POINTER(OfdisTuning)]
-        L.ofdis_batch_create_ex.argtypes = [C.POINTER(VP), C.POINTER(OfdisParams), C.c_int, C.c_uint]
-        L.ofdis_batch_flow_reverse.restype = VP
-        L.ofdis_batch_flow_reverse.argtypes = [VP]
-        L.ofdis_batch_level_flow_reverse.restype = VP
-        L.ofdis_batch_level_flow_reverse.argtypes = [VP, C.c_int]
-        L.ofdis_batch_set_initflow_reverse.argtypes = [VP, VP]
-        L.ofdis_batch_download_reverse.argtypes = [VP, C.c_int, FP, VP]
-        L.ofdis_batch_upsample_bidir.argtypes = [VP, C.c_int, C.c_int, VP, VP, VP, VP, C.c_int, C.c_int, C.c_float, C.c_float, VP]
-        L.ofdis_fb_check.argtypes = [VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, VP]
-        L.ofdis_interpolate.argtypes = [VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, FP, C.c_int, VP]
-        L.ofdis_batch_interpolate.argtypes = [VP, VP, VP, C.c_int, C.c_int, FP, C.c_int, VP, C.c_int, C.c_int, C.c_float,
-                                              C.c_float, VP]
-        L.ofdis_batch_flow_mirror.restype = VP
-        L.ofdis_batch_flow_mirror.argtypes = [VP]
-        L.ofdis_batch_level_flow_mirror.restype = VP
-        L.ofdis_batch_level_flow_mirror.argtypes = [VP, C.c_int]
-        L.ofdis_lr_check.argtypes = [VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, VP]
-        L.ofdis_disparity_fill.argtypes = [VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, VP]
-        L.ofdis_batch_upsample_lr.argtypes = [VP, C.c_int, C.c_int, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_float,
-                                              C.c_float, VP]
-        L.ofdis_encoding_bytes.restype = C.c_size_t
-        L.ofdis_encoding_bytes.argtypes = [C.c_int]
-        L.ofdis_encode.argtypes = [VP, VP, C.c_size_t, C.POINTER(Encoding), VP]
-        L.ofdis_batch_upsample_frames_enc.argtypes = [VP, C.c_int, C.c_int, VP, C.c_int, C.c_int, C.POINTER(Encoding), VP]
-        L.ofdis_batch_input_frames.argtypes = [VP]
-        L.ofdis_batch_upload_frame.argtypes = [VP, C.c_int, C.POINTER(FP), C.POINTER(FP), C.POINTER(FP), VP]
-        L.ofdis_batch_build_pyramids_u8_seq.argtypes = [VP, VP, C.c_size_t, C.c_size_t, C.c_int, C.c_int, VP]
-        L.ofdis_batch_device_bytes.restype = C.c_size_t
-        L.ofdis_batch_device_bytes.argtypes = [VP]
-        L.ofdis_track_points.argtypes = [VP, VP, C.c_int, C.c_int, C.c_int, VP, VP, C.c_int, C.c_int, C.c_float, C.c_float, VP,
-                                         VP, VP]
-        L.ofdis_batch_track_points.argtypes = [VP, C.c_int, C.c_int, VP, VP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
-                                               VP, VP, C.c_int, C.c_int, VP]
-        L.ofdis_dense_tracks_cells.argtypes = [C.c_int, C.c_int, C.c_int, VP, VP]
-        L.ofdis_dense_tracks_work_bytes.restype = C.c_size_t
-        L.ofdis_dense_tracks_work_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
-        L.ofdis_seed_texture.argtypes = [VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP]
-        L.ofdis_dense_tracks.argtypes = [VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                         C.c_float, C.c_float, C.c_int, VP, VP, VP, VP, VP, C.c_size_t, VP]
-        L.ofdis_batch_dense_tracks.argtypes = [VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
-                                               C.c_float, C.c_int, VP, VP, VP, VP, C.c_int, C.c_int, VP]
-        L.ofdis_track_select_defaults.restype = None
-        L.ofdis_track_select_defaults.argtypes = [VP]
-        L.ofdis_track_select_work_bytes.restype = C.c_size_t
-        L.ofdis_track_select_work_bytes.argtypes = [C.c_int]
-        L.ofdis_track_select.argtypes = [VP, VP, VP, VP, C.c_int, C.c_int, VP, C.c_int, C.c_int, C.c_int, VP, VP, VP, C.c_int, VP, VP,
-                                         VP, VP, VP, VP, VP, C.c_size_t, VP]
-        L.ofdis_track_descriptor_dims.argtypes = [C.c_int, C.c_int, C.c_int]
-        L.ofdis_track_descriptors.argtypes = [VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int,
-                                              C.c_int, C.c_int, C.c_float, VP, VP, VP]
-        L.ofdis_descriptor_normalize.argtypes = [VP, VP, C.c_int, C.c_int, C.c_int, VP, VP]
-        L.ofdis_codebook_assign.argtypes = [VP, VP, C.c_int, C.c_int, C.c_int, VP, C.c_int, VP, VP, VP]
-        L.ofdis_bof_histogram.argtypes = [VP, VP, VP, C.c_int, C.c_int, C.c_int, VP, VP]
-        L.ofdis_track_bof.argtypes = [VP, VP, VP, C.c_int, C.c_int, C.c_int, VP, C.c_int, C.c_int, VP, VP, VP]
-        L.ofdis_codebook_train_work_bytes.restype = C.c_size_t
-        L.ofdis_codebook_train_work_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
-        L.ofdis_codebook_seed.argtypes = [VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP]
-        L.ofdis_codebook_update.argtypes = [VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP, C.c_size_t, VP]
-        L.ofdis_codebook_train.argtypes = [VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP, VP,
-                                           C.c_size_t, VP]
-        L.ofdis_temporal_filter.argtypes = [VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
-                                            VP]
-        L.ofdis_batch_temporal_filter.argtypes = [VP, VP, C.c_int, C.c_int, VP, VP, C.c_int, C.c_int, C.c_float, C.c_float,
-                                                  C.c_float, C.c_float, VP]
-        L.ofdis_trajectory_filter.argtypes = [VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, VP, C.c_int, C.c_float,
-                                              C.c_int, C.c_float, C.c_float, VP]
-        L.ofdis_batch_trajectory_filter.argtypes = [VP, VP, C.c_int, C.c_int, VP, VP, C.c_int, C.c_int, VP, C.c_int, C.c_float,
-                                                    C.c_int, C.c_float, C.c_float, VP]
-        L.ofdis_global_motion_work_bytes.restype = C.c_size_t
-        L.ofdis_global_motion_work_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-        L.ofdis_global_motion.argtypes = [VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, VP, VP, VP, C.c_size_t,
-                                          VP]
-        L.ofdis_motion_compensate.argtypes = [VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_float, VP, VP, VP]
-        L.ofdis_batch_global_motion.argtypes = [VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float,
-                                                VP, VP, C.c_int, C.c_int, VP]
-        L.ofdis_batch_motion_compensate.argtypes = [VP, C.c_int, C.c_int, VP, C.c_float, C.c_int, C.c_float, C.c_float, VP, VP,
-                                                    C.c_int, C.c_int, VP]
-        L.ofdis_camera_path.argtypes = [VP, C.c_int, VP, C.c_int, C.c_double, VP, VP]
-        L.ofdis_warp_frames.argtypes = [VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP]
-        L.ofdis_batch_stabilize.argtypes = [VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float,
-                                            VP, C.c_int, C.c_double, C.c_int, VP, VP, VP, C.c_int, C.c_int, VP]
+        for name, (restype, argtypes) in _prototypes().items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
 

@@ -6,19 +6,16 @@ import math
 import numpy as np
 import pytest
 
+import abi
 from of_dis_amd import capi
 from of_dis_amd.params import oppoint
 
 
 def test_constants_match_the_header():
-    import os
-    import re
-    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "ofdis.h")).read()
-    assert int(re.search(r"#define OFDIS_BATCH_REVERSE (\d+)u", hdr).group(1)) == capi.BATCH_REVERSE
-    assert float(re.search(r"#define OFDIS_FB_ALPHA ([0-9.]+)f", hdr).group(1)) == capi.FB_ALPHA
-    assert float(re.search(r"#define OFDIS_FB_BETA\s+([0-9.]+)f", hdr).group(1)) == capi.FB_BETA
-    m = re.search(r"OFDIS_FB_CONSISTENT = (\d), OFDIS_FB_INCONSISTENT = (\d), OFDIS_FB_OUTSIDE = (\d)", hdr)
-    assert tuple(int(x) for x in m.groups()) == (capi.FB_CONSISTENT, capi.FB_INCONSISTENT, capi.FB_OUTSIDE)
+    assert abi.define("OFDIS_BATCH_REVERSE") == capi.BATCH_REVERSE
+    assert (abi.define("OFDIS_FB_ALPHA"), abi.define("OFDIS_FB_BETA")) == (capi.FB_ALPHA, capi.FB_BETA)
+    assert [abi.enumerator("OFDIS_FB_" + n) for n in ("CONSISTENT", "INCONSISTENT", "OUTSIDE")] \
+        == [capi.FB_CONSISTENT, capi.FB_INCONSISTENT, capi.FB_OUTSIDE]
 
 
 def test_create_ex_rejects_stereo_reverse_and_unknown_flags():

@@ -2,70 +2,29 @@
 ofdis_bof_histogram, ofdis_track_bof) in the header, the binding and the export list, and the argument checks that return before
 any device work.  Host buffers stand in for the device arrays: every call here returns before it would launch.  The kernels:
 tests/test_gpu_bof.py."""
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from of_dis_amd import build, capi, tracking
+import abi
+from of_dis_amd import capi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INVALID = -1
-SYMBOLS = ["ofdis_descriptor_normalize", "ofdis_codebook_assign", "ofdis_bof_histogram", "ofdis_track_bof"]
-NARGS = {"ofdis_descriptor_normalize": 7, "ofdis_codebook_assign": 10, "ofdis_bof_histogram": 8, "ofdis_track_bof": 12}
+_p = abi.ptr
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "ofdis.h")).read()
-
-
-@pytest.mark.parametrize("name", SYMBOLS)
-def test_declared_bound_and_exported(name):
-    assert name in build.abi_symbols()                      # a declaration outside the header's comments
-    assert name in capi.ABI_SYMBOLS
-    fn = getattr(capi.lib(), name)
-    assert fn.argtypes is not None
-    out = subprocess.run(["nm", "-D", "--defined-only", capi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert name in [line.split()[-1] for line in out.splitlines() if line.strip()]
-
-
-def test_prototypes_match_the_header():
-    """the binding's argument lists against the header's declarations, type by type"""
-    src = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    ctype = {"int": capi.C.c_int}
-    for name in SYMBOLS:
-        ret, args = re.search(r"\b(int) " + name + r"\s*\((.*?)\)\s*;", src, re.S).groups()
-        want = [capi.VP if "*" in a else ctype[a.split()[0]] for a in args.split(",")]
-        fn = getattr(capi.lib(), name)
-        assert fn.argtypes == want, name
-        assert fn.restype == ctype[ret], name
-        assert len(want) == NARGS[name], name
-
-
-def test_the_version_stays():
-    assert int(re.search(r"#define OFDIS_VERSION (\d+)", _header()).group(1)) == capi.OFDIS_VERSION == 3
-
-
-def test_the_constants_match_the_header():
-    hdr = _header()
-    scale = int(re.search(r"#define OFDIS_BOF_SCALE (\d+)", hdr).group(1))
-    words = int(re.search(r"#define OFDIS_BOF_MAX_WORDS (\d+)", hdr).group(1))
-    assert scale == capi.BOF_SCALE == tracking.BOF_SCALE == 510
-    assert words == capi.BOF_MAX_WORDS == tracking.BOF_MAX_WORDS == 16384
+def test_the_bounds_the_header_derives():
     assert 1152 * 255 * 255 < 2 ** 31 and 511 * 511 * 1152 * (2 ** 32 - 1) < 2 ** 62  # the header's two bounds
 
 
 def test_the_header_states_the_definition_and_its_consequences():
-    hdr = _header()
-    section = hdr[hdr.index("Bag-of-features encoding of those descriptors"):hdr.index("int ofdis_track_bof")]
+    section = abi.section("Bag-of-features encoding of those descriptors", "int ofdis_track_bof")
     for words in ("Identity:", "Known value:", "Ties:", "Sums:", "Contract independence:", "Not provided:", "k-means", "Fisher vectors",
                   "shape channel", "static tracks", "relies on no memset", r"q\*q\*S <= 510\*510\*h_e", "bit-identical",
                   "smallest k that attains the minimum", r"floor\(sqrt\(floor\(510\*510\*h_e / S\)\)\)", "normalize_descriptors_u8",
                   "codebook_assign_ref", "bof_ref"):
         assert re.search(words, section), words
-    desc = hdr[hdr.index("Trajectory-aligned descriptors of dense tracks"):hdr.index("int ofdis_track_descriptors")]
+    desc = abi.section("Trajectory-aligned descriptors of dense tracks", "int ofdis_track_descriptors")
     assert "ofdis_track_bof" in desc[desc.index("Not provided:"):]  # the descriptor section points here
 
 
@@ -79,10 +38,6 @@ class _Host:
         self.len, self.info = np.ones(64, np.int32), np.zeros(2, np.int64)
         self.codebook = np.zeros((5, D), np.uint8)
         self.words, self.dist, self.bof = np.zeros((64, 4), np.int32), np.zeros((64, 4), np.int32), np.zeros((4, 5), np.uint32)
-
-
-def _p(a, on=True):
-    return a.ctypes.data if on else None
 
 
 def _normalize(hb, hist=True, info=True, max_tracks=64, nxy=2, nt=2, desc=True, **_):
@@ -114,20 +69,14 @@ BAD = {"max_tracks": [0, -1, (1 << 24) + 1], "nxy": [0, -1, 5], "nt": [0, -1, 9]
 ENDS = {"max_tracks": [1, 1 << 24], "nxy": [1, 4], "nt": [1, 8], "nwords": [1, 16384], "min_len": [1, 2 ** 31 - 1]}
 
 
-def _rejected(rc, word):
-    assert rc == INVALID
-    msg = capi.lib().ofdis_last_error().decode()
-    assert msg and word in msg, (word, msg)
-
-
 @pytest.mark.parametrize("call,which", [(c, w) for c, ws in REQUIRED.items() for w in ws])
 def test_rejects_null_pointers(call, which):
-    _rejected(CALLS[call](_Host(), **{which: False}), {"length": "len"}.get(which, which))
+    abi.rejected(CALLS[call](_Host(), **{which: False}), {"length": "len"}.get(which, which))
 
 
 @pytest.mark.parametrize("call,name,value", [(c, n, v) for c, ns in VALUES.items() for n in ns for v in BAD[n]])
 def test_rejects_values_outside_their_ranges(call, name, value):
-    _rejected(CALLS[call](_Host(), **{name: value}), name)
+    abi.rejected(CALLS[call](_Host(), **{name: value}), name)
 
 
 @pytest.mark.parametrize("call", list(CALLS))
@@ -141,9 +90,9 @@ def test_the_value_checks_accept_their_closed_ranges(call):
     for at, name in enumerate(names[:-1]):
         later = names[at + 1]
         for v in ENDS[name]:
-            _rejected(CALLS[call](hb, **{name: v, later: BAD[later][0]}), later)
+            abi.rejected(CALLS[call](hb, **{name: v, later: BAD[later][0]}), later)
     # the optional pointers may be NULL: the call passes them and fails at the last value check
     last = names[-1]
     optional = {"assign": "dist", "fused": "words"}.get(call)
     if optional:
-        _rejected(CALLS[call](hb, **{optional: False, last: BAD[last][0]}), last)
+        abi.rejected(CALLS[call](hb, **{optional: False, last: BAD[last][0]}), last)

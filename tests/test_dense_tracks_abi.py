@@ -4,64 +4,20 @@ argument checks that return before any device work.  Host buffers stand in for t
 before it would launch.  The kernels, and the checks that need a context (creating one needs a device):
 tests/test_gpu_dense_tracks.py."""
 import math
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from of_dis_amd import build, capi, tracking
+import abi
+from of_dis_amd import capi, tracking
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INVALID = -1
 _f32 = np.float32
-SYMBOLS = ["ofdis_dense_tracks_cells", "ofdis_dense_tracks_work_bytes", "ofdis_seed_texture", "ofdis_dense_tracks",
-           "ofdis_batch_dense_tracks"]
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "ofdis.h")).read()
-
-
-@pytest.mark.parametrize("name", SYMBOLS)
-def test_declared_bound_and_exported(name):
-    assert name in build.abi_symbols()                      # a declaration outside the header's comments
-    assert name in capi.ABI_SYMBOLS
-    fn = getattr(capi.lib(), name)
-    assert fn.argtypes is not None
-    out = subprocess.run(["nm", "-D", "--defined-only", capi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert name in [line.split()[-1] for line in out.splitlines() if line.strip()]
-
-
-def test_prototypes_match_the_header():
-    """the binding's argument lists against the header's declarations, type by type"""
-    src = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    ctype = {"float": capi.C.c_float, "int": capi.C.c_int, "size_t": capi.C.c_size_t}
-    for name in SYMBOLS:
-        ret, args = re.search(r"\b(int|size_t) " + name + r"\s*\((.*?)\)\s*;", src, re.S).groups()
-        want = [capi.VP if "*" in a else ctype[a.split()[0]] for a in args.split(",")]
-        fn = getattr(capi.lib(), name)
-        assert fn.argtypes == want, name
-        assert fn.restype == ctype[ret], name
-
-
-def test_the_version_stays():
-    assert int(re.search(r"#define OFDIS_VERSION (\d+)", _header()).group(1)) == capi.OFDIS_VERSION == 3
-
-
-def test_the_constants_match_the_header():
-    hdr = _header()
-    assert re.search(r"#define OFDIS_DT_MAX_TRACKS \(1 << 24\)", hdr)
-    assert capi.DT_MAX_TRACKS == tracking.DT_MAX_TRACKS == 1 << 24
-    for name, value in (("STRIDE", 64), ("WINDOW", 7)):
-        assert int(re.search(r"#define OFDIS_DT_MAX_" + name + r" (\d+)", hdr).group(1)) == value
-        assert getattr(capi, "DT_MAX_" + name) == getattr(tracking, "DT_MAX_" + name) == value
+_p = abi.ptr
 
 
 def test_the_header_states_the_consequences():
-    hdr = _header()
-    section = hdr[hdr.index("Dense trajectories: the walk of ofdis_track_points"):hdr.index("int ofdis_batch_dense_tracks")]
+    section = abi.section("Dense trajectories: the walk of ofdis_track_points", "int ofdis_batch_dense_tracks")
     for words in ("Replay:", "Coverage:", "Slot order:", "Known count:", r"4 \* \(2wr\+1\)\^2 \* noc", "is not provided",
                   "relies on no memset"):
         assert re.search(words, section), words
@@ -117,10 +73,6 @@ class _Host:
         self.out = np.zeros((npairs + 1, h, w), np.uint8)
 
 
-def _p(a, on=True):
-    return a.ctypes.data if on else None
-
-
 def _dense(hb, frames=True, fw=True, rev=True, npairs=2, w=16, h=8, noc=1, stride=4, window=1, min_eig=5, max_len=0,
            alpha=capi.FB_ALPHA, beta=capi.FB_BETA, max_tracks=64, tracks=True, start=True, length=True, info=True, work=True,
            work_offset=0, work_bytes=None):
@@ -135,20 +87,14 @@ def _texture(hb, frames=True, out=True, nframes=3, w=16, h=8, noc=1, stride=4, w
     return capi.lib().ofdis_seed_texture(_p(hb.frames, frames), nframes, w, h, noc, stride, window, min_eig, _p(hb.out, out), None)
 
 
-def _rejected(rc, word=None):
-    assert rc == INVALID
-    msg = capi.lib().ofdis_last_error().decode()
-    assert msg and (word is None or word in msg), msg
-
-
 @pytest.mark.parametrize("which", ["frames", "fw", "tracks", "start", "info", "work"])
 def test_rejects_null_pointers(which):
-    _rejected(_dense(_Host(), **{which: False}), "flow_fw" if which == "fw" else which)
+    abi.rejected(_dense(_Host(), **{which: False}), "flow_fw" if which == "fw" else which)
 
 
 @pytest.mark.parametrize("which", ["frames", "out"])
 def test_seed_texture_rejects_null_pointers(which):
-    _rejected(_texture(_Host(), **{which: False}), which)
+    abi.rejected(_texture(_Host(), **{which: False}), which)
 
 
 @pytest.mark.parametrize("call", [_dense, _texture])
@@ -160,7 +106,7 @@ def test_seed_texture_rejects_null_pointers(which):
     (dict(w=0), "size"), (dict(h=0), "size"), (dict(w=-16), "size"), (dict(w=1 << 16, h=1 << 16), "size"),
 ], ids=lambda v: ",".join(f"{k}={x}" for k, x in v.items()) if isinstance(v, dict) else "")
 def test_rejects_what_both_calls_check(call, kw, word):
-    _rejected(call(_Host(), **kw), word)
+    abi.rejected(call(_Host(), **kw), word)
 
 
 @pytest.mark.parametrize("kw,word", [
@@ -170,18 +116,18 @@ def test_rejects_what_both_calls_check(call, kw, word):
     (dict(work_bytes=0), "work"), (dict(work_offset=4), "work"), (dict(work_offset=1), "work"),
 ], ids=lambda v: ",".join(f"{k}={x}" for k, x in v.items()) if isinstance(v, dict) else "")
 def test_rejects(kw, word):
-    _rejected(_dense(_Host(), **kw), word)
+    abi.rejected(_dense(_Host(), **kw), word)
 
 
 @pytest.mark.parametrize("nframes", [0, -1])
 def test_seed_texture_rejects_nframes(nframes):
-    _rejected(_texture(_Host(), nframes=nframes), "nframes")
+    abi.rejected(_texture(_Host(), nframes=nframes), "nframes")
 
 
 def test_a_work_buffer_one_byte_short_is_rejected():
     wb = capi.lib().ofdis_dense_tracks_work_bytes(2, 16, 8, 4)
     assert 0 < wb <= 1 << 16
-    _rejected(_dense(_Host(), work_bytes=wb - 1), "work")
+    abi.rejected(_dense(_Host(), work_bytes=wb - 1), "work")
 
 
 def test_the_value_checks_accept_their_closed_ranges():
@@ -191,13 +137,13 @@ def test_the_value_checks_accept_their_closed_ranges():
     for kw in (dict(max_tracks=1 << 24), dict(max_tracks=1), dict(stride=2), dict(stride=64), dict(window=0), dict(window=7),
                dict(min_eig=0), dict(min_eig=2 ** 31 - 1), dict(max_len=0), dict(max_len=2 ** 31 - 1), dict(alpha=0.0, beta=0.0),
                dict(noc=3), dict(rev=False), dict(length=False)):
-        _rejected(_dense(hb, **dict(dict(w=0), **kw)), "size")
+        abi.rejected(_dense(hb, **dict(dict(w=0), **kw)), "size")
     for kw in (dict(max_tracks=1 << 24), dict(max_len=2 ** 31 - 1), dict(rev=False), dict(length=False)):
-        _rejected(_dense(hb, work_bytes=8, **kw), "work")
+        abi.rejected(_dense(hb, work_bytes=8, **kw), "work")
 
 
 def test_batch_form_without_a_context():
     hb = _Host()
     rc = capi.lib().ofdis_batch_dense_tracks(None, hb.frames.ctypes.data, 0, 2, 4, 1, 5, 0, 1, capi.FB_ALPHA, capi.FB_BETA, 64,
                                              hb.tracks.ctypes.data, hb.start.ctypes.data, None, hb.info.ctypes.data, 16, 8, None)
-    _rejected(rc, "SEQUENCE")
+    abi.rejected(rc, "SEQUENCE")

@@ -2,61 +2,24 @@
 binding and the export list, and the argument checks that return before any device work.  Host buffers stand in for the device
 arrays: every call here returns before it would launch.  The kernel: tests/test_gpu_descriptors.py."""
 import math
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from of_dis_amd import build, capi, tracking
+import abi
+from of_dis_amd import capi, tracking
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INVALID = -1
 _f32 = np.float32
-SYMBOLS = ["ofdis_track_descriptor_dims", "ofdis_track_descriptors"]
+_p = abi.ptr
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "ofdis.h")).read()
-
-
-@pytest.mark.parametrize("name", SYMBOLS)
-def test_declared_bound_and_exported(name):
-    assert name in build.abi_symbols()                      # a declaration outside the header's comments
-    assert name in capi.ABI_SYMBOLS
-    fn = getattr(capi.lib(), name)
-    assert fn.argtypes is not None
-    out = subprocess.run(["nm", "-D", "--defined-only", capi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert name in [line.split()[-1] for line in out.splitlines() if line.strip()]
-
-
-def test_prototypes_match_the_header():
-    """the binding's argument lists against the header's declarations, type by type"""
-    src = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    ctype = {"float": capi.C.c_float, "int": capi.C.c_int}
-    for name in SYMBOLS:
-        ret, args = re.search(r"\b(int) " + name + r"\s*\((.*?)\)\s*;", src, re.S).groups()
-        want = [capi.VP if "*" in a else ctype[a.split()[0]] for a in args.split(",")]
-        fn = getattr(capi.lib(), name)
-        assert fn.argtypes == want, name
-        assert fn.restype == ctype[ret], name
-    assert len(capi.lib().ofdis_track_descriptors.argtypes) == 19
-
-
-def test_the_version_stays():
-    assert int(re.search(r"#define OFDIS_VERSION (\d+)", _header()).group(1)) == capi.OFDIS_VERSION == 3
-
-
-def test_the_constants_match_the_header():
-    value = int(re.search(r"#define OFDIS_DESC_MAX_PATCH (\d+)", _header()).group(1))
-    assert value == capi.DESC_MAX_PATCH == tracking.DESC_MAX_PATCH == 64
+def test_the_channels_have_33_bins():
     assert sum(bins for _, bins, _ in tracking.DESC_CHANNELS) == 33
 
 
 def test_the_header_states_the_definition_and_its_consequences():
-    hdr = _header()
-    section = hdr[hdr.index("Trajectory-aligned descriptors of dense tracks"):hdr.index("int ofdis_track_descriptors")]
+    section = abi.section("Trajectory-aligned descriptors of dense tracks", "int ofdis_track_descriptors")
     for words in ("Known value:", "Translation:", "Contract independence:", "Not provided:", "relies on no memset",
                   "ofdis_motion_compensate", r"N\*N\*lmax <= 65536", r"quant\(m, 16\)", r"quant\(m, 256\)", r"quant\(m, 4096\)",
                   r"t = j\*nt / lmax", "does not synchronise with the host"):
@@ -103,10 +66,6 @@ class _Host:
         self.shape = np.zeros((64, npairs, 2), _f32)
 
 
-def _p(a, on=True):
-    return a.ctypes.data if on else None
-
-
 def _call(hb, frames=True, fw=True, npairs=4, w=16, h=8, noc=1, tracks=True, start=True, length=True, info=True, lmax=3,
           max_tracks=64, patch=8, nxy=2, nt=2, min_flow=0.4, hist=True, shape=True):
     return capi.lib().ofdis_track_descriptors(_p(hb.frames, frames), _p(hb.flow, fw), npairs, w, h, noc, _p(hb.tracks, tracks),
@@ -114,15 +73,9 @@ def _call(hb, frames=True, fw=True, npairs=4, w=16, h=8, noc=1, tracks=True, sta
                                               nxy, nt, min_flow, _p(hb.hist, hist), _p(hb.shape, shape), None)
 
 
-def _rejected(rc, word=None):
-    assert rc == INVALID
-    msg = capi.lib().ofdis_last_error().decode()
-    assert msg and (word is None or word in msg), msg
-
-
 @pytest.mark.parametrize("which", ["frames", "fw", "tracks", "start", "length", "info", "hist"])
 def test_rejects_null_pointers(which):
-    _rejected(_call(_Host(), **{which: False}), {"fw": "flow_fw", "length": "len"}.get(which, which))
+    abi.rejected(_call(_Host(), **{which: False}), {"fw": "flow_fw", "length": "len"}.get(which, which))
 
 
 @pytest.mark.parametrize("kw,word", [
@@ -139,15 +92,15 @@ def test_rejects_null_pointers(which):
     (dict(min_flow=math.nan), "min_flow"),
 ], ids=lambda v: ",".join(f"{k}={x}" for k, x in v.items()) if isinstance(v, dict) else "")
 def test_rejects(kw, word):
-    _rejected(_call(_Host(), **kw), word)
+    abi.rejected(_call(_Host(), **kw), word)
 
 
 def test_rejects_a_tube_whose_sums_could_overflow():
     """N * N * lmax <= 65536: at N 64 that is lmax 16"""
     hb = _Host()
-    _rejected(_call(hb, patch=64, npairs=17, lmax=17), "65536")
-    _rejected(_call(hb, patch=2, npairs=16385, lmax=16385), "65536")
-    _rejected(_call(hb, patch=64, npairs=20, lmax=16, min_flow=-1.0), "min_flow")  # 64 * 64 * 16 passes, the next check fails
+    abi.rejected(_call(hb, patch=64, npairs=17, lmax=17), "65536")
+    abi.rejected(_call(hb, patch=2, npairs=16385, lmax=16385), "65536")
+    abi.rejected(_call(hb, patch=64, npairs=20, lmax=16, min_flow=-1.0), "min_flow")  # 64 * 64 * 16 passes, the next check fails
 
 
 def test_the_value_checks_accept_their_closed_ranges():
@@ -159,6 +112,6 @@ def test_the_value_checks_accept_their_closed_ranges():
                dict(patch=64, nxy=4), dict(patch=12, nxy=3), dict(patch=6, nxy=3), dict(nxy=1), dict(nxy=4), dict(nt=1),
                dict(nt=3), dict(npairs=8, lmax=8, nt=8), dict(patch=64, npairs=16, lmax=16), dict(patch=2, npairs=16384, lmax=16384),
                dict(w=1, h=1), dict(w=1 << 15, h=1 << 15), dict(shape=False)):
-        _rejected(_call(hb, **dict(kw, min_flow=-1.0)), "min_flow")
+        abi.rejected(_call(hb, **dict(kw, min_flow=-1.0)), "min_flow")
     # ... and min_flow's own closed end: 0 passes every check.  The call would launch, so it is only made where it cannot:
     # its accepted values are exercised on the device (tests/test_gpu_descriptors.py)

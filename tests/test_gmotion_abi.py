@@ -3,78 +3,20 @@ ofdis_motion_compensate and the two ofdis_batch_* twins) in the header, the bind
 checks that return before any device work.  Host buffers stand in for the device arrays: every call here returns before it
 would launch.  The kernels, and the checks that need a context (creating one needs a device): tests/test_gpu_gmotion.py."""
 import math
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from of_dis_amd import build, capi, gmotion
+import abi
+from of_dis_amd import capi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INVALID = -1
 _f32 = np.float32
-INT_SYMBOLS = ["ofdis_global_motion", "ofdis_motion_compensate", "ofdis_batch_global_motion", "ofdis_batch_motion_compensate"]
-SYMBOLS = ["ofdis_global_motion_work_bytes"] + INT_SYMBOLS
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "ofdis.h")).read()
-
-
-@pytest.mark.parametrize("name", SYMBOLS)
-def test_declared_bound_and_exported(name):
-    assert name in build.abi_symbols()                      # a declaration outside the header's comments
-    assert name in capi.ABI_SYMBOLS
-    fn = getattr(capi.lib(), name)
-    assert fn.argtypes is not None
-    out = subprocess.run(["nm", "-D", "--defined-only", capi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert name in [line.split()[-1] for line in out.splitlines() if line.strip()]
-
-
-def test_prototypes_match_the_header():
-    """the binding's argument lists against the header's declarations, type by type"""
-    src = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    ctype = {"float": capi.C.c_float, "int": capi.C.c_int, "size_t": capi.C.c_size_t}
-
-    def want(arg):
-        words = arg.replace("*", " * ").split()
-        if "*" in words:   # const float*, const uint8_t*, double*, const double*, long long*, void*, ofdis_batch*
-            assert words[-2] == "*" and words[0] in ("const", "float", "uint8_t", "double", "long", "void", "ofdis_batch"), arg
-            return capi.VP
-        assert len(words) == 2, arg
-        return ctype[words[0]]
-
-    for name in SYMBOLS:
-        ret, args = re.search(r"\b(int|size_t) " + name + r"\s*\((.*?)\)\s*;", src, re.S).groups()
-        assert getattr(capi.lib(), name).argtypes == [want(a) for a in args.split(",")], name
-        assert (ret == "size_t") == (getattr(capi.lib(), name).restype is capi.C.c_size_t), name
-    assert "double* models, long long* stats, void* work, size_t work_bytes" in re.sub(r"\s+", " ", src)
-
-
-def test_the_version_stays():
-    assert int(re.search(r"#define OFDIS_VERSION (\d+)", _header()).group(1)) == capi.OFDIS_VERSION == 3
-
-
-def test_constants_match_the_binding():
-    hdr = _header()
-    define = lambda name: re.search(r"#define " + name + r"\s+([0-9.]+)f?\s", hdr).group(1)
-    assert int(define("OFDIS_GM_MAX_SIDE")) == capi.GM_MAX_SIDE == gmotion.GM_MAX_SIDE == 8192
-    assert float(define("OFDIS_GM_MAX_FLOW")) == capi.GM_MAX_FLOW == gmotion.GM_MAX_FLOW == 4096.0
-    assert int(define("OFDIS_GM_MAX_ROUNDS")) == capi.GM_MAX_ROUNDS == gmotion.GM_MAX_ROUNDS == 8
-    enum = lambda name: int(re.search(r"\b" + name + r" = (\d+)", hdr).group(1))
-    for name in ("TRANSLATION_ONLY", "AFFINE", "OK_AFFINE", "TRANSLATION", "EMPTY", "INLIER", "OUTLIER", "INVALID"):
-        assert enum("OFDIS_GM_" + name) == getattr(capi, "GM_" + name) == getattr(gmotion, "GM_" + name), name
-    assert (capi.GM_TRANSLATION_ONLY, capi.GM_AFFINE) == (0, 1)
-    assert (capi.GM_OK_AFFINE, capi.GM_TRANSLATION, capi.GM_EMPTY) == (0, 1, 2)
-    assert (capi.GM_INLIER, capi.GM_OUTLIER, capi.GM_INVALID) == (0, 1, 2)
-    assert gmotion.FB_CONSISTENT == capi.FB_CONSISTENT
+_p = abi.ptr
 
 
 def test_the_header_derives_the_bound_and_names_the_caveat():
-    hdr = _header()
-    section = re.sub(r"\s+\*?\s*", " ", hdr[hdr.index("Global (camera) motion models"):hdr.index("#define OFDIS_GM_MAX_SIDE")])
+    section = re.sub(r"\s+\*?\s*", " ", abi.section("Global (camera) motion models", "#define OFDIS_GM_MAX_SIDE"))
     assert "2^59" in section and "int64 never overflows" in section
     assert "det == 0 exactly" in section and "only approximately 0" in section
     for word in ("homography", "similarity", "stabilisation", "reverse direction", "sequence driver"):
@@ -107,10 +49,6 @@ class _Host:
         self.label = np.zeros((npairs, h, w), np.uint8)
 
 
-def _p(a, on=True):
-    return a.ctypes.data if on else None
-
-
 def _fit(hb, flow=True, models=True, work=True, work_bytes=None, work_off=0, npairs=2, w=8, h=4, model=1, rounds=3, thresh=1.0):
     wb = hb.work.nbytes - 8 if work_bytes is None else work_bytes
     wp = hb.work.ctypes.data + work_off if work else None
@@ -123,36 +61,30 @@ def _comp(hb, flow=True, models=True, residual=True, label=True, npairs=2, w=8, 
                                               _p(hb.residual, residual), _p(hb.label, label), None)
 
 
-def _rejected(rc, word=None):
-    assert rc == INVALID
-    msg = capi.lib().ofdis_last_error().decode()
-    assert msg and (word is None or word in msg), msg
-
-
 @pytest.mark.parametrize("which", ["flow", "models"])
 def test_null_pointers(which):
-    _rejected(_fit(_Host(), **{which: False}))
-    _rejected(_comp(_Host(), **{which: False}))
+    abi.rejected(_fit(_Host(), **{which: False}))
+    abi.rejected(_comp(_Host(), **{which: False}))
 
 
 def test_compensate_needs_an_output():
-    _rejected(_comp(_Host(), residual=False, label=False))
+    abi.rejected(_comp(_Host(), residual=False, label=False))
 
 
 @pytest.mark.parametrize("model", [-1, 2, 3, 1 << 20])
 def test_rejects_model(model):
-    _rejected(_fit(_Host(), model=model), "model")
+    abi.rejected(_fit(_Host(), model=model), "model")
 
 
 @pytest.mark.parametrize("rounds", [0, -1, 9, 1 << 20])
 def test_rejects_rounds(rounds):
-    _rejected(_fit(_Host(), rounds=rounds), "rounds")
+    abi.rejected(_fit(_Host(), rounds=rounds), "rounds")
 
 
 @pytest.mark.parametrize("thresh", [0.0, -0.0, -1.0, math.nan, math.inf, -math.inf])
 def test_rejects_thresh(thresh):
-    _rejected(_fit(_Host(), thresh=thresh), "thresh")
-    _rejected(_comp(_Host(), thresh=thresh), "thresh")
+    abi.rejected(_fit(_Host(), thresh=thresh), "thresh")
+    abi.rejected(_comp(_Host(), thresh=thresh), "thresh")
 
 
 SIZES = [(0, 8, 4), (-1, 8, 4), (2, 0, 4), (2, 8, 0), (2, -8, 4), (2, 1 << 16, 1 << 16), (2, 8193, 4), (2, 8, 8193)]
@@ -160,30 +92,30 @@ SIZES = [(0, 8, 4), (-1, 8, 4), (2, 0, 4), (2, 8, 0), (2, -8, 4), (2, 1 << 16, 1
 
 @pytest.mark.parametrize("npairs,w,h", SIZES)
 def test_rejects_bad_sizes(npairs, w, h):
-    _rejected(_fit(_Host(), npairs=npairs, w=w, h=h), "size")
-    _rejected(_comp(_Host(), npairs=npairs, w=w, h=h), "size")
+    abi.rejected(_fit(_Host(), npairs=npairs, w=w, h=h), "size")
+    abi.rejected(_comp(_Host(), npairs=npairs, w=w, h=h), "size")
 
 
 def test_rejects_the_work_buffer():
     need = capi.lib().ofdis_global_motion_work_bytes(2, 8, 4)
     assert need == 2 * 96
-    _rejected(_fit(_Host(), work=False), "work")
-    _rejected(_fit(_Host(), work_bytes=need - 1), "work")
-    _rejected(_fit(_Host(), work_bytes=0), "work")
-    _rejected(_fit(_Host(), work_off=4), "work")
+    abi.rejected(_fit(_Host(), work=False), "work")
+    abi.rejected(_fit(_Host(), work_bytes=need - 1), "work")
+    abi.rejected(_fit(_Host(), work_bytes=0), "work")
+    abi.rejected(_fit(_Host(), work_off=4), "work")
 
 
 def test_the_value_checks_accept_their_ranges():
     """both models, rounds 1 and 8, tiny and huge thresholds, the largest side: the call gets as far as the work-buffer check"""
     for kw in (dict(model=0), dict(model=1), dict(rounds=1), dict(rounds=8), dict(thresh=1e-30), dict(thresh=3e38),
                dict(w=8192, h=1), dict(w=1, h=8192)):
-        _rejected(_fit(_Host(), work=False, **kw), "work")
+        abi.rejected(_fit(_Host(), work=False, **kw), "work")
 
 
 def test_batch_calls_without_a_context():
     hb = _Host()
     L = capi.lib()
-    _rejected(L.ofdis_batch_global_motion(None, 0, 2, 1, 3, 1.0, 0, capi.FB_ALPHA, capi.FB_BETA, _p(hb.models), _p(hb.stats), 8, 4,
+    abi.rejected(L.ofdis_batch_global_motion(None, 0, 2, 1, 3, 1.0, 0, capi.FB_ALPHA, capi.FB_BETA, _p(hb.models), _p(hb.stats), 8, 4,
                                           None))
-    _rejected(L.ofdis_batch_motion_compensate(None, 0, 2, _p(hb.models), 1.0, 0, capi.FB_ALPHA, capi.FB_BETA, _p(hb.residual),
+    abi.rejected(L.ofdis_batch_motion_compensate(None, 0, 2, _p(hb.models), 1.0, 0, capi.FB_ALPHA, capi.FB_BETA, _p(hb.residual),
                                               _p(hb.label), 8, 4, None))

@@ -2,62 +2,24 @@
 ofdis_codebook_update, ofdis_codebook_train) in the header, the binding and the export list, and the argument checks that return
 before any device work.  Host buffers stand in for the device arrays: every call here returns before it would launch.  The
 model: tests/test_kmeans_ref.py; the kernels: tests/test_gpu_kmeans.py."""
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from of_dis_amd import build, capi, tracking
+import abi
+from of_dis_amd import capi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INVALID = -1
-SYMBOLS = ["ofdis_codebook_train_work_bytes", "ofdis_codebook_seed", "ofdis_codebook_update", "ofdis_codebook_train"]
-NARGS = {"ofdis_codebook_train_work_bytes": 4, "ofdis_codebook_seed": 10, "ofdis_codebook_update": 14, "ofdis_codebook_train": 16}
+_p = abi.ptr
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "ofdis.h")).read()
-
-
-@pytest.mark.parametrize("name", SYMBOLS)
-def test_declared_bound_and_exported(name):
-    assert name in build.abi_symbols()                      # a declaration outside the header's comments
-    assert name in capi.ABI_SYMBOLS
-    fn = getattr(capi.lib(), name)
-    assert fn.argtypes is not None
-    out = subprocess.run(["nm", "-D", "--defined-only", capi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert name in [line.split()[-1] for line in out.splitlines() if line.strip()]
-
-
-def test_prototypes_match_the_header():
-    """the binding's argument lists and return types against the header's declarations, type by type"""
-    src = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    ctype = {"int": capi.C.c_int, "size_t": capi.C.c_size_t}
-    for name in SYMBOLS:
-        ret, args = re.search(r"\b(int|size_t) " + name + r"\s*\((.*?)\)\s*;", src, re.S).groups()
-        want = [capi.VP if "*" in a else ctype[a.split()[0]] for a in args.split(",")]
-        fn = getattr(capi.lib(), name)
-        assert fn.argtypes == want, name
-        assert fn.restype == ctype[ret], name
-        assert len(want) == NARGS[name], name
-    assert capi.lib().ofdis_codebook_update.argtypes[12] == capi.lib().ofdis_codebook_train.argtypes[14] == capi.C.c_size_t
-
-
-def test_the_version_stays():
-    assert int(re.search(r"#define OFDIS_VERSION (\d+)", _header()).group(1)) == capi.OFDIS_VERSION == 3
-
-
-def test_the_constants_match_the_header():
-    iters = int(re.search(r"#define OFDIS_KMEANS_MAX_ITERS (\d+)", _header()).group(1))
-    assert iters == capi.KMEANS_MAX_ITERS == tracking.KMEANS_MAX_ITERS == 1000
+def test_the_bounds_the_header_derives():
     assert 2 ** 24 * 255 < 2 ** 32 and 2 ** 24 * 1152 * 255 * 255 < 2 ** 55   # the header's two bounds
 
 
 def test_the_header_states_the_definition_and_its_consequences():
-    hdr = _header()
-    section = hdr[hdr.index("K-means training of the bag-of-features codebook"):hdr.index("int ofdis_codebook_train(")]
+    hdr = abi.header()
+    section = abi.section("K-means training of the bag-of-features codebook", "int ofdis_codebook_train(")
     assert hdr.index("int ofdis_track_bof") < hdr.index("K-means training of the bag-of-features codebook")   # its own section, after
     for words in ("Members\\.", "Seeding \\(ofdis_codebook_seed\\)", "Update \\(ofdis_codebook_update\\)",
                   "Training \\(ofdis_codebook_train\\)", r"s_k = floor\(\(2k\+1\)\*n / \(2\*nwords\)\)", "cyclically",
@@ -67,7 +29,7 @@ def test_the_header_states_the_definition_and_its_consequences():
                   "re-seeding of empty words", r"k-means\+\+", "subsampling", "early exit", "Fisher vectors", "shape channel",
                   "OFDIS_KMEANS_MAX_ITERS", "before the last update", "codebook_seed_ref", "codebook_update_ref", "codebook_train_ref"):
         assert re.search(words, section), words
-    bof = hdr[hdr.index("Bag-of-features encoding of those descriptors"):hdr.index("int ofdis_track_bof")]
+    bof = abi.section("Bag-of-features encoding of those descriptors", "int ofdis_track_bof")
     assert "ofdis_codebook_train" in bof[bof.index("Not provided:"):]   # the bag-of-features section points here
 
 
@@ -89,10 +51,6 @@ class _Host:
         self.codebook, self.counts = np.zeros((NWORDS, D), np.uint8), np.zeros((4, NWORDS), np.uint32)
         self.stats = np.zeros((capi.KMEANS_MAX_ITERS, 4, 2), np.int64)
         self.work = np.zeros(_need() // 8 + 2, np.int64)   # 8-byte aligned, a little more than needed
-
-
-def _p(a, on=True):
-    return a.ctypes.data if on else None
 
 
 def _work(hb, work, work_bytes):
@@ -134,20 +92,14 @@ BAD = {"max_tracks": [0, -1, (1 << 24) + 1], "nxy": [0, -1, 5], "nt": [0, -1, 9]
 ENDS = {"max_tracks": [1, 1 << 24], "nxy": [1, 4], "nt": [1, 8], "nwords": [1, 16384], "min_len": [1, 2 ** 31 - 1], "iters": [1, 1000]}
 
 
-def _rejected(rc, word):
-    assert rc == INVALID
-    msg = capi.lib().ofdis_last_error().decode()
-    assert msg and word in msg, (word, msg)
-
-
 @pytest.mark.parametrize("call,which", [(c, w) for c, ws in REQUIRED.items() for w in ws])
 def test_rejects_null_pointers(call, which):
-    _rejected(CALLS[call](_Host(), **{which: False}), which)
+    abi.rejected(CALLS[call](_Host(), **{which: False}), which)
 
 
 @pytest.mark.parametrize("call,name,value", [(c, n, v) for c, ns in VALUES.items() for n in ns for v in BAD[n]])
 def test_rejects_values_outside_their_ranges(call, name, value):
-    _rejected(CALLS[call](_Host(), **{name: value}), name)
+    abi.rejected(CALLS[call](_Host(), **{name: value}), name)
 
 
 @pytest.mark.parametrize("call", list(CALLS))
@@ -162,10 +114,10 @@ def test_the_value_checks_accept_their_closed_ranges(call):
     for at, name in enumerate(names[:-1]):
         later = names[at + 1]
         for v in ENDS[name]:
-            _rejected(CALLS[call](hb, **{name: v, later: BAD[later][0]}), later)
+            abi.rejected(CALLS[call](hb, **{name: v, later: BAD[later][0]}), later)
     if call != "seed":
         for v in ENDS[names[-1]]:
-            _rejected(CALLS[call](hb, **{names[-1]: v, "work_bytes": _need() - 1}), "work")
+            abi.rejected(CALLS[call](hb, **{names[-1]: v, "work_bytes": _need() - 1}), "work")
 
 
 @pytest.mark.parametrize("call", list(CALLS))
@@ -174,20 +126,20 @@ def test_the_optional_pointers_may_be_null(call):
     hb = _Host()
     last = VALUES[call][-1]
     for optional in OPTIONAL[call]:
-        _rejected(CALLS[call](hb, **{optional: False, last: BAD[last][0]}), last)
+        abi.rejected(CALLS[call](hb, **{optional: False, last: BAD[last][0]}), last)
         if call != "seed":
-            _rejected(CALLS[call](hb, **{optional: False, "work_bytes": _need() - 1}), "work")
+            abi.rejected(CALLS[call](hb, **{optional: False, "work_bytes": _need() - 1}), "work")
 
 
 @pytest.mark.parametrize("call", ["update", "train"])
 def test_rejects_a_small_or_misaligned_work_buffer(call):
     hb = _Host()
     for nbytes in (0, 8, _need() - 8, _need() - 1):
-        _rejected(CALLS[call](hb, work_bytes=nbytes), "work")
+        abi.rejected(CALLS[call](hb, work_bytes=nbytes), "work")
     for shift in (1, 2, 4, 7):   # enough bytes behind it, but not on a multiple of 8
-        _rejected(CALLS[call](hb, work=shift, work_bytes=_need()), "aligned")
+        abi.rejected(CALLS[call](hb, work=shift, work_bytes=_need()), "aligned")
     # the size is that of the call's own max_tracks and nwords, not of some other
-    _rejected(CALLS[call](hb, max_tracks=MAX_TRACKS + 1000, work_bytes=_need()), "work")
+    abi.rejected(CALLS[call](hb, max_tracks=MAX_TRACKS + 1000, work_bytes=_need()), "work")
 
 
 def test_the_work_bytes_are_zero_for_rejected_sizes_and_grow_with_the_sizes():

@@ -4,30 +4,27 @@ ofdis_batch_upsample_lr).  Argument checks that return before any device work, a
 The computations on the device: tests/test_gpu_stereo_lr.py."""
 import ctypes as C
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 
+import abi
 import natural
 import oracle
 import stereo_lr_ref as ref
 from of_dis_amd import capi
 from of_dis_amd.params import oppoint
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ALPHA, BETA = 0.01, 0.5  # (the issue's constants; OFDIS_FB_ALPHA / OFDIS_FB_BETA)
 
 
 def test_constants_match_the_header():
-    hdr = open(os.path.join(ROOT, "include", "ofdis.h")).read()
-    assert int(re.search(r"#define OFDIS_BATCH_STEREO_LR (\d+)u", hdr).group(1)) == capi.BATCH_STEREO_LR == 2
-    m = re.search(r"OFDIS_FILL_NONE = (\d), OFDIS_FILL_INVALIDATE = (\d), OFDIS_FILL_BACKGROUND = (\d)", hdr)
-    assert tuple(int(x) for x in m.groups()) == (capi.FILL_NONE, capi.FILL_INVALIDATE, capi.FILL_BACKGROUND) == (0, 1, 2)
+    assert abi.define("OFDIS_BATCH_STEREO_LR") == capi.BATCH_STEREO_LR == 2
+    fills = tuple(abi.enumerator("OFDIS_FILL_" + n) for n in ("NONE", "INVALIDATE", "BACKGROUND"))
+    assert fills == (capi.FILL_NONE, capi.FILL_INVALIDATE, capi.FILL_BACKGROUND) == (0, 1, 2)
     assert (ref.FILL_NONE, ref.FILL_INVALIDATE, ref.FILL_BACKGROUND) == (0, 1, 2)
-    assert int(re.search(r"#define OFDIS_LR_FUSED_MAX_WIDTH (\d+)", hdr).group(1)) == capi.LR_FUSED_MAX_WIDTH
-    assert int(re.search(r"#define OFDIS_VERSION\s+(\d+)", hdr).group(1)) == capi.OFDIS_VERSION == 3
+    assert abi.define("OFDIS_LR_FUSED_MAX_WIDTH") == capi.LR_FUSED_MAX_WIDTH
+    assert abi.define("OFDIS_VERSION") == capi.OFDIS_VERSION == 3
     for name in ("ofdis_batch_flow_mirror", "ofdis_batch_level_flow_mirror", "ofdis_lr_check", "ofdis_disparity_fill",
                  "ofdis_batch_upsample_lr"):
         assert name in capi.ABI_SYMBOLS and hasattr(capi.lib(), name)

@@ -3,23 +3,18 @@ that return before any device work, and properties of the numpy statement of the
 buffers stand in for the device arrays: every call here returns before it would launch.  The kernels, and the checks that
 need a context (creating one needs a device): tests/test_gpu_track.py."""
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 
+import abi
 from of_dis_amd import capi, tracking
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INVALID = -1
 _f32 = np.float32
 
 
 def test_max_points_matches_the_header():
-    hdr = open(os.path.join(ROOT, "include", "ofdis.h")).read()
-    m = re.search(r"#define OFDIS_TRACK_MAX_POINTS \(1 << (\d+)\)", hdr)
-    assert (1 << int(m.group(1))) == capi.TRACK_MAX_POINTS
+    assert abi.define("OFDIS_TRACK_MAX_POINTS") == capi.TRACK_MAX_POINTS
 
 
 def test_defaults_match_the_binding():
@@ -39,36 +34,31 @@ class _Host:
 
 def _track(hb, fw=True, rev=True, seeds=True, tracks=True, npairs=2, w=8, h=4, npoints=3, max_steps=0, alpha=capi.FB_ALPHA,
            beta=capi.FB_BETA):
-    p = lambda a, on: a.ctypes.data if on else None
+    p = abi.ptr
     return capi.lib().ofdis_track_points(p(hb.flow, fw), p(hb.flow, rev), npairs, w, h, p(hb.seeds, seeds),
                                          hb.seed_frame.ctypes.data, npoints, max_steps, alpha, beta, p(hb.tracks, tracks),
                                          hb.counts.ctypes.data, None)
 
 
-def _rejected(rc):
-    assert rc == INVALID
-    assert capi.lib().ofdis_last_error()
-
-
 @pytest.mark.parametrize("which", ["fw", "seeds", "tracks"])
 def test_track_points_rejects_null_pointers(which):
-    _rejected(_track(_Host(), **{which: False}))
+    abi.rejected(_track(_Host(), **{which: False}))
 
 
 @pytest.mark.parametrize("npoints", [0, -1, (1 << 24) + 1])
 def test_track_points_rejects_npoints(npoints):
-    _rejected(_track(_Host(), npoints=npoints))
+    abi.rejected(_track(_Host(), npoints=npoints))
     assert "npoints" in capi.lib().ofdis_last_error().decode()
 
 
 def test_track_points_rejects_negative_max_steps():
-    _rejected(_track(_Host(), max_steps=-1))
+    abi.rejected(_track(_Host(), max_steps=-1))
     assert "max_steps" in capi.lib().ofdis_last_error().decode()
 
 
 @pytest.mark.parametrize("npairs,w,h", [(0, 8, 4), (-1, 8, 4), (2, 0, 4), (2, 8, 0), (2, -8, 4), (2, 1 << 16, 1 << 16)])
 def test_track_points_rejects_bad_sizes(npairs, w, h):
-    _rejected(_track(_Host(), npairs=npairs, w=w, h=h))
+    abi.rejected(_track(_Host(), npairs=npairs, w=w, h=h))
     assert "size" in capi.lib().ofdis_last_error().decode()
 
 
@@ -76,13 +66,13 @@ def test_track_points_rejects_bad_sizes(npairs, w, h):
                                 dict(alpha=math.inf), dict(beta=math.nan)], ids=lambda kw: ",".join(f"{k}={v}" for k, v in kw.items()))
 def test_track_points_rejects_alpha_beta(kw):
     """as ofdis_fb_check rejects them, with and without the reverse flow"""
-    _rejected(_track(_Host(), **kw))
-    _rejected(_track(_Host(), rev=False, **kw))
+    abi.rejected(_track(_Host(), **kw))
+    abi.rejected(_track(_Host(), rev=False, **kw))
 
 
 def test_track_points_checks_pass_the_largest_point_count():
     """npoints = OFDIS_TRACK_MAX_POINTS passes the point-count check: the call gets as far as the size check"""
-    _rejected(_track(_Host(), npoints=capi.TRACK_MAX_POINTS, npairs=0))
+    abi.rejected(_track(_Host(), npoints=capi.TRACK_MAX_POINTS, npairs=0))
     assert "size" in capi.lib().ofdis_last_error().decode()
 
 
@@ -90,7 +80,7 @@ def test_batch_track_points_without_a_context():
     hb = _Host()
     rc = capi.lib().ofdis_batch_track_points(None, 0, 2, hb.seeds.ctypes.data, None, 3, 0, 1, capi.FB_ALPHA, capi.FB_BETA,
                                              hb.tracks.ctypes.data, None, 8, 4, None)
-    _rejected(rc)
+    abi.rejected(rc)
 
 
 # ------------------------------------------------------------------ the numpy statement of the definition

@@ -5,48 +5,20 @@ launch.  The kernels: tests/test_gpu_track_select.py; the definition: tests/test
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from of_dis_amd import build, capi, tracking
+import abi
+from of_dis_amd import capi, tracking
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INVALID = -1
 _f32 = np.float32
-SYMBOLS = ["ofdis_track_select_defaults", "ofdis_track_select_work_bytes", "ofdis_track_select"]
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "ofdis.h")).read()
-
-
-@pytest.mark.parametrize("name", SYMBOLS)
-def test_declared_bound_and_exported(name):
-    assert name in build.abi_symbols()                      # a declaration outside the header's comments
-    assert name in capi.ABI_SYMBOLS
-    fn = getattr(capi.lib(), name)
-    assert fn.argtypes is not None
-    out = subprocess.run(["nm", "-D", "--defined-only", capi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert name in [line.split()[-1] for line in out.splitlines() if line.strip()]
-
-
-def test_prototypes_match_the_header():
-    """the binding's argument lists against the header's declarations, type by type"""
-    src = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    ctype = {"float": capi.C.c_float, "int": capi.C.c_int, "size_t": capi.C.c_size_t, "void": None}
-    for name in SYMBOLS:
-        ret, args = re.search(r"\b(int|size_t|void)\s+" + name + r"\s*\((.*?)\)\s*;", src, re.S).groups()
-        want = [capi.VP if "*" in a else ctype[a.split()[0]] for a in args.split(",")]
-        fn = getattr(capi.lib(), name)
-        assert fn.argtypes == want, name
-        assert fn.restype == ctype[ret], name
-    assert len(capi.lib().ofdis_track_select.argtypes) == 23
+_p = abi.ptr
 
 
 def test_the_struct_matches_the_header():
-    src = _header()
+    src = abi.header()
     body = re.search(r"typedef struct ofdis_track_select_params \{(.*?)\} ofdis_track_select_params;", src, re.S).group(1)
     fields = re.findall(r"^\s*(int|float|unsigned)\s+(\w+);", body, re.M)
     ctype = {"int": capi.C.c_int, "float": capi.C.c_float, "unsigned": capi.C.c_uint}
@@ -54,16 +26,7 @@ def test_the_struct_matches_the_header():
     assert capi.C.sizeof(capi.TrackSelectParams) == 28
 
 
-def test_the_constants_match_the_header():
-    hdr = _header()
-    enum = re.search(r"enum \{ (OFDIS_TS_KEPT.*?) \};", hdr, re.S).group(1)
-    values = {k: int(v) for k, v in re.findall(r"OFDIS_(TS_\w+) = (\d+)", enum)}
-    assert len(values) == 7
-    for k, v in values.items():
-        assert v == getattr(capi, k) == getattr(tracking, k), k
-    assert sorted(values.values()) == list(range(7))
-    mask = int(re.search(r"#define OFDIS_TS_ALL_TESTS (0x[0-9A-Fa-f]+)u", hdr).group(1), 16)
-    assert mask == capi.TS_ALL_TESTS == tracking.TS_ALL_TESTS == 0x3F
+def test_the_lanes_match_the_kernel_source():
     assert f"kTsLanes = {capi.TRACK_SELECT_LANES};" in open(os.path.join(ROOT, "of_dis_amd", "csrc", "ofdis_track_select.hip")).read()
 
 
@@ -85,8 +48,8 @@ def test_the_defaults():
 
 
 def test_the_header_states_the_definition_and_its_consequences():
-    hdr = _header()
-    section = hdr[hdr.index("Track selection: the stage"):hdr.index("int ofdis_track_select(")]
+    hdr = abi.header()
+    section = abi.section("Track selection: the stage", "int ofdis_track_select(")
     for words in ("Drop-in:", "Identity:", "Sums:", "Known values:", "Contract independence:", "Not provided:", "relies on no memset",
                   "FIRST test that holds", "sequential over ascending j", r"L < max\(min_len, 1\)", r"sx < min_std && sy < min_std",
                   r"sx > max_std \|\| sy > max_std", r"mmax > max_step && mmax > S \* max_step_share", r"rmax <= min_camera",
@@ -129,10 +92,6 @@ class _Host:
         self.work = np.zeros(64, np.uint64)
 
 
-def _p(a, on=True):
-    return a.ctypes.data if on else None
-
-
 def _call(hb, tracks=True, start=True, length=True, info=True, lmax=3, max_tracks=64, models=False, npairs=5, w=16, h=8, params=True,
           code=True, counts=True, max_tracks_out=64, tracks_out=True, start_out=True, len_out=True, info_out=True, index=True,
           shape=True, work=True, work_bytes=None, work_offset=0, **fields):
@@ -146,15 +105,9 @@ def _call(hb, tracks=True, start=True, length=True, info=True, lmax=3, max_track
         need if work_bytes is None else work_bytes, None)
 
 
-def _rejected(rc, word=None):
-    assert rc == INVALID
-    msg = capi.lib().ofdis_last_error().decode()
-    assert msg and (word is None or word in msg), msg
-
-
 @pytest.mark.parametrize("which", ["tracks", "start", "length", "info", "params", "tracks_out", "start_out", "len_out", "info_out", "work"])
 def test_rejects_null_pointers(which):
-    _rejected(_call(_Host(), **{which: False}), {"length": "len"}.get(which, which))
+    abi.rejected(_call(_Host(), **{which: False}), {"length": "len"}.get(which, which))
 
 
 @pytest.mark.parametrize("kw,word", [
@@ -177,7 +130,7 @@ def test_rejects_null_pointers(which):
     (dict(work_offset=4), "work"), (dict(work_offset=1), "work"),
 ], ids=lambda v: ",".join(f"{k}={x}" for k, x in v.items()) if isinstance(v, dict) else "")
 def test_rejects(kw, word):
-    _rejected(_call(_Host(), **kw), word)
+    abi.rejected(_call(_Host(), **kw), word)
 
 
 def test_the_value_checks_accept_their_closed_ranges():
@@ -192,6 +145,6 @@ def test_the_value_checks_accept_their_closed_ranges():
                dict(min_camera=0.0), dict(tests=0), dict(tests=0x3F), dict(tests=0x20),
                dict(code=False), dict(counts=False), dict(index=False), dict(shape=False),
                dict(code=False, counts=False, index=False, shape=False)):
-        _rejected(_call(hb, **dict(kw, work_bytes=8)), "work")
+        abi.rejected(_call(hb, **dict(kw, work_bytes=8)), "work")
     # ... and the work buffer's own closed end, ofdis_track_select_work_bytes exactly, passes every check.  The call would
     # launch, so it is only made where it cannot: its accepted values are exercised on the device (tests/test_gpu_track_select.py)
