@@ -8,12 +8,9 @@ import pytest
 
 import gen_synth
 from of_dis_amd import tracking
+from stereo_lr_ref import bits as _bits
 
 _f32 = np.float32
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, _f32).view(np.uint32)
 
 
 @functools.lru_cache(maxsize=None)

@@ -13,6 +13,7 @@ import pytest
 import gen_synth
 from common import assert_bits_equal, synth_case
 from of_dis_amd.params import oppoint, padded_size
+from seq_products import check_levels, fill_u8, levels
 
 pytestmark = pytest.mark.gpu
 _f32 = np.float32
@@ -25,14 +26,6 @@ def _u8_frames(w, h, noc, seeds):
     return np.stack([a for a, _ in pairs]), np.stack([b for _, b in pairs])
 
 
-def _fill_u8(gpu, b, ia, ib, w, h):
-    da, db = gpu.Dev(ia), gpu.Dev(ib)
-    b.build_pyramids_u8(da.ptr, db.ptr, w, h)
-    gpu.check(gpu.lib().ofdis_sync(None))
-    da.free()
-    db.free()
-
-
 def _fill_host(b, cases, swap=False):
     """cases: list of (pa, pb) host pyramids per frame ([img, dx, dy] lists over levels)"""
     for k, (pa, pb) in enumerate(cases):
@@ -42,15 +35,6 @@ def _fill_host(b, cases, swap=False):
         b.upload_b_gradients(k, pb[1], pb[2])
 
 
-def _levels(b, p, reverse=False):
-    return {l: (b.level_flow_reverse(l) if reverse else b.level_flow(l)) for l in range(p.sc_l, p.sc_f + 1)}
-
-
-def _check_levels(got, want, what):
-    for l in want:
-        assert_bits_equal(got[l], want[l], f"{what}, level {l}")
-
-
 def _run_three(gpu, p, n, fill, data):
     """(reverse context: forward levels, reverse levels), plain context on (A, B), plain context on (B, A)"""
     rb = gpu.Batch(p, n, reverse=True)
@@ -58,16 +42,16 @@ def _run_three(gpu, p, n, fill, data):
     ps = gpu.Batch(p, n)
     if fill == "u8":
         ia, ib, w, h = data
-        _fill_u8(gpu, rb, ia, ib, w, h)
-        _fill_u8(gpu, pf, ia, ib, w, h)
-        _fill_u8(gpu, ps, ib, ia, w, h)
+        fill_u8(gpu, rb, ia, ib, w, h)
+        fill_u8(gpu, pf, ia, ib, w, h)
+        fill_u8(gpu, ps, ib, ia, w, h)
     else:
         _fill_host(rb, data)
         _fill_host(pf, data)
         _fill_host(ps, data, swap=True)
     for b in (rb, pf, ps):
         b.run()
-    out = (_levels(rb, p), _levels(rb, p, True), _levels(pf, p), _levels(ps, p))
+    out = (levels(rb, p), levels(rb, p, "reverse"), levels(pf, p), levels(ps, p))
     for b in (rb, pf, ps):
         b.close()
     return out
@@ -117,8 +101,8 @@ def test_reverse_equals_swapped_forward(gpu, orc, contract, noc, opp, fb, tv, n,
         fwd, rev, plain_fwd, plain_swp = _run_three(gpu, p, n, fill, data)
     finally:
         gpu.restore_tuning(old)
-    _check_levels(fwd, plain_fwd, "forward flow of the REVERSE context vs a plain context")
-    _check_levels(rev, plain_swp, "reverse flow vs a plain context on the swapped pairs")
+    check_levels(fwd, plain_fwd, "forward flow of the REVERSE context vs a plain context")
+    check_levels(rev, plain_swp, "reverse flow vs a plain context on the swapped pairs")
     assert not np.array_equal(rev[p.sc_l], fwd[p.sc_l])
     if contract == 0 and fb == 0:  # the restatement does not cover usefbcon
         for k in range(len(seeds)):
@@ -137,8 +121,8 @@ def test_reverse_across_tv_variants(gpu, orc, tv_variant):
     p = cases[0][0]
     data = [(c[1], c[2]) for c in (cases[0], cases[1], cases[1], cases[0])]
     fwd, rev, plain_fwd, plain_swp = _run_three(gpu, p, 4, "host", data)
-    _check_levels(fwd, plain_fwd, f"{tv_variant}: forward")
-    _check_levels(rev, plain_swp, f"{tv_variant}: reverse")
+    check_levels(fwd, plain_fwd, f"{tv_variant}: forward")
+    check_levels(rev, plain_swp, f"{tv_variant}: reverse")
     for k in range(2):
         _, pa, pb, _, _ = cases[k]
         assert_bits_equal(rev[p.sc_l][k], orc.flow(p, pb[0], pb[1], pb[2], pa[0]), f"{tv_variant}: oracle, frame {k}")
@@ -344,8 +328,8 @@ def test_upsample_bidir(gpu, w, h, opp, noc, n, first, count):
     p.width, p.height = padded_size(w, h, p.sc_f)
     ia, ib = _u8_frames(w, h, noc, [5100 + k for k in range(n)])
     rb, ps = gpu.Batch(p, n, reverse=True), gpu.Batch(p, n)
-    _fill_u8(gpu, rb, ia, ib, w, h)
-    _fill_u8(gpu, ps, ib, ia, w, h)
+    fill_u8(gpu, rb, ia, ib, w, h)
+    fill_u8(gpu, ps, ib, ia, w, h)
     rb.run()
     ps.run()
     count = n - first if count is None else count

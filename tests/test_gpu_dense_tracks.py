@@ -16,17 +16,12 @@ import pytest
 
 import gen_synth
 from of_dis_amd import tracking
-from of_dis_amd.params import oppoint, padded_size
+from seq_products import INVALID, assert_same_bits, flag_contexts, run_context, smooth_clip
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _f32 = np.float32
-INVALID = -1
 T_MAX = 2 ** 31 - 1
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, _f32).view(np.uint32)
 
 
 def assert_dense_equal(got, want, what):
@@ -38,11 +33,7 @@ def assert_dense_equal(got, want, what):
         if not np.array_equal(g, w):
             i = int(np.flatnonzero(g != w)[0])
             raise AssertionError(f"{what}: {(g != w).sum()} of {g.size} {name} values differ; first at slot {i}: {g[i]} vs {w[i]}")
-    if not np.array_equal(_bits(gt), _bits(wt)):
-        bad = np.argwhere(_bits(gt) != _bits(wt))
-        j, i, c = bad[0]
-        raise AssertionError(f"{what}: {len(bad)} of {gt.size} values differ; first at step {j}, slot {i}, component {c}: "
-                             f"{gt[j, i, c]!r} vs {wt[j, i, c]!r}")
+    assert_same_bits(gt, wt, what + ", tracks [step][slot][component]")
 
 
 def _threshold(frame0, stride, window, share):
@@ -221,7 +212,8 @@ def test_every_entry_is_written_and_nothing_else(gpu, with_len, capped):
         assert_dense_equal(got, want, "guarded")
     else:
         assert (length == 0xABABABAB).all()
-        assert np.array_equal(tracks[:, :n], _bits(want[0])) and np.array_equal(start[:n].view(np.int32), want[1])
+        assert_same_bits(tracks[:, :n].view(_f32), want[0], "len = NULL, tracks")
+        assert np.array_equal(start[:n].view(np.int32), want[1])
 
 
 # ------------------------------------------------------------------ 4. replay through ofdis_track_points
@@ -235,37 +227,10 @@ def test_every_slot_replays_through_track_points(gpu, with_rev):
     assert n > 0 and (start > 0).any()
     replay, counts = gpu.track_points(fw, r, tracks[0], start, max_steps=max_len)
     assert np.array_equal(counts, length)
-    assert np.array_equal(_bits(replay), _bits(tracking.to_frame_major(tracks, start, length, npairs)))
+    assert_same_bits(replay, tracking.to_frame_major(tracks, start, length, npairs), "replay")
 
 
 # ------------------------------------------------------------------ 5. the batch form against the standalone call
-CLIP_STEP = 0.15  # of gen_synth's flow (up to 12 px) per frame: at most 1.8 px per pair, 9 px over five pairs
-
-
-@functools.lru_cache(maxsize=None)
-def _clip(w, h, noc, nframes, seed=6200):
-    """nframes frames of one scene in smooth motion: gen_synth's texture displaced by 0, 1, 2, ... times CLIP_STEP of its flow"""
-    frames = [gen_synth.make_pair(w, h, seed, noc)[0]]
-    frames += [gen_synth.make_pair(w, h, seed, noc, flow_scale=CLIP_STEP * k)[1] for k in range(1, nframes)]
-    return np.ascontiguousarray(np.stack(frames))
-
-
-def _sequence_context(gpu, w, h, noc, n, contract, reverse=True, pipeline=1):
-    p = oppoint(2, w, h, noc=noc, verbosity=0)
-    p.width, p.height = padded_size(w, h, p.sc_f)
-    d = gpu.Dev(_clip(w, h, noc, n + 1))
-    old = gpu.set_tuning(contract=contract)
-    try:
-        b = gpu.Batch(p, n, sequence=True, reverse=reverse)
-        if pipeline > 1:
-            b.set_pipeline(pipeline)
-        b.build_pyramids_u8_seq(d.ptr, w, h)
-        b.run()
-    finally:
-        gpu.restore_tuning(old)
-    return b, d
-
-
 def _clip_threshold(frames, stride, window):
     """a T that 50 - 90 % of frame 0's cells pass (checked on the restatement)"""
     T = _threshold(frames[0], stride, window, 0.7)
@@ -290,9 +255,9 @@ STRIDE, WINDOW = 5, 2
 def test_batch_form_matches_standalone_on_the_materialised_flows(gpu, noc, w, h, n, contract, pipeline):
     """max_len 0 and 2, with the consistency test (against upsample_bidir's two flows) and without it, the full range and the
     sub-range (1, n - 1)"""
-    frames = _clip(w, h, noc, n + 1)
+    frames = smooth_clip(w, h, noc, n + 1)
     T = _clip_threshold(frames, STRIDE, WINDOW)
-    b, d = _sequence_context(gpu, w, h, noc, n, contract, pipeline=pipeline)
+    b, (d,) = run_context(gpu, frames, "seq_rev", contract=contract, pipeline=pipeline)
     try:
         before = b.device_bytes()
         fused = {(first, count, fb, ml): b.dense_tracks(d.ptr, w, h, STRIDE, WINDOW, T, ml, fb_check=fb, first=first, count=count)
@@ -314,9 +279,9 @@ def test_batch_form_matches_standalone_on_the_materialised_flows(gpu, noc, w, h,
 @pytest.mark.parametrize("contract", [0, 1], ids=["exact", "fused"])
 def test_batch_form_without_the_test_on_a_forward_only_sequence(gpu, contract):
     w, h, n = 250, 107, 3
-    frames = _clip(w, h, 1, n + 1)
+    frames = smooth_clip(w, h, 1, n + 1)
     T = _clip_threshold(frames, STRIDE, WINDOW)
-    b, d = _sequence_context(gpu, w, h, 1, n, contract, reverse=False)
+    b, (d,) = run_context(gpu, frames, "seq", contract=contract)
     try:
         got = b.dense_tracks(d.ptr, w, h, STRIDE, WINDOW, T, 2, fb_check=False)
         fw = b.upsample_frames(0, n, w, h)
@@ -329,8 +294,9 @@ def test_batch_form_grows_its_work_buffer(gpu):
     """one pair first, then all n: the second call needs more than the first left, allocates again and gives what a context
     that never held the smaller buffer gives; a call that needs no more allocates nothing"""
     w, h, n = 250, 107, 3
-    T = _clip_threshold(_clip(w, h, 1, n + 1), STRIDE, WINDOW)
-    b, d = _sequence_context(gpu, w, h, 1, n, 0)
+    frames = smooth_clip(w, h, 1, n + 1)
+    T = _clip_threshold(frames, STRIDE, WINDOW)
+    b, (d,) = run_context(gpu, frames)
     try:
         sizes = [b.device_bytes()]
         b.dense_tracks(d.ptr, w, h, STRIDE, WINDOW, T, first=0, count=1)
@@ -342,7 +308,7 @@ def test_batch_form_grows_its_work_buffer(gpu):
     finally:
         b.close()
     assert sizes[0] < sizes[1] < sizes[2] == sizes[3], sizes
-    fresh, d = _sequence_context(gpu, w, h, 1, n, 0)
+    fresh, (d,) = run_context(gpu, frames)
     try:
         want = fresh.dense_tracks(d.ptr, w, h, STRIDE, WINDOW, T, first=0, count=n)
     finally:
@@ -353,12 +319,7 @@ def test_batch_form_grows_its_work_buffer(gpu):
 # ------------------------------------------------------------------ 6. checks that need a context
 @pytest.fixture(scope="module")
 def contexts(gpu):
-    p = oppoint(2, 256, 112)
-    made = dict(plain=gpu.Batch(p, 3), reverse=gpu.Batch(p, 3, reverse=True), seq=gpu.Batch(p, 3, sequence=True),
-                seq_rev=gpu.Batch(p, 3, sequence=True, reverse=True))
-    yield made
-    for b in made.values():
-        b.close()
+    yield from flag_contexts(gpu)
 
 
 def _batch_call(gpu, b, frames=True, first=0, count=3, stride=5, window=2, min_eig=10, max_len=2, fb_check=1, alpha=0.01,
@@ -402,7 +363,7 @@ def test_flow_images_dense_tracks(gpu, tmp_path):
     what the standalone call makes of the .flo / .rev.flo files the same run writes; without --sequence it is refused"""
     from PIL import Image
     w, h, n = 250, 107, 3
-    frames = _clip(w, h, 1, n + 1)
+    frames = smooth_clip(w, h, 1, n + 1)
     T = _clip_threshold(frames, STRIDE, WINDOW)
     paths = []
     for k, f in enumerate(frames):

@@ -19,7 +19,8 @@ import pytest
 
 import gen_synth
 from of_dis_amd import tracking
-from test_gpu_dense_tracks import STRIDE, WINDOW, _clip, _clip_threshold, _sequence_context, _threshold, _wild_flows
+from seq_products import run_context, smooth_clip
+from test_gpu_dense_tracks import STRIDE, WINDOW, _clip_threshold, _threshold, _wild_flows
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -215,9 +216,9 @@ def test_known_value_on_the_device(gpu):
 def test_end_to_end_through_a_sequence_context(gpu, contract):
     """upsample_bidir -> dense_tracks -> track_descriptors, all on the device, against the model on the same arrays"""
     w, h, n, N, nxy, nt = 250, 107, 3, 16, 2, 3
-    frames = _clip(w, h, 1, n + 1)
+    frames = smooth_clip(w, h, 1, n + 1)
     T = _clip_threshold(frames, STRIDE, WINDOW)
-    b, d = _sequence_context(gpu, w, h, 1, n, contract)
+    b, _ = run_context(gpu, frames, "seq_rev", contract=contract)
     try:
         fw, rev, _, _ = b.upsample_bidir(w, h, outputs=(True, True, False, False))
     finally:
@@ -237,7 +238,7 @@ def test_flow_images_descriptors(gpu, tmp_path):
     --dense-tracks it is refused"""
     from PIL import Image
     w, h, n = 250, 107, 3
-    frames = _clip(w, h, 1, n + 1)
+    frames = smooth_clip(w, h, 1, n + 1)
     T = _clip_threshold(frames, STRIDE, WINDOW)
     paths = []
     for k, f in enumerate(frames):

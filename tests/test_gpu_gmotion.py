@@ -15,33 +15,21 @@ import gen_synth
 from of_dis_amd import gmotion
 from of_dis_amd.gmotion import (GM_AFFINE, GM_EMPTY, GM_INLIER, GM_INVALID, GM_OK_AFFINE, GM_OUTLIER, GM_TRANSLATION,
                                 GM_TRANSLATION_ONLY, global_motion_ref, motion_compensate_ref)
-from of_dis_amd.params import oppoint, padded_size
+from seq_products import (FB_REJECTS, INVALID, RANGE_REJECTS, SIZE_REJECTS, assert_same_bits, flag_contexts, run_context,
+                          smooth_clip)
 
 pytestmark = pytest.mark.gpu
 _f32 = np.float32
-INVALID = -1
-
-
-def assert_bits_equal(got, want, what):
-    """arrays of one dtype compared as raw bit patterns"""
-    assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape, got.dtype, want.dtype)
-    bits = {1: np.uint8, 4: np.uint32, 8: np.uint64}[got.dtype.itemsize]
-    g, w = np.ascontiguousarray(got).view(bits), np.ascontiguousarray(want).view(bits)
-    if not np.array_equal(g, w):
-        bad = np.argwhere(g != w)
-        i = tuple(bad[0])
-        raise AssertionError(f"{what}: {len(bad)} of {g.size} elements differ; first at {i}: {got[i]!r} ({g[i]:#x}) vs "
-                             f"{want[i]!r} ({w[i]:#x})")
 
 
 def assert_fit_equal(got, want, what):
-    assert_bits_equal(got[0], want[0], what + ", models")
-    assert_bits_equal(got[1], want[1], what + ", stats")
+    assert_same_bits(got[0], want[0], what + ", models")
+    assert_same_bits(got[1], want[1], what + ", stats")
 
 
 def assert_compensated_equal(got, want, what):
-    assert_bits_equal(got[0], want[0], what + ", residual")
-    assert_bits_equal(got[1], want[1], what + ", label")
+    assert_same_bits(got[0], want[0], what + ", residual")
+    assert_same_bits(got[1], want[1], what + ", label")
 
 
 # ------------------------------------------------------------------ 1. standalone kernels against the restatement
@@ -113,10 +101,10 @@ def test_either_output_alone_and_the_residual_in_place(gpu):
     assert np.isnan(want[0]).any() and np.isinf(want[0]).any() and len(np.unique(want[1])) == 3
     res, none = gpu.motion_compensate(flow, models, mask, thresh=1.0, label=False)
     assert none is None
-    assert_bits_equal(res, want[0], "label = NULL")
+    assert_same_bits(res, want[0], "label = NULL")
     none, label = gpu.motion_compensate(flow, models, mask, thresh=1.0, residual=False)
     assert none is None
-    assert_bits_equal(label, want[1], "residual = NULL")
+    assert_same_bits(label, want[1], "residual = NULL")
     for w, h in ((37, 11), (64, 16)):   # 4-byte and 16-byte stores over the array they were read from
         flow, mask = _random_case(3, w, h, "wild")
         models, _ = global_motion_ref(flow, mask, rounds=2, thresh=1.0)
@@ -130,7 +118,7 @@ def test_either_output_alone_and_the_residual_in_place(gpu):
     dwork = gpu.Dev(nbytes=wb)
     gpu.check(gpu.lib().ofdis_global_motion(df.ptr, dm.ptr, npairs, w, h, GM_AFFINE, 3, 1.0, dmod.ptr, None, dwork.ptr, wb, None))
     gpu.check(gpu.lib().ofdis_sync(None))
-    assert_bits_equal(dmod.get((npairs, 6), np.float64), global_motion_ref(flow, mask, rounds=3, thresh=1.0)[0], "stats = NULL")
+    assert_same_bits(dmod.get((npairs, 6), np.float64), global_motion_ref(flow, mask, rounds=3, thresh=1.0)[0], "stats = NULL")
 
 
 def test_more_pairs_than_xcds(gpu):
@@ -215,8 +203,8 @@ def test_unaligned_outputs_take_narrower_stores_with_the_same_bytes(gpu, w, h):
         r, l = dr.get((rbytes + 2 * roff,), np.uint8), dl.get((lbytes + 2 * loff,), np.uint8)
         for buf, off, n in ((r, roff, rbytes), (l, loff, lbytes)):
             assert (buf[:off] == 0xAB).all() and (buf[off + n:] == 0xAB).all(), (roff, loff)
-        assert_bits_equal(r[roff:roff + rbytes].copy().view(_f32).reshape(flow.shape), want[0], f"residual at offset {roff}")
-        assert_bits_equal(l[loff:loff + lbytes].reshape(npairs, h, w), want[1], f"labels at offset {loff}")
+        assert_same_bits(r[roff:roff + rbytes].copy().view(_f32).reshape(flow.shape), want[0], f"residual at offset {roff}")
+        assert_same_bits(l[loff:loff + lbytes].reshape(npairs, h, w), want[1], f"labels at offset {loff}")
 
 
 # ------------------------------------------------------------------ 2. the block scene
@@ -235,44 +223,6 @@ def test_block_scene_on_the_kernel(gpu):
 
 
 # ------------------------------------------------------------------ 3. fused kernels against the standalone ones
-CLIP_STEP = 0.15  # of gen_synth's flow (up to 12 px) per frame: at most 1.8 px per pair
-
-
-@functools.lru_cache(maxsize=None)
-def _clip(w, h, noc, nframes, seed=6200):
-    """nframes frames of one scene in smooth motion, as _clip of tests/test_gpu_tfilter.py makes them"""
-    frames = [gen_synth.make_pair(w, h, seed, noc)[0]]
-    frames += [gen_synth.make_pair(w, h, seed, noc, flow_scale=CLIP_STEP * k)[1] for k in range(1, nframes)]
-    return np.ascontiguousarray(np.stack(frames))
-
-
-def _context(gpu, clip, kind="seq_rev", opp=2, contract=0, pipeline=1):
-    """a context over the pairs of the clip [n + 1][h][w] (+ [3]), built and run.  kind: "plain" and "reverse" hold every pair's
-    two frames (A = clip[:-1], B = clip[1:]), "seq_rev" is SEQUENCE | REVERSE.  Returns (context, the device arrays it reads)."""
-    n, h, w = clip.shape[0] - 1, clip.shape[1], clip.shape[2]
-    noc = 1 if clip.ndim == 3 else 3
-    p = oppoint(opp, w, h, noc=noc, verbosity=0)
-    p.width, p.height = padded_size(w, h, p.sc_f)
-    old = gpu.set_tuning(contract=contract)
-    try:
-        if kind == "seq_rev":
-            devs = [gpu.Dev(clip)]
-            b = gpu.Batch(p, n, sequence=True, reverse=True)
-        else:
-            devs = [gpu.Dev(clip[:-1]), gpu.Dev(clip[1:])]
-            b = gpu.Batch(p, n, reverse=kind == "reverse")
-        if pipeline > 1:
-            b.set_pipeline(pipeline)
-        if kind == "seq_rev":
-            b.build_pyramids_u8_seq(devs[0].ptr, w, h)
-        else:
-            b.build_pyramids_u8(devs[0].ptr, devs[1].ptr, w, h)
-        b.run()
-    finally:
-        gpu.restore_tuning(old)
-    return b, devs
-
-
 FUSED_FITS = [(GM_AFFINE, 3, 1.0), (GM_TRANSLATION_ONLY, 2, 0.5)]
 
 # (kind, noc, op, w, h, n pairs, first, count, pipeline, contract, alpha, beta)
@@ -300,8 +250,8 @@ FUSED_CASES = [
 def test_fused_matches_standalone(gpu, kind, noc, opp, w, h, n, first, count, pipeline, contract, alpha, beta):
     """fb_check = 0 against the standalone calls on upsample_frames' output with mask NULL; fb_check = 1 (contexts with the
     reverse direction) against them on out_fw and mask_fw of upsample_bidir"""
-    clip = _clip(w, h, noc, n + 1)
-    b, devs = _context(gpu, clip, kind, opp, contract, pipeline)
+    clip = smooth_clip(w, h, noc, n + 1)
+    b, devs = run_context(gpu, clip, kind, opp, contract, pipeline)
     fused = {}
     try:
         bytes_before = b.device_bytes()
@@ -334,7 +284,7 @@ def test_fused_matches_standalone(gpu, kind, noc, opp, w, h, n, first, count, pi
         if not (fb and alpha == 0.0 and beta == 0.0):   # something was fitted in the comparison
             assert (standalone[1][:, 0] > 0).all()
     if kind != "plain":
-        assert_bits_equal(fw, plain, "upsample_bidir's forward flow is upsample_frames'")
+        assert_same_bits(fw, plain, "upsample_bidir's forward flow is upsample_frames'")
         if alpha == 0.0 and beta == 0.0:   # (a test nothing but an exact round trip passes: most pixels are masked here)
             assert (mf != 0).mean() > 0.5
         else:
@@ -344,8 +294,8 @@ def test_fused_matches_standalone(gpu, kind, noc, opp, w, h, n, first, count, pi
 def test_fused_into_device_buffers_on_a_stream(gpu):
     """models_ptr / stats_ptr / out_ptr / stream: the same bytes as the host-array form; stats = NULL and one output alone"""
     w, h, n = 256, 112, 2
-    clip = _clip(w, h, 1, n + 1)
-    b, devs = _context(gpu, clip)
+    clip = smooth_clip(w, h, 1, n + 1)
+    b, devs = run_context(gpu, clip)
     s = gpu.Stream()
     try:
         want_fit = b.global_motion(w, h, rounds=3, thresh=1.0, fb_check=True)
@@ -356,20 +306,20 @@ def test_fused_into_device_buffers_on_a_stream(gpu):
         # (the models are read from the device buffer the fit just wrote, on the same stream: no host round trip)
         assert b.motion_compensate(dm.ptr, w, h, thresh=1.0, fb_check=True, out_ptr=(dr.ptr, dl.ptr), stream=s.ptr) is None
         gpu.check(gpu.lib().ofdis_sync(s.ptr))
-        assert_bits_equal(dm.get((n, 6), np.float64), want_fit[0], "device-buffer form, models")
-        assert_bits_equal(dst.get((n, 3), np.int64), want_fit[1], "device-buffer form, stats")
-        assert_bits_equal(dr.get(want[0].shape, _f32), want[0], "device-buffer form, residual")
-        assert_bits_equal(dl.get(want[1].shape, np.uint8), want[1], "device-buffer form, label")
+        assert_same_bits(dm.get((n, 6), np.float64), want_fit[0], "device-buffer form, models")
+        assert_same_bits(dst.get((n, 3), np.int64), want_fit[1], "device-buffer form, stats")
+        assert_same_bits(dr.get(want[0].shape, _f32), want[0], "device-buffer form, residual")
+        assert_same_bits(dl.get(want[1].shape, np.uint8), want[1], "device-buffer form, label")
         dm2 = gpu.Dev(nbytes=n * 48)
         assert b.global_motion(w, h, rounds=3, thresh=1.0, fb_check=True, models_ptr=dm2.ptr, stream=s.ptr) is None
         gpu.check(gpu.lib().ofdis_sync(s.ptr))
-        assert_bits_equal(dm2.get((n, 6), np.float64), want_fit[0], "stats = NULL")
+        assert_same_bits(dm2.get((n, 6), np.float64), want_fit[0], "stats = NULL")
         res, none = b.motion_compensate(want_fit[0], w, h, thresh=1.0, fb_check=True, label=False)
         assert none is None
-        assert_bits_equal(res, want[0], "label = NULL")
+        assert_same_bits(res, want[0], "label = NULL")
         none, label = b.motion_compensate(want_fit[0], w, h, thresh=1.0, fb_check=True, residual=False)
         assert none is None
-        assert_bits_equal(label, want[1], "residual = NULL")
+        assert_same_bits(label, want[1], "residual = NULL")
     finally:
         b.close()
         s.close()
@@ -378,13 +328,7 @@ def test_fused_into_device_buffers_on_a_stream(gpu):
 # ------------------------------------------------------------------ 4. checks that need a context
 @pytest.fixture(scope="module")
 def contexts(gpu):
-    p = oppoint(2, 256, 112)
-    made = dict(plain=gpu.Batch(p, 3), reverse=gpu.Batch(p, 3, reverse=True), seq=gpu.Batch(p, 3, sequence=True),
-                seq_rev=gpu.Batch(p, 3, sequence=True, reverse=True), stereo=gpu.Batch(p.copy(selectmode=2), 3),
-                stereo_lr=gpu.Batch(p.copy(selectmode=2), 3, stereo_lr=True))
-    yield made
-    for b in made.values():
-        b.close()
+    yield from flag_contexts(gpu, stereo=True)
 
 
 def _fit_call(gpu, b, first=0, count=3, model=1, rounds=3, thresh=1.0, fb=0, alpha=0.01, beta=0.5, models=True, wo=256, ho=112):
@@ -416,12 +360,8 @@ def test_fb_check_names_the_missing_flag(gpu, contexts, which):
         assert "OFDIS_BATCH_REVERSE" in gpu.lib().ofdis_last_error().decode()
 
 
-COMMON_REJECTS = [
-    dict(models=False), dict(first=-1), dict(count=0), dict(count=-1), dict(first=1, count=3), dict(first=3, count=1), dict(count=4),
-    dict(wo=0), dict(ho=0), dict(wo=257), dict(ho=113),
-    dict(thresh=0.0), dict(thresh=-1.0), dict(thresh=math.nan), dict(thresh=math.inf),
-    dict(fb=2), dict(fb=-1), dict(alpha=-0.01), dict(beta=-0.5), dict(alpha=math.nan), dict(beta=math.inf),
-]
+COMMON_REJECTS = [dict(models=False)] + RANGE_REJECTS + SIZE_REJECTS + [
+    dict(thresh=0.0), dict(thresh=-1.0), dict(thresh=math.nan), dict(thresh=math.inf), dict(fb=2), dict(fb=-1)] + FB_REJECTS
 _ids = lambda kw: ",".join(f"{k}={v}" for k, v in kw.items())
 
 
@@ -477,7 +417,7 @@ def test_end_to_end_camera_and_moving_block(gpu):
     from scipy.ndimage import binary_dilation, binary_erosion
     w, h, cam, blk, side, at = 256, 128, (3, -2), (-5, 4), 70, (120, 30)
     A, B, inside = _moving_block_pair(w, h, cam, blk, side, at)
-    b, devs = _context(gpu, np.stack([A, B]), "reverse")
+    b, devs = run_context(gpu, np.stack([A, B]), "reverse")
     try:
         fits = {r: b.global_motion(w, h, model=GM_AFFINE, rounds=r, thresh=1.0, fb_check=True) for r in (1, 3)}
         label = b.motion_compensate(fits[3][0], w, h, thresh=1.0, fb_check=True, residual=False)[1][0]
@@ -506,7 +446,7 @@ def test_camera_motion_tool(gpu, tmp_path):
     import sys
     from PIL import Image
     w, h, n = 250, 107, 2
-    clip = _clip(w, h, 1, n + 1)
+    clip = smooth_clip(w, h, 1, n + 1)
     paths = []
     for k, f in enumerate(clip):
         paths.append(str(tmp_path / f"f{k}.png"))
@@ -516,7 +456,7 @@ def test_camera_motion_tool(gpu, tmp_path):
     res = subprocess.run([sys.executable, tool, "--rounds", "2", "--thresh", "0.75", "--labels", stem] + paths + [csv],
                          capture_output=True, text=True, timeout=300)
     assert res.returncode == 0, (res.stdout, res.stderr)
-    b, devs = _context(gpu, clip)
+    b, devs = run_context(gpu, clip)
     try:
         models, stats = b.global_motion(w, h, rounds=2, thresh=0.75, fb_check=True)
         label = b.motion_compensate(models, w, h, thresh=0.75, fb_check=True, residual=False)[1]
@@ -526,11 +466,11 @@ def test_camera_motion_tool(gpu, tmp_path):
     assert len(rows) == n and all(len(r) == 9 for r in rows)
     got_models = np.array([[float(v) for v in r[:6]] for r in rows], np.float64)
     got_stats = np.array([[int(v) for v in r[6:]] for r in rows], np.int64)
-    assert_bits_equal(got_models, models, "the tool's models")
-    assert_bits_equal(got_stats, stats, "the tool's stats")
+    assert_same_bits(got_models, models, "the tool's models")
+    assert_same_bits(got_stats, stats, "the tool's stats")
     assert (stats[:, 2] == GM_OK_AFFINE).all() and (stats[:, 1] > 0).all()
     grey = np.array([0, 127, 255], np.uint8)
     for k in range(n):
-        assert_bits_equal(np.asarray(Image.open(f"{stem}_{k:03d}.png")), grey[label[k]], f"label map {k}")
+        assert_same_bits(np.asarray(Image.open(f"{stem}_{k:03d}.png")), grey[label[k]], f"label map {k}")
     res = subprocess.run([sys.executable, tool, "--rounds", "9"] + paths, capture_output=True, text=True, timeout=300)
     assert res.returncode != 0 and "--rounds" in (res.stderr + res.stdout)

@@ -11,6 +11,7 @@ import pytest
 
 import gen_synth
 from of_dis_amd.params import oppoint, padded_size
+from seq_products import FB_REJECTS, SIZE_REJECTS, assert_same_bits
 
 pytestmark = pytest.mark.gpu
 _f32 = np.float32
@@ -88,14 +89,6 @@ def ref_frames(A, B, F01, F10, M01, M10, times):
     return out[..., 0] if gray else out
 
 
-def assert_u8_equal(got, want, what):
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    if not np.array_equal(got, want):
-        bad = np.argwhere(got != want)
-        i = tuple(bad[0])
-        raise AssertionError(f"{what}: {len(bad)} of {got.size} bytes differ; first at {i}: {got[i]} vs {want[i]}")
-
-
 # ------------------------------------------------------------------ standalone kernel against the restatement
 T_SETS = [
     pytest.param([0.5], id="t0.5"),
@@ -140,7 +133,7 @@ def test_standalone_matches_the_definition(gpu, noc, w, h, kind):
     for masks in ((M01, M10), (None, None), (M01, None), (None, M10)):
         got = gpu.interpolate(A, B, F01, F10, times, *masks)
         want = ref_frames(A, B, F01, F10, *masks, times)
-        assert_u8_equal(got, want, f"noc {noc}, {w}x{h}, {kind}, masks {[m is not None for m in masks]}")
+        assert_same_bits(got, want, f"noc {noc}, {w}x{h}, {kind}, masks {[m is not None for m in masks]}")
 
 
 @pytest.mark.parametrize("times", T_SETS)
@@ -148,7 +141,7 @@ def test_standalone_matches_the_definition(gpu, noc, w, h, kind):
 def test_standalone_time_sets(gpu, noc, times):
     rng = np.random.default_rng(77 + noc)
     A, B, F01, F10, M01, M10 = _random_case(rng, 3, 70, 23, noc, "wild")
-    assert_u8_equal(gpu.interpolate(A, B, F01, F10, times, M01, M10), ref_frames(A, B, F01, F10, M01, M10, times),
+    assert_same_bits(gpu.interpolate(A, B, F01, F10, times, M01, M10), ref_frames(A, B, F01, F10, M01, M10, times),
                     f"noc {noc}, times {times}")
 
 
@@ -160,8 +153,8 @@ def test_end_times_return_the_frames(gpu, noc):
     F01 *= 20
     for masks in ((M01, M10), (None, None)):
         got = gpu.interpolate(A, B, F01, F10, [0.0, 1.0], *masks)
-        assert_u8_equal(got[:, 0], A, "t = 0")
-        assert_u8_equal(got[:, 1], B, "t = 1")
+        assert_same_bits(got[:, 0], A, "t = 0")
+        assert_same_bits(got[:, 1], B, "t = 1")
 
 
 @pytest.mark.parametrize("noc", [1, 3])
@@ -180,7 +173,7 @@ def test_unaligned_out_takes_byte_stores_with_the_same_bytes(gpu, noc, w, h):
     gpu.check(gpu.lib().ofdis_sync(None))
     o = do.get((want.nbytes + 2 * guard,), np.uint8)
     assert (o[:guard] == 0xAB).all() and (o[guard + want.nbytes:] == 0xAB).all()
-    assert_u8_equal(o[guard:guard + want.nbytes].reshape(want.shape), want, "out, one byte off")
+    assert_same_bits(o[guard:guard + want.nbytes].reshape(want.shape), want, "out, one byte off")
 
 
 @pytest.mark.parametrize("d", [(4, -2), (-6, 3), (2, 0)])
@@ -267,9 +260,9 @@ def test_fused_matches_standalone_on_upsample_bidir(gpu, noc, opp, w, h, n, firs
         b.close()
     sl = slice(first, first + count)
     standalone = gpu.interpolate(ia[sl], ib[sl], fw, rev, times, mf, mr)
-    assert_u8_equal(fused, standalone, "fused vs standalone on upsample_bidir's outputs")
+    assert_same_bits(fused, standalone, "fused vs standalone on upsample_bidir's outputs")
     if count <= 2:
-        assert_u8_equal(standalone, ref_frames(ia[sl], ib[sl], fw, rev, mf, mr, times), "standalone vs the definition")
+        assert_same_bits(standalone, ref_frames(ia[sl], ib[sl], fw, rev, mf, mr, times), "standalone vs the definition")
 
 
 def test_fused_into_a_device_buffer_on_a_stream(gpu):
@@ -284,7 +277,7 @@ def test_fused_into_a_device_buffer_on_a_stream(gpu):
         out = gpu.Dev(nbytes=want.nbytes)
         assert b.interpolate(da.ptr, db.ptr, w, h, [0.5, 0.75], out_ptr=out.ptr, stream=s.ptr) is None
         gpu.check(gpu.lib().ofdis_sync(s.ptr))
-        assert_u8_equal(out.get(want.shape, np.uint8), want, "device-buffer form")
+        assert_same_bits(out.get(want.shape, np.uint8), want, "device-buffer form")
     finally:
         b.close()
         s.close()
@@ -320,9 +313,7 @@ def test_batch_interpolate_rejects_a_plain_context(gpu, contexts):
     dict(img=False), dict(out=False), dict(times_null=True), dict(ntimes=0), dict(ntimes=17, times=[0.5] * 17),
     dict(times=[math.nan]), dict(times=[1.5]), dict(times=[-0.25]), dict(times=[math.inf]), dict(times=[0.5, -math.inf]),
     dict(first=-1), dict(count=0), dict(first=1, count=2), dict(first=2, count=1), dict(count=3),
-    dict(wo=0), dict(ho=0), dict(wo=257), dict(ho=113),
-    dict(alpha=-0.01), dict(beta=-0.5), dict(alpha=math.nan), dict(beta=math.inf),
-], ids=lambda kw: ",".join(f"{k}={v if not isinstance(v, list) else len(v)}" for k, v in kw.items()))
+] + SIZE_REJECTS + FB_REJECTS, ids=lambda kw: ",".join(f"{k}={v if not isinstance(v, list) else len(v)}" for k, v in kw.items()))
 def test_batch_interpolate_rejects(gpu, contexts, kw):
     """host buffers stand in for the device arrays: every call returns before it would launch"""
     _, rev = contexts
@@ -368,6 +359,6 @@ def test_occlusion_masks_change_the_output(gpu, noc):
     finally:
         b.close()
     assert (mf != 0).any() and (mr != 0).any()
-    assert_u8_equal(fused, ref_frames(ia, ib, fw, rev, mf, mr, times), "fused vs the definition")
+    assert_same_bits(fused, ref_frames(ia, ib, fw, rev, mf, mr, times), "fused vs the definition")
     unmasked = gpu.interpolate(ia, ib, fw, rev, times)
     assert (unmasked != fused).sum() > 0

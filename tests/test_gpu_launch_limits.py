@@ -16,6 +16,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import seq_products
 import test_gpu_gmotion as gm_tests
 import test_gpu_stabilize as stab_tests
 from launch_hooks import chunk_walk, hooks, launch, quad_grid, trips
@@ -365,8 +366,8 @@ def seq_context(gpu):
     """a real SEQUENCE | REVERSE context over 27 gray frames of 64x48 at operating point 2, run: what its batch calls return, and
     its level flows and UpGeom as ofdis_products.hip makes it (finish_begin)"""
     w, h = SHAPES[0]
-    clip = gm_tests._clip(w, h, 1, NPAIRS + 1)
-    b, devs = gm_tests._context(gpu, clip, "seq_rev")
+    clip = seq_products.smooth_clip(w, h, 1, NPAIRS + 1)
+    b, devs = seq_products.run_context(gpu, clip, "seq_rev")
     try:
         p = b.p
         fw, rev = b.level_flow(p.sc_l), b.level_flow_reverse(p.sc_l)
@@ -388,8 +389,8 @@ def seq_context(gpu):
 def reverse_context(gpu):
     """the same clip's pairs in a plain REVERSE context: ofdis_batch_interpolate and the level flows it reads"""
     w, h = SHAPES[0]
-    clip = gm_tests._clip(w, h, 1, NPAIRS + 1)
-    b, devs = gm_tests._context(gpu, clip, "reverse")
+    clip = seq_products.smooth_clip(w, h, 1, NPAIRS + 1)
+    b, devs = seq_products.run_context(gpu, clip, "reverse")
     try:
         p = b.p
         fw, rev = b.level_flow(p.sc_l), b.level_flow_reverse(p.sc_l)

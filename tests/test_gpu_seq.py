@@ -12,6 +12,7 @@ import gen_synth
 import oracle
 from common import assert_bits_equal
 from of_dis_amd.params import oppoint, padded_size
+from seq_products import check_levels, fill_u8, levels
 
 pytestmark = pytest.mark.gpu
 _f32 = np.float32
@@ -45,11 +46,7 @@ def _sync(gpu):
 
 def _fill_pairs(gpu, b, frames, w, h):
     """a plain / reverse context from the same clip, the parent's way: every interior frame twice"""
-    da, db = gpu.Dev(frames[:-1]), gpu.Dev(frames[1:])
-    b.build_pyramids_u8(da.ptr, db.ptr, w, h)
-    _sync(gpu)
-    da.free()
-    db.free()
+    fill_u8(gpu, b, frames[:-1], frames[1:], w, h)
 
 
 def _fill_seq(gpu, b, frames, w, h):
@@ -62,15 +59,6 @@ def _fill_seq(gpu, b, frames, w, h):
 def _host_pyramids(p, frames):
     O = oracle.c_oracle()
     return [O.build_pyramid(p, f) for f in frames]
-
-
-def _levels(b, p, reverse=False):
-    return {l: (b.level_flow_reverse(l) if reverse else b.level_flow(l)) for l in range(p.sc_l, p.sc_f + 1)}
-
-
-def _check_levels(got, want, what):
-    for l in want:
-        assert_bits_equal(got[l], want[l], f"{what}, level {l}")
 
 
 def _planes(gpu, b, p, kind, nframes):
@@ -125,10 +113,10 @@ def test_sequence_equals_pairwise_contexts(gpu, contract, noc, opp, fb, tv, n, f
                     b.upload_frame(k, pyr[k][0], pyr[k][1], pyr[k][2])
         for b in (ref, sr, sf):
             b.run()
-        want_fw, want_rev = _levels(ref, p), _levels(ref, p, True)
-        _check_levels(_levels(sr, p), want_fw, "forward flow, sequence + reverse context")
-        _check_levels(_levels(sr, p, True), want_rev, "reverse flow, sequence + reverse context")
-        _check_levels(_levels(sf, p), want_fw, "forward flow, forward-only sequence context")
+        want_fw, want_rev = levels(ref, p), levels(ref, p, "reverse")
+        check_levels(levels(sr, p), want_fw, "forward flow, sequence + reverse context")
+        check_levels(levels(sr, p, "reverse"), want_rev, "reverse flow, sequence + reverse context")
+        check_levels(levels(sf, p), want_fw, "forward flow, forward-only sequence context")
         assert sr.status() == 0 and sf.status() == 0
         assert not np.array_equal(want_fw[p.sc_l], want_rev[p.sc_l])
         if n > 1:
@@ -151,7 +139,7 @@ def gray_ref(gpu):
         ref = gpu.Batch(p, n, reverse=True)
         _fill_pairs(gpu, ref, frames, w, h)
         ref.run()
-        out[n] = (p, frames, _levels(ref, p), _levels(ref, p, True))
+        out[n] = (p, frames, levels(ref, p), levels(ref, p, "reverse"))
         ref.close()
     return out
 
@@ -172,8 +160,8 @@ def test_sequence_pipelined_and_graph(gpu, gray_ref, how, arg, n):
         b.run()
         if how == "pipeline":
             b.run()  # two passes in flight before anything joins
-        _check_levels(_levels(b, p), want_fw, f"{how} {arg}, pass {rep}: forward")
-        _check_levels(_levels(b, p, True), want_rev, f"{how} {arg}, pass {rep}: reverse")
+        check_levels(levels(b, p), want_fw, f"{how} {arg}, pass {rep}: forward")
+        check_levels(levels(b, p, "reverse"), want_rev, f"{how} {arg}, pass {rep}: reverse")
         assert b.status() == 0
     b.close()
 
@@ -194,10 +182,10 @@ def test_sequence_warm_start(gpu, gray_ref):
         c.set_initflow(init[0].ptr)
         c.set_initflow_reverse(init[1].ptr)
         c.run()
-    want_fw = _levels(ref, p)
+    want_fw = levels(ref, p)
     assert not np.array_equal(want_fw[p.sc_l], cold_fw[p.sc_l])
-    _check_levels(_levels(b, p), want_fw, "warm start, forward")
-    _check_levels(_levels(b, p, True), _levels(ref, p, True), "warm start, reverse")
+    check_levels(levels(b, p), want_fw, "warm start, forward")
+    check_levels(levels(b, p, "reverse"), levels(ref, p, "reverse"), "warm start, reverse")
     ref.close()
     b.close()
 

@@ -13,25 +13,12 @@ import pytest
 
 import gen_synth
 from of_dis_amd import stabilize
-from of_dis_amd.params import oppoint, padded_size
 from of_dis_amd.stabilize import (BORDER_CONSTANT, BORDER_REPLICATE, camera_path_ref, gaussian_weights, smoothed_map,
                                   warp_frames_ref)
+from seq_products import INVALID, RANGE_REJECTS, SIZE_REJECTS, assert_same_bits, flag_contexts, run_context, smooth_clip
 
 pytestmark = pytest.mark.gpu
-INVALID = -1
 GM_AFFINE = 1
-
-
-def assert_bits_equal(got, want, what):
-    """arrays of one dtype compared as raw bit patterns"""
-    assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape, got.dtype, want.dtype)
-    bits = {1: np.uint8, 8: np.uint64}[got.dtype.itemsize]
-    g, w = np.ascontiguousarray(got).view(bits), np.ascontiguousarray(want).view(bits)
-    if not np.array_equal(g, w):
-        bad = np.argwhere(g != w)
-        i = tuple(bad[0])
-        raise AssertionError(f"{what}: {len(bad)} of {g.size} elements differ; first at {i}: {got[i]!r} ({g[i]:#x}) vs "
-                             f"{want[i]!r} ({w[i]:#x})")
 
 
 # ------------------------------------------------------------------ 1. ofdis_camera_path against the restatement
@@ -78,7 +65,7 @@ def test_camera_path_matches_the_definition(gpu, npairs, kind):
         for weights in _windows(radius):
             for zoom in (1.0, 1.25):
                 want = camera_path_ref(m, weights, zoom)
-                assert_bits_equal(gpu.camera_path(m, weights, zoom), want,
+                assert_same_bits(gpu.camera_path(m, weights, zoom), want,
                                   f"{npairs} pairs, {kind}, radius {radius}, zoom {zoom}, w_0 {weights[0]}")
                 assert np.isfinite(want).all()
     if npairs == 300:   # conditions on the input, on the restatement: full and truncated windows, breaks, corrections that matter
@@ -101,7 +88,7 @@ def test_camera_path_on_a_stream_into_a_device_buffer(gpu):
         want = camera_path_ref(m, weights, 1.25)
         weights[:] = math.nan
         gpu.check(gpu.lib().ofdis_sync(s.ptr))
-        assert_bits_equal(dw.get((8, 6), np.float64), want, "on a stream")
+        assert_same_bits(dw.get((8, 6), np.float64), want, "on a stream")
     finally:
         s.close()
 
@@ -136,12 +123,12 @@ def test_warp_frames_matches_the_definition(gpu, noc, w, h, border):
     frames, warps = _warp_case(w, h, noc)
     want = warp_frames_ref(frames, warps, border)
     got = gpu.warp_frames(frames, warps, border)
-    assert_bits_equal(got[0], want[0], f"noc {noc}, {w}x{h}, border {border}, out")
-    assert_bits_equal(got[1], want[1], f"noc {noc}, {w}x{h}, border {border}, inside")
+    assert_same_bits(got[0], want[0], f"noc {noc}, {w}x{h}, border {border}, out")
+    assert_same_bits(got[1], want[1], f"noc {noc}, {w}x{h}, border {border}, inside")
     # inside = NULL writes the same out
     only, none = gpu.warp_frames(frames, warps, border, inside=False)
     assert none is None
-    assert_bits_equal(only, want[0], "inside = NULL")
+    assert_same_bits(only, want[0], "inside = NULL")
     # the header's consequences, on the restatement the kernel was just compared with
     assert np.array_equal(want[0][0], frames[0]) and (want[1][0] == 1).all()
     assert not want[1][4:7].any()
@@ -173,41 +160,15 @@ def test_unaligned_outputs_take_byte_stores_with_the_same_bytes(gpu, noc, w, h):
         o, i = do.get((obytes + 2 * guard,), np.uint8), di.get((ibytes + 2 * guard,), np.uint8)
         for buf, n in ((o, obytes), (i, ibytes)):
             assert (buf[:off] == 0xAB).all() and (buf[off + n:] == 0xAB).all(), off
-        assert_bits_equal(o[off:off + obytes].reshape(frames.shape), want[0], f"out at offset {off}")
-        assert_bits_equal(i[off:off + ibytes].reshape(NFRAMES, h, w), want[1], f"inside at offset {off}")
+        assert_same_bits(o[off:off + obytes].reshape(frames.shape), want[0], f"out at offset {off}")
+        assert_same_bits(i[off:off + ibytes].reshape(NFRAMES, h, w), want[1], f"inside at offset {off}")
 
 
 # ------------------------------------------------------------------ 3. ofdis_batch_stabilize against its composition
-CLIP_STEP = 0.1  # of gen_synth's flow (up to 12 px) per step
-
-
-@functools.lru_cache(maxsize=None)
-def _clip(w, h, noc, nframes, seed=6200):
-    """nframes frames of one scene in UNEVEN motion: gen_synth's texture displaced by 0, 1, 3, 4, 6, 7, ... times CLIP_STEP of
-    its flow, so the pairs move by up to 1.2 and 2.4 px in turn and a smoothed path differs from the camera's"""
-    ks = np.cumsum([0] + [1 + (k % 2) for k in range(nframes - 1)])
-    frames = [gen_synth.make_pair(w, h, seed, noc)[0]]
-    frames += [gen_synth.make_pair(w, h, seed, noc, flow_scale=CLIP_STEP * k)[1] for k in ks[1:]]
-    return np.ascontiguousarray(np.stack(frames))
-
-
-def _sequence_context(gpu, clip, opp=2, contract=0, pipeline=1, reverse=True):
-    """a SEQUENCE (| REVERSE) context over the clip [n + 1][h][w] (+ [3]), built and run: (context, the clip's device array)"""
-    n, h, w = clip.shape[0] - 1, clip.shape[1], clip.shape[2]
-    noc = 1 if clip.ndim == 3 else 3
-    p = oppoint(opp, w, h, noc=noc, verbosity=0)
-    p.width, p.height = padded_size(w, h, p.sc_f)
-    d = gpu.Dev(clip)
-    old = gpu.set_tuning(contract=contract)
-    try:
-        b = gpu.Batch(p, n, sequence=True, reverse=reverse)
-        if pipeline > 1:
-            b.set_pipeline(pipeline)
-        b.build_pyramids_u8_seq(d.ptr, w, h)
-        b.run()
-    finally:
-        gpu.restore_tuning(old)
-    return b, d
+def _uneven_clip(w, h, noc, nframes):
+    """nframes (at most 6) frames of one scene in UNEVEN motion: gen_synth's texture displaced by 0, 1, 3, 4, 6, 7 times 0.1 of
+    its flow (up to 12 px), so the pairs move by up to 1.2 and 2.4 px in turn and a smoothed path differs from the camera's"""
+    return smooth_clip(w, h, noc, nframes, step=0.1, walk=(0, 1, 3, 4, 6, 7))
 
 
 # (noc, w, h, n pairs, first, count, pipeline, contract)
@@ -224,9 +185,9 @@ BATCH_CASES = [
 
 @pytest.mark.parametrize("noc,w,h,n,first,count,pipeline,contract", BATCH_CASES)
 def test_batch_stabilize_matches_the_three_calls(gpu, noc, w, h, n, first, count, pipeline, contract):
-    clip = _clip(w, h, noc, n + 1)
+    clip = _uneven_clip(w, h, noc, n + 1)
     weights, zoom = gaussian_weights(2, 1.0), 1.05
-    b, d = _sequence_context(gpu, clip, 2, contract, pipeline)
+    b, (d,) = run_context(gpu, clip, "seq_rev", 2, contract, pipeline)
     got, models = {}, {}
     try:
         bytes_before = b.device_bytes()
@@ -246,11 +207,11 @@ def test_batch_stabilize_matches_the_three_calls(gpu, noc, w, h, n, first, count
         border = BORDER_REPLICATE if fb else BORDER_CONSTANT
         warps = gpu.camera_path(models[fb], weights, zoom)
         out, inside = gpu.warp_frames(clip[first:first + count + 1], warps, border)
-        assert_bits_equal(got[fb][2], warps, f"fb_check {fb}, warps")
-        assert_bits_equal(got[fb][0], out, f"fb_check {fb}, out")
-        assert_bits_equal(got[fb][1], inside, f"fb_check {fb}, inside")
+        assert_same_bits(got[fb][2], warps, f"fb_check {fb}, warps")
+        assert_same_bits(got[fb][0], out, f"fb_check {fb}, out")
+        assert_same_bits(got[fb][1], inside, f"fb_check {fb}, inside")
         # ... and the composition is the definition's (conditions on the input: something was corrected, something uncovered)
-        assert_bits_equal(warps, camera_path_ref(models[fb], weights, zoom), f"fb_check {fb}, warps vs the definition")
+        assert_same_bits(warps, camera_path_ref(models[fb], weights, zoom), f"fb_check {fb}, warps vs the definition")
         assert np.abs(warps[1:-1, [0, 3]]).max() > 0.05 and not warps[0, [0, 2, 3, 4]].any()
         assert (out != clip[first:first + count + 1]).any()
 
@@ -258,22 +219,22 @@ def test_batch_stabilize_matches_the_three_calls(gpu, noc, w, h, n, first, count
 def test_batch_stabilize_into_device_buffers_on_a_stream(gpu):
     """out_ptr / inside pointer / warps_ptr / stream: the same bytes as the host-array form; inside = NULL and warps = NULL"""
     w, h, n = 256, 112, 3
-    clip = _clip(w, h, 1, n + 1)
+    clip = _uneven_clip(w, h, 1, n + 1)
     weights = gaussian_weights(1, 1.0)
-    b, d = _sequence_context(gpu, clip)
+    b, (d,) = run_context(gpu, clip)
     s = gpu.Stream()
     try:
         want = b.stabilize(d.ptr, w, h, weights, fb_check=True, inside=True)
         do, di, dw = gpu.Dev(nbytes=want[0].nbytes), gpu.Dev(nbytes=want[1].nbytes), gpu.Dev(nbytes=want[2].nbytes)
         assert b.stabilize(d.ptr, w, h, weights, fb_check=True, out_ptr=do.ptr, inside=di.ptr, warps_ptr=dw.ptr, stream=s.ptr) is None
         gpu.check(gpu.lib().ofdis_sync(s.ptr))
-        assert_bits_equal(do.get(want[0].shape, np.uint8), want[0], "device-buffer form, out")
-        assert_bits_equal(di.get(want[1].shape, np.uint8), want[1], "device-buffer form, inside")
-        assert_bits_equal(dw.get(want[2].shape, np.float64), want[2], "device-buffer form, warps")
+        assert_same_bits(do.get(want[0].shape, np.uint8), want[0], "device-buffer form, out")
+        assert_same_bits(di.get(want[1].shape, np.uint8), want[1], "device-buffer form, inside")
+        assert_same_bits(dw.get(want[2].shape, np.float64), want[2], "device-buffer form, warps")
         do2 = gpu.Dev(np.full(want[0].nbytes, 0xAB, np.uint8))
         assert b.stabilize(d.ptr, w, h, weights, fb_check=True, out_ptr=do2.ptr, stream=s.ptr) is None
         gpu.check(gpu.lib().ofdis_sync(s.ptr))
-        assert_bits_equal(do2.get(want[0].shape, np.uint8), want[0], "inside = NULL, warps = NULL")
+        assert_same_bits(do2.get(want[0].shape, np.uint8), want[0], "inside = NULL, warps = NULL")
     finally:
         b.close()
         s.close()
@@ -282,13 +243,7 @@ def test_batch_stabilize_into_device_buffers_on_a_stream(gpu):
 # ------------------------------------------------------------------ 4. checks that need a context
 @pytest.fixture(scope="module")
 def contexts(gpu):
-    p = oppoint(2, 256, 112)
-    made = dict(plain=gpu.Batch(p, 3), reverse=gpu.Batch(p, 3, reverse=True), seq=gpu.Batch(p, 3, sequence=True),
-                seq_rev=gpu.Batch(p, 3, sequence=True, reverse=True), stereo=gpu.Batch(p.copy(selectmode=2), 3),
-                stereo_lr=gpu.Batch(p.copy(selectmode=2), 3, stereo_lr=True))
-    yield made
-    for b in made.values():
-        b.close()
+    yield from flag_contexts(gpu, stereo=True)
 
 
 def _call(gpu, b, first=0, count=3, model=1, rounds=3, thresh=1.0, fb=0, alpha=0.01, beta=0.5, frames=True, out=True,
@@ -320,9 +275,8 @@ def test_fb_check_names_the_missing_flag(gpu, contexts):
 
 
 @pytest.mark.parametrize("kw", [
-    dict(frames=False), dict(out=False), dict(in_place=True), dict(weights=False),
-    dict(first=-1), dict(count=0), dict(count=-1), dict(first=1, count=3), dict(first=3, count=1), dict(count=4),
-    dict(wo=0), dict(ho=0), dict(wo=257), dict(ho=113), dict(wo=8193), dict(ho=8193),
+    dict(frames=False), dict(out=False), dict(in_place=True), dict(weights=False)] + RANGE_REJECTS + SIZE_REJECTS + [
+    dict(wo=8193), dict(ho=8193),
     dict(model=-1), dict(model=2), dict(rounds=0), dict(rounds=9), dict(thresh=0.0), dict(thresh=math.nan),
     dict(fb=2), dict(fb=-1), dict(alpha=-0.01), dict(beta=math.inf),
     dict(radius=-1), dict(radius=65), dict(w0=0.0), dict(w0=-1.0), dict(w0=math.nan), dict(w0=math.inf),
@@ -383,7 +337,7 @@ def test_end_to_end_a_jittered_pan_is_smoothed(gpu):
     rough_in = _roughness(pos)
     ideal = _roughness(pos + true_warps[:, [0, 3]]) / rough_in
     assert ideal < 0.1, ideal
-    b, d = _sequence_context(gpu, clip)
+    b, (d,) = run_context(gpu, clip)
     try:
         out, inside, warps = b.stabilize(d.ptr, w, h, weights, zoom=1.0, border=BORDER_CONSTANT, model=GM_AFFINE, rounds=3,
                                          thresh=1.0, fb_check=True, inside=True)
@@ -406,7 +360,7 @@ def test_stabilize_frames_tool(gpu, tmp_path):
     import sys
     from PIL import Image
     w, h, n = 250, 107, 4
-    clip = _clip(w, h, 1, n + 1)
+    clip = _uneven_clip(w, h, 1, n + 1)
     paths = []
     for k, f in enumerate(clip):
         paths.append(str(tmp_path / f"f{k}.png"))
@@ -416,16 +370,16 @@ def test_stabilize_frames_tool(gpu, tmp_path):
     res = subprocess.run([sys.executable, tool, "--radius", "2", "--sigma", "1.5", "--zoom", "1.1", "--border", "replicate"]
                          + paths + [stem], capture_output=True, text=True, timeout=300)
     assert res.returncode == 0, (res.stdout, res.stderr)
-    b, d = _sequence_context(gpu, clip)
+    b, (d,) = run_context(gpu, clip)
     try:
         want = b.stabilize(d.ptr, w, h, gaussian_weights(2, 1.5), zoom=1.1, border=BORDER_REPLICATE, fb_check=True)
     finally:
         b.close()
     got = np.stack([np.asarray(Image.open(f"{stem}_{k:03d}.png")) for k in range(n + 1)])
-    assert_bits_equal(got, want[0], "the tool's files")
+    assert_same_bits(got, want[0], "the tool's files")
     assert (got != clip).any()
     rows = [line.split(",") for line in open(stem + ".csv").read().splitlines()]
     assert len(rows) == n + 1 and all(len(r) == 6 for r in rows)
-    assert_bits_equal(np.array([[float(v) for v in r] for r in rows], np.float64), want[2], "the tool's warps")
+    assert_same_bits(np.array([[float(v) for v in r] for r in rows], np.float64), want[2], "the tool's warps")
     res = subprocess.run([sys.executable, tool, "--zoom", "0.5"] + paths + [stem], capture_output=True, text=True, timeout=300)
     assert res.returncode != 0 and "--zoom" in (res.stderr + res.stdout)

@@ -20,6 +20,7 @@ import natural
 import stereo_lr_ref as ref
 from common import assert_bits_equal
 from of_dis_amd.params import oppoint, padded_size
+from seq_products import check_levels, fill_u8, levels
 from test_stereo_lr_abi import assert_lr_inequalities
 
 pytestmark = pytest.mark.gpu
@@ -47,23 +48,6 @@ def _mir(frames):
     return np.ascontiguousarray(frames[:, :, ::-1])
 
 
-def _fill_u8(gpu, b, ia, ib, w, h):
-    da, db = gpu.Dev(ia), gpu.Dev(ib)
-    b.build_pyramids_u8(da.ptr, db.ptr, w, h)
-    gpu.check(gpu.lib().ofdis_sync(None))
-    da.free()
-    db.free()
-
-
-def _levels(b, p, mirror=False):
-    return {l: (b.level_flow_mirror(l) if mirror else b.level_flow(l)) for l in range(p.sc_l, p.sc_f + 1)}
-
-
-def _check_levels(got, want, what):
-    for l in want:
-        assert_bits_equal(got[l], want[l], f"{what}, level {l}")
-
-
 def _plane(gpu, b, level, kind):
     ptr = b.input_ptr(level, kind)
     assert ptr, (level, kind)
@@ -75,14 +59,14 @@ def _plane(gpu, b, level, kind):
 def _run_three(gpu, p, n, L, R, w, h, setup=None):
     """(LR context: forward levels, mirror levels), plain context on (L, R), plain context on (mir(R), mir(L))"""
     ctx = [gpu.Batch(p, n, stereo_lr=True), gpu.Batch(p, n), gpu.Batch(p, n)]
-    _fill_u8(gpu, ctx[0], L, R, w, h)
-    _fill_u8(gpu, ctx[1], L, R, w, h)
-    _fill_u8(gpu, ctx[2], _mir(R), _mir(L), w, h)
+    fill_u8(gpu, ctx[0], L, R, w, h)
+    fill_u8(gpu, ctx[1], L, R, w, h)
+    fill_u8(gpu, ctx[2], _mir(R), _mir(L), w, h)
     for b in ctx:
         if setup:
             setup(b)
         b.run()
-    out = (_levels(ctx[0], p), _levels(ctx[0], p, True), _levels(ctx[1], p), _levels(ctx[2], p))
+    out = (levels(ctx[0], p), levels(ctx[0], p, "mirror"), levels(ctx[1], p), levels(ctx[2], p))
     for b in ctx:
         assert b.status() == 0
         b.close()
@@ -95,9 +79,9 @@ def test_mirror_planes_equal_a_plain_context_on_mirrored_frames(gpu, noc, fb, w,
     p = _params(2, w, h, noc, fb=fb)
     L, R = _stereo_frames(w, h, noc, [5100, 5107])
     lr, plain, pm = gpu.Batch(p, 2, stereo_lr=True), gpu.Batch(p, 2), gpu.Batch(p, 2)
-    _fill_u8(gpu, lr, L, R, w, h)
-    _fill_u8(gpu, plain, L, R, w, h)
-    _fill_u8(gpu, pm, _mir(R), _mir(L), w, h)
+    fill_u8(gpu, lr, L, R, w, h)
+    fill_u8(gpu, plain, L, R, w, h)
+    fill_u8(gpu, pm, _mir(R), _mir(L), w, h)
     nin = 6 if fb else 4
     for l in range(p.sc_l, p.sc_f + 1):
         for k in range(nin):
@@ -143,8 +127,8 @@ def test_mirror_pass_equals_plain_context_on_mirrored_pair(gpu, monkeypatch, con
         fwd, mir, plain, plain_m = _run_three(gpu, p, n, L, R, w, h)
     finally:
         gpu.restore_tuning(old)
-    _check_levels(fwd, plain, "forward disparity of the LR context vs a plain context")
-    _check_levels(mir, plain_m, "mirror disparity vs a plain context on the mirrored, swapped pair")
+    check_levels(fwd, plain, "forward disparity of the LR context vs a plain context")
+    check_levels(mir, plain_m, "mirror disparity vs a plain context on the mirrored, swapped pair")
     assert (mir[p.sc_l] <= 0).all() and (fwd[p.sc_l] <= 0).all()
     assert not np.array_equal(mir[p.sc_l], fwd[p.sc_l])
 
@@ -157,7 +141,7 @@ def test_mirror_pass_pipelined_and_graph(gpu, how, arg):
     L, R = _stereo_frames(w, h, 1, [6200, 6207, 6214], n)
     _, _, plain, plain_m = _run_three(gpu, p, n, L, R, w, h)
     b = gpu.Batch(p, n, stereo_lr=True)
-    _fill_u8(gpu, b, L, R, w, h)
+    fill_u8(gpu, b, L, R, w, h)
     if how == "pipeline":
         b.set_pipeline(arg)
     else:
@@ -166,8 +150,8 @@ def test_mirror_pass_pipelined_and_graph(gpu, how, arg):
         b.run()
         if how == "pipeline":
             b.run()  # two passes in flight before anything joins
-        _check_levels(_levels(b, p), plain, f"{how} {arg}, pass {rep}: forward")
-        _check_levels(_levels(b, p, True), plain_m, f"{how} {arg}, pass {rep}: mirror")
+        check_levels(levels(b, p), plain, f"{how} {arg}, pass {rep}: forward")
+        check_levels(levels(b, p, "mirror"), plain_m, f"{how} {arg}, pass {rep}: mirror")
         assert b.status() == 0
     b.close()
 
@@ -181,15 +165,15 @@ def test_middlebury_pair_both_passes_and_warm_start(gpu):
     p = _params(2, w, h)
     L, R = natural.to_channels(a, 1)[None], natural.to_channels(b_, 1)[None]
     fwd, mir, plain, plain_m = _run_three(gpu, p, 1, L, R, w, h)
-    _check_levels(fwd, plain, "Middlebury: forward")
-    _check_levels(mir, plain_m, "Middlebury: mirror")
+    check_levels(fwd, plain, "Middlebury: forward")
+    check_levels(mir, plain_m, "Middlebury: mirror")
     # the warm start is forward-only: the mirror pass still starts from zero
     ctx = gpu.Batch(p, 1, stereo_lr=True)
-    _fill_u8(gpu, ctx, L, R, w, h)
+    fill_u8(gpu, ctx, L, R, w, h)
     n0 = gpu.lib().ofdis_batch_initflow_elems(ctx.h)
     ctx.upload_initflow(0, np.full(n0, -1.5, _f32))
     ctx.run()
-    _check_levels(_levels(ctx, p, True), plain_m, "mirror pass with a forward warm start")
+    check_levels(levels(ctx, p, "mirror"), plain_m, "mirror pass with a forward warm start")
     assert not np.array_equal(ctx.level_flow(p.sc_f), plain[p.sc_f])
     ctx.close()
 
@@ -286,9 +270,9 @@ def _lr_context(gpu, p, L, R, w, h):
     context on the mirrored, swapped frames (the same bits as the LR context's mirror levels: test 4)."""
     n = L.shape[0]
     b, pf, pm = gpu.Batch(p, n, stereo_lr=True), gpu.Batch(p, n), gpu.Batch(p, n)
-    _fill_u8(gpu, b, L, R, w, h)
-    _fill_u8(gpu, pf, L, R, w, h)
-    _fill_u8(gpu, pm, _mir(R), _mir(L), w, h)
+    fill_u8(gpu, b, L, R, w, h)
+    fill_u8(gpu, pf, L, R, w, h)
+    fill_u8(gpu, pm, _mir(R), _mir(L), w, h)
     for c in (b, pf, pm):
         c.run()
     assert_bits_equal(b.level_flow_mirror(p.sc_l), pm.level_flow(p.sc_l), "mirror disparity")
@@ -386,7 +370,7 @@ def test_shifted_plane_scene(gpu):
     band = (slice(y0 + 8, y1 - 8), slice(x0 - 8, x0 - 1))
     p = _params(3, w, h)
     b = gpu.Batch(p, 1, stereo_lr=True)
-    _fill_u8(gpu, b, L[None], R[None], w, h)
+    fill_u8(gpu, b, L[None], R[None], w, h)
     b.run()
     raw, _, ml, _ = b.upsample_lr(w, h, ref.FILL_NONE)
     filled = b.upsample_lr(w, h, ref.FILL_BACKGROUND, outputs=(True, False, False, False))[0]
@@ -415,7 +399,7 @@ def test_middlebury_inequalities_on_the_library(gpu, contract, opp):
     old = gpu.set_tuning(contract=contract)
     try:
         b = gpu.Batch(p, 1, stereo_lr=True)
-        _fill_u8(gpu, b, natural.to_channels(a, 1)[None], natural.to_channels(b_, 1)[None], w, h)
+        fill_u8(gpu, b, natural.to_channels(a, 1)[None], natural.to_channels(b_, 1)[None], w, h)
         b.run()
         dl, dr, ml, mr = b.upsample_lr(w, h, ref.FILL_NONE)
         filled = b.upsample_lr(w, h, ref.FILL_BACKGROUND, outputs=(True, False, False, False))[0]
@@ -505,7 +489,7 @@ def test_flow_images_lr_writes_what_the_binding_returns(gpu, tmp_path):
     assert r.returncode == 0, r.stdout + r.stderr
     p = _params(2, w, h)
     b = gpu.Batch(p, 1, stereo_lr=True)
-    _fill_u8(gpu, b, L, R, w, h)
+    fill_u8(gpu, b, L, R, w, h)
     b.run()
     want = b.upsample_lr(w, h, ref.FILL_BACKGROUND)
     b.close()

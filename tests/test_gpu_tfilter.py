@@ -12,26 +12,18 @@ import numpy as np
 import pytest
 
 import gen_synth
-from of_dis_amd.params import oppoint, padded_size
+from of_dis_amd.params import oppoint
 from of_dis_amd.temporal import SUPPORT_NEXT, SUPPORT_PREV, temporal_filter_ref
+from seq_products import (FB_REJECTS, FLT_MIN, INVALID, RANGE_REJECTS, SIZE_REJECTS, assert_same_bits, flag_contexts,
+                          run_context, smooth_clip)
 
 pytestmark = pytest.mark.gpu
 _f32 = np.float32
-INVALID = -1
-FLT_MIN = float(np.finfo(_f32).tiny)
-
-
-def assert_u8_equal(got, want, what):
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    if not np.array_equal(got, want):
-        bad = np.argwhere(got != want)
-        i = tuple(bad[0])
-        raise AssertionError(f"{what}: {len(bad)} of {got.size} bytes differ; first at {i}: {got[i]} vs {want[i]}")
 
 
 def assert_filtered_equal(got, want, what):
-    assert_u8_equal(got[0], want[0], what + ", out")
-    assert_u8_equal(got[1], want[1], what + ", support")
+    assert_same_bits(got[0], want[0], what + ", out")
+    assert_same_bits(got[1], want[1], what + ", support")
 
 
 # ------------------------------------------------------------------ 1. standalone kernel against the restatement
@@ -89,7 +81,7 @@ def test_standalone_matches_the_definition(gpu, noc, w, h, kind):
         # support = NULL writes the same out
         got, none = gpu.temporal_filter(frames, fw, rev, mfw, mrev, wn=0.5, tau=12.0, support=False)
         assert none is None
-        assert_u8_equal(got, temporal_filter_ref(frames, fw, rev, mfw, mrev, wn=0.5, tau=12.0)[0], "support = NULL")
+        assert_same_bits(got, temporal_filter_ref(frames, fw, rev, mfw, mrev, wn=0.5, tau=12.0)[0], "support = NULL")
     if kind == "smooth" and w * h >= 200:   # the finite gate is exercised with weights > 0 (condition on the restatement)
         assert partial > 0
 
@@ -102,7 +94,7 @@ def test_identical_frames_with_zero_flows_return_the_clip(gpu, noc):
     z = np.zeros((n, h, w, 2), _f32)
     for tau in (math.inf, 8.0):
         out, support = gpu.temporal_filter(frames, z, z, wn=1.0, tau=tau)
-        assert_u8_equal(out, frames, f"tau {tau}")
+        assert_same_bits(out, frames, f"tau {tau}")
         assert (support[0] == SUPPORT_NEXT).all() and (support[n] == SUPPORT_PREV).all() and (support[1:n] == 3).all()
 
 
@@ -123,8 +115,8 @@ def test_unaligned_arrays_take_byte_stores_with_the_same_bytes(gpu, noc, w, h):
     o, s = do.get((obytes + 2 * guard,), np.uint8), ds.get((sbytes + 2 * guard,), np.uint8)
     for buf, n in ((o, obytes), (s, sbytes)):
         assert (buf[:guard] == 0xAB).all() and (buf[guard + n:] == 0xAB).all()
-    assert_u8_equal(o[guard:guard + obytes].reshape(frames.shape), want[0], "out, one byte off")
-    assert_u8_equal(s[guard:guard + sbytes].reshape(npairs + 1, h, w), want[1], "support, one byte off")
+    assert_same_bits(o[guard:guard + obytes].reshape(frames.shape), want[0], "out, one byte off")
+    assert_same_bits(s[guard:guard + sbytes].reshape(npairs + 1, h, w), want[1], "support, one byte off")
 
 
 def test_many_frames_map_onto_their_own_neighbours(gpu):
@@ -135,37 +127,6 @@ def test_many_frames_map_onto_their_own_neighbours(gpu):
 
 
 # ------------------------------------------------------------------ 2. fused kernel against the standalone one
-CLIP_STEP = 0.15  # of gen_synth's flow (up to 12 px) per frame: at most 1.8 px per pair
-
-
-@functools.lru_cache(maxsize=None)
-def _clip(w, h, noc, nframes, seed=6200):
-    """nframes frames of one scene in smooth motion, as _clip of tests/test_gpu_track.py makes them: gen_synth's texture
-    displaced by 0, 1, 2, ... times CLIP_STEP of its flow"""
-    frames = [gen_synth.make_pair(w, h, seed, noc)[0]]
-    frames += [gen_synth.make_pair(w, h, seed, noc, flow_scale=CLIP_STEP * k)[1] for k in range(1, nframes)]
-    return np.ascontiguousarray(np.stack(frames))
-
-
-def _sequence_context(gpu, clip, opp=2, contract=0, pipeline=1):
-    """a SEQUENCE | REVERSE context over the clip [n + 1][h][w] (+ [3]), built and run: (context, the clip's device array)"""
-    n, h, w = clip.shape[0] - 1, clip.shape[1], clip.shape[2]
-    noc = 1 if clip.ndim == 3 else 3
-    p = oppoint(opp, w, h, noc=noc, verbosity=0)
-    p.width, p.height = padded_size(w, h, p.sc_f)
-    d = gpu.Dev(clip)
-    old = gpu.set_tuning(contract=contract)
-    try:
-        b = gpu.Batch(p, n, sequence=True, reverse=True)
-        if pipeline > 1:
-            b.set_pipeline(pipeline)
-        b.build_pyramids_u8_seq(d.ptr, w, h)
-        b.run()
-    finally:
-        gpu.restore_tuning(old)
-    return b, d
-
-
 FUSED_WN_TAU = [(1.0, math.inf), (0.75, 24.0)]
 
 # (noc, op, w, h, n pairs, first, count, pipeline, contract, alpha, beta)
@@ -188,8 +149,8 @@ FUSED_CASES = [
 
 @pytest.mark.parametrize("noc,opp,w,h,n,first,count,pipeline,contract,alpha,beta", FUSED_CASES)
 def test_fused_matches_standalone_on_upsample_bidir(gpu, noc, opp, w, h, n, first, count, pipeline, contract, alpha, beta):
-    clip = _clip(w, h, noc, n + 1)
-    b, d = _sequence_context(gpu, clip, opp, contract, pipeline)
+    clip = smooth_clip(w, h, noc, n + 1)
+    b, (d,) = run_context(gpu, clip, "seq_rev", opp, contract, pipeline)
     try:
         fused = [b.temporal_filter(d.ptr, w, h, wn=wn, tau=tau, first=first, count=count, alpha=alpha, beta=beta, support=True)
                  for wn, tau in FUSED_WN_TAU]
@@ -216,8 +177,8 @@ def test_fused_matches_standalone_on_upsample_bidir(gpu, noc, opp, w, h, n, firs
 def test_fused_into_device_buffers_on_a_stream(gpu):
     """out_ptr / support pointer / stream: the same bytes as the host-array form"""
     w, h, n = 256, 112, 2
-    clip = _clip(w, h, 1, n + 1)
-    b, d = _sequence_context(gpu, clip)
+    clip = smooth_clip(w, h, 1, n + 1)
+    b, (d,) = run_context(gpu, clip)
     s = gpu.Stream()
     try:
         want = b.temporal_filter(d.ptr, w, h, wn=0.75, tau=24.0, support=True)
@@ -225,9 +186,9 @@ def test_fused_into_device_buffers_on_a_stream(gpu):
         out, sup = gpu.Dev(nbytes=want[0].nbytes), gpu.Dev(nbytes=want[1].nbytes)
         assert b.temporal_filter(d.ptr, w, h, wn=0.75, tau=24.0, out_ptr=out.ptr, support=sup.ptr, stream=s.ptr) is None
         gpu.check(gpu.lib().ofdis_sync(s.ptr))
-        assert_u8_equal(out.get(want[0].shape, np.uint8), want[0], "device-buffer form, out")
-        assert_u8_equal(sup.get(want[1].shape, np.uint8), want[1], "device-buffer form, support")
-        assert_u8_equal(only_out, want[0], "support = NULL")
+        assert_same_bits(out.get(want[0].shape, np.uint8), want[0], "device-buffer form, out")
+        assert_same_bits(sup.get(want[1].shape, np.uint8), want[1], "device-buffer form, support")
+        assert_same_bits(only_out, want[0], "support = NULL")
     finally:
         b.close()
         s.close()
@@ -240,7 +201,7 @@ def test_occlusion_masks_change_the_output(gpu, noc):
     w, h = 256, 112
     a, b_ = gen_synth.make_pair_blocks(w, h, 42, noc)
     clip = np.ascontiguousarray(np.stack([a, b_, a, b_]))
-    b, d = _sequence_context(gpu, clip)
+    b, (d,) = run_context(gpu, clip)
     try:
         fused = b.temporal_filter(d.ptr, w, h, support=True)
         fw, rev, mf, mr = b.upsample_bidir(w, h)
@@ -248,8 +209,8 @@ def test_occlusion_masks_change_the_output(gpu, noc):
         b.close()
     assert (mf != 0).any() and (mr != 0).any()
     want = temporal_filter_ref(clip[:3], fw[:2], rev[:2], mf[:2], mr[:2])   # frames 0 and 1 do not depend on pair 2
-    assert_u8_equal(fused[0][:2], want[0][:2], "fused vs the definition, out")
-    assert_u8_equal(fused[1][:2], want[1][:2], "fused vs the definition, support")
+    assert_same_bits(fused[0][:2], want[0][:2], "fused vs the definition, out")
+    assert_same_bits(fused[1][:2], want[1][:2], "fused vs the definition, support")
     assert_filtered_equal(fused, gpu.temporal_filter(clip, fw, rev, mf, mr), "fused vs standalone")
     assert (fused[1][1:3] != 3).any()
     unmasked = gpu.temporal_filter(clip, fw, rev)
@@ -259,12 +220,7 @@ def test_occlusion_masks_change_the_output(gpu, noc):
 # ------------------------------------------------------------------ 3. checks that need a context
 @pytest.fixture(scope="module")
 def contexts(gpu):
-    p = oppoint(2, 256, 112)
-    made = dict(plain=gpu.Batch(p, 3), reverse=gpu.Batch(p, 3, reverse=True), seq=gpu.Batch(p, 3, sequence=True),
-                seq_rev=gpu.Batch(p, 3, sequence=True, reverse=True))
-    yield made
-    for b in made.values():
-        b.close()
+    yield from flag_contexts(gpu)
 
 
 def _batch_call(gpu, b, first=0, count=3, frames=True, out=True, in_place=False, wo=256, ho=112, wn=1.0, tau=math.inf,
@@ -282,14 +238,12 @@ def test_batch_temporal_filter_names_the_missing_flag(gpu, contexts, which, flag
     assert "OFDIS_BATCH_" + flag in gpu.lib().ofdis_last_error().decode()
 
 
-@pytest.mark.parametrize("kw", [
-    dict(frames=False), dict(out=False), dict(in_place=True),
-    dict(first=-1), dict(count=0), dict(count=-1), dict(first=1, count=3), dict(first=3, count=1), dict(count=4),
-    dict(wo=0), dict(ho=0), dict(wo=257), dict(ho=113),
+REJECTS = [dict(frames=False), dict(out=False), dict(in_place=True)] + RANGE_REJECTS + SIZE_REJECTS + [
     dict(wn=-0.01), dict(wn=1.01), dict(wn=math.nan), dict(wn=math.inf),
-    dict(tau=0.0), dict(tau=-1.0), dict(tau=math.nan), dict(tau=-math.inf), dict(tau=FLT_MIN / 2),
-    dict(alpha=-0.01), dict(beta=-0.5), dict(alpha=math.nan), dict(beta=math.inf),
-], ids=lambda kw: ",".join(f"{k}={v}" for k, v in kw.items()))
+    dict(tau=0.0), dict(tau=-1.0), dict(tau=math.nan), dict(tau=-math.inf), dict(tau=FLT_MIN / 2)] + FB_REJECTS
+
+
+@pytest.mark.parametrize("kw", REJECTS, ids=lambda kw: ",".join(f"{k}={v}" for k, v in kw.items()))
 def test_batch_temporal_filter_rejects(gpu, contexts, kw):
     assert _batch_call(gpu, contexts["seq_rev"], **kw) == INVALID
     assert gpu.lib().ofdis_last_error()
@@ -313,10 +267,10 @@ def test_quality_denoising_a_noisy_clip(gpu):
     for the flow's own error on noisy frames.  Measured on an MI355X: 2.921 against 6.376, ratio 0.458, both neighbours at every
     pixel of the crop (below 1 / sqrt(3): a neighbour's bilinear sample averages its noise over up to four pixels as well)."""
     w, h, n = 256, 128, 4
-    clean = _clip(w, h, 1, n + 1)
+    clean = smooth_clip(w, h, 1, n + 1)
     rng = np.random.default_rng(99)
     noisy = np.clip(np.rint(clean + rng.normal(0.0, 8.0, clean.shape)), 0, 255).astype(np.uint8)
-    b, d = _sequence_context(gpu, noisy)
+    b, (d,) = run_context(gpu, noisy)
     try:
         out, support = b.temporal_filter(d.ptr, w, h, wn=1.0, tau=math.inf, support=True)
     finally:
@@ -337,7 +291,7 @@ def test_temporal_filter_frames_tool(gpu, tmp_path):
     import sys
     from PIL import Image
     w, h, n = 250, 107, 2
-    clip = _clip(w, h, 1, n + 1)
+    clip = smooth_clip(w, h, 1, n + 1)
     paths = []
     for k, f in enumerate(clip):
         paths.append(str(tmp_path / f"f{k}.png"))
@@ -347,13 +301,13 @@ def test_temporal_filter_frames_tool(gpu, tmp_path):
     res = subprocess.run([sys.executable, tool, "--wn", "0.75", "--tau", "24"] + paths + [stem], capture_output=True, text=True,
                          timeout=300)
     assert res.returncode == 0, (res.stdout, res.stderr)
-    b, d = _sequence_context(gpu, clip)
+    b, (d,) = run_context(gpu, clip)
     try:
         want = b.temporal_filter(d.ptr, w, h, wn=0.75, tau=24.0)
     finally:
         b.close()
     got = np.stack([np.asarray(Image.open(f"{stem}_{k:03d}.png")) for k in range(n + 1)])
-    assert_u8_equal(got, want, "the tool's files")
+    assert_same_bits(got, want, "the tool's files")
     assert (got != clip).any()
     res = subprocess.run([sys.executable, tool, "--wn", "1.5"] + paths + [stem], capture_output=True, text=True, timeout=300)
     assert res.returncode != 0 and "--wn" in (res.stderr + res.stdout)

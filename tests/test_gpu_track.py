@@ -14,18 +14,12 @@ import sys
 import numpy as np
 import pytest
 
-import gen_synth
 from of_dis_amd import tracking
-from of_dis_amd.params import oppoint, padded_size
+from seq_products import INVALID, SIZE_REJECTS, assert_same_bits, flag_contexts, run_context, smooth_clip
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _f32 = np.float32
-INVALID = -1
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, _f32).view(np.uint32)
 
 
 def assert_tracks_equal(got, want, what):
@@ -34,11 +28,7 @@ def assert_tracks_equal(got, want, what):
     if not np.array_equal(gc, wc):
         i = int(np.flatnonzero(gc != wc)[0])
         raise AssertionError(f"{what}: {(gc != wc).sum()} of {gc.size} counts differ; first at point {i}: {gc[i]} vs {wc[i]}")
-    if not np.array_equal(_bits(gt), _bits(wt)):
-        bad = np.argwhere(_bits(gt) != _bits(wt))
-        f, i, c = bad[0]
-        raise AssertionError(f"{what}: {len(bad)} of {gt.size} values differ; first at frame {f}, point {i}, component {c}: "
-                             f"{gt[f, i, c]!r} vs {wt[f, i, c]!r}")
+    assert_same_bits(gt, wt, what + ", tracks [frame][point][component]")
 
 
 # ------------------------------------------------------------------ 1. standalone kernel against the restatement
@@ -184,33 +174,6 @@ def test_one_step_agrees_with_fb_check(gpu, w, h):
 
 
 # ------------------------------------------------------------------ 4. fused kernel against the standalone one
-CLIP_STEP = 0.15  # of gen_synth's flow (up to 12 px) per frame: at most 1.8 px per pair, 9 px over five pairs
-
-
-@functools.lru_cache(maxsize=None)
-def _clip(w, h, noc, nframes, seed=6200):
-    """nframes frames of one scene in smooth motion: gen_synth's texture displaced by 0, 1, 2, ... times CLIP_STEP of its flow"""
-    frames = [gen_synth.make_pair(w, h, seed, noc)[0]]
-    frames += [gen_synth.make_pair(w, h, seed, noc, flow_scale=CLIP_STEP * k)[1] for k in range(1, nframes)]
-    return np.ascontiguousarray(np.stack(frames))
-
-
-def _sequence_context(gpu, w, h, noc, n, contract, reverse=True, pipeline=1):
-    p = oppoint(2, w, h, noc=noc, verbosity=0)
-    p.width, p.height = padded_size(w, h, p.sc_f)
-    d = gpu.Dev(_clip(w, h, noc, n + 1))
-    old = gpu.set_tuning(contract=contract)
-    try:
-        b = gpu.Batch(p, n, sequence=True, reverse=reverse)
-        if pipeline > 1:
-            b.set_pipeline(pipeline)
-        b.build_pyramids_u8_seq(d.ptr, w, h)
-        b.run()
-    finally:
-        gpu.restore_tuning(old)
-    return b, d
-
-
 def _clip_seeds(w, h, n):
     """(seeds, seed frames, number of leading grid seeds): a stride-5 grid at frame 0, random fractional points and border points
     with seed frames from [-1, n + 1]"""
@@ -240,7 +203,7 @@ def test_fused_matches_standalone_on_the_materialised_flows(gpu, noc, w, h, n, c
     """the full range and the sub-range (1, n - 1), with the consistency test (against upsample_bidir's two flows) and
     without it"""
     seeds, sf, ngrid = _clip_seeds(w, h, n)
-    b, d = _sequence_context(gpu, w, h, noc, n, contract, pipeline=pipeline)
+    b, _ = run_context(gpu, smooth_clip(w, h, noc, n + 1), "seq_rev", contract=contract, pipeline=pipeline)
     try:
         fused = {(first, count, fb): b.track_points(seeds, w, h, sf, fb_check=fb, first=first, count=count)
                  for first, count in ((0, n), (1, n - 1)) for fb in (True, False)}
@@ -262,7 +225,7 @@ def test_fused_matches_standalone_on_the_materialised_flows(gpu, noc, w, h, n, c
 def test_fused_without_the_test_on_a_forward_only_sequence(gpu, contract):
     w, h, n = 250, 107, 3
     seeds, sf, _ = _clip_seeds(w, h, n)
-    b, d = _sequence_context(gpu, w, h, 1, n, contract, reverse=False)
+    b, _ = run_context(gpu, smooth_clip(w, h, 1, n + 1), "seq", contract=contract)
     try:
         got = b.track_points(seeds, w, h, sf, fb_check=False)
         fw = b.upsample_frames(0, n, w, h)
@@ -274,12 +237,7 @@ def test_fused_without_the_test_on_a_forward_only_sequence(gpu, contract):
 # ------------------------------------------------------------------ 5. checks that need a context
 @pytest.fixture(scope="module")
 def contexts(gpu):
-    p = oppoint(2, 256, 112)
-    made = dict(plain=gpu.Batch(p, 3), reverse=gpu.Batch(p, 3, reverse=True), seq=gpu.Batch(p, 3, sequence=True),
-                seq_rev=gpu.Batch(p, 3, sequence=True, reverse=True))
-    yield made
-    for b in made.values():
-        b.close()
+    yield from flag_contexts(gpu)
 
 
 def _batch_call(gpu, b, first=0, count=3, seeds=True, tracks=True, npoints=4, max_steps=0, fb_check=1, alpha=0.01, beta=0.5,
@@ -302,8 +260,7 @@ def test_batch_track_points_with_the_test_needs_a_reverse_context(gpu, contexts)
 
 
 @pytest.mark.parametrize("kw", [
-    dict(first=-1), dict(count=0), dict(first=1, count=3), dict(first=3, count=1), dict(count=4),
-    dict(wo=0), dict(ho=0), dict(wo=257), dict(ho=113),
+    dict(first=-1), dict(count=0), dict(first=1, count=3), dict(first=3, count=1), dict(count=4)] + SIZE_REJECTS + [
     dict(fb_check=2), dict(fb_check=-1), dict(seeds=False), dict(tracks=False), dict(npoints=0), dict(npoints=(1 << 24) + 1),
     dict(max_steps=-1), dict(alpha=-0.01), dict(beta=float("nan")),
 ], ids=lambda kw: ",".join(f"{k}={v}" for k, v in kw.items()))
@@ -319,7 +276,7 @@ def test_flow_images_tracks(gpu, tmp_path):
     from PIL import Image
     w, h, n = 250, 107, 3
     paths = []
-    for k, f in enumerate(_clip(w, h, 1, n + 1)):
+    for k, f in enumerate(smooth_clip(w, h, 1, n + 1)):
         paths.append(str(tmp_path / f"f{k}.png"))
         Image.fromarray(f).save(paths[-1])
     tool, stem = os.path.join(ROOT, "tools", "flow_images.py"), str(tmp_path / "clip")

@@ -303,9 +303,10 @@ def test_flow_images_track_select(gpu, tmp_path):
     import subprocess
     import sys
     from PIL import Image
-    from test_gpu_dense_tracks import STRIDE, WINDOW, _clip, _clip_threshold
+    from seq_products import smooth_clip
+    from test_gpu_dense_tracks import STRIDE, WINDOW, _clip_threshold
     w, h, n = 250, 107, 3
-    frames = _clip(w, h, 1, n + 1)
+    frames = smooth_clip(w, h, 1, n + 1)
     T = _clip_threshold(frames, STRIDE, WINDOW)
     paths = []
     for k, f in enumerate(frames):

@@ -6,33 +6,23 @@ header's definition in numpy float32, and at radius 1 with the existing ofdis_te
 the standalone one applied to out_fw and out_rev of ofdis_batch_upsample_bidir and, for ranges of at most five frames, with the
 definition as well.  Conditions on the generated inputs are checked on the restatement or the standalone result, never on the
 kernel under test."""
-import functools
 import math
 
 import numpy as np
 import pytest
 
-import gen_synth
-from of_dis_amd.params import oppoint, padded_size
 from of_dis_amd.temporal import reach, trajectory_filter_ref, trajectory_weights
-from trajfilter_cases import FLT_MIN, SIZES, coherent_case, old_support, random_case
+from seq_products import (FB_REJECTS, FLT_MIN, INVALID, RANGE_REJECTS, SIZE_REJECTS, assert_same_bits, flag_contexts,
+                          run_context, smooth_clip)
+from trajfilter_cases import SIZES, coherent_case, old_support, random_case
 
 pytestmark = pytest.mark.gpu
 _f32 = np.float32
-INVALID = -1
-
-
-def assert_u8_equal(got, want, what):
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    if not np.array_equal(got, want):
-        bad = np.argwhere(got != want)
-        i = tuple(bad[0])
-        raise AssertionError(f"{what}: {len(bad)} of {got.size} bytes differ; first at {i}: {got[i]} vs {want[i]}")
 
 
 def assert_filtered_equal(got, want, what):
-    assert_u8_equal(got[0], want[0], what + ", out")
-    assert_u8_equal(got[1], want[1], what + ", support")
+    assert_same_bits(got[0], want[0], what + ", out")
+    assert_same_bits(got[1], want[1], what + ", support")
 
 
 def _case(kind, n, w, h, noc):
@@ -73,7 +63,7 @@ def test_standalone_matches_the_definition(gpu, noc, w, h, kind):
         weights = trajectory_weights(2, 0.5)
         got, none = gpu.trajectory_filter(frames, fw, rev, weights, tau=12.0, support=False)
         assert none is None
-        assert_u8_equal(got, trajectory_filter_ref(frames, fw, rev, weights, tau=12.0)[0], "support = NULL")
+        assert_same_bits(got, trajectory_filter_ref(frames, fw, rev, weights, tau=12.0)[0], "support = NULL")
 
 
 @pytest.mark.parametrize("noc", [1, 3])
@@ -102,7 +92,7 @@ def test_identical_frames_with_zero_flows_return_the_clip(gpu, noc):
     z = np.zeros((n, h, w, 2), _f32)
     for R, tau in ((2, math.inf), (8, 8.0)):
         out, support = gpu.trajectory_filter(frames, z, z, trajectory_weights(R), tau=tau)
-        assert_u8_equal(out, frames, f"radius {R}, tau {tau}")
+        assert_same_bits(out, frames, f"radius {R}, tau {tau}")
         nb, nf = reach(support)
         for f in range(n + 1):
             assert (nb[f] == min(R, f)).all() and (nf[f] == min(R, n - f)).all()
@@ -126,8 +116,8 @@ def test_unaligned_arrays_take_byte_stores_with_the_same_bytes(gpu, noc, w, h):
     o, s = do.get((obytes + 2 * guard,), np.uint8), ds.get((sbytes + 2 * guard,), np.uint8)
     for buf, n in ((o, obytes), (s, sbytes)):
         assert (buf[:guard] == 0xAB).all() and (buf[guard + n:] == 0xAB).all()
-    assert_u8_equal(o[guard:guard + obytes].reshape(frames.shape), want[0], "out, one byte off")
-    assert_u8_equal(s[guard:guard + sbytes].reshape(npairs + 1, h, w), want[1], "support, one byte off")
+    assert_same_bits(o[guard:guard + obytes].reshape(frames.shape), want[0], "out, one byte off")
+    assert_same_bits(s[guard:guard + sbytes].reshape(npairs + 1, h, w), want[1], "support, one byte off")
     assert (want[1] != 0).any()
 
 
@@ -141,37 +131,6 @@ def test_many_frames_map_onto_their_own_neighbours(gpu):
 
 
 # ------------------------------------------------------------------ 2. fused kernel against the standalone one
-CLIP_STEP = 0.15  # of gen_synth's flow (up to 12 px) per frame: at most 1.8 px per pair
-
-
-@functools.lru_cache(maxsize=None)
-def _clip(w, h, noc, nframes, seed=6200):
-    """nframes frames of one scene in smooth motion, as _clip of tests/test_gpu_tfilter.py makes them: gen_synth's texture
-    displaced by 0, 1, 2, ... times CLIP_STEP of its flow"""
-    frames = [gen_synth.make_pair(w, h, seed, noc)[0]]
-    frames += [gen_synth.make_pair(w, h, seed, noc, flow_scale=CLIP_STEP * k)[1] for k in range(1, nframes)]
-    return np.ascontiguousarray(np.stack(frames))
-
-
-def _sequence_context(gpu, clip, opp=2, contract=0, pipeline=1):
-    """a SEQUENCE | REVERSE context over the clip [n + 1][h][w] (+ [3]), built and run: (context, the clip's device array)"""
-    n, h, w = clip.shape[0] - 1, clip.shape[1], clip.shape[2]
-    noc = 1 if clip.ndim == 3 else 3
-    p = oppoint(opp, w, h, noc=noc, verbosity=0)
-    p.width, p.height = padded_size(w, h, p.sc_f)
-    d = gpu.Dev(clip)
-    old = gpu.set_tuning(contract=contract)
-    try:
-        b = gpu.Batch(p, n, sequence=True, reverse=True)
-        if pipeline > 1:
-            b.set_pipeline(pipeline)
-        b.build_pyramids_u8_seq(d.ptr, w, h)
-        b.run()
-    finally:
-        gpu.restore_tuning(old)
-    return b, d
-
-
 # (weights, tau, fb_check)
 FUSED_SETTINGS = [(trajectory_weights(2), math.inf, 1), (trajectory_weights(4, 0.75, sigma=2.0), 24.0, 1),
                   (trajectory_weights(2), 24.0, 0)]
@@ -197,8 +156,8 @@ FUSED_CASES = [
 
 @pytest.mark.parametrize("noc,opp,w,h,n,first,count,pipeline,contract,alpha,beta", FUSED_CASES)
 def test_fused_matches_standalone_on_upsample_bidir(gpu, noc, opp, w, h, n, first, count, pipeline, contract, alpha, beta):
-    clip = _clip(w, h, noc, n + 1)
-    b, d = _sequence_context(gpu, clip, opp, contract, pipeline)
+    clip = smooth_clip(w, h, noc, n + 1)
+    b, (d,) = run_context(gpu, clip, "seq_rev", opp, contract, pipeline)
     try:
         fused = [b.trajectory_filter(d.ptr, w, h, wts, tau=tau, fb_check=fb, first=first, count=count, alpha=alpha, beta=beta,
                                      support=True) for wts, tau, fb in FUSED_SETTINGS]
@@ -226,8 +185,8 @@ def test_fused_matches_standalone_on_upsample_bidir(gpu, noc, opp, w, h, n, firs
 def test_fused_into_device_buffers_on_a_stream(gpu):
     """out_ptr / support pointer / stream: the same bytes as the host-array form"""
     w, h, n = 256, 112, 3
-    clip = _clip(w, h, 1, n + 1)
-    b, d = _sequence_context(gpu, clip)
+    clip = smooth_clip(w, h, 1, n + 1)
+    b, (d,) = run_context(gpu, clip)
     s = gpu.Stream()
     wts = trajectory_weights(2, 0.75)
     try:
@@ -236,9 +195,9 @@ def test_fused_into_device_buffers_on_a_stream(gpu):
         out, sup = gpu.Dev(nbytes=want[0].nbytes), gpu.Dev(nbytes=want[1].nbytes)
         assert b.trajectory_filter(d.ptr, w, h, wts, tau=24.0, out_ptr=out.ptr, support=sup.ptr, stream=s.ptr) is None
         gpu.check(gpu.lib().ofdis_sync(s.ptr))
-        assert_u8_equal(out.get(want[0].shape, np.uint8), want[0], "device-buffer form, out")
-        assert_u8_equal(sup.get(want[1].shape, np.uint8), want[1], "device-buffer form, support")
-        assert_u8_equal(only_out, want[0], "support = NULL")
+        assert_same_bits(out.get(want[0].shape, np.uint8), want[0], "device-buffer form, out")
+        assert_same_bits(sup.get(want[1].shape, np.uint8), want[1], "device-buffer form, support")
+        assert_same_bits(only_out, want[0], "support = NULL")
         # radius 1 on the context is the existing fused filter
         old = b.temporal_filter(d.ptr, w, h, wn=0.75, tau=24.0, support=True)
         new = b.trajectory_filter(d.ptr, w, h, [0.75], tau=24.0, support=True)
@@ -251,12 +210,7 @@ def test_fused_into_device_buffers_on_a_stream(gpu):
 # ------------------------------------------------------------------ 3. checks that need a context
 @pytest.fixture(scope="module")
 def contexts(gpu):
-    p = oppoint(2, 256, 112)
-    made = dict(plain=gpu.Batch(p, 3), reverse=gpu.Batch(p, 3, reverse=True), seq=gpu.Batch(p, 3, sequence=True),
-                seq_rev=gpu.Batch(p, 3, sequence=True, reverse=True))
-    yield made
-    for b in made.values():
-        b.close()
+    yield from flag_contexts(gpu)
 
 
 def _batch_call(gpu, b, first=0, count=3, frames=True, out=True, in_place=False, wo=256, ho=112, weights=(1.0, 0.5), radius=None,
@@ -277,16 +231,14 @@ def test_batch_form_names_the_missing_flag(gpu, contexts, which, flag, fb_check)
     assert "OFDIS_BATCH_" + flag in gpu.lib().ofdis_last_error().decode()
 
 
-@pytest.mark.parametrize("kw", [
-    dict(frames=False), dict(out=False), dict(in_place=True), dict(weights=None, radius=2),
-    dict(first=-1), dict(count=0), dict(count=-1), dict(first=1, count=3), dict(first=3, count=1), dict(count=4),
-    dict(wo=0), dict(ho=0), dict(wo=257), dict(ho=113),
+REJECTS = [dict(frames=False), dict(out=False), dict(in_place=True), dict(weights=None, radius=2)] + RANGE_REJECTS + SIZE_REJECTS + [
     dict(radius=0), dict(radius=-1), dict(weights=(1.0,) * 9),
     dict(weights=(-0.01,)), dict(weights=(1.0, 1.01)), dict(weights=(0.5, math.nan, 0.5)), dict(weights=(math.inf,)),
     dict(tau=0.0), dict(tau=-1.0), dict(tau=math.nan), dict(tau=-math.inf), dict(tau=FLT_MIN / 2),
-    dict(fb_check=2), dict(fb_check=-1),
-    dict(alpha=-0.01), dict(beta=-0.5), dict(alpha=math.nan), dict(beta=math.inf), dict(fb_check=0, alpha=math.nan),
-], ids=lambda kw: ",".join(f"{k}={v}" for k, v in kw.items()))
+    dict(fb_check=2), dict(fb_check=-1)] + FB_REJECTS + [dict(fb_check=0, alpha=math.nan)]
+
+
+@pytest.mark.parametrize("kw", REJECTS, ids=lambda kw: ",".join(f"{k}={v}" for k, v in kw.items()))
 def test_batch_form_rejects(gpu, contexts, kw):
     assert _batch_call(gpu, contexts["seq_rev"], **kw) == INVALID
     assert gpu.lib().ofdis_last_error()
@@ -303,10 +255,10 @@ def test_quality_five_frames_against_three(gpu):
     reach in both directions at every pixel of the crop (below sqrt(3 / 5): a bilinear sample averages its noise over up to
     four pixels, and the centre pixel, which is not resampled, weighs 1/5 instead of 1/3)."""
     w, h, n = 256, 128, 6
-    clean = _clip(w, h, 1, n + 1)
+    clean = smooth_clip(w, h, 1, n + 1)
     rng = np.random.default_rng(99)
     noisy = np.clip(np.rint(clean + rng.normal(0.0, 8.0, clean.shape)), 0, 255).astype(np.uint8)
-    b, d = _sequence_context(gpu, noisy)
+    b, (d,) = run_context(gpu, noisy)
     try:
         three = b.temporal_filter(d.ptr, w, h, wn=1.0, tau=math.inf)
         five, support = b.trajectory_filter(d.ptr, w, h, trajectory_weights(2), tau=math.inf, support=True)
@@ -330,7 +282,7 @@ def test_temporal_filter_frames_tool_with_a_radius(gpu, tmp_path):
     import sys
     from PIL import Image
     w, h, n = 250, 107, 4
-    clip = _clip(w, h, 1, n + 1)
+    clip = smooth_clip(w, h, 1, n + 1)
     paths = []
     for k, f in enumerate(clip):
         paths.append(str(tmp_path / f"f{k}.png"))
@@ -340,14 +292,14 @@ def test_temporal_filter_frames_tool_with_a_radius(gpu, tmp_path):
     res = subprocess.run([sys.executable, tool, "--radius", "2", "--sigma", "1.5", "--wn", "0.75", "--tau", "24"] + paths + [stem],
                          capture_output=True, text=True, timeout=300)
     assert res.returncode == 0, (res.stdout, res.stderr)
-    b, d = _sequence_context(gpu, clip)
+    b, (d,) = run_context(gpu, clip)
     try:
         want = b.trajectory_filter(d.ptr, w, h, trajectory_weights(2, 0.75, sigma=1.5), tau=24.0)
         three = b.temporal_filter(d.ptr, w, h, wn=0.75, tau=24.0)
     finally:
         b.close()
     got = np.stack([np.asarray(Image.open(f"{stem}_{k:03d}.png")) for k in range(n + 1)])
-    assert_u8_equal(got, want, "the tool's files")
+    assert_same_bits(got, want, "the tool's files")
     assert (got != three).any()
     res = subprocess.run([sys.executable, tool, "--radius", "9"] + paths + [stem], capture_output=True, text=True, timeout=300)
     assert res.returncode != 0 and "--radius" in (res.stderr + res.stdout)

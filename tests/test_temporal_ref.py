@@ -6,9 +6,9 @@ import pytest
 
 from of_dis_amd import temporal
 from of_dis_amd.temporal import SUPPORT_NEXT, SUPPORT_PREV, temporal_filter_ref
+from seq_products import FLT_MIN
 
 _f32 = np.float32
-FLT_MIN = float(np.finfo(_f32).tiny)
 
 
 def _frames(rng, n, h, w, noc):

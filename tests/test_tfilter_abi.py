@@ -10,9 +10,9 @@ import pytest
 
 import abi
 from of_dis_amd import capi, temporal
+from seq_products import FLT_MIN
 
 _f32 = np.float32
-FLT_MIN = float(np.finfo(_f32).tiny)
 
 
 def test_defaults_match_the_binding():

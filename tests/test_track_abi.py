@@ -9,6 +9,7 @@ import pytest
 
 import abi
 from of_dis_amd import capi, tracking
+from stereo_lr_ref import bits as _bits
 
 _f32 = np.float32
 
@@ -84,10 +85,6 @@ def test_batch_track_points_without_a_context():
 
 
 # ------------------------------------------------------------------ the numpy statement of the definition
-def _bits(a):
-    return np.ascontiguousarray(a, _f32).view(np.uint32)
-
-
 @pytest.mark.parametrize("d", [(0.25, -0.5), (1.75, 0.25), (-2.5, 1.0), (0.0, 0.0)])
 def test_constant_flow_moves_a_seed_by_k_times_d(d):
     """quarter-pixel values: every position and every product of the bilinear blend is exact in float32"""

@@ -10,9 +10,9 @@ import pytest
 
 import abi
 from of_dis_amd import capi
+from seq_products import FLT_MIN
 
 _f32 = np.float32
-FLT_MIN = float(np.finfo(_f32).tiny)
 
 
 def test_the_header_states_the_consequences():

@@ -8,7 +8,6 @@ from of_dis_amd import tracking
 
 _f32 = np.float32
 SIZES = [(37, 11), (64, 16), (1, 9), (13, 1), (1, 1), (6, 5), (33, 7)]
-FLT_MIN = float(np.finfo(_f32).tiny)
 
 
 def _frames(rng, n, w, h, noc, wild):
