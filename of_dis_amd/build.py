@@ -131,6 +131,20 @@ def testhooks_path():
     return os.path.join(LIBDIR, "libofdis_testhooks.so")
 
 
+IO_PROBE_SOURCES = [os.path.join(ROOT, "tests", "c", "image_io_probe.cpp"), os.path.join(CSRC, "host", "image_io.cpp")]
+
+
+def io_probe_path():
+    """The stand-alone program around host/image_io.cpp that tests/test_image_io.py feeds its files to."""
+    return os.path.join(LIBDIR, "image_io_probe")
+
+
+def io_probe_command(exe, extra_flags=()):
+    """The host compiler's command line for the probe (tools/host_sanitize.sh builds a second one with sanitizer flags)."""
+    return ["g++", "-O2", "-g", "-std=c++17", "-Wall", "-Wextra"] + list(extra_flags) + ["-I", os.path.join(CSRC, "host")] + \
+        IO_PROBE_SOURCES + ["-o", exe, "-lz"]
+
+
 def compile_units(csrc, outdir, force=False, verbose=False, extra_flags=None, only=None):
     """Compile every translation unit of the library (kernel files once per contract) from `csrc` into `outdir`; returns
     the object list.  extra_flags: {file name: [flags]} on top of PER_FILE_FLAGS (developer A/B builds, tools/ab_build.py).
@@ -201,6 +215,11 @@ def build(force=False, verbose=False):
                 _run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-O2", "-D_POSIX_C_SOURCE=199309L", "-I",
                       os.path.join(ROOT, "include"), c_test, "-o", exe, "-L", LIBDIR, "-lofdis_hip", "-Wl,-rpath,$ORIGIN"],
                      verbose)
+        # the host image readers and writers alone (tests/c/image_io_probe.cpp): image_io.cpp and zlib, no HIP runtime
+        if os.path.exists(IO_PROBE_SOURCES[0]):
+            exe = io_probe_path()
+            if force or _newer(exe, IO_PROBE_SOURCES + [os.path.join(CSRC, "host", "image_io.h")]):
+                _run(io_probe_command(exe), verbose)
         hooks = os.path.join(ROOT, "tests", "csrc", "ofdis_testhooks.hip")
         if os.path.exists(hooks):
             # the launch hooks (tests/csrc/ofdis_launch_hooks.hip) call the product's own launchers: TESTHOOK_UNITS compiled

@@ -1,25 +1,34 @@
 #include "image_io.h"
 
+#include <limits.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
+#include <sys/stat.h>
 #include <zlib.h>
 
-#include <fstream>
+#include <exception>
+#include <utility>
 
 namespace ofdis_host {
 namespace {
 
+// A reader's answer to a malformed file is `false` and a message: every index below is checked against the file's length, and
+// every size a header states against what the file could hold, before anything is allocated for it.
+
+// the whole of a REGULAR file (a directory opens as a stream as well, and then has no length to speak of)
 bool slurp(const std::string& path, std::vector<uint8_t>* buf) {
-  std::ifstream f(path, std::ios::binary);
+  struct stat st;
+  if (stat(path.c_str(), &st) != 0 || !S_ISREG(st.st_mode) || st.st_size < 0) return false;
+  FILE* f = fopen(path.c_str(), "rb");
   if (!f) return false;
-  f.seekg(0, std::ios::end);
-  const std::streamoff n = f.tellg();
-  f.seekg(0);
-  buf->resize((size_t)n);
-  f.read((char*)buf->data(), n);
-  return (bool)f;
+  buf->resize((size_t)st.st_size);
+  const bool ok = fread(buf->data(), 1, buf->size(), f) == buf->size();
+  fclose(f);
+  return ok;
 }
 
+// the next decimal number of a PNM header, after white space and comments; -1 if there is none, INT_MAX if it is larger
 int pnm_int(const std::vector<uint8_t>& b, size_t* pos) {
   size_t p = *pos;
   for (;;) {
@@ -33,7 +42,8 @@ int pnm_int(const std::vector<uint8_t>& b, size_t* pos) {
   int v = 0;
   bool any = false;
   while (p < b.size() && b[p] >= '0' && b[p] <= '9') {
-    v = v * 10 + (b[p] - '0');
+    const int d = b[p] - '0';
+    v = v > (INT_MAX - d) / 10 ? INT_MAX : v * 10 + d;  // saturates
     ++p;
     any = true;
   }
@@ -41,15 +51,21 @@ int pnm_int(const std::vector<uint8_t>& b, size_t* pos) {
   return any ? v : -1;
 }
 
+// the shortest P5 file: "P5 1 1 255", one white space, one sample
+const size_t kPnmMinBytes = 12;
+
 bool read_pnm(const std::vector<uint8_t>& b, Image8* im, std::string* err) {
+  if (b.size() < kPnmMinBytes) { *err = "PNM file is truncated"; return false; }
   const int ch = (b[1] == '5') ? 1 : 3;
   size_t pos = 2;
   const int w = pnm_int(b, &pos), h = pnm_int(b, &pos), maxv = pnm_int(b, &pos);
-  if (w <= 0 || h <= 0 || maxv <= 0 || maxv > 255) { *err = "unsupported PNM header (need 8-bit P5/P6)"; return false; }
+  // (a maxval below 255 would need the samples scaled by 255 / maxval, as every other reader does: not an 8-bit file)
+  if (w <= 0 || h <= 0 || maxv != 255) { *err = "unsupported PNM header (need 8-bit P5/P6, maxval 255)"; return false; }
   ++pos;  // single whitespace after maxval
-  if (pos + (size_t)w * h * ch > b.size()) { *err = "PNM file is truncated"; return false; }
+  if (pos >= b.size() || (uint64_t)w > (uint64_t)(b.size() - pos) / ((uint64_t)h * ch)) { *err = "PNM file is truncated"; return false; }
+  const size_t n = (size_t)w * h * ch;  // (at most the file's length)
   im->width = w; im->height = h; im->channels = ch;
-  im->data.assign(b.begin() + pos, b.begin() + pos + (size_t)w * h * ch);
+  im->data.assign(b.begin() + pos, b.begin() + pos + n);
   if (ch == 3)  // stored R,G,B -> B,G,R (cv::imread order)
     for (size_t i = 0; i < (size_t)w * h; ++i) std::swap(im->data[3 * i], im->data[3 * i + 2]);
   return true;
@@ -57,27 +73,45 @@ bool read_pnm(const std::vector<uint8_t>& b, Image8* im, std::string* err) {
 
 uint32_t be32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
 
+// the shortest PNG that can decode: signature, IHDR (12 + 13), one IDAT (12 + data); IEND is not insisted on
+const size_t kPngMinBytes = 8 + 25 + 12;
+// No deflate stream inflates to more than 1032 times its length (zlib's technical notes, "Maximum Compression Factor": a
+// length-258 match costs at least two bits): an image whose scanlines would take more than that is refused unallocated.
+const uint64_t kInflateMaxRatio = 1032;
+
 bool read_png(const std::vector<uint8_t>& b, Image8* im, std::string* err) {
+  if (b.size() < kPngMinBytes) { *err = "PNG file is truncated"; return false; }
   size_t pos = 8;
-  int w = 0, h = 0, depth = 0, ctype = 0, interlace = 0;
+  bool have_ihdr = false, have_plte = false;
+  uint32_t w = 0, h = 0;
+  int depth = 0, ctype = 0, compression = 0, filter = 0, interlace = 0;
   std::vector<uint8_t> idat, plte;
-  while (pos + 12 <= b.size()) {
+  while (b.size() - pos >= 12) {  // length, type, data, CRC (not checked)
     const uint32_t len = be32(&b[pos]);
     const char* type = (const char*)&b[pos + 4];
     const uint8_t* d = &b[pos + 8];
-    if (pos + 12 + len > b.size()) { *err = "PNG chunk overruns file"; return false; }
-    if (!memcmp(type, "IHDR", 4)) {
-      w = (int)be32(d); h = (int)be32(d + 4); depth = d[8]; ctype = d[9]; interlace = d[12];
+    if (len > b.size() - pos - 12) { *err = "PNG chunk overruns file"; return false; }
+    const bool ihdr = !memcmp(type, "IHDR", 4);
+    if (!ihdr && !have_ihdr) { *err = "PNG does not start with IHDR"; return false; }
+    if (ihdr && have_ihdr) { *err = "PNG has two IHDR chunks"; return false; }
+    if (ihdr) {
+      if (len != 13) { *err = "PNG IHDR chunk is not 13 bytes long"; return false; }
+      w = be32(d); h = be32(d + 4); depth = d[8]; ctype = d[9]; compression = d[10]; filter = d[11]; interlace = d[12];
+      have_ihdr = true;
     } else if (!memcmp(type, "PLTE", 4)) {
+      if (have_plte || len == 0 || len % 3 != 0 || len > 768) { *err = "PNG PLTE chunk is not 1..256 entries of 3 bytes, once"; return false; }
       plte.assign(d, d + len);
+      have_plte = true;
     } else if (!memcmp(type, "IDAT", 4)) {
       idat.insert(idat.end(), d, d + len);
     } else if (!memcmp(type, "IEND", 4)) {
       break;
     }
-    pos += 12 + len;
+    pos += 12 + (size_t)len;
   }
-  if (w <= 0 || h <= 0 || depth != 8 || interlace != 0) { *err = "unsupported PNG (need 8-bit, non-interlaced)"; return false; }
+  if (!have_ihdr) { *err = "PNG does not start with IHDR"; return false; }
+  if (w == 0 || h == 0 || w > 0x7fffffffu || h > 0x7fffffffu) { *err = "PNG size is not 1..2^31-1"; return false; }
+  if (depth != 8 || interlace != 0 || compression != 0 || filter != 0) { *err = "unsupported PNG (need 8-bit, non-interlaced)"; return false; }
   int spp;
   switch (ctype) {
     case 0: spp = 1; break;
@@ -87,16 +121,21 @@ bool read_png(const std::vector<uint8_t>& b, Image8* im, std::string* err) {
     case 6: spp = 4; break;
     default: *err = "unsupported PNG colour type"; return false;
   }
+  if (ctype == 3 && !have_plte) { *err = "PNG palette image without PLTE chunk"; return false; }
+  // filter byte + samples per scanline: below 2^33 each, below 2^64 together; against what the IDAT bytes could inflate to
+  const uint64_t raw_bytes = ((uint64_t)w * spp + 1) * h;
+  if (raw_bytes > kInflateMaxRatio * idat.size()) { *err = "PNG image data is too short for its size"; return false; }
   const size_t stride = (size_t)w * spp;
-  std::vector<uint8_t> raw((stride + 1) * h);
+  std::vector<uint8_t> raw((size_t)raw_bytes);
   uLongf rawlen = (uLongf)raw.size();
   if (uncompress(raw.data(), &rawlen, idat.data(), (uLong)idat.size()) != Z_OK || rawlen != raw.size()) {
     *err = "PNG inflate failed";
     return false;
   }
   std::vector<uint8_t> pix(stride * h);
-  for (int y = 0; y < h; ++y) {  // undo the scanline filters
+  for (size_t y = 0; y < h; ++y) {  // undo the scanline filters
     const int ft = raw[(stride + 1) * y];
+    if (ft > 4) { *err = "PNG scanline has an unknown filter type"; return false; }
     const uint8_t* in = &raw[(stride + 1) * y + 1];
     uint8_t* cur = &pix[stride * y];
     const uint8_t* up = y ? &pix[stride * (y - 1)] : nullptr;
@@ -118,16 +157,17 @@ bool read_png(const std::vector<uint8_t>& b, Image8* im, std::string* err) {
     }
   }
   const bool color = (ctype == 2 || ctype == 6 || ctype == 3);
-  im->width = w; im->height = h; im->channels = color ? 3 : 1;
-  im->data.resize((size_t)w * h * im->channels);
-  for (size_t i = 0; i < (size_t)w * h; ++i) {
+  const size_t n = (size_t)w * h;
+  im->width = (int)w; im->height = (int)h; im->channels = color ? 3 : 1;
+  im->data.resize(n * im->channels);
+  for (size_t i = 0; i < n; ++i) {
     if (ctype == 0 || ctype == 4) {
       im->data[i] = pix[i * spp];
     } else {
       uint8_t r, g, bl;
       if (ctype == 3) {
         const size_t k = (size_t)pix[i] * 3;
-        if (k + 2 >= plte.size()) { r = g = bl = 0; }
+        if (k + 2 >= plte.size()) { r = g = bl = 0; }  // an index beyond the palette: black
         else { r = plte[k]; g = plte[k + 1]; bl = plte[k + 2]; }
       } else {
         r = pix[i * spp]; g = pix[i * spp + 1]; bl = pix[i * spp + 2];
@@ -138,16 +178,14 @@ bool read_png(const std::vector<uint8_t>& b, Image8* im, std::string* err) {
   return true;
 }
 
-}  // namespace
-
-bool read_image(const std::string& path, int want_channels, Image8* out, std::string* err) {
+bool read_any(const std::string& path, int want_channels, Image8* out, std::string* err) {
   std::vector<uint8_t> b;
-  if (!slurp(path, &b) || b.size() < 16) { *err = "cannot read " + path; return false; }
+  if (!slurp(path, &b)) { *err = "cannot read " + path; return false; }
   Image8 im;
   static const uint8_t png_sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
   bool ok;
-  if (b[0] == 'P' && (b[1] == '5' || b[1] == '6')) ok = read_pnm(b, &im, err);
-  else if (!memcmp(b.data(), png_sig, 8)) ok = read_png(b, &im, err);
+  if (b.size() >= 2 && b[0] == 'P' && (b[1] == '5' || b[1] == '6')) ok = read_pnm(b, &im, err);
+  else if (b.size() >= 8 && !memcmp(b.data(), png_sig, 8)) ok = read_png(b, &im, err);
   else { *err = path + ": unsupported format (PGM/PPM binary or PNG)"; return false; }
   if (!ok) { *err = path + ": " + *err; return false; }
   if (im.channels == want_channels) { *out = std::move(im); return true; }
@@ -165,6 +203,18 @@ bool read_image(const std::string& path, int want_channels, Image8* out, std::st
   }
   *out = std::move(cv);
   return true;
+}
+
+}  // namespace
+
+// (never throws: a well-formed file too large for this machine's memory is an unreadable file like any other)
+bool read_image(const std::string& path, int want_channels, Image8* out, std::string* err) {
+  try {
+    return read_any(path, want_channels, out, err);
+  } catch (const std::exception& e) {
+    try { *err = path + ": " + e.what(); } catch (...) { err->clear(); }
+    return false;
+  }
 }
 
 bool write_flo(const std::string& path, const float* flow_uv, int width, int height, std::string* err) {

@@ -17,6 +17,9 @@ struct Image8 {
 // Reads P5/P6 PNM or PNG (8-bit gray / gray+alpha / RGB / RGBA / palette, non-interlaced).
 // want_channels = 1: colour input is converted with OpenCV's fixed-point BGR2GRAY
 // (Y = (4899 R + 9617 G + 1868 B + 8192) >> 14); = 3: gray input is replicated.
+// Anything else -- not a regular file, another format, maxval other than 255, a header that promises more than the file
+// holds -- is `false` and one line in *err that names the path: never an exception, never a read outside the file
+// (INTEGRATION.md 6 lists what is refused; tests/test_image_io.py).
 bool read_image(const std::string& path, int want_channels, Image8* out, std::string* err);
 
 // SaveFlowFile (run_dense.cpp:16-57): "PIEH", int32 width, int32 height, then rows of (float u, float v).

@@ -17,6 +17,7 @@
 #include <sys/time.h>
 
 #include <algorithm>
+#include <exception>
 #include <string>
 #include <vector>
 
@@ -51,7 +52,13 @@ int main(int argc, char** argv) {
   const char* f_out = argv[3];
   ofdis_host::Image8 ia, ib;
   std::string err;
-  if (!ofdis_host::read_image(f_a, OFDIS_NOC, &ia, &err) || !ofdis_host::read_image(f_b, OFDIS_NOC, &ib, &err)) {
+  bool readable = false;
+  try {
+    readable = ofdis_host::read_image(f_a, OFDIS_NOC, &ia, &err) && ofdis_host::read_image(f_b, OFDIS_NOC, &ib, &err);
+  } catch (const std::exception& e) {  // of last resort: the readers report, they do not throw
+    err = std::string(f_a) + " / " + f_b + ": " + e.what();
+  }
+  if (!readable) {
     fprintf(stderr, "%s\n", err.c_str());
     return 1;
   }

@@ -54,6 +54,7 @@
 #include <atomic>
 #include <condition_variable>
 #include <deque>
+#include <exception>
 #include <fstream>
 #include <memory>
 #include <mutex>
@@ -101,6 +102,19 @@ void frame_range(int total, int rank, int world, int* lo, int* hi) {  // of_dis_
   const int base = total / world, rem = total % world;
   *lo = rank * base + std::min(rank, rem);
   *hi = *lo + base + (rank < rem ? 1 : 0);
+}
+
+// read_image with a catch of last resort: whatever a decoder throws is that image's error line -- an exception that left a
+// decode worker would be std::terminate for every share on every GPU, with passes in flight
+bool read_frame(const std::string& path, ofdis_host::Image8* im, std::string* err) {
+  try {
+    return ofdis_host::read_image(path, OFDIS_NOC, im, err);
+  } catch (const std::exception& e) {
+    *err = path + ": " + e.what();
+  } catch (...) {
+    *err = path + ": cannot decode";
+  }
+  return false;
 }
 
 // The pairs of a chunk are decoded / written by `threads` workers side by side (--io-threads: the file system and the PNM / PNG
@@ -271,7 +285,7 @@ void run_share(const std::vector<Pair>& pairs, const ofdis_params& p0, int width
             const std::string& name = k < c->m ? pairs[c0 + k].a : pairs[c0 + k - 1].b;
             ofdis_host::Image8 im;
             std::string err;
-            c->fok[k] = ofdis_host::read_image(name, OFDIS_NOC, &im, &err);
+            c->fok[k] = read_frame(name, &im, &err);
             if (c->fok[k] && (im.width != width_org || im.height != height_org)) {
               c->fok[k] = 0;
               err = name + ": not " + std::to_string(width_org) + "x" + std::to_string(height_org) + " like the first readable frame";
@@ -299,7 +313,7 @@ void run_share(const std::vector<Pair>& pairs, const ofdis_params& p0, int width
           const Pair& pr = pairs[c0 + k];
           ofdis_host::Image8 ia, ib;
           std::string err;
-          c->ok[k] = ofdis_host::read_image(pr.a, OFDIS_NOC, &ia, &err) && ofdis_host::read_image(pr.b, OFDIS_NOC, &ib, &err);
+          c->ok[k] = read_frame(pr.a, &ia, &err) && read_frame(pr.b, &ib, &err);
           if (c->ok[k] && (ia.width != width_org || ia.height != height_org || ib.width != width_org || ib.height != height_org)) {
             c->ok[k] = 0;
             err = pr.a + " / " + pr.b + ": not " + std::to_string(width_org) + "x" + std::to_string(height_org) + " like the first readable pair";
@@ -682,7 +696,7 @@ int main(int argc, char** argv) {
     std::string err;
     for (size_t i = 0; i < pairs.size() && width_org < 1; ++i) {
       ofdis_host::Image8 first;
-      if (ofdis_host::read_image(pairs[i].a, OFDIS_NOC, &first, &err)) {
+      if (read_frame(pairs[i].a, &first, &err)) {
         width_org = first.width;
         height_org = first.height;
       }

@@ -369,3 +369,99 @@ def test_rgb_sequence_driver_chunks_take_the_fused_tv_kernel(gpu, tmp_path):
         r1 = subprocess.run([EXE[3], fa, fb, fo, "2"], capture_output=True, text=True, timeout=120)
         assert r1.returncode == 0, r1.stderr
         assert open(fo, "rb").read() == open(tmp_path / f"q{k:02d}.flo", "rb").read(), f"rgb pair {k}"
+
+
+def _bad_first_images(tmp_path, good_png):
+    """{name: path} of four things that are not images, each of which once ended the program that was given it: a directory, a
+    PNG of under 100 bytes whose IHDR claims (2^31-1)^2 pixels, a PNG whose IHDR chunk is 8 bytes long, and a PNG cut in its image
+    data (tests/test_image_io.py holds the whole corpus, on the CPU)."""
+    import png_files
+    (tmp_path / "bad_dir.png").mkdir()
+    blobs = {"bad_huge.png": png_files.png_raw(2 ** 31 - 1, 2 ** 31 - 1, 2, bytes(13)),
+             "bad_short_ihdr.png": png_files.SIGNATURE + png_files.chunk(b"IHDR", struct.pack(">II", 256, 128)) +
+             good_png[33:],  # (33: signature and the 25 bytes of a whole IHDR chunk)
+             "bad_truncated.png": good_png[:len(good_png) * 3 // 5]}
+    for name, blob in blobs.items():
+        (tmp_path / name).write_bytes(blob)
+    return {name: str(tmp_path / name) for name in ["bad_dir.png"] + list(blobs)}
+
+
+@pytest.mark.gpu
+def test_sequence_driver_survives_malformed_images(gpu, tmp_path):
+    """run_OF_RGB_seq over five good pairs and four whose first image is malformed in a way that used to end the process (an
+    exception in a decode worker): each bad path is named on stderr, its .flo is not written, the exit status is 1, and the
+    five good .flo files are the single-pair binary's, byte for byte."""
+    import png_files
+    w, h, n = 256, 128, 5
+    pairs = _write_pairs(tmp_path, n, w, h, channels=3, seed0=700)
+    ia, _, _ = gen_synth.make_pair(w, h, 700, channels=3)
+    bad = _bad_first_images(tmp_path, png_files.png(ia[..., ::-1], 2, 4))
+    lines = [f"{fa} {fb} {tmp_path}/o{k}.flo" for k, (fa, fb) in enumerate(pairs)]
+    for at, (name, path) in zip((0, 2, 5, 8), bad.items()):  # first, inside a chunk, first of a chunk, last
+        lines.insert(at, f"{path} {pairs[0][1]} {tmp_path}/{name}.flo")
+    lst = tmp_path / "bad.txt"
+    lst.write_text("\n".join(lines) + "\n")
+    r = subprocess.run([SEQ[3], str(lst), "--chunk", "3", "3"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 1, (r.returncode, r.stdout, r.stderr)
+    for name, path in bad.items():
+        assert path in r.stderr, (name, r.stderr)
+        assert not os.path.exists(tmp_path / f"{name}.flo"), name
+    for k, (fa, fb) in enumerate(pairs):
+        fo = str(tmp_path / f"s{k}.flo")
+        r1 = subprocess.run([EXE[3], fa, fb, fo, "3"], capture_output=True, text=True, timeout=120)
+        assert r1.returncode == 0, r1.stderr
+        assert open(fo, "rb").read() == open(tmp_path / f"o{k}.flo", "rb").read(), f"rgb pair {k}"
+
+
+@pytest.mark.gpu
+def test_run_of_int_reads_every_png_colour_type(gpu, tmp_path):
+    """run_OF_INT on the five pairs above stored as gray, gray+alpha, palette, RGB and RGBA PNG (every scanline filter in each
+    file; the last two converted to gray by the reader): the .flo files are the bytes of the run on PGMs written from the
+    arrays numpy converted.  A malformed first image is status 1 and one line on stderr."""
+    import png_files
+    w, h, n = 256, 128, 5
+    filters = (4, 1, 3, 0, 2)
+    shuffle = np.random.default_rng(3).permutation(256).astype(np.uint8)  # palette entry shuffle[g] is the gray level g
+
+    def store(path, bgr, gray, kind):
+        g = gray[..., None]
+        rgb = bgr[..., ::-1]
+        if kind == "gray":
+            blob = png_files.png(g, 0, filters)
+        elif kind == "gray_alpha":
+            blob = png_files.png(np.concatenate([g, 255 - g], -1), 4, filters)
+        elif kind == "palette":
+            pal = np.zeros((256, 3), np.uint8)
+            pal[shuffle] = np.arange(256, dtype=np.uint8)[:, None]
+            blob = png_files.png(shuffle[g], 3, filters, pal, idat_split=(1000, 0, 1))
+        elif kind == "rgb":
+            blob = png_files.png(rgb, 2, filters)
+        else:
+            blob = png_files.png(np.concatenate([rgb, g], -1), 6, filters)
+        with open(path, "wb") as f:
+            f.write(blob)
+
+    kinds = ["gray", "gray_alpha", "palette", "rgb", "rgba"]
+    for k in range(n):
+        ia, ib, _ = gen_synth.make_pair(w, h, 700 + k, channels=3)  # B,G,R
+        gray = [((im.astype(np.int64) @ np.array([1868, 9617, 4899]) + 8192) >> 14).astype(np.uint8) for im in (ia, ib)]
+        fa, fb = str(tmp_path / f"a{k}.pgm"), str(tmp_path / f"b{k}.pgm")
+        gen_synth.write_pgm(fa, gray[0])
+        gen_synth.write_pgm(fb, gray[1])
+        # the first image in format k, the second in the next one: every format holds two of the ten images
+        pa, pb = str(tmp_path / f"a{k}.png"), str(tmp_path / f"b{k}.png")
+        store(pa, ia, gray[0], kinds[k])
+        store(pb, ib, gray[1], kinds[(k + 1) % n])
+        out = []
+        for tag, xa, xb in (("pgm", fa, fb), ("png", pa, pb)):
+            fo = str(tmp_path / f"{tag}{k}.flo")
+            r = subprocess.run([EXE[1], xa, xb, fo, "2"], capture_output=True, text=True, timeout=120)
+            assert r.returncode == 0, (kinds[k], r.stderr)
+            out.append(open(fo, "rb").read())
+        assert len(out[0]) == 12 + 8 * w * h and out[1] == out[0], f"pair {k}: {kinds[k]} / {kinds[(k + 1) % n]} PNG differs from PGM"
+    for name, path in _bad_first_images(tmp_path, open(tmp_path / "a3.png", "rb").read()).items():
+        fo = tmp_path / f"{name}.flo"
+        r = subprocess.run([EXE[1], path, str(tmp_path / "b0.pgm"), str(fo), "2"], capture_output=True, text=True, timeout=120)
+        assert r.returncode == 1 and r.stdout == "", (name, r.returncode, r.stdout, r.stderr)
+        assert len(r.stderr.splitlines()) == 1 and path in r.stderr, (name, r.stderr)
+        assert not fo.exists()
