@@ -145,6 +145,40 @@ def io_probe_command(exe, extra_flags=()):
         IO_PROBE_SOURCES + ["-o", exe, "-lz"]
 
 
+# The host executables: main file -> (program, OFDIS_NOC, OFDIS_MODE).  Every program links its main and HOST_COMMON, nothing
+# else: a new .cpp under host/ belongs to one of the two lists, by name.
+HOST_DIR = os.path.join(CSRC, "host")
+HOST_COMMON = ["image_io.cpp"]
+HOST_MAINS = {"run_dense_main.cpp": (("run_OF_INT", 1, 1), ("run_OF_RGB", 3, 1), ("run_DE_INT", 1, 2), ("run_DE_RGB", 3, 2)),
+              "run_seq_main.cpp": (("run_OF_INT_seq", 1, 1), ("run_OF_RGB_seq", 3, 1), ("run_DE_INT_seq", 1, 2),
+                                   ("run_DE_RGB_seq", 3, 2))}
+
+
+def host_sources(main_name):
+    return [os.path.join(HOST_DIR, f) for f in [main_name] + HOST_COMMON]
+
+
+# The sequence driver linked against tests/c/ofdis_abi_stub.c instead of the library: no HIP runtime, runs without a GPU
+# (tests/test_seq_driver_stub.py).  program -> (OFDIS_NOC, OFDIS_MODE)
+SEQ_STUB_SOURCE = os.path.join(ROOT, "tests", "c", "ofdis_abi_stub.c")
+SEQ_STUB_PROGRAMS = {"run_OF_INT_seq_stub": (1, 1), "run_DE_RGB_seq_stub": (3, 2)}
+
+
+def seq_stub_path(name):
+    return os.path.join(LIBDIR, name)
+
+
+def seq_stub_commands(exe, name, extra_flags=()):
+    """The host compilers' command lines for a stub-linked driver: the stub as C, then the driver's own sources as C++ with it
+    (tools/host_sanitize.sh builds further pairs with sanitizer flags)."""
+    noc, mode = SEQ_STUB_PROGRAMS[name]
+    flags = ["-O2", "-g", "-Wall", "-Wextra", "-pthread"] + list(extra_flags) + ["-I", os.path.join(ROOT, "include")]
+    obj = exe + ".stub.o"
+    return [["gcc", "-std=c11"] + flags + ["-c", SEQ_STUB_SOURCE, "-o", obj],
+            ["g++", "-std=c++17"] + flags + [f"-DOFDIS_NOC={noc}", f"-DOFDIS_MODE={mode}"] + host_sources("run_seq_main.cpp")
+            + [obj, "-o", exe, "-lm", "-lz"]]
+
+
 def compile_units(csrc, outdir, force=False, verbose=False, extra_flags=None, only=None):
     """Compile every translation unit of the library (kernel files once per contract) from `csrc` into `outdir`; returns
     the object list.  extra_flags: {file name: [flags]} on top of PER_FILE_FLAGS (developer A/B builds, tools/ab_build.py).
@@ -186,24 +220,18 @@ def build(force=False, verbose=False):
         _run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", f"-Wl,--version-script={vs}", "-o", so] + objs, verbose)
     # host executables: the reference's CLI contract (run_OF_INT / run_OF_RGB and the stereo-depth run_DE_INT / run_DE_RGB,
     # one pair per process: host/run_dense_main.cpp) and the sequence drivers (run_OF_*_seq / run_DE_*_seq: many pairs,
-    # one host thread per GPU: host/run_seq_main.cpp); every other .cpp under host/ is shared by both mains
-    host_dir = os.path.join(CSRC, "host")
-    mains = {"run_dense_main.cpp": (("run_OF_INT", 1, 1), ("run_OF_RGB", 3, 1), ("run_DE_INT", 1, 2), ("run_DE_RGB", 3, 2)),
-             "run_seq_main.cpp": (("run_OF_INT_seq", 1, 1), ("run_OF_RGB_seq", 3, 1), ("run_DE_INT_seq", 1, 2),
-                                  ("run_DE_RGB_seq", 3, 2))}
-    if os.path.isdir(host_dir):
-        common = [os.path.join(host_dir, f) for f in sorted(os.listdir(host_dir)) if f.endswith(".cpp") and f not in mains]
-        host_hdrs = [os.path.join(host_dir, f) for f in os.listdir(host_dir) if f.endswith(".h")]
-        for main_name, exes in mains.items():
-            main_cpp = os.path.join(host_dir, main_name)
-            if not os.path.exists(main_cpp):
-                continue
-            for name, noc, mode in exes:
-                exe = os.path.join(LIBDIR, name)
-                if force or _newer(exe, [main_cpp] + common + host_hdrs + headers + [so]):
-                    _run(["g++", "-O2", "-std=c++17", "-Wall", "-pthread", f"-DOFDIS_NOC={noc}", f"-DOFDIS_MODE={mode}", "-I",
-                          os.path.join(ROOT, "include"), main_cpp] + common
-                         + ["-o", exe, "-L", LIBDIR, "-lofdis_hip", "-lz", "-Wl,-rpath,$ORIGIN"], verbose)
+    # one host thread per GPU: host/run_seq_main.cpp), each with HOST_COMMON
+    host_hdrs = [os.path.join(HOST_DIR, f) for f in os.listdir(HOST_DIR) if f.endswith(".h")] if os.path.isdir(HOST_DIR) else []
+    for main_name, exes in HOST_MAINS.items():
+        sources = host_sources(main_name)
+        if not os.path.exists(sources[0]):
+            continue
+        for name, noc, mode in exes:
+            exe = os.path.join(LIBDIR, name)
+            if force or _newer(exe, sources + host_hdrs + headers + [so]):
+                _run(["g++", "-O2", "-std=c++17", "-Wall", "-pthread", f"-DOFDIS_NOC={noc}", f"-DOFDIS_MODE={mode}", "-I",
+                      os.path.join(ROOT, "include")] + sources
+                     + ["-o", exe, "-L", LIBDIR, "-lofdis_hip", "-lz", "-Wl,-rpath,$ORIGIN"], verbose)
     # test-only artefacts: a failure here must not take the product down with it (it is reported, the tests that need
     # them fail on their own)
     try:
@@ -220,6 +248,14 @@ def build(force=False, verbose=False):
             exe = io_probe_path()
             if force or _newer(exe, IO_PROBE_SOURCES + [os.path.join(CSRC, "host", "image_io.h")]):
                 _run(io_probe_command(exe), verbose)
+        # the sequence driver on the host-only stand-in for the library (tests/c/ofdis_abi_stub.c)
+        if os.path.exists(SEQ_STUB_SOURCE):
+            for name in SEQ_STUB_PROGRAMS:
+                exe = seq_stub_path(name)
+                if force or _newer(exe, [SEQ_STUB_SOURCE, os.path.join(ROOT, "include", "ofdis.h")] + host_sources("run_seq_main.cpp")
+                                   + host_hdrs):
+                    for cmd in seq_stub_commands(exe, name):
+                        _run(cmd, verbose)
         hooks = os.path.join(ROOT, "tests", "csrc", "ofdis_testhooks.hip")
         if os.path.exists(hooks):
             # the launch hooks (tests/csrc/ofdis_launch_hooks.hip) call the product's own launchers: TESTHOOK_UNITS compiled

@@ -14,30 +14,18 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <sys/time.h>
 
 #include <algorithm>
 #include <exception>
 #include <string>
 #include <vector>
 
+#include "cli_common.h"
 #include "cli_params.h"
 #include "image_io.h"
 #include "ofdis.h"
 
-#ifndef OFDIS_NOC
-#define OFDIS_NOC 1
-#endif
-#ifndef OFDIS_MODE  // the reference's SELECTMODE: 1 optical flow (run_OF_*, .flo), 2 stereo depth (run_DE_*, .pfm)
-#define OFDIS_MODE 1
-#endif
-#define OFDIS_NCH (OFDIS_MODE == 2 ? 1 : 2)
-
-static double now_ms() {
-  struct timeval tv;
-  gettimeofday(&tv, nullptr);
-  return tv.tv_sec * 1000.0 + tv.tv_usec / 1000.0;
-}
+using ofdis_host::now_ms;
 
 int main(int argc, char** argv) {
   const double t_start = now_ms();
@@ -118,11 +106,7 @@ int main(int argc, char** argv) {
     return 1;
   }
   ofdis_dev_free(dfull);
-#if OFDIS_MODE == 2
-  if (!ofdis_host::write_pfm(f_out, full.data(), width_org, height_org, &err)) {
-#else
-  if (!ofdis_host::write_flo(f_out, full.data(), width_org, height_org, &err)) {
-#endif
+  if (!ofdis_host::write_float_result(f_out, full.data(), width_org, height_org, &err)) {
     printf("%s\n", err.c_str());  // the reference reports and carries on (run_dense.cpp:24-25)
   }
   if (verbosity > 1) printf("TIME (Saving flow file  ) (ms): %3g\n", now_ms() - t0);
