@@ -216,7 +216,7 @@ hipError_t launch_de_system(const DeSystemArgs& a, hipStream_t s) {
 }
 
 // sor_coupled_slow_but_readable_DE, all NS sweeps of the call in one pass
-// (the scheme of sor_wave_kernel, ofdis_sor.hip): lane = row j, at step t sweep s is at column t - j - 2s.  The
+// (the scheme of sor_kernel, ofdis_sor.hip): lane = row j, at step t sweep s is at column t - j - 2s.  The
 // updated left value is the lane's own previous result of the same sweep, the updated top value the previous
 // lane's; own, right and bottom are the previous sweep's results (the stored du for sweep 0: right and bottom
 // come from diag row t+1).  Loads run PD steps ahead through a register ring that also hands each pixel's
@@ -228,7 +228,7 @@ struct DeSlot {
 };
 
 // MAXT == 0: frames of at most 64 rows, 64 / R frames per wavefront, four wavefronts per workgroup.
-// MAXT > 0 (the scheme of sor_block_kernel): one workgroup per frame, wavefront k owns rows 64k .. 64k+63, all
+// MAXT > 0 (sor_kernel's lock-step mapping): one workgroup per frame, wavefront k owns rows 64k .. 64k+63, all
 // wavefronts advance in lock step; the values that cross a wavefront boundary travel through a double-buffered LDS
 // mailbox written at the end of a step and read at the start of the next.  Up to 16 wavefronts (h <= 1024).
 template <int NS, int PD, int MAXT>

@@ -166,7 +166,15 @@ def _spd_system(rng, B, h, w):
 @pytest.mark.parametrize("w,h,iters", [(128, 56, 3), (64, 28, 3), (32, 14, 3), (20, 15, 3), (40, 30, 1), (80, 60, 2),
                                         (128, 64, 4), (7, 5, 3), (2, 2, 3), (1, 5, 2), (30, 17, 5), (16, 70, 3),
                                         (33, 3, 3), (120, 68, 3), (37, 129, 2), (50, 300, 3), (24, 700, 1),
-                                        (12, 1030, 2)])
+                                        (12, 1030, 2),
+                                        # exactly 16 / 32 rows per frame slot and the first height of the 64-lane slot (the five
+                                        # frames leave the last wavefront ragged at four and two frames per wavefront)
+                                        (5, 16, 1), (6, 32, 2), (9, 33, 4),
+                                        (8, 65, 1),      # lock-step mapping with one sweep; the second wavefront owns one row
+                                        (6, 640, 3),     # last height of the 640-thread build, ten wavefronts
+                                        (6, 641, 2),     # first height of the 1024-thread build, two sweeps
+                                        (5, 1024, 3),    # the spilling build, all 16 wavefronts, fewer columns than ring slots
+                                        (4, 1025, 1)])   # first height of the serial fallback
 def test_sor_coupled(gpu, orc, w, h, iters):
     rng = np.random.default_rng(4)
     B = 5

@@ -68,7 +68,10 @@ def test_derivatives_smoothness_data_laplacian(pair, w, h):
 
 @pytest.mark.parametrize("w,h,iters,slow", [(128, 56, 3, False), (32, 14, 1, False), (30, 17, 5, False),
                                              (7, 5, 2, False), (2, 2, 3, False), (1, 6, 2, False), (6, 1, 2, False),
-                                             (20, 15, 3, True)])
+                                             (20, 15, 3, True),
+                                             # the sizes at which the GPU solver changes its mapping (tests/test_gpu_kernels.py)
+                                             (5, 16, 1, False), (6, 32, 2, False), (9, 33, 4, False), (8, 65, 1, False),
+                                             (6, 640, 3, False), (6, 641, 2, False), (5, 1024, 3, False), (4, 1025, 1, False)])
 def test_sor_coupled(pair, w, h, iters, slow):
     O, R = pair
     rng = np.random.default_rng(12)
