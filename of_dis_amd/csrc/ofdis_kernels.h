@@ -210,6 +210,14 @@ hipError_t launch_pyr_down(const float* src, float* dst, int nframes, int w, int
 hipError_t launch_pyr_planes(const float* src, float* img, float* dx, float* dy, int nframes, int w, int h, int noc,
                              int pad, hipStream_t s, float* down = nullptr);
 bool pyr_planes_fuses_down(int w, int h, int noc, int pad);
+// which kernels the three launchers above run, stated once (host only; the launchers call these and nothing else decides):
+// the base level's generic kernel or the 16-byte streaming kernel for blocks of 4, 8 or 16 pixels (the value is the block size)
+enum PyrBaseVariant { PYR_BASE_GENERIC = 0, PYR_BASE_STREAM4 = 4, PYR_BASE_STREAM8 = 8, PYR_BASE_STREAM16 = 16 };
+PyrBaseVariant pyr_base_variant(const uint8_t* src, int wo, int W, int noc, int l, size_t pitch, size_t stride);
+// the planes' generic kernel (a separate pyr_down launch where `down` is wanted), the gray quad kernel, or the quad kernel
+// writing `down` as well
+enum PyrPlanesVariant { PYR_PLANES_GENERIC = 0, PYR_PLANES_GRAY4 = 1, PYR_PLANES_GRAY4_DOWN = 2 };
+PyrPlanesVariant pyr_planes_variant(int w, int h, int noc, int pad, bool want_down);
 
 // result to full resolution (ofdis_upsample.hip).  x 2^sc_l, bilinear upsample (cv::resize INTER_LINEAR) and crop of the AoS
 // result (run_dense.cpp:406-414): the OFDIS_ENC_F32 kernel of launch_upsample_crop_enc

@@ -237,27 +237,43 @@ __global__ __launch_bounds__(256) void pyr_planes_gray4_kernel(const float* __re
   }
 }
 
+// ------------------------------------------------------------------------------------ which kernel runs (host only)
+// the base level: the 16-byte streaming kernel for gray frames whose width / left padding / row pitch / frame stride / base
+// address are multiples of 16 bytes (packed frames: pitch = wo, stride = wo * ho) at blocks of 4, 8 or 16 pixels
+PyrBaseVariant pyr_base_variant(const uint8_t* src, int wo, int W, int noc, int l, size_t pitch, size_t stride) {
+  const int left = (W - wo) / 2;
+  if (noc == 1 && (l == 2 || l == 3 || l == 4) && (wo & 15) == 0 && (left & 15) == 0 && (W & 15) == 0 &&
+      (pitch & 15) == 0 && (stride & 15) == 0 && ((uintptr_t)src & 15) == 0)
+    return l == 2 ? PYR_BASE_STREAM4 : l == 3 ? PYR_BASE_STREAM8 : PYR_BASE_STREAM16;
+  return PYR_BASE_GENERIC;
+}
+// what pyr_planes_gray4_kernel needs: gray, every quad of a padded row inside or outside the image, two rows for its window
+static bool pyr_planes_quads(int w, int h, int noc, int pad) {
+  return noc == 1 && (w & 3) == 0 && (pad & 3) == 0 && w >= 8 && h >= 2;
+}
+// the quad kernel also produces the next level's image (even sizes, gray, quads inside or outside the image)
+bool pyr_planes_fuses_down(int w, int h, int noc, int pad) { return pyr_planes_quads(w, h, noc, pad) && (h & 1) == 0; }
+// the planes: the quad kernel where the geometry allows -- with `down` wanted only where it can write that too -- else the
+// generic kernel, `down` by a launch of its own
+PyrPlanesVariant pyr_planes_variant(int w, int h, int noc, int pad, bool want_down) {
+  if (want_down) return pyr_planes_fuses_down(w, h, noc, pad) ? PYR_PLANES_GRAY4_DOWN : PYR_PLANES_GENERIC;
+  return pyr_planes_quads(w, h, noc, pad) ? PYR_PLANES_GRAY4 : PYR_PLANES_GENERIC;
+}
+
 hipError_t launch_pyr_base(const uint8_t* src, float* dst, int nframes, int wo, int ho, int W, int H, int noc, int l,
                            size_t pitch, size_t stride, hipStream_t s) {
   const long long total = (long long)nframes * (H >> l) * (W >> l) * noc;
-  const int left = (W - wo) / 2;
-  // 16-byte streaming variant: gray, width / left padding / row pitch / frame stride / base address multiples of 16 bytes
-  // (packed frames: pitch = wo, stride = wo * ho)
-  if (noc == 1 && (l == 2 || l == 3 || l == 4) && (wo & 15) == 0 && (left & 15) == 0 && (W & 15) == 0 &&
-      (pitch & 15) == 0 && (stride & 15) == 0 && ((uintptr_t)src & 15) == 0) {
+  const PyrBaseVariant v = pyr_base_variant(src, wo, W, noc, l, pitch, stride);
+  if (v != PYR_BASE_GENERIC) {
     const long long lanes = (long long)nframes * (H >> l) * (W / 16);
-    if (l == 2) hipLaunchKernelGGL(pyr_base16_kernel<4>, dim3(grid_for(lanes)), dim3(256), 0, s, src, dst, nframes, wo, ho, W, H, l, pitch, stride);
-    else if (l == 3) hipLaunchKernelGGL(pyr_base16_kernel<8>, dim3(grid_for(lanes)), dim3(256), 0, s, src, dst, nframes, wo, ho, W, H, l, pitch, stride);
+    if (v == PYR_BASE_STREAM4) hipLaunchKernelGGL(pyr_base16_kernel<4>, dim3(grid_for(lanes)), dim3(256), 0, s, src, dst, nframes, wo, ho, W, H, l, pitch, stride);
+    else if (v == PYR_BASE_STREAM8) hipLaunchKernelGGL(pyr_base16_kernel<8>, dim3(grid_for(lanes)), dim3(256), 0, s, src, dst, nframes, wo, ho, W, H, l, pitch, stride);
     else hipLaunchKernelGGL(pyr_base16_kernel<16>, dim3(grid_for(lanes)), dim3(256), 0, s, src, dst, nframes, wo, ho, W, H, l, pitch, stride);
     return hipGetLastError();
   }
   hipLaunchKernelGGL(pyr_base_kernel, dim3(grid_for(total)), dim3(256), 0, s, src, dst, nframes, wo, ho, W, H, noc, l, pitch,
                      stride);
   return hipGetLastError();
-}
-// the quad kernel also produces the next level's image (even sizes, gray, quads inside or outside the image)
-bool pyr_planes_fuses_down(int w, int h, int noc, int pad) {
-  return noc == 1 && (w & 3) == 0 && (pad & 3) == 0 && (h & 1) == 0 && w >= 8 && h >= 2;
 }
 hipError_t launch_pyr_down(const float* src, float* dst, int nframes, int w, int h, int noc, hipStream_t s) {
   const long long total = (long long)nframes * (h / 2) * (w / 2) * noc;
@@ -268,7 +284,7 @@ hipError_t launch_pyr_planes(const float* src, float* img, float* dx, float* dy,
                              int pad, hipStream_t s, float* down) {
   const long long per_frame = (long long)(h + 2 * pad) * (w + 2 * pad) * noc;
   if (nframes > 65535 || per_frame >= (1ll << 31)) return hipErrorInvalidValue;
-  if (pyr_planes_fuses_down(w, h, noc, pad) || (!down && noc == 1 && (w & 3) == 0 && (pad & 3) == 0 && w >= 8 && h >= 2)) {
+  if (pyr_planes_variant(w, h, noc, pad, down != nullptr) != PYR_PLANES_GENERIC) {
     // gray, quads: one launch for the three planes and (down != nullptr) the next level's image
     hipLaunchKernelGGL(pyr_planes_gray4_kernel, dim3((unsigned)((per_frame / 4 + 255) / 256), (unsigned)nframes), dim3(256), 0, s,
                        src, img, dx, dy, down, nframes, w, h, pad);

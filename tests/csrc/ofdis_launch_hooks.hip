@@ -89,6 +89,15 @@ HOOK void ofdis_test_km_geom(int C, int* np, int* el, int* rl) {
   *rl = g.rl;
 }
 HOOK int ofdis_test_km_finish_split(int n_c) { return 1 << km_finish_log2te(n_c); }
+// host only, needs no GPU: the kernels the pyramid's launchers pick (ofdis_pyr.hip).  Base level: 0 generic, 4 / 8 / 16 the
+// streaming kernel of that block size (`src` is only looked at as an address); planes: 0 generic, 1 gray quads, 2 gray quads
+// that write `down` as well
+HOOK int ofdis_test_pyr_base_variant(const uint8_t* src, int wo, int W, int noc, int l, size_t pitch, size_t stride) {
+  return (int)pyr_base_variant(src, wo, W, noc, l, pitch, stride);
+}
+HOOK int ofdis_test_pyr_planes_variant(int w, int h, int noc, int pad, int want_down) {
+  return (int)pyr_planes_variant(w, h, noc, pad, want_down != 0);
+}
 
 // ------------------------------------------------------------------------------------ launchers that walk quad_grid's chunks
 HOOK int ofdis_test_launch_interp_frames(const uint8_t* img_a, const uint8_t* img_b, const float* flow_fw, const float* flow_rev,
@@ -158,6 +167,11 @@ HOOK int ofdis_test_launch_pyr_base(const uint8_t* src, float* dst, int nframes,
 }
 HOOK int ofdis_test_launch_pyr_down(const float* src, float* dst, int nframes, int w, int h, int noc, void* stream) {
   return (int)launch_pyr_down(src, dst, nframes, w, h, noc, (hipStream_t)stream);
+}
+// (grid = (chunks of a frame, frames), no grid_for: here for the comparison with tests/pyr_ref.py, tests/test_gpu_pyramid.py)
+HOOK int ofdis_test_launch_pyr_planes(const float* src, float* img, float* dx, float* dy, float* down, int nframes, int w, int h,
+                                      int noc, int pad, void* stream) {
+  return (int)launch_pyr_planes(src, img, dx, dy, nframes, w, h, noc, pad, (hipStream_t)stream, down);
 }
 HOOK int ofdis_test_launch_encode(const float* src, void* dst, size_t n, int type, float scale, float offset, void* stream) {
   return (int)launch_encode(src, dst, n, type, scale, offset, (hipStream_t)stream);

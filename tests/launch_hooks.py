@@ -1,7 +1,9 @@
 """The launch hooks of the TEST library (tests/csrc/ofdis_launch_hooks.hip): the product's own launchers behind thin C wrappers, and
 the two launch limits of of_dis_amd/csrc/ofdis_kernels.h -- QUAD_MAX_BLOCKS (workgroups of one launch of a quad kernel: the
 launcher walks the frames in chunks) and GRID_MAX_BLOCKS (grid of a grid-stride kernel: the kernel loops) -- as variables of
-that library which a test lowers.  Shared by tests/test_launch_geometry.py (CPU) and tests/test_gpu_launch_limits.py.
+that library which a test lowers.  Shared by tests/test_launch_geometry.py (CPU) and tests/test_gpu_launch_limits.py; the
+pyramid's launchers and their kernel selection (pyr_base_variant, pyr_planes_variant) also by tests/pyr_classes.py,
+tests/test_pyr_ref.py (CPU) and tests/test_gpu_pyramid.py.
 
 libofdis_hip.so is a separate object with the limits compiled in as constants: nothing here changes what it does."""
 import contextlib
@@ -28,6 +30,7 @@ _SIGNATURES = {
     "warp_frames": [_VP] * 4 + [_I] * 5 + [_VP],
     "pyr_base": [_VP, _VP] + [_I] * 7 + [_SZ, _SZ, _VP],
     "pyr_down": [_VP, _VP] + [_I] * 4 + [_VP],
+    "pyr_planes": [_VP] * 5 + [_I] * 5 + [_VP],
     "encode": [_VP, _VP, _SZ, _I, _F, _F, _VP],
     "fb_check": [_VP] * 3 + [_I] * 3 + [_F, _F, _VP],
     "mirror_u8": [_VP, _VP] + [_I] * 4 + [_VP],
@@ -54,6 +57,8 @@ def hooks():
     L.ofdis_test_bof_shape.argtypes, L.ofdis_test_bof_shape.restype = [_I] + [C.POINTER(_I)] * 3, None
     L.ofdis_test_km_geom.argtypes, L.ofdis_test_km_geom.restype = [_I] + [C.POINTER(_I)] * 3, None
     L.ofdis_test_km_finish_split.argtypes, L.ofdis_test_km_finish_split.restype = [_I], _I
+    L.ofdis_test_pyr_base_variant.argtypes, L.ofdis_test_pyr_base_variant.restype = [_VP] + [_I] * 4 + [_SZ, _SZ], _I
+    L.ofdis_test_pyr_planes_variant.argtypes, L.ofdis_test_pyr_planes_variant.restype = [_I] * 5, _I
     return L
 
 
@@ -125,6 +130,18 @@ def km_geom(cells):
 def km_finish_split(n_c):
     """the entries km_finish_kernel's 256 threads take at a time on a channel of n_c entries: 16, 128 or 256"""
     return int(hooks().ofdis_test_km_finish_split(n_c))
+
+
+def pyr_base_variant(address, wo, W, noc, l, pitch, stride):
+    """pyr_base_variant (ofdis_pyr.hip) for frames at `address` (only its alignment matters): 0 = pyr_base_kernel, 4 / 8 / 16 =
+    pyr_base16_kernel of that block size"""
+    return int(hooks().ofdis_test_pyr_base_variant(address, wo, W, noc, l, pitch, stride))
+
+
+def pyr_planes_variant(w, h, noc, pad, want_down):
+    """pyr_planes_variant (ofdis_pyr.hip): 0 = pyr_planes_kernel (and a pyr_down launch where `down` is wanted), 1 =
+    pyr_planes_gray4_kernel, 2 = pyr_planes_gray4_kernel writing `down` too"""
+    return int(hooks().ofdis_test_pyr_planes_variant(w, h, noc, pad, int(bool(want_down))))
 
 
 def trips(total):
