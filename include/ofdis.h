@@ -540,8 +540,10 @@ int ofdis_batch_dense_tracks(ofdis_batch* b, const uint8_t* frames, int first_fr
  * -> ofdis_batch_upsample_bidir and, for the residual flow HOF and MBH are made of, ofdis_batch_motion_compensate ->
  * ofdis_track_descriptors on the selected set -> ofdis_track_bof.  The tracks follow the full flow; the camera models change
  * what is selected and what the descriptors see.  No context form is needed: no argument here belongs to a context.
- * Not provided: homography models and RANSAC (the models are those of ofdis_global_motion); a bag-of-features channel for the
- * shape.  of_dis_amd/tracking.py states the same definition in numpy (track_select_ref).
+ * ofdis_track_select_projective takes the 8-parameter models of ofdis_projective_motion instead (section "Projective camera
+ * models", which states the residual step under them).
+ * Not provided: RANSAC (the models are those of ofdis_global_motion or ofdis_projective_motion); a bag-of-features channel for
+ * the shape.  of_dis_amd/tracking.py states the same definition in numpy (track_select_ref).
  * ------------------------------------------------------------------------------------------- */
 enum { OFDIS_TS_KEPT = 0, OFDIS_TS_SHORT = 1, OFDIS_TS_INVALID = 2, OFDIS_TS_STATIC = 3, OFDIS_TS_ERRATIC = 4, OFDIS_TS_JUMP = 5,
        OFDIS_TS_CAMERA = 6 };
@@ -924,7 +926,9 @@ int ofdis_batch_trajectory_filter(ofdis_batch* b, const uint8_t* frames, int fir
  * inlier (background, moves with the camera), outlier (moves on its own) or invalid.  The uses: subtracting the camera motion
  * before a two-stream quantisation, the input of a stabiliser, foreground / background segmentation, scene-change statistics.
  * Warping frames along a smoothed camera path -- stabilisation itself -- is the next section, "Video stabilisation".
- * Not provided: homography and similarity models, models of the reverse direction, the C++ sequence driver.
+ * The 8-parameter projective model, the first-order flow of a homography, is the section after this one ("Projective camera
+ * models").
+ * Not provided: similarity models, models of the reverse direction, the C++ sequence driver.
  *
  * The frame is W x H with both sides <= OFDIS_GM_MAX_SIDE.  F is the flow [H][W][2] fp32 of one pair, M its mask of OFDIS_FB_*
  * codes or NULL.  Centred, doubled coordinates are integers: X = 2x - (W-1), Y = 2y - (H-1).
@@ -1006,6 +1010,89 @@ int ofdis_batch_global_motion(ofdis_batch* b, int first_frame, int count, int mo
 int ofdis_batch_motion_compensate(ofdis_batch* b, int first_frame, int count, const double* models, float thresh, int fb_check,
                                   float alpha, float beta, float* residual, uint8_t* label, int width_org, int height_org,
                                   void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Projective camera models: the 8-parameter twins of the section above -- fit, compensate, and track selection under them.
+ * An affine map cannot represent a pan or a tilt with perspective; the model here can, to first order.  It is the 8-parameter
+ * QUADRATIC flow model, the instantaneous flow of a planar scene or of a rotating camera, with xc = x - (W-1)/2, yc = y - (H-1)/2:
+ *   p = a6*xc + a7*yc
+ *   u = a0 + a1*xc + a2*yc + p*xc
+ *   v = a3 + a4*xc + a5*yc + p*yc
+ * It is linear in a0 .. a7; a6 = a7 = 0 is the affine model of ofdis_global_motion in the same parametrisation; to first order it
+ * is the flow of the homography [[1+a1, a2, a0], [a4, 1+a5, a3], [-a6, -a7, 1]] in centred coordinates.  It is THIS model and not
+ * a DLT homography fit: being linear in its parameters it is fitted from exact integer sums like the affine one, whereas the
+ * DLT needs moments of order x^2 * x'^2, which overflow 64 bits for a single pixel.
+ * Not provided (out of scope): ofdis_camera_path, ofdis_warp_frames and ofdis_batch_stabilize stay affine (the quadratic model
+ * is not closed under composition); similarity models; RANSAC; the C++ sequence driver.
+ *
+ * Everything that is not the model is word for word the section above: valid, qu = (int)rintf(u * 256.0f), X = 2x - (W-1),
+ * Y = 2y - (H-1), near, the rounds (S_0 = valid, S_r = near under the model of round r-1, an empty later set leaves the previous
+ * result), the labels, the store widths, the residual that may alias the flow.  Models are [npairs][8] fp64, a0 .. a7.
+ * Sums over a pixel set S, 23 exact integers: the twelve of the section above, then
+ *   XXX, XXY, XYY, YYY            (XXY = sum of X*X*Y, and so on)
+ *   XXXX, XXXY, XXYY, XYYY, YYYY
+ *   R6 = sum of (X*X*qu + X*Y*qv),  R7 = sum of (X*Y*qu + Y*Y*qv)
+ * Bounds: |X|, |Y| < 2^13 and |q| <= 2^20, so per pixel a fourth moment is below 2^52 and |R6|, |R7| below 2^47; a workgroup
+ * covers at most 1024 pixels, so every sum of its record fits int64 (a fourth moment at most 2^62).  A PAIR's sums do not: the
+ * sum of X^4 over 8192 x 2 pixels already needs more than 63 bits, a full 8192 x 8192 frame reaches 2^78.  The records of a pair
+ * are therefore added in 128 bits for these eleven sums, and each of them is converted to fp64 CORRECTLY ROUNDED (to nearest,
+ * ties to even -- Python's float(int)).  The twelve old sums stay below 2^59 and convert as before.
+ * Solve, in fp64, every operation separately rounded (no contraction).  In integer units b (u_q = b0 + b1 X + b2 Y + b6 X^2 + b7 XY,
+ * v_q = b3 + b4 X + b5 Y + b6 XY + b7 Y^2) the symmetric normal matrix N and the right-hand side t are, all sums as doubles:
+ *   rows and columns 0..2 and again 3..5: [[n, Sx, Sy], [Sx, Sxx, Sxy], [Sy, Sxy, Syy]]; zero between the two blocks
+ *   column 6 (rows 0..5): Sxx, XXX, XXY, Sxy, XXY, XYY        column 7 (rows 0..5): Sxy, XXY, XYY, Syy, XYY, YYY
+ *   N66 = XXXX + XXYY    N67 = XXXY + XYYY    N77 = XXYY + YYYY           (one fp64 addition each)
+ *   t = (Su, Sxu, Syu, Sv, Sxv, Syv, R6, R7)
+ * factored as L D L^T without a square root, column by column, every inner sum over ascending j:
+ *   for k = 0 .. 7:   for i = k .. 7:  C_ik = N_ik;  for j = 0 .. k-1:  C_ik = C_ik - C_ij * L_kj
+ *                     d_k = C_kk;  the pivot PASSES when d_k > N_kk * 2^-40;  for i = k+1 .. 7:  L_ik = C_ik / d_k
+ *   for i = 0 .. 7:   z_i = t_i;  for j = 0 .. i-1:  z_i = z_i - L_ij * z_j
+ *   for i = 7 .. 0:   b_i = z_i / d_i;  for j = i+1 .. 7:  b_i = b_i - L_ji * b_j
+ *   a0 = b0/256, a1 = b1/128, a2 = b2/128, a3 = b3/256, a4 = b4/128, a5 = b5/128, a6 = b6/64, a7 = b7/64
+ * Rank test: the projective branch is taken when n >= 4 and all eight pivots pass.  On exactly degenerate sets (one row, one
+ * diagonal, H = 1, W = 1) a pivot is 0 or below 2.2e-16 of its diagonal entry; a 2 x 2 block in the corner of a 300 x 70 frame
+ * has 1.2e-10, four random pixels 4e-3, a full frame 0.4: 2^-40 (9.1e-13) separates them.  Otherwise the solve of the section
+ * above runs unchanged on the twelve sums with model = OFDIS_GM_AFFINE: a0 .. a5 are the bits ofdis_global_motion gives on the
+ * same set, a6 = a7 = 0.
+ * stats[k] = { |S_0|, the size of the last set used, the number of parameters of the model that was solved: 8, 6 (affine), 2
+ * (translation) or 0 (empty) }.
+ * Residual, in fp32, every operation separately rounded; xc, yc as in the section above ((float)X * 0.5f):
+ *   p = af6*xc + af7*yc
+ *   mu = ((af0 + af1*xc) + af2*yc) + p*xc;  mv = ((af3 + af4*xc) + af5*yc) + p*yc;  ru = u - mu;  rv = v - mv
+ * Consequence: with a6 = a7 = 0 every output equals that of the 6-parameter function under == (only the sign of a zero may
+ * differ).  of_dis_amd/gmotion.py states the same arithmetic in numpy (projective_motion_ref, projective_compensate_ref).
+ * ------------------------------------------------------------------------------------------- */
+/* bytes of the work buffer ofdis_projective_motion needs (one record of 24 x 8 bytes per workgroup and pair: the 23 sums and a
+ * word of padding); 0 for sizes that function rejects */
+size_t ofdis_projective_motion_work_bytes(int npairs, int width, int height);
+/* ofdis_global_motion without `model`: models [npairs][8] f64, stats [npairs][3] int64 or NULL as stated above; the same
+ * launches (per round one that sums all pairs -- one record per workgroup, plain stores, no atomics -- and one that solves, one
+ * wavefront per pair, which adds the pair's records in 128 bits), no host synchronisation, the same OFDIS_ERR_INVALID cases
+ * before any device work. */
+int ofdis_projective_motion(const float* flow, const uint8_t* mask, int npairs, int width, int height, int rounds, float thresh,
+                            double* models, long long* stats /* or NULL */, void* work, size_t work_bytes, void* stream);
+/* ofdis_motion_compensate under models [npairs][8]: the same outputs, store widths, aliasing rule and rejections. */
+int ofdis_projective_compensate(const float* flow, const uint8_t* mask, const double* models, int npairs, int width, int height,
+                                float thresh, float* residual, uint8_t* label, void* stream);
+/* ofdis_batch_global_motion / ofdis_batch_motion_compensate under the 8-parameter model: straight from the level flows, fb_check
+ * as there, bit-identical to the two standalone calls above on what ofdis_batch_upsample_frames / ofdis_batch_upsample_bidir
+ * write, under both contracts.  The work buffer is a slab of its own that belongs to the context: allocated at the first call,
+ * counted by ofdis_batch_device_bytes from then on.  Joins a pipelined pass by itself.  OFDIS_ERR_INVALID as the 6-parameter calls. */
+int ofdis_batch_projective_motion(ofdis_batch* b, int first_frame, int count, int rounds, float thresh, int fb_check, float alpha,
+                                  float beta, double* models, long long* stats, int width_org, int height_org, void* stream);
+int ofdis_batch_projective_compensate(ofdis_batch* b, int first_frame, int count, const double* models, float thresh,
+                                      int fb_check, float alpha, float beta, float* residual, uint8_t* label, int width_org,
+                                      int height_org, void* stream);
+/* ofdis_track_select with models [npairs][8] of ofdis_projective_motion: the residual step of a slot becomes
+ *   pq = af6*xc + af7*yc;  mu = ((af0 + af1*xc) + af2*yc) + pq*xc;  mv = ((af3 + af4*xc) + af5*yc) + pq*yc
+ * with xc = x_j - (float)(W-1)*0.5f, yc = y_j - (float)(H-1)*0.5f as there; everything else, the rejections included, is that
+ * function's.  A track that follows an 8-parameter model exactly is OFDIS_TS_CAMERA with it and kept without. */
+int ofdis_track_select_projective(const float* tracks, const int* start, const int* len, const long long* info, int lmax,
+                                  int max_tracks, const double* models /* or NULL */, int npairs, int width, int height,
+                                  const ofdis_track_select_params* p, uint8_t* code /* or NULL */,
+                                  long long* counts /* or NULL */, int max_tracks_out, float* tracks_out, int* start_out,
+                                  int* len_out, long long* info_out, int* index /* or NULL */, float* shape_out /* or NULL */,
+                                  void* work, size_t work_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Video stabilisation: the per-pair camera models of a clip turned into one correcting warp per frame -- the classical

@@ -580,21 +580,25 @@ def track_select_work_bytes(max_tracks):
 
 def track_select_dev(tracks_ptr, start_ptr, len_ptr, info_ptr, lmax, max_tracks, max_tracks_out, tracks_out_ptr, start_out_ptr,
                      len_out_ptr, info_out_ptr, work_ptr, work_bytes, models_ptr=None, npairs=0, width=0, height=0, params=None,
-                     code_ptr=None, counts_ptr=None, index_ptr=None, shape_out_ptr=None, stream=None):
+                     code_ptr=None, counts_ptr=None, index_ptr=None, shape_out_ptr=None, stream=None, nparam=6):
     """ofdis_track_select on device pointers: the arrays ofdis_dense_tracks wrote stay where they are; the selected set
     (tracks_out [lmax + 1][max_tracks_out][2], start_out, len_out [max_tracks_out], info_out [2]) has the same layout and feeds
     track_descriptors_dev, track_bof_dev and codebook_train_dev unchanged.  models [npairs][6] float64 of a width x height
     clip, code [max_tracks] uint8, counts [7] int64, index [max_tracks_out] int32 and shape_out [max_tracks_out][lmax][2] are
-    optional.  Enqueues on `stream` and returns; nothing synchronises with the host."""
+    optional.  nparam=8: models [npairs][8] of projective_motion (ofdis_track_select_projective).  Enqueues on `stream` and
+    returns; nothing synchronises with the host."""
     p = TrackSelectParams.of(params)
-    check(lib().ofdis_track_select(tracks_ptr, start_ptr, len_ptr, info_ptr, lmax, max_tracks, models_ptr, npairs, width, height,
-                                   C.byref(p), code_ptr, counts_ptr, max_tracks_out, tracks_out_ptr, start_out_ptr, len_out_ptr,
-                                   info_out_ptr, index_ptr, shape_out_ptr, work_ptr, work_bytes, stream))
+    assert nparam in (6, 8), nparam
+    call = lib().ofdis_track_select if nparam == 6 else lib().ofdis_track_select_projective
+    check(call(tracks_ptr, start_ptr, len_ptr, info_ptr, lmax, max_tracks, models_ptr, npairs, width, height,
+               C.byref(p), code_ptr, counts_ptr, max_tracks_out, tracks_out_ptr, start_out_ptr, len_out_ptr,
+               info_out_ptr, index_ptr, shape_out_ptr, work_ptr, work_bytes, stream))
 
 
 def track_select(tracks, start, length, models=None, size=None, params=None, max_out=None, shape=True):
     """ofdis_track_select on host arrays: tracks [Lmax + 1, ntracks, 2], start, length [ntracks] as dense_tracks returns them;
-    models float64 [npairs, 6] as global_motion returns them with size = (width, height) of their frames, or None; params a
+    models float64 [npairs, 6] as global_motion returns them -- or [npairs, 8] as projective_motion does, which routes to
+    ofdis_track_select_projective -- with size = (width, height) of their frames, or None; params a
     TrackSelectParams (None: the defaults); max_out the slots of the output set (None: room for every track) -> (code uint8
     [ntracks], counts int64 [7], tracks_out [Lmax + 1, nkept, 2], start_out, len_out int32 [nkept], info_out int64 [2] =
     (nkept written, dropped), index int32 [nkept], shape_out float32 [nkept, Lmax, 2] or None with shape=False): the outputs
@@ -606,9 +610,11 @@ def track_select(tracks, start, length, models=None, size=None, params=None, max
     assert start.shape == length.shape == (n,), (start.shape, length.shape, n)
     slots = max(n, 1)  # (the library takes no empty array)
     out = slots if max_out is None else int(max_out)
-    dm, npairs, w, h = None, 0, 0, 0
+    dm, npairs, w, h, nparam = None, 0, 0, 0, 6
     if models is not None:
-        models = np.ascontiguousarray(models, np.float64).reshape(-1, 6)
+        models = np.ascontiguousarray(models, np.float64)
+        nparam = 8 if models.ndim == 2 and models.shape[1] == 8 else 6
+        models = models.reshape(-1, nparam)
         dm, npairs, (w, h) = Dev(models), len(models), size
     dt = Dev(tracks if n else np.zeros((lmax + 1, 1, 2), _f32))
     ds, dl = (Dev(a if n else np.zeros(1, np.int32)) for a in (start, length))
@@ -620,7 +626,7 @@ def track_select(tracks, start, length, models=None, size=None, params=None, max
     dwork = Dev(nbytes=max(8, wb))
     track_select_dev(dt.ptr, ds.ptr, dl.ptr, di.ptr, lmax, slots, out, outs[0].ptr, outs[1].ptr, outs[2].ptr, outs[3].ptr,
                      dwork.ptr, wb, dm.ptr if dm else None, npairs, w, h, params, dcode.ptr, dcounts.ptr, dindex.ptr,
-                     dshape.ptr if dshape else None)
+                     dshape.ptr if dshape else None, nparam=nparam)
     check(lib().ofdis_sync(None))
     tracks_out, start_out, len_out, info = _dense_results(outs, lmax, out)
     k = int(info[0])
@@ -891,6 +897,35 @@ def motion_compensate(flow, models, mask=None, thresh=1.0, residual=True, label=
     dl = Dev(nbytes=max(1, npairs * h * w)) if label else None
     check(lib().ofdis_motion_compensate(df.ptr, dm.ptr if dm else None, dmodels.ptr, npairs, w, h, thresh, dr.ptr if dr else None,
                                         dl.ptr if dl else None, None))
+    check(lib().ofdis_sync(None))
+    return dr.get(flow.shape, _f32) if dr else None, dl.get((npairs, h, w), np.uint8) if dl else None
+
+
+def projective_motion(flow, mask=None, rounds=3, thresh=1.0, stats=True):
+    """ofdis_projective_motion on the device: flow and mask as global_motion takes them -> (models [npairs, 8] float64, stats
+    [npairs, 3] int64: |S_0|, the size of the last set used, the parameters solved: 8, 6, 2 or 0; None with stats=False, which
+    passes NULL).  of_dis_amd/gmotion.py: projective_motion_ref is the numpy statement of the same arithmetic."""
+    flow, dm, npairs, h, w = _gm_inputs(flow, mask)
+    df = Dev(flow)
+    dmodels, dstats = Dev(nbytes=max(8, npairs * 64)), Dev(nbytes=max(8, npairs * 24)) if stats else None
+    wb = lib().ofdis_projective_motion_work_bytes(npairs, w, h)
+    dwork = Dev(nbytes=max(8, wb))
+    check(lib().ofdis_projective_motion(df.ptr, dm.ptr if dm else None, npairs, w, h, rounds, thresh, dmodels.ptr,
+                                        dstats.ptr if dstats else None, dwork.ptr, wb, None))
+    check(lib().ofdis_sync(None))
+    return dmodels.get((npairs, 8), np.float64), dstats.get((npairs, 3), np.int64) if dstats else None
+
+
+def projective_compensate(flow, models, mask=None, thresh=1.0, residual=True, label=True, in_place=False):
+    """ofdis_projective_compensate on the device: motion_compensate with models [npairs, 8] float64."""
+    flow, dm, npairs, h, w = _gm_inputs(flow, mask)
+    models = np.ascontiguousarray(models, np.float64)
+    assert models.shape == (npairs, 8), models.shape
+    df, dmodels = Dev(flow), Dev(models)
+    dr = (df if in_place else Dev(nbytes=max(8, flow.nbytes))) if residual else None
+    dl = Dev(nbytes=max(1, npairs * h * w)) if label else None
+    check(lib().ofdis_projective_compensate(df.ptr, dm.ptr if dm else None, dmodels.ptr, npairs, w, h, thresh,
+                                            dr.ptr if dr else None, dl.ptr if dl else None, None))
     check(lib().ofdis_sync(None))
     return dr.get(flow.shape, _f32) if dr else None, dl.get((npairs, h, w), np.uint8) if dl else None
 
@@ -1281,6 +1316,52 @@ class Batch:
             rptr, lptr = out_ptr
         check(lib().ofdis_batch_motion_compensate(self.h, first, count, models, thresh, int(fb_check), alpha, beta, rptr, lptr,
                                                   width_org, height_org, stream))
+        if out_ptr is not None:
+            if keep is not None:
+                check(lib().ofdis_sync(stream))  # the uploaded models must outlive the launch
+            return None
+        check(lib().ofdis_sync(stream))
+        return dr.get(rshape, _f32) if dr else None, dl.get(lshape, np.uint8) if dl else None
+
+    def projective_motion(self, width_org, height_org, rounds=3, thresh=1.0, fb_check=False, first=0, count=None, alpha=FB_ALPHA,
+                          beta=FB_BETA, models_ptr=None, stats_ptr=None, stream=None):
+        """ofdis_batch_projective_motion: global_motion with the 8-parameter model.  models_ptr None: returns the host arrays
+        (models [count, 8] float64, stats [count, 3] int64); else writes the device arrays on `stream` and returns None."""
+        count = self.nframes - first if count is None else count
+        n = max(count, 1)
+        dm = ds = None
+        if models_ptr is None:
+            dm, ds = Dev(nbytes=n * 64), Dev(nbytes=n * 24)
+            models_ptr, stats_ptr = dm.ptr, ds.ptr
+        check(lib().ofdis_batch_projective_motion(self.h, first, count, rounds, thresh, int(fb_check), alpha, beta, models_ptr,
+                                                  stats_ptr, width_org, height_org, stream))
+        if dm is None:
+            return None
+        check(lib().ofdis_sync(stream))
+        return dm.get((count, 8), np.float64), ds.get((count, 3), np.int64)
+
+    def projective_compensate(self, models, width_org, height_org, thresh=1.0, fb_check=False, first=0, count=None,
+                              alpha=FB_ALPHA, beta=FB_BETA, residual=True, label=True, out_ptr=None, stream=None):
+        """ofdis_batch_projective_compensate: motion_compensate with models [count, 8] float64 (host array or device pointer);
+        the outputs as there."""
+        count = self.nframes - first if count is None else count
+        n = max(count, 1)
+        keep = None
+        if not isinstance(models, (int, type(None))):
+            models = np.ascontiguousarray(models, np.float64)
+            assert models.shape == (n, 8), models.shape
+            keep = Dev(models)
+            models = keep.ptr
+        rshape, lshape = (n, height_org, width_org, 2), (n, height_org, width_org)
+        dr = dl = None
+        if out_ptr is None:
+            dr = Dev(nbytes=max(8, int(np.prod(rshape, dtype=np.int64)) * 4)) if residual else None
+            dl = Dev(nbytes=max(1, int(np.prod(lshape, dtype=np.int64)))) if label else None
+            rptr, lptr = dr.ptr if dr else None, dl.ptr if dl else None
+        else:
+            rptr, lptr = out_ptr
+        check(lib().ofdis_batch_projective_compensate(self.h, first, count, models, thresh, int(fb_check), alpha, beta, rptr,
+                                                      lptr, width_org, height_org, stream))
         if out_ptr is not None:
             if keep is not None:
                 check(lib().ofdis_sync(stream))  # the uploaded models must outlive the launch

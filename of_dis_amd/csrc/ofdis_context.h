@@ -171,6 +171,7 @@ struct ofdis_batch {
   float* mir_u8 = nullptr;           // ... and, OFDIS_BATCH_STEREO_LR, one mirrored 8-bit frame set (bytes, held as floats)
   float *lr_u = nullptr, *lr_dr = nullptr, *lr_mask = nullptr;  // staging of ofdis_batch_upsample_lr above its fused width, lazy
   float* gm_slab = nullptr;          // records of sums of ofdis_batch_global_motion (ofdis_gmotion.hip; int64, held as floats), lazy
+  float* pm_slab = nullptr;          // ... and the 24-sum records of ofdis_batch_projective_motion (int64, held as floats), lazy
   float* stab_path = nullptr;        // models [nframes][6] then warps [nframes + 1][6] of ofdis_batch_stabilize (fp64, held as floats), lazy
   float* dt_slab = nullptr;          // work buffer of ofdis_batch_dense_tracks (ofdis_dense_tracks.hip; held as floats), lazy: a
                                      // call that needs more than it holds requests a larger one (dstage)

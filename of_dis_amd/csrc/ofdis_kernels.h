@@ -290,12 +290,13 @@ hipError_t launch_dense_tracks_level(const uint8_t* frames, const float* fw, con
 // [max_tracks] u8 and counts [7] (either may be null) and the compacted set of max_tracks_out slots out -- tracks_out, start_out,
 // len_out, info_out [2], index [max_tracks_out] and shape_out [max_tracks_out][lmax][2] (either may be null); models [npairs][6]
 // of launch_gmotion_frames for a w x h frame, or null.  Three launches (classify, scan, scatter); work holds
-// track_select_work_bytes(max_tracks): one 64-byte record per workgroup, 8-byte aligned
+// track_select_work_bytes(max_tracks): one 64-byte record per workgroup, 8-byte aligned.  nparam: the doubles per model, 6, or
+// 8 for those of launch_projective_frames (ofdis_track_select_projective)
 size_t track_select_work_bytes(int max_tracks);
 hipError_t launch_track_select(const float* tracks, const int* start, const int* len, const long long* info, int lmax, int max_tracks,
                                const double* models, int npairs, int w, int h, const ofdis_track_select_params& p, uint8_t* code,
                                long long* counts, int max_tracks_out, float* tracks_out, int* start_out, int* len_out,
-                               long long* info_out, int* index, float* shape_out, void* work, hipStream_t s);
+                               long long* info_out, int* index, float* shape_out, void* work, hipStream_t s, int nparam = 6);
 // trajectory-aligned descriptors (include/ofdis.h: ofdis_track_descriptors; ofdis_descriptors.hip): the arrays of
 // launch_dense_tracks in, hist [max_tracks][33 nxy^2 nt] u32 and shape [max_tracks][lmax][2] (or null) out; one wavefront per
 // slot, the slots >= info[0] return at once
@@ -383,6 +384,17 @@ hipError_t launch_gmotion_level(const float* fw, const float* rev, int npairs, U
                                 float alpha, float beta, double* models, long long* stats, void* work, hipStream_t s);
 hipError_t launch_gmotion_compensate_level(const float* fw, const float* rev, const double* models, int npairs, UpGeom g,
                                            float thresh, float alpha, float beta, float* residual, uint8_t* label, hipStream_t s);
+// the 8-parameter projective twins (include/ofdis.h: ofdis_projective_motion): the same kernels with models [npairs][8], records
+// of 24 sums (projective_work_bytes) and, as the third value of stats, the number of parameters solved
+size_t projective_work_bytes(int npairs, int w, int h);
+hipError_t launch_projective_frames(const float* flow, const uint8_t* mask, int npairs, int w, int h, int rounds, float thresh,
+                                    double* models, long long* stats, void* work, hipStream_t s);
+hipError_t launch_projective_compensate_frames(const float* flow, const uint8_t* mask, const double* models, int npairs, int w,
+                                               int h, float thresh, float* residual, uint8_t* label, hipStream_t s);
+hipError_t launch_projective_level(const float* fw, const float* rev, int npairs, UpGeom g, int rounds, float thresh, float alpha,
+                                   float beta, double* models, long long* stats, void* work, hipStream_t s);
+hipError_t launch_projective_compensate_level(const float* fw, const float* rev, const double* models, int npairs, UpGeom g,
+                                              float thresh, float alpha, float beta, float* residual, uint8_t* label, hipStream_t s);
 // video stabilisation (include/ofdis.h: ofdis_camera_path, ofdis_warp_frames; ofdis_stabilize.hip).  The window travels in
 // the launch, as InterpTimes does: w[0 .. radius], the rest zero
 struct StabWindow {

@@ -357,10 +357,12 @@ size_t ofdis_track_select_work_bytes(int max_tracks) {
   return max_tracks >= 1 && max_tracks <= OFDIS_DT_MAX_TRACKS ? track_select_work_bytes(max_tracks) : 0;
 }
 
-int ofdis_track_select(const float* tracks, const int* start, const int* len, const long long* info, int lmax, int max_tracks,
-                       const double* models, int npairs, int width, int height, const ofdis_track_select_params* p, uint8_t* code,
-                       long long* counts, int max_tracks_out, float* tracks_out, int* start_out, int* len_out, long long* info_out,
-                       int* index, float* shape_out, void* work, size_t work_bytes, void* stream) {
+// ofdis_track_select and ofdis_track_select_projective: nparam doubles per model
+static int track_select_call(const float* tracks, const int* start, const int* len, const long long* info, int lmax, int max_tracks,
+                             const double* models, int npairs, int width, int height, const ofdis_track_select_params* p,
+                             uint8_t* code, long long* counts, int max_tracks_out, float* tracks_out, int* start_out, int* len_out,
+                             long long* info_out, int* index, float* shape_out, void* work, size_t work_bytes, void* stream,
+                             int nparam) {
   if (!tracks || !start || !len || !info) return fail(OFDIS_ERR_INVALID, "tracks, start, len or info is NULL");
   if (!p) return fail(OFDIS_ERR_INVALID, "params is NULL");
   if (!tracks_out || !start_out || !len_out || !info_out) return fail(OFDIS_ERR_INVALID, "tracks_out, start_out, len_out or info_out is NULL");
@@ -379,8 +381,26 @@ int ofdis_track_select(const float* tracks, const int* start, const int* len, co
   if (p->tests & ~OFDIS_TS_ALL_TESTS) return fail(OFDIS_ERR_INVALID, "tests has bits outside OFDIS_TS_ALL_TESTS");
   if (int rc = work_check(work, work_bytes, track_select_work_bytes(max_tracks), "ofdis_track_select_work_bytes")) return rc;
   HIPCHK(launch_track_select(tracks, start, len, info, lmax, max_tracks, models, npairs, width, height, *p, code, counts,
-                             max_tracks_out, tracks_out, start_out, len_out, info_out, index, shape_out, work, (hipStream_t)stream));
+                             max_tracks_out, tracks_out, start_out, len_out, info_out, index, shape_out, work, (hipStream_t)stream,
+                             nparam));
   return OFDIS_OK;
+}
+
+int ofdis_track_select(const float* tracks, const int* start, const int* len, const long long* info, int lmax, int max_tracks,
+                       const double* models, int npairs, int width, int height, const ofdis_track_select_params* p, uint8_t* code,
+                       long long* counts, int max_tracks_out, float* tracks_out, int* start_out, int* len_out, long long* info_out,
+                       int* index, float* shape_out, void* work, size_t work_bytes, void* stream) {
+  return track_select_call(tracks, start, len, info, lmax, max_tracks, models, npairs, width, height, p, code, counts,
+                           max_tracks_out, tracks_out, start_out, len_out, info_out, index, shape_out, work, work_bytes, stream, 6);
+}
+
+int ofdis_track_select_projective(const float* tracks, const int* start, const int* len, const long long* info, int lmax,
+                                  int max_tracks, const double* models, int npairs, int width, int height,
+                                  const ofdis_track_select_params* p, uint8_t* code, long long* counts, int max_tracks_out,
+                                  float* tracks_out, int* start_out, int* len_out, long long* info_out, int* index,
+                                  float* shape_out, void* work, size_t work_bytes, void* stream) {
+  return track_select_call(tracks, start, len, info, lmax, max_tracks, models, npairs, width, height, p, code, counts,
+                           max_tracks_out, tracks_out, start_out, len_out, info_out, index, shape_out, work, work_bytes, stream, 8);
 }
 
 // ------------------------------------------------------------------------------------ track descriptors (ofdis_descriptors.hip)
@@ -671,6 +691,62 @@ int ofdis_batch_motion_compensate(ofdis_batch* b, int first_frame, int count, co
   if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
   HIPCHK(launch_gmotion_compensate_level(fin.fw, fin.fb_rev, models, count, fin.g, thresh, alpha, beta, residual, label,
                                          (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+// the 8-parameter projective twins: the same checks, no `model` argument, models [npairs][8]
+static int pm_fit_check(int rounds, float thresh) { return gm_fit_check(OFDIS_GM_AFFINE, rounds, thresh); }
+
+size_t ofdis_projective_motion_work_bytes(int npairs, int width, int height) {
+  return gm_sizes_ok(npairs, width, height) ? projective_work_bytes(npairs, width, height) : 0;
+}
+
+int ofdis_projective_motion(const float* flow, const uint8_t* mask, int npairs, int width, int height, int rounds, float thresh,
+                            double* models, long long* stats, void* work, size_t work_bytes, void* stream) {
+  if (!flow || !models) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (int rc = pm_fit_check(rounds, thresh)) return rc;
+  if (!gm_sizes_ok(npairs, width, height)) return fail(OFDIS_ERR_INVALID, kGmSizes);
+  if (int rc = work_check(work, work_bytes, projective_work_bytes(npairs, width, height), "ofdis_projective_motion_work_bytes"))
+    return rc;
+  HIPCHK(launch_projective_frames(flow, mask, npairs, width, height, rounds, thresh, models, stats, work, (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+int ofdis_projective_compensate(const float* flow, const uint8_t* mask, const double* models, int npairs, int width, int height,
+                                float thresh, float* residual, uint8_t* label, void* stream) {
+  if (!flow || !models || (!residual && !label)) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (int rc = gm_thresh_check(thresh)) return rc;
+  if (!gm_sizes_ok(npairs, width, height)) return fail(OFDIS_ERR_INVALID, kGmSizes);
+  HIPCHK(launch_projective_compensate_frames(flow, mask, models, npairs, width, height, thresh, residual, label,
+                                             (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+int ofdis_batch_projective_motion(ofdis_batch* b, int first_frame, int count, int rounds, float thresh, int fb_check, float alpha,
+                                  float beta, double* models, long long* stats, int width_org, int height_org, void* stream) {
+  Finish fin;
+  if (int rc = gm_batch_check(b, fb_check, alpha, beta, width_org, height_org, fin)) return rc;
+  if (!models) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (int rc = pm_fit_check(rounds, thresh)) return rc;
+  if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
+  // records for every pair at the padded size (no original size needs more), held as floats
+  const size_t slab = projective_work_bytes(1, std::min(b->p.width, OFDIS_GM_MAX_SIDE), std::min(b->p.height, OFDIS_GM_MAX_SIDE));
+  if (int rc = dstage(b, {{&b->pm_slab, slab / sizeof(float)}})) return rc;
+  HIPCHK(launch_projective_level(fin.fw, fin.fb_rev, count, fin.g, rounds, thresh, alpha, beta, models, stats, b->pm_slab,
+                                 (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+int ofdis_batch_projective_compensate(ofdis_batch* b, int first_frame, int count, const double* models, float thresh, int fb_check,
+                                      float alpha, float beta, float* residual, uint8_t* label, int width_org, int height_org,
+                                      void* stream) {
+  Finish fin;
+  if (int rc = gm_batch_check(b, fb_check, alpha, beta, width_org, height_org, fin)) return rc;
+  if (!models || (!residual && !label)) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (int rc = gm_thresh_check(thresh)) return rc;
+  if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
+  HIPCHK(launch_projective_compensate_level(fin.fw, fin.fb_rev, models, count, fin.g, thresh, alpha, beta, residual, label,
+                                            (hipStream_t)stream));
   return OFDIS_OK;
 }
 

@@ -46,8 +46,8 @@ struct TsArgs {
   const int* len;         // [max_tracks]
   const long long* info;  // {ntracks, dropped}
   int lmax, max_tracks;
-  const double* models;   // [npairs][6] or null
-  int npairs;
+  const double* models;   // [npairs][nparam] or null
+  int npairs, nparam;     // nparam: 6, or 8 for the projective models (ofdis_track_select_projective)
   float cx, cy;           // (float)(W - 1) * 0.5f, (float)(H - 1) * 0.5f
   ofdis_track_select_params p;
   uint8_t* code;          // [max_tracks] or null
@@ -73,10 +73,15 @@ __device__ __forceinline__ bool ts_step(const TsArgs& a, int k, float2 p, float2
   r = d;
   if (!a.models) return true;
   if (k < 0 || k >= a.npairs) return false;
-  const double* m = a.models + (size_t)k * 6;
+  const double* m = a.models + (size_t)k * a.nparam;
   const float a0 = (float)m[0], a1 = (float)m[1], a2 = (float)m[2], a3 = (float)m[3], a4 = (float)m[4], a5 = (float)m[5];
   const float xc = p.x - a.cx, yc = p.y - a.cy;
-  const float mu = (a0 + a1 * xc) + a2 * yc, mv = (a3 + a4 * xc) + a5 * yc;
+  float mu = (a0 + a1 * xc) + a2 * yc, mv = (a3 + a4 * xc) + a5 * yc;
+  if (a.nparam == 8) {  // (uniform) the quadratic terms of the projective model
+    const float pq = (float)m[6] * xc + (float)m[7] * yc;
+    mu = mu + pq * xc;
+    mv = mv + pq * yc;
+  }
   r = make_float2(d.x - mu, d.y - mv);
   return true;
 }
@@ -257,8 +262,8 @@ size_t track_select_work_bytes(int max_tracks) { return (size_t)((max_tracks + k
 hipError_t launch_track_select(const float* tracks, const int* start, const int* len, const long long* info, int lmax, int max_tracks,
                                const double* models, int npairs, int w, int h, const ofdis_track_select_params& p, uint8_t* code,
                                long long* counts, int max_tracks_out, float* tracks_out, int* start_out, int* len_out,
-                               long long* info_out, int* index, float* shape_out, void* work, hipStream_t s) {
-  const TsArgs a{(const float2*)tracks, start, len, info, lmax, max_tracks, models, npairs, (float)(w - 1) * 0.5f,
+                               long long* info_out, int* index, float* shape_out, void* work, hipStream_t s, int nparam) {
+  const TsArgs a{(const float2*)tracks, start, len, info, lmax, max_tracks, models, npairs, nparam, (float)(w - 1) * 0.5f,
                  (float)(h - 1) * 0.5f, p, code, counts, max_tracks_out, (float2*)tracks_out, start_out, len_out, info_out, index,
                  (float2*)shape_out, (TsRecord*)work};
   const int workgroups = (max_tracks + kTsLanes - 1) / kTsLanes;

@@ -7,6 +7,9 @@ compare the kernels against `global_motion_ref` and `motion_compensate_ref` bit 
     models, stats = gmotion.global_motion_ref(flow, mask, model=gmotion.GM_AFFINE, rounds=3, thresh=1.0)
     residual, label = gmotion.motion_compensate_ref(flow, models, mask, thresh=1.0)
     foreground = label == gmotion.GM_OUTLIER
+
+The 8-parameter projective models (ofdis_projective_motion, ofdis_projective_compensate) are stated at the end of the file:
+`projective_motion_ref`, `projective_compensate_ref`, `sums23`, `model_flow8`, `homography`.
 """
 import numpy as np
 
@@ -164,3 +167,184 @@ def model_flow(a, w, h):
     xs -= (w - 1) / 2.0
     ys -= (h - 1) / 2.0
     return np.stack([a[0] + a[1] * xs + a[2] * ys, a[3] + a[4] * xs + a[5] * ys], axis=-1)
+
+
+# ------------------------------------------------------------------ 8-parameter projective models (ofdis_projective_motion)
+# include/ofdis.h, "Projective camera models": the quadratic (first-order projective) flow model
+#     p = a6*xc + a7*yc;  u = a0 + a1*xc + a2*yc + p*xc;  v = a3 + a4*xc + a5*yc + p*yc
+# fitted from 23 exact integer sums.  In integer units b (u_q = b0 + b1 X + b2 Y + b6 X^2 + b7 XY, v_q = b3 + b4 X + b5 Y +
+# b6 XY + b7 Y^2) the normal matrix N is
+#     rows / columns 0..2 and 3..5: [[n, SX, SY], [SX, SXX, SXY], [SY, SXY, SYY]], zero between the two blocks
+#     column 6: (SXX, XXX, XXY, SXY, XXY, XYY), N66 = XXXX + XXYY     column 7: (SXY, XXY, XYY, SYY, XYY, YYY), N77 = XXYY + YYYY
+#     N67 = XXXY + XYYY
+# and the right-hand side t = (Squ, SXqu, SYqu, Sqv, SXqv, SYqv, R6, R7).  Every sum is converted to float64 correctly rounded
+# (float(int)), the three sums of N66, N67, N77 are float64 additions.  Then, every operation rounded on its own:
+#     for k = 0..7:  for i = k..7:  C_ik = N_ik;  for j = 0..k-1 ascending: C_ik = C_ik - C_ij * L_kj
+#                    d_k = C_kk;  the pivot passes when d_k > N_kk * 2^-40;  for i = k+1..7: L_ik = C_ik / d_k
+#     z_i = t_i;  for j = 0..i-1 ascending: z_i = z_i - L_ij * z_j         (i = 0..7)
+#     y_i = z_i / d_i
+#     b_i = y_i;  for j = i+1..7 ascending: b_i = b_i - L_ji * b_j         (i = 7..0)
+#     a0 = b0/256, a1 = b1/128, a2 = b2/128, a3 = b3/256, a4 = b4/128, a5 = b5/128, a6 = b6/64, a7 = b7/64
+# The projective branch is taken when n >= 4 and all eight pivots pass; otherwise `solve(s[:12], GM_AFFINE)` decides, a6 = a7 = 0.
+PM_NSUMS = 23           # the sums of a record (padded to PM_RECORD int64 in the work buffer)
+PM_RECORD = 24
+PM_BLOCK_PIXELS = 1024  # a workgroup's share of a pair: 256 quads of 4 pixels
+PM_PIVOT = 2.0 ** -40
+_PM_COUNT = {GM_OK_AFFINE: 6, GM_TRANSLATION: 2, GM_EMPTY: 0}
+
+
+def sums23(flow, sel, perm=None, chunk=PM_BLOCK_PIXELS):
+    """The 23 sums over the pixels `sel` as Python ints, in the record order: the twelve of `sums`, then XXX, XXY, XYY, YYY,
+    XXXX, XXXY, XXYY, XYYY, YYYY, R6 = sum(X*X*qu + X*Y*qv), R7 = sum(X*Y*qu + Y*Y*qv).  Chunks of at most `chunk` pixels
+    (a workgroup's 1024) are summed in int64, as the accumulate kernel does, and the chunks are added as Python ints, as the
+    solve kernel's 128-bit sums are.  perm: as in `sums`."""
+    assert chunk <= PM_BLOCK_PIXELS
+    h, w = sel.shape
+    X, Y = coords(w, h)
+    X, Y = X[sel], Y[sel]
+    q = np.rint(flow[sel] * _f32(256.0)).astype(np.int64)
+    qu, qv = q[:, 0], q[:, 1]
+    if perm is not None:
+        X, Y, qu, qv = X[perm], Y[perm], qu[perm], qv[perm]
+    XX, XY, YY = X * X, X * Y, Y * Y
+    terms = [np.ones_like(X), X, Y, XX, XY, YY, qu, X * qu, Y * qu, qv, X * qv, Y * qv,
+             XX * X, XX * Y, X * YY, YY * Y, XX * XX, XX * XY, XX * YY, XY * YY, YY * YY, XX * qu + XY * qv, XY * qu + YY * qv]
+    out = [0] * PM_NSUMS
+    for c0 in range(0, len(X), chunk):
+        for k, t in enumerate(terms):
+            out[k] += int(t[c0:c0 + chunk].sum(dtype=np.int64))
+    return out
+
+
+def normal8(s):
+    """the normal matrix (8 rows of 8 floats) and right-hand side of the 23 sums, as stated above"""
+    f = [float(v) for v in s]
+    n, Sx, Sy, Sxx, Sxy, Syy = f[:6]
+    xxx, xxy, xyy, yyy, x4, x3y, x2y2, xy3, y4 = f[12:21]
+    M = [[n, Sx, Sy], [Sx, Sxx, Sxy], [Sy, Sxy, Syy]]
+    N = [[0.0] * 8 for _ in range(8)]
+    for i in range(3):
+        for j in range(3):
+            N[i][j] = N[3 + i][3 + j] = M[i][j]
+    col6 = [Sxx, xxx, xxy, Sxy, xxy, xyy]
+    col7 = [Sxy, xxy, xyy, Syy, xyy, yyy]
+    for i in range(6):
+        N[i][6] = N[6][i] = col6[i]
+        N[i][7] = N[7][i] = col7[i]
+    N[6][6] = x4 + x2y2
+    N[6][7] = N[7][6] = x3y + xy3
+    N[7][7] = x2y2 + y4
+    return N, f[6:12] + f[21:23]
+
+
+def solve8(s):
+    """The header's solve on the 23 sums: (a [8] float64, count), count = 8, 6, 2 or 0 parameters solved.  pivot_ratios(s)
+    gives the d_k / N_kk the rank test looks at."""
+    b = _ldl8(s)[0] if s[0] >= 4 else None
+    if b is not None:
+        a = [b[0] / 256.0, b[1] / 128.0, b[2] / 128.0, b[3] / 256.0, b[4] / 128.0, b[5] / 128.0, b[6] / 64.0, b[7] / 64.0]
+        return np.array(a, np.float64), 8
+    a6, status = solve(s[:12], GM_AFFINE)
+    return np.concatenate([a6, np.zeros(2)]), _PM_COUNT[status]
+
+
+def _ldl8(s):
+    """(b [8] or None where a pivot fails, the pivots d_k computed so far, the diagonal N_kk)"""
+    N, t = normal8(s)
+    C = [[0.0] * 8 for _ in range(8)]
+    L = [[0.0] * 8 for _ in range(8)]
+    d = []
+    for k in range(8):
+        for i in range(k, 8):
+            acc = N[i][k]
+            for j in range(k):
+                acc = acc - C[i][j] * L[k][j]
+            C[i][k] = acc
+        d.append(C[k][k])
+        if not d[k] > N[k][k] * PM_PIVOT:
+            return None, d, [N[i][i] for i in range(8)]
+        for i in range(k + 1, 8):
+            L[i][k] = C[i][k] / d[k]
+    z = list(t)
+    for i in range(8):
+        for j in range(i):
+            z[i] = z[i] - L[i][j] * z[j]
+    b = [z[i] / d[i] for i in range(8)]
+    for i in range(7, -1, -1):
+        for j in range(i + 1, 8):
+            b[i] = b[i] - L[j][i] * b[j]
+    return b, d, [N[i][i] for i in range(8)]
+
+
+def pivot_ratios(s):
+    """d_k / N_kk of the pivots the factorisation reached (the last one is the failing one where the rank test fails)"""
+    _, d, diag = _ldl8(s)
+    return [dk / nk if nk else 0.0 for dk, nk in zip(d, diag)]
+
+
+def residual8(flow, a):
+    """flow [h][w][2] float32 minus the 8-parameter model a (float64, converted to float32 first): [h][w][2] float32"""
+    h, w = flow.shape[:2]
+    X, Y = coords(w, h)
+    with np.errstate(over="ignore", invalid="ignore"):
+        af = np.asarray(a, np.float64).astype(_f32)
+        xc, yc = X.astype(_f32) * _f32(0.5), Y.astype(_f32) * _f32(0.5)
+        p = af[6] * xc + af[7] * yc
+        mu = ((af[0] + af[1] * xc) + af[2] * yc) + p * xc
+        mv = ((af[3] + af[4] * xc) + af[5] * yc) + p * yc
+        return np.stack([flow[..., 0] - mu, flow[..., 1] - mv], axis=-1)
+
+
+def projective_motion_ref(flow, mask=None, rounds=3, thresh=1.0, shuffle=None):
+    """flow [npairs][h][w][2] float32, mask [npairs][h][w] uint8 or None -> (models [npairs][8] float64, stats [npairs][3]
+    int64: |S_0|, the size of the last set used, the number of parameters solved: 8, 6, 2 or 0), what ofdis_projective_motion
+    writes.  shuffle: as in global_motion_ref."""
+    _check(rounds, thresh)
+    flow, mask = _pairs(flow, mask)
+    models = np.zeros((flow.shape[0], 8), np.float64)
+    stats = np.zeros((flow.shape[0], 3), np.int64)
+    for k in range(flow.shape[0]):
+        ok = valid(flow[k], None if mask is None else mask[k])
+        sel = ok
+        for r in range(rounds):
+            if r > 0:
+                sel = near(residual8(flow[k], models[k]), ok, thresh)
+            s = sums23(flow[k], sel, None if shuffle is None else shuffle.permutation(int(sel.sum())))
+            if r > 0 and s[0] == 0:
+                break   # the model, set size and count of round r-1 stay
+            models[k], count = solve8(s)
+            if r == 0:
+                stats[k, 0] = s[0]
+            stats[k, 1:] = s[0], count
+    return models, stats
+
+
+def projective_compensate_ref(flow, models, mask=None, thresh=1.0):
+    """flow [npairs][h][w][2] float32, models [npairs][8] float64 -> (residual [npairs][h][w][2] float32, label [npairs][h][w]
+    uint8), what ofdis_projective_compensate writes."""
+    _check(1, thresh)
+    flow, mask = _pairs(flow, mask)
+    models = np.asarray(models, np.float64).reshape(flow.shape[0], 8)
+    res = np.empty_like(flow)
+    label = np.empty(flow.shape[:3], np.uint8)
+    for k in range(flow.shape[0]):
+        ok = valid(flow[k], None if mask is None else mask[k])
+        res[k] = residual8(flow[k], models[k])
+        label[k] = np.where(near(res[k], ok, thresh), GM_INLIER, np.where(ok, GM_OUTLIER, GM_INVALID))
+    return res, label
+
+
+def model_flow8(a, w, h):
+    """the 8-parameter model's flow field [h][w][2] in float64 (for users and tests; the kernels use `residual8`)"""
+    ys, xs = np.mgrid[0:h, 0:w].astype(np.float64)
+    xs -= (w - 1) / 2.0
+    ys -= (h - 1) / 2.0
+    p = a[6] * xs + a[7] * ys
+    return np.stack([a[0] + a[1] * xs + a[2] * ys + p * xs, a[3] + a[4] * xs + a[5] * ys + p * ys], axis=-1)
+
+
+def homography(a):
+    """the homography the model a [8] is the first-order flow of, in centred coordinates: [[1+a1, a2, a0], [a4, 1+a5, a3],
+    [-a6, -a7, 1]] (float64 [3][3]); a 6-parameter model gives the affine matrix"""
+    a = np.concatenate([np.asarray(a, np.float64).ravel(), np.zeros(2)])[:8]
+    return np.array([[1.0 + a[1], a[2], a[0]], [a[4], 1.0 + a[5], a[3]], [-a[6], -a[7], 1.0]], np.float64)

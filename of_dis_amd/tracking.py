@@ -292,7 +292,9 @@ def _track_steps(tracks, start, models, size):
     """per step j < lmax: (d [n][2], r [n][2], has a model [n]) of the header's "step" and "residual step", float32"""
     lmax, n = tracks.shape[0] - 1, tracks.shape[1]
     if models is not None:
-        models = np.asarray(models, np.float64).reshape(-1, 6)
+        models = np.asarray(models, np.float64)
+        wide = models.ndim == 2 and models.shape[1] == 8   # the projective models of ofdis_track_select_projective
+        models = models.reshape(-1, 8 if wide else 6)
         af = models.astype(_f32)
         cx, cy = _f32(size[0] - 1) * _f32(0.5), _f32(size[1] - 1) * _f32(0.5)
     for j in range(lmax):
@@ -305,13 +307,17 @@ def _track_steps(tracks, start, models, size):
             xc, yc = tracks[j, :, 0] - cx, tracks[j, :, 1] - cy
             mu = (a[:, 0] + a[:, 1] * xc) + a[:, 2] * yc
             mv = (a[:, 3] + a[:, 4] * xc) + a[:, 5] * yc
+            if wide:
+                pq = a[:, 6] * xc + a[:, 7] * yc
+                mu, mv = mu + pq * xc, mv + pq * yc
             r = np.where(known[:, None], np.stack([d[:, 0] - mu, d[:, 1] - mv], 1), d)
         yield j, d, r, known
 
 
 def track_select_ref(tracks, start, length, models=None, size=None, params=None, max_out=None):
     """The definition of ofdis_track_select in numpy float32, operation by operation.  tracks [lmax + 1][ntracks][2], start,
-    length [ntracks] as dense_tracks_ref returns them; models float64 [npairs][6] as global_motion returns them with size =
+    length [ntracks] as dense_tracks_ref returns them; models float64 [npairs][6] as global_motion returns them (or [npairs][8]
+    as projective_motion does: the definition of ofdis_track_select_projective) with size =
     (W, H) of their frames, or None; params a TrackSelectParams (None: the defaults); max_out the slots of the output set
     (None: room for every track) -> (code uint8 [ntracks], counts int64 [7], tracks_out [lmax + 1][nkept_written][2], start_out,
     len_out int32 [nkept_written], info_out int64 [2] = (nkept_written, dropped_out), index int32 [nkept_written], shape_out

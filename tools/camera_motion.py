@@ -2,7 +2,7 @@
 from the level flows of a SEQUENCE | REVERSE batch context (ofdis_batch_global_motion, include/ofdis.h) -- a translation or a
 6-parameter affine model by trimmed least squares, pixels that fail the forward-backward test left out.
 
-    python tools/camera_motion.py [--rgb] [--op 1..4] [--fused] [--model affine|translation] [--rounds 3] [--thresh 1.0]
+    python tools/camera_motion.py [--rgb] [--op 1..4] [--fused] [--model affine|translation|projective] [--rounds 3] [--thresh 1.0]
                                   [--no-fb] [--labels STEM] img0 img1 ... imgN [out.csv]
 
 Images load as for tools/flow_images.py; at least two, all of one size.  Writes one CSV line per pair -- a0,a1,a2,a3,a4,a5,
@@ -12,7 +12,10 @@ significant digits (they read back to the same doubles); status 0 = affine, 1 = 
 pixels), 2 = no valid pixel.  --labels STEM also writes the label map of every pair as <STEM>_000.png ...: 0 = inlier (moves
 with the camera), 127 = outlier (moves on its own), 255 = invalid.  --no-fb fits on every pixel with a finite flow (no
 forward-backward test).  --fused selects the FMA / fast-reciprocal arithmetic contract for the flow (default: the exact one);
-the fit does not depend on it.  Not here: homography models, stabilisation (warping frames along a smoothed camera path)."""
+the fit does not depend on it.  --model projective fits the 8-parameter quadratic model of ofdis_batch_projective_motion
+instead -- u = a0 + a1*xc + a2*yc + p*xc, v = a3 + a4*xc + a5*yc + p*yc with p = a6*xc + a7*yc, xc = x - cx, yc = y - cy -- and
+writes a0,...,a7,n_valid,n_inliers,count per pair, count the number of parameters solved (8, or 6, 2, 0 where the pixels do
+not determine eight).  Not here: stabilisation (warping frames along a smoothed camera path)."""
 import math
 import os
 import sys
@@ -63,8 +66,8 @@ def main(argv):
     except (ValueError, StopIteration):
         sys.exit(f"{a}: a value is missing or is not a number")
     # every option is checked here, before the first device call
-    if model not in ("affine", "translation"):
-        sys.exit("--model: affine or translation")
+    if model not in ("affine", "translation", "projective"):
+        sys.exit("--model: affine, translation or projective")
     if not 1 <= rounds <= capi.GM_MAX_ROUNDS:
         sys.exit("--rounds: an integer in 1..%d" % capi.GM_MAX_ROUNDS)
     if not (math.isfinite(thresh) and thresh > 0.0):
@@ -87,9 +90,13 @@ def main(argv):
     d = capi.Dev(clip)
     b.build_pyramids_u8_seq(d.ptr, w, h)
     b.run()
-    gm = capi.GM_AFFINE if model == "affine" else capi.GM_TRANSLATION_ONLY
-    models, stats = b.global_motion(w, h, model=gm, rounds=rounds, thresh=thresh, fb_check=fb)
-    label = b.motion_compensate(models, w, h, thresh=thresh, fb_check=fb, residual=False)[1] if labels else None
+    if model == "projective":
+        models, stats = b.projective_motion(w, h, rounds=rounds, thresh=thresh, fb_check=fb)
+        label = b.projective_compensate(models, w, h, thresh=thresh, fb_check=fb, residual=False)[1] if labels else None
+    else:
+        gm = capi.GM_AFFINE if model == "affine" else capi.GM_TRANSLATION_ONLY
+        models, stats = b.global_motion(w, h, model=gm, rounds=rounds, thresh=thresh, fb_check=fb)
+        label = b.motion_compensate(models, w, h, thresh=thresh, fb_check=fb, residual=False)[1] if labels else None
     b.close()
     d.free()
     lines = [csv_line(m, s) for m, s in zip(models, stats)]
