@@ -870,64 +870,65 @@ def _gm_inputs(flow, mask):
     return flow, _mask_dev(mask, (npairs, h, w)), npairs, h, w
 
 
-def global_motion(flow, mask=None, model=GM_AFFINE, rounds=3, thresh=1.0):
-    """ofdis_global_motion on the device: flow [npairs, h, w, 2] float32, mask uint8 [npairs, h, w] or None (all consistent)
-    -> (models [npairs, 6] float64, stats [npairs, 3] int64: |S_0|, the size of the last set used, the status).
-    of_dis_amd/gmotion.py: global_motion_ref is the numpy statement of the same arithmetic."""
+# The camera-model families by nparam, the doubles per model (a pair's model takes nparam * 8 bytes): the C functions of the
+# fit (its work buffer: <fit>_work_bytes) and of the compensation, standalone and batch.  Only the 6-parameter fits take `model`.
+_CAMERA = {6: dict(fit="ofdis_global_motion", compensate="ofdis_motion_compensate", batch_fit="ofdis_batch_global_motion",
+                   batch_compensate="ofdis_batch_motion_compensate", model_arg=True),
+           8: dict(fit="ofdis_projective_motion", compensate="ofdis_projective_compensate",
+                   batch_fit="ofdis_batch_projective_motion", batch_compensate="ofdis_batch_projective_compensate",
+                   model_arg=False)}
+
+
+def _camera_fit(nparam, flow, mask, model, rounds, thresh, stats):
+    fam = _CAMERA[nparam]
     flow, dm, npairs, h, w = _gm_inputs(flow, mask)
     df = Dev(flow)
-    dmodels, dstats = Dev(nbytes=max(8, npairs * 48)), Dev(nbytes=max(8, npairs * 24))
-    wb = lib().ofdis_global_motion_work_bytes(npairs, w, h)
+    dmodels, dstats = Dev(nbytes=max(8, npairs * nparam * 8)), Dev(nbytes=max(8, npairs * 24)) if stats else None
+    wb = getattr(lib(), fam["fit"] + "_work_bytes")(npairs, w, h)
     dwork = Dev(nbytes=max(8, wb))
-    check(lib().ofdis_global_motion(df.ptr, dm.ptr if dm else None, npairs, w, h, model, rounds, thresh, dmodels.ptr, dstats.ptr,
-                                    dwork.ptr, wb, None))
+    check(getattr(lib(), fam["fit"])(df.ptr, dm.ptr if dm else None, npairs, w, h, *([model] if fam["model_arg"] else []), rounds,
+                                     thresh, dmodels.ptr, dstats.ptr if dstats else None, dwork.ptr, wb, None))
     check(lib().ofdis_sync(None))
-    return dmodels.get((npairs, 6), np.float64), dstats.get((npairs, 3), np.int64)
+    return dmodels.get((npairs, nparam), np.float64), dstats.get((npairs, 3), np.int64) if dstats else None
+
+
+def _camera_compensate(nparam, flow, models, mask, thresh, residual, label, in_place):
+    flow, dm, npairs, h, w = _gm_inputs(flow, mask)
+    models = np.ascontiguousarray(models, np.float64)
+    assert models.shape == (npairs, nparam), models.shape
+    df, dmodels = Dev(flow), Dev(models)
+    dr = (df if in_place else Dev(nbytes=max(8, flow.nbytes))) if residual else None
+    dl = Dev(nbytes=max(1, npairs * h * w)) if label else None
+    check(getattr(lib(), _CAMERA[nparam]["compensate"])(df.ptr, dm.ptr if dm else None, dmodels.ptr, npairs, w, h, thresh,
+                                                        dr.ptr if dr else None, dl.ptr if dl else None, None))
+    check(lib().ofdis_sync(None))
+    return dr.get(flow.shape, _f32) if dr else None, dl.get((npairs, h, w), np.uint8) if dl else None
+
+
+def global_motion(flow, mask=None, model=GM_AFFINE, rounds=3, thresh=1.0, stats=True):
+    """ofdis_global_motion on the device: flow [npairs, h, w, 2] float32, mask uint8 [npairs, h, w] or None (all consistent)
+    -> (models [npairs, 6] float64, stats [npairs, 3] int64: |S_0|, the size of the last set used, the status; None with
+    stats=False, which passes NULL).  of_dis_amd/gmotion.py: global_motion_ref is the numpy statement of the same arithmetic."""
+    return _camera_fit(6, flow, mask, model, rounds, thresh, stats)
 
 
 def motion_compensate(flow, models, mask=None, thresh=1.0, residual=True, label=True, in_place=False):
     """ofdis_motion_compensate on the device: flow [npairs, h, w, 2] float32, models [npairs, 6] float64, mask as above ->
     (residual [npairs, h, w, 2] float32, label [npairs, h, w] uint8); residual=False / label=False pass NULL and return None in
     that place.  in_place: `residual` is the flow's own device array (the library allows it)."""
-    flow, dm, npairs, h, w = _gm_inputs(flow, mask)
-    models = np.ascontiguousarray(models, np.float64)
-    assert models.shape == (npairs, 6), models.shape
-    df, dmodels = Dev(flow), Dev(models)
-    dr = (df if in_place else Dev(nbytes=max(8, flow.nbytes))) if residual else None
-    dl = Dev(nbytes=max(1, npairs * h * w)) if label else None
-    check(lib().ofdis_motion_compensate(df.ptr, dm.ptr if dm else None, dmodels.ptr, npairs, w, h, thresh, dr.ptr if dr else None,
-                                        dl.ptr if dl else None, None))
-    check(lib().ofdis_sync(None))
-    return dr.get(flow.shape, _f32) if dr else None, dl.get((npairs, h, w), np.uint8) if dl else None
+    return _camera_compensate(6, flow, models, mask, thresh, residual, label, in_place)
 
 
 def projective_motion(flow, mask=None, rounds=3, thresh=1.0, stats=True):
     """ofdis_projective_motion on the device: flow and mask as global_motion takes them -> (models [npairs, 8] float64, stats
     [npairs, 3] int64: |S_0|, the size of the last set used, the parameters solved: 8, 6, 2 or 0; None with stats=False, which
     passes NULL).  of_dis_amd/gmotion.py: projective_motion_ref is the numpy statement of the same arithmetic."""
-    flow, dm, npairs, h, w = _gm_inputs(flow, mask)
-    df = Dev(flow)
-    dmodels, dstats = Dev(nbytes=max(8, npairs * 64)), Dev(nbytes=max(8, npairs * 24)) if stats else None
-    wb = lib().ofdis_projective_motion_work_bytes(npairs, w, h)
-    dwork = Dev(nbytes=max(8, wb))
-    check(lib().ofdis_projective_motion(df.ptr, dm.ptr if dm else None, npairs, w, h, rounds, thresh, dmodels.ptr,
-                                        dstats.ptr if dstats else None, dwork.ptr, wb, None))
-    check(lib().ofdis_sync(None))
-    return dmodels.get((npairs, 8), np.float64), dstats.get((npairs, 3), np.int64) if dstats else None
+    return _camera_fit(8, flow, mask, None, rounds, thresh, stats)
 
 
 def projective_compensate(flow, models, mask=None, thresh=1.0, residual=True, label=True, in_place=False):
     """ofdis_projective_compensate on the device: motion_compensate with models [npairs, 8] float64."""
-    flow, dm, npairs, h, w = _gm_inputs(flow, mask)
-    models = np.ascontiguousarray(models, np.float64)
-    assert models.shape == (npairs, 8), models.shape
-    df, dmodels = Dev(flow), Dev(models)
-    dr = (df if in_place else Dev(nbytes=max(8, flow.nbytes))) if residual else None
-    dl = Dev(nbytes=max(1, npairs * h * w)) if label else None
-    check(lib().ofdis_projective_compensate(df.ptr, dm.ptr if dm else None, dmodels.ptr, npairs, w, h, thresh,
-                                            dr.ptr if dr else None, dl.ptr if dl else None, None))
-    check(lib().ofdis_sync(None))
-    return dr.get(flow.shape, _f32) if dr else None, dl.get((npairs, h, w), np.uint8) if dl else None
+    return _camera_compensate(8, flow, models, mask, thresh, residual, label, in_place)
 
 
 def _stab_weights(weights):
@@ -1273,24 +1274,57 @@ class Batch:
                             stream)
         return res if res is None or support else res[0]
 
+    def _camera_fit(self, nparam, width_org, height_org, model, rounds, thresh, fb_check, first, count, alpha, beta, models_ptr,
+                    stats_ptr, stream):
+        fam = _CAMERA[nparam]
+        count = self.nframes - first if count is None else count
+        n = max(count, 1)
+        dm = ds = None
+        if models_ptr is None:
+            dm, ds = Dev(nbytes=n * nparam * 8), Dev(nbytes=n * 24)
+            models_ptr, stats_ptr = dm.ptr, ds.ptr
+        check(getattr(lib(), fam["batch_fit"])(self.h, first, count, *([model] if fam["model_arg"] else []), rounds, thresh,
+                                               int(fb_check), alpha, beta, models_ptr, stats_ptr, width_org, height_org, stream))
+        if dm is None:
+            return None
+        check(lib().ofdis_sync(stream))
+        return dm.get((count, nparam), np.float64), ds.get((count, 3), np.int64)
+
+    def _camera_compensate(self, nparam, models, width_org, height_org, thresh, fb_check, first, count, alpha, beta, residual,
+                           label, out_ptr, stream):
+        count = self.nframes - first if count is None else count
+        n = max(count, 1)
+        keep = None
+        if not isinstance(models, (int, type(None))):
+            models = np.ascontiguousarray(models, np.float64)
+            assert models.shape == (n, nparam), models.shape
+            keep = Dev(models)
+            models = keep.ptr
+        rshape, lshape = (n, height_org, width_org, 2), (n, height_org, width_org)
+        dr = dl = None
+        if out_ptr is None:
+            dr = Dev(nbytes=max(8, int(np.prod(rshape, dtype=np.int64)) * 4)) if residual else None
+            dl = Dev(nbytes=max(1, int(np.prod(lshape, dtype=np.int64)))) if label else None
+            rptr, lptr = dr.ptr if dr else None, dl.ptr if dl else None
+        else:
+            rptr, lptr = out_ptr
+        check(getattr(lib(), _CAMERA[nparam]["batch_compensate"])(self.h, first, count, models, thresh, int(fb_check), alpha, beta,
+                                                                  rptr, lptr, width_org, height_org, stream))
+        if out_ptr is not None:
+            if keep is not None:
+                check(lib().ofdis_sync(stream))  # the uploaded models must outlive the launch
+            return None
+        check(lib().ofdis_sync(stream))
+        return dr.get(rshape, _f32) if dr else None, dl.get(lshape, np.uint8) if dl else None
+
     def global_motion(self, width_org, height_org, model=GM_AFFINE, rounds=3, thresh=1.0, fb_check=False, first=0, count=None,
                       alpha=FB_ALPHA, beta=FB_BETA, models_ptr=None, stats_ptr=None, stream=None):
         """ofdis_batch_global_motion over the pairs [first, first + count) of an optical-flow context, straight from its level
         flows.  fb_check=True (needs reverse=True) honours the forward mask of upsample_bidir.  models_ptr None: returns the
         host arrays (models [count, 6] float64, stats [count, 3] int64); else writes the device array models_ptr (and stats_ptr,
         if given) on `stream` and returns None."""
-        count = self.nframes - first if count is None else count
-        n = max(count, 1)
-        dm = ds = None
-        if models_ptr is None:
-            dm, ds = Dev(nbytes=n * 48), Dev(nbytes=n * 24)
-            models_ptr, stats_ptr = dm.ptr, ds.ptr
-        check(lib().ofdis_batch_global_motion(self.h, first, count, model, rounds, thresh, int(fb_check), alpha, beta, models_ptr,
-                                              stats_ptr, width_org, height_org, stream))
-        if dm is None:
-            return None
-        check(lib().ofdis_sync(stream))
-        return dm.get((count, 6), np.float64), ds.get((count, 3), np.int64)
+        return self._camera_fit(6, width_org, height_org, model, rounds, thresh, fb_check, first, count, alpha, beta, models_ptr,
+                                stats_ptr, stream)
 
     def motion_compensate(self, models, width_org, height_org, thresh=1.0, fb_check=False, first=0, count=None, alpha=FB_ALPHA,
                           beta=FB_BETA, residual=True, label=True, out_ptr=None, stream=None):
@@ -1298,76 +1332,22 @@ class Batch:
         device pointer.  out_ptr None: returns the host arrays (residual [count, height_org, width_org, 2] float32, label
         [count, height_org, width_org] uint8; None where residual=False / label=False); else out_ptr = (residual device pointer
         or None, label device pointer or None), written on `stream`, and the call returns None."""
-        count = self.nframes - first if count is None else count
-        n = max(count, 1)
-        keep = None
-        if not isinstance(models, (int, type(None))):
-            models = np.ascontiguousarray(models, np.float64)
-            assert models.shape == (n, 6), models.shape
-            keep = Dev(models)
-            models = keep.ptr
-        rshape, lshape = (n, height_org, width_org, 2), (n, height_org, width_org)
-        dr = dl = None
-        if out_ptr is None:
-            dr = Dev(nbytes=max(8, int(np.prod(rshape, dtype=np.int64)) * 4)) if residual else None
-            dl = Dev(nbytes=max(1, int(np.prod(lshape, dtype=np.int64)))) if label else None
-            rptr, lptr = dr.ptr if dr else None, dl.ptr if dl else None
-        else:
-            rptr, lptr = out_ptr
-        check(lib().ofdis_batch_motion_compensate(self.h, first, count, models, thresh, int(fb_check), alpha, beta, rptr, lptr,
-                                                  width_org, height_org, stream))
-        if out_ptr is not None:
-            if keep is not None:
-                check(lib().ofdis_sync(stream))  # the uploaded models must outlive the launch
-            return None
-        check(lib().ofdis_sync(stream))
-        return dr.get(rshape, _f32) if dr else None, dl.get(lshape, np.uint8) if dl else None
+        return self._camera_compensate(6, models, width_org, height_org, thresh, fb_check, first, count, alpha, beta, residual,
+                                       label, out_ptr, stream)
 
     def projective_motion(self, width_org, height_org, rounds=3, thresh=1.0, fb_check=False, first=0, count=None, alpha=FB_ALPHA,
                           beta=FB_BETA, models_ptr=None, stats_ptr=None, stream=None):
         """ofdis_batch_projective_motion: global_motion with the 8-parameter model.  models_ptr None: returns the host arrays
         (models [count, 8] float64, stats [count, 3] int64); else writes the device arrays on `stream` and returns None."""
-        count = self.nframes - first if count is None else count
-        n = max(count, 1)
-        dm = ds = None
-        if models_ptr is None:
-            dm, ds = Dev(nbytes=n * 64), Dev(nbytes=n * 24)
-            models_ptr, stats_ptr = dm.ptr, ds.ptr
-        check(lib().ofdis_batch_projective_motion(self.h, first, count, rounds, thresh, int(fb_check), alpha, beta, models_ptr,
-                                                  stats_ptr, width_org, height_org, stream))
-        if dm is None:
-            return None
-        check(lib().ofdis_sync(stream))
-        return dm.get((count, 8), np.float64), ds.get((count, 3), np.int64)
+        return self._camera_fit(8, width_org, height_org, None, rounds, thresh, fb_check, first, count, alpha, beta, models_ptr,
+                                stats_ptr, stream)
 
     def projective_compensate(self, models, width_org, height_org, thresh=1.0, fb_check=False, first=0, count=None,
                               alpha=FB_ALPHA, beta=FB_BETA, residual=True, label=True, out_ptr=None, stream=None):
         """ofdis_batch_projective_compensate: motion_compensate with models [count, 8] float64 (host array or device pointer);
         the outputs as there."""
-        count = self.nframes - first if count is None else count
-        n = max(count, 1)
-        keep = None
-        if not isinstance(models, (int, type(None))):
-            models = np.ascontiguousarray(models, np.float64)
-            assert models.shape == (n, 8), models.shape
-            keep = Dev(models)
-            models = keep.ptr
-        rshape, lshape = (n, height_org, width_org, 2), (n, height_org, width_org)
-        dr = dl = None
-        if out_ptr is None:
-            dr = Dev(nbytes=max(8, int(np.prod(rshape, dtype=np.int64)) * 4)) if residual else None
-            dl = Dev(nbytes=max(1, int(np.prod(lshape, dtype=np.int64)))) if label else None
-            rptr, lptr = dr.ptr if dr else None, dl.ptr if dl else None
-        else:
-            rptr, lptr = out_ptr
-        check(lib().ofdis_batch_projective_compensate(self.h, first, count, models, thresh, int(fb_check), alpha, beta, rptr,
-                                                      lptr, width_org, height_org, stream))
-        if out_ptr is not None:
-            if keep is not None:
-                check(lib().ofdis_sync(stream))  # the uploaded models must outlive the launch
-            return None
-        check(lib().ofdis_sync(stream))
-        return dr.get(rshape, _f32) if dr else None, dl.get(lshape, np.uint8) if dl else None
+        return self._camera_compensate(8, models, width_org, height_org, thresh, fb_check, first, count, alpha, beta, residual,
+                                       label, out_ptr, stream)
 
     def stabilize(self, frames_ptr, width_org, height_org, weights, zoom=1.0, border=BORDER_CONSTANT, model=GM_AFFINE, rounds=3,
                   thresh=1.0, fb_check=False, first=0, count=None, alpha=FB_ALPHA, beta=FB_BETA, inside=False, out_ptr=None,

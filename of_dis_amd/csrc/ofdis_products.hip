@@ -640,114 +640,120 @@ static int gm_batch_check(const ofdis_batch* b, int fb_check, float alpha, float
   return OFDIS_OK;
 }
 
+static size_t camera_work_bytes(int npairs, int width, int height, int nparam) {
+  return nparam == 8 ? projective_work_bytes(npairs, width, height) : gmotion_work_bytes(npairs, width, height);
+}
+
+// The four entry points of a family, nparam = 6 (ofdis_global_motion ...) or 8 (ofdis_projective_motion ...: no `model`
+// argument, the callers pass OFDIS_GM_AFFINE): the checks and the launch; the extern "C" functions below forward.
+static int camera_fit(const float* flow, const uint8_t* mask, int npairs, int width, int height, int model, int rounds,
+                      float thresh, double* models, long long* stats, void* work, size_t work_bytes, void* stream, int nparam) {
+  if (!flow || !models) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (int rc = gm_fit_check(model, rounds, thresh)) return rc;
+  if (!gm_sizes_ok(npairs, width, height)) return fail(OFDIS_ERR_INVALID, kGmSizes);
+  if (int rc = work_check(work, work_bytes, camera_work_bytes(npairs, width, height, nparam),
+                          nparam == 8 ? "ofdis_projective_motion_work_bytes" : "ofdis_global_motion_work_bytes"))
+    return rc;
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(nparam == 8 ? launch_projective_frames(flow, mask, npairs, width, height, rounds, thresh, models, stats, work, s)
+                     : launch_gmotion_frames(flow, mask, npairs, width, height, model, rounds, thresh, models, stats, work, s));
+  return OFDIS_OK;
+}
+
+static int camera_compensate(const float* flow, const uint8_t* mask, const double* models, int npairs, int width, int height,
+                             float thresh, float* residual, uint8_t* label, void* stream, int nparam) {
+  if (!flow || !models || (!residual && !label)) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (int rc = gm_thresh_check(thresh)) return rc;
+  if (!gm_sizes_ok(npairs, width, height)) return fail(OFDIS_ERR_INVALID, kGmSizes);
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(nparam == 8 ? launch_projective_compensate_frames(flow, mask, models, npairs, width, height, thresh, residual, label, s)
+                     : launch_gmotion_compensate_frames(flow, mask, models, npairs, width, height, thresh, residual, label, s));
+  return OFDIS_OK;
+}
+
+static int camera_batch_fit(ofdis_batch* b, int first_frame, int count, int model, int rounds, float thresh, int fb_check,
+                            float alpha, float beta, double* models, long long* stats, int width_org, int height_org, void* stream,
+                            int nparam) {
+  Finish fin;
+  if (int rc = gm_batch_check(b, fb_check, alpha, beta, width_org, height_org, fin)) return rc;
+  if (!models) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (int rc = gm_fit_check(model, rounds, thresh)) return rc;
+  if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
+  // records for every pair at the padded size (no original size needs more), held as floats; one slab per family
+  const size_t slab =
+      camera_work_bytes(1, std::min(b->p.width, OFDIS_GM_MAX_SIDE), std::min(b->p.height, OFDIS_GM_MAX_SIDE), nparam);
+  float*& held = nparam == 8 ? b->pm_slab : b->gm_slab;
+  if (int rc = dstage(b, {{&held, slab / sizeof(float)}})) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(nparam == 8
+             ? launch_projective_level(fin.fw, fin.fb_rev, count, fin.g, rounds, thresh, alpha, beta, models, stats, held, s)
+             : launch_gmotion_level(fin.fw, fin.fb_rev, count, fin.g, model, rounds, thresh, alpha, beta, models, stats, held, s));
+  return OFDIS_OK;
+}
+
+static int camera_batch_compensate(ofdis_batch* b, int first_frame, int count, const double* models, float thresh, int fb_check,
+                                   float alpha, float beta, float* residual, uint8_t* label, int width_org, int height_org,
+                                   void* stream, int nparam) {
+  Finish fin;
+  if (int rc = gm_batch_check(b, fb_check, alpha, beta, width_org, height_org, fin)) return rc;
+  if (!models || (!residual && !label)) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (int rc = gm_thresh_check(thresh)) return rc;
+  if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(nparam == 8
+             ? launch_projective_compensate_level(fin.fw, fin.fb_rev, models, count, fin.g, thresh, alpha, beta, residual, label, s)
+             : launch_gmotion_compensate_level(fin.fw, fin.fb_rev, models, count, fin.g, thresh, alpha, beta, residual, label, s));
+  return OFDIS_OK;
+}
+
 size_t ofdis_global_motion_work_bytes(int npairs, int width, int height) {
-  return gm_sizes_ok(npairs, width, height) ? gmotion_work_bytes(npairs, width, height) : 0;
+  return gm_sizes_ok(npairs, width, height) ? camera_work_bytes(npairs, width, height, 6) : 0;
+}
+size_t ofdis_projective_motion_work_bytes(int npairs, int width, int height) {
+  return gm_sizes_ok(npairs, width, height) ? camera_work_bytes(npairs, width, height, 8) : 0;
 }
 
 int ofdis_global_motion(const float* flow, const uint8_t* mask, int npairs, int width, int height, int model, int rounds,
                         float thresh, double* models, long long* stats, void* work, size_t work_bytes, void* stream) {
-  if (!flow || !models) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  if (int rc = gm_fit_check(model, rounds, thresh)) return rc;
-  if (!gm_sizes_ok(npairs, width, height)) return fail(OFDIS_ERR_INVALID, kGmSizes);
-  if (int rc = work_check(work, work_bytes, gmotion_work_bytes(npairs, width, height), "ofdis_global_motion_work_bytes")) return rc;
-  HIPCHK(launch_gmotion_frames(flow, mask, npairs, width, height, model, rounds, thresh, models, stats, work,
-                               (hipStream_t)stream));
-  return OFDIS_OK;
+  return camera_fit(flow, mask, npairs, width, height, model, rounds, thresh, models, stats, work, work_bytes, stream, 6);
+}
+int ofdis_projective_motion(const float* flow, const uint8_t* mask, int npairs, int width, int height, int rounds, float thresh,
+                            double* models, long long* stats, void* work, size_t work_bytes, void* stream) {
+  return camera_fit(flow, mask, npairs, width, height, OFDIS_GM_AFFINE, rounds, thresh, models, stats, work, work_bytes, stream, 8);
 }
 
 int ofdis_motion_compensate(const float* flow, const uint8_t* mask, const double* models, int npairs, int width, int height,
                             float thresh, float* residual, uint8_t* label, void* stream) {
-  if (!flow || !models || (!residual && !label)) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  if (int rc = gm_thresh_check(thresh)) return rc;
-  if (!gm_sizes_ok(npairs, width, height)) return fail(OFDIS_ERR_INVALID, kGmSizes);
-  HIPCHK(launch_gmotion_compensate_frames(flow, mask, models, npairs, width, height, thresh, residual, label,
-                                          (hipStream_t)stream));
-  return OFDIS_OK;
+  return camera_compensate(flow, mask, models, npairs, width, height, thresh, residual, label, stream, 6);
+}
+int ofdis_projective_compensate(const float* flow, const uint8_t* mask, const double* models, int npairs, int width, int height,
+                                float thresh, float* residual, uint8_t* label, void* stream) {
+  return camera_compensate(flow, mask, models, npairs, width, height, thresh, residual, label, stream, 8);
 }
 
 int ofdis_batch_global_motion(ofdis_batch* b, int first_frame, int count, int model, int rounds, float thresh, int fb_check,
                               float alpha, float beta, double* models, long long* stats, int width_org, int height_org,
                               void* stream) {
-  Finish fin;
-  if (int rc = gm_batch_check(b, fb_check, alpha, beta, width_org, height_org, fin)) return rc;
-  if (!models) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  if (int rc = gm_fit_check(model, rounds, thresh)) return rc;
-  if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
-  // records for every pair at the padded size (no original size needs more), held as floats
-  const size_t slab = gmotion_work_bytes(1, std::min(b->p.width, OFDIS_GM_MAX_SIDE), std::min(b->p.height, OFDIS_GM_MAX_SIDE));
-  if (int rc = dstage(b, {{&b->gm_slab, slab / sizeof(float)}})) return rc;
-  HIPCHK(launch_gmotion_level(fin.fw, fin.fb_rev, count, fin.g, model, rounds, thresh, alpha, beta, models, stats, b->gm_slab,
-                              (hipStream_t)stream));
-  return OFDIS_OK;
+  return camera_batch_fit(b, first_frame, count, model, rounds, thresh, fb_check, alpha, beta, models, stats, width_org,
+                          height_org, stream, 6);
+}
+int ofdis_batch_projective_motion(ofdis_batch* b, int first_frame, int count, int rounds, float thresh, int fb_check, float alpha,
+                                  float beta, double* models, long long* stats, int width_org, int height_org, void* stream) {
+  return camera_batch_fit(b, first_frame, count, OFDIS_GM_AFFINE, rounds, thresh, fb_check, alpha, beta, models, stats, width_org,
+                          height_org, stream, 8);
 }
 
 int ofdis_batch_motion_compensate(ofdis_batch* b, int first_frame, int count, const double* models, float thresh, int fb_check,
                                   float alpha, float beta, float* residual, uint8_t* label, int width_org, int height_org,
                                   void* stream) {
-  Finish fin;
-  if (int rc = gm_batch_check(b, fb_check, alpha, beta, width_org, height_org, fin)) return rc;
-  if (!models || (!residual && !label)) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  if (int rc = gm_thresh_check(thresh)) return rc;
-  if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
-  HIPCHK(launch_gmotion_compensate_level(fin.fw, fin.fb_rev, models, count, fin.g, thresh, alpha, beta, residual, label,
-                                         (hipStream_t)stream));
-  return OFDIS_OK;
+  return camera_batch_compensate(b, first_frame, count, models, thresh, fb_check, alpha, beta, residual, label, width_org,
+                                 height_org, stream, 6);
 }
-
-// the 8-parameter projective twins: the same checks, no `model` argument, models [npairs][8]
-static int pm_fit_check(int rounds, float thresh) { return gm_fit_check(OFDIS_GM_AFFINE, rounds, thresh); }
-
-size_t ofdis_projective_motion_work_bytes(int npairs, int width, int height) {
-  return gm_sizes_ok(npairs, width, height) ? projective_work_bytes(npairs, width, height) : 0;
-}
-
-int ofdis_projective_motion(const float* flow, const uint8_t* mask, int npairs, int width, int height, int rounds, float thresh,
-                            double* models, long long* stats, void* work, size_t work_bytes, void* stream) {
-  if (!flow || !models) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  if (int rc = pm_fit_check(rounds, thresh)) return rc;
-  if (!gm_sizes_ok(npairs, width, height)) return fail(OFDIS_ERR_INVALID, kGmSizes);
-  if (int rc = work_check(work, work_bytes, projective_work_bytes(npairs, width, height), "ofdis_projective_motion_work_bytes"))
-    return rc;
-  HIPCHK(launch_projective_frames(flow, mask, npairs, width, height, rounds, thresh, models, stats, work, (hipStream_t)stream));
-  return OFDIS_OK;
-}
-
-int ofdis_projective_compensate(const float* flow, const uint8_t* mask, const double* models, int npairs, int width, int height,
-                                float thresh, float* residual, uint8_t* label, void* stream) {
-  if (!flow || !models || (!residual && !label)) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  if (int rc = gm_thresh_check(thresh)) return rc;
-  if (!gm_sizes_ok(npairs, width, height)) return fail(OFDIS_ERR_INVALID, kGmSizes);
-  HIPCHK(launch_projective_compensate_frames(flow, mask, models, npairs, width, height, thresh, residual, label,
-                                             (hipStream_t)stream));
-  return OFDIS_OK;
-}
-
-int ofdis_batch_projective_motion(ofdis_batch* b, int first_frame, int count, int rounds, float thresh, int fb_check, float alpha,
-                                  float beta, double* models, long long* stats, int width_org, int height_org, void* stream) {
-  Finish fin;
-  if (int rc = gm_batch_check(b, fb_check, alpha, beta, width_org, height_org, fin)) return rc;
-  if (!models) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  if (int rc = pm_fit_check(rounds, thresh)) return rc;
-  if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
-  // records for every pair at the padded size (no original size needs more), held as floats
-  const size_t slab = projective_work_bytes(1, std::min(b->p.width, OFDIS_GM_MAX_SIDE), std::min(b->p.height, OFDIS_GM_MAX_SIDE));
-  if (int rc = dstage(b, {{&b->pm_slab, slab / sizeof(float)}})) return rc;
-  HIPCHK(launch_projective_level(fin.fw, fin.fb_rev, count, fin.g, rounds, thresh, alpha, beta, models, stats, b->pm_slab,
-                                 (hipStream_t)stream));
-  return OFDIS_OK;
-}
-
 int ofdis_batch_projective_compensate(ofdis_batch* b, int first_frame, int count, const double* models, float thresh, int fb_check,
                                       float alpha, float beta, float* residual, uint8_t* label, int width_org, int height_org,
                                       void* stream) {
-  Finish fin;
-  if (int rc = gm_batch_check(b, fb_check, alpha, beta, width_org, height_org, fin)) return rc;
-  if (!models || (!residual && !label)) return fail(OFDIS_ERR_INVALID, "bad arguments");
-  if (int rc = gm_thresh_check(thresh)) return rc;
-  if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
-  HIPCHK(launch_projective_compensate_level(fin.fw, fin.fb_rev, models, count, fin.g, thresh, alpha, beta, residual, label,
-                                            (hipStream_t)stream));
-  return OFDIS_OK;
+  return camera_batch_compensate(b, first_frame, count, models, thresh, fb_check, alpha, beta, residual, label, width_org,
+                                 height_org, stream, 8);
 }
 
 // ------------------------------------------------------------------------------------ video stabilisation (ofdis_stabilize.hip)

@@ -8,8 +8,10 @@ compare the kernels against `global_motion_ref` and `motion_compensate_ref` bit 
     residual, label = gmotion.motion_compensate_ref(flow, models, mask, thresh=1.0)
     foreground = label == gmotion.GM_OUTLIER
 
-The 8-parameter projective models (ofdis_projective_motion, ofdis_projective_compensate) are stated at the end of the file:
-`projective_motion_ref`, `projective_compensate_ref`, `sums23`, `model_flow8`, `homography`.
+The 8-parameter projective models (ofdis_projective_motion, ofdis_projective_compensate) share the round loop, the
+compensation, the term table of the sums, the residual and the model field with the 6-parameter ones, switched on the model's
+width; their sums and solve (`sums23`, `solve8`) are stated at the end of the file, with `projective_motion_ref`,
+`projective_compensate_ref` and `homography`.
 """
 import numpy as np
 
@@ -38,20 +40,27 @@ def valid(flow, mask=None):
     return ok
 
 
+def _terms(flow, sel, perm, nsums):
+    """the per-pixel terms of the first `nsums` sums (12 or PM_NSUMS) over the pixels `sel`, in the record order: int64 arrays"""
+    h, w = sel.shape
+    X, Y = coords(w, h)
+    X, Y = X[sel], Y[sel]
+    q = np.rint(flow[sel] * _f32(256.0)).astype(np.int64)   # (the product is exact; np.rint rounds to nearest even, like rintf)
+    qu, qv = q[:, 0], q[:, 1]
+    if perm is not None:
+        X, Y, qu, qv = X[perm], Y[perm], qu[perm], qv[perm]
+    XX, XY, YY = X * X, X * Y, Y * Y
+    terms = [np.ones_like(X), X, Y, XX, XY, YY, qu, X * qu, Y * qu, qv, X * qv, Y * qv]
+    if nsums > 12:
+        terms += [XX * X, XX * Y, X * YY, YY * Y, XX * XX, XX * XY, XX * YY, XY * YY, YY * YY, XX * qu + XY * qv, XY * qu + YY * qv]
+    return terms
+
+
 def sums(flow, sel, perm=None):
     """The twelve sums over the pixels `sel` (bool [h][w], all valid) as Python ints, in the record order n, SX, SY, SXX, SXY,
     SYY, Squ, SXqu, SYqu, Sqv, SXqv, SYqv.  perm: a permutation of the selected pixels applied before the summation (integer
     addition is associative: the tests use it to show that the order cannot matter)."""
-    h, w = sel.shape
-    X, Y = coords(w, h)
-    X, Y = X[sel], Y[sel]
-    uv = flow[sel]
-    q = np.rint(uv * _f32(256.0)).astype(np.int64)   # (the product is exact; np.rint rounds to nearest even, like rintf)
-    qu, qv = q[:, 0], q[:, 1]
-    if perm is not None:
-        X, Y, qu, qv = X[perm], Y[perm], qu[perm], qv[perm]
-    terms = [np.ones_like(X), X, Y, X * X, X * Y, Y * Y, qu, X * qu, Y * qu, qv, X * qv, Y * qv]
-    return [int(t.sum(dtype=np.int64)) for t in terms]
+    return [int(t.sum(dtype=np.int64)) for t in _terms(flow, sel, perm, 12)]
 
 
 def solve(s, model):
@@ -83,7 +92,7 @@ def solve(s, model):
 
 
 def residual(flow, a):
-    """flow [h][w][2] float32 minus the model a [6] (float64, converted to float32 first): [h][w][2] float32"""
+    """flow [h][w][2] float32 minus the model a [6] or [8] (float64, converted to float32 first): [h][w][2] float32"""
     h, w = flow.shape[:2]
     X, Y = coords(w, h)
     with np.errstate(over="ignore", invalid="ignore"):
@@ -91,6 +100,9 @@ def residual(flow, a):
         xc, yc = X.astype(_f32) * _f32(0.5), Y.astype(_f32) * _f32(0.5)
         mu = (af[0] + af[1] * xc) + af[2] * yc
         mv = (af[3] + af[4] * xc) + af[5] * yc
+        if af.size == 8:
+            p = af[6] * xc + af[7] * yc
+            mu, mv = mu + p * xc, mv + p * yc
         return np.stack([flow[..., 0] - mu, flow[..., 1] - mv], axis=-1)
 
 
@@ -119,15 +131,10 @@ def _pairs(flow, mask):
     return flow, mask
 
 
-def global_motion_ref(flow, mask=None, model=GM_AFFINE, rounds=3, thresh=1.0, shuffle=None):
-    """flow [npairs][h][w][2] float32, mask [npairs][h][w] uint8 or None -> (models [npairs][6] float64, stats [npairs][3]
-    int64: |S_0|, the size of the last set used, the status), what ofdis_global_motion writes.  shuffle: a
-    numpy.random.Generator that permutes the pixels of every sum (the result must not change)."""
-    _check(rounds, thresh)
-    if model not in (GM_TRANSLATION_ONLY, GM_AFFINE):
-        raise ValueError("model must be GM_TRANSLATION_ONLY or GM_AFFINE")
+def _fit_ref(nparam, flow, mask, model, rounds, thresh, shuffle):
+    """the rounds of a fit with models of nparam doubles: (models [npairs][nparam] float64, stats [npairs][3] int64)"""
     flow, mask = _pairs(flow, mask)
-    models = np.zeros((flow.shape[0], 6), np.float64)
+    models = np.zeros((flow.shape[0], nparam), np.float64)
     stats = np.zeros((flow.shape[0], 3), np.int64)
     for k in range(flow.shape[0]):
         ok = valid(flow[k], None if mask is None else mask[k])
@@ -135,22 +142,21 @@ def global_motion_ref(flow, mask=None, model=GM_AFFINE, rounds=3, thresh=1.0, sh
         for r in range(rounds):
             if r > 0:
                 sel = near(residual(flow[k], models[k]), ok, thresh)
-            s = sums(flow[k], sel, None if shuffle is None else shuffle.permutation(int(sel.sum())))
+            perm = None if shuffle is None else shuffle.permutation(int(sel.sum()))
+            s = sums(flow[k], sel, perm) if nparam == 6 else sums23(flow[k], sel, perm)
             if r > 0 and s[0] == 0:
-                break   # the model, set size and status of round r-1 stay
-            models[k], status = solve(s, model)
+                break   # the model, set size and status (or count) of round r-1 stay
+            models[k], status = solve(s, model) if nparam == 6 else solve8(s)
             if r == 0:
                 stats[k, 0] = s[0]
             stats[k, 1:] = s[0], status
     return models, stats
 
 
-def motion_compensate_ref(flow, models, mask=None, thresh=1.0):
-    """flow [npairs][h][w][2] float32, models [npairs][6] float64 -> (residual [npairs][h][w][2] float32, label [npairs][h][w]
-    uint8), what ofdis_motion_compensate writes."""
+def _compensate_ref(nparam, flow, models, mask, thresh):
     _check(1, thresh)
     flow, mask = _pairs(flow, mask)
-    models = np.asarray(models, np.float64).reshape(flow.shape[0], 6)
+    models = np.asarray(models, np.float64).reshape(flow.shape[0], nparam)
     res = np.empty_like(flow)
     label = np.empty(flow.shape[:3], np.uint8)
     for k in range(flow.shape[0]):
@@ -160,13 +166,32 @@ def motion_compensate_ref(flow, models, mask=None, thresh=1.0):
     return res, label
 
 
+def global_motion_ref(flow, mask=None, model=GM_AFFINE, rounds=3, thresh=1.0, shuffle=None):
+    """flow [npairs][h][w][2] float32, mask [npairs][h][w] uint8 or None -> (models [npairs][6] float64, stats [npairs][3]
+    int64: |S_0|, the size of the last set used, the status), what ofdis_global_motion writes.  shuffle: a
+    numpy.random.Generator that permutes the pixels of every sum (the result must not change)."""
+    _check(rounds, thresh)
+    if model not in (GM_TRANSLATION_ONLY, GM_AFFINE):
+        raise ValueError("model must be GM_TRANSLATION_ONLY or GM_AFFINE")
+    return _fit_ref(6, flow, mask, model, rounds, thresh, shuffle)
+
+
+def motion_compensate_ref(flow, models, mask=None, thresh=1.0):
+    """flow [npairs][h][w][2] float32, models [npairs][6] float64 -> (residual [npairs][h][w][2] float32, label [npairs][h][w]
+    uint8), what ofdis_motion_compensate writes."""
+    return _compensate_ref(6, flow, models, mask, thresh)
+
+
 def model_flow(a, w, h):
-    """the model's flow field [h][w][2] in float64: u = a0 + a1*(x - cx) + a2*(y - cy), v likewise (for users and tests; the
-    kernels use `residual`)"""
+    """the model's flow field [h][w][2] in float64: u = a0 + a1*(x - cx) + a2*(y - cy), v likewise, and for a [8] the quadratic
+    terms stated below (for users and tests; the kernels use `residual`)"""
     ys, xs = np.mgrid[0:h, 0:w].astype(np.float64)
     xs -= (w - 1) / 2.0
     ys -= (h - 1) / 2.0
-    return np.stack([a[0] + a[1] * xs + a[2] * ys, a[3] + a[4] * xs + a[5] * ys], axis=-1)
+    if len(a) == 6:
+        return np.stack([a[0] + a[1] * xs + a[2] * ys, a[3] + a[4] * xs + a[5] * ys], axis=-1)
+    p = a[6] * xs + a[7] * ys
+    return np.stack([a[0] + a[1] * xs + a[2] * ys + p * xs, a[3] + a[4] * xs + a[5] * ys + p * ys], axis=-1)
 
 
 # ------------------------------------------------------------------ 8-parameter projective models (ofdis_projective_motion)
@@ -199,21 +224,8 @@ def sums23(flow, sel, perm=None, chunk=PM_BLOCK_PIXELS):
     (a workgroup's 1024) are summed in int64, as the accumulate kernel does, and the chunks are added as Python ints, as the
     solve kernel's 128-bit sums are.  perm: as in `sums`."""
     assert chunk <= PM_BLOCK_PIXELS
-    h, w = sel.shape
-    X, Y = coords(w, h)
-    X, Y = X[sel], Y[sel]
-    q = np.rint(flow[sel] * _f32(256.0)).astype(np.int64)
-    qu, qv = q[:, 0], q[:, 1]
-    if perm is not None:
-        X, Y, qu, qv = X[perm], Y[perm], qu[perm], qv[perm]
-    XX, XY, YY = X * X, X * Y, Y * Y
-    terms = [np.ones_like(X), X, Y, XX, XY, YY, qu, X * qu, Y * qu, qv, X * qv, Y * qv,
-             XX * X, XX * Y, X * YY, YY * Y, XX * XX, XX * XY, XX * YY, XY * YY, YY * YY, XX * qu + XY * qv, XY * qu + YY * qv]
-    out = [0] * PM_NSUMS
-    for c0 in range(0, len(X), chunk):
-        for k, t in enumerate(terms):
-            out[k] += int(t[c0:c0 + chunk].sum(dtype=np.int64))
-    return out
+    return [sum(int(t[c0:c0 + chunk].sum(dtype=np.int64)) for c0 in range(0, len(t), chunk))
+            for t in _terms(flow, sel, perm, PM_NSUMS)]
 
 
 def normal8(s):
@@ -282,17 +294,8 @@ def pivot_ratios(s):
     return [dk / nk if nk else 0.0 for dk, nk in zip(d, diag)]
 
 
-def residual8(flow, a):
-    """flow [h][w][2] float32 minus the 8-parameter model a (float64, converted to float32 first): [h][w][2] float32"""
-    h, w = flow.shape[:2]
-    X, Y = coords(w, h)
-    with np.errstate(over="ignore", invalid="ignore"):
-        af = np.asarray(a, np.float64).astype(_f32)
-        xc, yc = X.astype(_f32) * _f32(0.5), Y.astype(_f32) * _f32(0.5)
-        p = af[6] * xc + af[7] * yc
-        mu = ((af[0] + af[1] * xc) + af[2] * yc) + p * xc
-        mv = ((af[3] + af[4] * xc) + af[5] * yc) + p * yc
-        return np.stack([flow[..., 0] - mu, flow[..., 1] - mv], axis=-1)
+residual8 = residual      # (the width of the model decides)
+model_flow8 = model_flow
 
 
 def projective_motion_ref(flow, mask=None, rounds=3, thresh=1.0, shuffle=None):
@@ -300,47 +303,13 @@ def projective_motion_ref(flow, mask=None, rounds=3, thresh=1.0, shuffle=None):
     int64: |S_0|, the size of the last set used, the number of parameters solved: 8, 6, 2 or 0), what ofdis_projective_motion
     writes.  shuffle: as in global_motion_ref."""
     _check(rounds, thresh)
-    flow, mask = _pairs(flow, mask)
-    models = np.zeros((flow.shape[0], 8), np.float64)
-    stats = np.zeros((flow.shape[0], 3), np.int64)
-    for k in range(flow.shape[0]):
-        ok = valid(flow[k], None if mask is None else mask[k])
-        sel = ok
-        for r in range(rounds):
-            if r > 0:
-                sel = near(residual8(flow[k], models[k]), ok, thresh)
-            s = sums23(flow[k], sel, None if shuffle is None else shuffle.permutation(int(sel.sum())))
-            if r > 0 and s[0] == 0:
-                break   # the model, set size and count of round r-1 stay
-            models[k], count = solve8(s)
-            if r == 0:
-                stats[k, 0] = s[0]
-            stats[k, 1:] = s[0], count
-    return models, stats
+    return _fit_ref(8, flow, mask, None, rounds, thresh, shuffle)
 
 
 def projective_compensate_ref(flow, models, mask=None, thresh=1.0):
     """flow [npairs][h][w][2] float32, models [npairs][8] float64 -> (residual [npairs][h][w][2] float32, label [npairs][h][w]
     uint8), what ofdis_projective_compensate writes."""
-    _check(1, thresh)
-    flow, mask = _pairs(flow, mask)
-    models = np.asarray(models, np.float64).reshape(flow.shape[0], 8)
-    res = np.empty_like(flow)
-    label = np.empty(flow.shape[:3], np.uint8)
-    for k in range(flow.shape[0]):
-        ok = valid(flow[k], None if mask is None else mask[k])
-        res[k] = residual8(flow[k], models[k])
-        label[k] = np.where(near(res[k], ok, thresh), GM_INLIER, np.where(ok, GM_OUTLIER, GM_INVALID))
-    return res, label
-
-
-def model_flow8(a, w, h):
-    """the 8-parameter model's flow field [h][w][2] in float64 (for users and tests; the kernels use `residual8`)"""
-    ys, xs = np.mgrid[0:h, 0:w].astype(np.float64)
-    xs -= (w - 1) / 2.0
-    ys -= (h - 1) / 2.0
-    p = a[6] * xs + a[7] * ys
-    return np.stack([a[0] + a[1] * xs + a[2] * ys + p * xs, a[3] + a[4] * xs + a[5] * ys + p * ys], axis=-1)
+    return _compensate_ref(8, flow, models, mask, thresh)
 
 
 def homography(a):

@@ -5,13 +5,14 @@ The standalone kernels are compared bit for bit -- models as raw 64-bit patterns
 label -- with of_dis_amd/gmotion.py, the header's definition in numpy; the fused kernels bit for bit with the standalone ones
 applied to the outputs of ofdis_batch_upsample_bidir (fb_check = 1) or ofdis_batch_upsample_frames (fb_check = 0).  Conditions
 on the generated inputs are checked on the restatement or the standalone result, never on the kernel under test."""
-import functools
 import math
 
 import numpy as np
 import pytest
 
+import camera_cases as cases
 import gen_synth
+from camera_cases import _keep_only, _random_case, assert_compensated_equal, assert_fit_equal
 from of_dis_amd import gmotion
 from of_dis_amd.gmotion import (GM_AFFINE, GM_EMPTY, GM_INLIER, GM_INVALID, GM_OK_AFFINE, GM_OUTLIER, GM_TRANSLATION,
                                 GM_TRANSLATION_ONLY, global_motion_ref, motion_compensate_ref)
@@ -22,56 +23,12 @@ pytestmark = pytest.mark.gpu
 _f32 = np.float32
 
 
-def assert_fit_equal(got, want, what):
-    assert_same_bits(got[0], want[0], what + ", models")
-    assert_same_bits(got[1], want[1], what + ", stats")
-
-
-def assert_compensated_equal(got, want, what):
-    assert_same_bits(got[0], want[0], what + ", residual")
-    assert_same_bits(got[1], want[1], what + ", label")
-
-
 # ------------------------------------------------------------------ 1. standalone kernels against the restatement
 # (300, 70): several workgroups per pair, so the slab sum is real; (8192, 2): |X| at its bound
 SIZES = [(37, 11), (64, 16), (1, 9), (13, 1), (1, 1), (6, 5), (33, 7), (257, 3), (300, 70), (8192, 2)]
 # (model, rounds, thresh)
 FITS = [(GM_AFFINE, 1, 1.0), (GM_AFFINE, 2, 0.5), (GM_AFFINE, 4, 1.0), (GM_AFFINE, 4, 1e-3), (GM_TRANSLATION_ONLY, 1, 0.5),
         (GM_TRANSLATION_ONLY, 2, 1.0), (GM_TRANSLATION_ONLY, 4, 0.5), (GM_TRANSLATION_ONLY, 2, 1e-3)]
-JUST_ABOVE = np.nextafter(_f32(4096.0), _f32(np.inf))
-
-
-@functools.lru_cache(maxsize=None)
-def _random_case(n, w, h, kind):
-    """npairs = n.  "smooth": an affine camera flow of a few pixels per pair plus noise of 0.3 px, a fifth of the pixels with
-    flows of 3 px of their own (what the gate removes) and some that stay put.  "wild": the same with large, infinite, NaN
-    (default, with a payload, negative), image-sized values and values of exactly +-4096 and just above mixed in, as _random_case
-    of tests/test_gpu_tfilter.py mixes them.  Masks with all three codes."""
-    rng = np.random.default_rng(w * 1000 + h * 10 + 100 * n + (5 if kind == "wild" else 0))
-    F = np.empty((n, h, w, 2), _f32)
-    for k in range(n):
-        a = rng.normal(0.0, 1.0, 6) * np.array([3.0, 0.02, 0.02, 3.0, 0.02, 0.02])
-        F[k] = (gmotion.model_flow(a, w, h) + rng.normal(0.0, 0.3, (h, w, 2))).astype(_f32)
-    own = rng.random((n, h, w)) < 0.2
-    F[own] = (rng.standard_normal((int(own.sum()), 2)) * 3).astype(_f32)
-    F[rng.random((n, h, w)) < 0.05] = 0.0
-    if kind == "wild":
-        pick = rng.random((n, h, w, 2))
-        F[pick < 0.04] = (rng.standard_normal(int((pick < 0.04).sum())) * 1e4).astype(_f32)
-        F[(pick >= 0.04) & (pick < 0.05)] = np.inf
-        F[(pick >= 0.05) & (pick < 0.06)] = -np.inf
-        F[(pick >= 0.06) & (pick < 0.07)] = np.nan
-        F[(pick >= 0.07) & (pick < 0.08)] = np.array([0x7FC12345], np.uint32).view(_f32)[0]
-        F[(pick >= 0.08) & (pick < 0.09)] = np.array([0xFFC00001], np.uint32).view(_f32)[0]
-        sized = (pick >= 0.09) & (pick < 0.10)
-        F[sized] = (rng.uniform(-2, 2, int(sized.sum())) * max(w, h)).astype(_f32)
-        F[(pick >= 0.130) & (pick < 0.133)] = 4096.0      # (rare: a valid flow of 4096 px pulls the whole fit)
-        F[(pick >= 0.133) & (pick < 0.136)] = -4096.0
-        F[(pick >= 0.14) & (pick < 0.15)] = JUST_ABOVE
-        F[(pick >= 0.15) & (pick < 0.16)] = -JUST_ABOVE
-    M = rng.integers(0, 3, (n, h, w), dtype=np.uint8)
-    M[rng.random((n, h, w)) < 0.5] = 0
-    return F, M
 
 
 @pytest.mark.parametrize("w,h", SIZES, ids=[f"{w}x{h}" for w, h in SIZES])
@@ -95,41 +52,11 @@ def test_standalone_matches_the_definition(gpu, w, h, kind):
 
 
 def test_either_output_alone_and_the_residual_in_place(gpu):
-    flow, mask = _random_case(3, 37, 11, "wild")
-    models, _ = global_motion_ref(flow, mask, rounds=2, thresh=1.0)
-    want = motion_compensate_ref(flow, models, mask, thresh=1.0)
-    assert np.isnan(want[0]).any() and np.isinf(want[0]).any() and len(np.unique(want[1])) == 3
-    res, none = gpu.motion_compensate(flow, models, mask, thresh=1.0, label=False)
-    assert none is None
-    assert_same_bits(res, want[0], "label = NULL")
-    none, label = gpu.motion_compensate(flow, models, mask, thresh=1.0, residual=False)
-    assert none is None
-    assert_same_bits(label, want[1], "residual = NULL")
-    for w, h in ((37, 11), (64, 16)):   # 4-byte and 16-byte stores over the array they were read from
-        flow, mask = _random_case(3, w, h, "wild")
-        models, _ = global_motion_ref(flow, mask, rounds=2, thresh=1.0)
-        assert_compensated_equal(gpu.motion_compensate(flow, models, mask, thresh=1.0, in_place=True),
-                                 motion_compensate_ref(flow, models, mask, thresh=1.0), f"residual aliases flow, {w}x{h}")
-    # stats = NULL: the same models
-    flow, mask = _random_case(3, 64, 16, "smooth")
-    npairs, h, w = flow.shape[:3]
-    df, dm, dmod = gpu.Dev(flow), gpu.Dev(mask), gpu.Dev(nbytes=npairs * 48)
-    wb = gpu.lib().ofdis_global_motion_work_bytes(npairs, w, h)
-    dwork = gpu.Dev(nbytes=wb)
-    gpu.check(gpu.lib().ofdis_global_motion(df.ptr, dm.ptr, npairs, w, h, GM_AFFINE, 3, 1.0, dmod.ptr, None, dwork.ptr, wb, None))
-    gpu.check(gpu.lib().ofdis_sync(None))
-    assert_same_bits(dmod.get((npairs, 6), np.float64), global_motion_ref(flow, mask, rounds=3, thresh=1.0)[0], "stats = NULL")
+    cases.check_either_output_alone_in_place_and_no_stats(gpu, 6)
 
 
 def test_more_pairs_than_xcds(gpu):
-    """10 pairs: the pair-to-XCD mapping with its padded last group, every pair with its own records and its own model"""
-    for w, h in ((33, 7), (300, 70)):
-        flow, mask = _random_case(10, w, h, "smooth")
-        want = global_motion_ref(flow, mask, rounds=3, thresh=1.0)
-        assert len({m.tobytes() for m in want[0]}) == 10
-        assert_fit_equal(gpu.global_motion(flow, mask, rounds=3, thresh=1.0), want, f"10 pairs {w}x{h}")
-        assert_compensated_equal(gpu.motion_compensate(flow, want[0], mask, thresh=1.0),
-                                 motion_compensate_ref(flow, want[0], mask, thresh=1.0), f"10 pairs {w}x{h}")
+    cases.check_more_pairs_than_xcds(gpu, 6)
 
 
 def test_the_largest_products(gpu):
@@ -144,12 +71,6 @@ def test_the_largest_products(gpu):
         assert_fit_equal(gpu.global_motion(flow, None, model=model, rounds=2, thresh=1.0), want, f"model {model}")
     s = gmotion.sums(flow[1], np.ones((h, w), bool))
     assert s[7] == 2 * sum(abs(2 * x - (w - 1)) for x in range(w)) << 20 > 1 << 45
-
-
-def _keep_only(shape, sel):
-    mask = np.full(shape, 1, np.uint8)
-    mask[sel] = 0
-    return mask
 
 
 def test_degenerate_sets(gpu):
@@ -186,25 +107,7 @@ def test_degenerate_sets(gpu):
 
 @pytest.mark.parametrize("w,h", [(64, 16), (37, 11), (6, 5)], ids=["64x16", "37x11", "6x5"])
 def test_unaligned_outputs_take_narrower_stores_with_the_same_bytes(gpu, w, h):
-    """the residual one element (4 bytes) and the labels one byte into their buffers: the same bytes as the aligned call, and the
-    guard bytes around both stay"""
-    npairs = 3
-    flow, mask = _random_case(npairs, w, h, "wild")
-    models, _ = global_motion_ref(flow, mask, rounds=2, thresh=1.0)
-    want = motion_compensate_ref(flow, models, mask, thresh=1.0)
-    rbytes, lbytes = flow.nbytes, npairs * h * w
-    devs = [gpu.Dev(x) for x in (flow, mask, models)]
-    for roff, loff in ((260, 257), (264, 258), (272, 260)):   # residual 4 / 8 / 16-byte aligned, labels 1 / 2 / 4-byte aligned
-        dr = gpu.Dev(np.full(rbytes + 2 * roff, 0xAB, np.uint8))
-        dl = gpu.Dev(np.full(lbytes + 2 * loff, 0xAB, np.uint8))
-        gpu.check(gpu.lib().ofdis_motion_compensate(devs[0].ptr, devs[1].ptr, devs[2].ptr, npairs, w, h, 1.0, dr.ptr + roff,
-                                                    dl.ptr + loff, None))
-        gpu.check(gpu.lib().ofdis_sync(None))
-        r, l = dr.get((rbytes + 2 * roff,), np.uint8), dl.get((lbytes + 2 * loff,), np.uint8)
-        for buf, off, n in ((r, roff, rbytes), (l, loff, lbytes)):
-            assert (buf[:off] == 0xAB).all() and (buf[off + n:] == 0xAB).all(), (roff, loff)
-        assert_same_bits(r[roff:roff + rbytes].copy().view(_f32).reshape(flow.shape), want[0], f"residual at offset {roff}")
-        assert_same_bits(l[loff:loff + lbytes].reshape(npairs, h, w), want[1], f"labels at offset {loff}")
+    cases.check_unaligned_outputs(gpu, 6, w, h)
 
 
 # ------------------------------------------------------------------ 2. the block scene
@@ -248,47 +151,8 @@ FUSED_CASES = [
 
 @pytest.mark.parametrize("kind,noc,opp,w,h,n,first,count,pipeline,contract,alpha,beta", FUSED_CASES)
 def test_fused_matches_standalone(gpu, kind, noc, opp, w, h, n, first, count, pipeline, contract, alpha, beta):
-    """fb_check = 0 against the standalone calls on upsample_frames' output with mask NULL; fb_check = 1 (contexts with the
-    reverse direction) against them on out_fw and mask_fw of upsample_bidir"""
-    clip = smooth_clip(w, h, noc, n + 1)
-    b, devs = run_context(gpu, clip, kind, opp, contract, pipeline)
-    fused = {}
-    try:
-        bytes_before = b.device_bytes()
-        for fb in ((0, 1) if kind != "plain" else (0,)):
-            for model, rounds, thresh in FUSED_FITS:
-                fit = b.global_motion(w, h, model=model, rounds=rounds, thresh=thresh, fb_check=fb, first=first, count=count,
-                                      alpha=alpha, beta=beta)
-                comp = b.motion_compensate(fit[0], w, h, thresh=thresh, fb_check=fb, first=first, count=count, alpha=alpha,
-                                           beta=beta)
-                fused[fb, model, rounds, thresh] = fit, comp
-        # the slab belongs to the context: allocated once, counted from then on
-        slab = b.device_bytes() - bytes_before
-        assert slab >= gpu.lib().ofdis_global_motion_work_bytes(n, w, h) > 0
-        plain = b.upsample_frames(first, count, w, h)
-        fw, mf = b.upsample_bidir(w, h, alpha, beta, first=first, count=count, outputs=(True, False, True, False))[0::2] \
-            if kind != "plain" else (None, None)
-        assert b.device_bytes() - bytes_before == slab
-    finally:
-        b.close()
-    for (fb, model, rounds, thresh), (fit, comp) in fused.items():
-        flow, mask = (fw, mf) if fb else (plain, None)
-        what = f"fb_check {fb}, model {model}, rounds {rounds}, thresh {thresh}"
-        standalone = gpu.global_motion(flow, mask, model=model, rounds=rounds, thresh=thresh)
-        assert_fit_equal(fit, standalone, "fused vs standalone, " + what)
-        assert_compensated_equal(comp, gpu.motion_compensate(flow, standalone[0], mask, thresh=thresh),
-                                 "fused vs standalone, " + what)
-        if count <= 3:
-            want = global_motion_ref(flow, mask, model=model, rounds=rounds, thresh=thresh)
-            assert_fit_equal(standalone, want, "standalone vs the definition, " + what)
-        if not (fb and alpha == 0.0 and beta == 0.0):   # something was fitted in the comparison
-            assert (standalone[1][:, 0] > 0).all()
-    if kind != "plain":
-        assert_same_bits(fw, plain, "upsample_bidir's forward flow is upsample_frames'")
-        if alpha == 0.0 and beta == 0.0:   # (a test nothing but an exact round trip passes: most pixels are masked here)
-            assert (mf != 0).mean() > 0.5
-        else:
-            assert (mf != 0).mean() < 0.5
+    fits = [dict(model=model, rounds=rounds, thresh=thresh) for model, rounds, thresh in FUSED_FITS]
+    cases.check_fused_matches_standalone(gpu, 6, fits, kind, noc, opp, w, h, n, first, count, pipeline, contract, alpha, beta)
 
 
 def test_fused_into_device_buffers_on_a_stream(gpu):

@@ -2,17 +2,18 @@
 ofdis_projective_compensate on materialised arrays, ofdis_batch_projective_motion / ofdis_batch_projective_compensate straight
 from the level flows of a context, ofdis_track_select_projective).
 
-As tests/test_gpu_gmotion.py does for the 6-parameter calls: the standalone kernels are compared bit for bit -- models as raw
-64-bit patterns, stats, residual (NaN payloads included) and label -- with of_dis_amd/gmotion.py, the header's definition in
-numpy; the fused kernels bit for bit with the standalone ones applied to the outputs of ofdis_batch_upsample_bidir (fb_check =
-1) or ofdis_batch_upsample_frames (fb_check = 0).  Conditions on the generated inputs are checked on the restatement or the
-standalone result, never on the kernel under test."""
-import functools
-
+As tests/test_gpu_gmotion.py does for the 6-parameter calls, with the cases and the checks both orders take from
+tests/camera_cases.py: the standalone kernels are compared bit for bit -- models as raw 64-bit patterns, stats, residual (NaN
+payloads included) and label -- with of_dis_amd/gmotion.py, the header's definition in numpy; the fused kernels bit for bit with
+the standalone ones applied to the outputs of ofdis_batch_upsample_bidir (fb_check = 1) or ofdis_batch_upsample_frames (fb_check
+= 0).  Conditions on the generated inputs are checked on the restatement or the standalone result, never on the kernel under
+test."""
 import numpy as np
 import pytest
 
+import camera_cases as cases
 import gen_synth
+from camera_cases import _keep_only, _random_case, assert_compensated_equal, assert_fit_equal
 from of_dis_amd import gmotion, tracking
 from of_dis_amd.gmotion import (GM_INLIER, GM_INVALID, GM_OUTLIER, global_motion_ref, motion_compensate_ref,
                                 projective_compensate_ref, projective_motion_ref)
@@ -23,55 +24,12 @@ pytestmark = pytest.mark.gpu
 _f32 = np.float32
 
 
-def assert_fit_equal(got, want, what):
-    assert_same_bits(got[0], want[0], what + ", models")
-    assert_same_bits(got[1], want[1], what + ", stats")
-
-
-def assert_compensated_equal(got, want, what):
-    assert_same_bits(got[0], want[0], what + ", residual")
-    assert_same_bits(got[1], want[1], what + ", label")
-
-
 # ------------------------------------------------------------------ 1. standalone kernels against the restatement
 # 1x1, 13x1, 1x9: the fallbacks; 2x2: the smallest full-rank set; 300x70: several records per pair; 8192x2: the pair's sums need
 # 128 bits and a workgroup's come near the int64 bound
 SIZES = [(1, 1), (13, 1), (1, 9), (2, 2), (6, 5), (37, 11), (64, 16), (257, 3), (300, 70), (8192, 2)]
 # (rounds, thresh): rounds 1, 2, 4 and thresh 1.0, 0.5, 1e-3
 FITS = [(1, 1.0), (2, 0.5), (4, 1.0), (4, 1e-3), (2, 1e-3), (1, 0.5)]
-JUST_ABOVE = np.nextafter(_f32(4096.0), _f32(np.inf))
-
-
-@functools.lru_cache(maxsize=None)
-def _random_case(n, w, h, kind):
-    """the "smooth" and "wild" generators of tests/test_gpu_gmotion.py (copied): an affine camera flow of a few pixels per pair
-    plus noise, a fifth of the pixels with flows of their own, some that stay put; "wild": large, infinite, NaN, image-sized
-    values and values of exactly +-4096 and just above mixed in.  Masks with all three codes."""
-    rng = np.random.default_rng(w * 1000 + h * 10 + 100 * n + (5 if kind == "wild" else 0))
-    F = np.empty((n, h, w, 2), _f32)
-    for k in range(n):
-        a = rng.normal(0.0, 1.0, 6) * np.array([3.0, 0.02, 0.02, 3.0, 0.02, 0.02])
-        F[k] = (gmotion.model_flow(a, w, h) + rng.normal(0.0, 0.3, (h, w, 2))).astype(_f32)
-    own = rng.random((n, h, w)) < 0.2
-    F[own] = (rng.standard_normal((int(own.sum()), 2)) * 3).astype(_f32)
-    F[rng.random((n, h, w)) < 0.05] = 0.0
-    if kind == "wild":
-        pick = rng.random((n, h, w, 2))
-        F[pick < 0.04] = (rng.standard_normal(int((pick < 0.04).sum())) * 1e4).astype(_f32)
-        F[(pick >= 0.04) & (pick < 0.05)] = np.inf
-        F[(pick >= 0.05) & (pick < 0.06)] = -np.inf
-        F[(pick >= 0.06) & (pick < 0.07)] = np.nan
-        F[(pick >= 0.07) & (pick < 0.08)] = np.array([0x7FC12345], np.uint32).view(_f32)[0]
-        F[(pick >= 0.08) & (pick < 0.09)] = np.array([0xFFC00001], np.uint32).view(_f32)[0]
-        sized = (pick >= 0.09) & (pick < 0.10)
-        F[sized] = (rng.uniform(-2, 2, int(sized.sum())) * max(w, h)).astype(_f32)
-        F[(pick >= 0.130) & (pick < 0.133)] = 4096.0
-        F[(pick >= 0.133) & (pick < 0.136)] = -4096.0
-        F[(pick >= 0.14) & (pick < 0.15)] = JUST_ABOVE
-        F[(pick >= 0.15) & (pick < 0.16)] = -JUST_ABOVE
-    M = rng.integers(0, 3, (n, h, w), dtype=np.uint8)
-    M[rng.random((n, h, w)) < 0.5] = 0
-    return F, M
 
 
 @pytest.mark.parametrize("w,h", SIZES, ids=[f"{w}x{h}" for w, h in SIZES])
@@ -114,12 +72,6 @@ def test_the_pair_sums_need_128_bits_and_the_largest_right_hand_sides(gpu):
                              projective_compensate_ref(flow, want[0], None, thresh=1.0), "largest products")
 
 
-def _keep_only(shape, sel):
-    mask = np.full(shape, 1, np.uint8)
-    mask[sel] = 0
-    return mask
-
-
 def test_degenerate_sets(gpu):
     """the degenerate sets of tests/test_gpu_gmotion.py::test_degenerate_sets as five pairs of ONE call: a row, a diagonal, a single
     pixel, nothing, everything -- the counts are the restatement's"""
@@ -153,56 +105,16 @@ def test_degenerate_sets(gpu):
 
 
 def test_more_pairs_than_xcds(gpu):
-    for w, h in ((33, 7), (300, 70)):
-        flow, mask = _random_case(10, w, h, "smooth")
-        want = projective_motion_ref(flow, mask, rounds=3, thresh=1.0)
-        assert len({m.tobytes() for m in want[0]}) == 10 and (want[1][:, 2] == 8).sum() >= 5
-        assert_fit_equal(gpu.projective_motion(flow, mask, rounds=3, thresh=1.0), want, f"10 pairs {w}x{h}")
-        assert_compensated_equal(gpu.projective_compensate(flow, want[0], mask, thresh=1.0),
-                                 projective_compensate_ref(flow, want[0], mask, thresh=1.0), f"10 pairs {w}x{h}")
+    cases.check_more_pairs_than_xcds(gpu, 8)
 
 
 @pytest.mark.parametrize("w,h", [(64, 16), (37, 11), (6, 5)], ids=["64x16", "37x11", "6x5"])
 def test_unaligned_outputs_take_narrower_stores_with_the_same_bytes(gpu, w, h):
-    npairs = 3
-    flow, mask = _random_case(npairs, w, h, "wild")
-    models, _ = projective_motion_ref(flow, mask, rounds=2, thresh=1.0)
-    want = projective_compensate_ref(flow, models, mask, thresh=1.0)
-    rbytes, lbytes = flow.nbytes, npairs * h * w
-    devs = [gpu.Dev(x) for x in (flow, mask, models)]
-    for roff, loff in ((260, 257), (264, 258), (272, 260)):   # residual 4 / 8 / 16-byte aligned, labels 1 / 2 / 4-byte aligned
-        dr = gpu.Dev(np.full(rbytes + 2 * roff, 0xAB, np.uint8))
-        dl = gpu.Dev(np.full(lbytes + 2 * loff, 0xAB, np.uint8))
-        gpu.check(gpu.lib().ofdis_projective_compensate(devs[0].ptr, devs[1].ptr, devs[2].ptr, npairs, w, h, 1.0, dr.ptr + roff,
-                                                        dl.ptr + loff, None))
-        gpu.check(gpu.lib().ofdis_sync(None))
-        r, l = dr.get((rbytes + 2 * roff,), np.uint8), dl.get((lbytes + 2 * loff,), np.uint8)
-        for buf, off, n in ((r, roff, rbytes), (l, loff, lbytes)):
-            assert (buf[:off] == 0xAB).all() and (buf[off + n:] == 0xAB).all(), (roff, loff)
-        assert_same_bits(r[roff:roff + rbytes].copy().view(_f32).reshape(flow.shape), want[0], f"residual at offset {roff}")
-        assert_same_bits(l[loff:loff + lbytes].reshape(npairs, h, w), want[1], f"labels at offset {loff}")
+    cases.check_unaligned_outputs(gpu, 8, w, h)
 
 
 def test_either_output_alone_the_residual_in_place_and_no_stats(gpu):
-    flow, mask = _random_case(3, 37, 11, "wild")   # (thresh 3: at 1 px the few valid +-4096 flows leave this fit no inlier)
-    models, _ = projective_motion_ref(flow, mask, rounds=2, thresh=3.0)
-    want = projective_compensate_ref(flow, models, mask, thresh=3.0)
-    assert np.isnan(want[0]).any() and np.isinf(want[0]).any() and len(np.unique(want[1])) == 3
-    res, none = gpu.projective_compensate(flow, models, mask, thresh=3.0, label=False)
-    assert none is None
-    assert_same_bits(res, want[0], "label = NULL")
-    none, label = gpu.projective_compensate(flow, models, mask, thresh=3.0, residual=False)
-    assert none is None
-    assert_same_bits(label, want[1], "residual = NULL")
-    for w, h in ((37, 11), (64, 16)):   # 4-byte and 16-byte stores over the array they were read from
-        flow, mask = _random_case(3, w, h, "wild")
-        models, _ = projective_motion_ref(flow, mask, rounds=2, thresh=1.0)
-        assert_compensated_equal(gpu.projective_compensate(flow, models, mask, thresh=1.0, in_place=True),
-                                 projective_compensate_ref(flow, models, mask, thresh=1.0), f"residual aliases flow, {w}x{h}")
-    flow, mask = _random_case(3, 64, 16, "smooth")
-    got, none = gpu.projective_motion(flow, mask, rounds=3, thresh=1.0, stats=False)
-    assert none is None
-    assert_same_bits(got, projective_motion_ref(flow, mask, rounds=3, thresh=1.0)[0], "stats = NULL")
+    cases.check_either_output_alone_in_place_and_no_stats(gpu, 8)
 
 
 # ------------------------------------------------------------------ 2. cross-checks with the 6-parameter calls
@@ -286,39 +198,8 @@ FUSED_CASES = [
 
 @pytest.mark.parametrize("kind,noc,w,h,n,first,count,pipeline,contract,alpha,beta", FUSED_CASES)
 def test_fused_matches_standalone(gpu, kind, noc, w, h, n, first, count, pipeline, contract, alpha, beta):
-    clip = smooth_clip(w, h, noc, n + 1)
-    b, devs = run_context(gpu, clip, kind, 2, contract, pipeline)
-    fused = {}
-    try:
-        bytes_before = b.device_bytes()
-        for fb in ((0, 1) if kind != "plain" else (0,)):
-            for rounds, thresh in FUSED_FITS:
-                fit = b.projective_motion(w, h, rounds=rounds, thresh=thresh, fb_check=fb, first=first, count=count, alpha=alpha,
-                                          beta=beta)
-                comp = b.projective_compensate(fit[0], w, h, thresh=thresh, fb_check=fb, first=first, count=count, alpha=alpha,
-                                               beta=beta)
-                fused[fb, rounds, thresh] = fit, comp
-        # the slab belongs to the context: allocated once, counted from then on
-        slab = b.device_bytes() - bytes_before
-        assert slab >= gpu.lib().ofdis_projective_motion_work_bytes(n, w, h) > 0
-        plain = b.upsample_frames(first, count, w, h)
-        fw, mf = b.upsample_bidir(w, h, alpha, beta, first=first, count=count, outputs=(True, False, True, False))[0::2] \
-            if kind != "plain" else (None, None)
-        assert b.device_bytes() - bytes_before == slab
-    finally:
-        b.close()
-    for (fb, rounds, thresh), (fit, comp) in fused.items():
-        flow, mask = (fw, mf) if fb else (plain, None)
-        what = f"fb_check {fb}, rounds {rounds}, thresh {thresh}"
-        standalone = gpu.projective_motion(flow, mask, rounds=rounds, thresh=thresh)
-        assert_fit_equal(fit, standalone, "fused vs standalone, " + what)
-        assert_compensated_equal(comp, gpu.projective_compensate(flow, standalone[0], mask, thresh=thresh),
-                                 "fused vs standalone, " + what)
-        if count <= 3:
-            assert_fit_equal(standalone, projective_motion_ref(flow, mask, rounds=rounds, thresh=thresh),
-                             "standalone vs the definition, " + what)
-        if not (fb and alpha == 0.0 and beta == 0.0):   # something was fitted in the comparison
-            assert (standalone[1][:, 0] > 0).all() and (standalone[1][:, 2] == 8).all()
+    fits = [dict(rounds=rounds, thresh=thresh) for rounds, thresh in FUSED_FITS]
+    cases.check_fused_matches_standalone(gpu, 8, fits, kind, noc, 2, w, h, n, first, count, pipeline, contract, alpha, beta)
 
 
 # ------------------------------------------------------------------ 5. end to end

@@ -4,6 +4,7 @@ their argument checks, which return before any device work -- every rejection th
 (tests/test_gmotion_abi.py, tests/test_track_select_abi.py).  Host buffers stand in for the device arrays: every call here
 returns before it would launch.  The kernels: tests/test_gpu_projective.py."""
 import ctypes as C
+import functools
 import math
 import re
 
@@ -11,6 +12,7 @@ import numpy as np
 import pytest
 
 import abi
+from camera_cases import BAD_SIZES, Host, host_compensate, host_fit
 from of_dis_amd import capi
 from of_dis_amd.abi import prototypes
 
@@ -61,29 +63,9 @@ def test_work_bytes():
 
 
 # ------------------------------------------------------------------ argument checks
-class _Host:
-    """host stand-ins for a 2-pair 8x4 case"""
-
-    def __init__(self, w=8, h=4, npairs=2):
-        self.flow = np.zeros((npairs, h, w, 2), _f32)
-        self.mask = np.zeros((npairs, h, w), np.uint8)
-        self.models = np.zeros((npairs, 8), np.float64)
-        self.stats = np.zeros((npairs, 3), np.int64)
-        self.work = np.zeros(4096, np.int64)
-        self.residual = np.zeros((npairs, h, w, 2), _f32)
-        self.label = np.zeros((npairs, h, w), np.uint8)
-
-
-def _fit(hb, flow=True, models=True, work=True, work_bytes=None, work_off=0, npairs=2, w=8, h=4, rounds=3, thresh=1.0):
-    wb = hb.work.nbytes - 8 if work_bytes is None else work_bytes
-    wp = hb.work.ctypes.data + work_off if work else None
-    return capi.lib().ofdis_projective_motion(_p(hb.flow, flow), _p(hb.mask), npairs, w, h, rounds, thresh, _p(hb.models, models),
-                                              _p(hb.stats), wp, wb, None)
-
-
-def _comp(hb, flow=True, models=True, residual=True, label=True, npairs=2, w=8, h=4, thresh=1.0):
-    return capi.lib().ofdis_projective_compensate(_p(hb.flow, flow), _p(hb.mask), _p(hb.models, models), npairs, w, h, thresh,
-                                                  _p(hb.residual, residual), _p(hb.label, label), None)
+# the host stand-ins and the two calls: tests/camera_cases.py, shared with the other model order
+_Host = functools.partial(Host, 8)
+_fit, _comp = host_fit, host_compensate
 
 
 @pytest.mark.parametrize("which", ["flow", "models"])
@@ -107,10 +89,7 @@ def test_rejects_thresh(thresh):
     abi.rejected(_comp(_Host(), thresh=thresh), "thresh")
 
 
-SIZES = [(0, 8, 4), (-1, 8, 4), (2, 0, 4), (2, 8, 0), (2, -8, 4), (2, 1 << 16, 1 << 16), (2, 8193, 4), (2, 8, 8193)]
-
-
-@pytest.mark.parametrize("npairs,w,h", SIZES)
+@pytest.mark.parametrize("npairs,w,h", BAD_SIZES)
 def test_rejects_bad_sizes(npairs, w, h):
     abi.rejected(_fit(_Host(), npairs=npairs, w=w, h=h), "size")
     abi.rejected(_comp(_Host(), npairs=npairs, w=w, h=h), "size")

@@ -30,6 +30,10 @@ from of_dis_amd import capi  # noqa: E402
 from of_dis_amd.params import oppoint, padded_size  # noqa: E402
 
 LABEL_GREY = np.array([0, 127, 255], np.uint8)  # GM_INLIER, GM_OUTLIER, GM_INVALID
+# --model: the Batch methods of the fit and of the compensation, and what the fit takes beyond rounds and thresh
+MODELS = {"affine": ("global_motion", "motion_compensate", dict(model=capi.GM_AFFINE)),
+          "translation": ("global_motion", "motion_compensate", dict(model=capi.GM_TRANSLATION_ONLY)),
+          "projective": ("projective_motion", "projective_compensate", {})}
 
 
 def csv_line(model, stats):
@@ -66,7 +70,7 @@ def main(argv):
     except (ValueError, StopIteration):
         sys.exit(f"{a}: a value is missing or is not a number")
     # every option is checked here, before the first device call
-    if model not in ("affine", "translation", "projective"):
+    if model not in MODELS:
         sys.exit("--model: affine, translation or projective")
     if not 1 <= rounds <= capi.GM_MAX_ROUNDS:
         sys.exit("--rounds: an integer in 1..%d" % capi.GM_MAX_ROUNDS)
@@ -90,13 +94,9 @@ def main(argv):
     d = capi.Dev(clip)
     b.build_pyramids_u8_seq(d.ptr, w, h)
     b.run()
-    if model == "projective":
-        models, stats = b.projective_motion(w, h, rounds=rounds, thresh=thresh, fb_check=fb)
-        label = b.projective_compensate(models, w, h, thresh=thresh, fb_check=fb, residual=False)[1] if labels else None
-    else:
-        gm = capi.GM_AFFINE if model == "affine" else capi.GM_TRANSLATION_ONLY
-        models, stats = b.global_motion(w, h, model=gm, rounds=rounds, thresh=thresh, fb_check=fb)
-        label = b.motion_compensate(models, w, h, thresh=thresh, fb_check=fb, residual=False)[1] if labels else None
+    fit, compensate, how = MODELS[model]
+    models, stats = getattr(b, fit)(w, h, rounds=rounds, thresh=thresh, fb_check=fb, **how)
+    label = getattr(b, compensate)(models, w, h, thresh=thresh, fb_check=fb, residual=False)[1] if labels else None
     b.close()
     d.free()
     lines = [csv_line(m, s) for m, s in zip(models, stats)]
