@@ -1022,8 +1022,10 @@ int ofdis_batch_motion_compensate(ofdis_batch* b, int first_frame, int count, co
  * is the flow of the homography [[1+a1, a2, a0], [a4, 1+a5, a3], [-a6, -a7, 1]] in centred coordinates.  It is THIS model and not
  * a DLT homography fit: being linear in its parameters it is fitted from exact integer sums like the affine one, whereas the
  * DLT needs moments of order x^2 * x'^2, which overflow 64 bits for a single pixel.
- * Not provided (out of scope): ofdis_camera_path, ofdis_warp_frames and ofdis_batch_stabilize stay affine (the quadratic model
- * is not closed under composition); similarity models; RANSAC; the C++ sequence driver.
+ * Stabilisation: ofdis_camera_path, ofdis_warp_frames and ofdis_batch_stabilize stay affine (the quadratic model is not closed
+ * under composition).  The homography above is: the section "Projective video stabilisation" chains, averages and inverts the
+ * camera path on it and resamples the frames by a perspective warp, from the models fitted here.
+ * Not provided (out of scope): a DLT fit; similarity models; RANSAC; the C++ sequence driver.
  *
  * Everything that is not the model is word for word the section above: valid, qu = (int)rintf(u * 256.0f), X = 2x - (W-1),
  * Y = 2y - (H-1), near, the rounds (S_0 = valid, S_r = near under the model of round r-1, an empty later set leaves the previous
@@ -1098,8 +1100,11 @@ int ofdis_track_select_projective(const float* tracks, const int* start, const i
  * Video stabilisation: the per-pair camera models of a clip turned into one correcting warp per frame -- the classical
  * Gaussian motion filter: the motions relative to a frame averaged over a window around it -- and the frames resampled by their
  * warps.  Two operations, each stated below one step at a time, both independent of the arithmetic contract.
- * Not provided: homography and similarity models, rolling-shutter correction, automatic crop or zoom selection, inpainting of
- * the exposed border, the C++ sequence driver, stereo contexts.
+ * The 8-parameter models of ofdis_projective_motion take the same route on 3 x 3 maps in the section after this one,
+ * "Projective video stabilisation"; the three functions here stay affine.
+ * Not provided: a DLT homography fit (the projective path takes the quadratic-flow models as they are), similarity models,
+ * rolling-shutter correction, automatic crop or zoom selection, inpainting of the exposed border, the C++ sequence driver,
+ * stereo contexts.
  *
  * Conventions.  A warp is six doubles b0 .. b5 in the parametrisation of a model of ofdis_global_motion: the displacement field
  * (b0 + b1*xc + b2*yc, b3 + b4*xc + b5*yc) in centred coordinates xc = x - (W-1)/2, yc = y - (H-1)/2; all zeros is the
@@ -1183,6 +1188,84 @@ int ofdis_batch_stabilize(ofdis_batch* b, const uint8_t* frames, int first_frame
                           float thresh, int fb_check, float alpha, float beta, const double* weights /* host */, int radius,
                           double zoom, int border, uint8_t* out, uint8_t* inside /* or NULL */,
                           double* warps /* device [count+1][6] or NULL */, int width_org, int height_org, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Projective video stabilisation: the section above for the 8-parameter models of ofdis_projective_motion.  The quadratic flow
+ * model does not compose, but the map it is the first-order flow of does: the path is chained, averaged and inverted on 3 x 3
+ * maps, and the frames are resampled by a true perspective warp -- a pan or a tilt leaves no keystone wobble at the corners.
+ * Both operations are independent of the arithmetic contract.  The affine functions are unchanged.
+ * Not provided: a DLT fit, similarity models, rolling-shutter correction, automatic crop or zoom selection, inpainting of the
+ * exposed border, the C++ sequence driver, stereo contexts.
+ *
+ * Conventions.  A warp is eight doubles g0 .. g7, the map [[1+g1, g2, g0], [g4, 1+g5, g3], [-g6, -g7, 1]] in centred
+ * coordinates xc = x - (W-1)/2, yc = y - (H-1)/2: all zeros is the identity, g6 = g7 = 0 is the affine warp b0 .. b5 of
+ * ofdis_warp_frames.  A map M = (a, b, c, d, tx, ty, gx, gy), with an implicit 1 in the corner, means
+ *   x' = (a*xc + b*yc + tx) / (1 + gx*xc + gy*yc),   y' = (c*xc + d*yc + ty) / (1 + gx*xc + gy*yc).
+ * The model a0 .. a7 of pair k is read as T_k = (1 + a1, a2, a4, 1 + a5, a0, a3, 0 - a6, 0 - a7).
+ *
+ * Camera path: models [npairs][8] fp64, the frame size W x H and the window w_0 .. w_radius -> warps [npairs+1][8] fp64.
+ * Every operation is a separately rounded fp64 operation (no contraction) in this order; det and ok are the section above's:
+ *   hx = (W-1)/2, hy = (H-1)/2                                                                       (exact in fp64)
+ *   usable(M) = all eight numbers finite, and ok(M.a*M.d - M.b*M.c), and
+ *               (1 - |M.gx|*hx) - |M.gy|*hy >= 0.5                                                   (a NaN fails each test)
+ *       The last test keeps the denominator at or above 0.5 on every pixel of the frame, which is why the path takes the
+ *       frame size.  usable(k) = usable(T_k); an unusable pair is a break.
+ *   T o M (M first), the 3 x 3 product in this order, then all eight divided by n:
+ *       a = (T.a*M.a + T.b*M.c) + T.tx*M.gx     b = (T.a*M.b + T.b*M.d) + T.tx*M.gy
+ *       c = (T.c*M.a + T.d*M.c) + T.ty*M.gx     d = (T.c*M.b + T.d*M.d) + T.ty*M.gy
+ *       tx = (T.a*M.tx + T.b*M.ty) + T.tx       ty = (T.c*M.tx + T.d*M.ty) + T.ty
+ *       gx = (T.gx*M.a + T.gy*M.c) + M.gx       gy = (T.gx*M.b + T.gy*M.d) + M.gy
+ *       n = (T.gx*M.tx + T.gy*M.ty) + 1
+ *   inv(T): the adjugate divided by its corner entry D = T.a*T.d - T.b*T.c, the determinant the usable test guards:
+ *       a = (T.d - T.ty*T.gy) / D        b = (T.tx*T.gy - T.b) / D        c = (T.ty*T.gx - T.c) / D        d = (T.a - T.tx*T.gx) / D
+ *       tx = (T.b*T.ty - T.tx*T.d) / D   ty = (T.tx*T.c - T.a*T.ty) / D   gx = (T.c*T.gy - T.d*T.gx) / D   gy = (T.b*T.gx - T.a*T.gy) / D
+ *   The walk, the window, its symmetric truncation and the breaks are word for word those of ofdis_camera_path, on eight
+ *   numbers: acc = w_0 times the identity (w_0, 0, 0, w_0, 0, 0, 0, 0), sw = w_0, Mf = Mb = identity, and for j = 1, 2, ...
+ *   while j <= radius and f + j - 1 < npairs and f - j >= 0 and usable(f + j - 1) and usable(f - j):
+ *       Mf = T_{f+j-1} o Mf;   Mb = inv(T_{f-j}) o Mb
+ *       acc.e = acc.e + (w_j*Mf.e + w_j*Mb.e)  for each of the eight numbers e;   sw = sw + (w_j + w_j)
+ *       Q = acc / sw  (eight divisions)
+ *       W = inv(Q) where usable(Q) and usable(inv(Q)) (so all eight numbers of inv(Q) are finite), else the identity
+ *       s = 1 / zoom:   g0 = W.tx   g1 = W.a*s - 1   g2 = W.b*s   g3 = W.ty   g4 = W.c*s   g5 = W.d*s - 1
+ *                       g6 = 0 - W.gx*s   g7 = 0 - W.gy*s
+ *   Weights, radius and zoom as in the section above.
+ *
+ * Frame warp: frames [n][H][W][noc] u8 and warps [n][8] fp64 -> out and inside as ofdis_warp_frames writes them.  fp32, every
+ * operation separately rounded, in DISPLACEMENT form, so that it degenerates exactly to the affine warp; gf_k = (float) g_k,
+ * xc and yc as there:
+ *   e = gf6*xc + gf7*yc;   D = 1.0f - e;   r = 1.0f / D                  (one correctly rounded division per pixel)
+ *   mu = ((gf0 + gf1*xc) + gf2*yc) + e*xc;   mv = ((gf3 + gf4*xc) + gf5*yc) + e*yc
+ *   p = ((float)x + mu*r, (float)y + mv*r)
+ *   ins = D > 0 and inside(p)                                            (a NaN fails the test)
+ * Clamping, sampling, border, rounding, out and inside are exactly those of ofdis_warp_frames.  (mu, mv) / D is the exact
+ * displacement of the map above, and its numerator is the quadratic model of "Projective camera models".
+ * Consequences.  With g6 = g7 = 0 every byte of out and inside equals ofdis_warp_frames on g0 .. g5 (e = +-0, D = 1, r = 1).  A
+ * zero warp returns the frame bit for bit, an integer translation (g0, g3 integers, the rest 0) the shifted frame bit for bit.
+ * With a6 = a7 = 0 models the path has g6 = g7 = 0 exactly and g0 .. g5 agree with ofdis_camera_path to rounding, not to the
+ * bit: the translation of the inverse is rounded differently (here from the adjugate, there from the inverted linear part).
+ * of_dis_amd/stabilize.py states the same arithmetic in numpy (camera_path_projective_ref, warp_frames_projective_ref;
+ * STAB_MIN_DENOM there and in of_dis_amd/capi.py is the 0.5 of usable).
+ * ------------------------------------------------------------------------------------------- */
+/* device arrays: models [npairs][8] f64, warps [npairs+1][8] f64; weights: HOST, radius + 1 doubles; width, height: the frame
+ * size of the clip the models were fitted on.  One lane per frame, one launch on `stream`, no host synchronisation.
+ * OFDIS_ERR_INVALID before any device work: a NULL models, weights or warps pointer; radius, the weights or zoom outside their
+ * ranges; npairs < 1; a side outside 1 .. OFDIS_GM_MAX_SIDE. */
+int ofdis_camera_path_projective(const double* models, int npairs, int width, int height, const double* weights /* host */,
+                                 int radius, double zoom, double* warps, void* stream);
+/* ofdis_warp_frames under warps [nframes][8]: the same arrays, store widths and rejections. */
+int ofdis_warp_frames_projective(const uint8_t* frames, const double* warps, uint8_t* out, uint8_t* inside /* or NULL */,
+                                 int nframes, int width, int height, int noc, int border, void* stream);
+/* ofdis_batch_stabilize without `model`: the composition, all enqueued on `stream`, of ofdis_batch_projective_motion(b,
+ * first_frame, count, rounds, thresh, fb_check, alpha, beta, ...), ofdis_camera_path_projective on its models at width_org x
+ * height_org and ofdis_warp_frames_projective on frames + first_frame frames -- bit-identical to those three calls made
+ * separately, under both contracts.  warps = device [count+1][8] or NULL.  Models and warps live in an array of the context of
+ * its own: allocated at the first call, counted by ofdis_batch_device_bytes from then on.  Joins a pipelined pass by itself.
+ * OFDIS_ERR_INVALID as ofdis_batch_stabilize, each before any allocation or device work. */
+int ofdis_batch_stabilize_projective(ofdis_batch* b, const uint8_t* frames, int first_frame, int count, int rounds,
+                                     float thresh, int fb_check, float alpha, float beta, const double* weights /* host */,
+                                     int radius, double zoom, int border, uint8_t* out, uint8_t* inside /* or NULL */,
+                                     double* warps /* device [count+1][8] or NULL */, int width_org, int height_org,
+                                     void* stream);
 
 /* Warm start (the reference's `initflow`, oflow.cpp:217-220; e.g. the previous frame pair's flow of a video):
  * per frame (w >> (sc_f+1)) x (h >> (sc_f+1)) x 2 floats, AoS.  set_initflow borrows a device array

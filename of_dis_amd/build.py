@@ -126,7 +126,7 @@ def lib_path():
 
 def testhooks_path():
     """The TEST library: kernels that expose header-only helpers to the parity tests (tests/csrc/ofdis_testhooks.hip) and the
-    product's post-processing launchers with lowered launch limits (tests/csrc/ofdis_launch_hooks.hip, TESTHOOK_UNITS).
+    product's post-processing launchers with lowered launch limits (tests/csrc/ofdis_launch_hooks*.hip, TESTHOOK_UNITS).
     Built next to the product, never linked into it."""
     return os.path.join(LIBDIR, "libofdis_testhooks.so")
 
@@ -264,17 +264,21 @@ def build(force=False, verbose=False):
             tdir = os.path.join(LIBDIR, "testhooks")
             os.makedirs(tdir, exist_ok=True)
             tobjs, _ = compile_units(CSRC, tdir, force, verbose, {u: TESTHOOK_FLAGS for u in TESTHOOK_UNITS}, only=TESTHOOK_UNITS)
-            launch_hooks = os.path.join(ROOT, "tests", "csrc", "ofdis_launch_hooks.hip")
-            lobj = os.path.join(tdir, "ofdis_launch_hooks.o")
-            if force or _newer(lobj, [launch_hooks] + headers):
-                _run([hipcc] + HIPFLAGS + TESTHOOK_FLAGS + ["-c", launch_hooks, "-o", lobj], verbose)
+            # (ofdis_launch_hooks.hip and the files beside it that add one product's hooks: ofdis_launch_hooks_*.hip)
+            lobjs = []
+            for name in sorted(f for f in os.listdir(os.path.join(ROOT, "tests", "csrc"))
+                               if f.startswith("ofdis_launch_hooks") and f.endswith(".hip")):
+                launch_hooks = os.path.join(ROOT, "tests", "csrc", name)
+                lobjs.append(os.path.join(tdir, name.replace(".hip", ".o")))
+                if force or _newer(lobjs[-1], [launch_hooks] + headers):
+                    _run([hipcc] + HIPFLAGS + TESTHOOK_FLAGS + ["-c", launch_hooks, "-o", lobjs[-1]], verbose)
             hobj = os.path.join(tdir, "ofdis_testhooks.o")
             if force or _newer(hobj, [hooks] + headers):
                 _run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-c", hooks, "-o", hobj],
                      verbose)
             tso = testhooks_path()
-            if force or _newer(tso, [hobj, lobj] + tobjs):
-                _run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", tso, hobj, lobj] + tobjs, verbose)
+            if force or _newer(tso, [hobj] + lobjs + tobjs):
+                _run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", tso, hobj] + lobjs + tobjs, verbose)
     except RuntimeError as e:
         print("of_dis_amd.build: test artefacts not built:", str(e)[:2000], file=sys.stderr)
     return so

@@ -48,6 +48,7 @@ GM_TRANSLATION_ONLY, GM_AFFINE = 0, 1  # OFDIS_GM_* model
 GM_OK_AFFINE, GM_TRANSLATION, GM_EMPTY = 0, 1, 2  # OFDIS_GM_* status
 GM_INLIER, GM_OUTLIER, GM_INVALID = 0, 1, 2  # OFDIS_GM_* label
 STAB_MAX_RADIUS, STAB_MIN_DET, STAB_MAX_DET, STAB_MAX_ZOOM = 64, 0.25, 4.0, 16.0  # OFDIS_STAB_*
+STAB_MIN_DENOM = 0.5  # include/ofdis.h, "Projective video stabilisation": the denominator bound of usable (no macro there)
 BORDER_CONSTANT, BORDER_REPLICATE = 0, 1  # OFDIS_BORDER_*
 OFDIS_VERSION = 3  # include/ofdis.h: the struct layouts below (OfdisTuning: 21 ints) belong to this ABI version
 
@@ -967,6 +968,34 @@ def warp_frames(frames, warps, border=BORDER_CONSTANT, inside=True):
     return do.get(frames.shape, np.uint8), di.get((n, h, w), np.uint8) if di else None
 
 
+def camera_path_projective(models, weights, w, h, zoom=1.0):
+    """ofdis_camera_path_projective on the device: models [npairs, 8] float64 (projective_motion's) of a clip of w x h frames,
+    weights as camera_path takes them -> warps [npairs + 1, 8] float64, one per frame.
+    of_dis_amd/stabilize.py: camera_path_projective_ref is the numpy statement of the same arithmetic."""
+    models = np.ascontiguousarray(models, np.float64)
+    assert models.ndim == 2 and models.shape[1] == 8, models.shape
+    npairs = models.shape[0]
+    weights, radius = _stab_weights(weights)
+    dm, dw = Dev(models), Dev(nbytes=(npairs + 1) * 64)
+    check(lib().ofdis_camera_path_projective(dm.ptr, npairs, w, h, weights.ctypes.data, radius, zoom, dw.ptr, None))
+    check(lib().ofdis_sync(None))
+    return dw.get((npairs + 1, 8), np.float64)
+
+
+def warp_frames_projective(frames, warps, border=BORDER_CONSTANT, inside=True):
+    """ofdis_warp_frames_projective on the device: warp_frames with warps [n, 8] float64.
+    of_dis_amd/stabilize.py: warp_frames_projective_ref is the numpy statement of the same arithmetic."""
+    n, h, w = np.shape(frames)[:3]
+    frames, noc = _clip_frames(frames, n, h, w)
+    warps = np.ascontiguousarray(warps, np.float64)
+    assert warps.shape == (n, 8), warps.shape
+    df, dw, do = Dev(frames), Dev(warps), Dev(nbytes=frames.nbytes)
+    di = Dev(nbytes=n * h * w) if inside else None
+    check(lib().ofdis_warp_frames_projective(df.ptr, dw.ptr, do.ptr, di.ptr if di else None, n, w, h, noc, border, None))
+    check(lib().ofdis_sync(None))
+    return do.get(frames.shape, np.uint8), di.get((n, h, w), np.uint8) if di else None
+
+
 class Batch:
     """ofdis_batch: `nframes` frame pairs of one geometry resident in HBM.  reverse=True: ofdis_batch_create_ex with
     OFDIS_BATCH_REVERSE (every pass also computes the flow B -> A of each pair).  stereo_lr=True: OFDIS_BATCH_STEREO_LR
@@ -1366,6 +1395,22 @@ class Batch:
                  (warps_ptr or out_ptr is None, (shape[0], 6), np.float64)]
         return self._outputs(out_ptr is None, specs, lambda out, ins, warps: check(lib().ofdis_batch_stabilize(
             self.h, frames_ptr, first, count, model, rounds, thresh, int(fb_check), alpha, beta, weights.ctypes.data, radius, zoom,
+            border, out, ins, warps, width_org, height_org, stream)), stream)
+
+    def stabilize_projective(self, frames_ptr, width_org, height_org, weights, zoom=1.0, border=BORDER_CONSTANT, rounds=3,
+                             thresh=1.0, fb_check=False, first=0, count=None, alpha=FB_ALPHA, beta=FB_BETA, inside=False,
+                             out_ptr=None, warps_ptr=None, stream=None):
+        """ofdis_batch_stabilize_projective: stabilize under the 8-parameter models of projective_motion(rounds, thresh,
+        fb_check), the path chained on homographies and the frames resampled by a perspective warp.  Arguments and returns as
+        stabilize, without `model`; the warps are [count + 1, 8] float64."""
+        count = self.nframes - first if count is None else count
+        weights, radius = _stab_weights(weights)
+        shape = (max(count, 0) + 1, height_org, width_org)
+        oshape = shape + ((self.p.noc,) if self.p.noc > 1 else ())
+        specs = [(out_ptr or True, oshape, np.uint8), (inside, shape, np.uint8),
+                 (warps_ptr or out_ptr is None, (shape[0], 8), np.float64)]
+        return self._outputs(out_ptr is None, specs, lambda out, ins, warps: check(lib().ofdis_batch_stabilize_projective(
+            self.h, frames_ptr, first, count, rounds, thresh, int(fb_check), alpha, beta, weights.ctypes.data, radius, zoom,
             border, out, ins, warps, width_org, height_org, stream)), stream)
 
     def timing(self, enable=True):

@@ -173,6 +173,7 @@ struct ofdis_batch {
   float* gm_slab = nullptr;          // records of sums of ofdis_batch_global_motion (ofdis_gmotion.hip; int64, held as floats), lazy
   float* pm_slab = nullptr;          // ... and the 24-sum records of ofdis_batch_projective_motion (int64, held as floats), lazy
   float* stab_path = nullptr;        // models [nframes][6] then warps [nframes + 1][6] of ofdis_batch_stabilize (fp64, held as floats), lazy
+  float* stab_path8 = nullptr;       // ... and models [nframes][8] then warps [nframes + 1][8] of ofdis_batch_stabilize_projective, lazy
   float* dt_slab = nullptr;          // work buffer of ofdis_batch_dense_tracks (ofdis_dense_tracks.hip; held as floats), lazy: a
                                      // call that needs more than it holds requests a larger one (dstage)
   float* retired = nullptr;          // always null: where the descriptions of outgrown staging buffers point (dstage)

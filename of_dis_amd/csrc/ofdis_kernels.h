@@ -407,6 +407,12 @@ hipError_t launch_camera_path(const double* models, int npairs, const StabWindow
 // frames, out [nframes][h][w][noc] u8, warps [nframes][6], inside [nframes][h][w] u8 or null; replicate: OFDIS_BORDER_REPLICATE
 hipError_t launch_warp_frames(const uint8_t* frames, const double* warps, uint8_t* out, uint8_t* inside, int nframes, int w,
                               int h, int noc, bool replicate, hipStream_t s);
+// the projective twins (include/ofdis.h: ofdis_camera_path_projective, ofdis_warp_frames_projective): models [npairs][8] of a
+// w x h clip -> warps [npairs + 1][8], and the frames under warps [nframes][8]
+hipError_t launch_camera_path_projective(const double* models, int npairs, int w, int h, const StabWindow& win, double* warps,
+                                         hipStream_t s);
+hipError_t launch_warp_frames_projective(const uint8_t* frames, const double* warps, uint8_t* out, uint8_t* inside, int nframes,
+                                         int w, int h, int noc, bool replicate, hipStream_t s);
 
 // ---- stereo-depth mode (SELECTMODE=2; ofdis_de.hip)
 struct DeSystemArgs {

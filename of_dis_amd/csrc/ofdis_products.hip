@@ -802,9 +802,12 @@ int ofdis_warp_frames(const uint8_t* frames, const double* warps, uint8_t* out, 
   return OFDIS_OK;
 }
 
-int ofdis_batch_stabilize(ofdis_batch* b, const uint8_t* frames, int first_frame, int count, int model, int rounds, float thresh,
-                          int fb_check, float alpha, float beta, const double* weights, int radius, double zoom, int border,
-                          uint8_t* out, uint8_t* inside, double* warps, int width_org, int height_org, void* stream) {
+// ofdis_batch_stabilize (nparam = 6) and ofdis_batch_stabilize_projective (nparam = 8: no `model` argument, the caller passes
+// OFDIS_GM_AFFINE): the checks, the context's array of models and warps, and the three stages on one stream
+static int camera_batch_stabilize(ofdis_batch* b, const uint8_t* frames, int first_frame, int count, int model, int rounds,
+                                  float thresh, int fb_check, float alpha, float beta, const double* weights, int radius,
+                                  double zoom, int border, uint8_t* out, uint8_t* inside, double* warps, int width_org,
+                                  int height_org, void* stream, int nparam) {
   Finish fin;
   if (int rc = gm_batch_check(b, fb_check, alpha, beta, width_org, height_org, fin)) return rc;
   if (int rc = context_check(b, OFDIS_BATCH_SEQUENCE)) return rc;  // (the pairs of any other context are no chain)
@@ -813,18 +816,62 @@ int ofdis_batch_stabilize(ofdis_batch* b, const uint8_t* frames, int first_frame
   if (int rc = stab_window(weights, radius, zoom, win)) return rc;
   if (int rc = stab_warp_check(frames, out, b->p.noc, border)) return rc;
   if (int rc = finish_begin(b, first_frame, count, width_org, height_org, stream, fin)) return rc;
-  if (int rc = dstage(b, {{&b->stab_path, 24, 1}})) return rc;  // 6 + 6 doubles per pair and 6 more for the last frame, held as floats
-  double* models = reinterpret_cast<double*>(b->stab_path);
-  double* path = models + (size_t)b->nframes * 6;
+  // nparam + nparam doubles per pair and nparam more for the last frame, held as floats
+  float*& held = nparam == 8 ? b->stab_path8 : b->stab_path;
+  if (int rc = dstage(b, {{&held, (size_t)4 * nparam, 1}})) return rc;
+  double* models = reinterpret_cast<double*>(held);
+  double* path = models + (size_t)b->nframes * nparam;
   hipStream_t s = (hipStream_t)stream;
-  if (int rc = ofdis_batch_global_motion(b, first_frame, count, model, rounds, thresh, fb_check, alpha, beta, models, nullptr,
-                                         width_org, height_org, stream))
+  if (int rc = camera_batch_fit(b, first_frame, count, model, rounds, thresh, fb_check, alpha, beta, models, nullptr, width_org,
+                                height_org, stream, nparam))
     return rc;
-  HIPCHK(launch_camera_path(models, count, win, path, s));
-  HIPCHK(launch_warp_frames(fin.clip(frames), path, out, inside, count + 1, width_org, height_org, b->p.noc,
-                            border == OFDIS_BORDER_REPLICATE, s));
-  if (warps) HIPCHK(hipMemcpyAsync(warps, path, (size_t)(count + 1) * 6 * sizeof(double), hipMemcpyDeviceToDevice, s));
+  const uint8_t* clip = fin.clip(frames);
+  const bool replicate = border == OFDIS_BORDER_REPLICATE;
+  if (nparam == 8) {
+    HIPCHK(launch_camera_path_projective(models, count, width_org, height_org, win, path, s));
+    HIPCHK(launch_warp_frames_projective(clip, path, out, inside, count + 1, width_org, height_org, b->p.noc, replicate, s));
+  } else {
+    HIPCHK(launch_camera_path(models, count, win, path, s));
+    HIPCHK(launch_warp_frames(clip, path, out, inside, count + 1, width_org, height_org, b->p.noc, replicate, s));
+  }
+  if (warps) HIPCHK(hipMemcpyAsync(warps, path, (size_t)(count + 1) * nparam * sizeof(double), hipMemcpyDeviceToDevice, s));
   return OFDIS_OK;
+}
+
+int ofdis_batch_stabilize(ofdis_batch* b, const uint8_t* frames, int first_frame, int count, int model, int rounds, float thresh,
+                          int fb_check, float alpha, float beta, const double* weights, int radius, double zoom, int border,
+                          uint8_t* out, uint8_t* inside, double* warps, int width_org, int height_org, void* stream) {
+  return camera_batch_stabilize(b, frames, first_frame, count, model, rounds, thresh, fb_check, alpha, beta, weights, radius, zoom,
+                                border, out, inside, warps, width_org, height_org, stream, 6);
+}
+
+int ofdis_camera_path_projective(const double* models, int npairs, int width, int height, const double* weights, int radius,
+                                 double zoom, double* warps, void* stream) {
+  if (!models || !warps) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  StabWindow win;
+  if (int rc = stab_window(weights, radius, zoom, win)) return rc;
+  if (npairs < 1) return fail(OFDIS_ERR_INVALID, "bad sizes (npairs < 1)");
+  if (!gm_sizes_ok(npairs, width, height)) return fail(OFDIS_ERR_INVALID, kGmSizes);
+  HIPCHK(launch_camera_path_projective(models, npairs, width, height, win, warps, (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+int ofdis_warp_frames_projective(const uint8_t* frames, const double* warps, uint8_t* out, uint8_t* inside, int nframes, int width,
+                                 int height, int noc, int border, void* stream) {
+  if (!warps) return fail(OFDIS_ERR_INVALID, "bad arguments");
+  if (int rc = stab_warp_check(frames, out, noc, border)) return rc;
+  if (!gm_sizes_ok(nframes, width, height)) return fail(OFDIS_ERR_INVALID, kGmSizes);
+  HIPCHK(launch_warp_frames_projective(frames, warps, out, inside, nframes, width, height, noc, border == OFDIS_BORDER_REPLICATE,
+                                       (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+int ofdis_batch_stabilize_projective(ofdis_batch* b, const uint8_t* frames, int first_frame, int count, int rounds, float thresh,
+                                     int fb_check, float alpha, float beta, const double* weights, int radius, double zoom,
+                                     int border, uint8_t* out, uint8_t* inside, double* warps, int width_org, int height_org,
+                                     void* stream) {
+  return camera_batch_stabilize(b, frames, first_frame, count, OFDIS_GM_AFFINE, rounds, thresh, fb_check, alpha, beta, weights,
+                                radius, zoom, border, out, inside, warps, width_org, height_org, stream, 8);
 }
 
 }  // extern "C"

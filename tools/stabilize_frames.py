@@ -1,14 +1,17 @@
 """A clip stabilised from Python through a SEQUENCE | REVERSE batch context: every frame held once, both flow directions of every
 pair on the device, then ofdis_batch_stabilize (include/ofdis.h): one affine camera model per pair by trimmed least squares,
 the motions relative to every frame averaged over a Gaussian window, and the frames resampled by the correcting warps.
+--model projective takes ofdis_batch_stabilize_projective instead: 8-parameter models, the path chained on homographies, the
+frames resampled by a perspective warp -- for pans and tilts, whose keystone an affine warp leaves at the corners.
 
-    python tools/stabilize_frames.py [--rgb] [--op 1..4] [--fused] [--radius 8] [--sigma 4.0] [--zoom 1.0]
-                                     [--border constant|replicate] img0 img1 ... imgN out_stem
+    python tools/stabilize_frames.py [--model affine|projective] [--rgb] [--op 1..4] [--fused] [--radius 8] [--sigma 4.0]
+                                     [--zoom 1.0] [--border constant|replicate] img0 img1 ... imgN out_stem
 
 Images load as for tools/flow_images.py (B G R for --rgb, OpenCV's fixed-point BGR2GRAY otherwise); at least two, all of one
 size.  Writes one PNG per frame, <out_stem>_000.png and so on (gray, or RGB converted back from B G R), and <out_stem>.csv with
 one line per frame: the six numbers b0..b5 of its warp (out(x) = in(x + (b0 + b1*xc + b2*yc, b3 + b4*xc + b5*yc)), centred
-coordinates), printed with repr so that they read back bit for bit.  --radius / --sigma: the window, w_j = exp(-j^2 / (2
+coordinates; --model projective: the eight numbers g0..g7 of the map [[1+g1, g2, g0], [g4, 1+g5, g3], [-g6, -g7, 1]]), printed
+with repr so that they read back bit for bit.  --radius / --sigma: the window, w_j = exp(-j^2 / (2
 sigma^2)) for j = 0..radius (radius 0..64); --zoom in [1, 16] magnifies about the centre to hide the border a correction
 exposes; --border: what the exposed border shows, zeros or the repeated edge.  --fused selects the FMA / fast-reciprocal
 arithmetic contract for the flow (default: the exact one); the stabiliser itself does not depend on it."""
@@ -27,7 +30,7 @@ from of_dis_amd.params import oppoint, padded_size  # noqa: E402
 
 def main(argv):
     rgb = fused = False
-    op, radius, sigma, zoom, border = 2, 8, 4.0, 1.0, "constant"
+    op, radius, sigma, zoom, border, model = 2, 8, 4.0, 1.0, "constant", "affine"
     args = []
     it = iter(argv)
     for a in it:
@@ -45,12 +48,16 @@ def main(argv):
             zoom = float(next(it))
         elif a == "--border":
             border = next(it)
+        elif a == "--model":
+            model = next(it)
         else:
             args.append(a)
     if len(args) < 3:
         sys.exit(__doc__)
     if border not in ("constant", "replicate"):
         sys.exit("--border: constant or replicate")
+    if model not in ("affine", "projective"):
+        sys.exit("--model: affine or projective")
     try:
         weights = stabilize.check_window(stabilize.gaussian_weights(radius, sigma), zoom)
     except ValueError as e:
@@ -68,9 +75,10 @@ def main(argv):
     d = capi.Dev(clip)
     b.build_pyramids_u8_seq(d.ptr, w, h)
     b.run()
-    out, inside, warps = b.stabilize(d.ptr, w, h, weights, zoom=zoom,
-                                     border=capi.BORDER_REPLICATE if border == "replicate" else capi.BORDER_CONSTANT,
-                                     fb_check=True, inside=True)
+    stabilise = b.stabilize_projective if model == "projective" else b.stabilize
+    out, inside, warps = stabilise(d.ptr, w, h, weights, zoom=zoom,
+                                   border=capi.BORDER_REPLICATE if border == "replicate" else capi.BORDER_CONSTANT,
+                                   fb_check=True, inside=True)
     b.close()
     d.free()
     from PIL import Image

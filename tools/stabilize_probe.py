@@ -1,6 +1,8 @@
 """Video stabilisation of a sequence context, stage by stage: ofdis_batch_global_motion (the models, from the level flows),
 ofdis_camera_path (one warp per frame) and ofdis_warp_frames (the frames resampled), then ofdis_batch_stabilize, which is the
-three in one call, and the bytes the warp kernel moves against the time it takes.
+three in one call, and the bytes the warp kernel moves against the time it takes.  Then the projective route on the same
+context, in the same job: ofdis_batch_projective_motion, ofdis_camera_path_projective, ofdis_warp_frames_projective and
+ofdis_batch_stabilize_projective, one row each beside the affine one.
 
 1024x436, gray and RGB, operating point 2, TV on, fused arithmetic contract for the flow passes (the stabilisation kernels are
 independent of the contract), one GPU, an OFDIS_BATCH_SEQUENCE | OFDIS_BATCH_REVERSE context of 1024 pairs over the clip of
@@ -32,8 +34,7 @@ RADIUS, SIGMA, ZOOM, BORDER = 16, 8.0, 1.05, capi.BORDER_CONSTANT
 
 
 def measure(frames, noc, tstream, dev, rounds, steps):
-    """frames: [n + 1][H][W] (gray) or [n + 1][H][W][3] u8 on the device"""
-    L = capi.lib()
+    """frames: [n + 1][H][W] (gray) or [n + 1][H][W][3] u8 on the device; returns the affine row and the projective row"""
     s = tstream.cuda_stream
     n = frames.shape[0] - 1
     p = oppoint(2, W, H, noc=noc, usetvref=1, verbosity=0)
@@ -44,28 +45,53 @@ def measure(frames, noc, tstream, dev, rounds, steps):
     tstream.synchronize()
     if b.status() != 0:
         raise SystemExit("the pass failed (ofdis_batch_status)")
-    before = b.device_bytes()
     weights = stabilize.gaussian_weights(RADIUS, SIGMA)
+    rows = [route(b, frames, noc, tstream, dev, rounds, steps, weights, nparam) for nparam in (6, 8)]
+    b.close()
+    return rows
+
+
+def route(b, frames, noc, tstream, dev, rounds, steps, weights, nparam):
+    """the three stages and the one call of the affine (nparam = 6) or the projective (8) route on the context b"""
+    L = capi.lib()
+    s = tstream.cuda_stream
+    n = frames.shape[0] - 1
+    before = b.device_bytes()
     wp = weights.ctypes.data
-    models = torch.empty((n, 6), dtype=torch.float64, device=dev)
-    warps = [torch.empty((n + 1, 6), dtype=torch.float64, device=dev) for _ in range(2)]
+    models = torch.empty((n, nparam), dtype=torch.float64, device=dev)
+    warps = [torch.empty((n + 1, nparam), dtype=torch.float64, device=dev) for _ in range(2)]
     out = [torch.empty_like(frames) for _ in range(2)]
     inside = [torch.empty((n + 1, H, W), dtype=torch.uint8, device=dev) for _ in range(2)]
     a, be = capi.FB_ALPHA, capi.FB_BETA
+    fp, o0, o1, i0, i1 = frames.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), inside[0].data_ptr(), inside[1].data_ptr()
+    mp, w0, w1 = models.data_ptr(), warps[0].data_ptr(), warps[1].data_ptr()
 
-    def fit():
-        capi.check(L.ofdis_batch_global_motion(b.h, 0, n, MODEL, ROUNDS, THRESH, 1, a, be, models.data_ptr(), None, W, H, s))
+    if nparam == 6:
+        def fit():
+            capi.check(L.ofdis_batch_global_motion(b.h, 0, n, MODEL, ROUNDS, THRESH, 1, a, be, mp, None, W, H, s))
 
-    def path():
-        capi.check(L.ofdis_camera_path(models.data_ptr(), n, wp, RADIUS, ZOOM, warps[0].data_ptr(), s))
+        def path():
+            capi.check(L.ofdis_camera_path(mp, n, wp, RADIUS, ZOOM, w0, s))
 
-    def warp():
-        capi.check(L.ofdis_warp_frames(frames.data_ptr(), warps[0].data_ptr(), out[0].data_ptr(), inside[0].data_ptr(), n + 1, W, H,
-                                       noc, BORDER, s))
+        def warp():
+            capi.check(L.ofdis_warp_frames(fp, w0, o0, i0, n + 1, W, H, noc, BORDER, s))
 
-    def whole():
-        capi.check(L.ofdis_batch_stabilize(b.h, frames.data_ptr(), 0, n, MODEL, ROUNDS, THRESH, 1, a, be, wp, RADIUS, ZOOM, BORDER,
-                                           out[1].data_ptr(), inside[1].data_ptr(), warps[1].data_ptr(), W, H, s))
+        def whole():
+            capi.check(L.ofdis_batch_stabilize(b.h, fp, 0, n, MODEL, ROUNDS, THRESH, 1, a, be, wp, RADIUS, ZOOM, BORDER, o1, i1, w1,
+                                               W, H, s))
+    else:
+        def fit():
+            capi.check(L.ofdis_batch_projective_motion(b.h, 0, n, ROUNDS, THRESH, 1, a, be, mp, None, W, H, s))
+
+        def path():
+            capi.check(L.ofdis_camera_path_projective(mp, n, W, H, wp, RADIUS, ZOOM, w0, s))
+
+        def warp():
+            capi.check(L.ofdis_warp_frames_projective(fp, w0, o0, i0, n + 1, W, H, noc, BORDER, s))
+
+        def whole():
+            capi.check(L.ofdis_batch_stabilize_projective(b.h, fp, 0, n, ROUNDS, THRESH, 1, a, be, wp, RADIUS, ZOOM, BORDER, o1,
+                                                          i1, w1, W, H, s))
 
     t_fit, t_path, t_warp, t_whole = alternate(tstream, [fit, path, warp, whole], rounds, steps, 2)
     tstream.synchronize()
@@ -75,20 +101,23 @@ def measure(frames, noc, tstream, dev, rounds, steps):
     px = (n + 1) * W * H
     warp_bytes = px * (2 * noc + 1)      # the frame read once, out and inside written once
     gbs = warp_bytes / (med(t_warp) * 1e-3) / 1e9
-    r = {"noc": noc, "pairs": n, "model": "affine", "rounds": ROUNDS, "thresh": THRESH, "radius": RADIUS, "sigma": SIGMA,
-         "zoom": ZOOM, "border": "constant",
-         "global_motion_ms": round(med(t_fit), 4), "camera_path_ms": round(med(t_path), 4), "warp_frames_ms": round(med(t_warp), 4),
-         "batch_stabilize_ms": round(med(t_whole), 4), "frames_per_s": round((n + 1) / (med(t_whole) * 1e-3)),
+    names = (("global_motion", "camera_path", "warp_frames", "batch_stabilize") if nparam == 6 else
+             ("projective_motion", "camera_path_projective", "warp_frames_projective", "batch_stabilize_projective"))
+    r = {"noc": noc, "pairs": n, "model": "affine" if nparam == 6 else "projective", "rounds": ROUNDS, "thresh": THRESH,
+         "radius": RADIUS, "sigma": SIGMA, "zoom": ZOOM, "border": "constant",
+         names[0] + "_ms": round(med(t_fit), 4), names[1] + "_ms": round(med(t_path), 4), names[2] + "_ms": round(med(t_warp), 4),
+         names[3] + "_ms": round(med(t_whole), 4), "frames_per_s": round((n + 1) / (med(t_whole) * 1e-3)),
          "warp_bytes": warp_bytes, "warp_bytes_per_pixel": 2 * noc + 1, "warp_GBs": round(gbs, 1),
          "warp_frac_of_hbm_peak": round(gbs / bench.HBM_PEAK_GBS, 4),
          "context_scratch_bytes": b.device_bytes() - before,
          "inside_share": round(float(inside[0].float().mean()), 4),
          "largest_shift_px": round(float(warps[0][:, [0, 3]].abs().max()), 4),
          "one_call_equals_three": equal,
-         "rounds_ms": {"global_motion": [round(x, 4) for x in t_fit], "camera_path": [round(x, 4) for x in t_path],
-                       "warp_frames": [round(x, 4) for x in t_warp], "batch_stabilize": [round(x, 4) for x in t_whole]}}
+         "rounds_ms": {names[0]: [round(x, 4) for x in t_fit], names[1]: [round(x, 4) for x in t_path],
+                       names[2]: [round(x, 4) for x in t_warp], names[3]: [round(x, 4) for x in t_whole]}}
+    if nparam == 8:
+        r["largest_perspective_term"] = float(warps[0][:, 6:].abs().max())
     print(json.dumps(r), flush=True)
-    b.close()
     return r
 
 
@@ -109,15 +138,15 @@ def main():
     old = capi.set_tuning(contract=1)
     rows = []
     try:
-        rows.append(measure(gray, 1, tstream, dev, args.rounds, args.steps))
+        rows += measure(gray, 1, tstream, dev, args.rounds, args.steps)
         rgb = gray[..., None].expand(-1, -1, -1, 3).contiguous()
         del gray
-        rows.append(measure(rgb, 3, tstream, dev, args.rounds, args.steps))
+        rows += measure(rgb, 3, tstream, dev, args.rounds, args.steps)
     finally:
         capi.restore_tuning(old)
     doc = {"tool": "tools/stabilize_probe.py", "build_id": capi.build_id(), "device": torch.cuda.get_device_name(0),
            "geometry": f"{W}x{H}, operating point 2, TV on, fused contract for the flow, SEQUENCE | REVERSE context, one texture in "
-                       f"periodic motion of at most ~1.2 px per pair; affine, {ROUNDS} rounds, thresh {THRESH}, fb_check = 1; "
+                       f"periodic motion of at most ~1.2 px per pair; affine and projective, {ROUNDS} rounds, thresh {THRESH}, fb_check = 1; "
                        f"Gaussian window radius {RADIUS} sigma {SIGMA}, zoom {ZOOM}, constant border, inside written",
            "basis": "HIP events on one stream, warm-up, the stages timed alternately per round, median round; warp_bytes = "
                     "(frames + 1) * W * H * (2 * noc + 1): every frame read once, out and inside written once; "
