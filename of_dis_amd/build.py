@@ -50,7 +50,8 @@ PER_FILE_FLAGS = {"ofdis_dis.hip": _NO_SLP, "ofdis_tv.hip": _NO_SLP, "ofdis_prep
 
 # The product's units the TEST library links as well (testhooks_path), compiled a second time with TESTHOOK_FLAGS.
 TESTHOOK_UNITS = ["ofdis_interp.hip", "ofdis_tfilter.hip", "ofdis_trajfilter.hip", "ofdis_gmotion.hip", "ofdis_stabilize.hip",
-                  "ofdis_upsample.hip", "ofdis_stereo_lr.hip", "ofdis_pyr.hip", "ofdis_bof.hip", "ofdis_kmeans.hip"]
+                  "ofdis_upsample.hip", "ofdis_stereo_lr.hip", "ofdis_pyr.hip", "ofdis_bof.hip", "ofdis_kmeans.hip",
+                  "ofdis_track.hip", "ofdis_dense_tracks.hip"]
 TESTHOOK_FLAGS = ["-DOFDIS_TEST_LAUNCH_LIMITS"]
 
 

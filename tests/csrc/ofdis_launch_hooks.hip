@@ -2,7 +2,7 @@
 // ofdis::launch_* functions of of_dis_amd/csrc/ofdis_kernels.h, and the two launch limits as variables a test can lower.
 //
 // The test library links the PRODUCT'S OWN units (ofdis_interp, ofdis_tfilter, ofdis_trajfilter, ofdis_gmotion, ofdis_stabilize,
-// ofdis_upsample, ofdis_stereo_lr, ofdis_pyr, ofdis_bof, ofdis_kmeans), compiled with the product's flags plus
+// ofdis_upsample, ofdis_stereo_lr, ofdis_pyr, ofdis_bof, ofdis_kmeans, ofdis_track, ofdis_dense_tracks), compiled with the product's flags plus
 // -DOFDIS_TEST_LAUNCH_LIMITS.  Under that
 // define quad_max_blocks() and grid_max_blocks() (ofdis_kernels.h) read the two variables below instead of returning the
 // product's constants.  Both are read in host code only (quad_grid, grid_for), so the kernels here are the product's kernels;

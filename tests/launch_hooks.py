@@ -1,9 +1,10 @@
-"""The launch hooks of the TEST library (tests/csrc/ofdis_launch_hooks.hip): the product's own launchers behind thin C wrappers, and
+"""The launch hooks of the TEST library (tests/csrc/ofdis_launch_hooks*.hip): the product's own launchers behind thin C wrappers, and
 the two launch limits of of_dis_amd/csrc/ofdis_kernels.h -- QUAD_MAX_BLOCKS (workgroups of one launch of a quad kernel: the
 launcher walks the frames in chunks) and GRID_MAX_BLOCKS (grid of a grid-stride kernel: the kernel loops) -- as variables of
 that library which a test lowers.  Shared by tests/test_launch_geometry.py (CPU) and tests/test_gpu_launch_limits.py; the
 pyramid's launchers and their kernel selection (pyr_base_variant, pyr_planes_variant) also by tests/pyr_classes.py,
-tests/test_pyr_ref.py (CPU) and tests/test_gpu_pyramid.py.
+tests/test_pyr_ref.py (CPU) and tests/test_gpu_pyramid.py; the level launchers with a free UpGeom by
+tests/test_gpu_level_routes.py.
 
 libofdis_hip.so is a separate object with the limits compiled in as constants: nothing here changes what it does."""
 import contextlib
@@ -36,6 +37,15 @@ _SIGNATURES = {
     "mirror_u8": [_VP, _VP] + [_I] * 4 + [_VP],
     "lr_check": [_VP] * 3 + [_I] * 3 + [_F, _F, _VP],
     "disparity_fill": [_VP] * 3 + [_I] * 4 + [_VP],
+    # tests/csrc/ofdis_launch_hooks_levels.hip
+    "upsample_crop_enc": [_VP, _VP, _I] + _UPG + [_I, _I, _F, _F, _VP],
+    "upsample_bidir": [_VP] * 6 + [_I] + _UPG + [_F, _F, _VP],
+    "projective_level": [_VP, _VP, _I] + _UPG + [_I, _F, _F, _F, _VP, _VP, _VP, _VP],
+    "projective_compensate_level": [_VP] * 3 + [_I] + _UPG + [_F, _F, _F, _VP, _VP, _VP],
+    "track_level": [_VP, _VP, _I] + _UPG + [_VP, _VP, _I, _I, _F, _F, _VP, _VP, _VP],
+    "dense_tracks_level": [_VP] * 3 + [_I] + _UPG + [_I] * 5 + [_F, _F, _I] + [_VP] * 6,
+    "upsample_lr": [_VP] * 6 + [_I] + _UPG + [_I, _F, _F, _VP],
+    "lr_materialise": [_VP] * 4 + [_I] + _UPG + [_VP],
 }
 
 
@@ -59,6 +69,7 @@ def hooks():
     L.ofdis_test_km_finish_split.argtypes, L.ofdis_test_km_finish_split.restype = [_I], _I
     L.ofdis_test_pyr_base_variant.argtypes, L.ofdis_test_pyr_base_variant.restype = [_VP] + [_I] * 4 + [_SZ, _SZ], _I
     L.ofdis_test_pyr_planes_variant.argtypes, L.ofdis_test_pyr_planes_variant.restype = [_I] * 5, _I
+    L.ofdis_test_upsample_lr_fuses.argtypes, L.ofdis_test_upsample_lr_fuses.restype = [_I], _I
     return L
 
 
@@ -142,6 +153,11 @@ def pyr_planes_variant(w, h, noc, pad, want_down):
     """pyr_planes_variant (ofdis_pyr.hip): 0 = pyr_planes_kernel (and a pyr_down launch where `down` is wanted), 1 =
     pyr_planes_gray4_kernel, 2 = pyr_planes_gray4_kernel writing `down` too"""
     return int(hooks().ofdis_test_pyr_planes_variant(w, h, noc, pad, int(bool(want_down))))
+
+
+def upsample_lr_fuses(wo):
+    """upsample_lr_fuses (ofdis_stereo_lr.hip): whether ofdis_batch_upsample_lr takes the fused kernel at original width wo"""
+    return bool(hooks().ofdis_test_upsample_lr_fuses(wo))
 
 
 def trips(total):

@@ -317,11 +317,11 @@ def test_fb_check_moving_square(gpu):
 
 # ------------------------------------------------------------------ ofdis_batch_upsample_bidir
 @pytest.mark.parametrize("w,h,opp,noc,n,first,count", [
-    (256, 112, 2, 1, 3, 0, None),    # x 4, no crop
+    (256, 112, 2, 1, 3, 0, None),    # sc_l = 1 (x 2), no crop
     (333, 251, 1, 1, 3, 1, 2),       # odd size: asymmetric crop, sub-range
     (321, 239, 3, 1, 2, 0, 1),       # sc_l = 0 (x 1), odd size, crop
     (250, 110, 2, 3, 3, 2, 1),       # RGB, crop, last frame
-    (1024, 436, 2, 1, 2, 0, None),   # the measured geometry (x 4)
+    (1024, 436, 2, 1, 2, 0, None),   # the measured geometry: sc_l = 3 (x 8)
 ])
 def test_upsample_bidir(gpu, w, h, opp, noc, n, first, count):
     p = oppoint(opp, w, h, noc=noc)
