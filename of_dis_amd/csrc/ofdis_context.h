@@ -25,32 +25,38 @@ namespace ofdis {
 // The launchers of one arithmetic contract (ofdis_kernels.h / ofdis_launchers.inc): every kernel file is compiled once per
 // contract into ofdis::exact and ofdis::fused; a context fixes its contract at creation (ofdis_tuning::contract) and
 // launches through its table.
+// The list is stated once, as X(member, function of ofdis_launchers.inc): the struct and both tables (ofdis_context.hip) are
+// made from it, every entry bound by name.
+#define OFDIS_LAUNCHERS(X)                                                     \
+  X(patch_optimize, launch_patch_optimize)                                     \
+  X(patch_pixel_weights_supported, patch_pixel_weights_supported)              \
+  X(densify, launch_densify)                                                   \
+  X(patch_p_reference_order, launch_patch_p_reference_order)                   \
+  X(warp, launch_warp)                                                         \
+  X(derivatives, launch_derivatives)                                           \
+  X(tv_prep_supported, tv_prep_supported)                                      \
+  X(tv_prep_densifies, tv_prep_densifies)                                      \
+  X(tv_prep, launch_tv_prep)                                                   \
+  X(tv_system, launch_tv_system)                                               \
+  X(sor, launch_sor)                                                           \
+  X(tv_fused_supported, tv_fused_supported)                                    \
+  X(tv_fused_params_ok, tv_fused_params_ok)                                    \
+  X(tv_fused_mode, tv_fused_mode)                                              \
+  X(tv_fused, launch_tv_fused)                                                 \
+  X(tv_finish_records, launch_tv_finish_records)                               \
+  X(to_diag, launch_to_diag)                                                   \
+  X(from_diag, launch_from_diag)                                               \
+  X(tv_finish, launch_tv_finish)                                               \
+  X(flow_split, launch_flow_split)                                             \
+  X(de_system, launch_de_system)                                               \
+  X(de_sor, launch_de_sor)                                                     \
+  X(de_update, launch_de_update)                                               \
+  X(de_fused_supported, de_fused_supported)                                    \
+  X(de_fused, launch_de_fused)
 struct Launchers {
-  decltype(&exact::launch_patch_optimize) patch_optimize;
-  decltype(&exact::patch_pixel_weights_supported) patch_pixel_weights_supported;
-  decltype(&exact::launch_densify) densify;
-  decltype(&exact::launch_patch_p_reference_order) patch_p_reference_order;
-  decltype(&exact::launch_warp) warp;
-  decltype(&exact::launch_derivatives) derivatives;
-  decltype(&exact::tv_prep_supported) tv_prep_supported;
-  decltype(&exact::tv_prep_densifies) tv_prep_densifies;
-  decltype(&exact::launch_tv_prep) tv_prep;
-  decltype(&exact::launch_tv_system) tv_system;
-  decltype(&exact::launch_sor) sor;
-  decltype(&exact::tv_fused_supported) tv_fused_supported;
-  decltype(&exact::tv_fused_params_ok) tv_fused_params_ok;
-  decltype(&exact::tv_fused_mode) tv_fused_mode;
-  decltype(&exact::launch_tv_fused) tv_fused;
-  decltype(&exact::launch_tv_finish_records) tv_finish_records;
-  decltype(&exact::launch_to_diag) to_diag;
-  decltype(&exact::launch_from_diag) from_diag;
-  decltype(&exact::launch_tv_finish) tv_finish;
-  decltype(&exact::launch_flow_split) flow_split;
-  decltype(&exact::launch_de_system) de_system;
-  decltype(&exact::launch_de_sor) de_sor;
-  decltype(&exact::launch_de_update) de_update;
-  decltype(&exact::de_fused_supported) de_fused_supported;
-  decltype(&exact::launch_de_fused) de_fused;
+#define OFDIS_LAUNCHER_MEMBER(member, function) decltype(&exact::function) member;
+  OFDIS_LAUNCHERS(OFDIS_LAUNCHER_MEMBER)
+#undef OFDIS_LAUNCHER_MEMBER
 };
 const Launchers& launchers(int contract);
 

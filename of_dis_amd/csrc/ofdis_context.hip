@@ -7,15 +7,18 @@ using namespace ofdis;
 
 namespace ofdis {
 
-#define OFDIS_LAUNCHER_TABLE(ns)                                                                                        \
-  {ns::launch_patch_optimize, ns::patch_pixel_weights_supported, ns::launch_densify, ns::launch_patch_p_reference_order, ns::launch_warp, ns::launch_derivatives, ns::tv_prep_supported, ns::tv_prep_densifies,      \
-   ns::launch_tv_prep, ns::launch_tv_system, ns::launch_sor, ns::tv_fused_supported, ns::tv_fused_params_ok,            \
-   ns::tv_fused_mode, ns::launch_tv_fused, ns::launch_tv_finish_records, ns::launch_to_diag, ns::launch_from_diag,      \
-   ns::launch_tv_finish, ns::launch_flow_split, ns::launch_de_system, ns::launch_de_sor, ns::launch_de_update,          \
-   ns::de_fused_supported, ns::launch_de_fused}
-const Launchers kExactLaunchers = OFDIS_LAUNCHER_TABLE(exact);
-const Launchers kFusedLaunchers = OFDIS_LAUNCHER_TABLE(fused);
-#undef OFDIS_LAUNCHER_TABLE
+template <int CONTRACT>
+static constexpr Launchers launcher_table() {
+  Launchers t{};
+#define OFDIS_LAUNCHER_ENTRY(member, function)                         \
+  if constexpr (CONTRACT) t.member = fused::function;                  \
+  else t.member = exact::function;
+  OFDIS_LAUNCHERS(OFDIS_LAUNCHER_ENTRY)
+#undef OFDIS_LAUNCHER_ENTRY
+  return t;
+}
+constexpr Launchers kExactLaunchers = launcher_table<0>();
+constexpr Launchers kFusedLaunchers = launcher_table<1>();
 const Launchers& launchers(int contract) { return contract ? kFusedLaunchers : kExactLaunchers; }
 
 // Kernel-selection knobs (include/ofdis.h: ofdis_tuning): read ONCE from the environment, changed only through

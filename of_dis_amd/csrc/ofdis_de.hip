@@ -211,7 +211,9 @@ __global__ __launch_bounds__(256) void de_system_kernel(const DeSystemArgs a) {
 
 hipError_t launch_de_system(const DeSystemArgs& a, hipStream_t s) {
   const int tiles = ((a.t.w + DT - 1) / DT) * ((a.t.h + DTH - 1) / DTH);
-  hipLaunchKernelGGL(de_system_kernel, dim3(((a.t.nframes + 7) / 8) * 8 * tiles), dim3(256), 0, s, a);
+  dim3 g;
+  if (xcd_grid(a.t.nframes, tiles, g) != hipSuccess) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(de_system_kernel, g, dim3(256), 0, s, a);
   return hipGetLastError();
 }
 
@@ -421,27 +423,19 @@ hipError_t launch_de_sor(const DeSorArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(de_sor_serial_kernel, dim3((a.t.nframes + 63) / 64), dim3(64), 0, s, a);
     return hipGetLastError();
   }
-  const int R = h <= 16 ? 16 : (h <= 32 ? 32 : 64);
+  const int R = slot_rows(h);
   const int waves = (a.t.nframes + 64 / R - 1) / (64 / R);
   const int threads = ((h + 63) / 64) * 64;
   for (int left = a.iterations; left > 0;) {   // at most four sweeps share a pass (three above 64 rows)
     const int ns = h <= 64 ? (left < 4 ? left : 4) : (left < 3 ? left : 3);
-    if (h <= 64) {
-      const dim3 g((waves + 3) / 4), b(256);
-      switch (ns) {
-        case 1: hipLaunchKernelGGL((de_sor_kernel<1, PD, 0>), g, b, 0, s, a, R); break;
-        case 2: hipLaunchKernelGGL((de_sor_kernel<2, PD, 0>), g, b, 0, s, a, R); break;
-        case 3: hipLaunchKernelGGL((de_sor_kernel<3, PD, 0>), g, b, 0, s, a, R); break;
-        default: hipLaunchKernelGGL((de_sor_kernel<4, PD, 0>), g, b, 0, s, a, R); break;
-      }
-    } else {
-      const dim3 g(a.t.nframes), b(threads);
-      switch (ns) {
-        case 1: hipLaunchKernelGGL((de_sor_kernel<1, PD, 1024>), g, b, 0, s, a, 64); break;
-        case 2: hipLaunchKernelGGL((de_sor_kernel<2, PD, 1024>), g, b, 0, s, a, 64); break;
-        default: hipLaunchKernelGGL((de_sor_kernel<3, PD, 1024>), g, b, 0, s, a, 64); break;
-      }
-    }
+    if (h <= 64)
+      with_constant<1, 2, 3, 4>(ns, [&](auto NS) {
+        hipLaunchKernelGGL((de_sor_kernel<decltype(NS)::value, PD, 0>), dim3((waves + 3) / 4), dim3(256), 0, s, a, R);
+      });
+    else
+      with_constant<1, 2, 3>(ns, [&](auto NS) {
+        hipLaunchKernelGGL((de_sor_kernel<decltype(NS)::value, PD, 1024>), dim3(a.t.nframes), dim3(threads), 0, s, a, 64);
+      });
     left -= ns;
   }
   return hipGetLastError();
@@ -659,22 +653,17 @@ hipError_t launch_de_fused(const DeFusedArgs& a, hipStream_t s) {
   if (!de_fused_supported(a.t, a.iterations) || a.n_inner < 1 || !tv_fused_params_ok(a.quarter_alpha, a.half_delta_over3, a.half_gamma_over3))
     return hipErrorInvalidValue;
   const int h = a.t.h;
-  const int R = h <= 16 ? 16 : (h <= 32 ? 32 : 64);
+  const int R = slot_rows(h);
   const int waves = (a.t.nframes + 64 / R - 1) / (64 / R);
   const dim3 g((waves + 3) / 4), b(256);
   const bool bright = a.half_delta_over3 != 0.0f;
-#define OFDIS_DE_FUSED(NS, NOC)                                                                  \
-  if (bright) hipLaunchKernelGGL((de_fused_kernel<NS, true, NOC>), g, b, 0, s, a, R);            \
-  else hipLaunchKernelGGL((de_fused_kernel<NS, false, NOC>), g, b, 0, s, a, R)
-#define OFDIS_DE_FUSED_NS(NOC)                                                                   \
-  switch (a.iterations) {                                                                        \
-    case 1: OFDIS_DE_FUSED(1, NOC); break;                                                       \
-    case 2: OFDIS_DE_FUSED(2, NOC); break;                                                       \
-    default: OFDIS_DE_FUSED(3, NOC); break;                                                      \
-  }
-  if (a.t.noc == 3) { OFDIS_DE_FUSED_NS(3) } else { OFDIS_DE_FUSED_NS(1) }
-#undef OFDIS_DE_FUSED_NS
-#undef OFDIS_DE_FUSED
+  with_constant<1, 2, 3>(a.iterations, [&](auto NS) {
+    with_constant<false, true>(bright, [&](auto BRIGHT) {
+      with_constant<3, 1>(a.t.noc, [&](auto NOC) {
+        hipLaunchKernelGGL((de_fused_kernel<decltype(NS)::value, decltype(BRIGHT)::value, decltype(NOC)::value>), g, b, 0, s, a, R);
+      });
+    });
+  });
   return hipGetLastError();
 }
 

@@ -324,7 +324,7 @@ __host__ __device__ __forceinline__ size_t sdiag_index(int frame, int x, int y, 
 
 // Blocks of one frame stay on one XCD: the dispatcher places block n on XCD n % 8 (observed, used for L2
 // affinity only -- correctness does not depend on it), so block n works on frame (n/8/bpf)*8 + n%8.
-// Launch ((nframes+7)/8)*8*blocks_per_frame blocks and skip frame >= nframes.
+// Launch the grid of xcd_grid (below) and skip frame >= nframes.
 // With fewer than 8 frames that mapping would leave whole XCDs without work (one 1080p frame on 32 of the 256 CUs:
 // measured 8x slower), so there the blocks of a frame are simply consecutive and spread over all XCDs.
 __host__ __device__ __forceinline__ void xcd_frame_map(int n, int blocks_per_frame, int nframes, int& frame, int& blk) {
@@ -337,6 +337,14 @@ __host__ __device__ __forceinline__ void xcd_frame_map(int n, int blocks_per_fra
   const int m = n >> 3;
   frame = (m / blocks_per_frame) * 8 + xcd;
   blk = m % blocks_per_frame;
+}
+// The grid that mapping expects, for every launcher whose kernel calls it: the frames padded to a multiple of 8.  Counted in
+// 64 bits; more than 2^31-1 blocks (the kernels index them with an int) are refused.
+inline hipError_t xcd_grid(int nframes, long long blocks_per_frame, dim3& grid) {
+  const long long blocks = (long long)((nframes + 7) / 8) * 8 * blocks_per_frame;
+  if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+  grid = dim3((unsigned)blocks);
+  return hipSuccess;
 }
 
 }  // namespace ofdis

@@ -1312,101 +1312,32 @@ __global__ __launch_bounds__(256, 3) void patch_optimize_rgb12x_kernel(const Dis
   }
 }
 
-// (a template so that the exact contract's object never instantiates the kernel above)
-template <bool FUSED>
-hipError_t launch_patch_optimize_rgb12(const DisArgs& a, hipStream_t s) {
-  const int wpf = (a.g.nop + 3) / 4;  // four patches per wavefront
-  const int blocks_per_frame = (wpf + 3) / 4;
-  const dim3 gd(((a.nframes + 7) / 8) * 8 * blocks_per_frame), bd(256);
-  const bool l1 = a.costfct != 0;
-#define OFDIS_P16L(KERNEL, NOC, BS)                                                                          \
-  do {                                                                                                       \
-    if (a.stereo) {                                                                                          \
-      if (l1) hipLaunchKernelGGL((KERNEL<1, NOC, true, BS>), gd, bd, 0, s, a);                               \
-      else hipLaunchKernelGGL((KERNEL<0, NOC, true, BS>), gd, bd, 0, s, a);                                  \
-    } else {                                                                                                 \
-      if (l1) hipLaunchKernelGGL((KERNEL<1, NOC, false, BS>), gd, bd, 0, s, a);                              \
-      else hipLaunchKernelGGL((KERNEL<0, NOC, false, BS>), gd, bd, 0, s, a);                                 \
-    }                                                                                                        \
-  } while (0)
-#define OFDIS_P16L_GEOM(KERNEL)                                                                              \
-  do {                                                                                                       \
-    if (a.g.P == 8) OFDIS_P16L(KERNEL, 3, 2);                                                                \
-    else if (a.g.noc == 1) OFDIS_P16L(KERNEL, 1, 3);                                                         \
-    else OFDIS_P16L(KERNEL, 3, 3);                                                                           \
-  } while (0)
-  if constexpr (FUSED) OFDIS_P16L_GEOM(patch_optimize_rgb12_kernel);
-  else OFDIS_P16L_GEOM(patch_optimize_rgb12x_kernel);
-#undef OFDIS_P16L_GEOM
-#undef OFDIS_P16L
-  return hipGetLastError();
-}
-
-// Does launch_patch_optimize run a kernel that honours DisArgs::pixw for these arguments?  (The 16-lanes-per-patch RGB 12x12
-// kernels of either contract; the caller passes pixw to the patch kernel and to the densification only then.)
+// Does launch_patch_optimize run a kernel that honours DisArgs::pixw for these arguments?  (The caller passes pixw to the patch
+// kernel and to the densification only then.)
 bool patch_pixel_weights_supported(const DisArgs& a, const ofdis_tuning* tnp) {
-  const ofdis_tuning tn = tnp ? *tnp : tuning();
-  const int rgb12_lpp = tn.rgb12_lpp == 0 ? 16 : tn.rgb12_lpp;
-  return a.g.novals == 432 && a.g.P == 12 && !a.stereo && (a.costfct == 0 || a.costfct == 1) && tn.rgb12 && rgb12_lpp == 16;
+  return choose_patch_kernel(a.g, a.stereo, a.costfct, true, tnp ? *tnp : tuning(), kFusedContract).pixw;
 }
 
 hipError_t launch_patch_optimize(const DisArgs& a, hipStream_t s, const ofdis_tuning* tnp) {
-  const int M = (a.g.novals + 63) / 64;
-  const bool full = a.g.novals == 64 * M;
   const ofdis_tuning tn = tnp ? *tnp : tuning();
-  const bool gray8 = a.g.noc == 1 && a.g.P == 8 && tn.gray8;
-  // RGB 12x12 (operating points 3 and 4, BASELINE configs[3]): 432 entries, 6 full groups of 64 + 48.  ofdis_tuning::rgb12_lpp = 32:
-  // two patches per wavefront (the scalar solve, predicates and every reduction instruction shared by two patches:
-  // 929 -> 705 instructions per patch and iteration, 82 -> 127 VGPRs).  Measured on configs[3] the same 19.6 +- 0.4 ms per
-  // 16-pair level-1 launch either way -- patches that reset early leave their wavefront's other half running alone
-  // (PMC: 18 % fewer VALU instructions, same time) -- so one patch per wavefront stayed the default until the
-  // 16-lanes-per-patch kernels (round 4) took it over.
-  const int rgb12_lpp = tn.rgb12_lpp == 0 ? 16 : tn.rgb12_lpp;
-  const bool rgb12 = a.g.novals == 432 && !a.stereo && (a.costfct == 0 || a.costfct == 1) && tn.rgb12;
-  // 12x12 patches, RGB or gray, and RGB 8x8 patches, flow or stereo, have their own mapping (16 lanes per patch, four
-  // patches per wavefront: ofdis_tuning::rgb12 with rgb12_lpp = 16, the default)
-  const bool p12 = ((a.g.P == 12 && (a.g.noc == 1 || a.g.noc == 3)) || (a.g.P == 8 && a.g.noc == 3)) &&
-                   (a.costfct == 0 || a.costfct == 1) && tn.rgb12;
-  if (p12 && rgb12_lpp == 16) return launch_patch_optimize_rgb12<kFusedContract>(a, s);
-  if (a.pixw) return hipErrorInvalidValue;  // (only the kernels above write the compact weights)
-  const int lpp = (M <= 1) ? (gray8 ? 4 : 8) : ((rgb12 && rgb12_lpp == 32) ? 32 : 64);  // lanes per patch
-  const int ppw = 64 / lpp;                           // patches per wavefront
-  const int wpf = (a.g.nop + ppw - 1) / ppw;          // wavefronts per frame
-  const bool fast = gray8 && M <= 1;
-  const int wpb = (fast && wpf < 4) ? wpf : 4;        // wavefronts per block (the generic kernels assume 4)
-  const int blocks_per_frame = (wpf + wpb - 1) / wpb;
-  const int grid = ((a.nframes + 7) / 8) * 8 * blocks_per_frame;
-  const dim3 gd(grid), bd(wpb * 64);
+  const PatchKernel k = choose_patch_kernel(a.g, a.stereo, a.costfct, a.pixw != nullptr, tn, kFusedContract);
+  dim3 gd;
+  if (k.row < 0 || xcd_grid(a.nframes, k.blocks_per_frame, gd) != hipSuccess) return hipErrorInvalidValue;
+  const dim3 bd(k.threads);
   DisArgs ag = a;  // the gray 8x8 kernel's copy
   ag.reload_window = !tn.patch_window_reuse;
-  if (M <= 1 && gray8 && a.stereo)
-    hipLaunchKernelGGL((patch_optimize_gray8_kernel<-1, true>), gd, bd, 0, s, ag);
-  else if (M <= 1 && gray8 && a.costfct == 0)
-    hipLaunchKernelGGL((patch_optimize_gray8_kernel<0, false>), gd, bd, 0, s, ag);
-  else if (M <= 1 && gray8)
-    hipLaunchKernelGGL((patch_optimize_gray8_kernel<-1, false>), gd, bd, 0, s, ag);
-  else if (M <= 1 && full && a.costfct == 0)
-    hipLaunchKernelGGL((patch_optimize_kernel<1, 8, 64, 0>), gd, bd, 0, s, a);
-  else if (M <= 1 && full)
-    hipLaunchKernelGGL((patch_optimize_kernel<1, 8, 64, -1>), gd, bd, 0, s, a);
-  else if (M <= 1)
-    hipLaunchKernelGGL((patch_optimize_kernel<1, 8, 0, -1>), gd, bd, 0, s, a);
-  else if (M <= 3)
-    hipLaunchKernelGGL((patch_optimize_kernel<3, 64, 0, -1>), gd, bd, 0, s, a);
-  else if (rgb12 && lpp == 32 && a.costfct == 0)
-    hipLaunchKernelGGL((patch_optimize_kernel<7, 32, 432, 0>), gd, bd, 0, s, a);
-  else if (rgb12 && lpp == 32)
-    hipLaunchKernelGGL((patch_optimize_kernel<7, 32, 432, 1>), gd, bd, 0, s, a);
-  else if (rgb12 && a.costfct == 0)
-    hipLaunchKernelGGL((patch_optimize_kernel<7, 64, 432, 0>), gd, bd, 0, s, a);
-  else if (rgb12)
-    hipLaunchKernelGGL((patch_optimize_kernel<7, 64, 432, 1>), gd, bd, 0, s, a);
-  else if (M <= 7)
-    hipLaunchKernelGGL((patch_optimize_kernel<7, 64, 0, -1>), gd, bd, 0, s, a);
-  else if (M <= 12)
-    hipLaunchKernelGGL((patch_optimize_kernel<12, 64, 0, -1>), gd, bd, 0, s, a);
-  else
-    return hipErrorInvalidValue;
+  with_index<kNumPatchKernels>(k.row, [&](auto ROW) {
+    constexpr PatchInstance i = kPatchKernels[decltype(ROW)::value];
+    if constexpr (i.family == PatchKernel::LANES16 && kFusedContract) {  // (the exact contract's object never instantiates it)
+      hipLaunchKernelGGL((patch_optimize_rgb12_kernel<i.t[0], i.t[1], i.t[2] != 0, i.t[3]>), gd, bd, 0, s, a);
+    } else if constexpr (i.family == PatchKernel::LANES16) {
+      hipLaunchKernelGGL((patch_optimize_rgb12x_kernel<i.t[0], i.t[1], i.t[2] != 0, i.t[3]>), gd, bd, 0, s, a);
+    } else if constexpr (i.family == PatchKernel::GRAY8) {
+      hipLaunchKernelGGL((patch_optimize_gray8_kernel<i.t[0], i.t[1] != 0>), gd, bd, 0, s, ag);
+    } else {
+      hipLaunchKernelGGL((patch_optimize_kernel<i.t[0], i.t[1], i.t[2], i.t[3]>), gd, bd, 0, s, a);
+    }
+  });
   return hipGetLastError();
 }
 
@@ -1665,10 +1596,11 @@ hipError_t launch_patch_p_reference_order(const LevelGeom& g, int nframes, const
 
 hipError_t launch_densify(const DensifyArgs& a_in, hipStream_t s) {
   DensifyArgs a = a_in;
-  if (a.flow_aos && !a.stereo && !a.cg_p && a.g.noc == 1 && a.g.P == 8 && a.g.steps == 4 && a.g.offw < 4 && a.g.offh < 4) {
+  dim3 gd;
+  if (a.flow_aos && !a.stereo && !a.cg_p && densify_quad_geometry(a.g)) {
     const int nbx = (a.g.w + 3 - a.g.offw) / 4 + 1;  // quads per row: the last one holds column w - 1
-    const int blocks_per_frame = (nbx * a.g.h + 255) / 256;
-    hipLaunchKernelGGL(densify_quad_kernel, dim3(((a.nframes + 7) / 8) * 8 * blocks_per_frame), dim3(256), 0, s, a, nbx);
+    if (xcd_grid(a.nframes, (nbx * a.g.h + 255) / 256, gd) != hipSuccess) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(densify_quad_kernel, gd, dim3(256), 0, s, a, nbx);
     return hipGetLastError();
   }
   {
@@ -1678,19 +1610,14 @@ hipError_t launch_densify(const DensifyArgs& a_in, hipStream_t s) {
   }
   // (A patch-major variant -- one wavefront per 32x32 tile accumulating in LDS, one contiguous 256-byte weight read per
   // patch -- was measured at twice the time of this gather: ~90 dependent LDS read-modify-write rounds per tile.)
-  const int blocks_per_frame = (a.g.w * a.g.h + 255) / 256;
-  const long long blocks = (long long)((a.nframes + 7) / 8) * 8 * blocks_per_frame;
-  if (a.cg_p) {  // forward-backward merging: 16 x 16 pixel tiles
-    const long long fblocks = (long long)((a.nframes + 7) / 8) * 8 * ((a.g.w + 15) / 16) * ((a.g.h + 15) / 16);
-    if (a.g.noc == 1) {
-      if (a.flow_aos) hipLaunchKernelGGL((densify_kernel<false, 1>), dim3((unsigned)fblocks), dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((densify_kernel<true, 1>), dim3((unsigned)fblocks), dim3(256), 0, s, a);
-    } else {
-      if (a.flow_aos) hipLaunchKernelGGL((densify_kernel<false, 3>), dim3((unsigned)fblocks), dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((densify_kernel<true, 3>), dim3((unsigned)fblocks), dim3(256), 0, s, a);
-    }
-  } else if (a.flow_aos) hipLaunchKernelGGL((densify_kernel<false, 0>), dim3((unsigned)blocks), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((densify_kernel<true, 0>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+  // forward-backward merging: 16 x 16 pixel tiles, and the channel count of the complementary grid's weights
+  const long long blocks_per_frame = a.cg_p ? (long long)((a.g.w + 15) / 16) * ((a.g.h + 15) / 16) : (a.g.w * a.g.h + 255) / 256;
+  if (xcd_grid(a.nframes, blocks_per_frame, gd) != hipSuccess) return hipErrorInvalidValue;
+  with_constant<0, 1, 3>(!a.cg_p ? 0 : a.g.noc == 1 ? 1 : 3, [&](auto FBN) {
+    with_constant<false, true>(a.flow_aos == nullptr, [&](auto PLANAR) {
+      hipLaunchKernelGGL((densify_kernel<decltype(PLANAR)::value, decltype(FBN)::value>), gd, dim3(256), 0, s, a);
+    });
+  });
   return hipGetLastError();
 }
 

@@ -541,7 +541,7 @@ int tv_fused_mode(const FusedArgs& a, const FusedXcu* x) {
   if (h > 64) return 0;  // two to four wavefronts per strip (ofdis_fused_tall.hip): the throughput mapping only, whatever the batch
   if (a.t.noc == 3)  // RGB: one frame per strip, one wavefront per frame or -- tp_pipe -- per fixed-point iteration
     return (a.tp_pipe && a.S == 1 && a.n_inner >= 2 && a.n_inner <= MW_MAX_ITERS) ? 1 : 0;
-  const int R = h <= 16 ? 16 : (h <= 32 ? 32 : 64);
+  const int R = slot_rows(h);
   const int groups = (a.t.nframes + 64 / R - 1) / (64 / R);
   const int total = a.total_frames > 0 ? a.total_frames : a.t.nframes;
   if (x && x->xbuf && x->err && a.S == 1 && a.n_inner >= 2 && groups <= x->max_groups && total <= MW_MAX_BATCH_FRAMES) return 3;
@@ -562,7 +562,7 @@ hipError_t launch_tv_fused(const FusedArgs& a, hipStream_t s, bool* wrote_flow, 
     if (wrote_flow) *wrote_flow = a.flow_out != nullptr;
     return launch_tv_fused_tall(a, s, a.tall_group);
   }
-  const int R = h <= 16 ? 16 : (h <= 32 ? 32 : 64);
+  const int R = slot_rows(h);
   const int G = 64 / R;
   const int nstrips = a.t.nframes / a.S;
   const int waves = (nstrips + G - 1) / G;
@@ -572,37 +572,22 @@ hipError_t launch_tv_fused(const FusedArgs& a, hipStream_t s, bool* wrote_flow, 
   const int mode = tv_fused_mode(a, x);
   if (wrote_flow) *wrote_flow = a.flow_out != nullptr;  // every mapping writes the refined AoS flow itself
   if (mode == 3) return launch_tv_fused_xcu(a, *x, waves, R, s);
-  if (a.t.noc == 3) {
-    if (a.S != 1) return hipErrorInvalidValue;
-#define OFDIS_FUSED_RGB(NS)                                                                                            \
-  if (mode == 1) {                                                                                                     \
-    if (bright) hipLaunchKernelGGL((tv_fused_kernel<NS, true, 1, 3>), dim3(waves), dim3(64 * a.n_inner), 0, s, a, R);  \
-    else hipLaunchKernelGGL((tv_fused_kernel<NS, false, 1, 3>), dim3(waves), dim3(64 * a.n_inner), 0, s, a, R);        \
-  } else if (bright) hipLaunchKernelGGL((tv_fused_kernel<NS, true, 0, 3>), dim3(blocks), dim3(256), 0, s, a, R);       \
-  else hipLaunchKernelGGL((tv_fused_kernel<NS, false, 0, 3>), dim3(blocks), dim3(256), 0, s, a, R)
-    switch (a.iterations) {
-      case 1: OFDIS_FUSED_RGB(1); break;
-      case 2: OFDIS_FUSED_RGB(2); break;
-      default: OFDIS_FUSED_RGB(3); break;
-    }
-#undef OFDIS_FUSED_RGB
-    return hipGetLastError();
-  }
-#define OFDIS_FUSED_LAUNCH(NS)                                                                                         \
-  if (mode == 2) {                                                                                                     \
-    if (bright) hipLaunchKernelGGL((tv_fused_kernel<NS, true, 2>), dim3(waves), dim3(128 * a.n_inner), 0, s, a, R);    \
-    else hipLaunchKernelGGL((tv_fused_kernel<NS, false, 2>), dim3(waves), dim3(128 * a.n_inner), 0, s, a, R);          \
-  } else if (mode == 1) {                                                                                              \
-    if (bright) hipLaunchKernelGGL((tv_fused_kernel<NS, true, 1>), dim3(waves), dim3(64 * a.n_inner), 0, s, a, R);     \
-    else hipLaunchKernelGGL((tv_fused_kernel<NS, false, 1>), dim3(waves), dim3(64 * a.n_inner), 0, s, a, R);           \
-  } else if (bright) hipLaunchKernelGGL((tv_fused_kernel<NS, true, 0>), dim3(blocks), dim3(256), 0, s, a, R);          \
-  else hipLaunchKernelGGL((tv_fused_kernel<NS, false, 0>), dim3(blocks), dim3(256), 0, s, a, R)
-  switch (a.iterations) {
-    case 1: OFDIS_FUSED_LAUNCH(1); break;
-    case 2: OFDIS_FUSED_LAUNCH(2); break;
-    default: OFDIS_FUSED_LAUNCH(3); break;
-  }
-#undef OFDIS_FUSED_LAUNCH
+  if (a.t.noc == 3 && a.S != 1) return hipErrorInvalidValue;
+  // MODE 0: four wavefronts per workgroup; 1 and 2: a workgroup per frame group, one or two wavefronts per fixed-point iteration
+  const dim3 gd(mode == 0 ? blocks : waves), bd(mode == 0 ? 256 : 64 * mode * a.n_inner);
+  auto launch = [&](auto NOC, auto MODE) {
+    with_constant<1, 2, 3>(a.iterations, [&](auto NS) {
+      with_constant<false, true>(bright, [&](auto BRIGHT) {
+        hipLaunchKernelGGL((tv_fused_kernel<decltype(NS)::value, decltype(BRIGHT)::value, decltype(MODE)::value, decltype(NOC)::value>),
+                           gd, bd, 0, s, a, R);
+      });
+    });
+  };
+  using std::integral_constant;
+  if (a.t.noc == 3)  // RGB: MODE 0 or 1 (tv_fused_mode)
+    with_constant<1, 0>(mode, [&](auto MODE) { launch(integral_constant<int, 3>{}, MODE); });
+  else
+    with_constant<2, 1, 0>(mode, [&](auto MODE) { launch(integral_constant<int, 1>{}, MODE); });
   return hipGetLastError();
 }
 

@@ -388,35 +388,18 @@ hipError_t launch_tv_fused_tall(const FusedArgs& a, hipStream_t s, int group) {
   if (h <= 96 && group) RT = h - 64 <= 4 ? 4 : (h - 64 <= 8 ? 8 : (h - 64 <= 16 ? 16 : 32));
   const int cap = group >= 2 ? std::min(group, 7) : 3;
   const int nh = RT < 64 ? std::min(std::min(cap, 64 / RT), nstrips) : 1;
-  if (nh >= 2) {
-    const dim3 bd(64 * (nh + 1)), gd((nstrips + nh - 1) / nh);
-#define OFDIS_TALL_LAUNCH_G(NS)                                                                           \
-  if (a.t.noc == 3) {                                                                                      \
-    if (bright) hipLaunchKernelGGL((tv_fused_tall_kernel<NS, true, true, 3>), gd, bd, 0, s, a, RT);        \
-    else hipLaunchKernelGGL((tv_fused_tall_kernel<NS, false, true, 3>), gd, bd, 0, s, a, RT);              \
-  } else if (bright) hipLaunchKernelGGL((tv_fused_tall_kernel<NS, true, true>), gd, bd, 0, s, a, RT);      \
-  else hipLaunchKernelGGL((tv_fused_tall_kernel<NS, false, true>), gd, bd, 0, s, a, RT)
-    switch (a.iterations) {
-      case 1: OFDIS_TALL_LAUNCH_G(1); break;
-      case 2: OFDIS_TALL_LAUNCH_G(2); break;
-      default: OFDIS_TALL_LAUNCH_G(3); break;
-    }
-#undef OFDIS_TALL_LAUNCH_G
-    return hipGetLastError();
-  }
-  const dim3 bd(64 * ((h + 63) / 64));  // two to four wavefronts per strip
-#define OFDIS_TALL_LAUNCH(NS)                                                                             \
-  if (a.t.noc == 3) {                                                                                      \
-    if (bright) hipLaunchKernelGGL((tv_fused_tall_kernel<NS, true, false, 3>), dim3(nstrips), bd, 0, s, a, 64); \
-    else hipLaunchKernelGGL((tv_fused_tall_kernel<NS, false, false, 3>), dim3(nstrips), bd, 0, s, a, 64);  \
-  } else if (bright) hipLaunchKernelGGL((tv_fused_tall_kernel<NS, true, false>), dim3(nstrips), bd, 0, s, a, 64); \
-  else hipLaunchKernelGGL((tv_fused_tall_kernel<NS, false, false>), dim3(nstrips), bd, 0, s, a, 64)
-  switch (a.iterations) {
-    case 1: OFDIS_TALL_LAUNCH(1); break;
-    case 2: OFDIS_TALL_LAUNCH(2); break;
-    default: OFDIS_TALL_LAUNCH(3); break;
-  }
-#undef OFDIS_TALL_LAUNCH
+  const bool grouped = nh >= 2;  // else two to four wavefronts per strip, a workgroup each
+  const dim3 bd(64 * (grouped ? nh + 1 : (h + 63) / 64)), gd(grouped ? (nstrips + nh - 1) / nh : nstrips);
+  with_constant<1, 2, 3>(a.iterations, [&](auto NS) {
+    with_constant<false, true>(bright, [&](auto BRIGHT) {
+      with_constant<false, true>(grouped, [&](auto GROUPED) {
+        with_constant<1, 3>(a.t.noc, [&](auto NOC) {
+          hipLaunchKernelGGL((tv_fused_tall_kernel<decltype(NS)::value, decltype(BRIGHT)::value, decltype(GROUPED)::value,
+                                                   decltype(NOC)::value>), gd, bd, 0, s, a, grouped ? RT : 64);
+        });
+      });
+    });
+  });
   return hipGetLastError();
 }
 

@@ -470,17 +470,12 @@ hipError_t launch_tv_fused_xcu(const FusedArgs& a, const FusedXcu& x, int waves,
   const unsigned spin = us <= 1 ? 0u : (unsigned)std::min<unsigned long long>(0xffffffffull, (unsigned long long)us * clock_khz / 1000);
   const unsigned flags = x.drop ? XC_FLAG_DROP : 0u;
   const bool bright = a.half_delta_over3 != 0.0f;
-#define OFDIS_XCU_LAUNCH(NS)                                                                                           \
-  if (bright)                                                                                                          \
-    hipLaunchKernelGGL((tv_fused_xcu_kernel<NS, true>), dim3(a.n_inner * G8), dim3(256), 0, s, a, R, G8, x.xbuf, x.err, spin, flags); \
-  else                                                                                                                 \
-    hipLaunchKernelGGL((tv_fused_xcu_kernel<NS, false>), dim3(a.n_inner * G8), dim3(256), 0, s, a, R, G8, x.xbuf, x.err, spin, flags)
-  switch (a.iterations) {
-    case 1: OFDIS_XCU_LAUNCH(1); break;
-    case 2: OFDIS_XCU_LAUNCH(2); break;
-    default: OFDIS_XCU_LAUNCH(3); break;
-  }
-#undef OFDIS_XCU_LAUNCH
+  with_constant<1, 2, 3>(a.iterations, [&](auto NS) {
+    with_constant<false, true>(bright, [&](auto BRIGHT) {
+      hipLaunchKernelGGL((tv_fused_xcu_kernel<decltype(NS)::value, decltype(BRIGHT)::value>), dim3(a.n_inner * G8), dim3(256), 0, s,
+                         a, R, G8, x.xbuf, x.err, spin, flags);
+    });
+  });
   return hipGetLastError();
 }
 

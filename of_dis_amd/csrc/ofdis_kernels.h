@@ -3,9 +3,30 @@
 // ofdis_launchers.inc is included into ofdis::exact and ofdis::fused, every kernel file defines its launchers in the
 // namespace of the contract it is being compiled for (OFDIS_KNS), and ofdis_capi.hip picks a set per context.
 #pragma once
+#include <type_traits>
+#include <utility>
+
 #include "ofdis_dev.h"
 
 namespace ofdis {
+
+// Runtime value -> template argument, written once per launcher: calls f with the std::integral_constant out of V0, V... that
+// equals v; a value that is not in the list takes the LAST one, as the `default:` arm of a switch would.  Nested calls handle
+// several arguments:  with_constant<1, 2, 3>(a.iterations, [&](auto NS) { ... kernel<decltype(NS)::value> ... });
+template <auto V0, auto... V, class T, class F>
+inline auto with_constant(T v, F&& f) {
+  if constexpr (sizeof...(V) == 0) return f(std::integral_constant<decltype(V0), V0>{});
+  else return v == V0 ? f(std::integral_constant<decltype(V0), V0>{}) : with_constant<V...>(v, f);
+}
+// ... and for a row 0 .. N-1 of a constexpr table of instantiations
+template <class F, int... I>
+inline auto with_index(int i, F&& f, std::integer_sequence<int, I...>) { return with_constant<I...>(i, f); }
+template <int N, class F>
+inline auto with_index(int i, F&& f) { return with_index(i, f, std::make_integer_sequence<int, N>{}); }
+
+// Rows per frame slot of a wavefront in the kernels that put several frames of a low level side by side in one wavefront
+// (64 / R frames: wavefront SOR, fused TV and their stereo twins).  The kernels take R as an argument and trust it.
+inline int slot_rows(int h) { return h <= 16 ? 16 : (h <= 32 ? 32 : 64); }
 
 // flow-plane layouts used between kernels
 //   AoS   : [frame][h][w][2]   -- the reference's dense-flow format (DIS init / output)
@@ -32,6 +53,87 @@ struct DisArgs {
 };
 // snapshot of the kernel-selection knobs (include/ofdis.h: ofdis_tuning; ofdis_capi.hip); *epoch counts the changes
 ofdis_tuning tuning(unsigned* epoch = nullptr);
+
+// Which patch kernel launch_patch_optimize runs, decided once: a pure host function of the level, the mode, the knobs and the
+// arithmetic contract.  The launcher launches what it says, patch_pixel_weights_supported is its `pixw`.
+struct PatchKernel {
+  // NONE: refused | LANES16: patch_optimize_rgb12_kernel (fused contract) / patch_optimize_rgb12x_kernel (exact), 16 lanes per
+  // patch | GRAY8: patch_optimize_gray8_kernel | GENERIC: patch_optimize_kernel
+  enum Family { NONE, LANES16, GRAY8, GENERIC };
+  int row;               // the instantiation: its row of kPatchKernels, -1 = no kernel
+  int contract;          // as given
+  int lpp;               // lanes per patch
+  int threads;           // workgroup size
+  int blocks_per_frame;  // (the grid: xcd_grid of them)
+  bool pixw;             // that kernel honours DisArgs::pixw: the compact per-pixel weights of RGB 12x12 flow patches
+};
+// every instantiation of the three kernels that exists: t = its template arguments in the order of its parameter list --
+// LANES16 <L1, NOC, STEREO, BS>, GRAY8 <COST, STEREO>, GENERIC <M, LPP, NV, COST>
+struct PatchInstance {
+  PatchKernel::Family family;
+  int t[4];
+};
+inline constexpr PatchInstance kPatchKernels[] = {
+    // RGB 8x8 | gray 12x12 | RGB 12x12, each flow / stereo with the L2 / L1 cost
+    {PatchKernel::LANES16, {0, 3, 0, 2}}, {PatchKernel::LANES16, {1, 3, 0, 2}}, {PatchKernel::LANES16, {0, 3, 1, 2}},
+    {PatchKernel::LANES16, {1, 3, 1, 2}}, {PatchKernel::LANES16, {0, 1, 0, 3}}, {PatchKernel::LANES16, {1, 1, 0, 3}},
+    {PatchKernel::LANES16, {0, 1, 1, 3}}, {PatchKernel::LANES16, {1, 1, 1, 3}}, {PatchKernel::LANES16, {0, 3, 0, 3}},
+    {PatchKernel::LANES16, {1, 3, 0, 3}}, {PatchKernel::LANES16, {0, 3, 1, 3}}, {PatchKernel::LANES16, {1, 3, 1, 3}},
+    {PatchKernel::GRAY8, {-1, 1}},        {PatchKernel::GRAY8, {0, 0}},         {PatchKernel::GRAY8, {-1, 0}},
+    {PatchKernel::GENERIC, {1, 8, 64, 0}},    {PatchKernel::GENERIC, {1, 8, 64, -1}},   {PatchKernel::GENERIC, {1, 8, 0, -1}},
+    {PatchKernel::GENERIC, {3, 64, 0, -1}},   {PatchKernel::GENERIC, {7, 32, 432, 0}},  {PatchKernel::GENERIC, {7, 32, 432, 1}},
+    {PatchKernel::GENERIC, {7, 64, 432, 0}},  {PatchKernel::GENERIC, {7, 64, 432, 1}},  {PatchKernel::GENERIC, {7, 64, 0, -1}},
+    {PatchKernel::GENERIC, {12, 64, 0, -1}},
+};
+constexpr int kNumPatchKernels = (int)(sizeof(kPatchKernels) / sizeof(kPatchKernels[0]));
+
+inline PatchKernel choose_patch_kernel(const LevelGeom& g, bool stereo, int costfct, bool pixw_asked, const ofdis_tuning& tn,
+                                       int contract) {
+  PatchKernel k{-1, contract, 0, 0, 0, false};
+  auto pick = [&](PatchKernel::Family family, int t0, int t1, int t2 = 0, int t3 = 0) {
+    for (int r = 0; r < kNumPatchKernels && k.row < 0; ++r) {
+      const PatchInstance& i = kPatchKernels[r];
+      if (i.family == family && i.t[0] == t0 && i.t[1] == t1 && i.t[2] == t2 && i.t[3] == t3) k.row = r;
+    }
+    const int wpf = (g.nop + 64 / k.lpp - 1) / (64 / k.lpp);                 // wavefronts per frame
+    const int wpb = (family == PatchKernel::GRAY8 && wpf < 4) ? wpf : 4;     // ... per block (the other kernels assume 4)
+    k.threads = 64 * wpb;
+    k.blocks_per_frame = (wpf + wpb - 1) / wpb;
+    return k;
+  };
+  const int M = (g.novals + 63) / 64;
+  const bool l2l1 = costfct == 0 || costfct == 1;
+  // 12x12 patches, RGB or gray, and RGB 8x8 patches, flow or stereo, have their own mapping (16 lanes per patch, four
+  // patches per wavefront: ofdis_tuning::rgb12 with rgb12_lpp = 16, the default)
+  const int rgb12_lpp = tn.rgb12_lpp == 0 ? 16 : tn.rgb12_lpp;
+  if (((g.P == 12 && (g.noc == 1 || g.noc == 3)) || (g.P == 8 && g.noc == 3)) && l2l1 && tn.rgb12 && rgb12_lpp == 16) {
+    k.lpp = 16;
+    k.pixw = g.novals == 432 && g.P == 12 && !stereo;
+    return pick(PatchKernel::LANES16, costfct != 0, g.P == 8 ? 3 : g.noc, stereo, g.P == 8 ? 2 : 3);
+  }
+  if (pixw_asked || M > 12) return k;  // (only the kernels above write the compact weights)
+  if (M <= 1 && g.noc == 1 && g.P == 8 && tn.gray8) {
+    k.lpp = 4;
+    return pick(PatchKernel::GRAY8, (!stereo && costfct == 0) ? 0 : -1, stereo);
+  }
+  // RGB 12x12 (operating points 3 and 4, BASELINE configs[3]): 432 entries, 6 full groups of 64 + 48.  ofdis_tuning::rgb12_lpp = 32:
+  // two patches per wavefront (the scalar solve, predicates and every reduction instruction shared by two patches:
+  // 929 -> 705 instructions per patch and iteration, 82 -> 127 VGPRs).  Measured on configs[3] the same 19.6 +- 0.4 ms per
+  // 16-pair level-1 launch either way -- patches that reset early leave their wavefront's other half running alone
+  // (PMC: 18 % fewer VALU instructions, same time) -- so one patch per wavefront stayed the default until the
+  // 16-lanes-per-patch kernels (round 4) took it over.
+  const bool rgb12 = g.novals == 432 && !stereo && l2l1 && tn.rgb12;
+  k.lpp = M <= 1 ? 8 : ((rgb12 && rgb12_lpp == 32) ? 32 : 64);
+  if (M <= 1 && g.novals == 64) return pick(PatchKernel::GENERIC, 1, 8, 64, costfct == 0 ? 0 : -1);
+  if (M <= 1) return pick(PatchKernel::GENERIC, 1, 8, 0, -1);
+  if (M <= 3) return pick(PatchKernel::GENERIC, 3, 64, 0, -1);
+  if (rgb12) return pick(PatchKernel::GENERIC, 7, k.lpp, 432, costfct);
+  return pick(PatchKernel::GENERIC, M <= 7 ? 7 : 12, 64, 0, -1);
+}
+
+// The geometry of densify_quad_kernel and of the densification inside tv_prep_kernel (PrepArgs::dens_*), which must agree: gray
+// 8x8 patches on a step-4 grid (operating point 2), at most 2 x 2 patches per pixel
+inline bool densify_quad_geometry(const LevelGeom& g) { return g.noc == 1 && g.P == 8 && g.steps == 4 && g.offw < 4 && g.offh < 4; }
 
 struct DensifyArgs {
   LevelGeom g;

@@ -501,9 +501,8 @@ __global__ __launch_bounds__(64 * WPF) void tv_prep_kernel(const PrepArgs a, con
 // up to 64 rows, two to four up to 256: ofdis_fused.hip, ofdis_fused_tall.hip)
 // (columns: one lane each, up to four wavefronts side by side)
 bool tv_prep_supported(const TvGeom& t) { return t.noc == 1 && t.w >= 16 && t.w <= 256 && t.h >= 4 && t.h <= 256; }
-// Can launch_tv_prep densify the flow itself for this patch grid (PrepArgs::dens_*)?  The geometry of densify_quad_kernel:
-// gray 8x8 patches on a step-4 grid (operating point 2), at most 2 x 2 patches per pixel.
-bool tv_prep_densifies(const LevelGeom& g) { return g.noc == 1 && g.P == 8 && g.steps == 4 && g.offw < 4 && g.offh < 4; }
+// Can launch_tv_prep densify the flow itself for this patch grid (PrepArgs::dens_*)?  The geometry of densify_quad_kernel.
+bool tv_prep_densifies(const LevelGeom& g) { return densify_quad_geometry(g); }
 
 hipError_t launch_tv_prep(const PrepArgs& a_in, hipStream_t s) {
   if (!tv_prep_supported(a_in.t) || a_in.S < 1) return hipErrorInvalidValue;
@@ -524,19 +523,16 @@ hipError_t launch_tv_prep(const PrepArgs& a_in, hipStream_t s) {
   }
   nbands = (h + a.band_rows - 1) / a.band_rows;
   const long long units = (long long)fgroups * nbands;
-  if (a.dens_p) {  // densification inside this kernel (tv_prep_densifies): patch results in, no dense flow read
-    if (!a.dens_pweight || a.dens_offw < 0 || a.dens_offw > 3 || a.dens_offh < 0 || a.dens_offh > 3 || a.dens_nopw < 1 || a.dens_noph < 1)
-      return hipErrorInvalidValue;
-    if (w > 192) hipLaunchKernelGGL((tv_prep_kernel<4, true>), dim3((unsigned)units), dim3(256), 0, s, a, lpf_shift, nbands);
-    else if (w > 128) hipLaunchKernelGGL((tv_prep_kernel<3, true>), dim3((unsigned)units), dim3(192), 0, s, a, lpf_shift, nbands);
-    else if (w > 64) hipLaunchKernelGGL((tv_prep_kernel<2, true>), dim3((unsigned)units), dim3(128), 0, s, a, lpf_shift, nbands);
-    else hipLaunchKernelGGL((tv_prep_kernel<1, true>), dim3((unsigned)units), dim3(64), 0, s, a, lpf_shift, nbands);
-    return hipGetLastError();
-  }
-  if (w > 192) hipLaunchKernelGGL((tv_prep_kernel<4, false>), dim3((unsigned)units), dim3(256), 0, s, a, lpf_shift, nbands);
-  else if (w > 128) hipLaunchKernelGGL((tv_prep_kernel<3, false>), dim3((unsigned)units), dim3(192), 0, s, a, lpf_shift, nbands);
-  else if (w > 64) hipLaunchKernelGGL((tv_prep_kernel<2, false>), dim3((unsigned)units), dim3(128), 0, s, a, lpf_shift, nbands);
-  else hipLaunchKernelGGL((tv_prep_kernel<1, false>), dim3((unsigned)units), dim3(64), 0, s, a, lpf_shift, nbands);
+  // densification inside this kernel (tv_prep_densifies): patch results in, no dense flow read
+  if (a.dens_p && (!a.dens_pweight || a.dens_offw < 0 || a.dens_offw > 3 || a.dens_offh < 0 || a.dens_offh > 3 || a.dens_nopw < 1 ||
+                   a.dens_noph < 1))
+    return hipErrorInvalidValue;
+  with_constant<1, 2, 3, 4>((w + 63) / 64, [&](auto WPF) {  // one lane per column: a wavefront per 64 of them
+    with_constant<false, true>(a.dens_p != nullptr, [&](auto DENS) {
+      hipLaunchKernelGGL((tv_prep_kernel<decltype(WPF)::value, decltype(DENS)::value>), dim3((unsigned)units),
+                         dim3(64 * decltype(WPF)::value), 0, s, a, lpf_shift, nbands);
+    });
+  });
   return hipGetLastError();
 }
 

@@ -94,7 +94,7 @@ DisArgs dis_args(const ofdis_params& p, const LevelGeom& g, int nframes) {
 static int strip_length(const ofdis_batch& b, const LevelGeom& g, const ofdis_tuning& tn, bool pipe) {
   const int n = b.nframes;
   if (tn.fused_strip > 0) return (n % tn.fused_strip == 0) ? tn.fused_strip : 1;
-  const int R = g.h <= 16 ? 16 : (g.h <= 32 ? 32 : 64);
+  const int R = slot_rows(g.h);
   for (int S = pipe ? 8 : 4; S > 1; S >>= 1)
     if (n % S == 0 && (n / S) / (64 / R) >= (pipe ? 1024 : 4096)) return S;
   return 1;

@@ -324,30 +324,27 @@ __global__ void sor_serial_kernel(const SorArgs a) {
 #undef DG
 }
 
-// sor_kernel<iterations, PD, MAXT> for 1 <= iterations <= MAXNS sweeps (3 or 4)
-template <int MAXT, int MAXNS>
+// sor_kernel<iterations, PD, MAXT> for the sweep counts NS... (1 to 3 or 4; more take the last)
+template <int MAXT, int... NS>
 static void launch_sor_sweeps(const SorArgs& a, dim3 g, dim3 b, int R, hipStream_t s) {
   constexpr int PD = 3;
-  switch (a.iterations) {
-    case 1: hipLaunchKernelGGL((sor_kernel<1, PD, MAXT>), g, b, 0, s, a, R); break;
-    case 2: hipLaunchKernelGGL((sor_kernel<2, PD, MAXT>), g, b, 0, s, a, R); break;
-    case 3: hipLaunchKernelGGL((sor_kernel<3, PD, MAXT>), g, b, 0, s, a, R); break;
-    default: hipLaunchKernelGGL((sor_kernel<MAXNS, PD, MAXT>), g, b, 0, s, a, R); break;
-  }
+  with_constant<NS...>(a.iterations, [&](auto N) {
+    hipLaunchKernelGGL((sor_kernel<decltype(N)::value, PD, MAXT>), g, b, 0, s, a, R);
+  });
 }
 
 hipError_t launch_sor(const SorArgs& a, hipStream_t s) {
   const int w = a.t.w, h = a.t.h;
   if (w >= 2 && h >= 2 && h <= 64 && a.iterations >= 1 && a.iterations <= 4) {
-    const int R = h <= 16 ? 16 : (h <= 32 ? 32 : 64);
+    const int R = slot_rows(h);
     const int G = 64 / R;
     const int waves = (a.t.nframes + G - 1) / G;
-    launch_sor_sweeps<0, 4>(a, dim3((waves + 3) / 4), dim3(256), R, s);
+    launch_sor_sweeps<0, 1, 2, 3, 4>(a, dim3((waves + 3) / 4), dim3(256), R, s);
   } else if (w >= 2 && h > 64 && h <= 1024 && a.iterations >= 1 && a.iterations <= 3) {
     const int threads = ((h + 63) / 64) * 64;
     // <= 640 threads leave 170 VGPRs per lane (no spills); taller levels take the 1024-thread build
-    if (threads <= 640) launch_sor_sweeps<640, 3>(a, dim3(a.t.nframes), dim3(threads), 64, s);
-    else launch_sor_sweeps<1024, 3>(a, dim3(a.t.nframes), dim3(threads), 64, s);
+    if (threads <= 640) launch_sor_sweeps<640, 1, 2, 3>(a, dim3(a.t.nframes), dim3(threads), 64, s);
+    else launch_sor_sweeps<1024, 1, 2, 3>(a, dim3(a.t.nframes), dim3(threads), 64, s);
   } else {
     hipLaunchKernelGGL(sor_serial_kernel, dim3((a.t.nframes + 63) / 64), dim3(64), 0, s, a);
   }

@@ -150,22 +150,16 @@ hipError_t launch_warp(const WarpArgs& a, hipStream_t s) {
   while ((1 << tx_shift) < cols && tx_shift < 8) ++tx_shift;
   const int rows_per_block = 256 >> tx_shift;
   const int gx = (cols + (1 << tx_shift) - 1) >> tx_shift, gy = (a.t.h + rows_per_block - 1) / rows_per_block;
-  const long long blocks = (long long)((a.t.nframes + 7) / 8) * 8 * gx * gy;
-  if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-  const dim3 g((unsigned)blocks), b(256);
-#define OFDIS_WARP_LAUNCH(P, V)                                                                          \
-  do {                                                                                                   \
-    if (a.t.noc == 1) hipLaunchKernelGGL((warp_kernel<P, V, 1>), g, b, 0, s, a, tx_shift, gx, gy);     \
-    else hipLaunchKernelGGL((warp_kernel<P, V, 3>), g, b, 0, s, a, tx_shift, gx, gy);                  \
-  } while (0)
-  if (a.src_padded) {
-    if (v4) OFDIS_WARP_LAUNCH(true, 4);
-    else OFDIS_WARP_LAUNCH(true, 1);
-  } else {
-    if (v4) OFDIS_WARP_LAUNCH(false, 4);
-    else OFDIS_WARP_LAUNCH(false, 1);
-  }
-#undef OFDIS_WARP_LAUNCH
+  dim3 g;
+  if (xcd_grid(a.t.nframes, (long long)gx * gy, g) != hipSuccess) return hipErrorInvalidValue;
+  with_constant<false, true>(a.src_padded != 0, [&](auto P) {
+    with_constant<1, 4>(v4 ? 4 : 1, [&](auto V) {
+      with_constant<1, 3>(a.t.noc, [&](auto NOC) {
+        hipLaunchKernelGGL((warp_kernel<decltype(P)::value, decltype(V)::value, decltype(NOC)::value>), g, dim3(256), 0, s, a,
+                           tx_shift, gx, gy);
+      });
+    });
+  });
   return hipGetLastError();
 }
 
@@ -310,13 +304,14 @@ __global__ __launch_bounds__(256) void derivatives_kernel(const DerivArgs a) {
 hipError_t launch_derivatives(const DerivArgs& a, hipStream_t s) {
   if (a.t.h < 4) return hipErrorInvalidValue;  // the reference's vertical filter reads rows 0..3
   const int tiles = ((a.t.w + DT_W - 1) / DT_W) * ((a.t.h + DT_H - 1) / DT_H);
-  const dim3 g(((a.t.nframes + 7) / 8) * 8 * tiles), b(256);
-  if (a.rec_d8) {
-    if (!a.rec_w || !a.mask || !a.wx || !a.wy) return hipErrorInvalidValue;
-    if (a.im1_padded) hipLaunchKernelGGL((derivatives_kernel<true, true>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((derivatives_kernel<false, true>), g, b, 0, s, a);
-  } else if (a.im1_padded) hipLaunchKernelGGL((derivatives_kernel<true, false>), g, b, 0, s, a);
-  else hipLaunchKernelGGL((derivatives_kernel<false, false>), g, b, 0, s, a);
+  dim3 g;
+  if (xcd_grid(a.t.nframes, tiles, g) != hipSuccess) return hipErrorInvalidValue;
+  if (a.rec_d8 && (!a.rec_w || !a.mask || !a.wx || !a.wy)) return hipErrorInvalidValue;
+  with_constant<false, true>(a.im1_padded != 0, [&](auto PADDED) {
+    with_constant<false, true>(a.rec_d8 != nullptr, [&](auto RECORDS) {
+      hipLaunchKernelGGL((derivatives_kernel<decltype(PADDED)::value, decltype(RECORDS)::value>), g, dim3(256), 0, s, a);
+    });
+  });
   return hipGetLastError();
 }
 
@@ -467,7 +462,9 @@ __global__ __launch_bounds__(256) void tv_system_kernel(const SystemArgs a) {
 
 hipError_t launch_tv_system(const SystemArgs& a, hipStream_t s) {
   const int tiles = ((a.t.w + ST_W - 1) / ST_W) * ((a.t.h + ST_H - 1) / ST_H);
-  hipLaunchKernelGGL(tv_system_kernel, dim3(((a.t.nframes + 7) / 8) * 8 * tiles), dim3(256), 0, s, a);
+  dim3 g;
+  if (xcd_grid(a.t.nframes, tiles, g) != hipSuccess) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(tv_system_kernel, g, dim3(256), 0, s, a);
   return hipGetLastError();
 }
 
@@ -511,8 +508,9 @@ __global__ __launch_bounds__(256) void tv_finish_kernel(int w, int h, int nframe
 hipError_t launch_tv_finish(const TvGeom& t, const float* wx, const float* wy, const float* du, const float* dv,
                             float* flow_aos, hipStream_t s) {
   const int tiles = ((t.w + 31) / 32) * ((t.h + 31) / 32);
-  hipLaunchKernelGGL(tv_finish_kernel, dim3(((t.nframes + 7) / 8) * 8 * tiles), dim3(256), 0, s, t.w, t.h, t.nframes, wx, wy,
-                     du, dv, reinterpret_cast<float2*>(flow_aos));
+  dim3 g;
+  if (xcd_grid(t.nframes, tiles, g) != hipSuccess) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(tv_finish_kernel, g, dim3(256), 0, s, t.w, t.h, t.nframes, wx, wy, du, dv, reinterpret_cast<float2*>(flow_aos));
   return hipGetLastError();
 }
 
@@ -548,8 +546,10 @@ __global__ __launch_bounds__(256) void tv_finish_records_kernel(int w, int h, in
 }
 hipError_t launch_tv_finish_records(const TvGeom& t, float* flow_aos, const float* uv, int S, hipStream_t s) {
   const int tiles = ((t.w + 31) / 32) * ((t.h + 31) / 32);
-  hipLaunchKernelGGL(tv_finish_records_kernel, dim3(((t.nframes + 7) / 8) * 8 * tiles), dim3(256), 0, s, t.w, t.h, t.nframes,
-                     S, reinterpret_cast<float2*>(flow_aos), reinterpret_cast<const float2*>(uv));
+  dim3 g;
+  if (xcd_grid(t.nframes, tiles, g) != hipSuccess) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(tv_finish_records_kernel, g, dim3(256), 0, s, t.w, t.h, t.nframes, S, reinterpret_cast<float2*>(flow_aos),
+                     reinterpret_cast<const float2*>(uv));
   return hipGetLastError();
 }
 

@@ -73,6 +73,35 @@ HOOK unsigned ofdis_test_grid_for(long long total) { return grid_for(total); }
 HOOK void ofdis_test_xcd_frame_map(int n0, int count, int blocks_per_frame, int nframes, int* frame, int* blk) {
   for (int i = 0; i < count; ++i) xcd_frame_map(n0 + i, blocks_per_frame, nframes, frame[i], blk[i]);
 }
+// host only, needs no GPU: the core launchers' geometry -- the padded grid xcd_frame_map expects (-1: refused) and the rows per
+// frame slot of the kernels that pack frames into a wavefront
+HOOK long long ofdis_test_xcd_grid(int nframes, long long blocks_per_frame) {
+  dim3 g;
+  return xcd_grid(nframes, blocks_per_frame, g) == hipSuccess ? (long long)g.x : -1;
+}
+HOOK int ofdis_test_slot_rows(int h) { return slot_rows(h); }
+// host only, needs no GPU: the patch kernel launch_patch_optimize runs (choose_patch_kernel) for a level of nop patches of
+// P x P pixels and noc channels -- out = family (PatchKernel::Family), its four template arguments, lanes per patch, workgroup
+// size, workgroups per frame, and whether it honours DisArgs::pixw (what patch_pixel_weights_supported returns)
+HOOK void ofdis_test_patch_kernel_choice(int P, int noc, int nop, int stereo, int costfct, int pixw_asked, int gray8, int rgb12,
+                                         int rgb12_lpp, int contract, int* out) {
+  LevelGeom g{};
+  g.P = P;
+  g.noc = noc;
+  g.nop = nop;
+  g.novals = noc * P * P;
+  ofdis_tuning tn{};
+  tn.gray8 = gray8;
+  tn.rgb12 = rgb12;
+  tn.rgb12_lpp = rgb12_lpp;
+  const PatchKernel k = choose_patch_kernel(g, stereo != 0, costfct, pixw_asked != 0, tn, contract);
+  out[0] = k.row < 0 ? (int)PatchKernel::NONE : (int)kPatchKernels[k.row].family;
+  for (int q = 0; q < 4; ++q) out[1 + q] = k.row < 0 ? 0 : kPatchKernels[k.row].t[q];
+  out[5] = k.lpp;
+  out[6] = k.threads;
+  out[7] = k.blocks_per_frame;
+  out[8] = k.pixw;
+}
 HOOK size_t ofdis_test_gmotion_work_bytes(int npairs, int w, int h) { return gmotion_work_bytes(npairs, w, h); }
 // host only, needs no GPU: the layout classes of the track-description chain for C = nxy^2 nt, as the launchers choose them
 // (bof_assign_shape, km_geom) and as km_finish_kernel splits its threads over a channel of n_c entries (km_finish_log2te)

@@ -4,7 +4,8 @@ launcher walks the frames in chunks) and GRID_MAX_BLOCKS (grid of a grid-stride 
 that library which a test lowers.  Shared by tests/test_launch_geometry.py (CPU) and tests/test_gpu_launch_limits.py; the
 pyramid's launchers and their kernel selection (pyr_base_variant, pyr_planes_variant) also by tests/pyr_classes.py,
 tests/test_pyr_ref.py (CPU) and tests/test_gpu_pyramid.py; the level launchers with a free UpGeom by
-tests/test_gpu_level_routes.py.
+tests/test_gpu_level_routes.py; the core launchers' host-only decisions (xcd_grid, slot_rows, choose_patch_kernel) by
+tests/test_launch_geometry.py and tests/test_patch_kernel_choice.py.
 
 libofdis_hip.so is a separate object with the limits compiled in as constants: nothing here changes what it does."""
 import contextlib
@@ -63,6 +64,9 @@ def hooks():
     L.ofdis_test_quad_chunks.argtypes, L.ofdis_test_quad_chunks.restype = [_I, _I, _I, _I, _VP], _I
     L.ofdis_test_grid_for.argtypes, L.ofdis_test_grid_for.restype = [_LL], C.c_uint
     L.ofdis_test_xcd_frame_map.argtypes, L.ofdis_test_xcd_frame_map.restype = [_I, _I, _I, _I, _VP, _VP], None
+    L.ofdis_test_xcd_grid.argtypes, L.ofdis_test_xcd_grid.restype = [_I, _LL], _LL
+    L.ofdis_test_slot_rows.argtypes, L.ofdis_test_slot_rows.restype = [_I], _I
+    L.ofdis_test_patch_kernel_choice.argtypes, L.ofdis_test_patch_kernel_choice.restype = [_I] * 10 + [C.POINTER(_I)], None
     L.ofdis_test_gmotion_work_bytes.argtypes, L.ofdis_test_gmotion_work_bytes.restype = [_I, _I, _I], _SZ
     L.ofdis_test_bof_shape.argtypes, L.ofdis_test_bof_shape.restype = [_I] + [C.POINTER(_I)] * 3, None
     L.ofdis_test_km_geom.argtypes, L.ofdis_test_km_geom.restype = [_I] + [C.POINTER(_I)] * 3, None
@@ -110,6 +114,30 @@ def xcd_frame_map(nblocks, bpf, nframes):
     frame, blk = np.empty(nblocks, np.int32), np.empty(nblocks, np.int32)
     hooks().ofdis_test_xcd_frame_map(0, nblocks, bpf, nframes, frame.ctypes.data, blk.ctypes.data)
     return frame, blk
+
+
+def xcd_grid(nframes, blocks_per_frame):
+    """workgroups of the grid xcd_grid (ofdis_dev.h) gives the core launchers whose kernels call xcd_frame_map; None: refused"""
+    n = int(hooks().ofdis_test_xcd_grid(nframes, blocks_per_frame))
+    return None if n < 0 else n
+
+
+def slot_rows(h):
+    """slot_rows (ofdis_kernels.h): rows per frame slot of a wavefront at level height h"""
+    return int(hooks().ofdis_test_slot_rows(h))
+
+
+PATCH_FAMILIES = ("none", "lanes16", "gray8", "generic")   # PatchKernel::Family
+
+
+def patch_kernel_choice(P, noc, nop, stereo, costfct, pixw_asked, gray8, rgb12, rgb12_lpp, contract):
+    """choose_patch_kernel (ofdis_kernels.h) as a dict: family (PATCH_FAMILIES), targs (the kernel's template arguments in its
+    parameter order, trailing zeros cut to the family's count), lpp, threads, blocks_per_frame, pixw"""
+    out = (_I * 9)()
+    hooks().ofdis_test_patch_kernel_choice(P, noc, nop, int(stereo), costfct, int(pixw_asked), gray8, rgb12, rgb12_lpp, contract, out)
+    family = PATCH_FAMILIES[out[0]]
+    return dict(family=family, targs=tuple(out[1:5])[:{"none": 0, "gray8": 2}.get(family, 4)], lpp=out[5], threads=out[6],
+                blocks_per_frame=out[7], pixw=bool(out[8]))
 
 
 def chunk_walk(nframes, w, h):

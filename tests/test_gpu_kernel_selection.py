@@ -3,6 +3,10 @@
 Under the exact contract every route gives the same bits, so the bit-exact tests cannot tell a misrouted level from a right
 one: a level that silently loses its fused route still passes them.  These cases pin, per kernel class of capi.K_NAMES, how
 many launches a pass makes.  Random 8-bit frames through the on-device pyramid: the counts do not depend on the content.
+
+The second group of cases runs the arms of the core launchers' own kernel choice that those routes leave out (patch kernels by
+geometry, cost function and knob; tv_prep by level width; tall and one-frame fused TV).  A count per class does not say which
+instantiation ran: the patch choice itself is held on the host by tests/test_patch_kernel_choice.py.
 """
 import numpy as np
 import pytest
@@ -14,6 +18,7 @@ pytestmark = pytest.mark.gpu
 GRAY = (1024, 436, 1)
 RGB_SMALL = (320, 240, 3)
 STEREO = (1242, 375, 1)
+WIDE = {"sc_f": 4, "sc_l": 3}
 
 # id: (frame size and channels, operating point, frames, params changed, knobs at creation, knobs set after creation, reverse)
 CASES = {
@@ -34,6 +39,24 @@ CASES = {
     "stereo_exact":           (STEREO, 2, 1, {"selectmode": 2}, {"contract": 0}, {}, False),
     "stereo_exact_forced":    (STEREO, 2, 1, {"selectmode": 2}, {"contract": 0, "fused_rgb_min": 1}, {}, False),
     "stereo_fused":           (STEREO, 2, 1, {"selectmode": 2}, {"contract": 1}, {}, False),
+    # the arms of the core launchers' kernel choice (choose_patch_kernel, launch_tv_prep, launch_tv_fused_tall, tv_fused_mode)
+    "rgb_op3_pixel_weights":  (RGB_SMALL, 3, 2, {}, {"contract": 0}, {}, False),
+    "rgb_op2_lanes16":        (RGB_SMALL, 2, 2, {}, {"contract": 0}, {}, False),
+    "gray_no_gray8":          (GRAY, 2, 4, {}, {"gray8": 0}, {}, False),
+    "rgb_op3_no_rgb12":       (RGB_SMALL, 3, 2, {}, {"contract": 0, "rgb12": 0}, {}, False),
+    "rgb_op3_lpp32":          (RGB_SMALL, 3, 2, {}, {"contract": 0, "rgb12_lpp": 32}, {}, False),
+    "gray_costfct1":          (GRAY, 2, 4, {"costfct": 1}, {}, {}, False),
+    "rgb_op3_costfct2":       (RGB_SMALL, 3, 2, {"costfct": 2}, {"contract": 0}, {}, False),
+    "stereo_rgb":             ((1242, 375, 3), 2, 1, {"selectmode": 2}, {"contract": 0}, {}, False),
+    # 64 rows leave two levels (the coarsest needs four rows): 96 x 4 and 192 x 8, three wavefronts side by side in tv_prep;
+    # 128 x 4 and 256 x 8, four; with and without the densification inside it
+    "gray_1536x64":           ((1536, 64, 1), 2, 4, WIDE, {}, {}, False),
+    "gray_1536x64_no_prep_densify": ((1536, 64, 1), 2, 4, WIDE, {"prep_densify": 0}, {}, False),
+    "gray_2048x64":           ((2048, 64, 1), 2, 4, WIDE, {}, {}, False),
+    "gray_2048x64_no_prep_densify": ((2048, 64, 1), 2, 4, WIDE, {"prep_densify": 0}, {}, False),
+    "gray_1080p":             ((1920, 1080, 1), 2, 4, {}, {}, {}, False),   # tall levels (more than 64 rows), grouped
+    "gray_1080p_ungrouped":   ((1920, 1080, 1), 2, 4, {}, {"fused_tall_group": 0}, {}, False),
+    "gray_one_frame":         (GRAY, 2, 1, {}, {}, {}, False),   # the multi-wave modes of the fused TV kernel
 }
 
 # launches per pass in the order of capi.K_NAMES: warp, derivatives, tv_system, sor, patch_optimize, densify, tv_finish,
@@ -56,6 +79,22 @@ EXPECTED = {
     "stereo_exact":           ( 3,  3, 15, 15,  3,  3,  3,  0),
     "stereo_exact_forced":    ( 3,  3,  0,  0,  3,  3,  3,  3),
     "stereo_fused":           ( 3,  3,  0,  0,  3,  3,  3,  3),
+    # (recorded with the library before the core launchers' choices were gathered)
+    "gray_1080p":                    ( 0,  3,  0,  0,  3,  0,  0,  3),
+    "gray_1080p_ungrouped":          ( 0,  3,  0,  0,  3,  0,  0,  3),
+    "gray_1536x64":                  ( 0,  2,  0,  0,  2,  0,  0,  2),
+    "gray_1536x64_no_prep_densify":  ( 0,  2,  0,  0,  2,  2,  0,  2),
+    "gray_2048x64":                  ( 0,  2,  0,  0,  2,  0,  0,  2),
+    "gray_2048x64_no_prep_densify":  ( 0,  2,  0,  0,  2,  2,  0,  2),
+    "gray_costfct1":                 ( 0,  3,  0,  0,  3,  0,  0,  3),
+    "gray_no_gray8":                 ( 0,  3,  0,  0,  3,  0,  0,  3),
+    "gray_one_frame":                ( 0,  3,  0,  0,  3,  0,  0,  3),
+    "rgb_op2_lanes16":               ( 3,  3, 12, 12,  3,  3,  3,  0),
+    "rgb_op3_costfct2":              ( 4,  4, 10, 10,  4,  4,  4,  0),
+    "rgb_op3_lpp32":                 ( 4,  4, 10, 10,  4,  4,  4,  0),
+    "rgb_op3_no_rgb12":              ( 4,  4, 10, 10,  4,  4,  4,  0),
+    "rgb_op3_pixel_weights":         ( 4,  4, 10, 10,  4,  4,  4,  0),
+    "stereo_rgb":                    ( 3,  3, 15, 15,  3,  3,  3,  0),
 }
 
 

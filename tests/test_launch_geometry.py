@@ -5,11 +5,15 @@ The launchers of ofdis_interp / tfilter / trajfilter / gmotion / stabilize walk 
 QUAD_MAX_BLOCKS workgroups (quad_chunks), and their kernels turn a workgroup index into (frame of the chunk, block of the
 frame) with xcd_frame_map.  Walked here by that loop itself, with a callback that records instead of launching, every (frame,
 block) of the clip must come up exactly once: for one launch and for many, for chunks below 8 frames (consecutive blocks) and
-from 8 (the XCD mapping with its padded last group)."""
+from 8 (the XCD mapping with its padded last group).
+
+The core launchers (patch search, densification, warp, derivatives, the per-stage TV and stereo systems, the finish) launch
+every frame at once on the grid of xcd_grid (ofdis_dev.h); the same coverage is required of it, and slot_rows
+(ofdis_kernels.h) is pinned at its thresholds."""
 import numpy as np
 import pytest
 
-from launch_hooks import QUAD_MAX_BLOCKS, chunk_walk, launch_limits, quad_grid, xcd_frame_map
+from launch_hooks import QUAD_MAX_BLOCKS, chunk_walk, launch_limits, quad_grid, slot_rows, xcd_frame_map, xcd_grid
 
 # (w, h) with 1, 3 and 7 workgroups of 256 quads per frame
 SHAPES = {1: (4, 1), 3: (64, 48), 7: (4, 7 * 256)}
@@ -60,6 +64,34 @@ def test_a_frames_blocks_share_an_xcd_from_8_frames():
             assert len(set(np.flatnonzero(frame == f) % 8)) == 1
     frame, blk = xcd_frame_map(7 * 3, 3, 7)
     assert np.array_equal(frame, np.repeat(np.arange(7), 3)) and np.array_equal(blk, np.tile(np.arange(3), 7))
+
+
+@pytest.mark.parametrize("bpf", [1, 3, 7])
+@pytest.mark.parametrize("nframes", [1, 7, 8, 9, 27])
+def test_core_grid_covers_every_block_of_every_frame_once(nframes, bpf):
+    """the core launchers (patch search, densification, warp, derivatives, TV system and finish, stereo system): the grid xcd_grid
+    gives them, walked by xcd_frame_map as their kernels do, reaches every (frame, block) exactly once; the rest is the
+    padding of the last group of 8 frames, which the kernels skip"""
+    blocks = xcd_grid(nframes, bpf)
+    assert blocks == -(-nframes // 8) * 8 * bpf
+    frame, blk = xcd_frame_map(blocks, bpf, nframes)
+    assert (blk >= 0).all() and (blk < bpf).all() and (frame >= 0).all()
+    live = frame < nframes
+    got = np.stack([frame[live], blk[live]], 1)
+    got = got[np.lexsort((got[:, 1], got[:, 0]))]
+    want = np.stack(np.meshgrid(np.arange(nframes), np.arange(bpf), indexing="ij"), -1).reshape(-1, 2)
+    assert got.shape == want.shape and np.array_equal(got, want)
+
+
+def test_core_grid_counts_in_64_bits_and_refuses_what_an_int_cannot_index():
+    assert xcd_grid(65535, 32767) == 65536 * 32767          # (2^31 - 65536: the largest multiple that fits)
+    assert xcd_grid(65535, 32768) is None                   # 2^31 blocks: wrapped to 0 in 32-bit arithmetic
+    assert xcd_grid(8, (1 << 28) - 1) == (1 << 31) - 8 and xcd_grid(8, 1 << 28) is None
+    assert xcd_grid(1, 1 << 40) is None
+
+
+def test_rows_per_frame_slot():
+    assert [slot_rows(h) for h in (1, 16, 17, 32, 33, 64)] == [16, 16, 32, 32, 64, 64]
 
 
 @pytest.mark.parametrize("nframes,w,h,bpf,chunk", [(16384, 1024, 436, 436, 9616), (65535, 1920, 1080, 2025, 2064),
