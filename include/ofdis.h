@@ -1097,6 +1097,59 @@ int ofdis_track_select_projective(const float* tracks, const int* start, const i
                                   void* work, size_t work_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Segments: connected components of a label map, small ones removed, one record per segment.  The step from the byte per pixel
+ * that ofdis_motion_compensate and ofdis_projective_compensate write to objects: the things that move against the camera are the
+ * components of the OFDIS_GM_OUTLIER pixels; the occlusion regions of a pair are those of an OFDIS_FB_* mask.
+ * Not provided: morphological opening or closing before labelling; hole filling; association of segments across frames; a form
+ * that reads a context's level flows directly (composing from materialised arrays wins, as the measurements of the fused
+ * global-motion, trajectory-filter and projective routes in README.md show: the labels come from either compensate call); the
+ * C++ sequence driver.
+ *
+ * label is [nmaps][H][W] u8, any byte map: OFDIS_GM_* labels, OFDIS_FB_* masks, or the caller's own.
+ * Foreground: codes is a bit set; pixel p is foreground iff label[p] < 8 and ((codes >> label[p]) & 1).  A byte of 8 or more is
+ * never foreground, so no shift by 8 or more is ever made.  Moving objects: codes = 1u << OFDIS_GM_OUTLIER.
+ * Connectivity: conn = 4 (edge neighbours) or 8 (edge and corner neighbours).  A component is a maximal connected set of
+ * foreground pixels within one map; maps never interact.
+ * Canonical numbering: the root of a component is its smallest raster index y*W + x; the components are ordered by ascending
+ * root, ncomp is their number; a component is kept iff area >= max(min_area, 1); the kept ones are numbered 1 .. nkept in the same
+ * order.  With min_area <= 1 this is what scipy.ndimage.label returns for the 4- or 8-structure.
+ * segments [nmaps][H][W] int32: 0 for background and for removed components, k for the k-th kept component.  Every entry is
+ * written once; nothing relies on a memset.  Segments beyond max_segments are still numbered here.
+ * records [nmaps][max_segments][12] int64: record k-1 of a map belongs to kept segment k, for k <= min(nkept, max_segments):
+ *   { area, root, xmin, ymin, xmax, ymax, sx, sy, nflow, squ, sqv, 0 }
+ * The box is inclusive; sx and sy are the sums of x and of y over the segment (the centroid is sx/area, sy/area).  flow is
+ * [nmaps][H][W][2] f32 or NULL -- the residual of the compensate call, or any other flow.  A pixel of the segment is usable iff
+ * fabsf(u) <= OFDIS_GM_MAX_FLOW and fabsf(v) <= OFDIS_GM_MAX_FLOW (a NaN fails this); nflow counts the usable pixels, squ is the
+ * sum of (int)rintf(u * 256.0f) over them and sqv that of v: the quantisation of "Global (camera) motion models" (the mean
+ * residual of the segment is squ / (256 nflow)).  Without flow the three are 0.  The slots at or beyond min(nkept, max_segments)
+ * are neither read nor written.
+ * info [nmaps][4] int64: { ncomp, nkept, min(nkept, max_segments), the number of foreground pixels }.
+ * Limits (in prose: the section adds no macro; of_dis_amd/capi.py and of_dis_amd/segments.py carry them as SEG_MAX_SEGMENTS = 2^24,
+ * SEG_RECORD_FIELDS = 12, SEG_INFO_FIELDS = 4): max_segments is 1 .. 16777216; both sides are at most OFDIS_GM_MAX_SIDE.
+ * Bounds: W, H <= 8192 = 2^13, so a raster index is below 2^26 and fits int32, as do area, ncomp and every number; sx < 2^26 *
+ * 2^13 = 2^39 and sy likewise; |q| <= 2^20, so |squ| <= 2^26 * 2^20 = 2^46: int64 never overflows.
+ * Order independence: integer min, max and add are associative and commutative, and the root of a component is a minimum, so
+ * every output is a pure function of the inputs whatever the order in which the unions are made and the atomics arrive: two
+ * calls give the same bits.  of_dis_amd/segments.py states the definition in numpy (label_segments_ref).
+ * ------------------------------------------------------------------------------------------- */
+/* bytes of the work buffer ofdis_label_segments needs: nmaps * (8 * W*H + 16 * ceil(W*H / 256)) -- the parent and the area /
+ * number of every pixel (int32 [nmaps][H*W] each) and four int32 of counts per block of 256 pixels; 0 for sizes that function
+ * rejects */
+size_t ofdis_segments_work_bytes(int nmaps, int width, int height);
+/* device arrays as stated above; work: 8-byte aligned, at least ofdis_segments_work_bytes.  label is read by several of the
+ * launches, which rely on finding the same bytes each time: whatever writes it must be ordered before the call on `stream`,
+ * and it must not change until the call's work has completed.  Seven launches are enqueued on
+ * `stream` without a host synchronisation: row runs from a wavefront ballot, unions by integer atomicMin on the parent array (no
+ * workgroup waits for another), a flattening pass, the areas, a two-level prefix sum over the kept roots in raster order, the
+ * records' initial values, and the relabelling pass that also accumulates the records with integer atomics (no floating-point
+ * atomic anywhere).  OFDIS_ERR_INVALID before any device work: a NULL label, info or work pointer; segments and records both
+ * NULL; codes 0 or with a bit above bit 7; conn not 4 or 8; min_area < 0; max_segments outside 1 .. 16777216; sizes as
+ * ofdis_fb_check rejects them or a side above OFDIS_GM_MAX_SIDE; a work buffer that is too small or not 8-byte aligned. */
+int ofdis_label_segments(const uint8_t* label, const float* flow /* or NULL */, int nmaps, int width, int height, unsigned codes,
+                         int conn, int min_area, int max_segments, int* segments /* or NULL */, long long* records /* or NULL */,
+                         long long* info, void* work, size_t work_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Video stabilisation: the per-pair camera models of a clip turned into one correcting warp per frame -- the classical
  * Gaussian motion filter: the motions relative to a frame averaged over a window around it -- and the frames resampled by their
  * warps.  Two operations, each stated below one step at a time, both independent of the arithmetic contract.

@@ -50,6 +50,9 @@ GM_INLIER, GM_OUTLIER, GM_INVALID = 0, 1, 2  # OFDIS_GM_* label
 STAB_MAX_RADIUS, STAB_MIN_DET, STAB_MAX_DET, STAB_MAX_ZOOM = 64, 0.25, 4.0, 16.0  # OFDIS_STAB_*
 STAB_MIN_DENOM = 0.5  # include/ofdis.h, "Projective video stabilisation": the denominator bound of usable (no macro there)
 BORDER_CONSTANT, BORDER_REPLICATE = 0, 1  # OFDIS_BORDER_*
+# include/ofdis.h, "Segments": the limits that section states in prose (no macro there); of_dis_amd/segments.py has the same
+SEG_MAX_SEGMENTS, SEG_RECORD_FIELDS, SEG_INFO_FIELDS = 1 << 24, 12, 4
+SEG_MOVING = 1 << GM_OUTLIER  # `codes` of the moving objects in a compensate call's labels
 OFDIS_VERSION = 3  # include/ofdis.h: the struct layouts below (OfdisTuning: 21 ints) belong to this ABI version
 
 
@@ -930,6 +933,39 @@ def projective_motion(flow, mask=None, rounds=3, thresh=1.0, stats=True):
 def projective_compensate(flow, models, mask=None, thresh=1.0, residual=True, label=True, in_place=False):
     """ofdis_projective_compensate on the device: motion_compensate with models [npairs, 8] float64."""
     return _camera_compensate(8, flow, models, mask, thresh, residual, label, in_place)
+
+
+def label_segments(label, flow=None, codes=SEG_MOVING, conn=8, min_area=0, max_segments=None, segments=True, records=True,
+                   records_fill=None):
+    """ofdis_label_segments on the device: label uint8 [nmaps, h, w], flow float32 [nmaps, h, w, 2] or None ->
+    (segments int32 [nmaps, h, w], records int64 [nmaps, max_segments, 12], info int64 [nmaps, 4]: ncomp, nkept,
+    min(nkept, max_segments), foreground pixels); segments=False / records=False pass NULL and return None in that place.
+    max_segments None: one slot per pixel (never truncates).  Only the record slots < info[:, 2] are written: the others keep
+    records_fill (int64, the records' shape), or zeros.  of_dis_amd/segments.py: label_segments_ref is the definition in numpy."""
+    label = np.ascontiguousarray(label, np.uint8)
+    assert label.ndim == 3, label.shape
+    nmaps, h, w = label.shape
+    if max_segments is None:
+        max_segments = min(h * w, SEG_MAX_SEGMENTS)
+    dl = Dev(label)
+    df = None
+    if flow is not None:
+        flow = _f(flow)
+        assert flow.shape == (nmaps, h, w, 2), flow.shape
+        df = Dev(flow)
+    ds = Dev(nbytes=max(8, nmaps * h * w * 4)) if segments else None
+    rshape = (nmaps, max_segments, SEG_RECORD_FIELDS)
+    dr = None
+    if records:
+        dr = Dev(np.zeros(rshape, np.int64) if records_fill is None else np.ascontiguousarray(records_fill, np.int64).reshape(rshape))
+    di = Dev(nbytes=nmaps * SEG_INFO_FIELDS * 8)
+    wb = lib().ofdis_segments_work_bytes(nmaps, w, h)
+    dwork = Dev(nbytes=max(8, wb))
+    check(lib().ofdis_label_segments(dl.ptr, df.ptr if df else None, nmaps, w, h, codes, conn, min_area, max_segments,
+                                     ds.ptr if ds else None, dr.ptr if dr else None, di.ptr, dwork.ptr, wb, None))
+    check(lib().ofdis_sync(None))
+    return (ds.get((nmaps, h, w), np.int32) if ds else None, dr.get(rshape, np.int64) if dr else None,
+            di.get((nmaps, SEG_INFO_FIELDS), np.int64))
 
 
 def _stab_weights(weights):

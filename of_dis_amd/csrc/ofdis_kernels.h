@@ -497,6 +497,14 @@ hipError_t launch_projective_level(const float* fw, const float* rev, int npairs
                                    float beta, double* models, long long* stats, void* work, hipStream_t s);
 hipError_t launch_projective_compensate_level(const float* fw, const float* rev, const double* models, int npairs, UpGeom g,
                                               float thresh, float alpha, float beta, float* residual, uint8_t* label, hipStream_t s);
+// segments of label maps (include/ofdis.h: ofdis_label_segments; ofdis_segments.hip): label [nmaps][h][w] u8, flow
+// [nmaps][h][w][2] or null -> segments [nmaps][h][w] int32 and records [nmaps][max_segments][12] int64 (either may be null), info
+// [nmaps][4] int64.  Seven launches on the stream (init, merge, flatten, count, scan, number, relabel), all grid-stride; work
+// holds segments_work_bytes: parent and area, int32 [nmaps][h * w] each, and four int32 per block of 256 pixels
+size_t segments_work_bytes(int nmaps, int w, int h);
+hipError_t launch_label_segments(const uint8_t* label, const float* flow, int nmaps, int w, int h, unsigned codes, int conn,
+                                 int min_area, int max_segments, int* segments, long long* records, long long* info, void* work,
+                                 hipStream_t s);
 // video stabilisation (include/ofdis.h: ofdis_camera_path, ofdis_warp_frames; ofdis_stabilize.hip).  The window travels in
 // the launch, as InterpTimes does: w[0 .. radius], the rest zero
 struct StabWindow {

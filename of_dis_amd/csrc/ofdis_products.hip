@@ -1,6 +1,6 @@
 // ofdis_products.hip -- what is made from a context's flows, and the same steps on caller-supplied arrays: the full-resolution
 // finish and its encodings, forward-backward and left-right checks, interpolation, point and dense trajectories, their selection, descriptors,
-// their bag-of-features encoding and the training of its codebook, the temporal filters, global motion and stabilisation.
+// their bag-of-features encoding and the training of its codebook, the temporal filters, global motion, the segments of its label maps and stabilisation.
 // Every entry point validates its arguments, joins the pass (finish_begin) and launches; the checks they share are stated once, below.  Reads no environment.
 #include <cfloat>
 #include <cmath>
@@ -754,6 +754,33 @@ int ofdis_batch_projective_compensate(ofdis_batch* b, int first_frame, int count
                                       void* stream) {
   return camera_batch_compensate(b, first_frame, count, models, thresh, fb_check, alpha, beta, residual, label, width_org,
                                  height_org, stream, 8);
+}
+
+// ------------------------------------------------------------------------------------ segments (ofdis_segments.hip)
+// The limits of the section "Segments" of include/ofdis.h, which states them in prose
+static const int kSegMaxSegments = 1 << 24;
+
+size_t ofdis_segments_work_bytes(int nmaps, int width, int height) {
+  return sizes_check(nmaps, width, height) == OFDIS_OK && gm_sizes_ok(nmaps, width, height) ? segments_work_bytes(nmaps, width, height)
+                                                                                           : 0;
+}
+
+int ofdis_label_segments(const uint8_t* label, const float* flow, int nmaps, int width, int height, unsigned codes, int conn,
+                         int min_area, int max_segments, int* segments, long long* records, long long* info, void* work,
+                         size_t work_bytes, void* stream) {
+  if (!label) return fail(OFDIS_ERR_INVALID, "label is NULL");
+  if (!info) return fail(OFDIS_ERR_INVALID, "info is NULL");
+  if (!segments && !records) return fail(OFDIS_ERR_INVALID, "segments and records are both NULL");
+  if (codes == 0 || codes > 0xFFu) return fail(OFDIS_ERR_INVALID, "codes must have a bit set and none above bit 7");
+  if (conn != 4 && conn != 8) return fail(OFDIS_ERR_INVALID, "conn must be 4 or 8");
+  if (min_area < 0) return fail(OFDIS_ERR_INVALID, "min_area must be >= 0");
+  if (max_segments < 1 || max_segments > kSegMaxSegments) return fail(OFDIS_ERR_INVALID, "max_segments outside 1..16777216");
+  if (int rc = sizes_check(nmaps, width, height)) return rc;
+  if (!gm_sizes_ok(nmaps, width, height)) return fail(OFDIS_ERR_INVALID, kGmSizes);
+  if (int rc = work_check(work, work_bytes, segments_work_bytes(nmaps, width, height), "ofdis_segments_work_bytes")) return rc;
+  HIPCHK(launch_label_segments(label, flow, nmaps, width, height, codes, conn, min_area, max_segments, segments, records, info, work,
+                               (hipStream_t)stream));
+  return OFDIS_OK;
 }
 
 // ------------------------------------------------------------------------------------ video stabilisation (ofdis_stabilize.hip)
