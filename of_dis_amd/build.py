@@ -265,16 +265,17 @@ def build(force=False, verbose=False):
             tdir = os.path.join(LIBDIR, "testhooks")
             os.makedirs(tdir, exist_ok=True)
             tobjs, _ = compile_units(CSRC, tdir, force, verbose, {u: TESTHOOK_FLAGS for u in TESTHOOK_UNITS}, only=TESTHOOK_UNITS)
+            hook_deps = headers + [os.path.join(ROOT, "tests", "csrc", "ofdis_test_hooks.h")]  # every hook's declaration
             # (ofdis_launch_hooks.hip and the files beside it that add one product's hooks: ofdis_launch_hooks_*.hip)
             lobjs = []
             for name in sorted(f for f in os.listdir(os.path.join(ROOT, "tests", "csrc"))
                                if f.startswith("ofdis_launch_hooks") and f.endswith(".hip")):
                 launch_hooks = os.path.join(ROOT, "tests", "csrc", name)
                 lobjs.append(os.path.join(tdir, name.replace(".hip", ".o")))
-                if force or _newer(lobjs[-1], [launch_hooks] + headers):
+                if force or _newer(lobjs[-1], [launch_hooks] + hook_deps):
                     _run([hipcc] + HIPFLAGS + TESTHOOK_FLAGS + ["-c", launch_hooks, "-o", lobjs[-1]], verbose)
             hobj = os.path.join(tdir, "ofdis_testhooks.o")
-            if force or _newer(hobj, [hooks] + headers):
+            if force or _newer(hobj, [hooks] + hook_deps):
                 _run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-c", hooks, "-o", hobj],
                      verbose)
             tso = testhooks_path()

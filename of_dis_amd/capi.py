@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from .abi import prototypes
+from .abi import bind, prototypes
 from .params import OfdisParams  # noqa: F401  (the struct callers pass by reference; stays a name of this module)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -130,10 +130,7 @@ def lib():
         if L.ofdis_version() != OFDIS_VERSION:  # a stale build: ofdis_get_tuning would write past / read garbage from our struct
             raise OfdisError(f"{LIB_PATH} has ABI version {L.ofdis_version()}, this binding expects {OFDIS_VERSION}: "
                              "rebuild with `python -m of_dis_amd.build`")
-        for name, (restype, argtypes) in _prototypes().items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _lib = L
+        _lib = bind(L, _prototypes())
     return _lib
 
 
@@ -285,6 +282,81 @@ class HostBuf:
             pass
 
 
+class DeviceCall:
+    """One call of the library on host arrays: the device buffers of the call and what happens to them after it.
+
+        with DeviceCall(stream) as c:
+            check(lib().ofdis_x(c.input(a), c.input(mask_or_None), n, c.output(shape, dtype, want), c.work(nbytes), nbytes, stream))
+            return c.results()
+
+    input, output and work each hand back the device pointer that goes into the C call, or None for NULL, so a wrapper names
+    them in the call's own argument order.  results() synchronises `stream` once, downloads the outputs in the order they
+    were declared (None where one was not wanted) and releases every buffer; nothing is released before that sync.  Leaving
+    the block releases them as well, so an OfdisError of the call leaks nothing.
+
+    own=False is the form of the Batch methods that are given device pointers: output() then takes the caller's pointer (or a
+    false value for NULL) as `want` and passes it through, and results() downloads nothing and returns None; it synchronises
+    only if an input was uploaded, which must outlive the launch."""
+    MIN_BYTES = 8  # the least allocation of an output or a work buffer: none of zero bytes (kernels write what the shapes say)
+
+    def __init__(self, stream=None, own=True):
+        self.stream, self.own = stream, own
+        self._devs = []  # every buffer of the call
+        self._outs = []  # (buffer or None, shape, dtype) of every output, in declaration order
+        self._uploaded = False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.release()
+
+    def _dev(self, arr=None, nbytes=None):
+        self._uploaded |= arr is not None
+        self._devs.append(Dev(arr, nbytes))
+        return self._devs[-1]
+
+    def input(self, arr):
+        """the device copy of a host array, coerced by the caller: its pointer; None for None"""
+        return None if arr is None else self._dev(arr).ptr
+
+    def output(self, shape, dtype=_f32, want=True, fill=None, over=None):
+        """An output of `shape` and `dtype`: its pointer, or None where it is not wanted.  fill: the contents it starts from, a host
+        array of that many elements (an array the call updates in place is an output filled with it).  over: the pointer
+        input() gave for the input whose device array the call is to overwrite with this output."""
+        if not self.own:
+            return want if want and want is not True else None  # (a bare True is no pointer)
+        dev = None
+        if want and over is not None:
+            dev = next(d for d in self._devs if d.ptr == over)
+        elif want and fill is not None:
+            dev = self._dev(np.ascontiguousarray(fill, dtype).reshape(shape))
+        elif want:
+            dev = self._dev(nbytes=max(self.MIN_BYTES, int(np.prod(shape, dtype=np.int64)) * np.dtype(dtype).itemsize))
+        self._outs.append((dev, shape, dtype))
+        return dev.ptr if dev else None
+
+    def work(self, nbytes):
+        """a work buffer of at least `nbytes` bytes: its pointer"""
+        return self._dev(nbytes=max(self.MIN_BYTES, int(nbytes))).ptr
+
+    def results(self):
+        """After the call: the tuple of the outputs as host arrays, in declaration order; None with own=False."""
+        try:
+            if self.own or self._uploaded:
+                check(lib().ofdis_sync(self.stream))
+            if not self.own:
+                return None
+            return tuple(dev.get(shape, dtype) if dev else None for dev, shape, dtype in self._outs)
+        finally:
+            self.release()
+
+    def release(self):
+        for dev in self._devs:
+            dev.free()
+        self._devs = []
+
+
 def _f(a):
     return np.ascontiguousarray(a, dtype=_f32)
 
@@ -299,13 +371,13 @@ def _pair_flows(flow_fw, flow_rev=None):
     return (flow_fw, flow_rev) + flow_fw.shape[:3]
 
 
-def _mask_dev(mask, shape):
-    """an optional uint8 mask of `shape` on the device: a Dev, or None for None"""
+def _mask(mask, shape):
+    """an optional uint8 mask of `shape`: the array to upload, or None for None"""
     if mask is None:
         return None
     mask = np.ascontiguousarray(mask, np.uint8)
     assert mask.shape == shape, (mask.shape, shape)
-    return Dev(mask)
+    return mask
 
 
 # ------------------------------------------------------------------ per-function entry points (numpy in/out)
@@ -313,22 +385,19 @@ def image_warp(src, wx, wy):
     """src [B,noc,h,w], wx/wy [B,h,w] -> dst [B,noc,h,w], mask [B,h,w]"""
     src, wx, wy = _f(src), _f(wx), _f(wy)
     B, noc, h, w = src.shape
-    dsrc, dwx, dwy = Dev(src), Dev(wx), Dev(wy)
-    ddst, dmask = Dev(nbytes=src.nbytes), Dev(nbytes=wx.nbytes)
-    check(lib().ofdis_image_warp(ddst.ptr, dmask.ptr, dsrc.ptr, dwx.ptr, dwy.ptr, w, h, noc, B, None))
-    check(lib().ofdis_sync(None))
-    return ddst.get(src.shape), dmask.get(wx.shape)
+    with DeviceCall() as c:
+        check(lib().ofdis_image_warp(c.output(src.shape), c.output(wx.shape), c.input(src), c.input(wx), c.input(wy), w, h, noc, B,
+                                     None))
+        return c.results()
 
 
 def get_derivatives(im1, im2w):
     """im1, im2w [B,noc,h,w] -> [B,8,noc,h,w]"""
     im1, im2w = _f(im1), _f(im2w)
     B, noc, h, w = im1.shape
-    d1, d2 = Dev(im1), Dev(im2w)
-    dout = Dev(nbytes=im1.nbytes * 8)
-    check(lib().ofdis_get_derivatives(dout.ptr, d1.ptr, d2.ptr, w, h, noc, B, None))
-    check(lib().ofdis_sync(None))
-    return dout.get((B, 8, noc, h, w))
+    with DeviceCall() as c:
+        check(lib().ofdis_get_derivatives(c.output((B, 8, noc, h, w)), c.input(im1), c.input(im2w), w, h, noc, B, None))
+        return c.results()[0]
 
 
 def tv_system(mask, wx, wy, du, dv, derivs, tv_alpha, tv_gamma, tv_delta):
@@ -336,45 +405,43 @@ def tv_system(mask, wx, wy, du, dv, derivs, tv_alpha, tv_gamma, tv_delta):
     mask, wx, wy, du, dv, derivs = [_f(x) for x in (mask, wx, wy, du, dv, derivs)]
     B, h, w = mask.shape
     noc = derivs.shape[2]
-    bufs = [Dev(x) for x in (mask, wx, wy, du, dv, derivs)]
-    dout = Dev(nbytes=mask.nbytes * 7)
-    check(lib().ofdis_tv_system(dout.ptr, *[b.ptr for b in bufs], tv_alpha, tv_gamma, tv_delta, w, h, noc, B, None))
-    check(lib().ofdis_sync(None))
-    return dout.get((B, 7, h, w))
+    with DeviceCall() as c:
+        check(lib().ofdis_tv_system(c.output((B, 7, h, w)), *[c.input(x) for x in (mask, wx, wy, du, dv, derivs)], tv_alpha,
+                                    tv_gamma, tv_delta, w, h, noc, B, None))
+        return c.results()[0]
 
 
 def sor_coupled(du, dv, sys, iterations, omega):
     """du, dv [B,h,w]; sys [B,7,h,w] -> new du, dv"""
     du, dv, sys = _f(du), _f(dv), _f(sys)
     B, h, w = du.shape
-    ddu, ddv, dsys = Dev(du), Dev(dv), Dev(sys)
-    check(lib().ofdis_sor_coupled(ddu.ptr, ddv.ptr, dsys.ptr, iterations, omega, w, h, B, None))
-    check(lib().ofdis_sync(None))
-    return ddu.get(du.shape), ddv.get(dv.shape)
+    with DeviceCall() as c:
+        check(lib().ofdis_sor_coupled(c.output(du.shape, fill=du), c.output(dv.shape, fill=dv), c.input(sys), iterations, omega,
+                                      w, h, B, None))
+        return c.results()
 
 
 def patchgrid_level(p, level, im_a, im_a_dx, im_a_dy, im_b, flow_prev=None):
     """Planes [B,tmp_h,tmp_w,noc]; flow_prev [B,h/2,w/2,2] or None -> p [B,nop,2], flow [B,h,w,2]"""
     im_a, im_a_dx, im_a_dy, im_b = [_f(x) for x in (im_a, im_a_dx, im_a_dy, im_b)]
+    flow_prev = _f(flow_prev) if flow_prev is not None else None
     B = im_a.shape[0]
     w, h = p.level_size(level)
     nw, nh = p.grid(level)
     nop = nw * nh
-    bufs = [Dev(x) for x in (im_a, im_a_dx, im_a_dy, im_b)]
-    dprev = Dev(_f(flow_prev)) if flow_prev is not None else None
-    dp, dflow = Dev(nbytes=B * nop * 2 * 4), Dev(nbytes=B * h * w * p.nop * 4)
-    check(lib().ofdis_patchgrid_level(C.byref(p), level, *[b.ptr for b in bufs], dprev.ptr if dprev else None,
-                                      dp.ptr, dflow.ptr, B, None))
-    return dp.get((B, nop, 2)), dflow.get((B, h, w, p.nop))
+    with DeviceCall() as c:
+        check(lib().ofdis_patchgrid_level(C.byref(p), level, *[c.input(x) for x in (im_a, im_a_dx, im_a_dy, im_b, flow_prev)],
+                                          c.output((B, nop, 2)), c.output((B, h, w, p.nop)), B, None))
+        return c.results()
 
 
 def varref_level(p, level, im_a, im_b, flow):
     """im_a, im_b [B,tmp_h,tmp_w,noc]; flow [B,h,w,2] -> refined flow"""
     im_a, im_b, flow = _f(im_a), _f(im_b), _f(flow)
     B = im_a.shape[0]
-    da, db, df = Dev(im_a), Dev(im_b), Dev(flow)
-    check(lib().ofdis_varref_level(C.byref(p), level, da.ptr, db.ptr, df.ptr, B, None))
-    return df.get(flow.shape)
+    with DeviceCall() as c:
+        check(lib().ofdis_varref_level(C.byref(p), level, c.input(im_a), c.input(im_b), c.output(flow.shape, fill=flow), B, None))
+        return c.results()[0]
 
 
 def _ptr_array(planes, n):
@@ -407,11 +474,9 @@ def fb_check(flow, other, alpha=FB_ALPHA, beta=FB_BETA):
     assert flow.shape == other.shape and flow.ndim >= 3 and flow.shape[-1] == 2, (flow.shape, other.shape)
     h, w = flow.shape[-3:-1]
     n = int(np.prod(flow.shape[:-3], dtype=np.int64))
-    df, do = Dev(flow), Dev(other)
-    dm = Dev(nbytes=max(1, n * h * w))
-    check(lib().ofdis_fb_check(df.ptr, do.ptr, dm.ptr, n, w, h, alpha, beta, None))
-    check(lib().ofdis_sync(None))
-    return dm.get(flow.shape[:-1], np.uint8)
+    with DeviceCall() as c:
+        check(lib().ofdis_fb_check(c.input(flow), c.input(other), c.output(flow.shape[:-1], np.uint8), n, w, h, alpha, beta, None))
+        return c.results()[0]
 
 
 def lr_check(disp, other, alpha=FB_ALPHA, beta=FB_BETA):
@@ -421,11 +486,9 @@ def lr_check(disp, other, alpha=FB_ALPHA, beta=FB_BETA):
     assert disp.shape == other.shape and disp.ndim >= 2, (disp.shape, other.shape)
     h, w = disp.shape[-2:]
     n = int(np.prod(disp.shape[:-2], dtype=np.int64))
-    dd, do = Dev(disp), Dev(other)
-    dm = Dev(nbytes=max(1, n * h * w))
-    check(lib().ofdis_lr_check(dd.ptr, do.ptr, dm.ptr, n, w, h, alpha, beta, None))
-    check(lib().ofdis_sync(None))
-    return dm.get(disp.shape, np.uint8)
+    with DeviceCall() as c:
+        check(lib().ofdis_lr_check(c.input(disp), c.input(other), c.output(disp.shape, np.uint8), n, w, h, alpha, beta, None))
+        return c.results()[0]
 
 
 def disparity_fill(disp, mask, mode, in_place=False):
@@ -436,21 +499,25 @@ def disparity_fill(disp, mask, mode, in_place=False):
     assert disp.shape == mask.shape and disp.ndim >= 2, (disp.shape, mask.shape)
     h, w = disp.shape[-2:]
     n = int(np.prod(disp.shape[:-2], dtype=np.int64))
-    dd, dm = Dev(disp), Dev(mask)
-    do = dd if in_place else Dev(nbytes=max(4, disp.nbytes))
-    check(lib().ofdis_disparity_fill(dd.ptr, dm.ptr, do.ptr, n, w, h, mode, None))
-    check(lib().ofdis_sync(None))
-    return do.get(disp.shape, _f32)
+    with DeviceCall() as c:
+        pd = c.input(disp)
+        check(lib().ofdis_disparity_fill(pd, c.input(mask), c.output(disp.shape, over=pd if in_place else None), n, w, h, mode,
+                                         None))
+        return c.results()[0]
+
+
+def _enc_dtype(enc):
+    """the dtype of an output in the encoding `enc`; bytes for an unknown type (ofdis_encoding_bytes gives 0), which the library
+    rejects"""
+    return enc.dtype if lib().ofdis_encoding_bytes(enc.type) else np.dtype(np.uint8)
 
 
 def encode(array, enc):
     """ofdis_encode on the device: a float32 array of any shape -> the same shape in enc.dtype."""
     a = _f(array)
-    out_bytes = a.size * lib().ofdis_encoding_bytes(enc.type)  # (0 for an unknown type: the library rejects it below)
-    ds, dd = Dev(a), Dev(nbytes=max(1, out_bytes))
-    check(lib().ofdis_encode(ds.ptr, dd.ptr, a.size, C.byref(enc), None))
-    check(lib().ofdis_sync(None))
-    return dd.get(a.shape, enc.dtype)
+    with DeviceCall() as c:
+        check(lib().ofdis_encode(c.input(a), c.output(a.shape, _enc_dtype(enc)), a.size, C.byref(enc), None))
+        return c.results()[0]
 
 
 def _times(times):
@@ -471,14 +538,12 @@ def interpolate(img_a, img_b, flow_fw, flow_rev, times, mask_fw=None, mask_rev=N
     assert img_a.shape == flow_fw.shape[:-1] + ((3,) if noc == 3 else ()), (img_a.shape, flow_fw.shape)
     n = int(np.prod(lead, dtype=np.int64))
     t, tp = _times(times)
-    devs = [Dev(x) for x in (img_a, img_b, flow_fw, flow_rev)]
-    masks = [_mask_dev(m, flow_fw.shape[:-1]) for m in (mask_fw, mask_rev)]
+    masks = [_mask(m, flow_fw.shape[:-1]) for m in (mask_fw, mask_rev)]
     shape = lead + (t.size, h, w) + ((3,) if noc == 3 else ())
-    do = Dev(nbytes=max(1, int(np.prod(shape, dtype=np.int64))))
-    check(lib().ofdis_interpolate(*[d.ptr for d in devs], *[m.ptr if m else None for m in masks], do.ptr, n, w, h, noc, tp,
-                                  t.size, None))
-    check(lib().ofdis_sync(None))
-    return do.get(shape, np.uint8)
+    with DeviceCall() as c:
+        check(lib().ofdis_interpolate(*[c.input(x) for x in (img_a, img_b, flow_fw, flow_rev, *masks)], c.output(shape, np.uint8),
+                                      n, w, h, noc, tp, t.size, None))
+        return c.results()[0]
 
 
 def _track_inputs(seeds, seed_frame):
@@ -498,13 +563,10 @@ def track_points(flow_fw, flow_rev, seeds, seed_frame=None, max_steps=0, alpha=F
     flow_fw, flow_rev, npairs, h, w = _pair_flows(flow_fw, flow_rev)
     seeds, seed_frame = _track_inputs(seeds, seed_frame)
     n = seeds.shape[0]
-    dfw, drev = Dev(flow_fw), Dev(flow_rev) if flow_rev is not None else None
-    dseeds, dsf = Dev(seeds), Dev(seed_frame) if seed_frame is not None else None
-    dtracks, dcounts = Dev(nbytes=max(8, (npairs + 1) * n * 8)), Dev(nbytes=max(4, n * 4))
-    check(lib().ofdis_track_points(dfw.ptr, drev.ptr if drev else None, npairs, w, h, dseeds.ptr, dsf.ptr if dsf else None, n,
-                                   max_steps, alpha, beta, dtracks.ptr, dcounts.ptr, None))
-    check(lib().ofdis_sync(None))
-    return dtracks.get((npairs + 1, n, 2), _f32), dcounts.get((n,), np.int32)
+    with DeviceCall() as c:
+        check(lib().ofdis_track_points(c.input(flow_fw), c.input(flow_rev), npairs, w, h, c.input(seeds), c.input(seed_frame), n,
+                                       max_steps, alpha, beta, c.output((npairs + 1, n, 2)), c.output((n,), np.int32), None))
+        return c.results()
 
 
 def dense_tracks_cells(width, height, stride):
@@ -529,29 +591,50 @@ def seed_texture(frames, stride, window, min_eig):
     n, h, w = frames.shape[:3]
     frames, noc = _clip_frames(frames, n, h, w)
     ncx, ncy = dense_tracks_cells(w, h, stride)
-    df, do = Dev(frames), Dev(nbytes=max(1, n * ncx * ncy))
-    check(lib().ofdis_seed_texture(df.ptr, n, w, h, noc, stride, window, min_eig, do.ptr, None))
-    check(lib().ofdis_sync(None))
-    return do.get((n, ncy, ncx), np.uint8)
+    with DeviceCall() as c:
+        check(lib().ofdis_seed_texture(c.input(frames), n, w, h, noc, stride, window, min_eig, c.output((n, ncy, ncx), np.uint8),
+                                       None))
+        return c.results()[0]
 
 
 def _dense_lmax(max_len, npairs):
     return min(max_len, npairs) if max_len else npairs
 
 
+def _dense_specs(lmax, slots):
+    """(shape, dtype) of the four outputs of a dense_tracks call with `slots` track slots: tracks, start, len, info"""
+    return [((lmax + 1, slots, 2), _f32), ((slots,), np.int32), ((slots,), np.int32), ((2,), np.int64)]
+
+
+def _dense_declare(c, lmax, slots):
+    """those four outputs declared on the DeviceCall `c`: their pointers"""
+    return tuple(c.output(shape, dtype) for shape, dtype in _dense_specs(lmax, slots))
+
+
+def _dense_cut(arrays, lmax, max_tracks):
+    """the four host arrays of such a call -> (tracks [lmax + 1, ntracks, 2], start [ntracks], len [ntracks], info [2]): the
+    slots the call wrote"""
+    tracks, start, length, info = arrays
+    n = int(info[0])
+    assert 0 <= n <= max_tracks and tracks.shape[0] == lmax + 1, (info, tracks.shape)
+    return np.ascontiguousarray(tracks[:, :n]), start[:n].copy(), length[:n].copy(), info
+
+
 def _dense_outputs(lmax, max_tracks):
-    """device arrays of a dense_tracks call: tracks, start, len, info"""
-    return (Dev(nbytes=(lmax + 1) * max_tracks * 8), Dev(nbytes=max_tracks * 4), Dev(nbytes=max_tracks * 4), Dev(nbytes=16))
+    """The same four outputs as device arrays of the caller's, outside a DeviceCall: tests/test_gpu_level_routes.py hands their
+    pointers to a launch hook, synchronises and reads them back with _dense_results."""
+    return tuple(Dev(nbytes=int(np.prod(shape, dtype=np.int64)) * np.dtype(dtype).itemsize)
+                 for shape, dtype in _dense_specs(lmax, max_tracks))
 
 
 def _dense_results(devs, lmax, max_tracks):
-    """(tracks [lmax + 1, ntracks, 2], start [ntracks], len [ntracks], info [2]): the slots the call wrote"""
-    dt, ds, dl, di = devs
-    info = di.get((2,), np.int64)
-    n = int(info[0])
-    assert 0 <= n <= max_tracks, info
-    tracks = dt.get((lmax + 1, max_tracks, 2), _f32)[:, :n]
-    return np.ascontiguousarray(tracks), ds.get((max_tracks,), np.int32)[:n].copy(), dl.get((max_tracks,), np.int32)[:n].copy(), info
+    """the device arrays of _dense_outputs, after the caller's sync -> what _dense_cut returns"""
+    return _dense_cut([d.get(shape, dtype) for d, (shape, dtype) in zip(devs, _dense_specs(lmax, max_tracks))], lmax, max_tracks)
+
+
+def _track_info(n):
+    """the `info` ofdis_dense_tracks writes, for n tracks on the host: (ntracks, dropped)"""
+    return np.array([n, 0], np.int64)
 
 
 def dense_tracks(frames, flow_fw, flow_rev, stride, window, min_eig, max_len=15, max_tracks=None, alpha=FB_ALPHA, beta=FB_BETA):
@@ -566,15 +649,12 @@ def dense_tracks(frames, flow_fw, flow_rev, stride, window, min_eig, max_len=15,
     if max_tracks is None:
         max_tracks = max(1, min(npairs * ncx * ncy, DT_MAX_TRACKS))
     lmax = _dense_lmax(max_len, npairs)
-    dfr, dfw, drev = Dev(frames), Dev(flow_fw), Dev(flow_rev) if flow_rev is not None else None
-    outs = _dense_outputs(lmax, max(1, min(max_tracks, DT_MAX_TRACKS)))
     wb = lib().ofdis_dense_tracks_work_bytes(npairs, w, h, stride)
-    dwork = Dev(nbytes=max(8, wb))
-    check(lib().ofdis_dense_tracks(dfr.ptr, dfw.ptr, drev.ptr if drev else None, npairs, w, h, noc, stride, window, min_eig,
-                                   max_len, alpha, beta, max_tracks, outs[0].ptr, outs[1].ptr, outs[2].ptr, outs[3].ptr,
-                                   dwork.ptr, wb, None))
-    check(lib().ofdis_sync(None))
-    return _dense_results(outs, lmax, max_tracks)
+    with DeviceCall() as c:
+        check(lib().ofdis_dense_tracks(c.input(frames), c.input(flow_fw), c.input(flow_rev), npairs, w, h, noc, stride, window,
+                                       min_eig, max_len, alpha, beta, max_tracks,
+                                       *_dense_declare(c, lmax, max(1, min(max_tracks, DT_MAX_TRACKS))), c.work(wb), wb, None))
+        return _dense_cut(c.results(), lmax, max_tracks)
 
 
 def track_select_work_bytes(max_tracks):
@@ -614,28 +694,26 @@ def track_select(tracks, start, length, models=None, size=None, params=None, max
     assert start.shape == length.shape == (n,), (start.shape, length.shape, n)
     slots = max(n, 1)  # (the library takes no empty array)
     out = slots if max_out is None else int(max_out)
-    dm, npairs, w, h, nparam = None, 0, 0, 0, 6
+    oslots = max(out, 1)
+    npairs, w, h, nparam = 0, 0, 0, 6
     if models is not None:
         models = np.ascontiguousarray(models, np.float64)
         nparam = 8 if models.ndim == 2 and models.shape[1] == 8 else 6
         models = models.reshape(-1, nparam)
-        dm, npairs, (w, h) = Dev(models), len(models), size
-    dt = Dev(tracks if n else np.zeros((lmax + 1, 1, 2), _f32))
-    ds, dl = (Dev(a if n else np.zeros(1, np.int32)) for a in (start, length))
-    di = Dev(np.array([n, 0], np.int64))
-    dcode, dcounts = Dev(nbytes=slots), Dev(nbytes=56)
-    outs = _dense_outputs(lmax, max(out, 1))
-    dindex, dshape = Dev(nbytes=max(out, 1) * 4), Dev(nbytes=max(out, 1) * lmax * 8) if shape else None
+        npairs, (w, h) = len(models), size
+    if not n:
+        tracks, start, length = np.zeros((lmax + 1, 1, 2), _f32), np.zeros(1, np.int32), np.zeros(1, np.int32)
     wb = track_select_work_bytes(slots)
-    dwork = Dev(nbytes=max(8, wb))
-    track_select_dev(dt.ptr, ds.ptr, dl.ptr, di.ptr, lmax, slots, out, outs[0].ptr, outs[1].ptr, outs[2].ptr, outs[3].ptr,
-                     dwork.ptr, wb, dm.ptr if dm else None, npairs, w, h, params, dcode.ptr, dcounts.ptr, dindex.ptr,
-                     dshape.ptr if dshape else None, nparam=nparam)
-    check(lib().ofdis_sync(None))
-    tracks_out, start_out, len_out, info = _dense_results(outs, lmax, out)
+    with DeviceCall() as c:  # (in the order of track_select_dev's parameters)
+        track_select_dev(*[c.input(a) for a in (tracks, start, length, _track_info(n))], lmax, slots, out,
+                         *_dense_declare(c, lmax, oslots), c.work(wb), wb, c.input(models), npairs, w, h, params,
+                         c.output((slots,), np.uint8), c.output((7,), np.int64), c.output((oslots,), np.int32),
+                         c.output((oslots, lmax, 2), _f32, shape), nparam=nparam)
+        *dense, code, counts, index, shape_out = c.results()
+    tracks_out, start_out, len_out, info = _dense_cut(dense, lmax, out)
     k = int(info[0])
-    return (dcode.get((slots,), np.uint8)[:n].copy(), dcounts.get((7,), np.int64), tracks_out, start_out, len_out, info,
-            dindex.get((out,), np.int32)[:k].copy(), dshape.get((out, lmax, 2), _f32)[:k].copy() if dshape else None)
+    return (code[:n].copy(), counts, tracks_out, start_out, len_out, info, index[:k].copy(),
+            shape_out[:k].copy() if shape else None)
 
 
 def track_descriptor_dims(patch, nxy, nt):
@@ -666,23 +744,32 @@ def track_descriptors(frames, flow_fw, tracks, start, length, patch, nxy, nt, mi
     assert start.shape == length.shape == (n,), (start.shape, length.shape, n)
     D = track_descriptor_dims(patch, nxy, nt)
     slots = max(n, 1)  # (the library takes no empty array)
-    dfr, dfw = Dev(frames), Dev(flow_fw)
-    dt = Dev(tracks if n else np.zeros((lmax + 1, 1, 2), _f32))
-    ds, dl = (Dev(a if n else np.zeros(1, np.int32)) for a in (start, length))
-    di = Dev(np.array([n, 0], np.int64))
-    dh, dsh = Dev(nbytes=max(1, slots * D * 4)), Dev(nbytes=slots * lmax * 8) if shape else None
-    track_descriptors_dev(dfr.ptr, dfw.ptr, npairs, w, h, noc, dt.ptr, ds.ptr, dl.ptr, di.ptr, lmax, slots, patch, nxy, nt,
-                          min_flow, dh.ptr, dsh.ptr if dsh else None)
-    check(lib().ofdis_sync(None))
-    return (dh.get((slots, D), np.uint32)[:n].copy(), dsh.get((slots, lmax, 2), _f32)[:n].copy() if dsh else None)
+    if not n:
+        tracks, start, length = np.zeros((lmax + 1, 1, 2), _f32), np.zeros(1, np.int32), np.zeros(1, np.int32)
+    with DeviceCall() as c:
+        track_descriptors_dev(c.input(frames), c.input(flow_fw), npairs, w, h, noc,
+                              *[c.input(a) for a in (tracks, start, length, _track_info(n))], lmax, slots, patch, nxy, nt, min_flow,
+                              c.output((slots, D), np.uint32), c.output((slots, lmax, 2), _f32, shape))
+        hist, shape_out = c.results()
+    return hist[:n].copy(), shape_out[:n].copy() if shape else None
 
 
 def _bof_inputs(rows, D, dtype):
-    """[ntracks, D] rows of `dtype` -> (the rows, ntracks, slots, a Dev of them with one idle slot for an empty array)"""
+    """[ntracks, D] rows of `dtype` -> (the rows to upload: one idle slot for an empty array, ntracks, slots)"""
     rows = np.ascontiguousarray(rows, dtype)
     assert rows.ndim == 2 and rows.shape[1] == D, (rows.shape, D)
     n = rows.shape[0]
-    return rows, n, max(n, 1), Dev(rows if n else np.zeros((1, D), dtype))
+    return rows if n else np.zeros((1, D), dtype), n, max(n, 1)
+
+
+def _bof_len(length, n, optional=False):
+    """length [ntracks] int32 -> the array to upload: one idle slot for an empty array.  optional: None stays None (the k-means
+    calls: every track is a member)"""
+    if optional and length is None:
+        return None
+    length = np.ascontiguousarray(length, np.int32)
+    assert length.shape == (n,), (length.shape, n)
+    return length if n else np.zeros(1, np.int32)
 
 
 def _bof_codebook(codebook, D):
@@ -695,11 +782,11 @@ def descriptor_normalize(hist, nxy, nt):
     """ofdis_descriptor_normalize on host arrays: hist uint32 [ntracks, 33 * nxy^2 * nt] -> desc uint8 of the same shape, every
     channel an 8-bit RootSIFT descriptor in units of 1 / BOF_SCALE.  of_dis_amd/tracking.py: normalize_descriptors_u8."""
     D = 33 * nxy * nxy * nt
-    hist, n, slots, dh = _bof_inputs(hist, D, np.uint32)
-    di, dd = Dev(np.array([n, 0], np.int64)), Dev(nbytes=slots * D)
-    check(lib().ofdis_descriptor_normalize(dh.ptr, di.ptr, slots, nxy, nt, dd.ptr, None))
-    check(lib().ofdis_sync(None))
-    return dd.get((slots, D), np.uint8)[:n].copy()
+    hist, n, slots = _bof_inputs(hist, D, np.uint32)
+    with DeviceCall() as c:
+        check(lib().ofdis_descriptor_normalize(c.input(hist), c.input(_track_info(n)), slots, nxy, nt,
+                                               c.output((slots, D), np.uint8), None))
+        return c.results()[0][:n].copy()
 
 
 def codebook_assign(desc, codebook, nxy, nt):
@@ -707,25 +794,23 @@ def codebook_assign(desc, codebook, nxy, nt):
     [ntracks, 4]: per channel (HOG, HOF, MBHx, MBHy) the nearest word, the lowest index on a tie, and its squared distance.
     of_dis_amd/tracking.py: codebook_assign_ref."""
     D = 33 * nxy * nxy * nt
-    desc, n, slots, dd = _bof_inputs(desc, D, np.uint8)
+    desc, n, slots = _bof_inputs(desc, D, np.uint8)
     codebook = _bof_codebook(codebook, D)
-    di, dc = Dev(np.array([n, 0], np.int64)), Dev(codebook)
-    dw, ds = Dev(nbytes=slots * 16), Dev(nbytes=slots * 16)
-    check(lib().ofdis_codebook_assign(dd.ptr, di.ptr, slots, nxy, nt, dc.ptr, len(codebook), dw.ptr, ds.ptr, None))
-    check(lib().ofdis_sync(None))
-    return dw.get((slots, 4), np.int32)[:n].copy(), ds.get((slots, 4), np.int32)[:n].copy()
+    with DeviceCall() as c:
+        check(lib().ofdis_codebook_assign(c.input(desc), c.input(_track_info(n)), slots, nxy, nt, c.input(codebook), len(codebook),
+                                          c.output((slots, 4), np.int32), c.output((slots, 4), np.int32), None))
+        words, dist = c.results()
+    return words[:n].copy(), dist[:n].copy()
 
 
 def bof_histogram(words, length, nwords, min_len=1):
     """ofdis_bof_histogram on host arrays: words int32 [ntracks, 4], length int32 [ntracks] -> bof uint32 [4, nwords], the tracks
     of at least min_len points counted by their words.  of_dis_amd/tracking.py: bof_ref."""
-    words, n, slots, dw = _bof_inputs(words, 4, np.int32)
-    length = np.ascontiguousarray(length, np.int32)
-    assert length.shape == (n,), (length.shape, n)
-    dl, di, db = Dev(length if n else np.zeros(1, np.int32)), Dev(np.array([n, 0], np.int64)), Dev(nbytes=16 * nwords)
-    check(lib().ofdis_bof_histogram(dw.ptr, dl.ptr, di.ptr, slots, nwords, min_len, db.ptr, None))
-    check(lib().ofdis_sync(None))
-    return db.get((4, nwords), np.uint32)
+    words, n, slots = _bof_inputs(words, 4, np.int32)
+    with DeviceCall() as c:
+        check(lib().ofdis_bof_histogram(c.input(words), c.input(_bof_len(length, n)), c.input(_track_info(n)), slots, nwords,
+                                        min_len, c.output((4, nwords), np.uint32), None))
+        return c.results()[0]
 
 
 def track_bof_dev(hist_ptr, len_ptr, info_ptr, max_tracks, nxy, nt, codebook_ptr, nwords, min_len, bof_ptr, words_ptr=None,
@@ -742,16 +827,13 @@ def track_bof(hist, length, codebook, nxy, nt, min_len=1, words=False):
     uint8 [nwords, D] -> bof uint32 [4, nwords], or (bof, words int32 [ntracks, 4]) with words=True: normalisation, assignment
     and counting in one pass, bit-identical to descriptor_normalize -> codebook_assign -> bof_histogram."""
     D = 33 * nxy * nxy * nt
-    hist, n, slots, dh = _bof_inputs(hist, D, np.uint32)
+    hist, n, slots = _bof_inputs(hist, D, np.uint32)
     codebook = _bof_codebook(codebook, D)
-    length = np.ascontiguousarray(length, np.int32)
-    assert length.shape == (n,), (length.shape, n)
-    dl, di, dc = Dev(length if n else np.zeros(1, np.int32)), Dev(np.array([n, 0], np.int64)), Dev(codebook)
-    db, dw = Dev(nbytes=16 * len(codebook)), Dev(nbytes=slots * 16) if words else None
-    track_bof_dev(dh.ptr, dl.ptr, di.ptr, slots, nxy, nt, dc.ptr, len(codebook), min_len, db.ptr, dw.ptr if dw else None)
-    check(lib().ofdis_sync(None))
-    bof = db.get((4, len(codebook)), np.uint32)
-    return (bof, dw.get((slots, 4), np.int32)[:n].copy()) if words else bof
+    with DeviceCall() as c:
+        track_bof_dev(c.input(hist), c.input(_bof_len(length, n)), c.input(_track_info(n)), slots, nxy, nt, c.input(codebook),
+                      len(codebook), min_len, c.output((4, len(codebook)), np.uint32), c.output((slots, 4), np.int32, words))
+        bof, words_out = c.results()
+    return (bof, words_out[:n].copy()) if words else bof
 
 
 def codebook_train_work_bytes(max_tracks, nxy, nt, nwords):
@@ -759,25 +841,16 @@ def codebook_train_work_bytes(max_tracks, nxy, nt, nwords):
     return int(lib().ofdis_codebook_train_work_bytes(max_tracks, nxy, nt, nwords))
 
 
-def _kmeans_len(length, n):
-    """length [ntracks] or None -> a Dev of it, or None: every track is a member"""
-    if length is None:
-        return None
-    length = np.ascontiguousarray(length, np.int32)
-    assert length.shape == (n,), (length.shape, n)
-    return Dev(length if n else np.zeros(1, np.int32))
-
-
 def codebook_seed(desc, nxy, nt, nwords, length=None, min_len=1):
     """ofdis_codebook_seed on host arrays: desc uint8 [ntracks, D], length int32 [ntracks] or None -> codebook uint8 [nwords, D],
     row k the descriptor of the first track of at least min_len points at or after slot floor((2 k + 1) ntracks / (2 nwords)),
     cyclically; all zero without such a track.  of_dis_amd/tracking.py: codebook_seed_ref."""
     D = 33 * nxy * nxy * nt
-    desc, n, slots, dd = _bof_inputs(desc, D, np.uint8)
-    dl, di, dc = _kmeans_len(length, n), Dev(np.array([n, 0], np.int64)), Dev(nbytes=nwords * D)
-    check(lib().ofdis_codebook_seed(dd.ptr, dl.ptr if dl else None, di.ptr, slots, nxy, nt, nwords, min_len, dc.ptr, None))
-    check(lib().ofdis_sync(None))
-    return dc.get((nwords, D), np.uint8)
+    desc, n, slots = _bof_inputs(desc, D, np.uint8)
+    with DeviceCall() as c:
+        check(lib().ofdis_codebook_seed(c.input(desc), c.input(_bof_len(length, n, optional=True)), c.input(_track_info(n)), slots,
+                                        nxy, nt, nwords, min_len, c.output((nwords, D), np.uint8), None))
+        return c.results()[0]
 
 
 def codebook_update(desc, words, codebook, nxy, nt, length=None, min_len=1):
@@ -785,18 +858,19 @@ def codebook_update(desc, words, codebook, nxy, nt, length=None, min_len=1):
     (codebook, counts uint32 [4, nwords]): per channel every word with members becomes their mean, rounded half up; a word
     without members keeps its bytes.  of_dis_amd/tracking.py: codebook_update_ref."""
     D = 33 * nxy * nxy * nt
-    desc, n, slots, dd = _bof_inputs(desc, D, np.uint8)
+    desc, n, slots = _bof_inputs(desc, D, np.uint8)
     codebook = _bof_codebook(codebook, D)
     words = np.ascontiguousarray(words, np.int32)
     assert words.shape == (n, 4), (words.shape, n)
-    dw, dl, di = Dev(words if n else np.zeros((1, 4), np.int32)), _kmeans_len(length, n), Dev(np.array([n, 0], np.int64))
+    words = words if n else np.zeros((1, 4), np.int32)
     nwords = len(codebook)
-    dc, dn = Dev(codebook), Dev(nbytes=16 * nwords)
-    work = Dev(nbytes=codebook_train_work_bytes(slots, nxy, nt, nwords))
-    check(lib().ofdis_codebook_update(dd.ptr, dw.ptr, dl.ptr if dl else None, di.ptr, slots, nxy, nt, nwords, min_len, dc.ptr, dn.ptr,
-                                      work.ptr, work.nbytes, None))
-    check(lib().ofdis_sync(None))
-    return dc.get((nwords, D), np.uint8), dn.get((4, nwords), np.uint32)
+    wb = codebook_train_work_bytes(slots, nxy, nt, nwords)
+    with DeviceCall() as c:
+        check(lib().ofdis_codebook_update(c.input(desc), c.input(words), c.input(_bof_len(length, n, optional=True)),
+                                          c.input(_track_info(n)), slots, nxy, nt, nwords, min_len,
+                                          c.output((nwords, D), np.uint8, fill=codebook), c.output((4, nwords), np.uint32),
+                                          c.work(wb), wb, None))
+        return c.results()
 
 
 def codebook_train_dev(desc_ptr, len_ptr, info_ptr, max_tracks, nxy, nt, nwords, min_len, iters, codebook_ptr, words_ptr, counts_ptr,
@@ -815,17 +889,16 @@ def codebook_train(desc, codebook, nxy, nt, iters, length=None, min_len=1):
     rounds of Lloyd's algorithm; stats[t][c] = (the members whose word changed, the sum of their squared distances).  words and
     counts belong to the last assignment, taken before the last update.  of_dis_amd/tracking.py: codebook_train_ref."""
     D = 33 * nxy * nxy * nt
-    desc, n, slots, dd = _bof_inputs(desc, D, np.uint8)
+    desc, n, slots = _bof_inputs(desc, D, np.uint8)
     codebook = _bof_codebook(codebook, D)
     nwords = len(codebook)
-    dl, di, dc = _kmeans_len(length, n), Dev(np.array([n, 0], np.int64)), Dev(codebook)
-    dw, dn, ds = Dev(nbytes=slots * 16), Dev(nbytes=16 * nwords), Dev(nbytes=iters * 64)
-    work = Dev(nbytes=codebook_train_work_bytes(slots, nxy, nt, nwords))
-    codebook_train_dev(dd.ptr, dl.ptr if dl else None, di.ptr, slots, nxy, nt, nwords, min_len, iters, dc.ptr, dw.ptr, dn.ptr, ds.ptr,
-                       work.ptr, work.nbytes)
-    check(lib().ofdis_sync(None))
-    return (dc.get((nwords, D), np.uint8), dw.get((slots, 4), np.int32)[:n].copy(), dn.get((4, nwords), np.uint32),
-            ds.get((iters, 4, 2), np.int64))
+    wb = codebook_train_work_bytes(slots, nxy, nt, nwords)
+    with DeviceCall() as c:
+        codebook_train_dev(c.input(desc), c.input(_bof_len(length, n, optional=True)), c.input(_track_info(n)), slots, nxy, nt,
+                           nwords, min_len, iters, c.output((nwords, D), np.uint8, fill=codebook), c.output((slots, 4), np.int32),
+                           c.output((4, nwords), np.uint32), c.output((iters, 4, 2), np.int64), c.work(wb), wb)
+        codebook, words, counts, stats = c.results()
+    return codebook, words[:n].copy(), counts, stats
 
 
 def temporal_filter(frames, flow_fw, flow_rev, mask_fw=None, mask_rev=None, wn=1.0, tau=np.inf, support=True):
@@ -835,14 +908,12 @@ def temporal_filter(frames, flow_fw, flow_rev, mask_fw=None, mask_rev=None, wn=1
     of_dis_amd/temporal.py: temporal_filter_ref is the numpy statement of the same arithmetic."""
     flow_fw, flow_rev, npairs, h, w = _pair_flows(flow_fw, _f(flow_rev))
     frames, noc = _clip_frames(frames, npairs + 1, h, w)
-    devs = [Dev(x) for x in (frames, flow_fw, flow_rev)]
-    masks = [_mask_dev(m, (npairs, h, w)) for m in (mask_fw, mask_rev)]
-    do = Dev(nbytes=frames.nbytes)
-    ds = Dev(nbytes=(npairs + 1) * h * w) if support else None
-    check(lib().ofdis_temporal_filter(*[d.ptr for d in devs], *[m.ptr if m else None for m in masks], do.ptr,
-                                      ds.ptr if ds else None, npairs, w, h, noc, wn, tau, None))
-    check(lib().ofdis_sync(None))
-    return do.get(frames.shape, np.uint8), ds.get((npairs + 1, h, w), np.uint8) if ds else None
+    masks = [_mask(m, (npairs, h, w)) for m in (mask_fw, mask_rev)]
+    with DeviceCall() as c:
+        check(lib().ofdis_temporal_filter(*[c.input(x) for x in (frames, flow_fw, flow_rev, *masks)],
+                                          c.output(frames.shape, np.uint8), c.output((npairs + 1, h, w), np.uint8, support),
+                                          npairs, w, h, noc, wn, tau, None))
+        return c.results()
 
 
 def _weights(weights):
@@ -859,19 +930,17 @@ def trajectory_filter(frames, flow_fw, flow_rev, weights, tau=np.inf, fb_check=T
     flow_fw, flow_rev, npairs, h, w = _pair_flows(flow_fw, _f(flow_rev))
     frames, noc = _clip_frames(frames, npairs + 1, h, w)
     wts, wp = _weights(weights)
-    devs = [Dev(x) for x in (frames, flow_fw, flow_rev)]
-    do = Dev(nbytes=frames.nbytes)
-    ds = Dev(nbytes=(npairs + 1) * h * w) if support else None
-    check(lib().ofdis_trajectory_filter(*[d.ptr for d in devs], do.ptr, ds.ptr if ds else None, npairs, w, h, noc, wp, wts.size,
-                                        tau, int(fb_check), alpha, beta, None))
-    check(lib().ofdis_sync(None))
-    return do.get(frames.shape, np.uint8), ds.get((npairs + 1, h, w), np.uint8) if ds else None
+    with DeviceCall() as c:
+        check(lib().ofdis_trajectory_filter(c.input(frames), c.input(flow_fw), c.input(flow_rev), c.output(frames.shape, np.uint8),
+                                            c.output((npairs + 1, h, w), np.uint8, support), npairs, w, h, noc, wp, wts.size,
+                                            tau, int(fb_check), alpha, beta, None))
+        return c.results()
 
 
 def _gm_inputs(flow, mask):
-    """(flow [npairs, h, w, 2] float32, its optional mask on the device, npairs, h, w)"""
+    """(flow [npairs, h, w, 2] float32, its optional mask uint8 [npairs, h, w], npairs, h, w)"""
     flow, _, npairs, h, w = _pair_flows(flow)
-    return flow, _mask_dev(mask, (npairs, h, w)), npairs, h, w
+    return flow, _mask(mask, (npairs, h, w)), npairs, h, w
 
 
 # The camera-model families by nparam, the doubles per model (a pair's model takes nparam * 8 bytes): the C functions of the
@@ -885,28 +954,26 @@ _CAMERA = {6: dict(fit="ofdis_global_motion", compensate="ofdis_motion_compensat
 
 def _camera_fit(nparam, flow, mask, model, rounds, thresh, stats):
     fam = _CAMERA[nparam]
-    flow, dm, npairs, h, w = _gm_inputs(flow, mask)
-    df = Dev(flow)
-    dmodels, dstats = Dev(nbytes=max(8, npairs * nparam * 8)), Dev(nbytes=max(8, npairs * 24)) if stats else None
+    flow, mask, npairs, h, w = _gm_inputs(flow, mask)
     wb = getattr(lib(), fam["fit"] + "_work_bytes")(npairs, w, h)
-    dwork = Dev(nbytes=max(8, wb))
-    check(getattr(lib(), fam["fit"])(df.ptr, dm.ptr if dm else None, npairs, w, h, *([model] if fam["model_arg"] else []), rounds,
-                                     thresh, dmodels.ptr, dstats.ptr if dstats else None, dwork.ptr, wb, None))
-    check(lib().ofdis_sync(None))
-    return dmodels.get((npairs, nparam), np.float64), dstats.get((npairs, 3), np.int64) if dstats else None
+    fit = getattr(lib(), fam["fit"])
+    with DeviceCall() as c:
+        check(fit(c.input(flow), c.input(mask), npairs, w, h, *([model] if fam["model_arg"] else []), rounds, thresh,
+                  c.output((npairs, nparam), np.float64), c.output((npairs, 3), np.int64, stats), c.work(wb), wb, None))
+        return c.results()
 
 
 def _camera_compensate(nparam, flow, models, mask, thresh, residual, label, in_place):
-    flow, dm, npairs, h, w = _gm_inputs(flow, mask)
+    flow, mask, npairs, h, w = _gm_inputs(flow, mask)
     models = np.ascontiguousarray(models, np.float64)
     assert models.shape == (npairs, nparam), models.shape
-    df, dmodels = Dev(flow), Dev(models)
-    dr = (df if in_place else Dev(nbytes=max(8, flow.nbytes))) if residual else None
-    dl = Dev(nbytes=max(1, npairs * h * w)) if label else None
-    check(getattr(lib(), _CAMERA[nparam]["compensate"])(df.ptr, dm.ptr if dm else None, dmodels.ptr, npairs, w, h, thresh,
-                                                        dr.ptr if dr else None, dl.ptr if dl else None, None))
-    check(lib().ofdis_sync(None))
-    return dr.get(flow.shape, _f32) if dr else None, dl.get((npairs, h, w), np.uint8) if dl else None
+    compensate = getattr(lib(), _CAMERA[nparam]["compensate"])
+    with DeviceCall() as c:
+        pflow = c.input(flow)
+        check(compensate(pflow, c.input(mask), c.input(models), npairs, w, h, thresh,
+                         c.output(flow.shape, _f32, residual, over=pflow if in_place else None),
+                         c.output((npairs, h, w), np.uint8, label), None))
+        return c.results()
 
 
 def global_motion(flow, mask=None, model=GM_AFFINE, rounds=3, thresh=1.0, stats=True):
@@ -947,25 +1014,19 @@ def label_segments(label, flow=None, codes=SEG_MOVING, conn=8, min_area=0, max_s
     nmaps, h, w = label.shape
     if max_segments is None:
         max_segments = min(h * w, SEG_MAX_SEGMENTS)
-    dl = Dev(label)
-    df = None
     if flow is not None:
         flow = _f(flow)
         assert flow.shape == (nmaps, h, w, 2), flow.shape
-        df = Dev(flow)
-    ds = Dev(nbytes=max(8, nmaps * h * w * 4)) if segments else None
     rshape = (nmaps, max_segments, SEG_RECORD_FIELDS)
-    dr = None
-    if records:
-        dr = Dev(np.zeros(rshape, np.int64) if records_fill is None else np.ascontiguousarray(records_fill, np.int64).reshape(rshape))
-    di = Dev(nbytes=nmaps * SEG_INFO_FIELDS * 8)
+    if records and records_fill is None:
+        records_fill = np.zeros(rshape, np.int64)
     wb = lib().ofdis_segments_work_bytes(nmaps, w, h)
-    dwork = Dev(nbytes=max(8, wb))
-    check(lib().ofdis_label_segments(dl.ptr, df.ptr if df else None, nmaps, w, h, codes, conn, min_area, max_segments,
-                                     ds.ptr if ds else None, dr.ptr if dr else None, di.ptr, dwork.ptr, wb, None))
-    check(lib().ofdis_sync(None))
-    return (ds.get((nmaps, h, w), np.int32) if ds else None, dr.get(rshape, np.int64) if dr else None,
-            di.get((nmaps, SEG_INFO_FIELDS), np.int64))
+    with DeviceCall() as c:
+        check(lib().ofdis_label_segments(c.input(label), c.input(flow), nmaps, w, h, codes, conn, min_area, max_segments,
+                                         c.output((nmaps, h, w), np.int32, segments),
+                                         c.output(rshape, np.int64, records, fill=records_fill),
+                                         c.output((nmaps, SEG_INFO_FIELDS), np.int64), c.work(wb), wb, None))
+        return c.results()
 
 
 def _stab_weights(weights):
@@ -983,10 +1044,10 @@ def camera_path(models, weights, zoom=1.0):
     assert models.ndim == 2 and models.shape[1] == 6, models.shape
     npairs = models.shape[0]
     weights, radius = _stab_weights(weights)
-    dm, dw = Dev(models), Dev(nbytes=(npairs + 1) * 48)
-    check(lib().ofdis_camera_path(dm.ptr, npairs, weights.ctypes.data, radius, zoom, dw.ptr, None))
-    check(lib().ofdis_sync(None))
-    return dw.get((npairs + 1, 6), np.float64)
+    with DeviceCall() as c:
+        check(lib().ofdis_camera_path(c.input(models), npairs, weights.ctypes.data, radius, zoom,
+                                      c.output((npairs + 1, 6), np.float64), None))
+        return c.results()[0]
 
 
 def warp_frames(frames, warps, border=BORDER_CONSTANT, inside=True):
@@ -997,11 +1058,10 @@ def warp_frames(frames, warps, border=BORDER_CONSTANT, inside=True):
     frames, noc = _clip_frames(frames, n, h, w)
     warps = np.ascontiguousarray(warps, np.float64)
     assert warps.shape == (n, 6), warps.shape
-    df, dw, do = Dev(frames), Dev(warps), Dev(nbytes=frames.nbytes)
-    di = Dev(nbytes=n * h * w) if inside else None
-    check(lib().ofdis_warp_frames(df.ptr, dw.ptr, do.ptr, di.ptr if di else None, n, w, h, noc, border, None))
-    check(lib().ofdis_sync(None))
-    return do.get(frames.shape, np.uint8), di.get((n, h, w), np.uint8) if di else None
+    with DeviceCall() as c:
+        check(lib().ofdis_warp_frames(c.input(frames), c.input(warps), c.output(frames.shape, np.uint8),
+                                      c.output((n, h, w), np.uint8, inside), n, w, h, noc, border, None))
+        return c.results()
 
 
 def camera_path_projective(models, weights, w, h, zoom=1.0):
@@ -1012,10 +1072,10 @@ def camera_path_projective(models, weights, w, h, zoom=1.0):
     assert models.ndim == 2 and models.shape[1] == 8, models.shape
     npairs = models.shape[0]
     weights, radius = _stab_weights(weights)
-    dm, dw = Dev(models), Dev(nbytes=(npairs + 1) * 64)
-    check(lib().ofdis_camera_path_projective(dm.ptr, npairs, w, h, weights.ctypes.data, radius, zoom, dw.ptr, None))
-    check(lib().ofdis_sync(None))
-    return dw.get((npairs + 1, 8), np.float64)
+    with DeviceCall() as c:
+        check(lib().ofdis_camera_path_projective(c.input(models), npairs, w, h, weights.ctypes.data, radius, zoom,
+                                                 c.output((npairs + 1, 8), np.float64), None))
+        return c.results()[0]
 
 
 def warp_frames_projective(frames, warps, border=BORDER_CONSTANT, inside=True):
@@ -1025,11 +1085,10 @@ def warp_frames_projective(frames, warps, border=BORDER_CONSTANT, inside=True):
     frames, noc = _clip_frames(frames, n, h, w)
     warps = np.ascontiguousarray(warps, np.float64)
     assert warps.shape == (n, 8), warps.shape
-    df, dw, do = Dev(frames), Dev(warps), Dev(nbytes=frames.nbytes)
-    di = Dev(nbytes=n * h * w) if inside else None
-    check(lib().ofdis_warp_frames_projective(df.ptr, dw.ptr, do.ptr, di.ptr if di else None, n, w, h, noc, border, None))
-    check(lib().ofdis_sync(None))
-    return do.get(frames.shape, np.uint8), di.get((n, h, w), np.uint8) if di else None
+    with DeviceCall() as c:
+        check(lib().ofdis_warp_frames_projective(c.input(frames), c.input(warps), c.output(frames.shape, np.uint8),
+                                                 c.output((n, h, w), np.uint8, inside), n, w, h, noc, border, None))
+        return c.results()
 
 
 class Batch:
@@ -1147,34 +1206,27 @@ class Batch:
     def upsample(self, width_org, height_org, out_ptr=None, stream=None):
         """ofdis_batch_upsample.  With out_ptr (device pointer) only enqueues; otherwise returns the host array
         [nframes][height_org][width_org][2]."""
-        if out_ptr is not None:
-            check(lib().ofdis_batch_upsample(self.h, out_ptr, width_org, height_org, stream))
-            return None
-        out = np.zeros((self.nframes, height_org, width_org, self.p.nop), _f32)
-        d = Dev(nbytes=out.nbytes)
-        check(lib().ofdis_batch_upsample(self.h, d.ptr, width_org, height_org, stream))
-        check(lib().ofdis_sync(stream))
-        check(lib().ofdis_memcpy_d2h(out.ctypes.data, d.ptr, out.nbytes))
-        return out
+        shape = (self.nframes, height_org, width_org, self.p.nop)
+        with DeviceCall(stream, own=out_ptr is None) as c:
+            check(lib().ofdis_batch_upsample(self.h, c.output(shape, _f32, out_ptr or True), width_org, height_org, stream))
+            res = c.results()
+        return res[0] if res else None
 
     def upsample_frames(self, first, count, width_org, height_org, stream=None):
         """ofdis_batch_upsample_frames: the full-resolution flow of frames [first, first + count) as a host array."""
-        out = np.zeros((count, height_org, width_org, self.p.nop), _f32)
-        d = Dev(nbytes=out.nbytes)
-        check(lib().ofdis_batch_upsample_frames(self.h, first, count, d.ptr, width_org, height_org, stream))
-        check(lib().ofdis_sync(stream))
-        check(lib().ofdis_memcpy_d2h(out.ctypes.data, d.ptr, out.nbytes))
-        return out
+        with DeviceCall(stream) as c:
+            check(lib().ofdis_batch_upsample_frames(self.h, first, count, c.output((count, height_org, width_org, self.p.nop)),
+                                                    width_org, height_org, stream))
+            return c.results()[0]
 
     def upsample_frames_enc(self, first, count, width_org, height_org, enc, stream=None):
         """ofdis_batch_upsample_frames_enc: the full-resolution result of frames [first, first + count) written in the
         encoding `enc` (an Encoding), as a host array [count][height_org][width_org][nop] of enc.dtype."""
         shape = (count, height_org, width_org, self.p.nop)
-        nbytes = int(np.prod(shape, dtype=np.int64)) * lib().ofdis_encoding_bytes(enc.type)
-        d = Dev(nbytes=max(1, nbytes))
-        check(lib().ofdis_batch_upsample_frames_enc(self.h, first, count, d.ptr, width_org, height_org, C.byref(enc), stream))
-        check(lib().ofdis_sync(stream))
-        return d.get(shape, enc.dtype)
+        with DeviceCall(stream) as c:
+            check(lib().ofdis_batch_upsample_frames_enc(self.h, first, count, c.output(shape, _enc_dtype(enc)), width_org,
+                                                        height_org, C.byref(enc), stream))
+            return c.results()[0]
 
     def _flow_array(self, ptr, level, missing=None):
         """A level's flow array at device pointer `ptr` as a host array [nframes][h][w][nop], the pass joined first.  `missing`:
@@ -1187,20 +1239,6 @@ class Batch:
         check(lib().ofdis_sync(None))
         check(lib().ofdis_memcpy_d2h(out.ctypes.data, ptr, out.nbytes))
         return out
-
-    def _outputs(self, own, specs, call, stream):
-        """The outputs of a batch call, specs = [(want, shape, dtype), ...], through call(*device pointers).  own: the call
-        was given no device arrays: allocates every output with a true `want` (the others are passed as NULL), calls,
-        synchronises `stream` and returns the tuple of host arrays (None where not wanted).  Otherwise each `want` is the
-        caller's device pointer, or false for NULL: only enqueues and returns None."""
-        if not own:
-            call(*[want if want else None for want, _, _ in specs])
-            return None
-        devs = [Dev(nbytes=max(1, int(np.prod(shape, dtype=np.int64)) * np.dtype(t).itemsize)) if want else None
-                for want, shape, t in specs]
-        call(*[d.ptr if d else None for d in devs])
-        check(lib().ofdis_sync(stream))
-        return tuple(d.get(shape, t) if d else None for d, (_, shape, t) in zip(devs, specs))
 
     def download_all(self):
         return self._flow_array(self.flow_ptr(), self.p.sc_l)
@@ -1238,9 +1276,10 @@ class Batch:
         others are passed as NULL and returned as None)."""
         count = self.nframes - first if count is None else count
         shape = (count, height_org, width_org)
-        specs = [(want, shape, t) for want, t in zip(outputs, (_f32, _f32, np.uint8, np.uint8))]
-        return self._outputs(True, specs, lambda *ptrs: check(lib().ofdis_batch_upsample_lr(
-            self.h, first, count, *ptrs, fill, width_org, height_org, alpha, beta, stream)), stream)
+        with DeviceCall(stream) as c:
+            ptrs = [c.output(shape, t, want) for want, t in zip(outputs, (_f32, _f32, np.uint8, np.uint8))]
+            check(lib().ofdis_batch_upsample_lr(self.h, first, count, *ptrs, fill, width_org, height_org, alpha, beta, stream))
+            return c.results()
 
     def upsample_bidir(self, width_org, height_org, alpha=FB_ALPHA, beta=FB_BETA, first=0, count=None,
                        outputs=(True, True, True, True), stream=None):
@@ -1249,9 +1288,10 @@ class Batch:
         four the library writes (the others are passed as NULL and returned as None)."""
         count = self.nframes - first if count is None else count
         shapes = [(count, height_org, width_org, 2)] * 2 + [(count, height_org, width_org)] * 2
-        specs = list(zip(outputs, shapes, (_f32, _f32, np.uint8, np.uint8)))
-        return self._outputs(True, specs, lambda *ptrs: check(lib().ofdis_batch_upsample_bidir(
-            self.h, first, count, *ptrs, width_org, height_org, alpha, beta, stream)), stream)
+        with DeviceCall(stream) as c:
+            ptrs = [c.output(shape, t, want) for want, shape, t in zip(outputs, shapes, (_f32, _f32, np.uint8, np.uint8))]
+            check(lib().ofdis_batch_upsample_bidir(self.h, first, count, *ptrs, width_org, height_org, alpha, beta, stream))
+            return c.results()
 
     def interpolate(self, img_a_ptr, img_b_ptr, width_org, height_org, times, first=0, count=None, alpha=FB_ALPHA,
                     beta=FB_BETA, out_ptr=None, stream=None):
@@ -1261,16 +1301,12 @@ class Batch:
         count = self.nframes - first if count is None else count
         t, tp = _times(times)
         shape = (count, t.size, height_org, width_org) + ((self.p.noc,) if self.p.noc > 1 else ())
-        d = None
-        if out_ptr is None:
-            d = Dev(nbytes=max(1, int(np.prod(shape, dtype=np.int64))))
-            out_ptr = d.ptr
-        check(lib().ofdis_batch_interpolate(self.h, img_a_ptr, img_b_ptr, first, count, tp, t.size, out_ptr, width_org,
-                                            height_org, alpha, beta, stream))
-        if d is None:
-            return None
-        check(lib().ofdis_sync(stream))
-        return d.get(shape, np.uint8)
+        with DeviceCall(stream, own=out_ptr is None) as c:
+            check(lib().ofdis_batch_interpolate(self.h, img_a_ptr, img_b_ptr, first, count, tp, t.size,
+                                                c.output(shape, np.uint8, out_ptr or True), width_org, height_org, alpha, beta,
+                                                stream))
+            res = c.results()
+        return res[0] if res else None
 
     def track_points(self, seeds, width_org, height_org, seed_frame=None, max_steps=0, fb_check=True, first=0, count=None,
                      alpha=FB_ALPHA, beta=FB_BETA, stream=None):
@@ -1280,12 +1316,11 @@ class Batch:
         count = self.nframes - first if count is None else count
         seeds, seed_frame = _track_inputs(seeds, seed_frame)
         n = seeds.shape[0]
-        dseeds, dsf = Dev(seeds), Dev(seed_frame) if seed_frame is not None else None
-        dtracks, dcounts = Dev(nbytes=max(8, (max(count, 0) + 1) * n * 8)), Dev(nbytes=max(4, n * 4))
-        check(lib().ofdis_batch_track_points(self.h, first, count, dseeds.ptr, dsf.ptr if dsf else None, n, max_steps,
-                                             int(fb_check), alpha, beta, dtracks.ptr, dcounts.ptr, width_org, height_org, stream))
-        check(lib().ofdis_sync(stream))
-        return dtracks.get((count + 1, n, 2), _f32), dcounts.get((n,), np.int32)
+        with DeviceCall(stream) as c:
+            check(lib().ofdis_batch_track_points(self.h, first, count, c.input(seeds), c.input(seed_frame), n, max_steps,
+                                                 int(fb_check), alpha, beta, c.output((count + 1, n, 2)), c.output((n,), np.int32),
+                                                 width_org, height_org, stream))
+            return c.results()
 
     def dense_tracks(self, frames_ptr, width_org, height_org, stride, window, min_eig, max_len=15, fb_check=True,
                      max_tracks=None, first=0, count=None, alpha=FB_ALPHA, beta=FB_BETA, stream=None):
@@ -1297,12 +1332,12 @@ class Batch:
         if max_tracks is None:
             max_tracks = max(1, min(max(count, 1) * ncx * ncy, DT_MAX_TRACKS))
         lmax = _dense_lmax(max_len, max(count, 1))
-        outs = _dense_outputs(lmax, max(1, min(max_tracks, DT_MAX_TRACKS)))
-        check(lib().ofdis_batch_dense_tracks(self.h, frames_ptr, first, count, stride, window, min_eig, max_len, int(fb_check),
-                                             alpha, beta, max_tracks, outs[0].ptr, outs[1].ptr, outs[2].ptr, outs[3].ptr,
-                                             width_org, height_org, stream))
-        check(lib().ofdis_sync(stream))
-        return _dense_results(outs, lmax, max_tracks)
+        with DeviceCall(stream) as c:
+            check(lib().ofdis_batch_dense_tracks(self.h, frames_ptr, first, count, stride, window, min_eig, max_len, int(fb_check),
+                                                 alpha, beta, max_tracks,
+                                                 *_dense_declare(c, lmax, max(1, min(max_tracks, DT_MAX_TRACKS))), width_org,
+                                                 height_org, stream))
+            return _dense_cut(c.results(), lmax, max_tracks)
 
     def temporal_filter(self, frames_ptr, width_org, height_org, wn=1.0, tau=np.inf, first=0, count=None, alpha=FB_ALPHA,
                         beta=FB_BETA, out_ptr=None, support=False, stream=None):
@@ -1314,10 +1349,11 @@ class Batch:
         count = self.nframes - first if count is None else count
         shape = (max(count, 0) + 1, height_org, width_org)
         oshape = shape + ((self.p.noc,) if self.p.noc > 1 else ())
-        res = self._outputs(out_ptr is None, [(out_ptr or True, oshape, np.uint8), (support, shape, np.uint8)],
-                            lambda out, sup: check(lib().ofdis_batch_temporal_filter(
-                                self.h, frames_ptr, first, count, out, sup, width_org, height_org, wn, tau, alpha, beta, stream)),
-                            stream)
+        with DeviceCall(stream, own=out_ptr is None) as c:
+            check(lib().ofdis_batch_temporal_filter(self.h, frames_ptr, first, count, c.output(oshape, np.uint8, out_ptr or True),
+                                                    c.output(shape, np.uint8, support), width_org, height_org, wn, tau, alpha, beta,
+                                                    stream))
+            res = c.results()
         return res if res is None or support else res[0]
 
     def trajectory_filter(self, frames_ptr, width_org, height_org, weights, tau=np.inf, fb_check=True, first=0, count=None,
@@ -1332,55 +1368,40 @@ class Batch:
         shape = (max(count, 0) + 1, height_org, width_org)
         oshape = shape + ((self.p.noc,) if self.p.noc > 1 else ())
         wts, wp = _weights(weights)
-        res = self._outputs(out_ptr is None, [(out_ptr or True, oshape, np.uint8), (support, shape, np.uint8)],
-                            lambda out, sup: check(lib().ofdis_batch_trajectory_filter(
-                                self.h, frames_ptr, first, count, out, sup, width_org, height_org, wp, wts.size, tau,
-                                int(fb_check), alpha, beta, stream)),
-                            stream)
+        with DeviceCall(stream, own=out_ptr is None) as c:
+            check(lib().ofdis_batch_trajectory_filter(self.h, frames_ptr, first, count, c.output(oshape, np.uint8, out_ptr or True),
+                                                      c.output(shape, np.uint8, support), width_org, height_org, wp, wts.size, tau,
+                                                      int(fb_check), alpha, beta, stream))
+            res = c.results()
         return res if res is None or support else res[0]
 
     def _camera_fit(self, nparam, width_org, height_org, model, rounds, thresh, fb_check, first, count, alpha, beta, models_ptr,
                     stats_ptr, stream):
         fam = _CAMERA[nparam]
         count = self.nframes - first if count is None else count
-        n = max(count, 1)
-        dm = ds = None
-        if models_ptr is None:
-            dm, ds = Dev(nbytes=n * nparam * 8), Dev(nbytes=n * 24)
-            models_ptr, stats_ptr = dm.ptr, ds.ptr
-        check(getattr(lib(), fam["batch_fit"])(self.h, first, count, *([model] if fam["model_arg"] else []), rounds, thresh,
-                                               int(fb_check), alpha, beta, models_ptr, stats_ptr, width_org, height_org, stream))
-        if dm is None:
-            return None
-        check(lib().ofdis_sync(stream))
-        return dm.get((count, nparam), np.float64), ds.get((count, 3), np.int64)
+        fit = getattr(lib(), fam["batch_fit"])
+        own = models_ptr is None  # (then both arrays are the call's own: stats_ptr counts only beside models_ptr)
+        with DeviceCall(stream, own) as c:
+            check(fit(self.h, first, count, *([model] if fam["model_arg"] else []), rounds, thresh, int(fb_check), alpha, beta,
+                      c.output((count, nparam), np.float64, own or models_ptr), c.output((count, 3), np.int64, own or stats_ptr),
+                      width_org, height_org, stream))
+            return c.results()
 
     def _camera_compensate(self, nparam, models, width_org, height_org, thresh, fb_check, first, count, alpha, beta, residual,
                            label, out_ptr, stream):
         count = self.nframes - first if count is None else count
         n = max(count, 1)
-        keep = None
-        if not isinstance(models, (int, type(None))):
+        on_host = not isinstance(models, (int, type(None)))
+        if on_host:
             models = np.ascontiguousarray(models, np.float64)
             assert models.shape == (n, nparam), models.shape
-            keep = Dev(models)
-            models = keep.ptr
         rshape, lshape = (n, height_org, width_org, 2), (n, height_org, width_org)
-        dr = dl = None
-        if out_ptr is None:
-            dr = Dev(nbytes=max(8, int(np.prod(rshape, dtype=np.int64)) * 4)) if residual else None
-            dl = Dev(nbytes=max(1, int(np.prod(lshape, dtype=np.int64)))) if label else None
-            rptr, lptr = dr.ptr if dr else None, dl.ptr if dl else None
-        else:
-            rptr, lptr = out_ptr
-        check(getattr(lib(), _CAMERA[nparam]["batch_compensate"])(self.h, first, count, models, thresh, int(fb_check), alpha, beta,
-                                                                  rptr, lptr, width_org, height_org, stream))
-        if out_ptr is not None:
-            if keep is not None:
-                check(lib().ofdis_sync(stream))  # the uploaded models must outlive the launch
-            return None
-        check(lib().ofdis_sync(stream))
-        return dr.get(rshape, _f32) if dr else None, dl.get(lshape, np.uint8) if dl else None
+        want_r, want_l = (residual, label) if out_ptr is None else out_ptr
+        compensate = getattr(lib(), _CAMERA[nparam]["batch_compensate"])
+        with DeviceCall(stream, own=out_ptr is None) as c:  # (uploaded models outlive the launch: results() synchronises for them)
+            check(compensate(self.h, first, count, c.input(models) if on_host else models, thresh, int(fb_check), alpha, beta,
+                             c.output(rshape, _f32, want_r), c.output(lshape, np.uint8, want_l), width_org, height_org, stream))
+            return c.results()
 
     def global_motion(self, width_org, height_org, model=GM_AFFINE, rounds=3, thresh=1.0, fb_check=False, first=0, count=None,
                       alpha=FB_ALPHA, beta=FB_BETA, models_ptr=None, stats_ptr=None, stream=None):
@@ -1427,11 +1448,13 @@ class Batch:
         weights, radius = _stab_weights(weights)
         shape = (max(count, 0) + 1, height_org, width_org)
         oshape = shape + ((self.p.noc,) if self.p.noc > 1 else ())
-        specs = [(out_ptr or True, oshape, np.uint8), (inside, shape, np.uint8),
-                 (warps_ptr or out_ptr is None, (shape[0], 6), np.float64)]
-        return self._outputs(out_ptr is None, specs, lambda out, ins, warps: check(lib().ofdis_batch_stabilize(
-            self.h, frames_ptr, first, count, model, rounds, thresh, int(fb_check), alpha, beta, weights.ctypes.data, radius, zoom,
-            border, out, ins, warps, width_org, height_org, stream)), stream)
+        with DeviceCall(stream, own=out_ptr is None) as c:
+            check(lib().ofdis_batch_stabilize(self.h, frames_ptr, first, count, model, rounds, thresh, int(fb_check), alpha, beta,
+                                              weights.ctypes.data, radius, zoom, border,
+                                              c.output(oshape, np.uint8, out_ptr or True), c.output(shape, np.uint8, inside),
+                                              c.output((shape[0], 6), np.float64, warps_ptr or out_ptr is None),
+                                              width_org, height_org, stream))
+            return c.results()
 
     def stabilize_projective(self, frames_ptr, width_org, height_org, weights, zoom=1.0, border=BORDER_CONSTANT, rounds=3,
                              thresh=1.0, fb_check=False, first=0, count=None, alpha=FB_ALPHA, beta=FB_BETA, inside=False,
@@ -1443,11 +1466,14 @@ class Batch:
         weights, radius = _stab_weights(weights)
         shape = (max(count, 0) + 1, height_org, width_org)
         oshape = shape + ((self.p.noc,) if self.p.noc > 1 else ())
-        specs = [(out_ptr or True, oshape, np.uint8), (inside, shape, np.uint8),
-                 (warps_ptr or out_ptr is None, (shape[0], 8), np.float64)]
-        return self._outputs(out_ptr is None, specs, lambda out, ins, warps: check(lib().ofdis_batch_stabilize_projective(
-            self.h, frames_ptr, first, count, rounds, thresh, int(fb_check), alpha, beta, weights.ctypes.data, radius, zoom,
-            border, out, ins, warps, width_org, height_org, stream)), stream)
+        with DeviceCall(stream, own=out_ptr is None) as c:
+            check(lib().ofdis_batch_stabilize_projective(self.h, frames_ptr, first, count, rounds, thresh, int(fb_check), alpha,
+                                                         beta, weights.ctypes.data, radius, zoom, border,
+                                                         c.output(oshape, np.uint8, out_ptr or True),
+                                                         c.output(shape, np.uint8, inside),
+                                                         c.output((shape[0], 8), np.float64, warps_ptr or out_ptr is None),
+                                                         width_org, height_org, stream))
+            return c.results()
 
     def timing(self, enable=True):
         check(lib().ofdis_batch_timing(self.h, int(enable)))

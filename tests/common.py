@@ -1,48 +1,51 @@
 """Shared helpers for the test-suite: seeded synthetic inputs (tools/gen_synth.py) and pyramids."""
 import functools
+import os
 
 import numpy as np
 
 import gen_synth
 import oracle
+from of_dis_amd.abi import bind, prototypes
 from of_dis_amd.params import oppoint
 
 _f32 = np.float32
+TESTHOOKS_HEADER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "ofdis_test_hooks.h")
 
 
+def testhook_prototypes():
+    """name -> (restype, [argtypes]) of every function tests/csrc/ofdis_test_hooks.h declares, by the parser that binds the
+    product, with the few types only the hooks use"""
+    return prototypes(open(TESTHOOKS_HEADER).read(), hook_types=True)
+
+
+@functools.lru_cache(maxsize=None)
 def testhooks():
-    """The TEST library (tests/csrc/ofdis_testhooks.hip, built by of_dis_amd.build next to the product): device kernels
-    around the header-only helpers of ofdis_dev.h.  Not part of the shipped library."""
+    """The TEST library (tests/csrc/ofdis_testhooks.hip and ofdis_launch_hooks*.hip, built by of_dis_amd.build next to the
+    product), opened once, every function with the prototype its header declares.  Not part of the shipped library.  No
+    fallback: a library without one of the declared functions is a failure."""
     import ctypes as C
     from of_dis_amd import build
     path = build.testhooks_path()
-    if not __import__("os").path.exists(path):
+    if not os.path.exists(path):
         build.build()
-    L = C.CDLL(path)
-    VP = C.c_void_p
-    L.ofdis_test_wave_sum.argtypes = [VP, VP, C.c_int, VP]
-    L.ofdis_test_div_sqrt.argtypes = [VP, VP, VP, C.c_int, VP]
-    L.ofdis_test_outlier_sq.restype = C.c_float
-    L.ofdis_test_outlier_sq.argtypes = [C.c_float]
-    return L
+    return bind(C.CDLL(path), testhook_prototypes())
 
 
 def wave_sum_test(gpu, x):
     x = np.ascontiguousarray(x, _f32)
-    d, o = gpu.Dev(x), gpu.Dev(nbytes=x.nbytes)
-    assert testhooks().ofdis_test_wave_sum(d.ptr, o.ptr, x.size, None) == 0
-    gpu.check(gpu.lib().ofdis_sync(None))
-    return o.get(x.shape)
+    with gpu.DeviceCall() as c:
+        assert testhooks().ofdis_test_wave_sum(c.input(x), c.output(x.shape), x.size, None) == 0
+        return c.results()[0]
 
 
 def div_sqrt_test(gpu, a, b):
     """Rows: div_rn(a,b), a/b, sqrt_rn(|a|), sqrtf(|a|), the fused TV kernel's quotient a/b, its quotient b / sqrt(|a|),
     computed on the device (ofdis_dev.h)."""
     a, b = np.ascontiguousarray(a, _f32), np.ascontiguousarray(b, _f32)
-    da, db, o = gpu.Dev(a), gpu.Dev(b), gpu.Dev(nbytes=6 * a.nbytes)
-    assert testhooks().ofdis_test_div_sqrt(da.ptr, db.ptr, o.ptr, a.size, None) == 0
-    gpu.check(gpu.lib().ofdis_sync(None))
-    return o.get((6, a.size))
+    with gpu.DeviceCall() as c:
+        assert testhooks().ofdis_test_div_sqrt(c.input(a), c.input(b), c.output((6, a.size)), a.size, None) == 0
+        return c.results()[0]
 
 
 @functools.lru_cache(maxsize=16)

@@ -1,16 +1,18 @@
 // ofdis_launch_hooks.hip -- TEST LIBRARY (libofdis_testhooks.so), not part of the product: thin C wrappers around the
 // ofdis::launch_* functions of of_dis_amd/csrc/ofdis_kernels.h, and the two launch limits as variables a test can lower.
 //
-// The test library links the PRODUCT'S OWN units (ofdis_interp, ofdis_tfilter, ofdis_trajfilter, ofdis_gmotion, ofdis_stabilize,
-// ofdis_upsample, ofdis_stereo_lr, ofdis_pyr, ofdis_bof, ofdis_kmeans, ofdis_track, ofdis_dense_tracks), compiled with the product's flags plus
-// -DOFDIS_TEST_LAUNCH_LIMITS.  Under that
+// The test library links the PRODUCT'S OWN units (TESTHOOK_UNITS of of_dis_amd/build.py has the list), compiled with the
+// product's flags plus -DOFDIS_TEST_LAUNCH_LIMITS.  Under that
 // define quad_max_blocks() and grid_max_blocks() (ofdis_kernels.h) read the two variables below instead of returning the
 // product's constants.  Both are read in host code only (quad_grid, grid_for), so the kernels here are the product's kernels;
 // what changes is how many launches (quad_grid's chunks) or grid-stride trips (grid_for) cover the work.  With the limits at
 // their product values the launches are the product's.
+//
+// Every hook is declared in ofdis_test_hooks.h, which also has HOOK, UPG_PARAMS and UPG (UpGeom travels as seven ints).
 #include <hip/hip_runtime.h>
 
 #include "../../of_dis_amd/csrc/ofdis_upsample.h"
+#include "ofdis_test_hooks.h"
 
 #ifndef OFDIS_TEST_LAUNCH_LIMITS
 #error "the test library is compiled with -DOFDIS_TEST_LAUNCH_LIMITS"
@@ -22,11 +24,6 @@ long long test_grid_max_blocks = GRID_MAX_BLOCKS;
 }  // namespace ofdis
 
 using namespace ofdis;
-
-#define HOOK extern "C" __attribute__((visibility("default")))
-// UpGeom travels as seven ints, in the order of its members
-#define UPG_PARAMS int sw, int sh, int sc_l, int left, int top, int wo, int ho
-#define UPG (UpGeom{sw, sh, sc_l, left, top, wo, ho})
 
 static InterpTimes interp_times(const float* times, int ntimes) {
   InterpTimes ts{};

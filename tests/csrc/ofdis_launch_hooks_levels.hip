@@ -5,17 +5,13 @@
 #include <hip/hip_runtime.h>
 
 #include "../../of_dis_amd/csrc/ofdis_kernels.h"
+#include "ofdis_test_hooks.h"
 
 #ifndef OFDIS_TEST_LAUNCH_LIMITS
 #error "the test library is compiled with -DOFDIS_TEST_LAUNCH_LIMITS"
 #endif
 
 using namespace ofdis;
-
-#define HOOK extern "C" __attribute__((visibility("default")))
-// UpGeom travels as seven ints, in the order of its members
-#define UPG_PARAMS int sw, int sh, int sc_l, int left, int top, int wo, int ho
-#define UPG (UpGeom{sw, sh, sc_l, left, top, wo, ho})
 
 // (OFDIS_ENC_F32 with two channels is launch_upsample_crop)
 HOOK int ofdis_test_launch_upsample_crop_enc(const float* flow, void* out, int nframes, UPG_PARAMS, int channels, int type,

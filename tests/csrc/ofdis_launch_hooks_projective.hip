@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../of_dis_amd/csrc/ofdis_kernels.h"
+#include "ofdis_test_hooks.h"
 
 #ifndef OFDIS_TEST_LAUNCH_LIMITS
 #error "the test library is compiled with -DOFDIS_TEST_LAUNCH_LIMITS"
@@ -12,7 +13,7 @@
 
 using namespace ofdis;
 
-extern "C" __attribute__((visibility("default"))) int ofdis_test_launch_warp_frames_projective(
+HOOK int ofdis_test_launch_warp_frames_projective(
     const uint8_t* frames, const double* warps, uint8_t* out, uint8_t* inside, int nframes, int w, int h, int noc, int replicate,
     void* stream) {
   return (int)launch_warp_frames_projective(frames, warps, out, inside, nframes, w, h, noc, replicate != 0, (hipStream_t)stream);

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../of_dis_amd/csrc/ofdis_kernels.h"
+#include "ofdis_test_hooks.h"
 
 #ifndef OFDIS_TEST_LAUNCH_LIMITS
 #error "the test library is compiled with -DOFDIS_TEST_LAUNCH_LIMITS"
@@ -12,11 +13,11 @@
 
 using namespace ofdis;
 
-extern "C" __attribute__((visibility("default"))) size_t ofdis_test_segments_work_bytes(int nmaps, int w, int h) {
+HOOK size_t ofdis_test_segments_work_bytes(int nmaps, int w, int h) {
   return segments_work_bytes(nmaps, w, h);
 }
 
-extern "C" __attribute__((visibility("default"))) int ofdis_test_launch_label_segments(
+HOOK int ofdis_test_launch_label_segments(
     const uint8_t* label, const float* flow, int nmaps, int w, int h, unsigned codes, int conn, int min_area, int max_segments,
     int* segments, long long* records, long long* info, void* work, void* stream) {
   return (int)launch_label_segments(label, flow, nmaps, w, h, codes, conn, min_area, max_segments, segments, records, info, work,

@@ -5,6 +5,7 @@
 #include <math.h>
 
 #include "../../of_dis_amd/csrc/ofdis_dev.h"
+#include "ofdis_test_hooks.h"
 
 using namespace ofdis;
 using namespace ofdis::exact;  // (the helpers under test are the exact contract's)
@@ -28,15 +29,13 @@ __global__ void div_sqrt_test_kernel(const float* a, const float* b, float* out,
   out[5 * n + i] = div_by_finite(y, 0.0f - sq, rcp_refined(sq));
 }
 
-extern "C" {
-int ofdis_test_wave_sum(const float* in, float* out, int n, void* stream) {
+HOOK int ofdis_test_wave_sum(const float* in, float* out, int n, void* stream) {
   hipLaunchKernelGGL(wave_sum_test_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, in, out, n);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
-int ofdis_test_div_sqrt(const float* a, const float* b, float* out, int n, void* stream) {
+HOOK int ofdis_test_div_sqrt(const float* a, const float* b, float* out, int n, void* stream) {
   hipLaunchKernelGGL(div_sqrt_test_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, a, b, out, n);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 // host only, needs no GPU: the squared outlier threshold of the patch kernels
-float ofdis_test_outlier_sq(float t) { return outlier_sq_threshold(t); }
-}
+HOOK float ofdis_test_outlier_sq(float t) { return outlier_sq_threshold(t); }

@@ -10,71 +10,17 @@ tests/test_launch_geometry.py and tests/test_patch_kernel_choice.py.
 libofdis_hip.so is a separate object with the limits compiled in as constants: nothing here changes what it does."""
 import contextlib
 import ctypes as C
-import functools
 
 import numpy as np
 
 QUAD_MAX_BLOCKS, GRID_MAX_BLOCKS = 1 << 22, 1 << 20   # the product's values
-_I, _F, _VP, _LL, _SZ = C.c_int, C.c_float, C.c_void_p, C.c_longlong, C.c_size_t
-_UPG = [_I] * 7   # UpGeom: sw, sh, sc_l, left, top, wo, ho
-
-_SIGNATURES = {
-    "interp_frames": [_VP] * 7 + [_I] * 4 + [_VP, _I, _VP],
-    "interp_bidir": [_VP] * 5 + [_I] + _UPG + [_I, _VP, _I, _F, _F, _VP],
-    "tfilter_frames": [_VP] * 7 + [_I] * 4 + [_F, _F, _VP],
-    "tfilter_level": [_VP] * 5 + [_I] + _UPG + [_I, _F, _F, _F, _F, _VP],
-    "trajfilter_frames": [_VP] * 5 + [_I] * 4 + [_VP, _I, _F, _I, _F, _F, _VP],
-    "trajfilter_level": [_VP] * 5 + [_I] + _UPG + [_I, _VP, _I, _F, _I, _F, _F, _VP],
-    "gmotion_frames": [_VP, _VP] + [_I] * 5 + [_F, _VP, _VP, _VP, _VP],
-    "gmotion_compensate_frames": [_VP] * 3 + [_I] * 3 + [_F, _VP, _VP, _VP],
-    "gmotion_level": [_VP, _VP, _I] + _UPG + [_I, _I, _F, _F, _F, _VP, _VP, _VP, _VP],
-    "gmotion_compensate_level": [_VP] * 3 + [_I] + _UPG + [_F, _F, _F, _VP, _VP, _VP],
-    "warp_frames": [_VP] * 4 + [_I] * 5 + [_VP],
-    "pyr_base": [_VP, _VP] + [_I] * 7 + [_SZ, _SZ, _VP],
-    "pyr_down": [_VP, _VP] + [_I] * 4 + [_VP],
-    "pyr_planes": [_VP] * 5 + [_I] * 5 + [_VP],
-    "encode": [_VP, _VP, _SZ, _I, _F, _F, _VP],
-    "fb_check": [_VP] * 3 + [_I] * 3 + [_F, _F, _VP],
-    "mirror_u8": [_VP, _VP] + [_I] * 4 + [_VP],
-    "lr_check": [_VP] * 3 + [_I] * 3 + [_F, _F, _VP],
-    "disparity_fill": [_VP] * 3 + [_I] * 4 + [_VP],
-    # tests/csrc/ofdis_launch_hooks_levels.hip
-    "upsample_crop_enc": [_VP, _VP, _I] + _UPG + [_I, _I, _F, _F, _VP],
-    "upsample_bidir": [_VP] * 6 + [_I] + _UPG + [_F, _F, _VP],
-    "projective_level": [_VP, _VP, _I] + _UPG + [_I, _F, _F, _F, _VP, _VP, _VP, _VP],
-    "projective_compensate_level": [_VP] * 3 + [_I] + _UPG + [_F, _F, _F, _VP, _VP, _VP],
-    "track_level": [_VP, _VP, _I] + _UPG + [_VP, _VP, _I, _I, _F, _F, _VP, _VP, _VP],
-    "dense_tracks_level": [_VP] * 3 + [_I] + _UPG + [_I] * 5 + [_F, _F, _I] + [_VP] * 6,
-    "upsample_lr": [_VP] * 6 + [_I] + _UPG + [_I, _F, _F, _VP],
-    "lr_materialise": [_VP] * 4 + [_I] + _UPG + [_VP],
-}
+_I = C.c_int
 
 
-@functools.lru_cache(maxsize=None)
 def hooks():
-    """libofdis_testhooks.so with the launch hooks' signatures.  No fallback: a library without them is a failure."""
+    """libofdis_testhooks.so, every hook with the prototype tests/csrc/ofdis_test_hooks.h declares (common.testhooks)"""
     from common import testhooks
-    L = testhooks()
-    for name, argtypes in _SIGNATURES.items():
-        fn = getattr(L, "ofdis_test_launch_" + name)
-        fn.argtypes, fn.restype = argtypes, _I
-    L.ofdis_test_set_launch_limits.argtypes, L.ofdis_test_set_launch_limits.restype = [_LL, _LL], None
-    L.ofdis_test_quad_grid.argtypes, L.ofdis_test_quad_grid.restype = [_I, _I, _I, C.POINTER(_I), C.POINTER(_I)], None
-    L.ofdis_test_quad_blocks.argtypes, L.ofdis_test_quad_blocks.restype = [_I, _I], C.c_uint
-    L.ofdis_test_quad_chunks.argtypes, L.ofdis_test_quad_chunks.restype = [_I, _I, _I, _I, _VP], _I
-    L.ofdis_test_grid_for.argtypes, L.ofdis_test_grid_for.restype = [_LL], C.c_uint
-    L.ofdis_test_xcd_frame_map.argtypes, L.ofdis_test_xcd_frame_map.restype = [_I, _I, _I, _I, _VP, _VP], None
-    L.ofdis_test_xcd_grid.argtypes, L.ofdis_test_xcd_grid.restype = [_I, _LL], _LL
-    L.ofdis_test_slot_rows.argtypes, L.ofdis_test_slot_rows.restype = [_I], _I
-    L.ofdis_test_patch_kernel_choice.argtypes, L.ofdis_test_patch_kernel_choice.restype = [_I] * 10 + [C.POINTER(_I)], None
-    L.ofdis_test_gmotion_work_bytes.argtypes, L.ofdis_test_gmotion_work_bytes.restype = [_I, _I, _I], _SZ
-    L.ofdis_test_bof_shape.argtypes, L.ofdis_test_bof_shape.restype = [_I] + [C.POINTER(_I)] * 3, None
-    L.ofdis_test_km_geom.argtypes, L.ofdis_test_km_geom.restype = [_I] + [C.POINTER(_I)] * 3, None
-    L.ofdis_test_km_finish_split.argtypes, L.ofdis_test_km_finish_split.restype = [_I], _I
-    L.ofdis_test_pyr_base_variant.argtypes, L.ofdis_test_pyr_base_variant.restype = [_VP] + [_I] * 4 + [_SZ, _SZ], _I
-    L.ofdis_test_pyr_planes_variant.argtypes, L.ofdis_test_pyr_planes_variant.restype = [_I] * 5, _I
-    L.ofdis_test_upsample_lr_fuses.argtypes, L.ofdis_test_upsample_lr_fuses.restype = [_I], _I
-    return L
+    return testhooks()
 
 
 def launch(name, *args):

@@ -5,7 +5,6 @@ The two kernels are compared bit for bit -- the warps as raw 64-bit patterns, `o
 of_dis_amd/stabilize.py, the header's definition in numpy; the context call bit for bit with its composition
 (Batch.projective_motion, capi.camera_path_projective, capi.warp_frames_projective).  Conditions on the generated inputs are
 checked on the restatement, never on the kernel under test (those of the models: tests/test_stabilize_projective_ref.py)."""
-import ctypes as C
 import math
 
 import numpy as np
@@ -165,7 +164,6 @@ def test_warp_frames_in_chunks(gpu, noc, w, h, limit):
     """the launcher's second chunk: the test library's launcher with QUAD_MAX_BLOCKS lowered to 8 (chunks of 8 and 3 frames) and
     to 3 (four chunks), the same bytes"""
     hook = launch_hooks.hooks().ofdis_test_launch_warp_frames_projective
-    hook.argtypes, hook.restype = [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p], C.c_int
     frames, warps = sp.warp_case(w, h, noc, "a")
     want = warp_frames_projective_ref(frames, warps, BORDER_CONSTANT)
     df, dw = gpu.Dev(frames), gpu.Dev(warps)
