@@ -1100,7 +1100,8 @@ int ofdis_track_select_projective(const float* tracks, const int* start, const i
  * Segments: connected components of a label map, small ones removed, one record per segment.  The step from the byte per pixel
  * that ofdis_motion_compensate and ofdis_projective_compensate write to objects: the things that move against the camera are the
  * components of the OFDIS_GM_OUTLIER pixels; the occlusion regions of a pair are those of an OFDIS_FB_* mask.
- * Not provided: morphological opening or closing before labelling; hole filling; association of segments across frames; a form
+ * Not provided: morphological opening or closing before labelling; hole filling; association of segments across frames by this
+ * call (the section "Object tracks" below does it: ofdis_segment_tracks); a form
  * that reads a context's level flows directly (composing from materialised arrays wins, as the measurements of the fused
  * global-motion, trajectory-filter and projective routes in README.md show: the labels come from either compensate call); the
  * C++ sequence driver.
@@ -1148,6 +1149,87 @@ size_t ofdis_segments_work_bytes(int nmaps, int width, int height);
 int ofdis_label_segments(const uint8_t* label, const float* flow /* or NULL */, int nmaps, int width, int height, unsigned codes,
                          int conn, int min_area, int max_segments, int* segments /* or NULL */, long long* records /* or NULL */,
                          long long* info, void* work, size_t work_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Object tracks: the segments of consecutive maps of a clip linked across frames.  ofdis_label_segments numbers the moving
+ * objects of every frame pair on its own; here segment a of map k and segment b of map k + 1 become the same object where the
+ * forward flow carries most of one onto the other, the links are chained into numbered tracks with one record each, and the
+ * maps are relabelled by track.  Four steps, each a call of its own, and ofdis_segment_tracks, which enqueues all four.
+ * Not provided: split and merge events (a split or a merge ends tracks and starts new ones; the caller has `overlap` to find
+ * them); tracks across a gap (an object that is not recorded in one map comes back as a new track); a sparse overlap for more
+ * than 1024 segments per map; a form that reads a context's level flows directly (any full-resolution forward flow will do:
+ * that of ofdis_batch_upsample_bidir, for example); the C++ sequence driver.
+ *
+ * Notation: N = nmaps, the maps of a clip in frame order, map k in the coordinates of frame k; S = max_segments, the value
+ * ofdis_label_segments was called with.  segments [N][H][W] int32, records [N][S][12] int64 and info [N][4] int64 are as that
+ * call wrote them; flow is [N][H][W][2] f32, flow k taking frame k to frame k + 1 (the flow of the last map is never read).
+ * n_k = min(max(info[k][2], 0), S), read on the device, never by the host.  A value s in map k is RECORDED iff 1 <= s <= n_k;
+ * every other value (0, negative, above n_k) is background here, so arbitrary int32 maps never index out of range.
+ * Integers throughout; the one floating-point step is (int)rintf(u), round to nearest even.
+ *
+ * 1. Overlap.  For k = 0 .. N-2 and every pixel (x, y) of map k whose value a is recorded in map k: (u, v) = flow[k][y][x] is
+ * usable iff fabsf(u) <= 4096 && fabsf(v) <= 4096 (a NaN fails this); xt = x + (int)rintf(u), yt = y + (int)rintf(v); if
+ * (xt, yt) is inside the frame and b = segments[k+1][yt][xt] is recorded in map k + 1, overlap[k][a-1][b-1] += 1.
+ * overlap is [N-1][S][S] int32.  Only the entries (i, j) with i < n_k and j < n_{k+1} are defined, zeros included: the call
+ * clears them itself (a launch of its own before the accumulating one); the rest is neither read nor written.
+ * Two routes give the same bits: wavefront-aggregated integer atomics on global memory for every S, and for S <= 128 a
+ * histogram in LDS per workgroup and band of rows (S * S * 4 <= 64 KiB), whose non-zero entries are then added to global memory.
+ *
+ * 2. Link: mutual best match.  Within pair k, c(a, b) = overlap[k][a-1][b-1]; fbest(a) is the recorded b with the largest
+ * c(a, b), among equals the smallest b, none if every c(a, b) is 0; bbest(b) is the same over a.  link[k][a-1] = b iff
+ * c(a, b) > 0 and fbest(a) = b and bbest(b) = a and c * 100 >= min_share * min(area_k(a), area_{k+1}(b)), compared in int64,
+ * and 0 otherwise; area is records[..][0] clamped to 0 .. 2^26; min_share is 0 .. 100 (per cent of the smaller segment).
+ * link is [N-1][S] int32; the entries a-1 < n_k are defined, the rest is neither read nor written.  Links are injective by
+ * construction: no two a share a b.  A split or a merge therefore ends tracks and starts new ones.
+ *
+ * 3. Chain.  (k, s) is BORN iff k = 0 or no a has link[k-1][a-1] = s (only a <= n_{k-1} and values 1 .. n_k count).  The born
+ * (k, s) are ordered by k, then by s, and numbered 1 .. ntracks.  ids[k][s-1] is its own number if born, otherwise the id of
+ * its predecessor a (for a link array that is not injective -- not one of step 2 -- the smallest such a).  ids is [N][S] int32,
+ * defined for s <= n_k.  tracks is [max_tracks][12] int64; record t-1 is written for t <= min(ntracks, max_tracks):
+ *   { first_map, first_segment, length, last_segment, sum area, sum sx, sum sy, sum nflow, sum squ, sum sqv, min area, max area }
+ * the sums over the member segments' record fields 0, 6, 7, 8, 9 and 10, in two's-complement arithmetic (garbage records wrap
+ * instead of being undefined); min and max of field 0 as it stands.  The slots beyond min(ntracks, max_tracks) are neither
+ * read nor written.  tinfo [4] int64: { ntracks, min(ntracks, max_tracks), the number of links followed (segments that are
+ * not born), the longest length }.  N = 1 is valid: every recorded segment is a track of length 1.
+ *
+ * 4. Relabel.  track_map[k][y][x] = ids[k][s-1] if s = segments[k][y][x] is recorded, else 0; every entry is written once.
+ *
+ * Limits (in prose: the section adds no macro; of_dis_amd/capi.py and of_dis_amd/segments.py carry them as SEGTRACK_MAX_SEGMENTS
+ * = 1024, SEGTRACK_MAX_MAPS = 65536, SEGTRACK_MAX_TRACKS = 2^24, SEGTRACK_FIELDS = 12, SEGTRACK_INFO_FIELDS = 4,
+ * SEGTRACK_LDS_MAX_SEGMENTS = 128): nmaps is 1 .. 65536, max_segments 1 .. 1024, max_tracks 1 .. 16777216, both sides at most
+ * OFDIS_GM_MAX_SIDE.
+ * Bounds: a count is at most W*H < 2^26 and fits int32; c * 100 < 2^33 and min_share * area <= 100 * 2^26 < 2^33.  With N <=
+ * 65536 = 2^16 and S <= 1024 = 2^10, ntracks <= N*S <= 2^26 fits int32, as does a length (<= N).  Over a track of at most 2^16
+ * segments of label_segments' records: sum area <= 2^26 * 2^16 = 2^42, sum sx < 2^39 * 2^16 = 2^55 and sum sy likewise,
+ * |sum squ| <= 2^46 * 2^16 = 2^62: int64 never overflows on records that call wrote.
+ * Order independence: integer adds and minima are associative and commutative, so every output is a pure function of the
+ * inputs whatever the order in which the atomics arrive: two calls give the same bits.  of_dis_amd/segments.py states the
+ * definitions in numpy (segment_overlap_ref, segment_link_ref, segment_chain_ref, segment_relabel_ref, segment_tracks_ref).
+ * Every call below enqueues on `stream` without a host synchronisation; no workgroup waits for another; there is no
+ * floating-point atomic.  OFDIS_ERR_INVALID before any device work: a NULL required pointer; nmaps outside 1 .. 65536;
+ * max_segments outside 1 .. 1024; min_share outside 0 .. 100; max_tracks outside 1 .. 16777216; sizes as ofdis_label_segments
+ * rejects them; a work buffer that is too small or not 8-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+/* bytes of the work buffer ofdis_segment_tracks needs: 8 * ceil((N-1) * S * (S+1) * 4 / 8), at least 8 -- overlap
+ * [N-1][S][S] and link [N-1][S], int32 each; 0 for arguments that function rejects */
+size_t ofdis_segment_tracks_work_bytes(int nmaps, int max_segments);
+/* step 1: two launches (clear, accumulate); with nmaps = 1 nothing is launched */
+int ofdis_segment_overlap(const int* segments, const float* flow, const long long* info, int nmaps, int width, int height,
+                          int max_segments, int* overlap, void* stream);
+/* step 2: one workgroup per pair computes the row and column arg-maxima; with nmaps = 1 nothing is launched */
+int ofdis_segment_link(const int* overlap, const long long* records, const long long* info, int nmaps, int max_segments,
+                       int min_share, int* link, void* stream);
+/* step 3: one workgroup walks the maps in order, a few barriers per map */
+int ofdis_segment_chain(const int* link, const long long* records, const long long* info, int nmaps, int max_segments,
+                        int max_tracks, int* ids, long long* tracks, long long* tinfo, void* stream);
+/* step 4 */
+int ofdis_segment_relabel(const int* segments, const int* ids, const long long* info, int nmaps, int width, int height,
+                          int max_segments, int* track_map, void* stream);
+/* steps 1 to 4 (4 only with a track_map) on `stream`, overlap and link in `work` (8-byte aligned, at least
+ * ofdis_segment_tracks_work_bytes): the same bits as the four calls */
+int ofdis_segment_tracks(const int* segments, const float* flow, const long long* records, const long long* info, int nmaps,
+                         int width, int height, int max_segments, int min_share, int max_tracks, int* ids, long long* tracks,
+                         long long* tinfo, int* track_map /* or NULL */, void* work, size_t work_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Video stabilisation: the per-pair camera models of a clip turned into one correcting warp per frame -- the classical

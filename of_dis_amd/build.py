@@ -21,13 +21,13 @@ ROOT = os.path.dirname(HERE)
 # Kernel files: compiled once per ARITHMETIC CONTRACT (csrc/ofdis_dev.h) from the same source, into ofdis::exact and
 # ofdis::fused; the pyramid (exact by construction for 8-bit input), the full-resolution finish and frame interpolation (exact
 # only: a fixed fp32 operation order, include/ofdis.h), the stereo left-right step, the point and dense trajectories, their selection and their
-# descriptors, their bag-of-features encoding and the k-means training of its codebook (integers throughout), the temporal filters, the global motion models, the segments of label maps and the stabiliser (exact only, likewise) and the C ABI are compiled once:
+# descriptors, their bag-of-features encoding and the k-means training of its codebook (integers throughout), the temporal filters, the global motion models, the segments of label maps, their tracks and the stabiliser (exact only, likewise) and the C ABI are compiled once:
 # the context (ofdis_context.hip), its launch schedule (ofdis_schedule.hip), what is made from its flows (ofdis_products.hip) and
 # the rest (ofdis_capi.hip).
 KERNEL_SOURCES = ["ofdis_dis.hip", "ofdis_tv.hip", "ofdis_prep.hip", "ofdis_sor.hip", "ofdis_fused.hip", "ofdis_fused_xcu.hip",
                   "ofdis_fused_tall.hip", "ofdis_de.hip"]
 COMMON_SOURCES = ["ofdis_pyr.hip", "ofdis_upsample.hip", "ofdis_interp.hip", "ofdis_stereo_lr.hip", "ofdis_track.hip", "ofdis_dense_tracks.hip", "ofdis_track_select.hip", "ofdis_descriptors.hip", "ofdis_bof.hip", "ofdis_kmeans.hip", "ofdis_tfilter.hip", "ofdis_trajfilter.hip", "ofdis_gmotion.hip",
-                  "ofdis_segments.hip", "ofdis_stabilize.hip", "ofdis_context.hip", "ofdis_schedule.hip", "ofdis_products.hip", "ofdis_capi.hip"]
+                  "ofdis_segments.hip", "ofdis_segment_tracks.hip", "ofdis_stabilize.hip", "ofdis_context.hip", "ofdis_schedule.hip", "ofdis_products.hip", "ofdis_capi.hip"]
 HIP_SOURCES = KERNEL_SOURCES + COMMON_SOURCES
 # -fvisibility=hidden: the shared library exports the C ABI of include/ofdis.h (marked in ofdis_context.h) and nothing else.
 BASEFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",

@@ -53,6 +53,13 @@ BORDER_CONSTANT, BORDER_REPLICATE = 0, 1  # OFDIS_BORDER_*
 # include/ofdis.h, "Segments": the limits that section states in prose (no macro there); of_dis_amd/segments.py has the same
 SEG_MAX_SEGMENTS, SEG_RECORD_FIELDS, SEG_INFO_FIELDS = 1 << 24, 12, 4
 SEG_MOVING = 1 << GM_OUTLIER  # `codes` of the moving objects in a compensate call's labels
+# include/ofdis.h, "Object tracks": likewise in prose there; of_dis_amd/segments.py has the same
+SEGTRACK_MAX_SEGMENTS, SEGTRACK_MAX_MAPS, SEGTRACK_MAX_TRACKS = 1024, 65536, 1 << 24
+SEGTRACK_FIELDS, SEGTRACK_INFO_FIELDS, SEGTRACK_LDS_MAX_SEGMENTS = 12, 4, 128
+# csrc/ofdis_segment_tracks.hip: kStGridBlocks, the most workgroups (of four 64-pixel chunks each) of its per-pixel launches: 8
+# for each of 256 compute units; kStLdsGridBlocks and kStBandRows, the same for the LDS route of the overlap (max_segments <=
+# SEGTRACK_LDS_MAX_SEGMENTS), where a workgroup takes a band of rows of one pair at a time
+SEGTRACK_GRID_BLOCKS, SEGTRACK_LDS_GRID_BLOCKS, SEGTRACK_BAND_ROWS = 256 * 8, 256 * 2, 32
 OFDIS_VERSION = 3  # include/ofdis.h: the struct layouts below (OfdisTuning: 21 ints) belong to this ABI version
 
 
@@ -1026,6 +1033,108 @@ def label_segments(label, flow=None, codes=SEG_MOVING, conn=8, min_area=0, max_s
                                          c.output((nmaps, h, w), np.int32, segments),
                                          c.output(rshape, np.int64, records, fill=records_fill),
                                          c.output((nmaps, SEG_INFO_FIELDS), np.int64), c.work(wb), wb, None))
+        return c.results()
+
+
+def segment_tracks_work_bytes(nmaps, max_segments):
+    """ofdis_segment_tracks_work_bytes: the work buffer of segment_tracks; 0 for rejected arguments."""
+    return lib().ofdis_segment_tracks_work_bytes(nmaps, max_segments)
+
+
+def _st_maps(segments, info):
+    """segments int32 [nmaps, h, w] and info int64 [nmaps, 4] of label_segments: (segments, info, nmaps, h, w)"""
+    segments, info = np.ascontiguousarray(segments, np.int32), np.ascontiguousarray(info, np.int64)
+    assert segments.ndim == 3 and info.shape == (segments.shape[0], SEG_INFO_FIELDS), (segments.shape, info.shape)
+    return (segments, info) + segments.shape
+
+
+def _st_array(a, dtype, shape):
+    """an input of `shape`; one of no elements (a clip of one map has no pair) is uploaded as 8 bytes that are never read"""
+    a = np.ascontiguousarray(a, dtype).reshape(shape)
+    return a if a.size else np.zeros(8 // np.dtype(dtype).itemsize, dtype)
+
+
+def _st_output(c, shape, dtype, fill):
+    """an output that starts from `fill` (None: zeros): the slots a definition leaves alone keep it"""
+    if not int(np.prod(shape)):
+        return c.output(shape, dtype)
+    return c.output(shape, dtype, fill=np.zeros(shape, dtype) if fill is None else fill)
+
+
+def segment_overlap(segments, flow, info, max_segments, overlap_fill=None):
+    """ofdis_segment_overlap on the device: segments int32 [nmaps, h, w] and info int64 [nmaps, 4] as label_segments returns
+    them, flow float32 [nmaps, h, w, 2] taking frame k to k + 1 -> overlap int32 [nmaps - 1, S, S].  Only [k, :n_k, :n_{k+1}]
+    is written: the rest keeps overlap_fill (int32, that shape), or zeros.  segments.py: segment_overlap_ref."""
+    segments, info, nmaps, h, w = _st_maps(segments, info)
+    flow = _f(flow)
+    assert flow.shape == (nmaps, h, w, 2), flow.shape
+    S = max_segments
+    with DeviceCall() as c:
+        check(lib().ofdis_segment_overlap(c.input(segments), c.input(flow), c.input(info), nmaps, w, h, S,
+                                          _st_output(c, (nmaps - 1, S, S), np.int32, overlap_fill), None))
+        return c.results()[0]
+
+
+def segment_link(overlap, records, info, max_segments, min_share, link_fill=None):
+    """ofdis_segment_link on the device: overlap int32 [nmaps - 1, S, S], records int64 [nmaps, S, 12], info int64 [nmaps, 4]
+    -> link int32 [nmaps - 1, S]; only [k, :n_k] is written: the rest keeps link_fill, or zeros.  segments.py: segment_link_ref."""
+    info = np.ascontiguousarray(info, np.int64)
+    nmaps, S = len(info), max_segments
+    with DeviceCall() as c:
+        check(lib().ofdis_segment_link(c.input(_st_array(overlap, np.int32, (nmaps - 1, S, S))),
+                                       c.input(_st_array(records, np.int64, (nmaps, S, SEG_RECORD_FIELDS))), c.input(info), nmaps, S,
+                                       min_share, _st_output(c, (nmaps - 1, S), np.int32, link_fill), None))
+        return c.results()[0]
+
+
+def segment_chain(link, records, info, max_segments, max_tracks, ids_fill=None, tracks_fill=None):
+    """ofdis_segment_chain on the device: link int32 [nmaps - 1, S], records, info -> (ids int32 [nmaps, S], tracks int64
+    [max_tracks, 12], tinfo int64 [4] = ntracks, tracks written, links followed, longest length).  ids [k, :n_k] and the first
+    tinfo[1] track records are written: the rest keeps ids_fill / tracks_fill, or zeros.  segments.py: segment_chain_ref."""
+    info = np.ascontiguousarray(info, np.int64)
+    nmaps, S = len(info), max_segments
+    with DeviceCall() as c:
+        check(lib().ofdis_segment_chain(c.input(_st_array(link, np.int32, (nmaps - 1, S))),
+                                        c.input(_st_array(records, np.int64, (nmaps, S, SEG_RECORD_FIELDS))), c.input(info), nmaps, S,
+                                        max_tracks, _st_output(c, (nmaps, S), np.int32, ids_fill),
+                                        _st_output(c, (max_tracks, SEGTRACK_FIELDS), np.int64, tracks_fill),
+                                        c.output((SEGTRACK_INFO_FIELDS,), np.int64), None))
+        return c.results()
+
+
+def segment_relabel(segments, ids, info, max_segments, track_map_fill=None):
+    """ofdis_segment_relabel on the device: segments int32 [nmaps, h, w], ids int32 [nmaps, S], info -> track_map int32
+    [nmaps, h, w].  Every entry is written: nothing of track_map_fill (the array it starts from) stays.  segments.py:
+    segment_relabel_ref."""
+    segments, info, nmaps, h, w = _st_maps(segments, info)
+    S = max_segments
+    with DeviceCall() as c:
+        check(lib().ofdis_segment_relabel(c.input(segments), c.input(_st_array(ids, np.int32, (nmaps, S))), c.input(info), nmaps, w, h,
+                                          S, _st_output(c, (nmaps, h, w), np.int32, track_map_fill), None))
+        return c.results()[0]
+
+
+def segment_tracks(segments, flow, records, info, max_segments, min_share=50, max_tracks=None, track_map=True, ids_fill=None,
+                   tracks_fill=None, track_map_fill=None):
+    """ofdis_segment_tracks on the device, the four steps in one call: (segments, records, info) of label_segments called with
+    max_segments, flow float32 [nmaps, h, w, 2] taking frame k to k + 1 -> (ids int32 [nmaps, S], tracks int64 [max_tracks, 12],
+    tinfo int64 [4], track_map int32 [nmaps, h, w] or None with track_map=False, which passes NULL).  max_tracks None: a slot
+    for every segment.  The fills as in segment_chain and segment_relabel.  segments.py: segment_tracks_ref."""
+    segments, info, nmaps, h, w = _st_maps(segments, info)
+    flow = _f(flow)
+    assert flow.shape == (nmaps, h, w, 2), flow.shape
+    S = max_segments
+    if max_tracks is None:
+        max_tracks = min(nmaps * S, SEGTRACK_MAX_TRACKS)
+    wb = segment_tracks_work_bytes(nmaps, S)
+    with DeviceCall() as c:
+        check(lib().ofdis_segment_tracks(c.input(segments), c.input(flow), c.input(_st_array(records, np.int64, (nmaps, S, SEG_RECORD_FIELDS))),
+                                         c.input(info), nmaps, w, h, S, min_share, max_tracks,
+                                         _st_output(c, (nmaps, S), np.int32, ids_fill),
+                                         _st_output(c, (max_tracks, SEGTRACK_FIELDS), np.int64, tracks_fill),
+                                         c.output((SEGTRACK_INFO_FIELDS,), np.int64),
+                                         _st_output(c, (nmaps, h, w), np.int32, track_map_fill) if track_map else c.output((nmaps, h, w), np.int32, False),
+                                         c.work(wb), wb, None))
         return c.results()
 
 

@@ -505,6 +505,20 @@ size_t segments_work_bytes(int nmaps, int w, int h);
 hipError_t launch_label_segments(const uint8_t* label, const float* flow, int nmaps, int w, int h, unsigned codes, int conn,
                                  int min_area, int max_segments, int* segments, long long* records, long long* info, void* work,
                                  hipStream_t s);
+// object tracks (include/ofdis.h: ofdis_segment_overlap, _link, _chain, _relabel, _tracks; ofdis_segment_tracks.hip): segments
+// [nmaps][h][w] int32, records [nmaps][S][12] int64 and info [nmaps][4] int64 of launch_label_segments, flow [nmaps][h][w][2]
+// -> overlap [nmaps - 1][S][S] int32 (two launches: clear, accumulate), link [nmaps - 1][S] int32, ids [nmaps][S] int32, tracks
+// [max_tracks][12] and tinfo [4] int64 (one workgroup), track_map [nmaps][h][w] int32.  One map: overlap and link launch nothing.
+// segment_tracks_work_bytes: overlap and link, rounded up to 8 bytes, at least 8
+size_t segment_tracks_work_bytes(int nmaps, int max_segments);
+hipError_t launch_segment_overlap(const int* segments, const float* flow, const long long* info, int nmaps, int w, int h,
+                                  int max_segments, int* overlap, hipStream_t s);
+hipError_t launch_segment_link(const int* overlap, const long long* records, const long long* info, int nmaps, int max_segments,
+                               int min_share, int* link, hipStream_t s);
+hipError_t launch_segment_chain(const int* link, const long long* records, const long long* info, int nmaps, int max_segments,
+                                int max_tracks, int* ids, long long* tracks, long long* tinfo, hipStream_t s);
+hipError_t launch_segment_relabel(const int* segments, const int* ids, const long long* info, int nmaps, int w, int h,
+                                  int max_segments, int* track_map, hipStream_t s);
 // video stabilisation (include/ofdis.h: ofdis_camera_path, ofdis_warp_frames; ofdis_stabilize.hip).  The window travels in
 // the launch, as InterpTimes does: w[0 .. radius], the rest zero
 struct StabWindow {

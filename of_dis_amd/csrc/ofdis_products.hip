@@ -1,6 +1,6 @@
 // ofdis_products.hip -- what is made from a context's flows, and the same steps on caller-supplied arrays: the full-resolution
 // finish and its encodings, forward-backward and left-right checks, interpolation, point and dense trajectories, their selection, descriptors,
-// their bag-of-features encoding and the training of its codebook, the temporal filters, global motion, the segments of its label maps and stabilisation.
+// their bag-of-features encoding and the training of its codebook, the temporal filters, global motion, the segments of its label maps, their tracks and stabilisation.
 // Every entry point validates its arguments, joins the pass (finish_begin) and launches; the checks they share are stated once, below.  Reads no environment.
 #include <cfloat>
 #include <cmath>
@@ -782,6 +782,110 @@ int ofdis_label_segments(const uint8_t* label, const float* flow, int nmaps, int
                                (hipStream_t)stream));
   return OFDIS_OK;
 }
+
+// ------------------------------------------------------------------------------------ object tracks (ofdis_segment_tracks.hip)
+// The limits of the section "Object tracks" of include/ofdis.h, which states them in prose
+static const int kSegTrackMaxSegments = 1024, kSegTrackMaxMaps = 65536, kSegTrackMaxTracks = 1 << 24;
+
+// the checks the five calls share: the clip (nmaps, max_segments) and, for the calls that read pixels, the frame
+static int segtrack_clip_check(int nmaps, int max_segments) {
+  if (nmaps < 1 || nmaps > kSegTrackMaxMaps) return fail(OFDIS_ERR_INVALID, "nmaps outside 1..65536");
+  if (max_segments < 1 || max_segments > kSegTrackMaxSegments) return fail(OFDIS_ERR_INVALID, "max_segments outside 1..1024");
+  return OFDIS_OK;
+}
+static int segtrack_frame_check(int nmaps, int width, int height) {
+  if (int rc = sizes_check(nmaps, width, height)) return rc;
+  return gm_sizes_ok(nmaps, width, height) ? OFDIS_OK : fail(OFDIS_ERR_INVALID, kGmSizes);
+}
+static int segtrack_share_check(int min_share) {
+  return min_share >= 0 && min_share <= 100 ? OFDIS_OK : fail(OFDIS_ERR_INVALID, "min_share outside 0..100");
+}
+static int segtrack_tracks_check(int max_tracks) {
+  return max_tracks >= 1 && max_tracks <= kSegTrackMaxTracks ? OFDIS_OK : fail(OFDIS_ERR_INVALID, "max_tracks outside 1..16777216");
+}
+#define SEGTRACK_NEED(p) \
+  if (!(p)) return fail(OFDIS_ERR_INVALID, #p " is NULL")
+
+size_t ofdis_segment_tracks_work_bytes(int nmaps, int max_segments) {
+  const bool ok = nmaps >= 1 && nmaps <= kSegTrackMaxMaps && max_segments >= 1 && max_segments <= kSegTrackMaxSegments;
+  return ok ? segment_tracks_work_bytes(nmaps, max_segments) : 0;
+}
+
+int ofdis_segment_overlap(const int* segments, const float* flow, const long long* info, int nmaps, int width, int height,
+                          int max_segments, int* overlap, void* stream) {
+  SEGTRACK_NEED(segments);
+  SEGTRACK_NEED(flow);
+  SEGTRACK_NEED(info);
+  SEGTRACK_NEED(overlap);
+  if (int rc = segtrack_clip_check(nmaps, max_segments)) return rc;
+  if (int rc = segtrack_frame_check(nmaps, width, height)) return rc;
+  HIPCHK(launch_segment_overlap(segments, flow, info, nmaps, width, height, max_segments, overlap, (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+int ofdis_segment_link(const int* overlap, const long long* records, const long long* info, int nmaps, int max_segments,
+                       int min_share, int* link, void* stream) {
+  SEGTRACK_NEED(overlap);
+  SEGTRACK_NEED(records);
+  SEGTRACK_NEED(info);
+  SEGTRACK_NEED(link);
+  if (int rc = segtrack_clip_check(nmaps, max_segments)) return rc;
+  if (int rc = segtrack_share_check(min_share)) return rc;
+  HIPCHK(launch_segment_link(overlap, records, info, nmaps, max_segments, min_share, link, (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+int ofdis_segment_chain(const int* link, const long long* records, const long long* info, int nmaps, int max_segments,
+                        int max_tracks, int* ids, long long* tracks, long long* tinfo, void* stream) {
+  SEGTRACK_NEED(link);
+  SEGTRACK_NEED(records);
+  SEGTRACK_NEED(info);
+  SEGTRACK_NEED(ids);
+  SEGTRACK_NEED(tracks);
+  SEGTRACK_NEED(tinfo);
+  if (int rc = segtrack_clip_check(nmaps, max_segments)) return rc;
+  if (int rc = segtrack_tracks_check(max_tracks)) return rc;
+  HIPCHK(launch_segment_chain(link, records, info, nmaps, max_segments, max_tracks, ids, tracks, tinfo, (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+int ofdis_segment_relabel(const int* segments, const int* ids, const long long* info, int nmaps, int width, int height,
+                          int max_segments, int* track_map, void* stream) {
+  SEGTRACK_NEED(segments);
+  SEGTRACK_NEED(ids);
+  SEGTRACK_NEED(info);
+  SEGTRACK_NEED(track_map);
+  if (int rc = segtrack_clip_check(nmaps, max_segments)) return rc;
+  if (int rc = segtrack_frame_check(nmaps, width, height)) return rc;
+  HIPCHK(launch_segment_relabel(segments, ids, info, nmaps, width, height, max_segments, track_map, (hipStream_t)stream));
+  return OFDIS_OK;
+}
+
+int ofdis_segment_tracks(const int* segments, const float* flow, const long long* records, const long long* info, int nmaps,
+                         int width, int height, int max_segments, int min_share, int max_tracks, int* ids, long long* tracks,
+                         long long* tinfo, int* track_map, void* work, size_t work_bytes, void* stream) {
+  SEGTRACK_NEED(segments);
+  SEGTRACK_NEED(flow);
+  SEGTRACK_NEED(records);
+  SEGTRACK_NEED(info);
+  SEGTRACK_NEED(ids);
+  SEGTRACK_NEED(tracks);
+  SEGTRACK_NEED(tinfo);
+  if (int rc = segtrack_clip_check(nmaps, max_segments)) return rc;
+  if (int rc = segtrack_frame_check(nmaps, width, height)) return rc;
+  if (int rc = segtrack_share_check(min_share)) return rc;
+  if (int rc = segtrack_tracks_check(max_tracks)) return rc;
+  if (int rc = work_check(work, work_bytes, segment_tracks_work_bytes(nmaps, max_segments), "ofdis_segment_tracks_work_bytes")) return rc;
+  int* overlap = (int*)work;   // [nmaps - 1][S][S], then link [nmaps - 1][S]
+  int* link = overlap + (size_t)(nmaps - 1) * max_segments * max_segments;
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(launch_segment_overlap(segments, flow, info, nmaps, width, height, max_segments, overlap, s));
+  HIPCHK(launch_segment_link(overlap, records, info, nmaps, max_segments, min_share, link, s));
+  HIPCHK(launch_segment_chain(link, records, info, nmaps, max_segments, max_tracks, ids, tracks, tinfo, s));
+  if (track_map) HIPCHK(launch_segment_relabel(segments, ids, info, nmaps, width, height, max_segments, track_map, s));
+  return OFDIS_OK;
+}
+#undef SEGTRACK_NEED
 
 // ------------------------------------------------------------------------------------ video stabilisation (ofdis_stabilize.hip)
 static_assert(sizeof(StabWindow::w) / sizeof(double) == OFDIS_STAB_MAX_RADIUS + 1, "StabWindow holds OFDIS_STAB_MAX_RADIUS + 1 weights");
